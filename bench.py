@@ -1,22 +1,28 @@
 """bench.py -- headline benchmark: trainer->training_step() throughput (samples/s) of HashGrid + 64-wide FullyFusedMLP at
 batch 256k (BASELINE.json `metric`, configs[2] = SURVEY C3a), one replica per GPU.
 
-    python bench.py --gpus N --steps K --warmup W [--workload c3a|c3b|c2|c5]
+    python bench.py --gpus N --steps K --warmup W [--workload c3a|c3b|c2|c5|c4] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line: `value` (samples/s), `ms_per_step` and the `roofline` of the
+profiled timed steps.  `--full` adds what takes runs of its own: the no-settle repeat, the MLP kernel at batch 2^21, the other BASELINE
+configurations (`other_configs`), the CPU oracle (`cpu_baseline`) and, for N > 1, the sharded inference (`c4_sharded_inference`).
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (float32 / float64; seeded samples of the larger arrays):
+same arguments, same inputs, so two builds can be compared output for output.
 
 For N > 1 the driver launches one process per GPU with torch.distributed.run; training does not shard in the reference
 ("replicas only"), so every rank trains its own replica on its own synthetic batch -- weak scaling, no
 data-path collective; the only collectives are the timing barrier and the MAX over ranks.
 
 `python bench.py --gpus N` with N > 1 and no RANK in the environment starts the N ranks itself (a child torch.distributed.run,
-before this process touches the GPU).  For N > 1 the line also carries `c4_sharded_inference`: BASELINE config 4, the one path
+before this process touches the GPU).  For N > 1 with `--full` the line also carries `c4_sharded_inference`: BASELINE config 4, the one path
 of the reference that shards (rows over the GPUs, one RCCL all-gather of the half outputs per step).
 
 The JSON line carries `roofline` for the step's MFMA kernel, the fused MLP training kernel (BASELINE metric: "% fp16-MFMA
 peak"; SURVEY 8d: achieved = samples/s of the kernel x 38 016 FLOP), timed live with HIP events on the launch stream inside
 the timed region on every 8th step (tcnn_trainer_profile_next_step), with the other pieces of the step beside it
 (`roofline.pieces`: encoding forward, encoding backward, optimizer against the HBM peak; `hbm_floor_frac`: the step's
-compulsory HBM bytes over the whole step time), and `cpu_baseline`: the CPU oracle (a port of the reference algorithm, the
-reference has no CPU path) timed on a bounded sample on rank 0.
+compulsory HBM bytes over the whole step time), and with `--full` `cpu_baseline`: the CPU oracle (a port of the reference algorithm,
+the reference has no CPU path) timed on a bounded sample on rank 0.
 """
 import argparse
 import json
@@ -121,7 +127,7 @@ def c4_measure(steps, warmup, world, setup=None):
         elapsed = float(el.item())
     b, e = shard_rows(C4_ROWS, world, 0)
     stream_ms = e0.elapsed_time(e1) / max(steps, 1)  # this rank's stream: its shard's kernels + the all-gather
-    res = {"elapsed": elapsed, "rows_per_gpu": e - b, "stream_ms_per_step": stream_ms, "checksum": float(y.double().sum().item())}
+    res = {"elapsed": elapsed, "rows_per_gpu": e - b, "stream_ms_per_step": stream_ms, "checksum": float(y.double().sum().item()), "output": y}
     # the last timed step taken apart (this rank): the infer_fn calls, and what was left of the gathers when the kernels were done
     if timing.get("kernel_events"):
         res["kernel_ms"] = sum(k0.elapsed_time(k1) for k0, k1 in timing["kernel_events"])
@@ -159,6 +165,8 @@ def run_c4(args):
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         dist.init_process_group(backend=args.backend, device_id=torch.device("cuda", local_rank) if args.backend == "nccl" else None)
     m = c4_measure(args.steps, args.warmup, world)
+    if rank == 0 and args.dump_outputs:  # the gathered half outputs of the last timed step: every row on every rank
+        dump_outputs(args.dump_outputs, {"output": sample_rows(m["output"][:, :C4_OUT], DUMP_BYTES // (4 * C4_OUT))})
     if rank == 0:
         achieved = m["rows_per_gpu"] * C4_FLOP_PER_ROW / (m["stream_ms_per_step"] * 1e-3) / 1e12
         print(json.dumps({
@@ -248,6 +256,30 @@ METRIC = {
 
 POOL = 4  # pre-generated batches, visited in turn: the step is timed on fresh samples, not on one batch its scatter plan was cut for
 
+DUMP_BYTES = 16 << 20  # --dump-outputs: at most this many bytes of float32 rows per output (a seeded sample of the rows beyond that)
+DUMP_PARAMS = 1 << 20  # --dump-outputs: at most this many parameters (a seeded sample beyond that)
+
+
+def sample_rows(t, limit, seed=0):
+    """Rows of a device tensor at a fixed seeded set of at most `limit` row indices (every row if there are no more), as float32 numpy."""
+    import numpy as np
+    import torch
+
+    n = t.shape[0]
+    if n > limit:
+        idx = np.unique(np.random.default_rng(seed).integers(0, n, size=limit))
+        t = t[torch.from_numpy(idx).to(t.device)]
+    return t.float().cpu().numpy()
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
 
 SETTLE_MS = 100.0  # --settle-ms
 
@@ -275,12 +307,13 @@ def settle_device(torch, ms):
     del a, b
 
 
-def measure_training(tcnn, torch, name, batch, steps, warmup, seed=42, barrier=None, settle_ms=None):
+def measure_training(tcnn, torch, name, batch, steps, warmup, seed=42, barrier=None, settle_ms=None, dump=False):
     """`steps` timed trainer->training_step(input, target) calls (trainer.h:163-190) of workload `name` after `warmup` untimed ones.
     Every 8th timed step (steps 4, 12, ...; every 4th -- 2, 6, ... -- in runs of at most 32 steps, so that the driver's `--steps 20` averages
     five launches, not two) also records HIP events on the launch stream around its pieces (tcnn_trainer_profile_next_step: events without
     the system-scope fence; the eight records of such a step cost it ~10 us of dispatch bubbles, hence not on every step).
-    settle_ms: None = the run's --settle-ms."""
+    settle_ms: None = the run's --settle-ms.  dump: also return `outputs`, what the last timed step handed its caller (the output columns
+    and the loss) and the parameters it left, copied after the timed region."""
     n_in, n_out, _, cfg = WORKLOADS[name]
     gen = torch.Generator(device="cuda")
     gen.manual_seed(seed)
@@ -313,8 +346,15 @@ def measure_training(tcnn, torch, name, batch, steps, warmup, seed=42, barrier=N
     pieces, n_profiled = tr.profile_collect()
     n_params = tr.n_params
     wide = tr.scatter_wide_fallbacks()  # grid gradient tasks that could not prove their packed 32-bit sums (they then sum in 64 bits: slower, same bits)
+    outputs = None
+    if dump:
+        import numpy as np
+
+        outputs = {"output": sample_rows(ctx.output()[:, :n_out], max(DUMP_BYTES // (4 * n_out), 1)), "loss": np.array([loss1], dtype=np.float64),
+                   "params": sample_rows(tr.params_full_precision(), DUMP_PARAMS, seed=1)}
     del tr, xs, ts, ctx
-    return {"elapsed": elapsed, "n_params": n_params, "pieces": pieces, "n_profiled": n_profiled, "loss0": loss0, "loss1": loss1, "scatter_wide_tasks": wide}
+    return {"elapsed": elapsed, "n_params": n_params, "pieces": pieces, "n_profiled": n_profiled, "loss0": loss0, "loss1": loss1, "scatter_wide_tasks": wide,
+            "outputs": outputs}
 
 
 def mlp_param_count(name):
@@ -412,8 +452,11 @@ def main():
     ap.add_argument("--settle-ms", type=float, default=SETTLE_MS, help="milliseconds of unrelated device work (memory-bound fp32 elementwise passes) behind the first warmup step, so that an idle device's clocks have settled (settle_device); 0: none")
     ap.add_argument("--workload", default="c3a", choices=sorted(WORKLOADS) + ["c4"])
     ap.add_argument("--batch", type=int, default=0, help="override the workload's batch size")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the short runs of the other BASELINE configurations behind the headline")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: the no-settle repeat, the MLP kernel at batch 2^21, the other "
+                    "BASELINE configurations, the CPU baseline and (N > 1) the sharded inference")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the last timed step returned as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the short runs of the other BASELINE configurations behind the headline")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend of the timing collectives (tests: gloo)")
     ap.add_argument("--device", default="cuda", choices=["cuda", "none"], help="none: launcher / collective plumbing only, no GPU work (CPU tests)")
     args = ap.parse_args()
@@ -452,7 +495,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    m = measure_training(tcnn, torch, args.workload, batch, args.steps, args.warmup, seed=42 + rank, barrier=barrier)
+    m = measure_training(tcnn, torch, args.workload, batch, args.steps, args.warmup, seed=42 + rank, barrier=barrier, dump=bool(args.dump_outputs) and rank == 0)
     elapsed, n_params, pieces, n_profiled, loss0, loss1 = m["elapsed"], m["n_params"], m["pieces"], m["n_profiled"], m["loss0"], m["loss1"]
     scatter_wide_tasks = m.get("scatter_wide_tasks")
     if world > 1:
@@ -460,8 +503,11 @@ def main():
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
         elapsed = float(el.item())
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, m["outputs"])
+
     sharded = None
-    if world > 1:  # the path that shards, on the same ranks: rows over the GPUs + one RCCL all-gather per step
+    if world > 1 and args.full:  # the path that shards, on the same ranks: rows over the GPUs + one RCCL all-gather per step
         # allocations first, on every rank, and a vote: a rank that cannot set up (out of memory) must not leave the others waiting
         # in the measurement's collectives -- either all ranks measure or none does, and the headline line is printed either way
         setup, err = None, None
@@ -486,7 +532,7 @@ def main():
     # The same run without the settle pass, for comparison with rounds 1-3 (whose lines had none): the device idles for two seconds -- as
     # it does in front of a fresh process's first step -- then W warmup and K timed steps (at most 20) of a new trainer, nothing in between.
     no_settle_ms = None
-    if world == 1 and SETTLE_MS > 0 and not args.batch:
+    if world == 1 and SETTLE_MS > 0 and not args.batch and args.full:
         try:
             k_ns, w_ns = min(args.steps, 20), min(args.warmup, 5)
             torch.cuda.synchronize()
@@ -510,7 +556,7 @@ def main():
         bound = "hbm" if (hbm_floor_ms or 0.0) > mfma_floor_ms else "mfma"
         # the same kernel at batch 2^21: the ~6 us a launch costs whatever its size (fill, final reduction, write-back) are 1/8 of what they are at 2^18
         frac_2p21 = None
-        if world == 1 and args.workload == "c3a" and not args.batch and not args.no_other_configs:
+        if world == 1 and args.workload == "c3a" and not args.batch and args.full and not args.no_other_configs:
             try:
                 m21 = measure_training(tcnn, torch, args.workload, 1 << 21, 16, 4)
                 ms21 = m21["pieces"]["mlp_kernel"]
@@ -568,9 +614,9 @@ def main():
         }
         if sharded is not None:
             result["c4_sharded_inference"] = sharded
-        if world == 1 and args.workload == "c3a" and not args.batch and not args.no_other_configs:
+        if world == 1 and args.workload == "c3a" and not args.batch and args.full and not args.no_other_configs:
             result["other_configs"] = other_configs(tcnn, torch)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(args.workload)
         print(json.dumps(result), flush=True)
 

@@ -1,8 +1,8 @@
 """CPU tests of the harness's JPEG reader (samples/jpeg_decoder.h; the reference loads its sample images through the vendored
 stb_image, dependencies/stbi/stbi_wrapper.cpp:37-44).  JPEG decoders may differ by the rounding of their inverse DCT (+-1 per
 sample) and, for subsampled chroma, by the interpolation filter; the decoder is pinned against PIL (libjpeg) within those bounds
-on baseline and progressive files, grayscale and colour, with and without restart markers -- and on the reference's
-data/images/albert.jpg (progressive grayscale, BASELINE config 3) where the reference tree is present."""
+on baseline and progressive files, grayscale and colour, with and without restart markers -- and on a crop of the reference's
+data/images/albert.jpg (progressive grayscale, BASELINE config 3; a public-domain photograph), tests/golden/albert_crop.jpg."""
 import io
 import os
 import shutil
@@ -14,7 +14,7 @@ import pytest
 from conftest import ROOT
 
 PIL = pytest.importorskip("PIL.Image")
-ALBERT = "/root/reference/data/images/albert.jpg"
+ALBERT = os.path.join(ROOT, "tests", "golden", "albert_crop.jpg")
 
 
 @pytest.fixture(scope="module")
@@ -93,11 +93,12 @@ def test_errors_are_reported(tool, tmp_path):
     assert r.returncode in (0, 1)
 
 
-@pytest.mark.skipif(not os.path.exists(ALBERT), reason="reference tree not present (GPU box)")
 def test_reference_sample_image(tool, tmp_path):
-    """data/images/albert.jpg, the image BASELINE config 3 trains on: 3250 x 4333, 8-bit grayscale, progressive."""
+    """data/images/albert.jpg, the image BASELINE config 3 trains on (3250 x 4333, 8-bit grayscale, progressive), as a 1026 x 1285
+    crop re-encoded with the original's quantisation table, scan script and ICC segment; neither side is a multiple of 8."""
+    assert open(ALBERT, "rb").read().count(b"\xff\xda") == 6  # the original's six progressive scans
     want = np.asarray(PIL.open(ALBERT).convert("L"), dtype=np.int32)
     got = _decode(tool, ALBERT, tmp_path).astype(np.int32)[:, :, 0]
-    assert got.shape == want.shape == (4333, 3250)
+    assert got.shape == want.shape == (1285, 1026)
     diff = np.abs(got - want)
     assert diff.max() <= 2 and diff.mean() <= 0.5, (diff.max(), diff.mean())
