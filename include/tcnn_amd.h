@@ -204,6 +204,24 @@ size_t tcnn_trainer_optimizer_prologue_steps(tcnn_trainer_t t);
  * which kernel produced the gradients they compare with the oracle (replaces kernel_grid_backward, grid.h:215-320). */
 size_t tcnn_trainer_list_scatters(tcnn_trainer_t t);
 size_t tcnn_module_list_scatters(tcnn_module_t m); /* the same count for a module's grid encoding(s) (callers with their own network) */
+
+/* max_level of the grid encodings (GridEncoding::set_max_level / max_level / set_max_level_gpu / max_level_gpu, grid_interface.h:101-123):
+ * a fraction of the levels, 1000 (the default) keeps every one.  With m = max_level * n_levels, level l produces zeros (in its features and
+ * in the input gradients) when l >= m + 1e-3f, and receives no parameter gradient when l > m + 1e-3f (grid.h:67-90, :237-245, :377-384,
+ * :482-490; fp32 arithmetic, NaN keeps every level on).  A skipped level's gradients are zero under Overwrite and untouched under
+ * Accumulate; the optimizer still steps those parameters.  Every grid nested in the module (Composite) takes the setting, which is read
+ * when each call runs and is neither part of the hyperparameters nor of snapshots.
+ * per_sample: device memory the caller owns, one float per row, read instead of the scalar (NULL: the scalar again).  It must hold at
+ * least n_elements floats for EVERY call made on the module / trainer while it is set, and stay valid until those calls have run.
+ * A module or trainer without a grid encoding: TCNN_ERROR, or NaN from the getters, and tcnn_last_error() names the model; a getter that
+ * succeeds leaves tcnn_last_error() empty (which tells a NaN that was set from an error). */
+int   tcnn_module_set_max_level(tcnn_module_t m, float max_level);
+float tcnn_module_max_level(tcnn_module_t m);
+int   tcnn_module_set_max_level_gpu(tcnn_module_t m, const float* per_sample);
+/* the trainer's model: training_step, forward / backward and both inference calls */
+int   tcnn_trainer_set_max_level(tcnn_trainer_t t, float max_level);
+int   tcnn_trainer_set_max_level_gpu(tcnn_trainer_t t, const float* per_sample);
+float tcnn_trainer_max_level(tcnn_trainer_t t);
 /* Introspection: 1 when this context owns the network's weight-gradient slabs because their reduction was left to the optimizer's
  * launch (tcnn_trainer_optimizer_prologue_steps): they must outlive training_step()'s own scope, until that launch is enqueued. */
 int tcnn_train_ctx_keeps_weight_gradient_slabs(tcnn_trainer_t t, tcnn_train_ctx_t ctx);

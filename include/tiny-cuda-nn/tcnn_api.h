@@ -199,11 +199,36 @@ public:
 	const json& encoding_config() const { return m_encoding; }
 	const json& network_config() const { return m_network; }
 
+	// max_level of the grid encoding (GridEncoding, grid_interface.h:101-123; tcnn_amd.h states the rule): a fraction of the levels,
+	// 1000 keeps every one.  A value set before a Trainer binds the network is held here and applied at binding.
+	// set_max_level_gpu: one float per row in device memory (the caller's; nullptr: the scalar again), at least as many as the rows of
+	// every call made while it is set.
+	float max_level() const { return m_trainer ? tcnn_trainer_max_level(m_trainer) : m_max_level; }
+	void set_max_level(float value) {
+		if (m_trainer) detail::check(tcnn_trainer_set_max_level(m_trainer, value));
+		m_max_level = value;
+	}
+	float* max_level_gpu() const { return m_max_level_gpu; }
+	void set_max_level_gpu(float* per_sample) {
+		if (m_trainer) detail::check(tcnn_trainer_set_max_level_gpu(m_trainer, per_sample));
+		m_max_level_gpu = per_sample;
+	}
+
 private:
 	template <typename A, typename B, typename C> friend class Trainer;
+	// at binding: a setting made before reaches the trainer (nothing is called while nothing was set)
+	void bind(tcnn_trainer_t trainer) {
+		m_trainer = trainer;
+		if (!(m_max_level == 1000.f) || m_max_level_gpu) {
+			detail::check(tcnn_trainer_set_max_level(trainer, m_max_level));
+			detail::check(tcnn_trainer_set_max_level_gpu(trainer, m_max_level_gpu));
+		}
+	}
 	uint32_t m_n_input_dims, m_n_output_dims;
 	json m_encoding, m_network;
 	tcnn_trainer_t m_trainer = nullptr; // borrowed from the Trainer that bound this network
+	float m_max_level = 1000.f;         // grid_interface.h:118
+	float* m_max_level_gpu = nullptr;
 };
 
 // ---------------------------------------------------------------------------------------------------------------- Trainer
@@ -227,7 +252,13 @@ public:
 		config["optimizer"] = m_optimizer->hyperparams();
 		config["loss"] = m_loss->hyperparams();
 		detail::check(tcnn_create_from_config_seeded(m_model->input_width(), m_model->output_width(), config.dump().c_str(), seed, &m_handle));
-		m_model->m_trainer = m_handle;
+		try {
+			m_model->bind(m_handle);
+		} catch (...) {
+			m_model->m_trainer = nullptr;
+			tcnn_trainer_destroy(m_handle);
+			throw;
+		}
 	}
 	Trainer(const Trainer&) = delete;
 	Trainer& operator=(const Trainer&) = delete;

@@ -231,6 +231,35 @@ uint32_t tcnn_module_n_input_dims(tcnn_module_t m) { return m->model->input_widt
 uint32_t tcnn_module_n_output_dims(tcnn_module_t m) { return m->model->padded_output_width(); }
 size_t tcnn_module_n_params(tcnn_module_t m) { return m->model->n_params(); }
 size_t tcnn_module_list_scatters(tcnn_module_t m) { return (size_t)m->model->list_scatters(); }
+
+namespace {
+[[noreturn]] void no_grid(Model& model) {
+	throw std::runtime_error{"max_level: " + model.name() + " has no grid encoding (GridEncoding::set_max_level, grid_interface.h:101-123)"};
+}
+} // namespace
+
+int tcnn_module_set_max_level(tcnn_module_t m, float max_level) {
+	return guarded([&] {
+		CHECK_THROW(m && m->model);
+		if (!m->model->set_max_level(max_level)) no_grid(*m->model);
+	});
+}
+int tcnn_module_set_max_level_gpu(tcnn_module_t m, const float* per_sample) {
+	return guarded([&] {
+		CHECK_THROW(m && m->model);
+		if (!m->model->set_max_level_gpu(per_sample)) no_grid(*m->model);
+	});
+}
+float tcnn_module_max_level(tcnn_module_t m) {
+	float v = std::numeric_limits<float>::quiet_NaN();
+	const float* per_sample = nullptr;
+	guarded([&] {
+		CHECK_THROW(m && m->model);
+		if (!m->model->get_max_level(v, per_sample)) no_grid(*m->model);
+		g_last_error.clear();
+	});
+	return v;
+}
 int tcnn_module_param_precision(tcnn_module_t m) { return (int)m->model->precision(); }
 int tcnn_module_output_precision(tcnn_module_t m) { return (int)m->model->precision(); }
 
@@ -360,6 +389,28 @@ size_t tcnn_trainer_scatter_wide_fallbacks(tcnn_trainer_t t) {
 	try { return (size_t)t->trainer->scatter_wide_fallbacks(); } catch (const std::exception& e) { g_last_error = e.what(); return (size_t)-1; }
 }
 size_t tcnn_trainer_list_scatters(tcnn_trainer_t t) { return (size_t)t->trainer->list_scatters(); }
+int tcnn_trainer_set_max_level(tcnn_trainer_t t, float max_level) {
+	return guarded([&] {
+		CHECK_THROW(t && t->trainer);
+		if (!t->trainer->model().set_max_level(max_level)) no_grid(t->trainer->model());
+	});
+}
+int tcnn_trainer_set_max_level_gpu(tcnn_trainer_t t, const float* per_sample) {
+	return guarded([&] {
+		CHECK_THROW(t && t->trainer);
+		if (!t->trainer->model().set_max_level_gpu(per_sample)) no_grid(t->trainer->model());
+	});
+}
+float tcnn_trainer_max_level(tcnn_trainer_t t) {
+	float v = std::numeric_limits<float>::quiet_NaN();
+	const float* per_sample = nullptr;
+	guarded([&] {
+		CHECK_THROW(t && t->trainer);
+		if (!t->trainer->model().get_max_level(v, per_sample)) no_grid(t->trainer->model());
+		g_last_error.clear();
+	});
+	return v;
+}
 int tcnn_train_ctx_keeps_weight_gradient_slabs(tcnn_trainer_t t, tcnn_train_ctx_t ctx) {
 	return (t && ctx && ctx->ctx && ctx->ctx->model_ctx && t->trainer->model().context_keeps_slabs(*ctx->ctx->model_ctx)) ? 1 : 0;
 }

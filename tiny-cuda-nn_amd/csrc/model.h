@@ -283,6 +283,11 @@ public:
 	}
 	virtual Json hyperparams() const = 0;
 	bool fp32() const { return m_fp32; }
+	// max_level of the grid encodings (grid_interface.h:101-123), read at call time.  false: no grid encoding here to take it.
+	// per_sample: n floats in device memory for every call made while it is set (the caller's; nullptr: the scalar applies)
+	virtual bool set_max_level(float max_level) { return false; }
+	virtual bool set_max_level_gpu(const float* per_sample) { return false; }
+	virtual bool get_max_level(float& max_level, const float*& per_sample) const { return false; }
 protected:
 	explicit Encoding(bool fp32) : m_fp32{fp32} {}
 	bool m_fp32;
@@ -435,6 +440,11 @@ public:
 		ArenaBuf mask;
 		if (want_filter) mask = ArenaBuf{stream, (size_t)m_meta.n_levels * n * (GRID_FILTER_MAX_CHUNKS / 64) * sizeof(uint64_t)};
 		grid_forward(stream, m_meta, dev_meta(), m_fp32, n, x, params, out, padded_output_width(), ctx.dy_dx.as<float>(), mask.as<uint64_t>());
+		if (max_level_forward_active()) { // grid.h:67-90: an off level writes zeros into its features and into dy_dx
+			const uint32_t F = m_meta.n_features_per_level, D = m_meta.n_pos_dims;
+			if (out) zero_levels(stream, m_fp32 ? 4 : 2, n, F, padded_output_width(), F, out, false);
+			if (ctx.dy_dx) zero_levels(stream, 4, n, F * D, (uint64_t)m_n_features * D, (uint64_t)F * D, ctx.dy_dx.data(), false);
+		}
 		if (want_filter) {
 			ctx.chunk_mask = ArenaBuf{stream, (size_t)m_meta.n_levels * grid_scatter_max_chunks() * (n / 64) * sizeof(uint64_t)};
 			ctx.n = n;
@@ -506,11 +516,41 @@ public:
 		grid_forward_planes(stream, m_meta, dev_meta(), plan.dev_work.as<uint32_t>(), plan.max_items, plan.blocks_per_xcd, n, x, params, out_planes, ctx.chunk_mask.as<uint64_t>(), prep_job,
 		                    want_lists ? &ctx.hit_lists : nullptr);
 		if (m_n_to_pad) HIP_CHECK_THROW(hipMemsetAsync((uint16_t*)out_planes + (size_t)n * m_n_features, 0, (size_t)n * m_n_to_pad * sizeof(uint16_t), stream)); // grid.h:749-759: the grid pads with zeros
+		if (max_level_forward_active()) { // grid.h:67-90 (hit lists and chunk masks stay those of every level: the gradient side decides for itself)
+			const uint32_t F = m_meta.n_features_per_level;
+			zero_levels(stream, 2, n, F, F, (uint64_t)n * F, out_planes, false);
+		}
 		return ctx;
 	}
 
 	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes) override {
 		if ((!dL_dx && mode == GradientMode::Ignore) || n == 0) return;
+		const uint32_t l_bwd = m_max_level_gpu ? m_meta.n_levels : levels_on(true); // (a per-sample array overrides the scalar)
+		if (!m_max_level_gpu && l_bwd == m_meta.n_levels) return backward_all_levels(stream, ctx, n, x, dL_dy, dL_dx, params, grads, mode, dy_planes);
+		if (m_max_level_gpu) { // per sample: dL/dy of the skipped (sample, level) pairs zeroed -- the exact sums add nothing for a zero product
+			CHECK_THROW(!ctx.dy_records); // (scatter_records_usable() is false while a per-sample array is set)
+			const uint32_t F = m_meta.n_features_per_level;
+			const size_t elem = dy_planes ? 2 : (m_fp32 ? 4 : 2);
+			ArenaBuf masked{stream, (size_t)n * padded_output_width() * elem};
+			if (dy_planes) zero_levels(stream, 2, n, F, F, (uint64_t)n * F, masked.data(), true, dL_dy);
+			else zero_levels(stream, elem, n, F, padded_output_width(), F, masked.data(), true, dL_dy);
+			return backward_all_levels(stream, ctx, n, x, masked.data(), dL_dx, params, grads, mode, dy_planes);
+		}
+		// scalar (grid.h:237-245): the optimizer's offers to ride on this pass are declined -- the off levels' gradients are settled below,
+		// after the kernels, and the optimizer's own launch sees every parameter
+		const AdamInFlush* adam = ctx.adam;
+		AdamPrologue* prologue = ctx.prologue;
+		ctx.adam = nullptr;
+		ctx.prologue = nullptr;
+		GradientTail tail{*this, stream, grads, mode, l_bwd};
+		backward_all_levels(stream, ctx, n, x, dL_dy, dL_dx, params, grads, mode, dy_planes);
+		tail.settle();
+		ctx.adam_done.clear();
+		ctx.adam = adam;
+		ctx.prologue = prologue;
+	}
+
+	void backward_all_levels(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes) {
 		const size_t elem = m_fp32 ? 4 : 2;
 		if (mode != GradientMode::Ignore) {
 			CHECK_THROW(grads != nullptr);
@@ -608,6 +648,25 @@ public:
 	void backward_backward_input(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, MatView dL_ddLdx, const void* dL_dy, void* dL_ddLdy,
 	                             MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode) override {
 		if ((!dL_ddLdy && mode == GradientMode::Ignore && !dL_dx) || padded_output_width() == 0 || n == 0) return;
+		const uint32_t l_bwd = m_max_level_gpu ? m_meta.n_levels : levels_on(true);
+		if (!m_max_level_gpu && l_bwd == m_meta.n_levels) return backward_backward_input_all_levels(stream, ctx, n, x, dL_ddLdx, dL_dy, dL_ddLdy, dL_dx, params, grads, mode);
+		// grid.h:377-384, :482-490: both kernels skip the (sample, level) pairs the gradient rule puts off -- a zero dL/dy there gives them
+		// nothing (dL_ddLdy reads dy_dx, which the forward pass zeroed by the forward rule, :626-650)
+		ArenaBuf masked;
+		if (dL_dy) {
+			const uint32_t F = m_meta.n_features_per_level;
+			const size_t elem = m_fp32 ? 4 : 2;
+			masked = ArenaBuf{stream, (size_t)n * padded_output_width() * elem};
+			zero_levels(stream, elem, n, F, padded_output_width(), F, masked.data(), true, dL_dy);
+			dL_dy = masked.data();
+		}
+		GradientTail tail{*this, stream, grads, mode, l_bwd};
+		backward_backward_input_all_levels(stream, ctx, n, x, dL_ddLdx, dL_dy, dL_ddLdy, dL_dx, params, grads, mode);
+		tail.settle();
+	}
+
+	void backward_backward_input_all_levels(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, MatView dL_ddLdx, const void* dL_dy, void* dL_ddLdy,
+	                                        MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode) {
 		const size_t elem = m_fp32 ? 4 : 2;
 		if (dL_ddLdy) CHECK_THROW(ctx.dy_dx); // needs the forward pass to have run with prepare_input_gradients
 		const float* dy_dx = ctx.dy_dx.as<float>();
@@ -638,7 +697,7 @@ public:
 	// The MLP kernel writes {coordinates, gradient} records and the scatter does one gather per hit instead of two: measured on
 	// C3a the scatter gains 12 us and the MLP kernel loses 6 us (4x the dX bytes).  TCNN_AMD_SCATTER_RECORDS=0 turns it off.
 	bool scatter_records_usable(MatView x) const override {
-		return switches().scatter_records && lds_scatter_usable() && !m_any_binned && grid_scatter_records_supported(m_meta) && x.stride_dim == 1 && x.stride_sample == m_meta.n_pos_dims;
+		return !m_max_level_gpu && switches().scatter_records && lds_scatter_usable() && !m_any_binned && grid_scatter_records_supported(m_meta) && x.stride_dim == 1 && x.stride_sample == m_meta.n_pos_dims;
 	}
 
 	uint32_t scatter_record_planes() const override { return grid_scatter_record_planes(m_meta); }
@@ -790,6 +849,63 @@ public:
 
 	uint64_t list_scatters() const override { return m_list_scatters; }
 
+	// grid_interface.h:101-123 (not part of the hyperparameters or snapshots, as there)
+	bool set_max_level(float max_level) override { m_max_level = max_level; return true; }
+	bool set_max_level_gpu(const float* per_sample) override { m_max_level_gpu = per_sample; return true; }
+	bool get_max_level(float& max_level, const float*& per_sample) const override {
+		max_level = m_max_level;
+		per_sample = m_max_level_gpu;
+		return true;
+	}
+
+	// The scalar cut-off's levels that produce output (gradient_rule false) or receive gradients (true); the off levels are a suffix.
+	// The reference's fp32 expressions (grid.h:67-75, :237-245): m = (max_level * num_grid_features) / F, then l >= m + 1e-3f / l > m + 1e-3f.
+	uint32_t levels_on(bool gradient_rule) const {
+		const volatile float m = (m_max_level * (float)m_n_features) / (float)m_meta.n_features_per_level;
+		const volatile float threshold = m + 1e-3f;
+		for (uint32_t l = 0; l < m_meta.n_levels; ++l) {
+			if (gradient_rule ? (float)l > threshold : (float)l >= threshold) return l;
+		}
+		return m_meta.n_levels;
+	}
+	bool max_level_forward_active() const { return m_max_level_gpu || levels_on(false) < m_meta.n_levels; }
+
+private:
+	// zeroes the off (sample, level) pairs of a forward output / dy_dx (gradient_rule false) or of a dL/dy copy (true), laid out as
+	// data + i * sample_stride + l * level_stride, `width` elements per pair
+	// src: a masked copy of src into data instead (the levels' elements only: padding features are left unwritten)
+	void zero_levels(hipStream_t stream, size_t elem_bytes, uint32_t n, uint32_t width, uint64_t sample_stride, uint64_t level_stride, void* data, bool gradient_rule,
+	                 const void* src = nullptr) const {
+		const uint32_t level0 = m_max_level_gpu ? 0u : levels_on(gradient_rule);
+		grid_zero_levels(stream, elem_bytes, n, m_meta.n_levels, level0, width, sample_stride, level_stride, data, src, m_max_level_gpu, m_n_features, m_meta.n_features_per_level, gradient_rule);
+	}
+	// The scalar cut-off skips the levels from l_bwd on: their parameter gradients, one contiguous tail, end up zero (Overwrite, grid.h:857)
+	// or untouched (Accumulate, signed zeros included) whatever the gradient kernels wrote there.
+	struct GradientTail {
+		hipStream_t stream;
+		char* tail = nullptr;
+		size_t bytes = 0;
+		bool accumulate = false;
+		ArenaBuf saved;
+		GradientTail(const GridEncoding& e, hipStream_t s, void* grads, GradientMode mode, uint32_t l_bwd) : stream{s} {
+			if (!grads || mode == GradientMode::Ignore || l_bwd >= e.m_meta.n_levels) return;
+			const size_t elem = e.m_fp32 ? 4 : 2, first = (size_t)e.m_meta.levels[l_bwd].offset * e.m_meta.n_features_per_level;
+			tail = (char*)grads + first * elem;
+			bytes = (e.n_params() - first) * elem;
+			accumulate = mode == GradientMode::Accumulate;
+			if (accumulate) {
+				saved = ArenaBuf{stream, bytes};
+				HIP_CHECK_THROW(hipMemcpyAsync(saved.data(), tail, bytes, hipMemcpyDeviceToDevice, stream));
+			}
+		}
+		void settle() {
+			if (!tail) return;
+			if (accumulate) HIP_CHECK_THROW(hipMemcpyAsync(tail, saved.data(), bytes, hipMemcpyDeviceToDevice, stream));
+			else HIP_CHECK_THROW(hipMemsetAsync(tail, 0, bytes, stream));
+		}
+	};
+
+public:
 	Json hyperparams() const override { // grid.h:1098-1115
 		static const char* types[] = {"Hash", "Dense", "Tiled"};
 		static const char* interps[] = {"Nearest", "Linear", "Smoothstep"};
@@ -817,6 +933,8 @@ private:
 	bool m_scatter_levels_ok = true;
 	bool m_any_binned = false;
 	uint64_t m_list_scatters = 0;
+	float m_max_level = 1000.f;               // grid_interface.h:118: every level on
+	const float* m_max_level_gpu = nullptr;   // grid_interface.h:119
 	std::vector<uint32_t> m_resolutions;
 	uint32_t m_n_features, m_log2_hashmap_size, m_base_resolution, m_n_entries;
 	float m_per_level_scale;
@@ -1271,6 +1389,23 @@ public:
 		for (const auto& e : m_nested) total += e->list_scatters();
 		return total;
 	}
+	// every grid nested here takes the setting; a nested grid sees all n rows (its own input columns), so the per-sample array is indexed by row
+	bool set_max_level(float max_level) override {
+		bool any = false;
+		for (auto& e : m_nested) any |= e->set_max_level(max_level);
+		return any;
+	}
+	bool set_max_level_gpu(const float* per_sample) override {
+		bool any = false;
+		for (auto& e : m_nested) any |= e->set_max_level_gpu(per_sample);
+		return any;
+	}
+	bool get_max_level(float& max_level, const float*& per_sample) const override {
+		for (const auto& e : m_nested) {
+			if (e->get_max_level(max_level, per_sample)) return true;
+		}
+		return false;
+	}
 
 private:
 	uint32_t m_n_dims;
@@ -1567,6 +1702,11 @@ public:
 	virtual std::vector<std::pair<uint32_t, uint32_t>> layer_sizes() const = 0;
 	virtual void initialize_params(Pcg32& rng, float* params_full_precision, float scale) = 0;
 	virtual uint64_t list_scatters() const { return 0; } // backward passes of the model's grid encoding(s) that ran the list-fed gradient kernel
+	// max_level of the model's grid encoding(s) (Encoding::set_max_level); false: the model has none
+	virtual Encoding* input_encoding() { return nullptr; }
+	bool set_max_level(float max_level) { Encoding* e = input_encoding(); return e && e->set_max_level(max_level); }
+	bool set_max_level_gpu(const float* per_sample) { Encoding* e = input_encoding(); return e && e->set_max_level_gpu(per_sample); }
+	bool get_max_level(float& max_level, const float*& per_sample) { Encoding* e = input_encoding(); return e && e->get_max_level(max_level, per_sample); }
 	virtual void inference(hipStream_t stream, uint32_t n, MatView input, void* output, const void* params) = 0;
 	// float output of the unpadded width (object.h:147-176: inference + trim_and_cast_from); models may fuse the conversion
 	virtual void inference_f32(hipStream_t stream, uint32_t n, MatView input, MatViewMut output, const void* params) {
@@ -1667,6 +1807,7 @@ public:
 	Precision precision() const override { return Precision::Fp16; }
 	std::vector<std::pair<uint32_t, uint32_t>> layer_sizes() const override { return m_network->layer_sizes(); }
 	Encoding& encoding() { return *m_encoding; }
+	Encoding* input_encoding() override { return m_encoding.get(); }
 	Network& network() { return *m_network; }
 
 	void initialize_params(Pcg32& rng, float* params_full_precision, float scale) override { // :124-130, network first
@@ -2000,6 +2141,7 @@ public:
 	std::vector<std::pair<uint32_t, uint32_t>> layer_sizes() const override { return {}; }
 	void initialize_params(Pcg32& rng, float* params_full_precision, float scale) override { m_encoding->initialize_params(rng, params_full_precision, scale); }
 	uint64_t list_scatters() const override { return m_encoding->list_scatters(); }
+	Encoding* input_encoding() override { return m_encoding.get(); }
 
 	struct Ctx : public ModelContext {
 		EncodingContext encoding_ctx;

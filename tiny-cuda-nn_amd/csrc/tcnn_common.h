@@ -491,5 +491,11 @@ void cast_half_to_float(hipStream_t stream, size_t n, const void* in, float* out
 // object.cu:61-67: [n][in_stride] T -> float out(dim, sample) = out.data[i*stride_sample + d*stride_dim], d < dims
 void trim_and_cast(hipStream_t stream, bool fp32, uint32_t n, uint32_t in_stride, uint32_t dims, const void* in, MatViewMut out);
 void fill_half(hipStream_t stream, size_t n, void* out, float value);
+// max_level (k_grid_max_level.hip): zeroes the `width` elements at data + i * sample_stride + l * level_stride (2- or 4-byte elements) of every
+// (sample i < n, level level0 <= l < n_levels) pair that is off -- all of them without per_sample (the scalar cut-off's suffix), else those
+// whose per_sample[i] puts them off by the forward rule (l >= m + 1e-3f) or the gradient rule (l > m + 1e-3f), m = per_sample[i] * n_grid_features / F.
+// src (same layout): a masked copy instead -- every pair of every level is written, from src where the pair is on (scalar: l < level0)
+void grid_zero_levels(hipStream_t stream, size_t elem_bytes, uint32_t n, uint32_t n_levels, uint32_t level0, uint32_t width, uint64_t sample_stride, uint64_t level_stride,
+                      void* data, const void* src, const float* per_sample, uint32_t n_grid_features, uint32_t F, bool gradient_rule);
 
 } // namespace tcnn_amd

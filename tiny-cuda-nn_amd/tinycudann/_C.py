@@ -77,6 +77,9 @@ _SIGNATURES = {
     "tcnn_module_n_output_dims": (_u32, [_vp]),
     "tcnn_module_n_params": (_sz, [_vp]),
     "tcnn_module_list_scatters": (_sz, [_vp]),
+    "tcnn_module_set_max_level": (_int, [_vp, _f32]),
+    "tcnn_module_max_level": (_f32, [_vp]),
+    "tcnn_module_set_max_level_gpu": (_int, [_vp, _vp]),
     "tcnn_module_param_precision": (_int, [_vp]),
     "tcnn_module_output_precision": (_int, [_vp]),
     "tcnn_module_initialize_params": (_int, [_vp, _u64, _vp, _f32]),
@@ -114,6 +117,9 @@ _SIGNATURES = {
     "tcnn_trainer_scatter_wide_fallbacks": (C.c_size_t, [_vp]),
     "tcnn_trainer_optimizer_prologue_steps": (C.c_size_t, [_vp]),
     "tcnn_trainer_list_scatters": (C.c_size_t, [_vp]),
+    "tcnn_trainer_set_max_level": (_int, [_vp, _f32]),
+    "tcnn_trainer_set_max_level_gpu": (_int, [_vp, _vp]),
+    "tcnn_trainer_max_level": (_f32, [_vp]),
     "tcnn_train_ctx_keeps_weight_gradient_slabs": (C.c_int, [_vp, _vp]),
     "tcnn_trainer_profile_next_step": (_int, [_vp]),
     "tcnn_trainer_profile_collect": (_int, [_vp, _vp, C.POINTER(C.c_float), C.POINTER(_u32)]),

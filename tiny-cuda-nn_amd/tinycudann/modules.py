@@ -5,6 +5,7 @@ Same names, constructor arguments and tensor contracts as the reference's Python
 callers can switch by changing nothing but the installed package; the implementation behind those names is this package's.  PyTorch is used for what it is here: device memory,
 streams and autograd plumbing; every computation happens in libtcnn_amd.so behind the C ABI.
 """
+import contextlib
 import gc
 import json
 import warnings
@@ -46,11 +47,30 @@ class NativeModule:
 
     def __init__(self, handle):
         self._h = handle
+        self._max_level_gpu = None  # the per-sample array handed to the native module (kept alive here)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
         if h and _C is not None and getattr(_C, 'lib', None) is not None:  # modules may already be torn down at exit
             _C.lib.tcnn_module_destroy(h)
+
+    # --- max_level of the grid encoding(s) (GridEncoding::set_max_level / set_max_level_gpu, grid_interface.h:101-123; tcnn_amd.h)
+    def set_max_level(self, value):
+        _C.check(_C.lib.tcnn_module_set_max_level(self._h, float(value)))
+
+    def max_level(self):
+        value = float(_C.lib.tcnn_module_max_level(self._h))
+        if value != value and _C.lib.tcnn_last_error():  # NaN: an error, or a NaN that was set (tcnn_last_error() is empty then)
+            raise RuntimeError(_C.lib.tcnn_last_error().decode("utf-8", "replace"))
+        return value
+
+    def set_max_level_gpu(self, per_sample):
+        """per_sample: a float32 device tensor with one value per row of every later call (kept alive here), or None"""
+        _C.check(_C.lib.tcnn_module_set_max_level_gpu(self._h, _ptr(per_sample)))
+        self._max_level_gpu = per_sample
+
+    def max_level_gpu(self):
+        return self._max_level_gpu
 
     # --- bindings.cpp:242-260
     def n_input_dims(self):
@@ -175,14 +195,32 @@ def _create(fn, *args):
 class _Call:
     """What one forward call leaves behind for its backward passes."""
 
-    __slots__ = ("native", "native_ctx", "loss_scale", "wants_input", "wants_params")
+    __slots__ = ("native", "native_ctx", "loss_scale", "wants_input", "wants_params", "max_level")
 
-    def __init__(self, native, loss_scale, wants_input, wants_params):
+    def __init__(self, native, loss_scale, wants_input, wants_params, max_level=None):
         self.native = native
         self.native_ctx = None
         self.loss_scale = loss_scale
         self.wants_input = wants_input
         self.wants_params = wants_params
+        self.max_level = max_level  # None, or the max_level setting of the forward pass: (value, per-sample array padded to the batch or None)
+
+    @contextlib.contextmanager
+    def setting(self):
+        """The call's max_level in force on the native module (its backward passes belong to the forward pass's setting); the one
+        in force before comes back afterwards."""
+        if self.max_level is None:
+            yield
+            return
+        native = self.native
+        previous = (native.max_level(), native.max_level_gpu())
+        native.set_max_level(self.max_level[0])
+        native.set_max_level_gpu(self.max_level[1])
+        try:
+            yield
+        finally:
+            native.set_max_level(previous[0])
+            native.set_max_level_gpu(previous[1])
 
     def flagged(self, input, params, wants_input=None, wants_params=None):
         """The native entry points key on requires_grad (bindings.cpp:85, 126-131): aliases that carry exactly the flags of this call."""
@@ -193,7 +231,8 @@ class _Call:
     def first_order(self, input, params, output, doutput):
         """(dL/dinput, dL/dparams) for an upstream gradient doutput; None where the call did not ask for one."""
         inp, par = self.flagged(input, params)
-        gi, gp = self.native.bwd(self.native_ctx, inp, par, output, (doutput * self.loss_scale).contiguous())
+        with self.setting():
+            gi, gp = self.native.bwd(self.native_ctx, inp, par, output, (doutput * self.loss_scale).contiguous())
         inv = 1.0 / self.loss_scale
         return (None if gi is None else gi * inv), (None if gp is None else gp * inv)
 
@@ -202,17 +241,21 @@ class _Call:
         term for doutput carries no loss scale, the other two were computed at loss_scale."""
         inp, par = self.flagged(input, params, wants_input, wants_params)
         scaled = (doutput.detach() * self.loss_scale).contiguous().requires_grad_(wants_doutput)
-        g_doutput, g_params, g_input = self.native.bwd_bwd_input(self.native_ctx, inp, par, d_input_grad.contiguous().float(), scaled)
+        with self.setting():
+            g_doutput, g_params, g_input = self.native.bwd_bwd_input(self.native_ctx, inp, par, d_input_grad.contiguous().float(), scaled)
         inv = 1.0 / self.loss_scale
         return g_doutput, (None if g_input is None else g_input * inv), (None if g_params is None else g_params * inv)
 
 
 class _Evaluate(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, input, params, native, loss_scale):
-        call = _Call(native, loss_scale, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+    def forward(ctx, input, params, native, loss_scale, *max_level):
+        # (max_level: optional, the setting recorded by Module._max_level_of_call)
+        call = _Call(native, loss_scale, ctx.needs_input_grad[0], ctx.needs_input_grad[1], max_level[0] if max_level else None)
+        ctx.n_inputs = 4 + len(max_level)
         inp, par = call.flagged(input, params)
-        call.native_ctx, output = native.fwd(inp, par)  # no flag set: inference mode, no context
+        with call.setting():
+            call.native_ctx, output = native.fwd(inp, par)  # no flag set: inference mode, no context
         ctx.call = call
         ctx.save_for_backward(input, params, output)
         ctx.set_materialize_grads(False)
@@ -221,13 +264,13 @@ class _Evaluate(torch.autograd.Function):
     @staticmethod
     def backward(ctx, doutput):
         if doutput is None:
-            return None, None, None, None
+            return (None,) * ctx.n_inputs
         if not doutput.is_cuda:
             warnings.warn("doutput must be a CUDA tensor, but isn't. This indicates suboptimal performance.")
             doutput = doutput.cuda()
         input, params, output = ctx.saved_tensors
         g_input, g_params = _Differentiate.apply(doutput, input, params, output, ctx.call)
-        return g_input, g_params, None, None
+        return (g_input, g_params) + (None,) * (ctx.n_inputs - 2)
 
 
 class _Differentiate(torch.autograd.Function):
@@ -326,12 +369,53 @@ class Module(torch.nn.Module):
             working = self.params.contiguous()
         else:
             working = _WorkingCopy.apply(self.params, self)
-        output = _Evaluate.apply(rows, working, self.native_tcnn_module, self.loss_scale)
+        output = _Evaluate.apply(rows, working, self.native_tcnn_module, self.loss_scale, self._max_level_of_call(n, rows))
         return output[:n, : self.n_output_dims]
+
+    # --- max_level of the grid encoding(s) (the reference's GridEncoding::set_max_level / set_max_level_gpu, grid_interface.h:101-123).
+    # Every forward call records the setting in force; its backward and double-backward passes run under that setting.
+    def set_max_level(self, value):
+        """A fraction of the grid levels: `value * n_levels` levels produce output (1000, the default: every level)."""
+        self.native_tcnn_module.set_max_level(value)
+        self._max_level_value = float(value)
+
+    @property
+    def max_level(self):
+        return self.native_tcnn_module.max_level()
+
+    def set_max_level_gpu(self, per_sample):
+        """One max_level per row (instant-ngp's random max level): a contiguous float32 tensor on the module's device with at
+        least as many values as the rows of every later call (the module keeps a reference), or None to go back to the scalar."""
+        if per_sample is not None:
+            if not isinstance(per_sample, torch.Tensor) or per_sample.dtype != torch.float32 or not per_sample.is_contiguous() or per_sample.dim() != 1:
+                raise RuntimeError("tcnn: the per-sample max_level must be a contiguous one-dimensional float32 tensor")
+            if per_sample.device != self.params.device:
+                raise RuntimeError(f"tcnn: the per-sample max_level lives on {per_sample.device}, the module on {self.params.device}")
+        self.native_tcnn_module.set_max_level_gpu(per_sample)
+        self._max_level_tensor = per_sample
+
+    @property
+    def max_level_gpu(self):
+        return getattr(self, "_max_level_tensor", None)
+
+    def _max_level_of_call(self, n, rows):
+        """None while max_level was never set on this module, else (value, per-sample array padded to the rows of this call)"""
+        value, per_sample = getattr(self, "_max_level_value", None), getattr(self, "_max_level_tensor", None)
+        if value is None and per_sample is None:
+            return None
+        if value is None:
+            value = 1000.0
+        if per_sample is not None:
+            if per_sample.numel() < n:
+                raise RuntimeError(f"tcnn: the per-sample max_level holds {per_sample.numel()} values for a batch of {n} rows")
+            if per_sample.device != rows.device:
+                raise RuntimeError(f"tcnn: the per-sample max_level lives on {per_sample.device}, the input on {rows.device}")
+            per_sample = per_sample[:n] if rows.shape[0] == n else _pad_rows(per_sample[:n], rows.shape[0])  # the kernels read one value per padded row
+        return (value, per_sample)
 
     # native handles do not pickle: drop them, and rebuild them from the configuration on the other side
     def __getstate__(self):
-        return {k: v for k, v in self.__dict__.items() if k not in ("native_tcnn_module", "_working_copy", "_working_key")}
+        return {k: v for k, v in self.__dict__.items() if k not in ("native_tcnn_module", "_working_copy", "_working_key", "_max_level_value", "_max_level_tensor")}
 
     def __setstate__(self, state):
         self.__dict__.update(state)

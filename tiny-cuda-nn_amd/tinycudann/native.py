@@ -72,6 +72,7 @@ class Trainer:
         self.n_input_dims = n_input_dims
         self.n_output_dims = n_output_dims
         self.padded_output_width = int(_C.lib.tcnn_trainer_padded_output_width(h))
+        self._max_level_gpu = None
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -82,6 +83,7 @@ class Trainer:
     def training_step(self, input, target, data_pdf=None, run_optimizer=True, dL_dinput=None, use_inference_params=False,
                       gradient_mode=GRADIENT_OVERWRITE, external_dL_dy=None, input_layout=LAYOUT_AOS, stream=None):
         n = input.shape[0] if input_layout == LAYOUT_AOS else input.shape[1]
+        self._check_max_level_rows(n)
         ctx = C.c_void_p()
         _C.check(_C.lib.tcnn_trainer_training_step(self._h, _stream(stream), n, _ptr(input), input_layout, _ptr(target), _ptr(data_pdf),
                                                    int(run_optimizer), _ptr(dL_dinput), int(use_inference_params), gradient_mode,
@@ -134,12 +136,14 @@ class Trainer:
 
     def forward(self, input, target, loss_scale=128.0, data_pdf=None, prepare_input_gradients=False, external_dL_dy=None, input_layout=LAYOUT_AOS, stream=None):
         n = input.shape[0] if input_layout == LAYOUT_AOS else input.shape[1]
+        self._check_max_level_rows(n)
         ctx = C.c_void_p()
         _C.check(_C.lib.tcnn_trainer_forward(self._h, _stream(stream), loss_scale, n, _ptr(input), input_layout, _ptr(target), _ptr(data_pdf), 0,
                                              int(prepare_input_gradients), _ptr(external_dL_dy), C.byref(ctx)))
         return ForwardContext(ctx, n, self.padded_output_width)
 
     def backward(self, ctx, input, dL_dinput=None, gradient_mode=GRADIENT_OVERWRITE, input_layout=LAYOUT_AOS, stream=None):
+        self._check_max_level_rows(ctx.n)
         _C.check(_C.lib.tcnn_trainer_backward(self._h, _stream(stream), ctx._h, ctx.n, _ptr(input), input_layout, _ptr(dL_dinput), 0, gradient_mode))
 
     def optimizer_step(self, loss_scale=128.0, stream=None):
@@ -151,6 +155,7 @@ class Trainer:
         if output is None:
             shape = (n, self.n_output_dims) if output_layout == LAYOUT_AOS else (self.n_output_dims, n)
             output = torch.empty(shape, dtype=torch.float32, device=input.device)
+        self._check_max_level_rows(n)
         _C.check(_C.lib.tcnn_trainer_inference(self._h, _stream(stream), n, _ptr(input), input_layout, _ptr(output), output_layout, 1))
         return output
 
@@ -160,8 +165,39 @@ class Trainer:
         if output is None:
             output = torch.empty((n, self.padded_output_width), dtype=torch.half, device=input.device)
         assert output.dtype == torch.half and output.is_contiguous() and output.shape == (n, self.padded_output_width)
+        self._check_max_level_rows(n)
         _C.check(_C.lib.tcnn_trainer_inference_mixed_precision(self._h, _stream(stream), n, _ptr(input), input_layout, _ptr(output), 1))
         return output
+
+    # -- max_level of the model's grid encoding(s) (GridEncoding::set_max_level / max_level / set_max_level_gpu, grid_interface.h:101-123):
+    # read by every later training_step / forward / backward / inference call
+    def set_max_level(self, value):
+        """A fraction of the grid levels: `value * n_levels` levels produce output (1000, the default: every level)."""
+        _C.check(_C.lib.tcnn_trainer_set_max_level(self._h, float(value)))
+
+    @property
+    def max_level(self):
+        value = float(_C.lib.tcnn_trainer_max_level(self._h))
+        if value != value and _C.lib.tcnn_last_error():  # NaN: an error, or a NaN that was set (tcnn_last_error() is empty then)
+            raise RuntimeError(_C.lib.tcnn_last_error().decode("utf-8", "replace"))
+        return value
+
+    def set_max_level_gpu(self, per_sample):
+        """One max_level per row: a contiguous float32 device tensor with at least as many values as the rows of every later call
+        (the trainer keeps a reference), or None to go back to the scalar."""
+        if per_sample is not None:
+            if not isinstance(per_sample, torch.Tensor) or per_sample.dtype != torch.float32 or not per_sample.is_contiguous() or not per_sample.is_cuda:
+                raise RuntimeError("tcnn: the per-sample max_level must be a contiguous float32 device tensor")
+        _C.check(_C.lib.tcnn_trainer_set_max_level_gpu(self._h, _ptr(per_sample)))
+        self._max_level_gpu = per_sample
+
+    @property
+    def max_level_gpu(self):
+        return self._max_level_gpu
+
+    def _check_max_level_rows(self, n):
+        if self._max_level_gpu is not None and self._max_level_gpu.numel() < n:
+            raise RuntimeError(f"tcnn: the per-sample max_level holds {self._max_level_gpu.numel()} values for a batch of {n} rows")
 
     @property
     def n_params(self):
