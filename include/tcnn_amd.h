@@ -204,6 +204,11 @@ size_t tcnn_trainer_optimizer_prologue_steps(tcnn_trainer_t t);
  * which kernel produced the gradients they compare with the oracle (replaces kernel_grid_backward, grid.h:215-320). */
 size_t tcnn_trainer_list_scatters(tcnn_trainer_t t);
 size_t tcnn_module_list_scatters(tcnn_module_t m); /* the same count for a module's grid encoding(s) (callers with their own network) */
+/* Introspection (no counterpart in the reference): a short, stable name of the MLP training kernel the last training_step() of this
+ * trainer launched -- "r32", "r32a", "r32w", "r32ob", "regs_fast", "regs", "train<W,NB,NW,MAXT>/relu", "train<W,NB,NW,MAXT>/act",
+ * "train_pw28/...", "train_pw32/...", "train_regw/...", "train_ob/..." (/act: the hidden activation is chosen at run time) or "unfused"
+ * (forward, loss, backward and weight-gradient kernels of their own); "" before the first step.  A static string: do not free it. */
+const char* tcnn_trainer_last_step_kernel(tcnn_trainer_t t);
 
 /* max_level of the grid encodings (GridEncoding::set_max_level / max_level / set_max_level_gpu / max_level_gpu, grid_interface.h:101-123):
  * a fraction of the levels, 1000 (the default) keeps every one.  With m = max_level * n_levels, level l produces zeros (in its features and

@@ -1628,14 +1628,22 @@ class Trainer:
         self.params = half_bits(self.params_fp)
         self.grads = np.zeros(n, dtype=np.uint16)
 
-    def training_step(self, x, target, run_optimizer=True, want_dL_dx=False, grads_f32=None):
+    def training_step(self, x, target, run_optimizer=True, want_dL_dx=False, grads_f32=None, data_pdf=None, external_dL_dy=None, use_inference_params=False):
+        """trainer.h:163-190.  data_pdf [n][n_out] float goes to the loss; external_dL_dy ([n][padded] half bits) replaces the loss (L is then
+        all zeros); use_inference_params runs forward and backward at params_inference() (EMA weights) while the gradients still land in
+        self.grads.  dL_dinput stays in loss-scaled units, as the reference's."""
         x = np.ascontiguousarray(x, dtype=np.float32)
         n = x.shape[0]
         if n % BATCH_SIZE_GRANULARITY:
             raise RuntimeError("batch size must be a multiple of 256")  # object.h:130
-        out, ctx = self.model.forward(x, self.params, prepare_input_gradients=want_dL_dx)
-        values, dL_dout = loss_evaluate(self.loss_type, out, target)
-        dL_dx, dnet_in = self.model.backward(x, self.params, ctx, out, dL_dout, want_dL_dx, self.grads, grads_f32)
+        params = self.params_inference() if use_inference_params else self.params
+        out, ctx = self.model.forward(x, params, prepare_input_gradients=want_dL_dx)
+        if external_dL_dy is None:
+            values, dL_dout = loss_evaluate(self.loss_type, out, target, data_pdf=data_pdf)
+        else:
+            dL_dout = np.ascontiguousarray(external_dL_dy, dtype=np.uint16).reshape(out.shape)
+            values = np.zeros(out.shape, dtype=np.float32)
+        dL_dx, dnet_in = self.model.backward(x, params, ctx, out, dL_dout, want_dL_dx, self.grads, grads_f32)
         if run_optimizer:
             self.optimizer.step(LOSS_SCALE, self.params_fp, self.params, self.grads)
         return {"output": out, "L": values, "dL_doutput": dL_dout, "dL_dinput": dL_dx, "dL_dnetwork_input": dnet_in, "ctx": ctx,

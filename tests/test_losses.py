@@ -101,12 +101,12 @@ def test_training_step_with_each_loss(tcnn, oracle, name):
     assert tr.loss(ctx) < first
 
 
-def _assert_fused_loss_close(got_v, want_v, got_g, want_g):
-    """float32 loss values within 4 ulp, >= 99.9 % of the fp16 gradients bit-identical, the others adjacent halves"""
+def _assert_fused_loss_close(got_v, want_v, got_g, want_g, max_ulp=4):
+    """float32 loss values within 4 ulp (max_ulp), >= 99.9 % of the fp16 gradients bit-identical, the others adjacent halves"""
     gv, wv = np.ascontiguousarray(got_v, dtype=np.float32).ravel(), np.ascontiguousarray(want_v, dtype=np.float32).ravel()
     assert np.array_equal(gv == 0, wv == 0)  # padding columns, exact hits
     ulps = np.abs(gv.view(np.int32).astype(np.int64) - wv.view(np.int32).astype(np.int64))
-    assert int(ulps.max()) <= 4, int(ulps.max())
+    assert int(ulps.max()) <= max_ulp, int(ulps.max())
     gg, wg = np.ascontiguousarray(got_g).view(np.uint16).ravel(), np.ascontiguousarray(want_g).view(np.uint16).ravel()
     same = gg == wg
     assert float(np.mean(same)) >= 0.999, float(np.mean(same))

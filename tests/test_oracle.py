@@ -322,3 +322,117 @@ def test_oracle_training_learns(oracle, cfg):
     assert tr.inference(x).shape == (1024, 3)
     with pytest.raises(RuntimeError):
         tr.training_step(x[:100], t[:100])  # batch granularity 256 (object.h:130)
+
+
+# ---------------------------------------------------------------------------------------------------- training_step options of the oracle
+def test_oracle_training_step_data_pdf(oracle):
+    """data_pdf reaches loss_evaluate: L and dL_doutput of the step are the float64 loss formulas of test_losses.py divided by the pdf,
+    applied to the step's own predictions; the pdf changes the parameter gradients."""
+    from test_losses import _numpy_loss
+
+    n, n_out = 1024, 3
+    for name in ("L2", "RelativeL2", "L1"):
+        cfg = {**CONFIG_C3B, "loss": {"otype": name}}
+        x, t = oracle.synthetic_batch(n, 2, n_out, seed=42)
+        pdf = np.random.RandomState(1).uniform(0.25, 4.0, (n, n_out)).astype(np.float32)
+        pdf[np.log2(pdf) == np.round(np.log2(pdf))] *= np.float32(1.1)  # no powers of two: a dropped or inverted pdf cannot hide
+        tr = oracle.Trainer(2, n_out, cfg, seed=1337)
+        got = tr.training_step(x, t, run_optimizer=False, data_pdf=pdf)
+        g_pdf = tr.grads.copy()
+        p = oracle.half_to_f32(got["output"])[:, :n_out]
+        want_v, want_g = _numpy_loss(name, p, t, pdf, 128.0)
+        assert np.allclose(got["L"][:, :n_out], want_v, rtol=2e-6, atol=1e-12), name
+        assert np.allclose(oracle.half_to_f32(got["dL_doutput"])[:, :n_out], want_g, rtol=2e-3, atol=1e-7), name
+        assert np.all(got["L"][:, n_out:] == 0)
+        plain = oracle.Trainer(2, n_out, cfg, seed=1337)
+        plain.training_step(x, t, run_optimizer=False)
+        assert not np.array_equal(plain.grads, g_pdf), name
+
+
+def test_oracle_training_step_external_dL_dy(oracle):
+    """external_dL_dy replaces the loss: L is zero and the backward pass starts from the given dL/doutput."""
+    n = 512
+    x, t = oracle.synthetic_batch(n, 2, 3, seed=42)
+    tr = oracle.Trainer(2, 3, CONFIG_C3B, seed=1337)
+    dy = oracle.half_bits(oracle.Pcg32(9).uniform_strided(n * 16, -1.0, 1.0).reshape(n, 16))
+    got = tr.training_step(x, None, run_optimizer=False, external_dL_dy=dy, want_dL_dx=True)
+    assert np.all(got["L"] == 0) and got["loss"] == 0.0 and np.array_equal(got["dL_doutput"], dy)
+    out, ctx = tr.model.forward(x, tr.params, prepare_input_gradients=True)
+    grads = np.zeros(tr.model.n_params, dtype=np.uint16)
+    dL_dx, _ = tr.model.backward(x, tr.params, ctx, out, dy, True, grads)
+    assert np.array_equal(tr.grads, grads) and np.array_equal(got["dL_dinput"], dL_dx) and np.any(dL_dx != 0)
+
+
+def test_oracle_training_step_use_inference_params(oracle):
+    """use_inference_params (trainer.h:163-190): forward and backward at the EMA weights, gradients still written, weights untouched."""
+    cfg = {**CONFIG_C3B, "optimizer": {"otype": "Ema", "decay": 0.9, "nested": CONFIG_C3B["optimizer"]}}
+    n = 1024
+    tr = oracle.Trainer(2, 3, cfg, seed=1337)
+    for s in range(3):
+        x, t = oracle.synthetic_batch(n, 2, 3, seed=100 + s)
+        tr.training_step(x, t)
+    ema = tr.params_inference().copy()
+    assert not np.array_equal(ema, tr.params)  # else the test could not tell the two apart
+    params, params_fp = tr.params.copy(), tr.params_fp.copy()
+    x, t = oracle.synthetic_batch(n, 2, 3, seed=7)
+    got = tr.training_step(x, t, run_optimizer=False, use_inference_params=True, want_dL_dx=True)
+    out, ctx = tr.model.forward(x, ema, prepare_input_gradients=True)
+    values, dy = oracle.loss_evaluate(tr.loss_type, out, t)
+    grads = np.zeros(tr.model.n_params, dtype=np.uint16)
+    dL_dx, _ = tr.model.backward(x, ema, ctx, out, dy, True, grads)
+    assert np.array_equal(got["output"], out) and np.array_equal(got["L"], values) and np.array_equal(got["dL_doutput"], dy)
+    assert np.array_equal(tr.grads, grads) and np.array_equal(got["dL_dinput"], dL_dx)
+    assert np.array_equal(tr.params, params) and np.array_equal(tr.params_fp, params_fp) and np.array_equal(tr.params_inference(), ema)
+    out_train, _ = tr.model.forward(x, params)
+    assert not np.array_equal(out_train, out)
+
+
+def _grid_y_f64(oracle, g, x, params_h, idx):
+    """y(x) of a Linear / Smoothstep grid in float64 at the corners `idx` ([n][levels][2^D] from the oracle's forward pass)."""
+    n, D, F = x.shape[0], g.n_in, int(g.g.n_features_per_level)
+    table = params_h.view(np.float16).astype(np.float64).reshape(-1, F)
+    smooth = int(g.g.interpolation) == oracle.INTERP["smoothstep"]
+    y = np.zeros((n, g.n_output_dims))
+    for lv in range(int(g.g.n_levels)):
+        pos = np.float64(g.scales[lv]) * x + 0.5
+        w = pos - np.floor(pos)
+        if smooth:
+            w = w * w * (3.0 - 2.0 * w)
+        for corner in range(1 << D):
+            wgt = np.ones(n)
+            for d in range(D):
+                wgt *= w[:, d] if (corner >> d) & 1 else 1.0 - w[:, d]
+            y[:, F * lv : F * lv + F] += wgt[:, None] * table[idx[:, lv, corner].astype(np.int64) + int(g.offsets[lv])]
+    return y
+
+
+@pytest.mark.parametrize("n_in,interp", [(2, "Linear"), (3, "Linear"), (2, "Smoothstep"), (3, "Smoothstep")])
+def test_grid_input_gradient_against_central_differences(oracle, n_in, interp):
+    """First-order dL/dx of a grid (orc_grid_forward's dy_dx, then orc_grid_backward_input) against float64 central differences of
+    sum(dL_dy * y(x)).  Samples whose step crosses a cell boundary of some level are excused (y is only piecewise smooth)."""
+    cfg = {"otype": "HashGrid", "n_levels": 8, "n_features_per_level": 2, "log2_hashmap_size": 14, "base_resolution": 4, "per_level_scale": 1.6, "interpolation": interp}
+    g = oracle.GridEncoding(n_in, cfg)
+    n = 1024
+    x = oracle.Pcg32(42).uniform_strided(n * n_in).reshape(n, n_in)
+    params_h = oracle.half_bits(oracle.Pcg32(3).uniform_strided(g.n_params, -1.0, 1.0))
+    dy = oracle.half_bits(oracle.Pcg32(9).uniform_strided(n * g.padded_output_width, -2.0, 2.0).reshape(n, g.padded_output_width))
+    _, ctx = g.forward(x, params_h, want_indices=True, want_dy_dx=True)
+    got = g.backward(x, ctx, dy, want_dL_dx=True)
+    dyf = dy.view(np.float16).astype(np.float64)[:, : g.n_output_dims]
+    h = 1e-5
+    x64 = x.astype(np.float64)
+    fd = np.zeros((n, n_in))
+    ok = np.ones(n, dtype=bool)
+    for d in range(n_in):
+        e = np.zeros(n_in)
+        e[d] = h
+        for lv in range(int(g.g.n_levels)):
+            s = np.float64(g.scales[lv])
+            ok &= np.all(np.floor(s * (x64 + e) + 0.5) == np.floor(s * (x64 - e) + 0.5), axis=1)
+        yp, ym = _grid_y_f64(oracle, g, x64 + e, params_h, ctx["indices"]), _grid_y_f64(oracle, g, x64 - e, params_h, ctx["indices"])
+        fd[:, d] = np.sum(dyf * (yp - ym), axis=1) / (2 * h)
+    assert np.mean(ok) > 0.8
+    scale = float(np.max(np.abs(fd[ok])))
+    # dy_dx and the sum over features are fp32 (grid.h:177-205, 543-578); the pos = scale * x + 0.5 of the oracle rounds to fp32 first
+    assert np.max(np.abs(got[ok] - fd[ok])) <= 1e-4 * scale, float(np.max(np.abs(got[ok] - fd[ok])) / scale)
+    assert np.all(np.isfinite(got)) and np.any(got != 0)

@@ -389,6 +389,7 @@ size_t tcnn_trainer_scatter_wide_fallbacks(tcnn_trainer_t t) {
 	try { return (size_t)t->trainer->scatter_wide_fallbacks(); } catch (const std::exception& e) { g_last_error = e.what(); return (size_t)-1; }
 }
 size_t tcnn_trainer_list_scatters(tcnn_trainer_t t) { return (size_t)t->trainer->list_scatters(); }
+const char* tcnn_trainer_last_step_kernel(tcnn_trainer_t t) { return t->trainer->last_step_kernel(); }
 int tcnn_trainer_set_max_level(tcnn_trainer_t t, float max_level) {
 	return guarded([&] {
 		CHECK_THROW(t && t->trainer);

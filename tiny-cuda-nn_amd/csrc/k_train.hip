@@ -732,32 +732,40 @@ inline TrainConfig pick_config(const MlpDesc& d) {
 	return cfg;
 }
 
+// the kernel's short name (Trainer::last_step_kernel): "train<W,NB,NW,MAXT>/relu" or ".../act" (ACT = -1, activation chosen at run time)
 template <int W, int NB, int NW, int MAXT>
-void launch_train(hipStream_t stream, const MlpDesc& d, const TrainArgs& a, uint32_t grid, uint32_t lds_bytes) {
+const char* launch_train(hipStream_t stream, const MlpDesc& d, const TrainArgs& a, uint32_t grid, uint32_t lds_bytes) {
 	auto go = [&](auto kernel) {
 		HIP_CHECK_THROW(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
 		hipLaunchKernelGGL(kernel, dim3(grid), dim3(NW * 64), lds_bytes, stream, d, a);
 		HIP_CHECK_THROW(hipGetLastError());
 	};
-	if (d.activation == (uint32_t)Activation::ReLU) go(k_mlp_train<W, NB, NW, MAXT, (int)Activation::ReLU>);
-	else go(k_mlp_train<W, NB, NW, MAXT, -1>);
+	static const std::string relu = "train<" + std::to_string(W) + "," + std::to_string(NB) + "," + std::to_string(NW) + "," + std::to_string(MAXT) + ">/relu";
+	static const std::string act = relu.substr(0, relu.size() - 4) + "act";
+	if (d.activation == (uint32_t)Activation::ReLU) {
+		go(k_mlp_train<W, NB, NW, MAXT, (int)Activation::ReLU>);
+		return relu.c_str();
+	}
+	go(k_mlp_train<W, NB, NW, MAXT, -1>);
+	return act.c_str();
 }
 
-void dispatch_train(hipStream_t stream, const MlpDesc& d, const TrainArgs& a, const TrainConfig& cfg, uint32_t grid) {
+const char* dispatch_train(hipStream_t stream, const MlpDesc& d, const TrainArgs& a, const TrainConfig& cfg, uint32_t grid) {
 	if (cfg.pw) {
 		auto go = [&](auto kernel) {
 			HIP_CHECK_THROW(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cfg.lds_bytes));
 			hipLaunchKernelGGL(kernel, dim3(grid), dim3(8 * 64), cfg.lds_bytes, stream, d, a);
 			HIP_CHECK_THROW(hipGetLastError());
 		};
+		const bool relu = d.activation == (uint32_t)Activation::ReLU;
 		if (cfg.maxt == 28) {
-			if (d.activation == (uint32_t)Activation::ReLU) go(k_mlp_train<64, 1, 8, 28, (int)Activation::ReLU, true>);
+			if (relu) go(k_mlp_train<64, 1, 8, 28, (int)Activation::ReLU, true>);
 			else go(k_mlp_train<64, 1, 8, 28, -1, true>);
-		} else {
-			if (d.activation == (uint32_t)Activation::ReLU) go(k_mlp_train<64, 1, 8, 32, (int)Activation::ReLU, true>);
-			else go(k_mlp_train<64, 1, 8, 32, -1, true>);
+			return relu ? "train_pw28/relu" : "train_pw28/act";
 		}
-		return;
+		if (relu) go(k_mlp_train<64, 1, 8, 32, (int)Activation::ReLU, true>);
+		else go(k_mlp_train<64, 1, 8, 32, -1, true>);
+		return relu ? "train_pw32/relu" : "train_pw32/act";
 	}
 	if (cfg.regw) {
 		auto go = [&](auto kernel) {
@@ -765,9 +773,12 @@ void dispatch_train(hipStream_t stream, const MlpDesc& d, const TrainArgs& a, co
 			hipLaunchKernelGGL(kernel, dim3(grid), dim3(8 * 64), cfg.lds_bytes, stream, d, a);
 			HIP_CHECK_THROW(hipGetLastError());
 		};
-		if (d.activation == (uint32_t)Activation::ReLU) go(k_mlp_train<64, 1, 8, 8, (int)Activation::ReLU, false, true>);
-		else go(k_mlp_train<64, 1, 8, 8, -1, false, true>);
-		return;
+		if (d.activation == (uint32_t)Activation::ReLU) {
+			go(k_mlp_train<64, 1, 8, 8, (int)Activation::ReLU, false, true>);
+			return "train_regw/relu";
+		}
+		go(k_mlp_train<64, 1, 8, 8, -1, false, true>);
+		return "train_regw/act";
 	}
 	if (a.ob_log2) { // the OneBlob input is evaluated in the kernel: one shape (C2's)
 		CHECK_THROW((int)d.width == 64 && cfg.nb == 1 && cfg.nw == 8 && cfg.maxt == 8 && !cfg.pw && !cfg.regw);
@@ -776,9 +787,12 @@ void dispatch_train(hipStream_t stream, const MlpDesc& d, const TrainArgs& a, co
 			hipLaunchKernelGGL(kernel, dim3(grid), dim3(8 * 64), cfg.lds_bytes, stream, d, a);
 			HIP_CHECK_THROW(hipGetLastError());
 		};
-		if (d.activation == (uint32_t)Activation::ReLU) go(k_mlp_train<64, 1, 8, 8, (int)Activation::ReLU, false, false, true>);
-		else go(k_mlp_train<64, 1, 8, 8, -1, false, false, true>);
-		return;
+		if (d.activation == (uint32_t)Activation::ReLU) {
+			go(k_mlp_train<64, 1, 8, 8, (int)Activation::ReLU, false, false, true>);
+			return "train_ob/relu";
+		}
+		go(k_mlp_train<64, 1, 8, 8, -1, false, false, true>);
+		return "train_ob/act";
 	}
 #define TCNN_TRAIN_CASE(W_, NB_, NW_, MAXT_) \
 	if ((int)d.width == W_ && cfg.nb == NB_ && cfg.nw == NW_ && cfg.maxt == MAXT_) return launch_train<W_, NB_, NW_, MAXT_>(stream, d, a, grid, cfg.lds_bytes);
@@ -819,15 +833,17 @@ uint32_t mlp_train_fused_grid(const MlpDesc& d, uint32_t n, uint32_t oneblob_bin
 	return std::max(1u, std::min(trips, cap));
 }
 
-void mlp_train_fused(hipStream_t stream, const MlpDesc& d, const void* image, uint32_t n, const void* x, uint32_t x_plane_features, const float* target, const float* data_pdf,
-                     const void* external_dL_dy, uint32_t dims, LossType loss, float loss_scale, void* out, void* dL_dout, float* L, bool compact_context, void* dL_dx,
-                     uint32_t dx_plane_features, const float* dx_record_x, uint32_t dx_record_dims, float* slabs, uint32_t n_params, const MlpOneBlobInput* oneblob) {
+const char* mlp_train_fused(hipStream_t stream, const MlpDesc& d, const void* image, uint32_t n, const void* x, uint32_t x_plane_features, const float* target, const float* data_pdf,
+                            const void* external_dL_dy, uint32_t dims, LossType loss, float loss_scale, void* out, void* dL_dout, float* L, bool compact_context, void* dL_dx,
+                            uint32_t dx_plane_features, const float* dx_record_x, uint32_t dx_record_dims, float* slabs, uint32_t n_params, const MlpOneBlobInput* oneblob) {
 	CHECK_THROW(!oneblob || mlp_train_fused_oneblob_supported(d, n, oneblob->n_bins));
 	if (!compact_context && mlp_train_r32ob_applies(d, n, oneblob, data_pdf, external_dL_dy, dims, loss, out, dL_dx, slabs)) {
-		return mlp_train_r32ob(stream, d, image, n, *oneblob, target, dims, loss, loss_scale, out, dL_dout, L, slabs, n_params);
+		mlp_train_r32ob(stream, d, image, n, *oneblob, target, dims, loss, loss_scale, out, dL_dout, L, slabs, n_params);
+		return "r32ob";
 	}
 	if (!compact_context && mlp_train_r32w_applies(d, n, x_plane_features, data_pdf, external_dL_dy, dims, loss, out, dL_dx, dx_plane_features, dx_record_x, slabs, oneblob != nullptr)) {
-		return mlp_train_r32w(stream, d, image, n, x, target, dims, loss, loss_scale, out, dL_dout, L, dL_dx, slabs, n_params, mlp_train_fused_grid(d, n));
+		mlp_train_r32w(stream, d, image, n, x, target, dims, loss, loss_scale, out, dL_dout, L, dL_dx, slabs, n_params, mlp_train_fused_grid(d, n));
+		return "r32w";
 	}
 	if (mlp_train_regs_supported(d, n) && slabs != nullptr) { // without weight gradients (GradientMode::Ignore): the kernels below
 		CHECK_THROW(compact_context || external_dL_dy);
@@ -851,13 +867,14 @@ void mlp_train_fused(hipStream_t stream, const MlpDesc& d, const void* image, ui
 #else
 	int timing_left = 0; (void)timing_left;
 #endif
-	dispatch_train(stream, d, a, cfg, mlp_train_fused_grid(d, n));
+	const char* name = dispatch_train(stream, d, a, cfg, mlp_train_fused_grid(d, n));
 	if (a.dbg) {
 		unsigned long long h[8];
 		HIP_CHECK_THROW(hipMemcpy(h, a.dbg, 64, hipMemcpyDeviceToHost));
 		if (--timing_left == 0) fprintf(stderr, "k_mlp_train wave 0 clocks over its trips: fwd %llu loss %llu bwd %llu dX+stores %llu barrier1 %llu wgrad %llu barrier2 %llu\n", h[0], h[1], h[2], h[3], h[4], h[5], h[6]);
 		(void)hipFree(a.dbg);
 	}
+	return name;
 }
 
 } // namespace tcnn_amd

@@ -512,6 +512,8 @@ static bool r32a_chosen(uint32_t n) {
 	if (forced >= 0) return forced == 1;
 	return n <= 131072u;
 }
+const char* mlp_train_r32_name(uint32_t n) { return r32a_chosen(n) ? "r32a" : "r32"; }
+
 // workgroups = weight-gradient slabs of the kernel mlp_train_r32 launches for this batch
 uint32_t mlp_train_r32_grid(uint32_t n) {
 	if (r32a_chosen(n)) {

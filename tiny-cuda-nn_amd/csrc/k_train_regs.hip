@@ -564,7 +564,8 @@ template <int IN_T, int NH> bool regs_layout_matches(const MlpDesc& d) {
 	return (int)d.layers[NH].fwd_off == Lay::fwd_out && (int)(d.n_frags_fwd + d.layers[NH].bwd_off) == Lay::bwd_out;
 }
 
-template <int IN_T, int NH> void launch_regs(hipStream_t stream, const MlpDesc& d, const RegsArgs& a, uint32_t grid, int loss) {
+// returns the kernel's short name (Trainer::last_step_kernel): "regs_fast" (compile-time formats) or "regs"
+template <int IN_T, int NH> const char* launch_regs(hipStream_t stream, const MlpDesc& d, const RegsArgs& a, uint32_t grid, int loss) {
 	const uint32_t lds = regs_lds_bytes<IN_T, NH>();
 	auto go = [&](auto kernel) {
 		HIP_CHECK_THROW(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -579,16 +580,28 @@ template <int IN_T, int NH> void launch_regs(hipStream_t stream, const MlpDesc& 
 	if constexpr (IN_T == 2 && NH == 2) {
 #ifdef TCNN_AMD_DEV
 		static const bool phases = getenv("TCNN_AMD_MLP_TIMING") && getenv("TCNN_AMD_MLP_TIMING")[0] == '2';
-		if (phases && a.dbg && fast && loss == 2) return go(k_mlp_train_regs<IN_T, NH, RELU, 2, true, true>);
+		if (phases && a.dbg && fast && loss == 2) {
+			go(k_mlp_train_regs<IN_T, NH, RELU, 2, true, true>);
+			return "regs_fast";
+		}
 #endif
 	}
-	if (fast) return loss == 1 ? go(k_mlp_train_regs<IN_T, NH, RELU, 1, true>) : go(k_mlp_train_regs<IN_T, NH, RELU, 2, true>);
+	if (fast) {
+		if (loss == 1) go(k_mlp_train_regs<IN_T, NH, RELU, 1, true>);
+		else go(k_mlp_train_regs<IN_T, NH, RELU, 2, true>);
+		return "regs_fast";
+	}
 #define TCNN_REGS_CASE(L_) \
-	if (loss == L_) return relu ? go(k_mlp_train_regs<IN_T, NH, RELU, L_, false>) : go(k_mlp_train_regs<IN_T, NH, NONE, L_, false>);
+	if (loss == L_) { \
+		if (relu) go(k_mlp_train_regs<IN_T, NH, RELU, L_, false>); \
+		else go(k_mlp_train_regs<IN_T, NH, NONE, L_, false>); \
+		return "regs"; \
+	}
 	TCNN_REGS_CASE(0)
 	TCNN_REGS_CASE(1)
 	TCNN_REGS_CASE(2)
 #undef TCNN_REGS_CASE
+	throw std::runtime_error{"mlp_train_regs: no kernel instance for this loss"};
 }
 
 // compact context matrices -> the reference's padded ones: dL_dout [n][16] halves, L [n][16] floats, zero beyond `dims`
@@ -620,16 +633,17 @@ uint32_t mlp_train_regs_grid(const MlpDesc& d, uint32_t n) {
 	return std::max(1u, std::min(cap, div_round_up(n / 16, (uint32_t)REGS_NW)));
 }
 
-void mlp_train_regs(hipStream_t stream, const MlpDesc& d, const void* image, uint32_t n, const void* x, uint32_t x_plane_features, const float* target, const float* data_pdf,
-                    const void* external_dL_dy, uint32_t dims, LossType loss, float loss_scale, void* out, void* compact_dL_dout, float* compact_L, void* dL_dx,
-                    uint32_t dx_plane_features, const float* dx_record_x, uint32_t dx_record_dims, float* slabs, uint32_t n_params) {
+const char* mlp_train_regs(hipStream_t stream, const MlpDesc& d, const void* image, uint32_t n, const void* x, uint32_t x_plane_features, const float* target, const float* data_pdf,
+                           const void* external_dL_dy, uint32_t dims, LossType loss, float loss_scale, void* out, void* compact_dL_dout, float* compact_L, void* dL_dx,
+                           uint32_t dx_plane_features, const float* dx_record_x, uint32_t dx_record_dims, float* slabs, uint32_t n_params) {
 	CHECK_THROW(mlp_train_regs_supported(d, n));
 	CHECK_THROW(external_dL_dy != nullptr || (target != nullptr && (loss == LossType::L2 || loss == LossType::RelativeL2)));
 	CHECK_THROW(slabs != nullptr && dims >= 1 && dims <= 16);
 	CHECK_THROW(external_dL_dy || (compact_dL_dout != nullptr && compact_L != nullptr));
 	// BASELINE configs 3 in the formats of the grid encoding's training step: the 32x32x16 kernel (k_train_r32.hip), same slabs
 	if (mlp_train_r32_applies(d, n, x_plane_features, data_pdf, external_dL_dy, dims, loss, out, dL_dx, dx_plane_features, dx_record_x, dx_record_dims)) {
-		return mlp_train_r32(stream, d, image, n, x, target, dims, loss, loss_scale, out, compact_dL_dout, compact_L, dL_dx, dx_record_x, slabs, n_params, mlp_train_r32_grid(n));
+		mlp_train_r32(stream, d, image, n, x, target, dims, loss, loss_scale, out, compact_dL_dout, compact_L, dL_dx, dx_record_x, slabs, n_params, mlp_train_r32_grid(n));
+		return mlp_train_r32_name(n);
 	}
 	RegsArgs a{(const half_t*)x, target, data_pdf, (const half_t*)external_dL_dy, (half_t*)out, (half_t*)compact_dL_dout, compact_L, (half_t*)dL_dx, slabs, (const h8*)image,
 	           dx_record_x, n, dims, dx_record_dims, x_plane_features, dx_plane_features, n_params, loss_scale, 1u, nullptr};
@@ -646,10 +660,11 @@ void mlp_train_regs(hipStream_t stream, const MlpDesc& d, const void* image, uin
 #else
 	int timing_left = 0; (void)timing_left;
 #endif
-	if (regs_layout_matches<2, 2>(d)) launch_regs<2, 2>(stream, d, a, grid, loss_id);
-	else if (regs_layout_matches<1, 2>(d)) launch_regs<1, 2>(stream, d, a, grid, loss_id);
-	else if (regs_layout_matches<2, 1>(d)) launch_regs<2, 1>(stream, d, a, grid, loss_id);
-	else launch_regs<1, 1>(stream, d, a, grid, loss_id);
+	const char* name;
+	if (regs_layout_matches<2, 2>(d)) name = launch_regs<2, 2>(stream, d, a, grid, loss_id);
+	else if (regs_layout_matches<1, 2>(d)) name = launch_regs<1, 2>(stream, d, a, grid, loss_id);
+	else if (regs_layout_matches<2, 1>(d)) name = launch_regs<2, 1>(stream, d, a, grid, loss_id);
+	else name = launch_regs<1, 1>(stream, d, a, grid, loss_id);
 	if (a.dbg) {
 		std::vector<unsigned long long> h((size_t)grid * (4 + REGS_NW + 8));
 		HIP_CHECK_THROW(hipMemcpy(h.data(), a.dbg, h.size() * 8, hipMemcpyDeviceToHost));
@@ -685,6 +700,7 @@ void mlp_train_regs(hipStream_t stream, const MlpDesc& d, const void* image, uin
 		}
 		(void)hipFree(a.dbg);
 	}
+	return name;
 }
 
 void mlp_expand_context(hipStream_t stream, uint32_t n, uint32_t dims, const void* compact_dL_dout, const float* compact_L, void* dL_dout, float* L) {

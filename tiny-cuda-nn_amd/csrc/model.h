@@ -1936,6 +1936,7 @@ public:
 	bool live_image_kept() const { return m_live_image_kept; }           // the last fused step's optimizer launch left the live image current
 	void invalidate_live_image() { m_network->invalidate_live_image(); } // the parameters change(d) some other way
 	size_t image_preps() const { return m_image_preps; }                 // k_mlp_prep launches of fused steps so far (a test's view of the above)
+	const char* last_train_kernel() const { return m_last_train_kernel; } // short name of the MLP kernel the last fused step launched (mlp_train_fused)
 	uint64_t scatter_wide_fallbacks() { return m_encoding->scatter_wide_fallbacks(); }
 	uint64_t list_scatters() const override { return m_encoding->list_scatters(); }
 	bool context_keeps_slabs(const ModelContext& c) const { const Ctx* x = dynamic_cast<const Ctx*>(&c); return x && (bool)x->slabs_kept; }
@@ -2051,7 +2052,7 @@ public:
 		}
 		const MlpOneBlobInput oneblob_input{input, m_encoding->input_width(), ctx.oneblob_bins};
 		if (profile) profile->mark(stream, StepProfile::MlpKernel, false);
-		mlp_train_fused(stream, d, image_data, n, ctx.network_input.data(), x_plane_f, target, data_pdf, external_dL_dy, m_network->output_width(), loss, loss_scale, out, dL_dout, L, compact_context,
+		m_last_train_kernel = mlp_train_fused(stream, d, image_data, n, ctx.network_input.data(), x_plane_f, target, data_pdf, external_dL_dy, m_network->output_width(), loss, loss_scale, out, dL_dout, L, compact_context,
 		                dL_dnetwork_input.data(), plane_f, records ? input.data : nullptr, records ? m_encoding->input_width() : 0u, slabs.as<float>(), n_net,
 		                ctx.oneblob_bins ? &oneblob_input : nullptr);
 		if (profile) profile->mark(stream, StepProfile::MlpKernel, true);
@@ -2123,6 +2124,7 @@ public:
 private:
 	bool m_live_image_kept = false;
 	size_t m_image_preps = 0;
+	const char* m_last_train_kernel = "";
 	std::unique_ptr<Encoding> m_encoding;
 	std::unique_ptr<Network> m_network;
 };
@@ -3224,8 +3226,10 @@ public:
 				m_profile.mark(stream, StepProfile::Optimizer, true);
 			} else if (prologue.pending) run_prologue_alone(stream, prologue); // (never: nothing is offered without an optimizer step)
 			m_profile.end_step();
+			m_last_step_kernel = m_model->last_train_kernel();
 			return ctx;
 		} else {
+			m_last_step_kernel = "unfused";
 			ctx = forward(stream, loss_scale, n, input, target, data_pdf, use_inference_params, dL_dinput != nullptr, external_dL_dy);
 			backward(stream, *ctx, n, input, dL_dinput, use_inference_params, mode);
 		}
@@ -3335,6 +3339,8 @@ public:
 	uint64_t scatter_wide_fallbacks() { return m_model->scatter_wide_fallbacks(); }
 	uint64_t list_scatters() const { return m_model->list_scatters(); }
 	size_t prologue_steps() const { return m_prologue_steps; }
+	// short name of the MLP training kernel the last training_step launched ("unfused": k_mlp_fwd -> k_loss -> k_mlp_bwd -> k_wgrad*; "" before the first)
+	const char* last_step_kernel() const { return m_last_step_kernel; }
 	void* param_gradients() const { return m_grads.data(); }
 
 private:
@@ -3345,6 +3351,7 @@ private:
 	DeviceBuf m_params_fp, m_params, m_grads, m_scalar;
 	StepProfile m_profile;
 	size_t m_params_updated_in_flush = 0;
+	const char* m_last_step_kernel = "";
 	bool m_params_exposed = false;
 	void expose_params() {
 		m_params_exposed = true;

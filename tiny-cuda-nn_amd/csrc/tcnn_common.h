@@ -340,9 +340,11 @@ uint32_t mlp_train_fused_grid(const MlpDesc& d, uint32_t n, uint32_t oneblob_bin
 // dx_record_x != nullptr (with dx_plane_features = F): dL_dx is written as 16-byte scatter records {coordinates (dx_record_dims
 // floats, read from dx_record_x [n][dims]), gradient halves}, float4 [in_width / F][n] or, for 2 dims and F = 2, [in_width / 4][n]
 // with two levels per record (mlp_device.h store_dx_record); needs 4 dims + 2 F <= 16.
-void mlp_train_fused(hipStream_t stream, const MlpDesc& d, const void* image, uint32_t n, const void* x, uint32_t x_plane_features, const float* target, const float* data_pdf,
-                     const void* external_dL_dy, uint32_t dims, LossType loss, float loss_scale, void* out, void* dL_dout, float* L, bool compact_context, void* dL_dx,
-                     uint32_t dx_plane_features, const float* dx_record_x, uint32_t dx_record_dims, float* slabs, uint32_t n_params, const MlpOneBlobInput* oneblob = nullptr);
+// Returns the launched kernel's short name, a static string (Trainer::last_step_kernel): "r32", "r32a", "r32w", "r32ob", "regs_fast",
+// "regs", "train<W,NB,NW,MAXT>/relu|act", "train_pw28|train_pw32|train_regw|train_ob/relu|act" (act: the activation chosen at run time).
+const char* mlp_train_fused(hipStream_t stream, const MlpDesc& d, const void* image, uint32_t n, const void* x, uint32_t x_plane_features, const float* target, const float* data_pdf,
+                            const void* external_dL_dy, uint32_t dims, LossType loss, float loss_scale, void* out, void* dL_dout, float* L, bool compact_context, void* dL_dx,
+                            uint32_t dx_plane_features, const float* dx_record_x, uint32_t dx_record_dims, float* slabs, uint32_t n_params, const MlpOneBlobInput* oneblob = nullptr);
 // oneblob (optional; x is then not read): the network's input is the OneBlob encoding of these coordinates, evaluated inside the kernel
 // (mlp_train_fused_oneblob_supported says whether this network / batch has such a kernel)
 bool mlp_train_fused_oneblob_supported(const MlpDesc& d, uint32_t n, uint32_t n_bins);
@@ -352,15 +354,16 @@ bool mlp_train_fused_oneblob_supported(const MlpDesc& d, uint32_t n, uint32_t n_
 // stores are zeros); mlp_expand_context produces the reference's [n][16] matrices from them.  Requires slabs != nullptr.
 bool mlp_train_regs_supported(const MlpDesc& d, uint32_t n);
 uint32_t mlp_train_regs_grid(const MlpDesc& d, uint32_t n);
-void mlp_train_regs(hipStream_t stream, const MlpDesc& d, const void* image, uint32_t n, const void* x, uint32_t x_plane_features, const float* target, const float* data_pdf,
-                    const void* external_dL_dy, uint32_t dims, LossType loss, float loss_scale, void* out, void* compact_dL_dout, float* compact_L, void* dL_dx,
-                    uint32_t dx_plane_features, const float* dx_record_x, uint32_t dx_record_dims, float* slabs, uint32_t n_params);
+const char* mlp_train_regs(hipStream_t stream, const MlpDesc& d, const void* image, uint32_t n, const void* x, uint32_t x_plane_features, const float* target, const float* data_pdf,
+                           const void* external_dL_dy, uint32_t dims, LossType loss, float loss_scale, void* out, void* compact_dL_dout, float* compact_L, void* dL_dx,
+                           uint32_t dx_plane_features, const float* dx_record_x, uint32_t dx_record_dims, float* slabs, uint32_t n_params); // the kernel's name, as mlp_train_fused
 // ---- the same step for 32 -> 64 -> 64 -> 16 networks fed by a 2-D grid encoding with 2 features per level, on the 32x32x16 matrix
 // instruction (k_train_r32.hip): 32 samples per wave and trip, operands of the weight-gradient products transposed through wave-private
 // LDS images.  mlp_train_regs dispatches to it (TCNN_AMD_MLP_R32=0: never); `grid` workgroups write one slab each.
 bool mlp_train_r32_applies(const MlpDesc& d, uint32_t n, uint32_t x_plane_features, const float* data_pdf, const void* external_dL_dy, uint32_t dims, LossType loss, const void* out,
                            const void* dL_dx, uint32_t dx_plane_features, const float* dx_record_x, uint32_t dx_record_dims);
 uint32_t mlp_train_r32_grid(uint32_t n); // workgroups (= slabs) of the launch: the caller sizes `slabs` with it
+const char* mlp_train_r32_name(uint32_t n); // "r32a" or "r32": which of the two kernels mlp_train_r32 launches for this batch
 void mlp_train_r32(hipStream_t stream, const MlpDesc& d, const void* image, uint32_t n, const void* x, const float* target, uint32_t dims, LossType loss, float loss_scale, void* out,
                    void* compact_dL_dout, float* compact_L, void* dL_dx, const float* dx_record_x, float* slabs, uint32_t n_params, uint32_t grid);
 // ---- BASELINE config 2's step, OneBlob(64 bins, 2 dims) -> 64 -> 64 -> 16 with the encoding evaluated in the kernel, on the 32x32x16

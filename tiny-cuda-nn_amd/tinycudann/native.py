@@ -112,6 +112,11 @@ class Trainer:
         """backward passes of the grid encoding that ran the list-fed gradient kernel (tcnn_amd.h: tcnn_trainer_list_scatters)"""
         return int(_C.lib.tcnn_trainer_list_scatters(self._h))
 
+    def last_step_kernel(self):
+        """short name of the MLP training kernel the last training_step launched, e.g. "r32", "regs", "train<64,1,8,8>/act" or "unfused"
+        (tcnn_amd.h: tcnn_trainer_last_step_kernel)"""
+        return _C.lib.tcnn_trainer_last_step_kernel(self._h).decode()
+
     def context_keeps_slabs(self, ctx):
         """whether `ctx` owns the weight-gradient slabs the optimizer's launch reduces (tcnn_amd.h: tcnn_train_ctx_keeps_weight_gradient_slabs)"""
         return bool(_C.lib.tcnn_train_ctx_keeps_weight_gradient_slabs(self._h, ctx._h))
