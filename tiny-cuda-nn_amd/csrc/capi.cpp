@@ -97,6 +97,7 @@ void switches_reload() {
 	w.mlp_regs = !env_is("TCNN_AMD_MLP_REGS", '0');
 	w.mlp_fast = !env_is("TCNN_AMD_MLP_FAST", '0');
 	if (const char* e = getenv("TCNN_AMD_MLP_PRIO")) w.mlp_prio = (uint32_t)atoi(e);
+	w.mlp_layerwise = env_is("TCNN_AMD_MLP_LAYERWISE", '1');
 	std::lock_guard<std::mutex> lock{g_switches_mutex};
 	g_switches = w;
 }

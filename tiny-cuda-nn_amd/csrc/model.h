@@ -1463,7 +1463,7 @@ inline std::unique_ptr<Encoding> create_encoding(uint32_t n_dims_to_encode, cons
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// Network: FullyFusedMLP (and CutlassMLP configs that the fused kernels cover; identical math)
+// Network: FullyFusedMLP and CutlassMLP (identical math): the fused kernels where they cover the shape, else layer by layer
 // ------------------------------------------------------------------------------------------------------------------
 inline Activation string_to_activation(const std::string& s) {
 	static const std::pair<const char*, Activation> table[] = {
@@ -1480,6 +1480,7 @@ inline const char* to_string(Activation a) {
 
 struct NetworkContext {
 	ArenaBuf hidden; // half [n_hidden][n][width]
+	ArenaBuf pre;    // layer-by-layer Sine networks: the hidden layers' pre-activations, laid out as `hidden` (cutlass_mlp.cu:53)
 };
 
 class Network {
@@ -1498,15 +1499,25 @@ public:
 		m_n_hidden = net.value("n_hidden_layers", 5u);
 		m_activation = string_to_activation(net.value("activation", "ReLU"));
 		m_output_activation = string_to_activation(net.value("output_activation", "None"));
-		// fully_fused_mlp.cu:869-881 restricts FullyFusedMLP to these widths; CutlassMLP (cutlass_mlp.cu:39-92) takes any -- here: 256 as well
-		const bool width_ok = m_width == 16 || m_width == 32 || m_width == 64 || m_width == 128 || (cutlass && m_width == 256);
-		if (!width_ok) {
-			throw std::runtime_error{"FullyFusedMLP only supports 16, 32, 64, and 128 neurons, but got " + std::to_string(m_width) + ". (CutlassMLP: also 256; other widths are not provided by this build.)"};
+		// fully_fused_mlp.cu:869-881 restricts FullyFusedMLP to these widths; the fused kernels also cover CutlassMLP at 256
+		const bool fused_width = m_width == 16 || m_width == 32 || m_width == 64 || m_width == 128 || (cutlass && m_width == 256);
+		if (cutlass) {
+			// CutlassMLP (cutlass_mlp.cu:39-92) takes any width; here multiples of REQUIRED_ALIGNMENT up to 1024 (cutlass_mlp.h:115-121),
+			// zero hidden layers and Sine -- the shapes the fused kernels do not cover run layer by layer (k_mlp_layers.hip)
+			if (m_width % REQUIRED_ALIGNMENT != 0 || m_width < 16 || m_width > 1024) {
+				throw std::runtime_error{"CutlassMLP: n_neurons must be a multiple of 16 between 16 and 1024, but got " + std::to_string(m_width) + "."};
+			}
+			m_layerwise = !fused_width || m_n_hidden == 0 || m_activation == Activation::Sine;
+		} else {
+			if (!fused_width) {
+				throw std::runtime_error{"FullyFusedMLP only supports 16, 32, 64, and 128 neurons, but got " + std::to_string(m_width) + ". (CutlassMLP: any multiple of 16 up to 1024.)"};
+			}
+			if (m_n_hidden <= 0) throw std::runtime_error{"FullyFusedMLP requires at least 1 hidden layer (3 layers in total)."};
+			if (m_activation == Activation::Sine) throw std::runtime_error{"FullyFusedMLP: Sine activation is not supported in the fused kernels"};
 		}
-		if (m_n_hidden <= 0) throw std::runtime_error{"FullyFusedMLP requires at least 1 hidden layer (3 layers in total)."};
 		if (m_n_hidden + 1 > MAX_MLP_LAYERS) throw std::runtime_error{"MLP: too many layers for this build"};
-		if (m_activation == Activation::Sine) throw std::runtime_error{"FullyFusedMLP: Sine activation is not supported in the fused kernels"};
 		if (m_input_width % 16 != 0) throw std::runtime_error{"MLP: input width must be a multiple of 16"};
+		m_layerwise = m_layerwise || switches().mlp_layerwise; // TCNN_AMD_MLP_LAYERWISE=1: the A/B form for any shape
 		m_padded_output_width = next_multiple(m_output_width, REQUIRED_ALIGNMENT);
 
 		// matrices: fully_fused_mlp.cu:659-671
@@ -1533,11 +1544,17 @@ public:
 			b_off += (L.cols / 16) * L.ks_bwd;
 			w_off += L.rows * L.cols;
 		}
-		m_desc.n_frags_fwd = f_off;
-		m_desc.n_frags_bwd = b_off;
-		m_desc.n_frags_r32 = r32_shape_ok(m_desc) ? R32Frags(m_desc).n_frags() : 0u;
+		// (the layer-by-layer path reads the parameters as they are: no fragment images)
+		m_desc.n_frags_fwd = m_layerwise ? 0u : f_off;
+		m_desc.n_frags_bwd = m_layerwise ? 0u : b_off;
+		m_desc.n_frags_r32 = !m_layerwise && r32_shape_ok(m_desc) ? R32Frags(m_desc).n_frags() : 0u;
 		m_n_params = w_off;
 	}
+
+	// the network runs layer by layer (k_mlp_layers.hip) instead of the fused kernels: CutlassMLP shapes they do not cover, or
+	// TCNN_AMD_MLP_LAYERWISE=1 when the model was created.  Fragment images, fused input / output forms and the fused training step
+	// are then never used.
+	bool layerwise() const { return m_layerwise; }
 
 	uint32_t input_width() const { return m_input_width; }
 	uint32_t output_width() const { return m_output_width; }
@@ -1557,7 +1574,10 @@ public:
 		std::vector<float> host(m_n_params);
 		for (uint32_t l = 0; l < m_desc.n_layers; ++l) {
 			const MlpLayer& L = m_desc.layers[l];
-			const float s = scale * std::sqrt(6.0f / (float)(L.cols + L.rows));
+			// Sine: SIREN (cutlass_mlp.cu:360-366, gpu_matrix.h:335-369) -- U(+-30 scale / fan_in) for the first matrix, U(+-scale sqrt(6 / fan_in))
+			// for the others; else Xavier over fan_in + fan_out
+			const float s = m_activation != Activation::Sine ? scale * std::sqrt(6.0f / (float)(L.cols + L.rows))
+			                : l == 0 ? scale * (30.0f / (float)L.cols) : scale * std::sqrt(6.0f / (float)L.cols);
 			float* w = host.data() + L.w_off;
 			for (size_t i = 0; i < (size_t)L.rows * L.cols; ++i) w[i] = rng.next_float() * 2.0f * s - s;
 		}
@@ -1575,6 +1595,7 @@ public:
 	};
 	// nullptr: a weight of this network sits in more than IMAGE_INV_WIDTH image elements (no supported shape does)
 	LiveImage* live_image() const {
+		if (m_layerwise) return nullptr;
 		if (m_live_state == 0) {
 			const uint32_t total = (m_desc.n_frags_fwd + m_desc.n_frags_bwd + m_desc.n_frags_r32) * 512;
 			std::vector<uint32_t> inv(m_n_params * IMAGE_INV_WIDTH, 0xffffffffu), count(m_n_params, 0);
@@ -1597,17 +1618,25 @@ public:
 
 	// images: [fwd][bwd] fragment images of `params`
 	ArenaBuf prepare(hipStream_t stream, const void* params, bool want_bwd) const {
+		if (m_layerwise) throw std::runtime_error{"Network::prepare: a layer-by-layer network has no fragment images"};
 		ArenaBuf image{stream, mlp_image_bytes(m_desc)};
 		mlp_prepare_weights(stream, m_desc, params, image.data(), want_bwd);
 		return image;
 	}
 
 	void inference(hipStream_t stream, uint32_t n, const void* input, void* output, const void* params) const {
+		if (m_layerwise) return forward_layers(stream, n, input, output, params, nullptr, nullptr);
 		ArenaBuf image = prepare(stream, params, false);
 		mlp_forward(stream, m_desc, image.data(), n, input, output, nullptr);
 	}
-	// inference with the input / output conversions fused into the kernel (see MlpIo)
+	// inference with the input / output conversions fused into the kernel (see MlpIo); the layer-by-layer path takes the plain form only
 	void inference_io(hipStream_t stream, uint32_t n, const MlpIo& io, const void* params) const {
+		if (m_layerwise) {
+			if (!io.x_half || io.x_plane_features || io.x_f32.data || io.x_oneblob_bins || !io.out_half || io.out_f32.data) {
+				throw std::runtime_error{"Network::inference_io: a layer-by-layer network takes a half input matrix and writes a half output matrix"};
+			}
+			return forward_layers(stream, n, io.x_half, io.out_half, params, nullptr, nullptr);
+		}
 		ArenaBuf image = prepare(stream, params, false);
 		mlp_forward_io(stream, m_desc, image.data(), n, io, nullptr);
 	}
@@ -1615,6 +1644,11 @@ public:
 	NetworkContext forward(hipStream_t stream, uint32_t n, const void* input, void* output, const void* params) const {
 		NetworkContext ctx;
 		ctx.hidden = ArenaBuf{stream, (size_t)m_n_hidden * n * m_width * 2};
+		if (m_layerwise) {
+			if (m_activation == Activation::Sine) ctx.pre = ArenaBuf{stream, (size_t)m_n_hidden * n * m_width * 2};
+			forward_layers(stream, n, input, output, params, ctx.hidden.data(), ctx.pre.data());
+			return ctx;
+		}
 		ArenaBuf image = prepare(stream, params, false);
 		mlp_forward(stream, m_desc, image.data(), n, input, output, ctx.hidden.data());
 		return ctx;
@@ -1623,8 +1657,6 @@ public:
 	// dL_dinput: optional half [n][in_width]; gradients: half[n_params] or nullptr
 	void backward(hipStream_t stream, const NetworkContext& ctx, uint32_t n, const void* input, const void* output, const void* dL_doutput,
 	              void* dL_dinput, const void* params, void* gradients, GradientMode mode, uint32_t dx_plane_features = 0) const {
-		ArenaBuf image = prepare(stream, params, true);
-		ArenaBuf dhidden{stream, (size_t)m_n_hidden * n * m_width * 2};
 		// output-activation transfer, computed once up front like the reference (fully_fused_mlp.cu:757-762)
 		const void* dY = dL_doutput;
 		ArenaBuf dY_tmp;
@@ -1635,6 +1667,12 @@ public:
 			dY = dY_tmp.data();
 			desc.output_activation = (uint32_t)Activation::None;
 		}
+		if (m_layerwise) {
+			if (dx_plane_features) throw std::runtime_error{"Network::backward: a layer-by-layer network writes dL/dinput as a matrix, not as level planes"};
+			return backward_layers(stream, ctx, n, input, dY, dL_dinput, params, gradients, mode);
+		}
+		ArenaBuf image = prepare(stream, params, true);
+		ArenaBuf dhidden{stream, (size_t)m_n_hidden * n * m_width * 2};
 		mlp_backward(stream, desc, image.data(), n, dY, output, ctx.hidden.data(), dhidden.data(), dL_dinput, dx_plane_features);
 		if (mode == GradientMode::Ignore) return;
 		CHECK_THROW(gradients != nullptr);
@@ -1675,7 +1713,83 @@ public:
 	}
 
 private:
+	// ---- the layer-by-layer path (cutlass_mlp.cu:140-300): activations [n][width] half in memory, one GEMM launch per layer
+	uint32_t layer_act(uint32_t l) const { return (uint32_t)(l == m_desc.n_layers - 1 ? m_output_activation : m_activation); }
+	uint32_t layer_ld(uint32_t l) const { return l == m_desc.n_layers - 1 ? m_padded_output_width : m_width; } // of the layer's output
+
+	// hidden: [n_hidden][n][width] post-activations (nullptr: inference, two rotating buffers); pre: the same for the pre-activations (Sine)
+	void forward_layers(hipStream_t stream, uint32_t n, const void* input, void* output, const void* params, void* hidden, void* pre) const {
+		const size_t hstride = (size_t)n * m_width;
+		ArenaBuf rotate;
+		if (!hidden && m_n_hidden > 0) rotate = ArenaBuf{stream, std::min<size_t>(m_n_hidden, 2) * hstride * 2};
+		const _Float16* in = (const _Float16*)input;
+		uint32_t ldi = m_input_width;
+		for (uint32_t l = 0; l < m_desc.n_layers; ++l) {
+			const MlpLayer& L = m_desc.layers[l];
+			const bool last = l == m_desc.n_layers - 1;
+			_Float16* out = last ? (_Float16*)output : hidden ? (_Float16*)hidden + hstride * l : rotate.as<_Float16>() + hstride * (l & 1);
+			_Float16* p = !last && pre ? (_Float16*)pre + hstride * l : nullptr;
+			mlp_layer_forward(stream, n, in, ldi, (const _Float16*)params + L.w_off, L.rows, L.cols, layer_act(l), out, layer_ld(l), p);
+			in = out;
+			ldi = m_width;
+		}
+	}
+
+	void backward_layers(hipStream_t stream, const NetworkContext& ctx, uint32_t n, const void* input, const void* dY, void* dL_dinput, const void* params, void* gradients,
+	                     GradientMode mode) const {
+		const size_t hstride = (size_t)n * m_width;
+		const bool sine = m_activation == Activation::Sine;
+		const _Float16* hidden = ctx.hidden.as<_Float16>();
+		const _Float16* aux = sine ? ctx.pre.as<_Float16>() : hidden; // what act' reads: cos of the pre-activation for Sine, else the output
+		ArenaBuf dhidden{stream, (size_t)m_n_hidden * hstride * 2};
+		// W^T of every layer that passes a gradient on: layer 0 only when dL/dinput is wanted
+		ArenaBuf wt{stream, m_n_params * 2};
+		const _Float16* p = (const _Float16*)params;
+		for (uint32_t l = dL_dinput ? 0 : 1; l < m_desc.n_layers; ++l) {
+			const MlpLayer& L = m_desc.layers[l];
+			mlp_layer_transpose(stream, L.rows, L.cols, p + L.w_off, wt.as<_Float16>() + L.w_off);
+		}
+		for (uint32_t l = m_desc.n_layers; l-- > 0;) {
+			const MlpLayer& L = m_desc.layers[l];
+			const _Float16* dO = l == m_desc.n_layers - 1 ? (const _Float16*)dY : dhidden.as<_Float16>() + hstride * l;
+			const uint32_t ldo = layer_ld(l);
+			if (l > 0) { // dL/d(hidden l - 1), through the derivative of its activation
+				mlp_layer_backward(stream, n, dO, ldo, wt.as<_Float16>() + L.w_off, L.rows, L.cols, (uint32_t)m_activation, aux + hstride * (l - 1),
+				                   dhidden.as<_Float16>() + hstride * (l - 1), m_width);
+			} else if (dL_dinput) {
+				mlp_layer_backward(stream, n, dO, ldo, wt.as<_Float16>() + L.w_off, L.rows, L.cols, (uint32_t)Activation::None, nullptr, dL_dinput, m_input_width);
+			}
+		}
+		if (mode == GradientMode::Ignore) return;
+		CHECK_THROW(gradients != nullptr);
+		// weight gradients: mlp_wgrad_panels on the row-major buffers, panels of at most 128 x 128, launched in groups whose fp32 slabs
+		// fit a bounded workspace (a 1024-wide layer is 64 panels of up to 256 slabs each; the groups run in stream order and share it)
+		std::vector<WgradPanel> panels;
+		for (uint32_t l = 0; l < m_desc.n_layers; ++l) {
+			const MlpLayer& L = m_desc.layers[l];
+			const _Float16* dO = l == m_desc.n_layers - 1 ? (const _Float16*)dY : dhidden.as<_Float16>() + hstride * l;
+			const _Float16* In = l == 0 ? (const _Float16*)input : hidden + hstride * (l - 1);
+			const uint32_t ldo = layer_ld(l), ldi = l == 0 ? m_input_width : m_width;
+			_Float16* g = (_Float16*)gradients + L.w_off;
+			for (uint32_t r0 = 0; r0 < L.rows; r0 += 128)
+				for (uint32_t c0 = 0; c0 < L.cols; c0 += 128)
+					panels.push_back(WgradPanel{dO + r0, ldo, std::min(128u, L.rows - r0), In + c0, ldi, std::min(128u, L.cols - c0), g + (size_t)r0 * L.cols + c0, L.cols, false, false});
+		}
+		constexpr size_t WORKSPACE_FLOATS = (size_t)64 << 20; // 256 MB
+		size_t max_floats = 0;
+		for (const WgradPanel& q : panels) max_floats = std::max(max_floats, wgrad_panels_workspace_floats(&q, 1, n));
+		ArenaBuf ws{stream, std::max(max_floats, std::min(WORKSPACE_FLOATS, wgrad_panels_workspace_floats(panels.data(), (uint32_t)panels.size(), n))) * sizeof(float)};
+		const size_t ws_floats = ws.bytes() / sizeof(float);
+		for (size_t i = 0; i < panels.size();) {
+			size_t j = i, floats = 0;
+			while (j < panels.size() && floats + wgrad_panels_workspace_floats(&panels[j], 1, n) <= ws_floats) floats += wgrad_panels_workspace_floats(&panels[j++], 1, n);
+			mlp_wgrad_panels(stream, n, panels.data() + i, (uint32_t)(j - i), mode == GradientMode::Accumulate, ws.as<float>());
+			i = j;
+		}
+	}
+
 	bool m_fully_fused;
+	bool m_layerwise = false;
 	uint32_t m_input_width, m_output_width, m_padded_output_width, m_width, m_n_hidden;
 	Activation m_activation, m_output_activation;
 	MlpDesc m_desc;
@@ -1829,6 +1943,14 @@ public:
 		check_batch(n);
 		if (n == 0) return;
 		const _Float16* p = (const _Float16*)params;
+		if (m_network->layerwise()) { // no fused input or output forms: the encoding's own kernel writes the batch, a trim casts the output
+			ArenaBuf network_input{stream, (size_t)n * m_encoding->padded_output_width() * 2}, out_tmp;
+			m_encoding->forward(stream, n, input, p + m_network->n_params(), network_input.data(), false, false);
+			if (!output_half) out_tmp = ArenaBuf{stream, (size_t)n * m_network->padded_output_width() * 2};
+			m_network->inference(stream, n, network_input.data(), output_half ? output_half : out_tmp.data(), p);
+			if (output_f32) trim_and_cast(stream, false, n, m_network->padded_output_width(), m_network->output_width(), output_half ? output_half : out_tmp.data(), *output_f32);
+			return;
+		}
 		MlpIo io{};
 		io.out_half = output_half;
 		if (output_f32) {
@@ -1915,7 +2037,7 @@ public:
 			dL_dnetwork_input = ArenaBuf{stream, (size_t)n * m_encoding->padded_output_width() * 2};
 		}
 		// the grid scatter reads dL/d(encoding) with unit stride when the MLP writes it as level planes
-		const uint32_t plane_f = dL_dnetwork_input ? m_encoding->level_plane_features(dL_dinput != nullptr, mode) : 0;
+		const uint32_t plane_f = dL_dnetwork_input && !m_network->layerwise() ? m_encoding->level_plane_features(dL_dinput != nullptr, mode) : 0;
 		m_network->backward(stream, ctx.network_ctx, n, ctx.network_input.data(), output, dL_doutput, dL_dnetwork_input.data(), p, g, mode, plane_f);
 		if (dL_dnetwork_input) {
 			m_encoding->backward(stream, ctx.encoding_ctx, n, input, dL_dnetwork_input.data(), dL_dinput, p + m_network->n_params(),
@@ -1927,7 +2049,7 @@ public:
 	static bool use_fused_step() { return switches().fused_step; }
 	// TCNN_AMD_SIDE_JOBS=0: k_mlp_prep stays a launch of its own (A/B runs; read per step so that tests cover both)
 	static bool side_jobs_enabled() { return switches().side_jobs; }
-	bool fused_step_supported(uint32_t n) const { return use_fused_step() && mlp_train_fused_supported(m_network->desc(), n); }
+	bool fused_step_supported(uint32_t n) const { return use_fused_step() && !m_network->layerwise() && mlp_train_fused_supported(m_network->desc(), n); }
 	// the fused step of a model without encoding parameters hands its weight gradients to the optimizer inside the slab reduction
 	bool optimizer_rides_on_reduce() const { return m_encoding->n_params() == 0; }
 	// TCNN_AMD_LIVE_IMAGE=0: every step builds its fragment images with k_mlp_prep again instead of keeping one current (Network::live_image;
@@ -1942,6 +2064,7 @@ public:
 	bool context_keeps_slabs(const ModelContext& c) const { const Ctx* x = dynamic_cast<const Ctx*>(&c); return x && (bool)x->slabs_kept; }
 	// the register-resident fused kernel (k_train_regs.hip) writes dL_doutput / L as compact [n][dims] matrices (TrainContext::compact)
 	bool fused_compact_context_supported(uint32_t n) const {
+		if (m_network->layerwise()) return false;
 		const bool ok = use_fused_step() && mlp_train_regs_supported(m_network->desc(), n) && m_network->padded_output_width() == 16;
 		// the register-resident kernels address [n][...] matrices with 32-bit byte offsets: beyond 2^22 rows the step silently took the
 		// much slower LDS-image kernel -- say so once (a caller can split the batch)
@@ -1980,6 +2103,7 @@ public:
 	void fused_encode(hipStream_t stream, Ctx& ctx, uint32_t n, MatView input, const void* params, bool prepare_input_gradients, bool prepare_param_gradients, bool prep_image = false) {
 		const _Float16* p = (const _Float16*)params;
 		const uint32_t n_net = (uint32_t)m_network->n_params();
+		if (m_network->layerwise()) throw std::runtime_error{"NetworkWithInputEncoding::fused_encode: a layer-by-layer network has no fused training step"};
 		// a OneBlob encoding is evaluated by the MLP kernels inside their input load where they can (k_mlp.hip, k_train.hip)
 		if (!prepare_input_gradients && m_encoding->as_oneblob() && m_encoding->padded_output_width() == m_network->input_width() &&
 		    mlp_train_fused_oneblob_supported(m_network->desc(), n, m_encoding->as_oneblob())) {

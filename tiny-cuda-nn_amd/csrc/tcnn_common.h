@@ -62,6 +62,7 @@ struct Switches {
 	bool mlp_regs = true;         // TCNN_AMD_MLP_REGS=0: the LDS-image kernels of k_train.hip
 	bool mlp_fast = true;         // TCNN_AMD_MLP_FAST=0: k_mlp_train_regs with run-time formats
 	uint32_t mlp_prio = 1;        // TCNN_AMD_MLP_PRIO: wave priorities of the MLP kernels (0 none, 1 alternating per trip, 2, 3)
+	bool mlp_layerwise = false;   // TCNN_AMD_MLP_LAYERWISE=1: every network of a model created now runs the layer-by-layer kernels (k_mlp_layers.hip)
 };
 Switches switches(); // a copy of the process-wide set, taken under its lock
 void switches_reload();
@@ -398,6 +399,16 @@ size_t wgrad_panels_workspace_floats(const WgradPanel* panels, uint32_t count, u
 void mlp_wgrad_panels(hipStream_t stream, uint32_t n, const WgradPanel* panels, uint32_t count, bool accumulate, float* workspace);
 void mlp_wgrad(hipStream_t stream, uint32_t n, const void* dO, uint32_t ldo, uint32_t rows, const void* In, uint32_t ldi, uint32_t cols,
                void* grad_half, uint32_t ldg, bool accumulate, float* workspace);
+// ---- the layer-by-layer path (k_mlp_layers.hip; Network::layerwise): one GEMM per layer on row-major half matrices, n % 256 == 0,
+// rows / cols multiples of 16, leading dimensions multiples of 8 (x) and 4 (y).
+// forward: y[s][r] = act((half) sum_c x[s][c] w[r][c]) for r < rows; w [rows][cols]; pre (optional): the half pre-activation, laid out as y
+void mlp_layer_forward(hipStream_t stream, uint32_t n, const void* x, uint32_t ldx, const void* w, uint32_t rows, uint32_t cols, uint32_t activation, void* y, uint32_t ldy,
+                       void* pre);
+// backward data: dL_din[s][c] = act'((half) sum_r dL_dout[s][r] w[r][c]) for c < cols, from wt = w^T [cols][rows] (mlp_layer_transpose);
+// aux (laid out as dL_din): the forward output of the layer that produced the input -- its pre-activation for Sine; activation None: unused
+void mlp_layer_backward(hipStream_t stream, uint32_t n, const void* dL_dout, uint32_t ldo, const void* wt, uint32_t rows, uint32_t cols, uint32_t activation, const void* aux,
+                        void* dL_din, uint32_t ldi);
+void mlp_layer_transpose(hipStream_t stream, uint32_t rows, uint32_t cols, const void* w, void* wt); // wt [cols][rows] = w [rows][cols]^T
 
 // ------------------------------------------------------------------------------------------------------------------
 // loss / reduction / optimizer / init plumbing
