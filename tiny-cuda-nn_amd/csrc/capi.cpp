@@ -215,14 +215,21 @@ int tcnn_module_backward(tcnn_module_t m, tcnn_stream_t stream, tcnn_context_t c
 
 int tcnn_module_backward_backward_input(tcnn_module_t m, tcnn_stream_t stream, tcnn_context_t ctx, uint32_t n, const float* dL_ddLdinput, const float* input, const void* dL_doutput,
                                         void* dL_dparams, void* dL_ddLdoutput, float* dL_dinput, const void* params) {
+	return tcnn_module_backward_backward_input_mode(m, stream, ctx, n, dL_ddLdinput, input, dL_doutput, dL_dparams, dL_ddLdoutput, dL_dinput, params,
+	                                                dL_dparams ? TCNN_GRADIENT_OVERWRITE : TCNN_GRADIENT_IGNORE);
+}
+
+int tcnn_module_backward_backward_input_mode(tcnn_module_t m, tcnn_stream_t stream, tcnn_context_t ctx, uint32_t n, const float* dL_ddLdinput, const float* input, const void* dL_doutput,
+                                             void* dL_dparams, void* dL_ddLdoutput, float* dL_dinput, const void* params, int gradient_mode) {
 	return guarded([&] { // cpp_api.cu:111-127
+		CHECK_THROW(gradient_mode == TCNN_GRADIENT_IGNORE || ((gradient_mode == TCNN_GRADIENT_OVERWRITE || gradient_mode == TCNN_GRADIENT_ACCUMULATE) && dL_dparams != nullptr));
 		CHECK_THROW(m && m->model);
 		if (!ctx || !ctx->ctx) throw std::runtime_error{"Module::bwd_bwd_input: called with invalid context. fwd likely (mistakenly) ran in inference mode."};
 		CHECK_THROW(dL_ddLdinput != nullptr && input != nullptr);
 		const uint32_t w = m->model->input_width();
 		MatViewMut dx{dL_dinput, w, 1u};
 		m->model->backward_backward_input((hipStream_t)stream, *ctx->ctx, n, MatView{input, w, 1u}, MatView{dL_ddLdinput, w, 1u}, dL_doutput, dL_ddLdoutput, dL_dinput ? &dx : nullptr, params,
-		                                  dL_dparams, dL_dparams ? GradientMode::Overwrite : GradientMode::Ignore);
+		                                  gradient_mode == TCNN_GRADIENT_IGNORE ? nullptr : dL_dparams, (GradientMode)gradient_mode);
 	});
 }
 

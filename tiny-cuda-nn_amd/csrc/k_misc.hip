@@ -192,6 +192,15 @@ __global__ void __launch_bounds__(256) k_identity_bwd_input(const uint32_t n, co
 	dL_dx.data[(size_t)i * dL_dx.stride_sample + (size_t)j * dL_dx.stride_dim] = (float)(T)((float)dL_dy[(size_t)i * dy_stride + j] * scale);
 }
 
+template <typename T>
+__global__ void __launch_bounds__(256) k_identity_bwd_bwd_input(const uint32_t n, const uint32_t n_dims, const float scale, const MatView dL_ddLdx, T* __restrict__ dL_ddLdy, const uint32_t dy_stride) {
+	const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
+	const uint32_t i = gid / dy_stride;
+	if (i >= n) return;
+	const uint32_t j = gid - i * dy_stride;
+	dL_ddLdy[gid] = j >= n_dims ? (T)0.0f : (T)(dL_ddLdx.data[(size_t)i * dL_ddLdx.stride_sample + (size_t)j * dL_ddLdx.stride_dim] * scale);
+}
+
 // ---- loss: l2.h:40-74 / relative_l2.h:40-75 and the other element-wise losses.  One element: the reference's expressions, term for term.
 // (row: the sample's padded prediction row -- RelativeL2Luminance reads the pixel's other channels from it)
 __device__ inline void loss_element(const uint32_t type, const float prediction, const float target, const float pdf, const uint32_t n_total, const float loss_scale,
@@ -608,6 +617,14 @@ void identity_backward_input(hipStream_t stream, bool fp32, uint32_t n, uint32_t
 	if (total == 0) return;
 	if (fp32) hipLaunchKernelGGL(k_identity_bwd_input<float>, dim3(blocks_for(total, 256)), dim3(256), 0, stream, n, n_dims, scale, (const float*)dL_dy, dy_stride, dL_dx);
 	else hipLaunchKernelGGL(k_identity_bwd_input<half_t>, dim3(blocks_for(total, 256)), dim3(256), 0, stream, n, n_dims, scale, (const half_t*)dL_dy, dy_stride, dL_dx);
+}
+
+void identity_backward_backward_input(hipStream_t stream, bool fp32, uint32_t n, uint32_t n_dims, float scale, MatView dL_ddLdx, void* dL_ddLdy, uint32_t dy_stride) {
+	const uint64_t total = (uint64_t)n * dy_stride;
+	if (total == 0) return;
+	CHECK_THROW(total < (1ull << 32));
+	if (fp32) hipLaunchKernelGGL(k_identity_bwd_bwd_input<float>, dim3(blocks_for(total, 256)), dim3(256), 0, stream, n, n_dims, scale, dL_ddLdx, (float*)dL_ddLdy, dy_stride);
+	else hipLaunchKernelGGL(k_identity_bwd_bwd_input<half_t>, dim3(blocks_for(total, 256)), dim3(256), 0, stream, n, n_dims, scale, dL_ddLdx, (half_t*)dL_ddLdy, dy_stride);
 }
 
 void loss_evaluate(hipStream_t stream, LossType type, uint32_t n, uint32_t stride, uint32_t dims, float loss_scale,

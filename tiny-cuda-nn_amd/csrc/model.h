@@ -258,11 +258,15 @@ public:
 	// dL_dy [n][padded] T; grads: T[n_params] or nullptr (Ignore)
 	// dy_planes: dL_dy is laid out as level planes [padded / F][n][F] (only if level_plane_features() allowed it), else AoS
 	virtual void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes) = 0;
-	// second-order input gradients (object.h:278-288); the grid encoding (grid.h:902-1026) and PPNG3 (ppng_3.h:609-676) provide them
+	// second-order input gradients (object.h:278-288); the grid encoding (grid.h:902-1026), PPNG3 (ppng_3.h:609-676) and Identity provide them
 	virtual void backward_backward_input(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, MatView dL_ddLdx, const void* dL_dy, void* dL_ddLdy,
 	                                     MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode) {
 		throw std::runtime_error{"DifferentiableObject::backward_backward_input_impl: not implemented error"};
 	}
+	// false: backward_backward_input() throws the error above.  A model that puts more passes around the encoding's asks first, so that
+	// the error comes before anything of its own is allocated or launched (NetworkWithInputEncoding).
+	virtual bool has_second_order() const { return false; }
+	virtual bool second_order_reads_dL_dy() const { return true; } // false: backward_backward_input() needs no dL_dy (dL/dx is linear in x)
 	// > 0: this encoding's backward prefers dL_dy in level planes with that many features per plane (see k_grid_bwd_lds)
 	virtual uint32_t level_plane_features(bool need_dL_dx, GradientMode mode) const { return 0; }
 	// true: the encoding is half(x * scale + offset) padded with ones -- cheap enough to apply inside the consumer's load
@@ -645,6 +649,7 @@ public:
 	}
 
 	// grid.h:902-1026
+	bool has_second_order() const override { return true; }
 	void backward_backward_input(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, MatView dL_ddLdx, const void* dL_dy, void* dL_ddLdy,
 	                             MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode) override {
 		if ((!dL_ddLdy && mode == GradientMode::Ignore && !dL_dx) || padded_output_width() == 0 || n == 0) return;
@@ -1068,6 +1073,7 @@ public:
 		                                                   padded_output_width(), scratch, grads, mode == GradientMode::Accumulate);
 	}
 	// ppng_3.h:609-676 (PPNG1 / PPNG2 have none)
+	bool has_second_order() const override { return m_variant == 3; }
 	void backward_backward_input(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, MatView dL_ddLdx, const void* dL_dy, void* dL_ddLdy,
 	                             MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode) override {
 		if (m_variant != 3) return Encoding::backward_backward_input(stream, ctx, n, x, dL_ddLdx, dL_dy, dL_ddLdy, dL_dx, params, grads, mode);
@@ -1124,6 +1130,14 @@ public:
 	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes) override {
 		if (!dL_dx) return;
 		identity_backward_input(stream, m_fp32, n, m_n_dims, m_scale, dL_dy, padded_output_width(), *dL_dx);
+	}
+	// dL/dx = scale dL/dy is linear in dL/dy and does not depend on x: the tangent t = scale v (zero in the padding) is all there is
+	bool has_second_order() const override { return true; }
+	bool second_order_reads_dL_dy() const override { return false; }
+	void backward_backward_input(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, MatView dL_ddLdx, const void* dL_dy, void* dL_ddLdy,
+	                             MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode) override {
+		if (dL_ddLdy && padded_output_width() > 0) identity_backward_backward_input(stream, m_fp32, n, m_n_dims, m_scale, dL_ddLdx, dL_ddLdy, padded_output_width());
+		if (dL_dx) zero_input_gradient(stream, n, m_n_dims, *dL_dx);
 	}
 	Json hyperparams() const override {
 		Json j = Json::object();
@@ -1555,6 +1569,8 @@ public:
 	// TCNN_AMD_MLP_LAYERWISE=1 when the model was created.  Fragment images, fused input / output forms and the fused training step
 	// are then never used.
 	bool layerwise() const { return m_layerwise; }
+	bool has_output_activation() const { return m_output_activation != Activation::None; }
+	bool fully_fused() const { return m_fully_fused; } // otype FullyFusedMLP: no second-order pass (as in the reference); CutlassMLP has one
 
 	uint32_t input_width() const { return m_input_width; }
 	uint32_t output_width() const { return m_output_width; }
@@ -1702,6 +1718,126 @@ public:
 		mlp_wgrad_panels(stream, n, panels.data(), (uint32_t)panels.size(), accumulate, ws.as<float>()); // (layers of one shape share a launch)
 	}
 
+	// ---- Second-order input gradients of a CutlassMLP: the gradients of S = <v, dL/dinput> for a given v = dL2/d(dL/dinput).
+	// With h_0 = input, z_k = W_k h_{k-1}, h_k = a_k(z_k), g_K = dL/dy, d_k = g_k a_k'(z_k), g_{k-1} = W_k^T d_k (dL/dinput = g_0):
+	//   tangent    u_0 = v, z'_k = W_k u_{k-1}, u_k = a_k'(z_k) z'_k                  dS/d(dL/dy) = u_K
+	//   bilinear   dS/dW_k = d_k^T u_{k-1}
+	//   curvature  r_k = a_k''(z_k) g_k z'_k, p_K = r_K, p_k = r_k + a_k'(z_k) W_{k+1}^T p_{k+1}, dS/dW_k += p_k^T h_{k-1}, dS/dinput = W_1^T p_1
+	// The curvature pass exists only where some a_k'' != 0: for None / ReLU / LeakyReLU throughout it is not launched and dS/dinput is zero.
+	// Always layer by layer on row-major matrices (k_mlp_layers.hip), whatever kernels the first-order passes of this shape run: the
+	// forward pass and the first-order data pass are run again from the network's input (second_order_begin), keeping z_k (or h_k where
+	// the sign is all a' needs), g_k for the layers with curvature, and d_k; g_0 is not needed and not computed.  Two steps, so that a
+	// model with an encoding in front can allocate v in between (NetworkWithInputEncoding::backward_backward_input).
+	static bool has_curvature(uint32_t act) {
+		return act != (uint32_t)Activation::None && act != (uint32_t)Activation::ReLU && act != (uint32_t)Activation::LeakyReLU;
+	}
+	bool any_curvature() const { return has_curvature((uint32_t)m_output_activation) || (m_n_hidden > 0 && has_curvature((uint32_t)m_activation)); }
+
+	struct SecondOrderPass {
+		ArenaBuf h, z, g, d, wt; // [n_layers] slots of n x max(width, padded output width) halfs each (wt: laid out as the parameters)
+		size_t slot = 0;
+		const void* input = nullptr;
+		const void* dL_doutput = nullptr;
+		bool have_d = false, have_wt0 = false;
+	};
+
+	// need_d: second_order_finish() will be asked for parameter gradients or for dS_dinput (else only the forward pass is run again)
+	SecondOrderPass second_order_begin(hipStream_t stream, uint32_t n, const void* input, const void* dL_doutput, const void* params, bool need_d) const {
+		CHECK_THROW(!m_fully_fused);
+		SecondOrderPass s;
+		const uint32_t K = m_desc.n_layers;
+		s.slot = (size_t)n * std::max(m_width, m_padded_output_width);
+		s.input = input;
+		s.dL_doutput = dL_doutput;
+		const bool curved = any_curvature();
+		const _Float16* p = (const _Float16*)params;
+		s.h = ArenaBuf{stream, K * s.slot * 2};
+		if (curved) s.z = ArenaBuf{stream, K * s.slot * 2};
+		const _Float16* in = (const _Float16*)input;
+		uint32_t ldi = m_input_width;
+		for (uint32_t l = 0; l < K; ++l) {
+			const MlpLayer& L = m_desc.layers[l];
+			_Float16* out = s.h.as<_Float16>() + s.slot * l;
+			mlp_layer_forward(stream, n, in, ldi, p + L.w_off, L.rows, L.cols, layer_act(l), out, layer_ld(l), has_curvature(layer_act(l)) ? s.z.as<_Float16>() + s.slot * l : nullptr);
+			in = out;
+			ldi = m_width;
+		}
+		if (!need_d) return s;
+		s.have_d = true;
+		s.d = ArenaBuf{stream, K * s.slot * 2};
+		if (curved) s.g = ArenaBuf{stream, K * s.slot * 2};
+		s.wt = ArenaBuf{stream, m_n_params * 2};
+		for (uint32_t l = 1; l < K; ++l) mlp_layer_transpose(stream, m_desc.layers[l].rows, m_desc.layers[l].cols, p + m_desc.layers[l].w_off, s.wt.as<_Float16>() + m_desc.layers[l].w_off);
+		if (layer_act(K - 1) != (uint32_t)Activation::None) { // d_K = a_K'(z_K) g_K
+			mlp_layer_delta(stream, (size_t)n * m_padded_output_width, layer_act(K - 1), dL_doutput, aux_of(s, K - 1), s.d.as<_Float16>() + s.slot * (K - 1));
+		}
+		for (uint32_t l = K - 1; l > 0; --l) {
+			const MlpLayer& L = m_desc.layers[l];
+			const uint32_t act = layer_act(l - 1);
+			mlp_layer_backward_keep(stream, n, d_of(s, l), layer_ld(l), s.wt.as<_Float16>() + L.w_off, L.rows, L.cols, act, aux_of(s, l - 1),
+			                        has_curvature(act) ? s.g.as<_Float16>() + s.slot * (l - 1) : nullptr, s.d.as<_Float16>() + s.slot * (l - 1), m_width);
+		}
+		return s;
+	}
+
+	// v: half [n][in_width].  Optional results: dL_ddLdoutput half [n][padded output width]; dS_dinput half [n][in_width], written only if
+	// any_curvature() (else it is zero and nothing is launched for it); gradients per mode.
+	void second_order_finish(hipStream_t stream, SecondOrderPass& s, uint32_t n, const void* v, void* dL_ddLdoutput, void* dS_dinput, const void* params, void* gradients,
+	                         GradientMode mode) const {
+		const uint32_t K = m_desc.n_layers;
+		const bool curved = any_curvature();
+		const bool want_grads = mode != GradientMode::Ignore;
+		const bool want_p = curved && (want_grads || dS_dinput);
+		if (!dL_ddLdoutput && !want_grads && !(curved && dS_dinput)) return;
+		if (want_grads) CHECK_THROW(gradients != nullptr);
+		if (want_grads || want_p) CHECK_THROW(s.have_d);
+		const _Float16* p = (const _Float16*)params;
+		ArenaBuf u{stream, K * s.slot * 2}, r;
+		if (want_p) r = ArenaBuf{stream, K * s.slot * 2};
+		auto u_of = [&](uint32_t l) { return l == K - 1 && dL_ddLdoutput ? (_Float16*)dL_ddLdoutput : u.as<_Float16>() + s.slot * l; };
+		const _Float16* in = (const _Float16*)v;
+		uint32_t ldi = m_input_width;
+		for (uint32_t l = 0; l < K; ++l) {
+			const MlpLayer& L = m_desc.layers[l];
+			const bool curv = want_p && has_curvature(layer_act(l));
+			const _Float16* g = l == K - 1 ? (const _Float16*)s.dL_doutput : s.g.as<_Float16>() + s.slot * l;
+			mlp_layer_tangent(stream, n, in, ldi, p + L.w_off, L.rows, L.cols, layer_act(l), aux_of(s, l), curv ? g : nullptr, u_of(l), curv ? r.as<_Float16>() + s.slot * l : nullptr, layer_ld(l));
+			in = u_of(l);
+			ldi = m_width;
+		}
+		uint32_t top = 0; // the last layer with curvature: p_k = 0 above it
+		for (uint32_t l = 0; l < K; ++l) if (has_curvature(layer_act(l))) top = l;
+		if (want_p) {
+			if (dS_dinput && !s.have_wt0) {
+				mlp_layer_transpose(stream, m_desc.layers[0].rows, m_desc.layers[0].cols, p, s.wt.as<_Float16>());
+				s.have_wt0 = true;
+			}
+			for (uint32_t l = top; l > 0; --l) {
+				const MlpLayer& L = m_desc.layers[l];
+				_Float16* below = r.as<_Float16>() + s.slot * (l - 1);
+				mlp_layer_curvature_backward(stream, n, r.as<_Float16>() + s.slot * l, layer_ld(l), s.wt.as<_Float16>() + L.w_off, L.rows, L.cols, layer_act(l - 1), aux_of(s, l - 1),
+				                             has_curvature(layer_act(l - 1)) ? below : nullptr, below, m_width);
+			}
+			if (dS_dinput) {
+				const MlpLayer& L = m_desc.layers[0];
+				mlp_layer_backward(stream, n, r.as<_Float16>(), layer_ld(0), s.wt.as<_Float16>(), L.rows, L.cols, (uint32_t)Activation::None, nullptr, dS_dinput, m_input_width);
+			}
+		}
+		if (!want_grads) return;
+		// dS/dW_k = d_k^T u_{k-1}, then += p_k^T h_{k-1} for the layers up to `top` (the sum is rounded to half once per term)
+		std::vector<WgradPanel> panels;
+		for (uint32_t pass = 0; pass < (want_p ? 2u : 1u); ++pass) {
+			panels.clear();
+			for (uint32_t l = 0; l < (pass ? top + 1 : K); ++l) {
+				const MlpLayer& L = m_desc.layers[l];
+				const _Float16* dO = pass ? r.as<_Float16>() + s.slot * l : d_of(s, l);
+				const _Float16* In = l == 0 ? (const _Float16*)(pass ? s.input : v) : pass ? s.h.as<_Float16>() + s.slot * (l - 1) : u.as<_Float16>() + s.slot * (l - 1);
+				add_wgrad_panels(panels, L, dO, layer_ld(l), In, l == 0 ? m_input_width : m_width, (_Float16*)gradients + L.w_off);
+			}
+			launch_wgrad_panels(stream, n, panels, pass ? true : mode == GradientMode::Accumulate);
+		}
+	}
+
 	Json hyperparams() const { // fully_fused_mlp.h:137-145
 		Json j = Json::object();
 		j["otype"] = m_fully_fused ? "FullyFusedMLP" : "CutlassMLP";
@@ -1769,12 +1905,28 @@ private:
 			const MlpLayer& L = m_desc.layers[l];
 			const _Float16* dO = l == m_desc.n_layers - 1 ? (const _Float16*)dY : dhidden.as<_Float16>() + hstride * l;
 			const _Float16* In = l == 0 ? (const _Float16*)input : hidden + hstride * (l - 1);
-			const uint32_t ldo = layer_ld(l), ldi = l == 0 ? m_input_width : m_width;
-			_Float16* g = (_Float16*)gradients + L.w_off;
-			for (uint32_t r0 = 0; r0 < L.rows; r0 += 128)
-				for (uint32_t c0 = 0; c0 < L.cols; c0 += 128)
-					panels.push_back(WgradPanel{dO + r0, ldo, std::min(128u, L.rows - r0), In + c0, ldi, std::min(128u, L.cols - c0), g + (size_t)r0 * L.cols + c0, L.cols, false, false});
+			add_wgrad_panels(panels, L, dO, layer_ld(l), In, l == 0 ? m_input_width : m_width, (_Float16*)gradients + L.w_off);
 		}
+		launch_wgrad_panels(stream, n, panels, mode == GradientMode::Accumulate);
+	}
+
+	// what a' (and a'') of layer l are evaluated from in the second-order pass: z_l where the layer has curvature, else h_l (the sign)
+	const _Float16* aux_of(const SecondOrderPass& s, uint32_t l) const {
+		if (layer_act(l) == (uint32_t)Activation::None) return nullptr;
+		return (has_curvature(layer_act(l)) ? s.z.as<_Float16>() : s.h.as<_Float16>()) + s.slot * l;
+	}
+	const _Float16* d_of(const SecondOrderPass& s, uint32_t l) const { // d_K = g_K for an output layer without activation
+		return l == m_desc.n_layers - 1 && layer_act(l) == (uint32_t)Activation::None ? (const _Float16*)s.dL_doutput : s.d.as<_Float16>() + s.slot * l;
+	}
+
+	// row-major operands: panels of at most 128 x 128 of one layer's weight gradient
+	static void add_wgrad_panels(std::vector<WgradPanel>& panels, const MlpLayer& L, const _Float16* dO, uint32_t ldo, const _Float16* In, uint32_t ldi, _Float16* g) {
+		for (uint32_t r0 = 0; r0 < L.rows; r0 += 128)
+			for (uint32_t c0 = 0; c0 < L.cols; c0 += 128)
+				panels.push_back(WgradPanel{dO + r0, ldo, std::min(128u, L.rows - r0), In + c0, ldi, std::min(128u, L.cols - c0), g + (size_t)r0 * L.cols + c0, L.cols, false, false});
+	}
+
+	void launch_wgrad_panels(hipStream_t stream, uint32_t n, const std::vector<WgradPanel>& panels, bool accumulate) const {
 		constexpr size_t WORKSPACE_FLOATS = (size_t)64 << 20; // 256 MB
 		size_t max_floats = 0;
 		for (const WgradPanel& q : panels) max_floats = std::max(max_floats, wgrad_panels_workspace_floats(&q, 1, n));
@@ -1783,7 +1935,7 @@ private:
 		for (size_t i = 0; i < panels.size();) {
 			size_t j = i, floats = 0;
 			while (j < panels.size() && floats + wgrad_panels_workspace_floats(&panels[j], 1, n) <= ws_floats) floats += wgrad_panels_workspace_floats(&panels[j++], 1, n);
-			mlp_wgrad_panels(stream, n, panels.data() + i, (uint32_t)(j - i), mode == GradientMode::Accumulate, ws.as<float>());
+			mlp_wgrad_panels(stream, n, panels.data() + i, (uint32_t)(j - i), accumulate, ws.as<float>());
 			i = j;
 		}
 	}
@@ -1984,6 +2136,7 @@ public:
 		NetworkContext network_ctx; // hidden activations; empty for fused contexts
 		uint32_t x_plane_f = 0;
 		bool fused = false;         // produced by fused_encode(): backward() goes through the fused MLP kernel
+		bool input_gradients = false; // forward() ran with prepare_input_gradients
 		uint32_t oneblob_bins = 0;  // > 0: no encoded batch was written -- the MLP kernels evaluate the OneBlob encoding of the input themselves
 		ArenaBuf image;             // the network's fragment images, if the encoding's forward kernel built them on the way (MlpPrepJob)
 		// the MLP's weight-gradient slabs once their reduction was handed to a LATER launch (AdamPrologue: the optimizer's, enqueued after
@@ -1997,6 +2150,7 @@ public:
 	std::unique_ptr<ModelContext> forward(hipStream_t stream, uint32_t n, MatView input, void* output, const void* params, bool prepare_input_gradients) override {
 		check_batch(n);
 		auto ctx = std::make_unique<Ctx>();
+		ctx->input_gradients = prepare_input_gradients;
 		if (n == 0) return ctx;
 		const _Float16* p = (const _Float16*)params;
 		if (!prepare_input_gradients && fused_step_supported(n)) {
@@ -2043,6 +2197,60 @@ public:
 			m_encoding->backward(stream, ctx.encoding_ctx, n, input, dL_dnetwork_input.data(), dL_dinput, p + m_network->n_params(),
 			                     g ? g + m_network->n_params() : nullptr, mode, plane_f > 0);
 		}
+	}
+
+	// Second-order input gradients through encoding and network (the network: Network::second_order_*, CutlassMLP only).  With
+	// e = encoding(x) and v = dL_ddLdinput:
+	//   1. g_e = dL/de from the network's first-order backward pass on the context's activations -- the very kernels backward() runs, so
+	//      that the model gives what its parts give when a caller chains them by hand -- and the network's layer-by-layer passes from e
+	//   2. encoding.backward_backward_input(x, v, dL_dy = g_e) -> t = J_enc v, the encoding's second-order gradients, its part of dL_dinput
+	//   3. the network's second-order pass with v := t -> dL_ddLdoutput, the network's gradients, q = dS/de
+	//   4. where the network has curvature (q != 0): encoding.backward(dL_dy = q), accumulated onto the results of 2.
+	// FullyFusedMLP has no second-order pass, as in the reference (ask for "otype": "CutlassMLP"), and neither have most encodings: both
+	// are reported before anything is allocated or launched.
+	void backward_backward_input(hipStream_t stream, const ModelContext& mctx, uint32_t n, MatView input, MatView dL_ddLdinput, const void* dL_doutput,
+	                             void* dL_ddLdoutput, MatViewMut* dL_dinput, const void* params, void* gradients, GradientMode mode) override {
+		if (m_network->fully_fused() || !m_encoding->has_second_order()) {
+			return Model::backward_backward_input(stream, mctx, n, input, dL_ddLdinput, dL_doutput, dL_ddLdoutput, dL_dinput, params, gradients, mode);
+		}
+		check_batch(n);
+		const Ctx& ctx = dynamic_cast<const Ctx&>(mctx);
+		if (ctx.fused || !ctx.input_gradients) throw std::runtime_error{"NetworkWithInputEncoding::backward: input gradients were not prepared by forward()"};
+		const bool want_grads = mode != GradientMode::Ignore;
+		if (n == 0 || (!dL_ddLdoutput && !dL_dinput && !want_grads)) return;
+		CHECK_THROW(!want_grads || gradients != nullptr);
+		const _Float16* p = (const _Float16*)params;
+		_Float16* g = want_grads ? (_Float16*)gradients : nullptr;
+		const size_t n_net = m_network->n_params();
+		const size_t enc_bytes = (size_t)n * m_encoding->padded_output_width() * 2;
+		const bool enc_grads = want_grads && m_encoding->n_params() > 0;
+		// q feeds the encoding's parameter gradients and dL_dinput only
+		const bool want_q = m_network->any_curvature() && (enc_grads || dL_dinput);
+
+		ArenaBuf g_e, t{stream, enc_bytes}, q;
+		if (m_encoding->second_order_reads_dL_dy() && (enc_grads || dL_dinput)) {
+			g_e = ArenaBuf{stream, enc_bytes};
+			ArenaBuf output; // backward() reads it for the output activation's derivative only
+			if (m_network->has_output_activation()) {
+				output = ArenaBuf{stream, (size_t)n * m_network->padded_output_width() * 2};
+				m_network->inference(stream, n, ctx.network_input.data(), output.data(), p);
+			}
+			m_network->backward(stream, ctx.network_ctx, n, ctx.network_input.data(), output.data(), dL_doutput, g_e.data(), p, nullptr, GradientMode::Ignore);
+		}
+		Network::SecondOrderPass pass = m_network->second_order_begin(stream, n, ctx.network_input.data(), dL_doutput, p, want_grads || want_q);
+		m_encoding->backward_backward_input(stream, ctx.encoding_ctx, n, input, dL_ddLdinput, g_e.data(), t.data(), dL_dinput, p + n_net, g ? g + n_net : nullptr, mode);
+		if (want_q) q = ArenaBuf{stream, enc_bytes};
+		m_network->second_order_finish(stream, pass, n, t.data(), dL_ddLdoutput, q.data(), p, g, mode);
+		if (!want_q) return;
+		ArenaBuf dx_more;
+		MatViewMut dx_view{nullptr, m_encoding->input_width(), 1u};
+		if (dL_dinput) {
+			dx_more = ArenaBuf{stream, (size_t)n * m_encoding->input_width() * sizeof(float)};
+			dx_view.data = dx_more.as<float>();
+		}
+		m_encoding->backward(stream, ctx.encoding_ctx, n, input, q.data(), dL_dinput ? &dx_view : nullptr, p + n_net, enc_grads ? g + n_net : nullptr,
+		                     enc_grads ? GradientMode::Accumulate : GradientMode::Ignore, false);
+		if (dL_dinput) add_input_gradient(stream, n, m_encoding->input_width(), MatView{dx_view.data, dx_view.stride_sample, dx_view.stride_dim}, *dL_dinput);
 	}
 
 	// TCNN_AMD_FUSED_STEP=0 selects the reference-shaped kernel sequence (forward / loss / backward / wgrad) for A/B runs

@@ -269,6 +269,8 @@ void oneblob_forward(hipStream_t stream, bool fp32, uint32_t n, uint32_t n_dims,
 void oneblob_backward_input(hipStream_t stream, bool fp32, uint32_t n, uint32_t n_dims, uint32_t n_bins, MatView x, const void* dL_dy, uint32_t dy_stride, MatViewMut dL_dx);
 void identity_forward(hipStream_t stream, bool fp32, uint32_t n, uint32_t n_dims, float scale, float offset, MatView x, void* out, uint32_t out_stride);
 void identity_backward_input(hipStream_t stream, bool fp32, uint32_t n, uint32_t n_dims, float scale, const void* dL_dy, uint32_t dy_stride, MatViewMut dL_dx);
+// second order: dL_ddLdy[i][j] = (T)(dL_ddLdx[i][j] * scale) for j < n_dims, 0 for the padding
+void identity_backward_backward_input(hipStream_t stream, bool fp32, uint32_t n, uint32_t n_dims, float scale, MatView dL_ddLdx, void* dL_ddLdy, uint32_t dy_stride);
 // Frequency / TriangleWave (k_encodings.hip): dy_dx (optional) float [n][n_dims * outputs_per_input], consumed by the backward pass
 void periodic_forward(hipStream_t stream, bool triangle, bool fp32, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, MatView x, void* out, uint32_t out_stride, float* dy_dx);
 void periodic_backward_input(hipStream_t stream, bool fp32, uint32_t n, uint32_t n_dims, uint32_t outputs_per_input, const void* dL_dy, uint32_t dy_stride, const float* dy_dx, MatViewMut dL_dx);
@@ -409,6 +411,20 @@ void mlp_layer_forward(hipStream_t stream, uint32_t n, const void* x, uint32_t l
 void mlp_layer_backward(hipStream_t stream, uint32_t n, const void* dL_dout, uint32_t ldo, const void* wt, uint32_t rows, uint32_t cols, uint32_t activation, const void* aux,
                         void* dL_din, uint32_t ldi);
 void mlp_layer_transpose(hipStream_t stream, uint32_t rows, uint32_t cols, const void* w, void* wt); // wt [cols][rows] = w [rows][cols]^T
+// ---- the three products of the second-order pass (Network::second_order_begin / _finish).  a', a'' are evaluated in fp32 from aux: the
+// layer's half pre-activation, or its output for ReLU / LeakyReLU; unused for None.  One rounding to half per stored matrix.
+// tangent: acc = sum_c u_in[s][c] w[r][c];  u_out = a'(aux) acc;  r_out (optional, needs g) = a''(aux) g acc.  aux, g, u_out, r_out: [n][ldy]
+void mlp_layer_tangent(hipStream_t stream, uint32_t n, const void* u_in, uint32_t ldu, const void* w, uint32_t rows, uint32_t cols, uint32_t activation, const void* aux, const void* g,
+                       void* u_out, void* r_out, uint32_t ldy);
+// backward data, keeping the gradient from before the derivative: acc = sum_r d_out[s][r] w[r][c] (from wt);  g_in (optional) = (half) acc;
+// d_in = a'(aux) g_in.  aux, g_in, d_in: [n][ldi]
+void mlp_layer_backward_keep(hipStream_t stream, uint32_t n, const void* d_out, uint32_t ldo, const void* wt, uint32_t rows, uint32_t cols, uint32_t activation, const void* aux,
+                             void* g_in, void* d_in, uint32_t ldi);
+// curvature: acc = sum_r p_out[s][r] w[r][c] (from wt);  p_in = r_in + a'(aux) acc (r_in optional: zero; p_in may be r_in).  [n][ldi]
+void mlp_layer_curvature_backward(hipStream_t stream, uint32_t n, const void* p_out, uint32_t ldo, const void* wt, uint32_t rows, uint32_t cols, uint32_t activation, const void* aux,
+                                  const void* r_in, void* p_in, uint32_t ldi);
+void mlp_layer_delta(hipStream_t stream, size_t n_elems, uint32_t activation, const void* g, const void* aux, void* delta); // delta = a'(aux) g, element by element
+void add_input_gradient(hipStream_t stream, uint32_t n, uint32_t dims, MatView src, MatViewMut dst);                          // dst += src, [n][dims] floats
 
 // ------------------------------------------------------------------------------------------------------------------
 // loss / reduction / optimizer / init plumbing

@@ -72,6 +72,7 @@ _SIGNATURES = {
     "tcnn_module_forward": (_int, [_vp, _vp, _u32, _vp, _vp, _vp, _int, _pp]),
     "tcnn_module_backward": (_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tcnn_module_backward_backward_input": (_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tcnn_module_backward_backward_input_mode": (_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int]),
     "tcnn_context_destroy": (None, [_vp]),
     "tcnn_module_n_input_dims": (_u32, [_vp]),
     "tcnn_module_n_output_dims": (_u32, [_vp]),

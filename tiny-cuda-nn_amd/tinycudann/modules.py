@@ -190,7 +190,9 @@ def _create(fn, *args):
 # forward runs in inference mode when nothing requires a gradient; gradients are computed at loss_scale and divided
 # afterwards; the first-order backward pass is itself differentiable with respect to dL_doutput, input and params (second-order
 # INPUT gradients: eikonal / SDF losses); nothing is propagated through dL_dparams.  The construction is this package's own:
-# one record per call, two Functions that only shuttle tensors in and out of it.
+# one record per call, two Functions that only shuttle tensors in and out of it.  The native second-order pass exists for the
+# grid, PPNG3 and Identity encodings and for CutlassMLP networks, alone or behind one of those encodings; FullyFusedMLP and
+# the other encodings raise the reference's "not implemented error" (for a network: ask for "otype": "CutlassMLP").
 # ----------------------------------------------------------------------------------------------------------------------
 class _Call:
     """What one forward call leaves behind for its backward passes."""
