@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import CONFIG_C3B
+from grad_checks import assert_structural_zeros, assert_weight_grads_close, layer_slices
 
 gpu = pytest.mark.gpu
 
@@ -117,6 +118,13 @@ ORACLE_CASES = [
 ]
 
 
+# Over 2^16 rows the ReLU flips of _check_dx reach the weight gradients of the two wide, two-hidden-layer ReLU cases (by n_neurons): a flipped
+# unit's dL/dhidden of one sample is a whole term of the sum, and 1e-3 of a layer's largest gradient is about one term at this batch size.
+# float64 sums against the oracle's fp32 ones exceed the per-layer bar there on the CPU alone, with every input seed tried (1.2-2.4 x in the second
+# layer); tests/test_grad_checks.py asserts that, and that every other case -- and these two at 512 rows -- stays below half of it.
+FLIPS_EXCEED_THE_BAR_AT_2_16 = (192, 512)
+
+
 @gpu
 @pytest.mark.parametrize("n", [512, (1 << 16) + 256])
 @pytest.mark.parametrize("n_in,n_out,net_cfg", ORACLE_CASES)
@@ -138,6 +146,10 @@ def test_layerwise_network_matches_oracle(tcnn, oracle, n_in, n_out, net_cfg, n)
     grads_h = np.zeros(ref.n_params, dtype=np.uint16)
     want_dx, _ = ref.backward(x, params_h, ctx, want_out, dy_scaled, want_dL_dx=True, grads_half=grads_h, grads_f32=grads32)
     assert rel_err(got_dp, grads32) < 2e-2
+    what = f"layer by layer {n_in} -> {n_out} {net_cfg} n = {n}"
+    if n <= 512 or net_cfg["n_neurons"] not in FLIPS_EXCEED_THE_BAR_AT_2_16:
+        assert_weight_grads_close(got_dp, grads32, layer_slices(ref.network), 2e-2, True, what)  # per layer, per element (grad_checks.weight_grad_ratios)
+    assert_structural_zeros(got_dp, grads32, layer_slices(ref.network), what)
     _check_dx(got_dx, want_dx)
 
 
@@ -223,6 +235,8 @@ def test_sine_network(tcnn, oracle, width, hidden):
     assert elem_close(got, np_out[:, :n_out].astype(np.float32)) <= 1.0
     want_dp, want_dx = backward(dy_h * 128.0)
     assert rel_err(got_dp, want_dp) < 2e-2
+    assert_weight_grads_close(got_dp, want_dp, layer_slices(ref.network), 2e-2, True, f"Sine {width} x {hidden}")
+    assert_structural_zeros(got_dp, want_dp, layer_slices(ref.network), f"Sine {width} x {hidden}")
     assert rel_err(got_dx, want_dx) < 2e-2
 
 
@@ -408,6 +422,8 @@ def test_network_with_input_encoding(tcnn, oracle, enc, n_in, width):
     grads32 = np.zeros(ref.n_params, dtype=np.float32)
     ref.backward(x, params_h, ctx, want_out, dy_scaled, want_dL_dx=False, grads_f32=grads32)
     assert rel_err(got_dp, grads32) < 2e-2
+    assert_weight_grads_close(got_dp, grads32, layer_slices(ref.network), 2e-2, True, f"tcnn.NetworkWithInputEncoding {enc['otype']} -> {width} x 2")
+    assert_structural_zeros(got_dp, grads32, layer_slices(ref.network), f"tcnn.NetworkWithInputEncoding {enc['otype']} -> {width} x 2")
 
 
 @gpu

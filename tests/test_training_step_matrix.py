@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import CONFIG_C2, CONFIG_C3A, CONFIG_C3B, CONFIG_C5_SMALL
+from grad_checks import assert_structural_zeros, assert_weight_grads_close, layer_slices, subnormal_share
 from test_gpu_parity import _bits, _exact_external_dy, _f32, _linear_net_params, _t, elem_close, rel_err
 from test_losses import _assert_fused_loss_close
 
@@ -37,14 +38,17 @@ def _targets(out_act, n, n_out, seed):
     return np.ascontiguousarray(t)
 
 
-def _run(tcnn, monkeypatch, n_in, n_out, cfg, env, x, t, layout=None, **kw):
-    """one training_step of a fresh trainer under `env`: (kernel name, output, L, dL_doutput, gradients, loss)"""
+def _run(tcnn, monkeypatch, n_in, n_out, cfg, env, x, t, layout=None, params_half=None, **kw):
+    """one training_step of a fresh trainer under `env`: (kernel name, output, L, dL_doutput, gradients, loss); params_half (uint16 bits of
+    every parameter) replaces the initial parameters"""
     from tinycudann.native import LAYOUT_AOS, LAYOUT_SOA
 
     with monkeypatch.context() as m:
         for k, v in env.items():
             m.setenv(k, v)
         tr = tcnn.Trainer(n_in, n_out, cfg, seed=1337)
+        if params_half is not None:
+            tr.set_params(_t(params_half.view(np.float16)))
         xin = _t(x) if layout != "soa" else _t(np.ascontiguousarray(x.T))
         ctx = tr.training_step(xin, None if t is None else _t(t), run_optimizer=False, input_layout=LAYOUT_SOA if layout == "soa" else LAYOUT_AOS, **kw)
         res = {"kernel": tr.last_step_kernel(), "out": _bits(ctx.output()), "L": ctx.L().cpu().numpy(), "dy": _bits(ctx.dL_doutput()),
@@ -52,7 +56,12 @@ def _run(tcnn, monkeypatch, n_in, n_out, cfg, env, x, t, layout=None, **kw):
     return res
 
 
-def _check_against_oracle(ref, want, grads32, got, n, n_out):
+PER_LAYER_BAR_NOT_AT_INIT = {"v64_2_4_16_act"}
+
+
+def _check_against_oracle(ref, want, grads32, got, n, n_out, what="", untouched=None, per_layer=True):
+    """`untouched`: boolean mask over the encoding's parameters that no sample reaches; without it, the entries whose fp32 gradient is zero in
+    the oracle stand for them (true while no touched entry's gradient rounds to zero)"""
     out, w_out = _f32(got["out"]).reshape(n, -1), _f32(want["output"])
     assert elem_close(out[:, :n_out], w_out[:, :n_out]) <= 1.0
     assert abs(got["loss"] - want["loss"]) <= 3e-2 * abs(want["loss"])
@@ -63,9 +72,16 @@ def _check_against_oracle(ref, want, grads32, got, n, n_out):
     g = _f32(got["g"])
     n_net = ref.model.network.n_params
     assert rel_err(g[:n_net], grads32[:n_net]) < 3e-2
+    # the same 3e-2 with the maximum taken per layer and every element bounded by its own size (grad_checks.weight_grad_ratios); whole
+    # rows / columns the oracle leaves zero -- padded outputs, zero-padded inputs -- are zero bit for bit
+    what = f"{what} [{got.get('kernel', '?')}]"
+    slices = layer_slices(ref.model.network)
+    if per_layer:
+        assert_weight_grads_close(g[:n_net], grads32[:n_net], slices, 3e-2, True, what)
+    assert_structural_zeros(got["g"][:n_net], grads32[:n_net], slices, what)
     if ref.model.encoding.n_params > 0:
         ge, we = g[n_net:], grads32[n_net:]
-        assert float(np.linalg.norm(ge - we)) <= 5e-2 * float(np.linalg.norm(we)) and np.all(ge[we == 0] == 0)
+        assert float(np.linalg.norm(ge - we)) <= 5e-2 * float(np.linalg.norm(we)) and np.all(ge[we == 0 if untouched is None else untouched] == 0)
 
 
 def _check_against_unfused(got, unf):
@@ -94,6 +110,10 @@ FORM_CASES = [
     ("v64_2_4_8_act", GRID16, 2, 64, 2, "Sigmoid", "None", 5, 256 * 9, _v(2, 4, 8), "train<64,2,4,8>/act"),
     ("v64_2_4_16_relu", GRID16, 2, 64, 3, "ReLU", "None", 32, 256 * 5, _v(2, 4, 16), "train<64,2,4,16>/relu"),
     ("v64_2_4_16_act", GRID16, 2, 64, 4, "LeakyReLU", "ReLU", 8, 256 * 11, _v(2, 4, 16), "train<64,2,4,16>/act"),
+    # (with the grid at its initial values the negative side of a fourth LeakyReLU layer holds fp16 subnormals of 1-4 bits, and the order of
+    # the fp32 sums alone moves the first layers' gradients by 0.6 of the per-layer bar -- tests/test_grad_checks.py asserts it: the 4-layer case
+    # keeps every other bar there, PER_LAYER_BAR_NOT_AT_INIT, and meets the per-layer one with a U(-1, 1) grid; 3 layers meet it at init too)
+    ("v64_2_4_16_act_3_hidden", GRID16, 2, 64, 3, "LeakyReLU", "ReLU", 8, 256 * 11, _v(2, 4, 16), "train<64,2,4,16>/act"),
     ("v64_1_4_16_relu", GRID16, 2, 64, 1, "ReLU", "None", 1, 256 * 13, _v(1, 4, 16), "train<64,1,4,16>/relu"),
     ("v64_1_4_16_act", GRID16, 2, 64, 4, "Squareplus", "Tanh", 24, 256 * 5, _v(1, 4, 16), "train<64,1,4,16>/act"),
     ("v64_1_4_32_relu", GRID16, 2, 64, 8, "ReLU", "None", 3, 256 * 9, _v(1, 4, 32), "train<64,1,4,32>/relu"),
@@ -147,9 +167,12 @@ def test_training_kernel_forms_match_oracle(tcnn, oracle, monkeypatch, case):
     want = ref.training_step(x, t, run_optimizer=False, grads_f32=grads32)
     got = _run(tcnn, monkeypatch, n_in, n_out, cfg, env, x, t)
     assert got["kernel"] == kernel
-    _check_against_oracle(ref, want, grads32, got, n, n_out)
+    per_layer = case[0] not in PER_LAYER_BAR_NOT_AT_INIT
+    _check_against_oracle(ref, want, grads32, got, n, n_out, case[0], per_layer=per_layer)
     if kernel != "unfused":
-        _check_against_unfused(got, _run(tcnn, monkeypatch, n_in, n_out, cfg, {**env, "TCNN_AMD_FUSED_STEP": "0"}, x, t))
+        unf = _run(tcnn, monkeypatch, n_in, n_out, cfg, {**env, "TCNN_AMD_FUSED_STEP": "0"}, x, t)
+        _check_against_unfused(got, unf)
+        _check_against_oracle(ref, want, grads32, unf, n, n_out, case[0] + " with TCNN_AMD_FUSED_STEP=0", per_layer=per_layer)
 
 
 # ---------------------------------------------------------------------------------------------------- c.2 data_pdf
@@ -190,7 +213,73 @@ def test_data_pdf_in_each_training_kernel(tcnn, oracle, monkeypatch, case, loss)
     ref = oracle.Trainer(n_in, n_out, cfg, seed=1337)
     grads32 = np.zeros(ref.model.n_params, dtype=np.float32)
     want = ref.training_step(x, t, run_optimizer=False, grads_f32=grads32, data_pdf=pdf)
-    _check_against_oracle(ref, want, grads32, got, n, n_out)
+    _check_against_oracle(ref, want, grads32, got, n, n_out, f"pdf_{case[0]}/{loss}")
+
+
+# ---------------------------------------------------------------------------------------------------- c.2b the same kernels, gradients in fp16's normal range
+def o1_grid_params(oracle, ref):
+    """the oracle trainer's parameters with the encoding's drawn from U(-1, 1) (as the encoding tests do) instead of the initial U(+-1e-4)"""
+    n_net = ref.model.network.n_params
+    p = ref.params.copy()
+    p[n_net:] = oracle.half_bits(oracle.Pcg32(3).uniform_strided(ref.model.encoding.n_params, -1.0, 1.0))
+    return p
+
+
+MAX_SUBNORMAL_SHARE = 0.15  # a cap on the oracle's own half gradients (measured: <= 10 %)
+
+# (id, config, n_in, n_out, n, env, kernel, output activation of the targets, pdf seed): every kernel form and every pdf case (a OneBlob
+# encoding has no parameters to set: its cases run as above, their gradients are normal numbers already)
+NORMAL_RANGE_CASES = [(c[0], _cfg(c[1], c[3], c[4], c[5], c[6]), c[2], c[7], c[8], c[9], c[10], c[6], None) for c in FORM_CASES] + \
+                     [(f"pdf_{c[0]}_{loss}", {**c[1], "loss": {"otype": loss}}, c[2], c[3], c[4], c[5], c[6], None, 3) for c in PDF_CASES for loss in ("L2", "RelativeL2")]
+
+
+def untouched_grid_entries(oracle, ref, x):
+    """mask over the encoding's parameters: True where no sample of x lands with a non-zero interpolation weight (the gradient of an all-ones
+    dL/dy is zero there).  With O(1) grid entries some touched entries' gradients are fp16 subnormals that round to zero on one side and to
+    2^-24 on the other: "zero in the oracle" no longer means "untouched"."""
+    enc = ref.model.encoding
+    if enc.n_params == 0:
+        return np.zeros(0, dtype=bool)
+    _, ctx = enc.forward(x, np.ascontiguousarray(ref.params[ref.model.network.n_params:]))
+    ones = oracle.half_bits(np.ones((x.shape[0], enc.padded_output_width), dtype=np.float32))
+    touched = np.zeros(enc.n_params, dtype=np.float32)
+    enc.backward(x, ctx, ones, grad_f32=touched)
+    return touched == 0
+
+
+def normal_range_inputs(oracle, case):
+    """(x, targets, data_pdf) of a NORMAL_RANGE_CASES entry: those of the first regime's test of the same case"""
+    _, cfg, n_in, n_out, n, _, _, out_act, pdf_seed = case
+    if pdf_seed is None:
+        return oracle.Pcg32(42).uniform_strided(n * n_in).reshape(n, n_in), _targets(out_act, n, n_out, 17), None
+    x, t = oracle.synthetic_batch(n, n_in, n_out, seed=42)
+    return x, t, _pdf(n, n_out, pdf_seed)
+
+
+@pytest.mark.parametrize("case", NORMAL_RANGE_CASES, ids=[c[0] for c in NORMAL_RANGE_CASES])
+def test_training_kernels_match_oracle_with_gradients_in_the_normal_range(tcnn, oracle, monkeypatch, case):
+    """With the L2 loss and the grid at its initial U(+-1e-4) values -- the setting of the tests above -- 90-100 % of the half gradients of
+    every layer but the last are fp16 subnormals: the kernels' half stores are exercised where a half holds 1-9 significant bits.  Here the
+    same kernels (asserted first) run with the grid's entries drawn from U(-1, 1): at most 15 % of any layer's gradients are subnormal (asserted
+    on the oracle's values), and every bar of _check_against_oracle holds -- the per-layer, per-element one on gradients that are normal
+    numbers."""
+    name, cfg, n_in, n_out, n, env, kernel, _, _ = case
+    x, t, pdf = normal_range_inputs(oracle, case)
+    ref = oracle.Trainer(n_in, n_out, cfg, seed=1337)
+    ref.params = o1_grid_params(oracle, ref)
+    grads32 = np.zeros(ref.model.n_params, dtype=np.float32)
+    want = ref.training_step(x, t, run_optimizer=False, grads_f32=grads32, data_pdf=pdf)
+    share = subnormal_share(ref.grads[:ref.model.network.n_params], layer_slices(ref.model.network))
+    assert max(share) <= MAX_SUBNORMAL_SHARE, share
+    kw = {} if pdf is None else {"data_pdf": _t(pdf)}
+    untouched = untouched_grid_entries(oracle, ref, x)
+    got = _run(tcnn, monkeypatch, n_in, n_out, cfg, env, x, t, params_half=ref.params, **kw)
+    assert got["kernel"] == kernel
+    _check_against_oracle(ref, want, grads32, got, n, n_out, name + " (grid U(-1, 1))", untouched)
+    if kernel != "unfused":
+        unf = _run(tcnn, monkeypatch, n_in, n_out, cfg, {**env, "TCNN_AMD_FUSED_STEP": "0"}, x, t, params_half=ref.params, **kw)
+        _check_against_unfused(got, unf)
+        _check_against_oracle(ref, want, grads32, unf, n, n_out, name + " (grid U(-1, 1)) with TCNN_AMD_FUSED_STEP=0", untouched)
 
 
 @pytest.mark.parametrize("name", ["RelativeL2Luminance", "L1", "RelativeL1", "Mape", "Smape", "CrossEntropy", "Variance"])
