@@ -101,11 +101,12 @@ int  tcnn_module_backward(tcnn_module_t m, tcnn_stream_t stream, tcnn_context_t 
 /* second-order input gradients (cpp_api.h:94, cpp_api.cu:111-127; grid.h:902-1026): dL_ddLdinput [n][n_input_dims] float is the
  * gradient arriving at dL_dinput; optional results dL_dparams (Overwrite), dL_ddLdoutput [n][n_output_dims], dL_dinput [n][n_input_dims]
  * (overwritten; the reference adds into a zeroed buffer).  The context must come from tcnn_module_forward(prepare_input_gradients = 1).
- * Modules that implement it: the grid encodings, PPNG3 and Identity; networks of otype CutlassMLP / MLP (every width, depth and
- * activation the constructor accepts), alone (tcnn_create_network) or behind one of those encodings.  FullyFusedMLP does not, as in the
- * reference: ask for "otype": "CutlassMLP", whose first-order passes still run the fused kernels for the shapes those cover.  It and
- * every other encoding report "DifferentiableObject::backward_backward_input_impl: not implemented error" (object.h:288) before
- * anything is allocated or launched. */
+ * Modules that implement it: the grid encodings, PPNG3, Identity, Frequency, TriangleWave, SphericalHarmonics, Empty and a Composite of
+ * those (Concatenation, Sum or Product); networks of otype CutlassMLP / MLP (every width, depth and activation the constructor accepts),
+ * alone (tcnn_create_network) or behind one of those encodings.  FullyFusedMLP does not, as in the reference: ask for "otype":
+ * "CutlassMLP", whose first-order passes still run the fused kernels for the shapes those cover.  It, OneBlob, PPNG1 / PPNG2 and a
+ * Composite that holds one of them (OneBlobFrequency / NRC) report "DifferentiableObject::backward_backward_input_impl: not implemented
+ * error" (object.h:288) before anything is allocated or launched. */
 int  tcnn_module_backward_backward_input(tcnn_module_t m, tcnn_stream_t stream, tcnn_context_t ctx, uint32_t n_elements, const float* dL_ddLdinput,
                                          const float* input, const void* dL_doutput, void* dL_dparams, void* dL_ddLdoutput, float* dL_dinput, const void* params);
 /* the same with an explicit TCNN_GRADIENT_* mode for dL_dparams (ACCUMULATE adds onto what the buffer holds; IGNORE: dL_dparams unused) */

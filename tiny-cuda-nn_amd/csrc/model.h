@@ -258,7 +258,11 @@ public:
 	// dL_dy [n][padded] T; grads: T[n_params] or nullptr (Ignore)
 	// dy_planes: dL_dy is laid out as level planes [padded / F][n][F] (only if level_plane_features() allowed it), else AoS
 	virtual void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes) = 0;
-	// second-order input gradients (object.h:278-288); the grid encoding (grid.h:902-1026), PPNG3 (ppng_3.h:609-676) and Identity provide them
+	// second-order input gradients (object.h:278-288), with v = dL_ddLdx [n][d_in] fp32 and d = dL_dy [n][padded] T:
+	//   dL_ddLdy [n][padded] T = J v (the tangent; exactly zero in the padding columns), dL_dx = d/dx <v, J^T d> in fp32 through the view,
+	//   grads = d/dparams of the same by `mode`.  Null results (and Ignore) are not computed; dL_dy may be null when only dL_ddLdy is asked for.
+	// Provided by the grid encoding (grid.h:902-1026), PPNG3 (ppng_3.h:609-676), Identity, Frequency, TriangleWave, SphericalHarmonics,
+	// Empty, and a Composite of those (any reduction).  OneBlob, PPNG1 and PPNG2 have none.
 	virtual void backward_backward_input(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, MatView dL_ddLdx, const void* dL_dy, void* dL_ddLdy,
 	                                     MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode) {
 		throw std::runtime_error{"DifferentiableObject::backward_backward_input_impl: not implemented error"};
@@ -1003,6 +1007,14 @@ public:
 	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes) override {
 		if (dL_dx) zero_input_gradient(stream, n, m_n_dims, *dL_dx);
 	}
+	// the output is constant: a zero tangent over the padding and no Hessian term
+	bool has_second_order() const override { return true; }
+	bool second_order_reads_dL_dy() const override { return false; }
+	void backward_backward_input(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, MatView dL_ddLdx, const void* dL_dy, void* dL_ddLdy,
+	                             MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode) override {
+		if (dL_ddLdy && padded_output_width() > 0 && n > 0) HIP_CHECK_THROW(hipMemsetAsync(dL_ddLdy, 0, (size_t)n * padded_output_width() * (m_fp32 ? 4 : 2), stream));
+		if (dL_dx) zero_input_gradient(stream, n, m_n_dims, *dL_dx);
+	}
 	Json hyperparams() const override {
 		Json j = Json::object();
 		j["otype"] = "Empty";
@@ -1171,6 +1183,16 @@ public:
 		CHECK_THROW(ctx.dy_dx); // frequency.h:150-152: needs a forward pass with prepare_input_gradients
 		periodic_backward_input(stream, m_fp32, n, m_n_dims, outputs_per_input(), dL_dy, padded_output_width(), ctx.dy_dx.as<float>(), *dL_dx);
 	}
+	// Frequency: tangent and Hessian term in one launch, from x (ctx.dy_dx is not read).  TriangleWave is piecewise linear: the tangent is all there is.
+	bool has_second_order() const override { return true; }
+	bool second_order_reads_dL_dy() const override { return !m_triangle; }
+	void backward_backward_input(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, MatView dL_ddLdx, const void* dL_dy, void* dL_ddLdy,
+	                             MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode) override {
+		if (n == 0) return;
+		if (dL_dx && (m_triangle || padded_output_width() == 0)) zero_input_gradient(stream, n, m_n_dims, *dL_dx);
+		if (padded_output_width() == 0) return;
+		periodic_backward_backward_input(stream, m_triangle, m_fp32, n, m_n_dims, m_n_frequencies, x, dL_ddLdx, dL_dy, dL_ddLdy, padded_output_width(), m_triangle ? nullptr : dL_dx);
+	}
 	Json hyperparams() const override {
 		Json j = Json::object();
 		j["otype"] = m_triangle ? "TriangleWave" : "Frequency";
@@ -1199,6 +1221,17 @@ public:
 	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes) override {
 		if (!dL_dx) return;
 		sh_backward_input(stream, m_fp32, n, m_degree, x, dL_dy, padded_output_width(), *dL_dx);
+	}
+	// one launch: sh_eval with a dotted twin of every quantity (k_sh_bwd_bwd_input)
+	bool has_second_order() const override { return true; }
+	void backward_backward_input(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, MatView dL_ddLdx, const void* dL_dy, void* dL_ddLdy,
+	                             MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode) override {
+		if (n == 0) return;
+		if (padded_output_width() == 0) {
+			if (dL_dx) zero_input_gradient(stream, n, 3, *dL_dx);
+			return;
+		}
+		sh_backward_backward_input(stream, m_fp32, n, m_degree, x, dL_ddLdx, dL_dy, dL_ddLdy, padded_output_width(), dL_dx);
 	}
 	Json hyperparams() const override {
 		Json j = Json::object();
@@ -1373,6 +1406,112 @@ public:
 			col += w;
 			p_off += e.n_params();
 		}
+	}
+	// Second-order pass: every nested encoding's own, on its slices of x, v, dL_dx, the parameters and the gradients.
+	//   Concatenation: dL_dy's column range copied out, the tangent copied into the same range of dL_ddLdy.
+	//   Sum: every nested pass receives dL_dy as it is; dL_ddLdy = sum_i t_i (the forward reduction on the tangents).
+	//   Product (y = prod_i y_i, P_i = prod_{k != i} y_k, S = sum_i <t_i, dL_dy P_i>):
+	//     1. g_i = dL_dy P_i (the first-order reduction kernel)   2. nested_i(v_i, dL_dy = g_i) -> t_i, its Hessian term, its gradients
+	//     3. k_composite_reduce_bwd_bwd -> dL_ddLdy = sum_i t_i P_i and q_k = dS/dy_k
+	//     4. nested_k.backward(dL_dy = q_k), accumulated onto the results of 2. (two or more factors only: q is zero for one)
+	// Input dims no nested encoding reads get zero dL_dx; where slices overlap the later encoding's slice replaces the earlier one's, as in
+	// backward() (and the reference's composite.h:302-330) -- in step 4 as well, which runs into a buffer of its own before it is added.
+	bool has_second_order() const override {
+		for (const auto& e : m_nested) {
+			if (!e->has_second_order()) return false;
+		}
+		return true;
+	}
+	bool second_order_reads_dL_dy() const override {
+		if (m_reduction == Reduction::Product && m_nested.size() > 1) return true; // q_k
+		for (const auto& e : m_nested) {
+			if (e->second_order_reads_dL_dy()) return true;
+		}
+		return false;
+	}
+	void backward_backward_input(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, MatView dL_ddLdx, const void* dL_dy, void* dL_ddLdy,
+	                             MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode) override {
+		if (!has_second_order()) return Encoding::backward_backward_input(stream, ctx, n, x, dL_ddLdx, dL_dy, dL_ddLdy, dL_dx, params, grads, mode);
+		const bool want_grads = mode != GradientMode::Ignore && n_params() > 0;
+		if (n == 0 || (!dL_ddLdy && !dL_dx && !want_grads)) return;
+		CHECK_THROW(ctx.nested.size() == m_nested.size());
+		CHECK_THROW(!want_grads || grads != nullptr);
+		CHECK_THROW(dL_dy != nullptr || !(second_order_reads_dL_dy() && (dL_dx || want_grads)));
+		const size_t elem = m_fp32 ? 4 : 2;
+		if (dL_dx) zero_input_gradient(stream, n, m_n_dims, *dL_dx);
+		const auto slice = [&](const MatView& m, size_t i) { return MatView{m.data + (size_t)m_begin[i] * m.stride_dim, m.stride_sample, m.stride_dim}; };
+		const auto slice_mut = [&](const MatViewMut& m, size_t i) { return MatViewMut{m.data + (size_t)m_begin[i] * m.stride_dim, m.stride_sample, m.stride_dim}; };
+		size_t p_off = 0;
+		if (m_reduction == Reduction::Concatenation) {
+			uint32_t col = 0;
+			for (size_t i = 0; i < m_nested.size(); ++i) {
+				Encoding& e = *m_nested[i];
+				const uint32_t w = e.padded_output_width();
+				ArenaBuf d_block, t_block;
+				if (w > 0 && dL_dy && e.second_order_reads_dL_dy()) {
+					d_block = ArenaBuf{stream, (size_t)n * w * elem};
+					copy_columns(stream, elem, n, dL_dy, padded_output_width(), col, d_block.data(), w, 0, w);
+				}
+				if (w > 0 && dL_ddLdy) t_block = ArenaBuf{stream, (size_t)n * w * elem};
+				MatViewMut dxs{};
+				if (dL_dx) dxs = slice_mut(*dL_dx, i);
+				e.backward_backward_input(stream, ctx.nested[i], n, slice(x, i), slice(dL_ddLdx, i), d_block.data(), t_block.data(), dL_dx ? &dxs : nullptr, (const char*)params + p_off * elem,
+				                          grads ? (char*)grads + p_off * elem : nullptr, mode);
+				if (t_block) copy_columns(stream, elem, n, t_block.data(), w, 0, dL_ddLdy, padded_output_width(), col, w);
+				col += w;
+				p_off += e.n_params();
+			}
+			return;
+		}
+		const bool product = m_reduction == Reduction::Product;
+		const uint32_t n_nested = (uint32_t)m_nested.size();
+		const uint32_t w = reduction_width();
+		const size_t n_elems = (size_t)n * w, block_bytes = n_elems * elem;
+		if (w == 0) return;
+		const bool want_q = product && n_nested > 1 && (dL_dx || want_grads);
+		ArenaBuf g_nested, tangents;
+		if (product && dL_dy) { // 1.
+			CHECK_THROW(ctx.to_reduce);
+			g_nested = ArenaBuf{stream, block_bytes * n_nested};
+			composite_reduce_backward(stream, m_fp32, true, n_elems, n_nested, ctx.to_reduce.data(), dL_dy, g_nested.data());
+		}
+		if (dL_ddLdy || want_q) tangents = ArenaBuf{stream, block_bytes * n_nested};
+		for (size_t i = 0; i < n_nested; ++i) { // 2.
+			Encoding& e = *m_nested[i];
+			MatViewMut dxs{};
+			if (dL_dx) dxs = slice_mut(*dL_dx, i);
+			const void* d_i = product ? (g_nested ? (const char*)g_nested.data() + i * block_bytes : nullptr) : dL_dy;
+			e.backward_backward_input(stream, ctx.nested[i], n, slice(x, i), slice(dL_ddLdx, i), d_i, tangents ? (char*)tangents.data() + i * block_bytes : nullptr, dL_dx ? &dxs : nullptr,
+			                          (const char*)params + p_off * elem, grads ? (char*)grads + p_off * elem : nullptr, mode);
+			p_off += e.n_params();
+		}
+		if (!product) {
+			if (dL_ddLdy) composite_reduce_forward(stream, m_fp32, false, n_elems, n_nested, tangents.data(), dL_ddLdy);
+			return;
+		}
+		ArenaBuf q;
+		if (want_q) q = ArenaBuf{stream, block_bytes * n_nested};
+		CHECK_THROW(ctx.to_reduce);
+		composite_reduce_backward_backward(stream, m_fp32, n_elems, n_nested, ctx.to_reduce.data(), tangents.data(), dL_dy, dL_ddLdy, q.data()); // 3.
+		if (!want_q) return;
+		ArenaBuf dx_more;
+		MatViewMut dx_view{nullptr, m_n_dims, 1u};
+		if (dL_dx) {
+			dx_more = ArenaBuf{stream, (size_t)n * m_n_dims * sizeof(float)};
+			dx_view.data = dx_more.as<float>();
+			zero_input_gradient(stream, n, m_n_dims, dx_view);
+		}
+		p_off = 0;
+		for (size_t k = 0; k < n_nested; ++k) { // 4.
+			Encoding& e = *m_nested[k];
+			MatViewMut dxs{};
+			if (dL_dx) dxs = slice_mut(dx_view, k);
+			const bool grads_k = want_grads && e.n_params() > 0;
+			e.backward(stream, ctx.nested[k], n, slice(x, k), (const char*)q.data() + k * block_bytes, dL_dx ? &dxs : nullptr, (const char*)params + p_off * elem,
+			           grads_k ? (char*)grads + p_off * elem : nullptr, grads_k ? GradientMode::Accumulate : GradientMode::Ignore, false);
+			p_off += e.n_params();
+		}
+		if (dL_dx) add_input_gradient(stream, n, m_n_dims, MatView{dx_view.data, dx_view.stride_sample, dx_view.stride_dim}, *dL_dx);
 	}
 	Json hyperparams() const override {
 		Json j = Json::object();

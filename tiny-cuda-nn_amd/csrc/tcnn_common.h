@@ -274,12 +274,19 @@ void identity_backward_backward_input(hipStream_t stream, bool fp32, uint32_t n,
 // Frequency / TriangleWave (k_encodings.hip): dy_dx (optional) float [n][n_dims * outputs_per_input], consumed by the backward pass
 void periodic_forward(hipStream_t stream, bool triangle, bool fp32, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, MatView x, void* out, uint32_t out_stride, float* dy_dx);
 void periodic_backward_input(hipStream_t stream, bool fp32, uint32_t n, uint32_t n_dims, uint32_t outputs_per_input, const void* dL_dy, uint32_t dy_stride, const float* dy_dx, MatViewMut dL_dx);
+// second-order pass: dL_ddLdy [n][dy_stride] T = J dL_ddLdx (zero in the padding) and / or dL_dx (Frequency: the Hessian term, read from x and dL_dy,
+// not from dy_dx; TriangleWave has none and writes no dL_dx); a null result is not computed
+void periodic_backward_backward_input(hipStream_t stream, bool triangle, bool fp32, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, MatView x, MatView dL_ddLdx, const void* dL_dy,
+                                       void* dL_ddLdy, uint32_t dy_stride, MatViewMut* dL_dx);
 // Composite encoding reductions (composite.h:47-133): `in` holds the nested outputs [n_nested][n_elems], T = float if fp32 else half
 void composite_reduce_forward(hipStream_t stream, bool fp32, bool product, size_t n_elems, uint32_t n_nested, const void* in, void* out);
 void composite_reduce_backward(hipStream_t stream, bool fp32, bool product, size_t n_elems, uint32_t n_nested, const void* in, const void* dL_dout, void* dL_din);
+// Product, second order: from the nested values, their tangents [n_nested][n_elems] and dL_dout to dL_ddLdout [n_elems] and q [n_nested][n_elems] (either may be null)
+void composite_reduce_backward_backward(hipStream_t stream, bool fp32, size_t n_elems, uint32_t n_nested, const void* in, const void* tangents, const void* dL_dout, void* dL_ddLdout, void* q);
 // SphericalHarmonics: degree^2 outputs, the padding columns FIRST (spherical_harmonics.h:58-64)
 void sh_forward(hipStream_t stream, bool fp32, uint32_t n, uint32_t degree, MatView x, void* out, uint32_t out_stride);
 void sh_backward_input(hipStream_t stream, bool fp32, uint32_t n, uint32_t degree, MatView x, const void* dL_dy, uint32_t dy_stride, MatViewMut dL_dx);
+void sh_backward_backward_input(hipStream_t stream, bool fp32, uint32_t n, uint32_t degree, MatView x, MatView dL_ddLdx, const void* dL_dy, void* dL_ddLdy, uint32_t dy_stride, MatViewMut* dL_dx);
 
 // ------------------------------------------------------------------------------------------------------------------
 // Fully fused MLP.  Weight matrices are row-major [fan_out][fan_in] half, contiguous (fully_fused_mlp.cu:656-671).

@@ -191,8 +191,10 @@ def _create(fn, *args):
 # afterwards; the first-order backward pass is itself differentiable with respect to dL_doutput, input and params (second-order
 # INPUT gradients: eikonal / SDF losses); nothing is propagated through dL_dparams.  The construction is this package's own:
 # one record per call, two Functions that only shuttle tensors in and out of it.  The native second-order pass exists for the
-# grid, PPNG3 and Identity encodings and for CutlassMLP networks, alone or behind one of those encodings; FullyFusedMLP and
-# the other encodings raise the reference's "not implemented error" (for a network: ask for "otype": "CutlassMLP").
+# grid, PPNG3, Identity, Frequency, TriangleWave, SphericalHarmonics and Empty encodings, for a Composite of those (Concatenation,
+# Sum or Product) and for CutlassMLP networks, alone or behind one of those encodings; FullyFusedMLP, OneBlob, PPNG1 / PPNG2 and a
+# Composite that holds one of them (OneBlobFrequency / NRC) raise the reference's "not implemented error" (for a network: ask for
+# "otype": "CutlassMLP").
 # ----------------------------------------------------------------------------------------------------------------------
 class _Call:
     """What one forward call leaves behind for its backward passes."""
