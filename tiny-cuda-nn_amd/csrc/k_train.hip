@@ -21,6 +21,7 @@
 //   order (bitwise reproducible, no atomics) and rounds to fp16.
 #include "mlp_device.h"
 #include "oneblob_device.h"
+#include "mlp_train_kernels.h"
 
 namespace tcnn_amd {
 namespace {
@@ -641,13 +642,7 @@ __global__ void __launch_bounds__(NW * 64) k_mlp_train(const MlpDesc d, const Tr
 	}
 }
 
-struct TrainConfig {
-	int nb, nw, maxt;
-	uint32_t lds_bytes, s;
-	bool ok, image_in_lds;
-	bool pw; // private weight gradients (barrier-free trips), see k_mlp_train
-	bool regw; // all weight fragments in registers, see k_mlp_train
-};
+using TrainConfig = MlpTrainPlan::Config; // ok, (nb, nw, maxt): the instance; s: samples per trip; pw / regw: the special forms below
 
 // (NB, NW, MAXT) triples that are instantiated; pick_config only ever returns one of them
 struct TrainVariant { int width_class, nb, nw, maxt; }; // width_class: 64 or 128
@@ -700,7 +695,7 @@ inline TrainConfig pick_config(const MlpDesc& d) {
 		cfg.ok = true;
 		return cfg;
 	}
-	// Occupancy first: the variant that puts the most waves on a CU (workgroups per CU as mlp_train_fused_grid launches them,
+	// Occupancy first: the variant that puts the most waves on a CU (workgroups per CU as train_grid launches them,
 	// at most 2) wins; among equals, the one whose weight images fit in LDS next to the activation images, then table order.
 	// (Preferring "images in LDS" outright picked a 4-wave workgroup for C2 -- 128 inputs, 56 KB of fragments -- and ran at one
 	// wave per SIMD: 84 us per step against 68 us with 8 waves and the images in L2.)
@@ -732,70 +727,25 @@ inline TrainConfig pick_config(const MlpDesc& d) {
 	return cfg;
 }
 
-// the kernel's short name (Trainer::last_step_kernel): "train<W,NB,NW,MAXT>/relu" or ".../act" (ACT = -1, activation chosen at run time)
-template <int W, int NB, int NW, int MAXT>
-const char* launch_train(hipStream_t stream, const MlpDesc& d, const TrainArgs& a, uint32_t grid, uint32_t lds_bytes) {
-	auto go = [&](auto kernel) {
-		HIP_CHECK_THROW(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-		hipLaunchKernelGGL(kernel, dim3(grid), dim3(NW * 64), lds_bytes, stream, d, a);
-		HIP_CHECK_THROW(hipGetLastError());
-	};
-	static const std::string relu = "train<" + std::to_string(W) + "," + std::to_string(NB) + "," + std::to_string(NW) + "," + std::to_string(MAXT) + ">/relu";
-	static const std::string act = relu.substr(0, relu.size() - 4) + "act";
-	if (d.activation == (uint32_t)Activation::ReLU) {
-		go(k_mlp_train<W, NB, NW, MAXT, (int)Activation::ReLU>);
-		return relu.c_str();
-	}
-	go(k_mlp_train<W, NB, NW, MAXT, -1>);
-	return act.c_str();
+// The instance of k_mlp_train a plan names.  run == false: only its short name (Trainer::last_step_kernel) is wanted -- a static string,
+// ".../relu" or ".../act" (ACT = -1, activation chosen at run time); nullptr: no such instance.
+template <int W, int NB, int NW, int MAXT, bool PW = false, bool REGW = false, bool OB = false>
+const char* train_instance(const char* stem, bool run, hipStream_t stream, const MlpDesc& d, const TrainArgs& a, uint32_t grid, uint32_t lds_bytes) {
+	static const std::string relu_name = (stem ? std::string{stem} : "train<" + std::to_string(W) + "," + std::to_string(NB) + "," + std::to_string(NW) + "," + std::to_string(MAXT) + ">") + "/relu";
+	static const std::string act_name = relu_name.substr(0, relu_name.size() - 4) + "act";
+	const bool relu = d.activation == (uint32_t)Activation::ReLU;
+	if (run && relu) launch_with_lds(k_mlp_train<W, NB, NW, MAXT, (int)Activation::ReLU, PW, REGW, OB>, stream, grid, NW * 64, lds_bytes, d, a);
+	else if (run) launch_with_lds(k_mlp_train<W, NB, NW, MAXT, -1, PW, REGW, OB>, stream, grid, NW * 64, lds_bytes, d, a);
+	return (relu ? relu_name : act_name).c_str();
 }
 
-const char* dispatch_train(hipStream_t stream, const MlpDesc& d, const TrainArgs& a, const TrainConfig& cfg, uint32_t grid) {
-	if (cfg.pw) {
-		auto go = [&](auto kernel) {
-			HIP_CHECK_THROW(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cfg.lds_bytes));
-			hipLaunchKernelGGL(kernel, dim3(grid), dim3(8 * 64), cfg.lds_bytes, stream, d, a);
-			HIP_CHECK_THROW(hipGetLastError());
-		};
-		const bool relu = d.activation == (uint32_t)Activation::ReLU;
-		if (cfg.maxt == 28) {
-			if (relu) go(k_mlp_train<64, 1, 8, 28, (int)Activation::ReLU, true>);
-			else go(k_mlp_train<64, 1, 8, 28, -1, true>);
-			return relu ? "train_pw28/relu" : "train_pw28/act";
-		}
-		if (relu) go(k_mlp_train<64, 1, 8, 32, (int)Activation::ReLU, true>);
-		else go(k_mlp_train<64, 1, 8, 32, -1, true>);
-		return relu ? "train_pw32/relu" : "train_pw32/act";
-	}
-	if (cfg.regw) {
-		auto go = [&](auto kernel) {
-			HIP_CHECK_THROW(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cfg.lds_bytes));
-			hipLaunchKernelGGL(kernel, dim3(grid), dim3(8 * 64), cfg.lds_bytes, stream, d, a);
-			HIP_CHECK_THROW(hipGetLastError());
-		};
-		if (d.activation == (uint32_t)Activation::ReLU) {
-			go(k_mlp_train<64, 1, 8, 8, (int)Activation::ReLU, false, true>);
-			return "train_regw/relu";
-		}
-		go(k_mlp_train<64, 1, 8, 8, -1, false, true>);
-		return "train_regw/act";
-	}
-	if (a.ob_log2) { // the OneBlob input is evaluated in the kernel: one shape (C2's)
-		CHECK_THROW((int)d.width == 64 && cfg.nb == 1 && cfg.nw == 8 && cfg.maxt == 8 && !cfg.pw && !cfg.regw);
-		auto go = [&](auto kernel) {
-			HIP_CHECK_THROW(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cfg.lds_bytes));
-			hipLaunchKernelGGL(kernel, dim3(grid), dim3(8 * 64), cfg.lds_bytes, stream, d, a);
-			HIP_CHECK_THROW(hipGetLastError());
-		};
-		if (d.activation == (uint32_t)Activation::ReLU) {
-			go(k_mlp_train<64, 1, 8, 8, (int)Activation::ReLU, false, false, true>);
-			return "train_ob/relu";
-		}
-		go(k_mlp_train<64, 1, 8, 8, -1, false, false, true>);
-		return "train_ob/act";
-	}
+const char* dispatch_train(bool run, hipStream_t stream, const MlpDesc& d, const TrainArgs& a, const TrainConfig& cfg, bool oneblob, uint32_t grid) {
+	if (cfg.pw && cfg.maxt == 28) return train_instance<64, 1, 8, 28, true>("train_pw28", run, stream, d, a, grid, cfg.lds_bytes);
+	if (cfg.pw) return train_instance<64, 1, 8, 32, true>("train_pw32", run, stream, d, a, grid, cfg.lds_bytes);
+	if (cfg.regw) return train_instance<64, 1, 8, 8, false, true>("train_regw", run, stream, d, a, grid, cfg.lds_bytes);
+	if (oneblob) return train_instance<64, 1, 8, 8, false, false, true>("train_ob", run, stream, d, a, grid, cfg.lds_bytes); // one shape (C2's): oneblob_takes
 #define TCNN_TRAIN_CASE(W_, NB_, NW_, MAXT_) \
-	if ((int)d.width == W_ && cfg.nb == NB_ && cfg.nw == NW_ && cfg.maxt == MAXT_) return launch_train<W_, NB_, NW_, MAXT_>(stream, d, a, grid, cfg.lds_bytes);
+	if ((int)d.width == W_ && cfg.nb == NB_ && cfg.nw == NW_ && cfg.maxt == MAXT_) return train_instance<W_, NB_, NW_, MAXT_>(nullptr, run, stream, d, a, grid, cfg.lds_bytes);
 	TCNN_TRAIN_CASE(64, 1, 8, 8)
 	TCNN_TRAIN_CASE(64, 2, 4, 8)
 	TCNN_TRAIN_CASE(64, 2, 4, 16)
@@ -805,60 +755,88 @@ const char* dispatch_train(hipStream_t stream, const MlpDesc& d, const TrainArgs
 	TCNN_TRAIN_CASE(128, 1, 8, 32)
 	TCNN_TRAIN_CASE(128, 1, 4, 32)
 #undef TCNN_TRAIN_CASE
-	throw std::runtime_error{"mlp_train_fused: no kernel instance for this configuration"};
+	return nullptr;
+}
+
+bool train_config_takes(const TrainConfig& cfg, uint32_t n) { return cfg.ok && n > 0 && n % cfg.s == 0; }
+// A OneBlob encoding of n_bins bins can be evaluated inside the kernel: by r32ob and by the one train_ob instance (C2's shape), for
+// networks and batches with that configuration of k_train.hip -- never by the family of k_train_regs.hip (regs: regs_shape)
+bool oneblob_takes(const MlpDesc& d, uint32_t n, uint32_t n_bins, bool regs, const TrainConfig& cfg) {
+	return n_bins >= 32 && (n_bins & (n_bins - 1)) == 0 && !regs && train_config_takes(cfg, n) && d.width == 64 && cfg.nb == 1 && cfg.nw == 8 && cfg.maxt == 8 && !cfg.pw && !cfg.regw;
+}
+// workgroups of k_mlp_train: a trip each, up to two per CU where their LDS allows it
+uint32_t train_grid(const TrainConfig& cfg, uint32_t n) {
+	if (!cfg.ok) return 0;
+	const uint32_t per_cu = std::max(1u, (160u * 1024u) / std::max(cfg.lds_bytes, 1u));
+	return std::max(1u, std::min(n / cfg.s, 256 * std::min(per_cu, 2u)));
 }
 
 } // namespace
 
-bool mlp_train_fused_oneblob_supported(const MlpDesc& d, uint32_t n, uint32_t n_bins) {
-	if (n_bins < 32 || (n_bins & (n_bins - 1)) != 0 || mlp_train_regs_supported(d, n)) return false;
-	const TrainConfig cfg = pick_config(d);
-	return cfg.ok && n % cfg.s == 0 && n > 0 && d.width == 64 && cfg.nb == 1 && cfg.nw == 8 && cfg.maxt == 8 && !cfg.pw && !cfg.regw;
+// ---- the dispatcher: the one place where the step's kernel and its grid are chosen.
+// Order of preference: r32ob, r32w, the family of k_train_regs.hip's shapes (r32 / r32a, then regs_fast / regs), k_train.hip's table.
+// A request with weight gradients for a network and batch of that family belongs to the family alone, and k_train.hip alone evaluates
+// OneBlob encodings of other shapes than r32ob's: what they do not take has no kernel.
+MlpTrainPlan mlp_train_plan(const MlpDesc& d, const MlpTrainRequest& r) {
+	MlpTrainPlan p;
+	p.request = r;
+	const Switches sw = switches();
+	TrainConfig cfg{};
+	bool cfg_picked = false;
+	auto config = [&]() -> const TrainConfig& { // k_train.hip's configuration, read from the environment at most once and only where it is asked
+		if (!cfg_picked) cfg = pick_config(d);
+		cfg_picked = true;
+		return cfg;
+	};
+	const bool regs = regs_shape(d, r.n, sw);
+	if (r.oneblob_bins && !oneblob_takes(d, r.n, r.oneblob_bins, regs, config())) return p;
+	if (r32ob_plan(d, r, sw, p)) p.ok = true;
+	else if (r32w_plan(d, r, sw, p)) { // keeps the grid k_train.hip's table would launch for this network
+		p.grid = train_grid(config(), r.n);
+		p.ok = p.grid >= 1;
+	} else if (r.gradients && regs) p.ok = r32_plan(d, r, sw, p) || regs_plan(d, r, sw, p);
+	else if (!r.compact_context && train_config_takes(config(), r.n)) { // compact context matrices are a feature of k_train_regs.hip
+		p.kernel = MlpTrainKernel::Train;
+		p.config = cfg;
+		// (a network and batch of k_train_regs.hip's shapes that wants no weight gradients has always run here over that file's grid; the two
+		// formulas differ where the configuration leaves room for two workgroups per CU, and no slab depends on it)
+		p.grid = regs ? regs_grid(r.n) : train_grid(cfg, r.n);
+		p.name = dispatch_train(false, nullptr, d, TrainArgs{}, cfg, r.oneblob_bins != 0, p.grid);
+		p.ok = p.name != nullptr;
+	}
+	if (!p.ok) p.name = "";
+	return p;
 }
 
-bool mlp_train_fused_supported(const MlpDesc& d, uint32_t n) {
-	if (mlp_train_regs_supported(d, n)) return true;
-	const TrainConfig cfg = pick_config(d);
-	return cfg.ok && n % cfg.s == 0 && n > 0;
-}
+bool mlp_train_any_kernel(const MlpDesc& d, uint32_t n) { return regs_shape(d, n, switches()) || train_config_takes(pick_config(d), n); }
 
-uint32_t mlp_train_fused_grid(const MlpDesc& d, uint32_t n, uint32_t oneblob_bins, uint32_t oneblob_dims) {
-	if (oneblob_bins && mlp_train_r32ob_shape(d, n, oneblob_bins, oneblob_dims)) return mlp_train_r32ob_grid(n); // mlp_train_fused: the same test
-	if (mlp_train_regs_supported(d, n)) return mlp_train_regs_grid(d, n);
-	const TrainConfig cfg = pick_config(d);
-	if (!cfg.ok) return 0;
-	const uint32_t trips = n / cfg.s;
-	const uint32_t per_cu = std::max(1u, (160u * 1024u) / std::max(cfg.lds_bytes, 1u));
-	const uint32_t cap = 256 * std::min(per_cu, 2u);
-	return std::max(1u, std::min(trips, cap));
-}
+bool mlp_train_oneblob_in_kernel(const MlpDesc& d, uint32_t n, uint32_t n_bins) { return oneblob_takes(d, n, n_bins, regs_shape(d, n, switches()), pick_config(d)); }
 
-const char* mlp_train_fused(hipStream_t stream, const MlpDesc& d, const void* image, uint32_t n, const void* x, uint32_t x_plane_features, const float* target, const float* data_pdf,
-                            const void* external_dL_dy, uint32_t dims, LossType loss, float loss_scale, void* out, void* dL_dout, float* L, bool compact_context, void* dL_dx,
-                            uint32_t dx_plane_features, const float* dx_record_x, uint32_t dx_record_dims, float* slabs, uint32_t n_params, const MlpOneBlobInput* oneblob) {
-	CHECK_THROW(!oneblob || mlp_train_fused_oneblob_supported(d, n, oneblob->n_bins));
-	if (!compact_context && mlp_train_r32ob_applies(d, n, oneblob, data_pdf, external_dL_dy, dims, loss, out, dL_dx, slabs)) {
-		mlp_train_r32ob(stream, d, image, n, *oneblob, target, dims, loss, loss_scale, out, dL_dout, L, slabs, n_params);
-		return "r32ob";
+bool mlp_train_compact_context(const MlpDesc& d, uint32_t n) { return regs_shape(d, n, switches()); }
+
+void mlp_train_launch(hipStream_t stream, const MlpDesc& d, const MlpTrainPlan& p, const MlpTrainArgs& in) {
+	const MlpTrainRequest& r = p.request;
+	CHECK_THROW(p.ok && p.grid >= 1 && in.image != nullptr);
+	CHECK_THROW(r.oneblob_bins ? in.oneblob_x.data != nullptr : in.x != nullptr);
+	CHECK_THROW((in.data_pdf != nullptr) == r.data_pdf && (in.external_dL_dy != nullptr) == r.external_dL_dy && (in.out != nullptr) == r.out);
+	CHECK_THROW(r.external_dL_dy || (in.target != nullptr && in.dL_dout != nullptr && in.L != nullptr));
+	CHECK_THROW((in.dL_dx != nullptr) == r.dL_dx && (in.dx_record_x != nullptr) == (r.dx_record_dims != 0));
+	CHECK_THROW((in.slabs != nullptr) == r.gradients);
+	switch (p.kernel) {
+	case MlpTrainKernel::R32ob: return r32ob_launch(stream, d, p, in);
+	case MlpTrainKernel::R32w: return r32w_launch(stream, d, p, in);
+	case MlpTrainKernel::R32:
+	case MlpTrainKernel::R32a: return r32_launch(stream, d, p, in);
+	case MlpTrainKernel::Regs: return regs_launch(stream, d, p, in);
+	default: break;
 	}
-	if (!compact_context && mlp_train_r32w_applies(d, n, x_plane_features, data_pdf, external_dL_dy, dims, loss, out, dL_dx, dx_plane_features, dx_record_x, slabs, oneblob != nullptr)) {
-		mlp_train_r32w(stream, d, image, n, x, target, dims, loss, loss_scale, out, dL_dout, L, dL_dx, slabs, n_params, mlp_train_fused_grid(d, n));
-		return "r32w";
-	}
-	if (mlp_train_regs_supported(d, n) && slabs != nullptr) { // without weight gradients (GradientMode::Ignore): the kernels below
-		CHECK_THROW(compact_context || external_dL_dy);
-		return mlp_train_regs(stream, d, image, n, x, x_plane_features, target, data_pdf, external_dL_dy, dims, loss, loss_scale, out, dL_dout, L, dL_dx, dx_plane_features,
-		                      dx_record_x, dx_record_dims, slabs, n_params);
-	}
-	CHECK_THROW(!compact_context); // compact context matrices are a feature of k_train_regs.hip
-	const TrainConfig cfg = pick_config(d);
-	CHECK_THROW(cfg.ok && n % cfg.s == 0);
-	TrainArgs a{(const half_t*)x, target, data_pdf, (const half_t*)external_dL_dy, (half_t*)out, (half_t*)dL_dout, L, (half_t*)dL_dx, slabs, (const h8*)image,
-	            n, dims, (uint32_t)loss, loss_scale, dx_plane_features, n_params, cfg.image_in_lds ? 1u : 0u, dx_record_x, dx_record_dims, x_plane_features, MatView{}, 0u, 0u, nullptr};
-	if (oneblob) {
-		a.ob_x = oneblob->x;
-		a.ob_dims = oneblob->n_dims;
-		while ((1u << a.ob_log2) < oneblob->n_bins) ++a.ob_log2;
+	const TrainConfig& cfg = p.config;
+	TrainArgs a{(const half_t*)in.x, in.target, in.data_pdf, (const half_t*)in.external_dL_dy, (half_t*)in.out, (half_t*)in.dL_dout, in.L, (half_t*)in.dL_dx, in.slabs, (const h8*)in.image,
+	            r.n, r.dims, (uint32_t)r.loss, in.loss_scale, r.dx_plane_features, in.n_params, cfg.image_in_lds ? 1u : 0u, in.dx_record_x, r.dx_record_dims, r.x_plane_features, MatView{}, 0u, 0u, nullptr};
+	if (r.oneblob_bins) {
+		a.ob_x = in.oneblob_x;
+		a.ob_dims = r.oneblob_dims;
+		while ((1u << a.ob_log2) < r.oneblob_bins) ++a.ob_log2;
 	}
 #ifdef TCNN_AMD_DEV // laboratory build (build.py --dev): in-kernel clocks of the 5th launch
 	static const bool timing = getenv("TCNN_AMD_MLP_TIMING") != nullptr;
@@ -867,14 +845,13 @@ const char* mlp_train_fused(hipStream_t stream, const MlpDesc& d, const void* im
 #else
 	int timing_left = 0; (void)timing_left;
 #endif
-	const char* name = dispatch_train(stream, d, a, cfg, mlp_train_fused_grid(d, n));
+	dispatch_train(true, stream, d, a, cfg, r.oneblob_bins != 0, p.grid);
 	if (a.dbg) {
 		unsigned long long h[8];
 		HIP_CHECK_THROW(hipMemcpy(h, a.dbg, 64, hipMemcpyDeviceToHost));
 		if (--timing_left == 0) fprintf(stderr, "k_mlp_train wave 0 clocks over its trips: fwd %llu loss %llu bwd %llu dX+stores %llu barrier1 %llu wgrad %llu barrier2 %llu\n", h[0], h[1], h[2], h[3], h[4], h[5], h[6]);
 		(void)hipFree(a.dbg);
 	}
-	return name;
 }
 
 } // namespace tcnn_amd

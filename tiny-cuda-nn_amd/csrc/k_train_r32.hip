@@ -22,6 +22,7 @@
 #include "r32_device.h"
 #include "r32_train.h"
 #include "mlp_side_jobs.h"
+#include "mlp_train_kernels.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -87,7 +88,7 @@ __global__ void __launch_bounds__(R32_NW * 64, 2) k_mlp_train_r32(const R32Args 
 	// ---- global addressing: raw buffer accesses -- descriptor (scalar, per matrix) + a lane offset that never changes + a scalar offset of the
 	// trip's 32-sample block: the trip loop spends one scalar addition per stream on addresses and no vector instruction (as plain
 	// pointers the compiler carried 64-bit vector addresses: ~40 vector and ~50 scalar instructions per trip).  Offsets are 32-bit
-	// (mlp_train_r32_applies caps n); an access beyond a matrix would be dropped by the range check instead of faulting.
+	// (r32_plan caps n); an access beyond a matrix would be dropped by the range check instead of faulting.
 	// STORES of 16 bytes take the block's offset in the vector offset (one addition) and no scalar offset: with a scalar-register
 	// offset the compiler assumes the hardware needs no wait state between such a store and a vector instruction that overwrites
 	// its data registers (GCNHazardRecognizer: "only if the instruction is not using a register in the soffset field"); on gfx950 it
@@ -489,71 +490,57 @@ __global__ void __launch_bounds__(R32_NW * 64, 2) k_mlp_train_r32(const R32Args 
 
 } // namespace
 
-// TCNN_AMD_MLP_R32=0 keeps k_train_regs.hip's kernel (A/B runs; Switches, read once per model)
-static bool r32_enabled() { return switches().mlp_r32; }
-
-// the one shape this kernel is instantiated for, with the formats of the grid encoding's training step: input as level planes of 2
-// features, <= 4 outputs, ReLU, L2 / RelativeL2, `out` and 2-D scatter records written, no data_pdf
-bool mlp_train_r32_applies(const MlpDesc& d, uint32_t n, uint32_t x_plane_features, const float* data_pdf, const void* external_dL_dy, uint32_t dims, LossType loss, const void* out,
-                           const void* dL_dx, uint32_t dx_plane_features, const float* dx_record_x, uint32_t dx_record_dims) {
-	if (!r32_enabled() || !r32_shape_ok(d) || d.in_width != 32 || d.n_hidden != 2 || d.n_frags_r32 != (uint32_t)R32_NF) return false;
+// The one shape these kernels are instantiated for, with the formats of the grid encoding's training step: input as level planes of 2
+// features, <= 4 outputs, ReLU, L2 / RelativeL2, `out` and 2-D scatter records (or plain level planes) written, no data_pdf, compact context
+// matrices.  Asked for the networks and batches of k_train_regs.hip only (regs_shape), whose slabs it shares; TCNN_AMD_MLP_R32=0 keeps
+// that file's kernel.
+bool r32_plan(const MlpDesc& d, const MlpTrainRequest& r, const Switches& sw, MlpTrainPlan& p) {
+	if (!sw.mlp_r32 || !r32_shape_ok(d) || d.in_width != 32 || d.n_hidden != 2 || d.n_frags_r32 != (uint32_t)R32_NF) return false;
 	if (d.activation != (uint32_t)Activation::ReLU || d.output_activation != (uint32_t)Activation::None) return false;
-	if (n == 0 || n % 32 != 0 || n > (1u << 22)) return false; // 32-bit byte offsets into [n][...] matrices
-	return x_plane_features == 2 && data_pdf == nullptr && external_dL_dy == nullptr && dims >= 1 && dims <= 4 && (loss == LossType::L2 || loss == LossType::RelativeL2) && out != nullptr &&
-	       dL_dx != nullptr && dx_plane_features == 2 && (dx_record_x == nullptr || dx_record_dims == 2); // records {x, y, gradients} or plain level planes
-}
-
-// Which of the two kernels: k_mlp_train_r32a (k_train_r32a.hip: weights in registers, weight-gradient tiles shared out over a workgroup's
-// waves, no final sum over waves) is the faster one while that final sum is a large part of the launch -- up to 2 trips per wave,
-// 131 072 samples (MLP kernel at 2^14 / 2^16 / 2^17 samples: 7.9 / 12.0 / 16.0 us against 10.1 / 12.6 / 16.7); at 2^18 the two are equal
-// (24.7 us) and k_mlp_train_r32 stays.  TCNN_AMD_MLP_R32A=1 / 0 forces one (A/B runs, tests).
-static bool r32a_chosen(uint32_t n) {
-	const int forced = switches().mlp_r32a;
-	if (forced >= 0) return forced == 1;
-	return n <= 131072u;
-}
-const char* mlp_train_r32_name(uint32_t n) { return r32a_chosen(n) ? "r32a" : "r32"; }
-
-// workgroups = weight-gradient slabs of the kernel mlp_train_r32 launches for this batch
-uint32_t mlp_train_r32_grid(uint32_t n) {
-	if (r32a_chosen(n)) {
+	if (r.n == 0 || r.n % 32 != 0 || r.n > (1u << 22)) return false; // 32-bit byte offsets into [n][...] matrices
+	if (r.oneblob_bins || r.x_plane_features != 2 || r.data_pdf || !loss_l2_or_relative(r) || r.dims < 1 || r.dims > 4 || !r.out || !r.gradients || !r.compact_context) return false;
+	if (!r.dL_dx || r.dx_plane_features != 2 || (r.dx_record_dims != 0 && r.dx_record_dims != 2)) return false; // records {x, y, gradients} or plain level planes
+	// Which of the two kernels: k_mlp_train_r32a (k_train_r32a.hip: weights in registers, weight-gradient tiles shared out over a workgroup's
+	// waves, no final sum over waves) is the faster one while that final sum is a large part of the launch -- up to 2 trips per wave,
+	// 131 072 samples (MLP kernel at 2^14 / 2^16 / 2^17 samples: 7.9 / 12.0 / 16.0 us against 10.1 / 12.6 / 16.7); at 2^18 the two are equal
+	// (24.7 us) and k_mlp_train_r32 stays.  TCNN_AMD_MLP_R32A=1 / 0 forces one (A/B runs, tests).
+	const bool r32a = sw.mlp_r32a >= 0 ? sw.mlp_r32a == 1 : r.n <= 131072u;
+	p.kernel = r32a ? MlpTrainKernel::R32a : MlpTrainKernel::R32;
+	p.name = r32a ? "r32a" : "r32";
+	if (r32a) {
 		uint32_t cap = 512u;
 #ifdef TCNN_AMD_DEV
 		static const uint32_t dev_cap = getenv("TCNN_AMD_MLP_GRID") ? (uint32_t)std::max(1, atoi(getenv("TCNN_AMD_MLP_GRID"))) : 512u; // laboratory knob
 		cap = dev_cap;
 #endif
-		return std::max(1u, std::min(cap, div_round_up(n / 32, (uint32_t)R32A_NW))); // two workgroups of four waves per CU
-	}
-	return std::max(1u, std::min(256u, div_round_up(n / 32, (uint32_t)R32_NW)));
+		p.grid = std::max(1u, std::min(cap, div_round_up(r.n / 32, (uint32_t)R32A_NW))); // two workgroups of four waves per CU
+	} else p.grid = std::max(1u, std::min(256u, div_round_up(r.n / 32, (uint32_t)R32_NW)));
+	return true;
 }
 
-void mlp_train_r32(hipStream_t stream, const MlpDesc& d, const void* image, uint32_t n, const void* x, const float* target, uint32_t dims, LossType loss, float loss_scale, void* out,
-                   void* compact_dL_dout, float* compact_L, void* dL_dx, const float* dx_record_x, float* slabs, uint32_t n_params, uint32_t grid) {
-	CHECK_THROW(slabs != nullptr && compact_dL_dout != nullptr && compact_L != nullptr && target != nullptr);
+void r32_launch(hipStream_t stream, const MlpDesc& d, const MlpTrainPlan& p, const MlpTrainArgs& in) {
+	const uint32_t n = p.request.n, grid = p.grid;
+	const bool r32a = p.kernel == MlpTrainKernel::R32a;
+	const LossType loss = p.request.loss;
 	R32Args a{};
-	a.x = (const half_t*)x;
-	a.target = target;
-	a.out = (half_t*)out;
-	a.dL_dout = (half_t*)compact_dL_dout;
-	a.L = compact_L;
-	a.rec = (u32x4*)dL_dx;
-	a.rec_x = dx_record_x;
-	a.slabs = slabs;
-	a.image = (const h8*)((const char*)image + (size_t)(d.n_frags_fwd + d.n_frags_bwd) * 1024);
+	a.x = (const half_t*)in.x;
+	a.target = in.target;
+	a.out = (half_t*)in.out;
+	a.dL_dout = (half_t*)in.dL_dout;
+	a.L = in.L;
+	a.rec = (u32x4*)in.dL_dx;
+	a.rec_x = in.dx_record_x;
+	a.slabs = in.slabs;
+	a.image = (const h8*)((const char*)in.image + (size_t)(d.n_frags_fwd + d.n_frags_bwd) * 1024);
 	a.n = n;
-	a.dims = dims;
-	a.n_params = n_params;
+	a.dims = p.request.dims;
+	a.n_params = in.n_params;
 	for (int l = 0; l < 3; ++l) a.w_off[l] = d.layers[l].w_off;
-	a.loss_scale = loss_scale;
-	auto go = [&](auto kernel) {
-		HIP_CHECK_THROW(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, R32_LDS_BYTES));
-		hipLaunchKernelGGL(kernel, dim3(grid), dim3(R32_NW * 64), R32_LDS_BYTES, stream, a);
-		HIP_CHECK_THROW(hipGetLastError());
-	};
+	a.loss_scale = in.loss_scale;
+	auto go = [&](auto kernel) { launch_with_lds(kernel, stream, grid, R32_NW * 64, R32_LDS_BYTES, a); };
 	a.prio_mode = switches().mlp_prio;
-	CHECK_THROW(grid == mlp_train_r32_grid(n));
 #ifndef TCNN_AMD_DEV
-	if (r32a_chosen(n)) return mlp_train_r32a_launch(stream, a, grid, loss == LossType::L2 ? 1 : 2);
+	if (r32a) return r32a_launch(stream, a, grid, loss == LossType::L2 ? 1 : 2);
 	if (loss == LossType::L2) { if (a.rec_x) go(k_mlp_train_r32<1, true>); else go(k_mlp_train_r32<1, false>); }
 	else { if (a.rec_x) go(k_mlp_train_r32<2, true>); else go(k_mlp_train_r32<2, false>); }
 #else
@@ -568,8 +555,8 @@ void mlp_train_r32(hipStream_t stream, const MlpDesc& d, const void* image, uint
 	if (const char* e = getenv("TCNN_AMD_MLP_STAGGER")) a.stagger = (uint32_t)atoi(e);
 	static const int diag_env = getenv("TCNN_AMD_MLP_DIAG") ? atoi(getenv("TCNN_AMD_MLP_DIAG")) : 0;
 	const int diag = a.rec_x ? diag_env : 0; // (the timing-only variants exist in the record form)
-	if (r32a_chosen(n)) {
-		mlp_train_r32a_launch(stream, a, grid, loss == LossType::L2 ? 1 : 2);
+	if (r32a) {
+		r32a_launch(stream, a, grid, loss == LossType::L2 ? 1 : 2);
 		if (a.dbg) {
 			std::vector<unsigned long long> hst((size_t)grid * (7 + 4 * R32A_NW));
 			HIP_CHECK_THROW(hipMemcpy(hst.data(), a.dbg, hst.size() * 8, hipMemcpyDeviceToHost));

@@ -17,11 +17,12 @@
 //     clock -- is the wall, 30 KiB per wave and trip; measured 9.6 k clocks per trip against k_mlp_train_r32's 6.2 k.)
 // Measured ("The 32x32x16 kernels"): what the missing fill and final sum save, the two barriers per trip and the doubled
 // transposing reads give back at 4 trips per wave (24.7 us both at 2^18 samples); with fewer trips this kernel is the faster one
-// (2^14 / 2^16 / 2^17 samples: 7.9 / 12.0 / 16.0 us against 10.1 / 12.6 / 16.7) and mlp_train_r32 launches it up to 131 072 samples.
+// (2^14 / 2^16 / 2^17 samples: 7.9 / 12.0 / 16.0 us against 10.1 / 12.6 / 16.7) and r32_plan (k_train_r32.hip) chooses it up to 131 072 samples.
 // The chain's instructions and their order are k_mlp_train_r32's: outputs, context matrices and scatter records are bit-identical;
 // the weight gradients differ in the order of the fp32 sum (per slab 4 x trips blocks in tile order instead of 8 waves' partial sums).
 #include "r32_train.h"
 #include "mlp_side_jobs.h"
+#include "mlp_train_kernels.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -403,12 +404,8 @@ __global__ void __launch_bounds__(R32A_NW * 64, 2) k_mlp_train_r32a(const R32Arg
 
 } // namespace
 
-void mlp_train_r32a_launch(hipStream_t stream, const R32Args& a, uint32_t grid, int loss_id) {
-	auto go = [&](auto kernel) {
-		HIP_CHECK_THROW(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, A_LDS_BYTES));
-		hipLaunchKernelGGL(kernel, dim3(grid), dim3(R32A_NW * 64), A_LDS_BYTES, stream, a);
-		HIP_CHECK_THROW(hipGetLastError());
-	};
+void r32a_launch(hipStream_t stream, const R32Args& a, uint32_t grid, int loss_id) {
+	auto go = [&](auto kernel) { launch_with_lds(kernel, stream, grid, R32A_NW * 64, A_LDS_BYTES, a); };
 	if (loss_id == 1) { if (a.rec_x) go(k_mlp_train_r32a<1, true>); else go(k_mlp_train_r32a<1, false>); }
 	else { if (a.rec_x) go(k_mlp_train_r32a<2, true>); else go(k_mlp_train_r32a<2, false>); }
 }

@@ -8,7 +8,7 @@
 //   * dW0 alone is 8 tiles of 32 x 32: with dW1 and dWout 208 accumulator registers if every wave keeps every tile.  A wave runs alone on
 //     its SIMD (4 waves per workgroup, 512 registers each), accumulators in the ACCUMULATION registers (AGPRs; the matrix instructions that
 //     add into them are inline assembly, every other one is a builtin that the compiler places in ordinary registers: -mllvm
-//     -amdgpu-mfma-vgpr-form, build.py).  Two forms, chosen by the launch's length (mlp_train_r32ob):
+//     -amdgpu-mfma-vgpr-form, build.py).  Two forms, chosen by the launch's length (r32ob_plan):
 //       - k_mlp_train_r32ob (up to 4 trips per wave; BASELINE config 2 has 2): the TILES are shared out over the workgroup's waves as in
 //         k_train_r32w.hip -- wave w owns 2 tiles of dW0, 1 of dW1 and half of dWout, 64 registers, summed over the samples of all four
 //         waves: every wave reads every wave's images between two workgroup barriers per trip (dH1 and dH0 have images of their own),
@@ -24,6 +24,7 @@
 #include "r32_device.h"
 #include "mlp_side_jobs.h"
 #include "oneblob_device.h"
+#include "mlp_train_kernels.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -774,39 +775,41 @@ __global__ void __launch_bounds__(OB_NW * 64, 1) k_mlp_train_r32ob_acc(const ObA
 
 } // namespace
 
-// TCNN_AMD_MLP_R32=0 keeps k_train.hip's kernel
-static bool r32ob_enabled() { return switches().mlp_r32; }
-
-bool mlp_train_r32ob_shape(const MlpDesc& d, uint32_t n, uint32_t n_bins, uint32_t n_dims) {
-	if (!r32ob_enabled() || d.width != 64 || d.in_width != 128 || d.out_width != 16 || d.n_hidden != 2 || d.n_frags_r32 == 0) return false;
+// the one shape this kernel is instantiated for, padded context matrices, weight gradients wanted (TCNN_AMD_MLP_R32=0 keeps k_train.hip's kernel)
+bool r32ob_plan(const MlpDesc& d, const MlpTrainRequest& r, const Switches& sw, MlpTrainPlan& p) {
+	if (!sw.mlp_r32 || d.width != 64 || d.in_width != 128 || d.out_width != 16 || d.n_hidden != 2 || d.n_frags_r32 == 0) return false;
 	if (d.activation != (uint32_t)Activation::ReLU || d.output_activation != (uint32_t)Activation::None) return false;
-	return n > 0 && n % 32 == 0 && n <= (1u << 22) && n_bins == 64 && n_dims == 2;
+	if (r.n == 0 || r.n % 32 != 0 || r.n > (1u << 22) || r.oneblob_bins != 64 || r.oneblob_dims != 2) return false;
+	if (r.compact_context || r.data_pdf || !loss_l2_or_relative(r) || r.dims < 1 || r.dims > 4 || !r.out || r.dL_dx || !r.gradients) return false;
+	p.kernel = MlpTrainKernel::R32ob;
+	p.name = "r32ob";
+	p.grid = std::max(1u, std::min(256u, div_round_up(r.n / 32, (uint32_t)OB_NW)));
+	// Which form: the shared tiles spare the final sum over waves (7.5 k clocks) and cost 1.25 k clocks more per trip (two barriers, the tile
+	// products behind the chain instead of inside it) -- they win up to 4 trips per wave (131 072 samples), the per-wave accumulators beyond
+	// (the reference's benchmark protocol at 2^21 samples: 6.8e9 against 5.95e9 samples/s).  TCNN_AMD_MLP_R32OB_FORM=shared|acc forces one.
+	p.r32ob_shared = div_round_up(r.n / 32, p.grid * OB_NW) <= 4;
+#ifdef TCNN_AMD_DEV
+	if (const char* e = getenv("TCNN_AMD_MLP_R32OB_FORM")) p.r32ob_shared = e[0] == 's';
+#endif
+	return true;
 }
-uint32_t mlp_train_r32ob_grid(uint32_t n) { return std::max(1u, std::min(256u, div_round_up(n / 32, (uint32_t)OB_NW))); }
 
-bool mlp_train_r32ob_applies(const MlpDesc& d, uint32_t n, const MlpOneBlobInput* oneblob, const float* data_pdf, const void* external_dL_dy, uint32_t dims, LossType loss, const void* out,
-                             const void* dL_dx, const float* slabs) {
-	return oneblob && mlp_train_r32ob_shape(d, n, oneblob->n_bins, oneblob->n_dims) && data_pdf == nullptr && external_dL_dy == nullptr && dims >= 1 && dims <= 4 &&
-	       (loss == LossType::L2 || loss == LossType::RelativeL2) && out != nullptr && dL_dx == nullptr && slabs != nullptr;
-}
-
-void mlp_train_r32ob(hipStream_t stream, const MlpDesc& d, const void* image, uint32_t n, const MlpOneBlobInput& oneblob, const float* target, uint32_t dims, LossType loss, float loss_scale,
-                     void* out, void* dL_dout, float* L, float* slabs, uint32_t n_params) {
-	CHECK_THROW(slabs != nullptr && dL_dout != nullptr && L != nullptr && target != nullptr && out != nullptr);
+void r32ob_launch(hipStream_t stream, const MlpDesc& d, const MlpTrainPlan& p, const MlpTrainArgs& in) {
+	const uint32_t n = p.request.n, grid = p.grid;
+	const bool shared = p.r32ob_shared, l2 = p.request.loss == LossType::L2;
 	ObArgs a{};
-	a.x = oneblob.x;
-	a.target = target;
-	a.out = (half_t*)out;
-	a.dL_dout = (half_t*)dL_dout;
-	a.L = L;
-	a.slabs = slabs;
-	a.image = (const h8*)((const char*)image + (size_t)(d.n_frags_fwd + d.n_frags_bwd) * 1024);
+	a.x = in.oneblob_x;
+	a.target = in.target;
+	a.out = (half_t*)in.out;
+	a.dL_dout = (half_t*)in.dL_dout;
+	a.L = in.L;
+	a.slabs = in.slabs;
+	a.image = (const h8*)((const char*)in.image + (size_t)(d.n_frags_fwd + d.n_frags_bwd) * 1024);
 	a.n = n;
-	a.dims = dims;
-	a.n_params = n_params;
+	a.dims = p.request.dims;
+	a.n_params = in.n_params;
 	for (int l = 0; l < 3; ++l) a.w_off[l] = d.layers[l].w_off;
-	a.loss_scale = loss_scale;
-	const uint32_t grid = mlp_train_r32ob_grid(n);
+	a.loss_scale = in.loss_scale;
 #ifdef TCNN_AMD_DEV // laboratory build (build.py --dev): in-kernel clocks of the 5th launch
 	static const bool timing = getenv("TCNN_AMD_MLP_TIMING") != nullptr;
 	static int timing_left = 5;
@@ -817,25 +820,12 @@ void mlp_train_r32ob(hipStream_t stream, const MlpDesc& d, const void* image, ui
 #else
 	int timing_left = 0; (void)timing_left;
 #endif
-	auto go = [&](auto kernel, int lds_bytes) {
-		HIP_CHECK_THROW(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-		hipLaunchKernelGGL(kernel, dim3(grid), dim3(OB_NW * 64), lds_bytes, stream, a);
-		HIP_CHECK_THROW(hipGetLastError());
-	};
-	// Which form: the shared tiles spare the final sum over waves (7.5 k clocks) and cost 1.25 k clocks more per trip (two barriers, the tile
-	// products behind the chain instead of inside it) -- they win up to 4 trips per wave (131 072 samples), the per-wave accumulators beyond
-	// (the reference's benchmark protocol at 2^21 samples: 6.8e9 against 5.95e9 samples/s).  TCNN_AMD_MLP_R32OB_FORM=shared|acc forces one.
-	const uint32_t trips = div_round_up(n / 32, grid * OB_NW);
-	bool shared = trips <= 4;
-#ifdef TCNN_AMD_DEV
-	if (const char* e = getenv("TCNN_AMD_MLP_R32OB_FORM")) shared = e[0] == 's';
-#endif
 	if (shared) {
-		if (loss == LossType::L2) go(k_mlp_train_r32ob<1>, OB_LDS_BYTES);
-		else go(k_mlp_train_r32ob<2>, OB_LDS_BYTES);
+		if (l2) launch_with_lds(k_mlp_train_r32ob<1>, stream, grid, OB_NW * 64, OB_LDS_BYTES, a);
+		else launch_with_lds(k_mlp_train_r32ob<2>, stream, grid, OB_NW * 64, OB_LDS_BYTES, a);
 	} else {
-		if (loss == LossType::L2) go(k_mlp_train_r32ob_acc<1>, OBA_LDS_BYTES);
-		else go(k_mlp_train_r32ob_acc<2>, OBA_LDS_BYTES);
+		if (l2) launch_with_lds(k_mlp_train_r32ob_acc<1>, stream, grid, OB_NW * 64, OBA_LDS_BYTES, a);
+		else launch_with_lds(k_mlp_train_r32ob_acc<2>, stream, grid, OB_NW * 64, OBA_LDS_BYTES, a);
 	}
 	if (a.dbg) {
 		std::vector<unsigned long long> hst((size_t)grid * 6);
@@ -848,7 +838,7 @@ void mlp_train_r32ob(hipStream_t stream, const MlpDesc& d, const void* image, ui
 				tail += (double)(hst[g * 4 + 3] - hst[g * 4 + 2]);
 			}
 			fprintf(stderr, "k_mlp_train_r32ob%s wave 0 clocks, mean over %u workgroups: fill %.0f trips %.0f (%u blocks of 32 per wave) %s %.0f\n", shared ? "" : "_acc", grid, fill / grid,
-			        loop / grid, trips, shared ? "slab stores" : "final sum", tail / grid);
+			        loop / grid, div_round_up(n / 32, grid * OB_NW), shared ? "slab stores" : "final sum", tail / grid);
 			unsigned long long s0 = ~0ull, s1 = 0, e0 = ~0ull, e1 = 0;
 			for (uint32_t g = 0; g < grid; ++g) {
 				const unsigned long long st = hst[(size_t)grid * 4 + g * 2], en = hst[(size_t)grid * 4 + g * 2 + 1];

@@ -16,6 +16,7 @@
 //     reads), context matrices in the reference's padded form [n][16].
 #include "r32_device.h"
 #include "mlp_side_jobs.h"
+#include "mlp_train_kernels.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -366,37 +367,34 @@ __global__ void __launch_bounds__(W_NW * 64, 1) k_mlp_train_r32w(const WArgs a) 
 
 } // namespace
 
-static bool r32w_enabled() { return switches().mlp_r32; }
-
-bool mlp_train_r32w_shape(const MlpDesc& d, uint32_t n) {
-	if (!r32w_enabled() || d.width != 128 || d.in_width != 64 || d.out_width != 16 || d.n_hidden != 2 || d.n_frags_r32 != (uint32_t)W_NFRAGS) return false;
+// the one shape this kernel is instantiated for, padded context matrices, weight gradients wanted (TCNN_AMD_MLP_R32=0 keeps k_train.hip's kernels)
+bool r32w_plan(const MlpDesc& d, const MlpTrainRequest& r, const Switches& sw, MlpTrainPlan& p) {
+	if (!sw.mlp_r32 || d.width != 128 || d.in_width != 64 || d.out_width != 16 || d.n_hidden != 2 || d.n_frags_r32 != (uint32_t)W_NFRAGS) return false;
 	if (d.activation != (uint32_t)Activation::ReLU || d.output_activation != (uint32_t)Activation::None) return false;
-	return n > 0 && n % 32 == 0 && n <= (1u << 22);
+	if (r.n == 0 || r.n % 32 != 0 || r.n > (1u << 22) || r.oneblob_bins || r.x_plane_features != 4) return false;
+	if (r.compact_context || r.data_pdf || !loss_l2_or_relative(r) || r.dims < 1 || r.dims > 4 || !r.out || !r.gradients) return false;
+	if (!r.dL_dx || r.dx_plane_features != 4 || r.dx_record_dims != 0) return false;
+	p.kernel = MlpTrainKernel::R32w;
+	p.name = "r32w";
+	return true;
 }
 
-bool mlp_train_r32w_applies(const MlpDesc& d, uint32_t n, uint32_t x_plane_features, const float* data_pdf, const void* external_dL_dy, uint32_t dims, LossType loss, const void* out,
-                            const void* dL_dx, uint32_t dx_plane_features, const float* dx_record_x, const float* slabs, bool oneblob) {
-	return mlp_train_r32w_shape(d, n) && !oneblob && x_plane_features == 4 && data_pdf == nullptr && external_dL_dy == nullptr && dims >= 1 && dims <= 4 &&
-	       (loss == LossType::L2 || loss == LossType::RelativeL2) && out != nullptr && dL_dx != nullptr && dx_plane_features == 4 && dx_record_x == nullptr && slabs != nullptr;
-}
-
-void mlp_train_r32w(hipStream_t stream, const MlpDesc& d, const void* image, uint32_t n, const void* x, const float* target, uint32_t dims, LossType loss, float loss_scale, void* out,
-                    void* dL_dout, float* L, void* dL_dx, float* slabs, uint32_t n_params, uint32_t grid) {
-	CHECK_THROW(grid >= 1 && slabs != nullptr && dL_dout != nullptr && L != nullptr && target != nullptr && out != nullptr && dL_dx != nullptr);
+void r32w_launch(hipStream_t stream, const MlpDesc& d, const MlpTrainPlan& p, const MlpTrainArgs& in) {
+	const uint32_t n = p.request.n, grid = p.grid;
 	WArgs a{};
-	a.x = (const half_t*)x;
-	a.target = target;
-	a.out = (half_t*)out;
-	a.dL_dout = (half_t*)dL_dout;
-	a.L = L;
-	a.dL_dx = (half_t*)dL_dx;
-	a.slabs = slabs;
-	a.image = (const h8*)((const char*)image + (size_t)(d.n_frags_fwd + d.n_frags_bwd) * 1024);
+	a.x = (const half_t*)in.x;
+	a.target = in.target;
+	a.out = (half_t*)in.out;
+	a.dL_dout = (half_t*)in.dL_dout;
+	a.L = in.L;
+	a.dL_dx = (half_t*)in.dL_dx;
+	a.slabs = in.slabs;
+	a.image = (const h8*)((const char*)in.image + (size_t)(d.n_frags_fwd + d.n_frags_bwd) * 1024);
 	a.n = n;
-	a.dims = dims;
-	a.n_params = n_params;
+	a.dims = p.request.dims;
+	a.n_params = in.n_params;
 	for (int l = 0; l < 3; ++l) a.w_off[l] = d.layers[l].w_off;
-	a.loss_scale = loss_scale;
+	a.loss_scale = in.loss_scale;
 #ifdef TCNN_AMD_DEV // laboratory build (build.py --dev): in-kernel clocks of the 5th launch
 	static const bool timing = getenv("TCNN_AMD_MLP_TIMING") != nullptr;
 	static int timing_left = 5;
@@ -407,13 +405,8 @@ void mlp_train_r32w(hipStream_t stream, const MlpDesc& d, const void* image, uin
 #else
 	int timing_left = 0; (void)timing_left;
 #endif
-	auto go = [&](auto kernel) {
-		HIP_CHECK_THROW(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, W_LDS_BYTES));
-		hipLaunchKernelGGL(kernel, dim3(grid), dim3(W_NW * 64), W_LDS_BYTES, stream, a);
-		HIP_CHECK_THROW(hipGetLastError());
-	};
-	if (loss == LossType::L2) go(k_mlp_train_r32w<1>);
-	else go(k_mlp_train_r32w<2>);
+	if (p.request.loss == LossType::L2) launch_with_lds(k_mlp_train_r32w<1>, stream, grid, W_NW * 64, W_LDS_BYTES, a);
+	else launch_with_lds(k_mlp_train_r32w<2>, stream, grid, W_NW * 64, W_LDS_BYTES, a);
 	if (a.dbg) {
 		std::vector<unsigned long long> hst((size_t)grid * 4);
 		HIP_CHECK_THROW(hipMemcpy(hst.data(), a.dbg, hst.size() * 8, hipMemcpyDeviceToHost));

@@ -19,6 +19,7 @@
 //
 // MFMA work per 16 samples: 30 (chain) + 19 (transposes) + 28 (k = 16 weight-gradient products) issue slots of 16 clocks.
 #include "mlp_device.h"
+#include "mlp_train_kernels.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -50,7 +51,7 @@ struct RegsArgs {
 constexpr int REGS_NW = 8; // waves per workgroup
 
 // fragment slots inside the LDS copy of the images for a (16 IN_T) -> 64 -> ... -> 64 -> 16 network; Network's constructor
-// (model.h) lays the images out the same way, checked by mlp_train_regs_supported
+// (model.h) lays the images out the same way, checked by regs_shape
 template <int IN_T, int NH> struct RegsLayout {
 	static constexpr int T = 4, KS = 2;
 	static constexpr int fwd0 = 0;                                   // T fragments (one k-step)
@@ -93,7 +94,7 @@ template <int ACT> __device__ inline h4 act_bwd_tile(const h4 g, const h4 fwd) {
 		return g;
 	}
 }
-// loads / stores at 32-bit byte offsets from wave-uniform bases (saddr + voffset addressing; mlp_train_regs_supported caps n)
+// loads / stores at 32-bit byte offsets from wave-uniform bases (saddr + voffset addressing; regs_shape caps n)
 template <typename V> __device__ inline V ld32(const void* base, const uint32_t byte_off) { return *(const V*)((const char*)base + byte_off); }
 template <typename V> __device__ inline void st32(void* base, const uint32_t byte_off, const V v) { *(V*)((char*)base + byte_off) = v; }
 // the same as a streaming store, for data nobody on the GPU reads soon (the step's outputs: out, dL_doutput, L): it leaves this
@@ -372,7 +373,7 @@ __global__ void __launch_bounds__(REGS_NW * 64, 2) k_mlp_train_regs(const MlpDes
 			o = mfma(frag(Lay::fwd_out + 1), hf[NH - 1][1], o);
 #pragma unroll
 			for (int tc = 0; tc < T; ++tc) ph_t[NH - 1][tc] = transpose_chain(hf[NH - 1][tc / 2], tc & 1);
-			const h4 ov = to_h4(o); // output activation None (mlp_train_regs_supported)
+			const h4 ov = to_h4(o); // output activation None (regs_shape)
 			if constexpr (LOSS == 0) {
 				gv = aux.dy;
 			} else {
@@ -564,44 +565,33 @@ template <int IN_T, int NH> bool regs_layout_matches(const MlpDesc& d) {
 	return (int)d.layers[NH].fwd_off == Lay::fwd_out && (int)(d.n_frags_fwd + d.layers[NH].bwd_off) == Lay::bwd_out;
 }
 
-// returns the kernel's short name (Trainer::last_step_kernel): "regs_fast" (compile-time formats) or "regs"
-template <int IN_T, int NH> const char* launch_regs(hipStream_t stream, const MlpDesc& d, const RegsArgs& a, uint32_t grid, int loss) {
-	const uint32_t lds = regs_lds_bytes<IN_T, NH>();
-	auto go = [&](auto kernel) {
-		HIP_CHECK_THROW(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-		hipLaunchKernelGGL(kernel, dim3(grid), dim3(REGS_NW * 64), lds, stream, d, a);
-		HIP_CHECK_THROW(hipGetLastError());
-	};
+// loss: 0 external dL/dy, 1 L2, 2 RelativeL2; fast: the compile-time formats of k_mlp_train_regs<FAST>
+template <int IN_T, int NH> void launch_regs(hipStream_t stream, const MlpDesc& d, const RegsArgs& a, uint32_t grid, int loss, bool fast) {
+	auto go = [&](auto kernel) { launch_with_lds(kernel, stream, grid, REGS_NW * 64, regs_lds_bytes<IN_T, NH>(), d, a); };
 	const bool relu = d.activation == (uint32_t)Activation::ReLU;
 	constexpr int RELU = (int)Activation::ReLU, NONE = (int)Activation::None;
-	// the compile-time formats of k_mlp_train_regs<FAST> (TCNN_AMD_MLP_FAST=0: the general form, for A/B runs and tests)
-	const bool fast = switches().mlp_fast && loss != 0 && relu && a.x_plane_f == 2 && a.dims <= 4 && a.data_pdf == nullptr && a.out != nullptr && a.dL_dx != nullptr &&
-	                  a.rec_x != nullptr && a.rec_dims == 2 && a.dx_plane_f == 2;
 	if constexpr (IN_T == 2 && NH == 2) {
 #ifdef TCNN_AMD_DEV
 		static const bool phases = getenv("TCNN_AMD_MLP_TIMING") && getenv("TCNN_AMD_MLP_TIMING")[0] == '2';
-		if (phases && a.dbg && fast && loss == 2) {
-			go(k_mlp_train_regs<IN_T, NH, RELU, 2, true, true>);
-			return "regs_fast";
-		}
+		if (phases && a.dbg && fast && loss == 2) return go(k_mlp_train_regs<IN_T, NH, RELU, 2, true, true>);
 #endif
 	}
 	if (fast) {
 		if (loss == 1) go(k_mlp_train_regs<IN_T, NH, RELU, 1, true>);
 		else go(k_mlp_train_regs<IN_T, NH, RELU, 2, true>);
-		return "regs_fast";
+		return;
 	}
 #define TCNN_REGS_CASE(L_) \
 	if (loss == L_) { \
 		if (relu) go(k_mlp_train_regs<IN_T, NH, RELU, L_, false>); \
 		else go(k_mlp_train_regs<IN_T, NH, NONE, L_, false>); \
-		return "regs"; \
+		return; \
 	}
 	TCNN_REGS_CASE(0)
 	TCNN_REGS_CASE(1)
 	TCNN_REGS_CASE(2)
 #undef TCNN_REGS_CASE
-	throw std::runtime_error{"mlp_train_regs: no kernel instance for this loss"};
+	throw std::runtime_error{"regs_launch: no kernel instance for this loss"};
 }
 
 // compact context matrices -> the reference's padded ones: dL_dout [n][16] halves, L [n][16] floats, zero beyond `dims`
@@ -617,15 +607,12 @@ __global__ void __launch_bounds__(256) k_expand_context(const uint32_t n, const 
 } // namespace
 
 // TCNN_AMD_MLP_REGS=0 keeps k_train.hip's kernels (A/B runs; Switches, read once per model)
-static bool regs_enabled() { return switches().mlp_regs; }
-
-bool mlp_train_regs_supported(const MlpDesc& d, uint32_t n) {
-	if (!regs_enabled() || n == 0 || n % 16 != 0 || n > (1u << 22)) return false; // 32-bit byte offsets into [n][...] matrices
+bool regs_shape(const MlpDesc& d, uint32_t n, const Switches& sw) {
+	if (!sw.mlp_regs || n == 0 || n % 16 != 0 || n > (1u << 22)) return false; // 32-bit byte offsets into [n][...] matrices
 	return regs_layout_matches<2, 2>(d) || regs_layout_matches<1, 2>(d) || regs_layout_matches<2, 1>(d) || regs_layout_matches<1, 1>(d);
 }
 
-uint32_t mlp_train_regs_grid(const MlpDesc& d, uint32_t n) {
-	(void)d;
+uint32_t regs_grid(uint32_t n) {
 	uint32_t cap = 256;
 #ifdef TCNN_AMD_DEV
 	if (const char* e = getenv("TCNN_AMD_MLP_GRID")) cap = std::max(1, atoi(e)); // laboratory knob (how the trip time depends on the number of busy CUs: it does not)
@@ -633,23 +620,29 @@ uint32_t mlp_train_regs_grid(const MlpDesc& d, uint32_t n) {
 	return std::max(1u, std::min(cap, div_round_up(n / 16, (uint32_t)REGS_NW)));
 }
 
-const char* mlp_train_regs(hipStream_t stream, const MlpDesc& d, const void* image, uint32_t n, const void* x, uint32_t x_plane_features, const float* target, const float* data_pdf,
-                           const void* external_dL_dy, uint32_t dims, LossType loss, float loss_scale, void* out, void* compact_dL_dout, float* compact_L, void* dL_dx,
-                           uint32_t dx_plane_features, const float* dx_record_x, uint32_t dx_record_dims, float* slabs, uint32_t n_params) {
-	CHECK_THROW(mlp_train_regs_supported(d, n));
-	CHECK_THROW(external_dL_dy != nullptr || (target != nullptr && (loss == LossType::L2 || loss == LossType::RelativeL2)));
-	CHECK_THROW(slabs != nullptr && dims >= 1 && dims <= 16);
-	CHECK_THROW(external_dL_dy || (compact_dL_dout != nullptr && compact_L != nullptr));
-	// BASELINE configs 3 in the formats of the grid encoding's training step: the 32x32x16 kernel (k_train_r32.hip), same slabs
-	if (mlp_train_r32_applies(d, n, x_plane_features, data_pdf, external_dL_dy, dims, loss, out, dL_dx, dx_plane_features, dx_record_x, dx_record_dims)) {
-		mlp_train_r32(stream, d, image, n, x, target, dims, loss, loss_scale, out, compact_dL_dout, compact_L, dL_dx, dx_record_x, slabs, n_params, mlp_train_r32_grid(n));
-		return mlp_train_r32_name(n);
-	}
-	RegsArgs a{(const half_t*)x, target, data_pdf, (const half_t*)external_dL_dy, (half_t*)out, (half_t*)compact_dL_dout, compact_L, (half_t*)dL_dx, slabs, (const h8*)image,
-	           dx_record_x, n, dims, dx_record_dims, x_plane_features, dx_plane_features, n_params, loss_scale, 1u, nullptr};
+// Weight gradients are part of the kernel, and dL_dout / L leave it as compact matrices [n][dims] (96 of the 256 bytes per sample the
+// padded ones would add to the kernel's stores are zeros; mlp_expand_context produces the reference's [n][16] matrices from them).
+bool regs_plan(const MlpDesc& d, const MlpTrainRequest& r, const Switches& sw, MlpTrainPlan& p) {
+	if (!r.gradients || !regs_shape(d, r.n, sw) || r.oneblob_bins) return false;
+	if (!(r.external_dL_dy || (r.compact_context && loss_l2_or_relative(r))) || r.dims < 1 || r.dims > 16) return false;
+	p.regs_in_tiles = (int)d.in_width / 16;
+	p.regs_hidden = (int)d.n_hidden;
+	// TCNN_AMD_MLP_FAST=0: the general form, for A/B runs and tests
+	p.regs_fast = sw.mlp_fast && !r.external_dL_dy && d.activation == (uint32_t)Activation::ReLU && r.x_plane_features == 2 && r.dims <= 4 && !r.data_pdf && r.out && r.dL_dx &&
+	              r.dx_record_dims == 2 && r.dx_plane_features == 2;
+	p.kernel = MlpTrainKernel::Regs;
+	p.name = p.regs_fast ? "regs_fast" : "regs";
+	p.grid = regs_grid(r.n);
+	return true;
+}
+
+void regs_launch(hipStream_t stream, const MlpDesc& d, const MlpTrainPlan& p, const MlpTrainArgs& in) {
+	const MlpTrainRequest& r = p.request;
+	const uint32_t n = r.n, grid = p.grid;
+	RegsArgs a{(const half_t*)in.x, in.target, in.data_pdf, (const half_t*)in.external_dL_dy, (half_t*)in.out, (half_t*)in.dL_dout, in.L, (half_t*)in.dL_dx, in.slabs, (const h8*)in.image,
+	           in.dx_record_x, n, r.dims, r.dx_record_dims, r.x_plane_features, r.dx_plane_features, in.n_params, in.loss_scale, 1u, nullptr};
 	a.prio_mode = switches().mlp_prio;
-	const int loss_id = external_dL_dy ? 0 : (loss == LossType::L2 ? 1 : 2);
-	const uint32_t grid = mlp_train_regs_grid(d, n);
+	const int loss_id = r.external_dL_dy ? 0 : (r.loss == LossType::L2 ? 1 : 2);
 #ifdef TCNN_AMD_DEV // laboratory build (build.py --dev): in-kernel clocks of the 5th launch
 	static const bool timing = getenv("TCNN_AMD_MLP_TIMING") != nullptr;
 	static int timing_left = 5;
@@ -660,11 +653,10 @@ const char* mlp_train_regs(hipStream_t stream, const MlpDesc& d, const void* ima
 #else
 	int timing_left = 0; (void)timing_left;
 #endif
-	const char* name;
-	if (regs_layout_matches<2, 2>(d)) name = launch_regs<2, 2>(stream, d, a, grid, loss_id);
-	else if (regs_layout_matches<1, 2>(d)) name = launch_regs<1, 2>(stream, d, a, grid, loss_id);
-	else if (regs_layout_matches<2, 1>(d)) name = launch_regs<2, 1>(stream, d, a, grid, loss_id);
-	else name = launch_regs<1, 1>(stream, d, a, grid, loss_id);
+	if (p.regs_in_tiles == 2 && p.regs_hidden == 2) launch_regs<2, 2>(stream, d, a, grid, loss_id, p.regs_fast);
+	else if (p.regs_in_tiles == 1 && p.regs_hidden == 2) launch_regs<1, 2>(stream, d, a, grid, loss_id, p.regs_fast);
+	else if (p.regs_in_tiles == 2 && p.regs_hidden == 1) launch_regs<2, 1>(stream, d, a, grid, loss_id, p.regs_fast);
+	else launch_regs<1, 1>(stream, d, a, grid, loss_id, p.regs_fast);
 	if (a.dbg) {
 		std::vector<unsigned long long> h((size_t)grid * (4 + REGS_NW + 8));
 		HIP_CHECK_THROW(hipMemcpy(h.data(), a.dbg, h.size() * 8, hipMemcpyDeviceToHost));
@@ -700,7 +692,6 @@ const char* mlp_train_regs(hipStream_t stream, const MlpDesc& d, const void* ima
 		}
 		(void)hipFree(a.dbg);
 	}
-	return name;
 }
 
 void mlp_expand_context(hipStream_t stream, uint32_t n, uint32_t dims, const void* compact_dL_dout, const float* compact_L, void* dL_dout, float* L) {

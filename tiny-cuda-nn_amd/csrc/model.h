@@ -221,7 +221,7 @@ struct EncodingContext {
 	uint64_t hit_generation = 0; // the encoding's list counters are reused by later forward passes: lists are valid while this is the latest one on its stream
 	const void* hit_stream = nullptr;
 	uint32_t n = 0;
-	mutable bool dy_records = false; // the level planes handed to backward() hold 16-byte scatter records {coordinates, gradients} (mlp_train_fused); set by the caller of backward()
+	mutable bool dy_records = false; // the level planes handed to backward() hold 16-byte scatter records {coordinates, gradients} (MlpTrainRequest::dx_record_dims); set by the caller of backward()
 	// Set by the caller of backward() for a step whose optimizer update may ride on the gradient kernel (AdamInFlush, arrays
 	// indexed from this encoding's first parameter).  An encoding that takes the offer reports in adam_done which of its
 	// parameters it has updated; whatever is not listed there is still the optimizer's to do.
@@ -2396,7 +2396,7 @@ public:
 	static bool use_fused_step() { return switches().fused_step; }
 	// TCNN_AMD_SIDE_JOBS=0: k_mlp_prep stays a launch of its own (A/B runs; read per step so that tests cover both)
 	static bool side_jobs_enabled() { return switches().side_jobs; }
-	bool fused_step_supported(uint32_t n) const { return use_fused_step() && !m_network->layerwise() && mlp_train_fused_supported(m_network->desc(), n); }
+	bool fused_step_supported(uint32_t n) const { return use_fused_step() && !m_network->layerwise() && mlp_train_any_kernel(m_network->desc(), n); }
 	// the fused step of a model without encoding parameters hands its weight gradients to the optimizer inside the slab reduction
 	bool optimizer_rides_on_reduce() const { return m_encoding->n_params() == 0; }
 	// TCNN_AMD_LIVE_IMAGE=0: every step builds its fragment images with k_mlp_prep again instead of keeping one current (Network::live_image;
@@ -2405,17 +2405,17 @@ public:
 	bool live_image_kept() const { return m_live_image_kept; }           // the last fused step's optimizer launch left the live image current
 	void invalidate_live_image() { m_network->invalidate_live_image(); } // the parameters change(d) some other way
 	size_t image_preps() const { return m_image_preps; }                 // k_mlp_prep launches of fused steps so far (a test's view of the above)
-	const char* last_train_kernel() const { return m_last_train_kernel; } // short name of the MLP kernel the last fused step launched (mlp_train_fused)
+	const char* last_train_kernel() const { return m_last_train_kernel; } // short name of the MLP kernel the last fused step launched (MlpTrainPlan::name)
 	uint64_t scatter_wide_fallbacks() { return m_encoding->scatter_wide_fallbacks(); }
 	uint64_t list_scatters() const override { return m_encoding->list_scatters(); }
 	bool context_keeps_slabs(const ModelContext& c) const { const Ctx* x = dynamic_cast<const Ctx*>(&c); return x && (bool)x->slabs_kept; }
 	// the register-resident fused kernel (k_train_regs.hip) writes dL_doutput / L as compact [n][dims] matrices (TrainContext::compact)
 	bool fused_compact_context_supported(uint32_t n) const {
 		if (m_network->layerwise()) return false;
-		const bool ok = use_fused_step() && mlp_train_regs_supported(m_network->desc(), n) && m_network->padded_output_width() == 16;
+		const bool ok = use_fused_step() && mlp_train_compact_context(m_network->desc(), n) && m_network->padded_output_width() == 16;
 		// the register-resident kernels address [n][...] matrices with 32-bit byte offsets: beyond 2^22 rows the step silently took the
 		// much slower LDS-image kernel -- say so once (a caller can split the batch)
-		if (!ok && use_fused_step() && n > (1u << 22) && mlp_train_regs_supported(m_network->desc(), 1u << 22)) {
+		if (!ok && use_fused_step() && n > (1u << 22) && mlp_train_compact_context(m_network->desc(), 1u << 22)) {
 			static bool told = false;
 			if (!told) {
 				told = true;
@@ -2453,7 +2453,7 @@ public:
 		if (m_network->layerwise()) throw std::runtime_error{"NetworkWithInputEncoding::fused_encode: a layer-by-layer network has no fused training step"};
 		// a OneBlob encoding is evaluated by the MLP kernels inside their input load where they can (k_mlp.hip, k_train.hip)
 		if (!prepare_input_gradients && m_encoding->as_oneblob() && m_encoding->padded_output_width() == m_network->input_width() &&
-		    mlp_train_fused_oneblob_supported(m_network->desc(), n, m_encoding->as_oneblob())) {
+		    mlp_train_oneblob_in_kernel(m_network->desc(), n, m_encoding->as_oneblob())) {
 			ctx.oneblob_bins = m_encoding->as_oneblob();
 			ctx.fused = true;
 			return;
@@ -2511,21 +2511,42 @@ public:
 			++m_image_preps;
 			image_data = prepared.data();
 		}
+		// which kernel, and over how many workgroups: decided once, here (mlp_train_plan); each workgroup writes one weight-gradient slab
+		MlpTrainRequest request;
+		request.n = n;
+		request.x_plane_features = x_plane_f;
+		request.oneblob_bins = ctx.oneblob_bins;
+		request.oneblob_dims = ctx.oneblob_bins ? m_encoding->input_width() : 0u;
+		request.dims = m_network->output_width();
+		request.loss = loss;
+		request.external_dL_dy = external_dL_dy != nullptr;
+		request.data_pdf = data_pdf != nullptr;
+		request.out = out != nullptr;
+		request.dL_dx = need_dx;
+		request.dx_plane_features = plane_f;
+		request.dx_record_dims = records ? m_encoding->input_width() : 0u;
+		request.gradients = mode != GradientMode::Ignore;
+		request.compact_context = compact_context;
+		const MlpTrainPlan plan = mlp_train_plan(d, request);
+		if (!plan.ok) throw std::runtime_error{"NetworkWithInputEncoding: no fused training kernel for this network, batch and set of options"};
+		CHECK_THROW(gradients != nullptr || !request.gradients);
+		const uint32_t n_slabs = request.gradients ? plan.grid : 0u;
 		ArenaBuf slabs;
-		uint32_t n_slabs = 0;
-		if (mode != GradientMode::Ignore) {
-			CHECK_THROW(gradients != nullptr);
-			// the 32x32x16 kernels of BASELINE configs 3 have a grid of their own (k_train_r32.hip); the test is the one mlp_train_regs makes
-			const bool r32 = !ctx.oneblob_bins && mlp_train_regs_supported(d, n) && mlp_train_r32_applies(d, n, x_plane_f, data_pdf, external_dL_dy, m_network->output_width(), loss, out,
-			                                                           need_dx ? dL_dnetwork_input.data() : nullptr, plane_f, records ? input.data : nullptr, records ? m_encoding->input_width() : 0u);
-			n_slabs = r32 ? mlp_train_r32_grid(n) : mlp_train_fused_grid(d, n, ctx.oneblob_bins, ctx.oneblob_bins ? m_encoding->input_width() : 0u);
-			slabs = ArenaBuf{stream, (size_t)n_slabs * n_net * sizeof(float)};
-		}
-		const MlpOneBlobInput oneblob_input{input, m_encoding->input_width(), ctx.oneblob_bins};
+		if (n_slabs) slabs = ArenaBuf{stream, (size_t)n_slabs * n_net * sizeof(float)};
+		MlpTrainArgs args;
+		args.image = image_data;
+		args.x = ctx.network_input.data();
+		if (ctx.oneblob_bins) args.oneblob_x = input;
+		args.target = target, args.data_pdf = data_pdf, args.external_dL_dy = external_dL_dy;
+		args.loss_scale = loss_scale;
+		args.out = out, args.dL_dout = dL_dout, args.L = L;
+		args.dL_dx = dL_dnetwork_input.data();
+		args.dx_record_x = records ? input.data : nullptr;
+		args.slabs = slabs.as<float>();
+		args.n_params = n_net;
 		if (profile) profile->mark(stream, StepProfile::MlpKernel, false);
-		m_last_train_kernel = mlp_train_fused(stream, d, image_data, n, ctx.network_input.data(), x_plane_f, target, data_pdf, external_dL_dy, m_network->output_width(), loss, loss_scale, out, dL_dout, L, compact_context,
-		                dL_dnetwork_input.data(), plane_f, records ? input.data : nullptr, records ? m_encoding->input_width() : 0u, slabs.as<float>(), n_net,
-		                ctx.oneblob_bins ? &oneblob_input : nullptr);
+		mlp_train_launch(stream, d, plan, args);
+		m_last_train_kernel = plan.name;
 		if (profile) profile->mark(stream, StepProfile::MlpKernel, true);
 		// (Carrying the slab reduction on the grid scatter's launch the way k_mlp_prep rides on the forward kernel was built and
 		// measured: its workgroups each take a whole CU's LDS slot for a few microseconds, in front of the task list they delay the

@@ -40,6 +40,6 @@ struct R32Args {
 constexpr int R32A_NW = 4; // waves per workgroup of k_mlp_train_r32a: one per SIMD
 
 // loss_id 1: L2, 2: RelativeL2; grid = workgroups = slabs
-void mlp_train_r32a_launch(hipStream_t stream, const R32Args& a, uint32_t grid, int loss_id);
+void r32a_launch(hipStream_t stream, const R32Args& a, uint32_t grid, int loss_id);
 
 } // namespace tcnn_amd

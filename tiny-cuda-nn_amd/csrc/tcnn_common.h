@@ -320,7 +320,6 @@ void mlp_forward(hipStream_t stream, const MlpDesc& d, const void* image, uint32
 //           the float matrix itself with the Identity encoding applied on the fly ((half)(x * scale + offset), padding = 1), or
 //           with the OneBlob encoding applied on the fly (x_oneblob_bins);
 //   output: out_half [n][out_width] and / or out_f32: the first out_f32_dims outputs as floats (trim_and_cast, object.cu:61-67).
-struct MlpOneBlobInput { MatView x; uint32_t n_dims, n_bins; }; // coordinates [n][n_dims] (any layout), n_bins a power of two >= 32
 struct MlpIo {
 	const void* x_half;
 	uint32_t x_plane_features;
@@ -337,60 +336,65 @@ void mlp_forward_io(hipStream_t stream, const MlpDesc& d, const void* image, uin
 // dx_plane_features = 0: dL_dx is AoS [n][in_width]; = F > 0: "level planes" [in_width / F][n][F] (what the grid scatter reads)
 void mlp_backward(hipStream_t stream, const MlpDesc& d, const void* image, uint32_t n, const void* dL_dout, const void* out, const void* hidden, void* dhidden, void* dL_dx,
                   uint32_t dx_plane_features);
-// ---- the Trainer's fused step (k_train.hip): forward + loss + backward + weight gradients in one kernel.
-// Supported when out_width <= 32, width in {64, 128} and the activations of one trip fit in LDS; else use the pieces above.
-bool mlp_train_fused_supported(const MlpDesc& d, uint32_t n);
-uint32_t mlp_train_fused_grid(const MlpDesc& d, uint32_t n, uint32_t oneblob_bins = 0, uint32_t oneblob_dims = 0); // workgroups = number of weight-gradient slabs (oneblob_*: the encoding is evaluated inside the kernel)
-// x [n][in_width] half (x_plane_features = 0) or level planes [in_width / F][n][F] (x_plane_features = F in {2, 4, 8}).
-// target / data_pdf [n][dims] float or external_dL_dy [n][out_width] half (loss-scaled).
-// compact_context (only where mlp_train_regs_supported() and slabs != nullptr): dL_dout and L are the COMPACT matrices [n][dims]
-// (the live columns of the padded ones; mlp_expand_context pads them), else the padded [n][out_width] ones.
-// Writes out, dL_dout, L ([n][out_width]; dL_dout and L only without external_dL_dy), dL_dx (optional; AoS or level planes),
-// and -- if slabs != nullptr -- one fp32 slab of partial weight gradients per workgroup: slabs[grid][n_params].
-// dx_record_x != nullptr (with dx_plane_features = F): dL_dx is written as 16-byte scatter records {coordinates (dx_record_dims
-// floats, read from dx_record_x [n][dims]), gradient halves}, float4 [in_width / F][n] or, for 2 dims and F = 2, [in_width / 4][n]
-// with two levels per record (mlp_device.h store_dx_record); needs 4 dims + 2 F <= 16.
-// Returns the launched kernel's short name, a static string (Trainer::last_step_kernel): "r32", "r32a", "r32w", "r32ob", "regs_fast",
-// "regs", "train<W,NB,NW,MAXT>/relu|act", "train_pw28|train_pw32|train_regw|train_ob/relu|act" (act: the activation chosen at run time).
-const char* mlp_train_fused(hipStream_t stream, const MlpDesc& d, const void* image, uint32_t n, const void* x, uint32_t x_plane_features, const float* target, const float* data_pdf,
-                            const void* external_dL_dy, uint32_t dims, LossType loss, float loss_scale, void* out, void* dL_dout, float* L, bool compact_context, void* dL_dx,
-                            uint32_t dx_plane_features, const float* dx_record_x, uint32_t dx_record_dims, float* slabs, uint32_t n_params, const MlpOneBlobInput* oneblob = nullptr);
-// oneblob (optional; x is then not read): the network's input is the OneBlob encoding of these coordinates, evaluated inside the kernel
-// (mlp_train_fused_oneblob_supported says whether this network / batch has such a kernel)
-bool mlp_train_fused_oneblob_supported(const MlpDesc& d, uint32_t n, uint32_t n_bins);
-// ---- the same step for (16 | 32) -> 64 -> [64 ->] 16 networks with everything in registers (k_train_regs.hip): no LDS images, no
-// barriers, transposes on the matrix cores.  mlp_train_fused* dispatch to it when it applies (TCNN_AMD_MLP_REGS=0: never).
-// Writes dL_dout and L as compact matrices [n][dims] (96 of the 256 bytes per sample the padded ones would add to the kernel's
-// stores are zeros); mlp_expand_context produces the reference's [n][16] matrices from them.  Requires slabs != nullptr.
-bool mlp_train_regs_supported(const MlpDesc& d, uint32_t n);
-uint32_t mlp_train_regs_grid(const MlpDesc& d, uint32_t n);
-const char* mlp_train_regs(hipStream_t stream, const MlpDesc& d, const void* image, uint32_t n, const void* x, uint32_t x_plane_features, const float* target, const float* data_pdf,
-                           const void* external_dL_dy, uint32_t dims, LossType loss, float loss_scale, void* out, void* compact_dL_dout, float* compact_L, void* dL_dx,
-                           uint32_t dx_plane_features, const float* dx_record_x, uint32_t dx_record_dims, float* slabs, uint32_t n_params); // the kernel's name, as mlp_train_fused
-// ---- the same step for 32 -> 64 -> 64 -> 16 networks fed by a 2-D grid encoding with 2 features per level, on the 32x32x16 matrix
-// instruction (k_train_r32.hip): 32 samples per wave and trip, operands of the weight-gradient products transposed through wave-private
-// LDS images.  mlp_train_regs dispatches to it (TCNN_AMD_MLP_R32=0: never); `grid` workgroups write one slab each.
-bool mlp_train_r32_applies(const MlpDesc& d, uint32_t n, uint32_t x_plane_features, const float* data_pdf, const void* external_dL_dy, uint32_t dims, LossType loss, const void* out,
-                           const void* dL_dx, uint32_t dx_plane_features, const float* dx_record_x, uint32_t dx_record_dims);
-uint32_t mlp_train_r32_grid(uint32_t n); // workgroups (= slabs) of the launch: the caller sizes `slabs` with it
-const char* mlp_train_r32_name(uint32_t n); // "r32a" or "r32": which of the two kernels mlp_train_r32 launches for this batch
-void mlp_train_r32(hipStream_t stream, const MlpDesc& d, const void* image, uint32_t n, const void* x, const float* target, uint32_t dims, LossType loss, float loss_scale, void* out,
-                   void* compact_dL_dout, float* compact_L, void* dL_dx, const float* dx_record_x, float* slabs, uint32_t n_params, uint32_t grid);
-// ---- BASELINE config 2's step, OneBlob(64 bins, 2 dims) -> 64 -> 64 -> 16 with the encoding evaluated in the kernel, on the 32x32x16
-// matrix instruction (k_train_r32ob.hip): one wave per SIMD, weight-gradient accumulators in AGPRs.  mlp_train_fused dispatches to it.
-bool mlp_train_r32ob_shape(const MlpDesc& d, uint32_t n, uint32_t n_bins, uint32_t n_dims);
-uint32_t mlp_train_r32ob_grid(uint32_t n);
-bool mlp_train_r32ob_applies(const MlpDesc& d, uint32_t n, const MlpOneBlobInput* oneblob, const float* data_pdf, const void* external_dL_dy, uint32_t dims, LossType loss, const void* out,
-                             const void* dL_dx, const float* slabs);
-void mlp_train_r32ob(hipStream_t stream, const MlpDesc& d, const void* image, uint32_t n, const MlpOneBlobInput& oneblob, const float* target, uint32_t dims, LossType loss, float loss_scale,
-                     void* out, void* dL_dout, float* L, float* slabs, uint32_t n_params);
-// ---- BASELINE config 5's MLP part, 64 -> 128 -> 128 -> 16 fed by level planes of 4 features, on the 32x32x16 matrix instruction
-// (k_train_r32w.hip): the weight-gradient tiles shared out over a workgroup's four waves, fragments from L2.  mlp_train_fused dispatches
-// to it with the grid of mlp_train_fused_grid.
-bool mlp_train_r32w_applies(const MlpDesc& d, uint32_t n, uint32_t x_plane_features, const float* data_pdf, const void* external_dL_dy, uint32_t dims, LossType loss, const void* out,
-                            const void* dL_dx, uint32_t dx_plane_features, const float* dx_record_x, const float* slabs, bool oneblob);
-void mlp_train_r32w(hipStream_t stream, const MlpDesc& d, const void* image, uint32_t n, const void* x, const float* target, uint32_t dims, LossType loss, float loss_scale, void* out,
-                    void* dL_dout, float* L, void* dL_dx, float* slabs, uint32_t n_params, uint32_t grid);
+// ---- the Trainer's fused step: forward + loss + backward + weight gradients in ONE kernel, one of about twenty (k_train.hip: LDS images,
+// any 64- / 128-wide network with <= 32 outputs; k_train_regs.hip: (16 | 32) -> 64 -> [64 ->] 16 with everything in registers;
+// k_train_r32{,a}.hip, k_train_r32ob.hip, k_train_r32w.hip: BASELINE configs 3, 2 and 5 on the 32x32x16 matrix instruction).  Which one runs
+// and over how many workgroups is decided ONCE per step, by mlp_train_plan, from a request that holds everything the choice depends on;
+// the caller sizes the weight-gradient slabs with the plan's grid and hands the same plan to mlp_train_launch, which decides nothing.
+struct MlpTrainRequest {
+	uint32_t n = 0;
+	// the network's input: half AoS [n][in_width] (both 0), level planes [in_width / F][n][F] (x_plane_features = F in {2, 4, 8}), or the
+	// OneBlob encoding of oneblob_dims coordinates per sample evaluated inside the kernel (oneblob_bins > 0, a power of two >= 32)
+	uint32_t x_plane_features = 0, oneblob_bins = 0, oneblob_dims = 0;
+	uint32_t dims = 0;               // live outputs: columns of target / data_pdf
+	LossType loss = LossType::L2;    // unused with external_dL_dy
+	bool external_dL_dy = false;     // dL/dy [n][out_width] half (loss-scaled) comes from the caller: no target, no loss, dL_dout and L not written
+	bool data_pdf = false;
+	bool out = false;                // the network's output [n][out_width] is written
+	// dL/d(input): none; AoS [n][in_width] (dx_plane_features = 0); level planes of F features; or -- dx_record_dims = k > 0, with planes --
+	// 16-byte scatter records {k coordinates (floats, read from dx_record_x [n][k]), gradient halves}, float4 [in_width / F][n] or, for
+	// 2 dims and F = 2, [in_width / 4][n] with two levels per record (mlp_device.h store_dx_record; needs 4 k + 2 F <= 16)
+	bool dL_dx = false;
+	uint32_t dx_plane_features = 0, dx_record_dims = 0;
+	bool gradients = false;          // weight gradients: one fp32 slab of partial sums per workgroup, slabs [plan.grid][n_params]
+	bool compact_context = false;    // dL_dout and L are the COMPACT matrices [n][dims] (mlp_expand_context pads them), else [n][out_width]
+};
+enum class MlpTrainKernel : uint32_t { None, R32ob, R32w, R32, R32a, Regs, Train }; // Regs: "regs_fast" | "regs"; Train: the k_train.hip table
+struct MlpTrainPlan {
+	bool ok = false;                 // false: no fused kernel takes this request (name says nothing then)
+	MlpTrainKernel kernel = MlpTrainKernel::None;
+	// the kernel's short name, a static string (Trainer::last_step_kernel): "r32", "r32a", "r32w", "r32ob", "regs_fast", "regs",
+	// "train<W,NB,NW,MAXT>/relu|act", "train_pw28|train_pw32|train_regw|train_ob/relu|act" (act: the activation chosen at run time)
+	const char* name = "";
+	uint32_t grid = 0;               // workgroups of the launch = weight-gradient slabs
+	MlpTrainRequest request;
+	// what the chosen kernel's launch needs besides:
+	struct Config { int nb, nw, maxt; uint32_t lds_bytes, s; bool ok, image_in_lds, pw, regw; } config{}; // Train: the instance of k_mlp_train (pw: private weight gradients, regw: weight fragments in registers)
+	int regs_in_tiles = 0, regs_hidden = 0; // Regs: the instance's input tiles of 16 and hidden layers
+	bool regs_fast = false;          // Regs: compile-time formats
+	bool r32ob_shared = false;       // R32ob: shared weight-gradient tiles, else per-wave accumulators
+};
+// Pure host code: no GPU call, no allocation.  Reads the process switches (switches()) and k_train.hip's per-call environment
+// variables (TCNN_AMD_MLP_PW / _REGW / _IMAGE_LDS / _VARIANT) when called -- once per step.
+MlpTrainPlan mlp_train_plan(const MlpDesc& d, const MlpTrainRequest& request);
+struct MlpTrainArgs {
+	const void* image = nullptr;                           // the network's fragment images
+	const void* x = nullptr;                               // the network's input (not with OneBlob)
+	MatView oneblob_x{};                                   // with OneBlob: the coordinates [n][oneblob_dims], any layout
+	const float *target = nullptr, *data_pdf = nullptr;    // [n][dims]
+	const void* external_dL_dy = nullptr;
+	float loss_scale = 1.0f;
+	void *out = nullptr, *dL_dout = nullptr, *dL_dx = nullptr;
+	float *L = nullptr, *slabs = nullptr;
+	const float* dx_record_x = nullptr;
+	uint32_t n_params = 0;                                 // floats per slab
+};
+// launches plan.grid workgroups of plan's kernel; args must be what plan.request describes (checked)
+void mlp_train_launch(hipStream_t stream, const MlpDesc& d, const MlpTrainPlan& plan, const MlpTrainArgs& args);
+// what a caller asks before it knows the whole request -- the kernels' own predicates, as mlp_train_plan applies them:
+bool mlp_train_any_kernel(const MlpDesc& d, uint32_t n);                          // some fused kernel takes batches of n samples
+bool mlp_train_oneblob_in_kernel(const MlpDesc& d, uint32_t n, uint32_t n_bins);  // one of them evaluates a OneBlob encoding of n_bins bins itself
+bool mlp_train_compact_context(const MlpDesc& d, uint32_t n);                     // the kernel for (d, n) with weight gradients writes compact context matrices
 void mlp_expand_context(hipStream_t stream, uint32_t n, uint32_t dims, const void* compact_dL_dout, const float* compact_L, void* dL_dout, float* L);
 // grad[i] (=|+=) sum_k slabs[k][i], fixed order, rounded to half once
 // adam (optional, not with accumulate): the optimizer's update of these (matrix) weights is applied behind the reduction, bit-identical to adam_step run afterwards
