@@ -56,6 +56,7 @@ typedef struct tcnn_module_s* tcnn_module_t;       /* tcnn::cpp::Module         
 typedef struct tcnn_context_s* tcnn_context_t;     /* tcnn::cpp::Context           cpp_api.h:82-84  */
 typedef struct tcnn_trainer_s* tcnn_trainer_t;     /* tcnn::TrainableModel         config.h:46-51   */
 typedef struct tcnn_train_ctx_s* tcnn_train_ctx_t; /* Trainer::ForwardContext      trainer.h:89-95  */
+typedef struct tcnn_optimizer_s* tcnn_optimizer_t; /* tcnn::Optimizer<T>            optimizer.h:40-66 */
 typedef void* tcnn_stream_t;                       /* hipStream_t */
 
 const char* tcnn_last_error(void);
@@ -238,6 +239,43 @@ float tcnn_trainer_max_level(tcnn_trainer_t t);
 /* Introspection: 1 when this context owns the network's weight-gradient slabs because their reduction was left to the optimizer's
  * launch (tcnn_trainer_optimizer_prologue_steps): they must outlive training_step()'s own scope, until that launch is enqueued. */
 int tcnn_train_ctx_keeps_weight_gradient_slabs(tcnn_trainer_t t, tcnn_train_ctx_t ctx);
+
+
+/* ---- standalone optimizers (optimizer.h:44-95, src/optimizer.cu:50-82): the optimizers a trainer runs, for callers that compute the
+ * gradients themselves -- Adam, SGD, Novograd, Ema, ExponentialDecay, Average, Batched, Lookahead, Composite, nested as in a trainer's
+ * "optimizer" configuration.
+ * tcnn_module_layer_sizes: the (rows, cols) of the module's weight matrices in parameter order -- what Optimizer::allocate takes beside
+ * n_params (matrix weights come first in the parameter vector; Adam's l2_reg and non_matrix_learning_rate_factor, Novograd's layers and
+ * Composite's slices go by them).  Writes min(n_layers, capacity) pairs into rows_cols and the full count into *n_layers_out.
+ * tcnn_optimizer_create: the configuration is checked before anything is allocated ("Invalid optimizer type: ..." needs no device);
+ * layer_sizes holds n_layers (rows, cols) pairs.
+ * tcnn_optimizer_step: one step on `stream`.  params_full_precision float[n_params] and params_half half[n_params] are the caller's:
+ * the fp32 master weights and the half working copy, both updated (a non-matrix parameter whose gradient is zero keeps both, adam.h:76-84).
+ * gradients: n_params values in gradient_precision -- TCNN_PRECISION_FP16, scaled by loss_scale like a trainer's, or TCNN_PRECISION_FP32
+ * (a caller's own, e.g. a PyTorch .grad: loss_scale 1 when they are unscaled already).  Both forms run the same arithmetic on the unscaled
+ * value; fp32 gradients are not rounded to half anywhere (Batched hands its fp32 mean to the nested optimizer as it is).
+ * serialize / deserialize: the MessagePack bytes of the object a trainer's snapshot carries as its "optimizer" entry (tcnn_trainer_serialize),
+ * so the two are interchangeable; the buffer belongs to the handle until its next serialize call or its destruction.  Both synchronise
+ * with the device.
+ * custom_weights: half[n_params] the optimizer keeps for inference (Ema, Average, Lookahead; Composite when a nested one has any), or NULL.
+ * The getters return 0 / NaN / NULL and leave a message in tcnn_last_error() when given a NULL handle.
+ * weights_restored: call after overwriting params_half by other means, and after deserialize (optimizers that assemble their custom
+ * weights from several sources -- Composite -- rebuild them from params_half; a snapshot does not carry them). */
+int         tcnn_module_layer_sizes(tcnn_module_t m, uint32_t* rows_cols, size_t capacity, size_t* n_layers_out);
+int         tcnn_optimizer_create(const char* optimizer_json, size_t n_params, const uint32_t* layer_sizes, size_t n_layers, tcnn_optimizer_t* out);
+void        tcnn_optimizer_destroy(tcnn_optimizer_t o);
+int         tcnn_optimizer_step(tcnn_optimizer_t o, tcnn_stream_t stream, float loss_scale, float* params_full_precision, void* params_half,
+                                const void* gradients, int gradient_precision);                 /* optimizer.h:49 */
+uint32_t    tcnn_optimizer_step_count(tcnn_optimizer_t o);                                      /* optimizer.h:52 step() */
+size_t      tcnn_optimizer_n_params(tcnn_optimizer_t o);                                        /* optimizer.h:53 n_weights() */
+float       tcnn_optimizer_learning_rate(tcnn_optimizer_t o);                                   /* optimizer.h:50 */
+int         tcnn_optimizer_set_learning_rate(tcnn_optimizer_t o, float learning_rate);          /* optimizer.h:51 */
+int         tcnn_optimizer_update_hyperparams(tcnn_optimizer_t o, const char* json);
+const char* tcnn_optimizer_hyperparams(tcnn_optimizer_t o);                                     /* JSON text owned by the handle */
+void*       tcnn_optimizer_custom_weights(tcnn_optimizer_t o);                                  /* optimizer.h:54 */
+int         tcnn_optimizer_weights_restored(tcnn_optimizer_t o, tcnn_stream_t stream, const void* params_half);
+int         tcnn_optimizer_serialize(tcnn_optimizer_t o, const void** out_bytes, size_t* out_size);
+int         tcnn_optimizer_deserialize(tcnn_optimizer_t o, const void* bytes, size_t size);
 
 #ifdef __cplusplus
 }

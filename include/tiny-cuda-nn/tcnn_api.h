@@ -7,7 +7,7 @@
 //   tcnn::GPUMemory<T>                             gpu_memory.h:60-392   (allocation, host <-> device copies, memset)
 //   tcnn::GPUMatrixDynamic<T>, GPUMatrix<T, L>     gpu_matrix.h:115-470  (m x n, column-major by default = [n][m] in memory)
 //   tcnn::Loss<T>, create_loss<T>                  loss.h:48-77, src/loss.cu:54-68          (L2, RelativeL2)
-//   tcnn::Optimizer<T>, create_optimizer<T>        optimizer.h:44-95, src/optimizer.cu:50-82 (Adam)
+//   tcnn::Optimizer<T>, create_optimizer<T>        optimizer.h:44-95, src/optimizer.cu:50-82 (every optimizer of the library; allocate / step for callers with their own gradients)
 //   tcnn::NetworkWithInputEncoding<T>              network_with_input_encoding.h:40-180
 //   tcnn::Trainer<T, PARAMS_T, COMPUTE_T>          trainer.h:48-363  (training_step, loss, inference via the network, params)
 //   tcnn::TrainableModel, create_from_config       config.h:46-63
@@ -27,6 +27,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace tcnn {
@@ -163,15 +164,71 @@ private:
 };
 template <typename T> Loss<T>* create_loss(const json& params) { return new Loss<T>{params}; }
 
+// optimizer.h:40-66.  Configuration only until allocate(), which makes the native optimizer (tcnn_optimizer_t); a Trainer does not
+// need that -- it builds its own optimizer from hyperparams().  T is the type of the working weights and of the gradients: half.
 template <typename T>
 class Optimizer {
 public:
 	explicit Optimizer(const json& params) : m_params(params) {}
-	json hyperparams() const { return m_params; }
-	void update_hyperparams(const json& params) { m_params = params; }
+	Optimizer(const Optimizer&) = delete;
+	Optimizer& operator=(const Optimizer&) = delete;
+	~Optimizer() { if (m_handle) tcnn_optimizer_destroy(m_handle); }
+
+	void allocate(size_t n_weights, const std::vector<std::pair<uint32_t, uint32_t>>& layer_sizes = {}) {
+		static_assert(sizeof(T) == 2, "tcnn::Optimizer<T>: the working weights are half precision");
+		std::vector<uint32_t> flat;
+		for (const auto& ls : layer_sizes) { flat.push_back(ls.first); flat.push_back(ls.second); }
+		tcnn_optimizer_t fresh = nullptr;
+		detail::check(tcnn_optimizer_create(m_params.dump().c_str(), n_weights, flat.data(), layer_sizes.size(), &fresh));
+		if (m_handle) tcnn_optimizer_destroy(m_handle);
+		m_handle = fresh;
+	}
+	// gradients: scaled by loss_scale, like the ones a Trainer's backward pass writes
+	void step(stream_t stream, float loss_scale, float* weights_full_precision, T* weights, const T* gradients) {
+		detail::check(tcnn_optimizer_step(allocated("step"), stream, loss_scale, weights_full_precision, weights, gradients, TCNN_PRECISION_FP16));
+	}
+	// the same on fp32 gradients (no counterpart in the reference): read as they are, never rounded to half
+	void step(stream_t stream, float loss_scale, float* weights_full_precision, T* weights, const float* gradients) {
+		detail::check(tcnn_optimizer_step(allocated("step"), stream, loss_scale, weights_full_precision, weights, gradients, TCNN_PRECISION_FP32));
+	}
+	float learning_rate() const { return tcnn_optimizer_learning_rate(allocated("learning_rate")); }
+	void set_learning_rate(float val) { detail::check(tcnn_optimizer_set_learning_rate(allocated("set_learning_rate"), val)); }
+	uint32_t step() const { return tcnn_optimizer_step_count(allocated("step")); }
+	size_t n_weights() const { return m_handle ? tcnn_optimizer_n_params(m_handle) : 0; }
+	T* custom_weights() const { return m_handle ? (T*)tcnn_optimizer_custom_weights(m_handle) : nullptr; }
+	// after the caller has overwritten `weights` by other means (a loaded snapshot)
+	void weights_restored(stream_t stream, const T* weights) { detail::check(tcnn_optimizer_weights_restored(allocated("weights_restored"), stream, weights)); }
+
+	json hyperparams() const {
+		if (!m_handle) return m_params;
+		const char* text = tcnn_optimizer_hyperparams(m_handle);
+		if (!text) throw std::runtime_error{tcnn_last_error()};
+		return json::parse(text);
+	}
+	void update_hyperparams(const json& params) {
+		if (m_handle) detail::check(tcnn_optimizer_update_hyperparams(m_handle, params.dump().c_str()));
+		else m_params = params;
+	}
+	// the object a Trainer's snapshot carries as its "optimizer" entry (binary values inside)
+	json serialize() const {
+		const void* bytes = nullptr;
+		size_t size = 0;
+		detail::check(tcnn_optimizer_serialize(allocated("serialize"), &bytes, &size));
+		return json::from_msgpack(std::vector<uint8_t>((const uint8_t*)bytes, (const uint8_t*)bytes + size));
+	}
+	void deserialize(const json& data) {
+		const std::vector<uint8_t> bytes = json::to_msgpack(data);
+		detail::check(tcnn_optimizer_deserialize(allocated("deserialize"), bytes.data(), bytes.size()));
+	}
+	tcnn_optimizer_t handle() const { return m_handle; }
 
 private:
+	tcnn_optimizer_t allocated(const char* what) const {
+		if (!m_handle) throw std::runtime_error{std::string{"Optimizer::"} + what + ": call allocate() first"};
+		return m_handle;
+	}
 	json m_params;
+	tcnn_optimizer_t m_handle = nullptr;
 };
 template <typename T> Optimizer<T>* create_optimizer(const json& params) { return new Optimizer<T>{params}; }
 

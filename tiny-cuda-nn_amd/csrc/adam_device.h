@@ -11,11 +11,14 @@ namespace tcnn_amd {
 // `updated` reports whether adam.h:76-84 lets this parameter through.
 // debias_of(t): the debiasing factor of step t <= common_step (a table lookup: k_adam reads the global table, the gradient kernels a
 // window of it they keep in LDS).
-template <typename DebiasOf>
-__device__ inline void adam_one(const AdamArgs& a, DebiasOf&& debias_of, const float common_debias, const bool is_matrix, const _Float16 g_h, float& w_fp, _Float16& w_h,
+// G: the type the gradient was loaded as, _Float16 (the trainer's gradient vector) or float (a caller's own fp32 gradients, standalone
+// optimizers): the value is taken to float as it is and unscaled the same way -- no rounding in between for either type.
+template <typename DebiasOf, typename G>
+__device__ inline void adam_one(const AdamArgs& a, DebiasOf&& debias_of, const float common_debias, const bool is_matrix, const G g_in, float& w_fp, _Float16& w_h,
                                 float& m1, float& m2, uint32_t& step, bool& updated) {
+	const float g = (float)g_in;
 	// loss_scale is a power of two in practice (128): the reciprocal multiply is then exact, i.e. identical to the division
-	float gradient = a.inv_loss_scale_exact ? (float)g_h * a.inv_loss_scale : (float)g_h / a.loss_scale;
+	float gradient = a.inv_loss_scale_exact ? g * a.inv_loss_scale : g / a.loss_scale;
 	updated = is_matrix ? a.optimize_matrix_params != 0 : (a.optimize_non_matrix_params != 0 && gradient != 0);
 	const float weight_fp = w_fp;
 	if (is_matrix) gradient += a.l2_reg * weight_fp;

@@ -68,6 +68,13 @@ struct tcnn_train_ctx_s {
 	std::unique_ptr<TrainContext> ctx;
 };
 
+struct tcnn_optimizer_s {
+	std::unique_ptr<Optimizer> optimizer;
+	size_t n_params = 0;
+	std::string hyperparams_text;
+	std::vector<uint8_t> snapshot; // tcnn_optimizer_serialize's result
+};
+
 namespace tcnn_amd {
 Switches switches() {
 	std::lock_guard<std::mutex> lock{g_switches_mutex};
@@ -487,6 +494,120 @@ int tcnn_trainer_deserialize(tcnn_trainer_t t, const void* bytes, size_t size) {
 	return guarded([&] {
 		CHECK_THROW(bytes != nullptr && size > 0);
 		t->trainer->deserialize(Json::from_msgpack((const uint8_t*)bytes, size));
+	});
+}
+
+// ---------------------------------------------------------------------------------------------------------- standalone optimizer
+int tcnn_module_layer_sizes(tcnn_module_t m, uint32_t* rows_cols, size_t capacity, size_t* n_layers_out) {
+	return guarded([&] {
+		CHECK_THROW(m && m->model && n_layers_out && (rows_cols || capacity == 0));
+		const auto sizes = m->model->layer_sizes();
+		*n_layers_out = sizes.size();
+		for (size_t i = 0; i < sizes.size() && i < capacity; ++i) {
+			rows_cols[2 * i] = sizes[i].first;
+			rows_cols[2 * i + 1] = sizes[i].second;
+		}
+	});
+}
+
+int tcnn_optimizer_create(const char* optimizer_json, size_t n_params, const uint32_t* layer_sizes, size_t n_layers, tcnn_optimizer_t* out) {
+	switches_reload(); // the A/B switches are read once per model (tcnn_common.h: Switches)
+	return guarded([&] {
+		CHECK_THROW(out != nullptr && (layer_sizes != nullptr || n_layers == 0));
+		auto o = std::make_unique<tcnn_optimizer_s>();
+		o->optimizer = create_optimizer(parse_or_empty(optimizer_json)); // the configuration is checked here: nothing on the device yet
+		std::vector<std::pair<uint32_t, uint32_t>> sizes;
+		size_t n_matrix = 0;
+		for (size_t i = 0; i < n_layers; ++i) {
+			sizes.emplace_back(layer_sizes[2 * i], layer_sizes[2 * i + 1]);
+			n_matrix += (size_t)layer_sizes[2 * i] * layer_sizes[2 * i + 1];
+		}
+		if (n_matrix > n_params) throw std::runtime_error{"Optimizer: the layer sizes hold more weights than n_params."};
+		o->optimizer->allocate(n_params, sizes);
+		o->n_params = n_params;
+		HIP_CHECK_THROW(hipDeviceSynchronize()); // the state's memsets ran on the null stream; steps run on the caller's
+		*out = o.release();
+	});
+}
+
+void tcnn_optimizer_destroy(tcnn_optimizer_t o) { delete o; }
+
+int tcnn_optimizer_step(tcnn_optimizer_t o, tcnn_stream_t stream, float loss_scale, float* params_full_precision, void* params_half, const void* gradients, int gradient_precision) {
+	return guarded([&] {
+		CHECK_THROW(o && o->optimizer);
+		CHECK_THROW(gradient_precision == TCNN_PRECISION_FP32 || gradient_precision == TCNN_PRECISION_FP16);
+		CHECK_THROW(o->n_params == 0 || (params_full_precision && params_half && gradients));
+		o->optimizer->step((hipStream_t)stream, loss_scale, params_full_precision, params_half, gradients, (GradientPrecision)gradient_precision);
+		HIP_CHECK_THROW(hipGetLastError());
+	});
+}
+
+// getters: guarded like everything else -- a NULL handle or an exception leaves the message in tcnn_last_error() and returns the neutral value
+uint32_t tcnn_optimizer_step_count(tcnn_optimizer_t o) {
+	uint32_t v = 0;
+	guarded([&] { CHECK_THROW(o && o->optimizer); v = o->optimizer->step_count(); });
+	return v;
+}
+size_t tcnn_optimizer_n_params(tcnn_optimizer_t o) {
+	size_t v = 0;
+	guarded([&] { CHECK_THROW(o && o->optimizer); v = o->n_params; });
+	return v;
+}
+float tcnn_optimizer_learning_rate(tcnn_optimizer_t o) {
+	float v = std::numeric_limits<float>::quiet_NaN();
+	guarded([&] { CHECK_THROW(o && o->optimizer); v = o->optimizer->learning_rate(); });
+	return v;
+}
+int tcnn_optimizer_set_learning_rate(tcnn_optimizer_t o, float learning_rate) {
+	return guarded([&] {
+		CHECK_THROW(o && o->optimizer);
+		o->optimizer->set_learning_rate(learning_rate);
+	});
+}
+int tcnn_optimizer_update_hyperparams(tcnn_optimizer_t o, const char* json) {
+	return guarded([&] {
+		CHECK_THROW(o && o->optimizer);
+		o->optimizer->update_hyperparams(parse_or_empty(json));
+	});
+}
+const char* tcnn_optimizer_hyperparams(tcnn_optimizer_t o) {
+	const char* text = nullptr;
+	guarded([&] {
+		CHECK_THROW(o && o->optimizer);
+		o->hyperparams_text = o->optimizer->hyperparams().dump();
+		text = o->hyperparams_text.c_str();
+	});
+	return text;
+}
+void* tcnn_optimizer_custom_weights(tcnn_optimizer_t o) {
+	void* p = nullptr;
+	guarded([&] { CHECK_THROW(o && o->optimizer); p = o->optimizer->custom_weights(); });
+	return p;
+}
+
+int tcnn_optimizer_weights_restored(tcnn_optimizer_t o, tcnn_stream_t stream, const void* params_half) {
+	return guarded([&] {
+		CHECK_THROW(o && o->optimizer && (params_half || o->n_params == 0));
+		o->optimizer->weights_restored((hipStream_t)stream, params_half);
+	});
+}
+
+int tcnn_optimizer_serialize(tcnn_optimizer_t o, const void** out_bytes, size_t* out_size) {
+	return guarded([&] {
+		CHECK_THROW(o && o->optimizer && out_bytes != nullptr && out_size != nullptr);
+		HIP_CHECK_THROW(hipDeviceSynchronize());
+		o->snapshot = Json::to_msgpack(o->optimizer->serialize());
+		*out_bytes = o->snapshot.data();
+		*out_size = o->snapshot.size();
+	});
+}
+
+int tcnn_optimizer_deserialize(tcnn_optimizer_t o, const void* bytes, size_t size) {
+	return guarded([&] {
+		CHECK_THROW(o && o->optimizer && bytes != nullptr && size > 0);
+		HIP_CHECK_THROW(hipDeviceSynchronize());
+		o->optimizer->deserialize(Json::from_msgpack((const uint8_t*)bytes, size), o->n_params);
+		HIP_CHECK_THROW(hipDeviceSynchronize());
 	});
 }
 

@@ -394,29 +394,35 @@ template <typename STEP_T> __device__ inline void adam_store_steps(STEP_T* p, co
 	if constexpr (sizeof(STEP_T) == 2) *(adam_u16x4*)p = adam_u16x4{(uint16_t)v.x, (uint16_t)v.y, (uint16_t)v.z, (uint16_t)v.w};
 	else *(uint4*)p = v;
 }
-template <bool QUAD_UNIFORM, typename STEP_T>
+// G: the gradients' type, half_t (8-byte quads) or float (16-byte quads: a caller's own fp32 gradients, standalone optimizers)
+typedef float f4 __attribute__((ext_vector_type(4)));
+template <typename G> struct GradQuad;
+template <> struct GradQuad<half_t> { typedef h4 type; };
+template <> struct GradQuad<float> { typedef f4 type; };
+template <bool QUAD_UNIFORM, typename STEP_T, typename G>
 __global__ void __launch_bounds__(256) k_adam(
 	const AdamArgs a, const size_t n, const size_t n_matrix,
-	float* __restrict__ w_fp, half_t* __restrict__ w, const half_t* __restrict__ g, float* __restrict__ m1, float* __restrict__ m2, STEP_T* __restrict__ steps,
+	float* __restrict__ w_fp, half_t* __restrict__ w, const G* __restrict__ g, float* __restrict__ m1, float* __restrict__ m2, STEP_T* __restrict__ steps,
 	const float* __restrict__ debias_table
 ) {
 	const size_t base = (size_t)blockIdx.x * (256 * 4 * ADAM_Q) + threadIdx.x * 4;
 	const float debias = debias_table[a.common_step];
 	const auto from_table = [&](const uint32_t t) { return debias_table[t]; };
-	// phase 1: the gradients of all quads (8 B each).  Grid (non-matrix) quads whose 4 gradients are all zero are skipped
+	// phase 1: the gradients of all quads (8 B each, 16 B for fp32 gradients).  Grid (non-matrix) quads whose 4 gradients are all zero are skipped
 	// without touching the other 32 B/param (adam.h:76-79 returns before reading anything else).
-	h4 gv[ADAM_Q];
+	typedef typename GradQuad<G>::type g4;
+	g4 gv[ADAM_Q];
 	bool live[ADAM_Q];
 #pragma unroll
 	for (int q = 0; q < ADAM_Q; ++q) {
 		const size_t i4 = base + (size_t)q * 1024;
 		live[q] = i4 + 4 <= n;
-		gv[q] = live[q] ? *(const h4*)(g + i4) : h4{0, 0, 0, 0};
+		gv[q] = live[q] ? *(const g4*)(g + i4) : g4{0, 0, 0, 0};
 	}
 #pragma unroll
 	for (int q = 0; q < ADAM_Q; ++q) {
 		const size_t i4 = base + (size_t)q * 1024;
-		const bool zero = gv[q][0] == (half_t)0.0f && gv[q][1] == (half_t)0.0f && gv[q][2] == (half_t)0.0f && gv[q][3] == (half_t)0.0f;
+		const bool zero = gv[q][0] == (G)0.0f && gv[q][1] == (G)0.0f && gv[q][2] == (G)0.0f && gv[q][3] == (G)0.0f;
 		if (live[q] && i4 >= n_matrix && zero) live[q] = false;
 	}
 	// phase 2: all remaining loads in flight together
@@ -468,10 +474,10 @@ __global__ void __launch_bounds__(256) k_adam(
 
 // One parameter per thread, no vector accesses: for parameter ranges that do not start on a 16-byte boundary (a Composite
 // optimizer hands its nested optimizers slices at arbitrary offsets, optimizers/composite.h:126-135)
-template <typename STEP_T>
+template <typename STEP_T, typename G>
 __global__ void __launch_bounds__(256) k_adam_scalar(
 	const AdamArgs a, const size_t n, const size_t n_matrix,
-	float* __restrict__ w_fp, half_t* __restrict__ w, const half_t* __restrict__ g, float* __restrict__ m1, float* __restrict__ m2, STEP_T* __restrict__ steps,
+	float* __restrict__ w_fp, half_t* __restrict__ w, const G* __restrict__ g, float* __restrict__ m1, float* __restrict__ m2, STEP_T* __restrict__ steps,
 	const float* __restrict__ debias_table
 ) {
 	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -681,17 +687,22 @@ __global__ void __launch_bounds__(256) k_adam_widen_steps(const size_t n, const 
 	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i < n) out[i] = in[i];
 }
-template <typename STEP_T>
-void adam_launch(hipStream_t stream, const AdamArgs& a, size_t n, size_t n_matrix, float* w_fp, void* w_half, const void* g_half, float* m1, float* m2, STEP_T* steps, const float* debias_table) {
-	// the quad kernel reads float4 / 4 step counts / half4: every base pointer must allow that
+template <typename STEP_T, typename G>
+void adam_launch(hipStream_t stream, const AdamArgs& a, size_t n, size_t n_matrix, float* w_fp, void* w_half, const G* g, float* m1, float* m2, STEP_T* steps, const float* debias_table) {
+	// the quad kernel reads float4 / 4 step counts / half4 / 4 gradients: every base pointer must allow that
 	const auto aligned = [](const void* p, size_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; };
-	if (!(aligned(w_fp, 16) && aligned(m1, 16) && aligned(m2, 16) && aligned(steps, 4 * sizeof(STEP_T)) && aligned(w_half, 8) && aligned(g_half, 8))) {
-		hipLaunchKernelGGL(k_adam_scalar<STEP_T>, dim3(blocks_for(n, 256)), dim3(256), 0, stream, a, n, n_matrix, w_fp, (half_t*)w_half, (const half_t*)g_half, m1, m2, steps, debias_table);
+	if (!(aligned(w_fp, 16) && aligned(m1, 16) && aligned(m2, 16) && aligned(steps, 4 * sizeof(STEP_T)) && aligned(w_half, 8) && aligned(g, 4 * sizeof(G)))) {
+		hipLaunchKernelGGL((k_adam_scalar<STEP_T, G>), dim3(blocks_for(n, 256)), dim3(256), 0, stream, a, n, n_matrix, w_fp, (half_t*)w_half, g, m1, m2, steps, debias_table);
 		return;
 	}
 	const dim3 grid(blocks_for((n + 3) / 4, 256 * ADAM_Q));
-	if (n_matrix % 4 == 0) hipLaunchKernelGGL((k_adam<true, STEP_T>), grid, dim3(256), 0, stream, a, n, n_matrix, w_fp, (half_t*)w_half, (const half_t*)g_half, m1, m2, steps, debias_table);
-	else hipLaunchKernelGGL((k_adam<false, STEP_T>), grid, dim3(256), 0, stream, a, n, n_matrix, w_fp, (half_t*)w_half, (const half_t*)g_half, m1, m2, steps, debias_table);
+	if (n_matrix % 4 == 0) hipLaunchKernelGGL((k_adam<true, STEP_T, G>), grid, dim3(256), 0, stream, a, n, n_matrix, w_fp, (half_t*)w_half, g, m1, m2, steps, debias_table);
+	else hipLaunchKernelGGL((k_adam<false, STEP_T, G>), grid, dim3(256), 0, stream, a, n, n_matrix, w_fp, (half_t*)w_half, g, m1, m2, steps, debias_table);
+}
+template <typename G>
+void adam_launch_steps(hipStream_t stream, const AdamArgs& a, size_t n, size_t n_matrix, float* w_fp, void* w_half, const G* g, float* m1, float* m2, void* steps, bool steps16, const float* debias_table) {
+	if (steps16) adam_launch<uint16_t, G>(stream, a, n, n_matrix, w_fp, w_half, g, m1, m2, (uint16_t*)steps, debias_table);
+	else adam_launch<uint32_t, G>(stream, a, n, n_matrix, w_fp, w_half, g, m1, m2, (uint32_t*)steps, debias_table);
 }
 } // namespace
 
@@ -701,11 +712,11 @@ void adam_widen_steps(hipStream_t stream, size_t n, const void* steps16, void* s
 }
 
 void adam_step(hipStream_t stream, const AdamHyper& h, size_t n, size_t n_matrix, float loss_scale, uint32_t current_step,
-               float* w_fp, void* w_half, const void* g_half, float* m1, float* m2, void* steps, bool steps16, const float* debias_table) {
+               float* w_fp, void* w_half, const void* gradients, float* m1, float* m2, void* steps, bool steps16, const float* debias_table, GradientPrecision precision) {
 	if (n == 0) return;
 	const AdamArgs a = make_adam_args(h, loss_scale, current_step);
-	if (steps16) adam_launch<uint16_t>(stream, a, n, n_matrix, w_fp, w_half, g_half, m1, m2, (uint16_t*)steps, debias_table);
-	else adam_launch<uint32_t>(stream, a, n, n_matrix, w_fp, w_half, g_half, m1, m2, (uint32_t*)steps, debias_table);
+	if (precision == GradientPrecision::Fp32) adam_launch_steps(stream, a, n, n_matrix, w_fp, w_half, (const float*)gradients, m1, m2, steps, steps16, debias_table);
+	else adam_launch_steps(stream, a, n, n_matrix, w_fp, w_half, (const half_t*)gradients, m1, m2, steps, steps16, debias_table);
 }
 
 // ---- Adam with the backward pass's last two reductions in front (AdamPrologue, tcnn_common.h): workgroups [0, n_reduce_blocks) sum the MLP's
@@ -903,8 +914,9 @@ void adam_fill_debias_table(hipStream_t stream, float beta1, float beta2, uint32
 
 namespace {
 // optimizers/sgd.h:44-72
+template <typename G>
 __global__ void __launch_bounds__(256) k_sgd(const size_t n, const float loss_scale, const float learning_rate, const float l2_reg, float* __restrict__ w_fp, half_t* __restrict__ w,
-                                             const half_t* __restrict__ g) {
+                                             const G* __restrict__ g) {
 	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
 	const float weight_fp = w_fp[i];
@@ -934,7 +946,8 @@ __global__ void __launch_bounds__(256) k_average_step(const size_t n, const uint
 	current[i] = weight;
 }
 // optimizers/batched.h:44-61: pool (+)= gradient / batch_size_multiplier, restarted with the first gradient of a group
-__global__ void __launch_bounds__(256) k_batched_accumulate(const size_t n, const int first, const uint32_t multiplier, const half_t* __restrict__ gradients, float* __restrict__ pool) {
+template <typename G>
+__global__ void __launch_bounds__(256) k_batched_accumulate(const size_t n, const int first, const uint32_t multiplier, const G* __restrict__ gradients, float* __restrict__ pool) {
 	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
 	float v = first ? 0.0f : pool[i];
@@ -943,7 +956,8 @@ __global__ void __launch_bounds__(256) k_batched_accumulate(const size_t n, cons
 }
 // optimizers/novograd.h:44-94.  One workgroup per layer sums the squared gradients (fixed tree: reproducible) and folds the sum
 // into the layer's second moment, moment = beta2 moment + (1 - beta2) sum / loss_scale / loss_scale; then the element-wise step.
-__global__ void __launch_bounds__(1024) k_novo_second_moment(const size_t n, const float loss_scale, const float beta2, const half_t* __restrict__ gradients, float* __restrict__ moment) {
+template <typename G>
+__global__ void __launch_bounds__(1024) k_novo_second_moment(const size_t n, const float loss_scale, const float beta2, const G* __restrict__ gradients, float* __restrict__ moment) {
 	__shared__ float part[1024];
 	float acc = 0.0f;
 	for (size_t i = threadIdx.x; i < n; i += 1024) {
@@ -958,8 +972,9 @@ __global__ void __launch_bounds__(1024) k_novo_second_moment(const size_t n, con
 	}
 	if (threadIdx.x == 0) *moment = beta2 * *moment + (1 - beta2) * part[0] / loss_scale / loss_scale;
 }
+template <typename G>
 __global__ void __launch_bounds__(256) k_novo_step(const size_t n, const float relative_weight_decay, const float absolute_weight_decay, const float loss_scale, const float learning_rate,
-                                                   const float beta1, const float epsilon, float* __restrict__ weights_fp, half_t* __restrict__ weights, const half_t* __restrict__ gradients,
+                                                   const float beta1, const float epsilon, float* __restrict__ weights_fp, half_t* __restrict__ weights, const G* __restrict__ gradients,
                                                    float* __restrict__ first_moments, const float* __restrict__ layer_second_moment) {
 	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
@@ -1006,24 +1021,32 @@ void copy_columns(hipStream_t stream, size_t elem_bytes, uint32_t n, const void*
 	else hipLaunchKernelGGL((k_copy_columns<uint32_t>), blocks, dim3(256), 0, stream, (uint32_t)total, width, (const uint32_t*)src, src_stride, src_col, (uint32_t*)dst, dst_stride, dst_col);
 }
 
-void sgd_step(hipStream_t stream, size_t n, float loss_scale, float learning_rate, float l2_reg, float* weights_full_precision, void* weights, const void* gradients) {
+void sgd_step(hipStream_t stream, size_t n, float loss_scale, float learning_rate, float l2_reg, float* weights_full_precision, void* weights, const void* gradients, GradientPrecision precision) {
 	if (n == 0) return;
-	hipLaunchKernelGGL(k_sgd, dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, loss_scale, learning_rate, l2_reg, weights_full_precision, (half_t*)weights, (const half_t*)gradients);
+	if (precision == GradientPrecision::Fp32) hipLaunchKernelGGL(k_sgd<float>, dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, loss_scale, learning_rate, l2_reg, weights_full_precision, (half_t*)weights, (const float*)gradients);
+	else hipLaunchKernelGGL(k_sgd<half_t>, dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, loss_scale, learning_rate, l2_reg, weights_full_precision, (half_t*)weights, (const half_t*)gradients);
 }
 
 void average_step(hipStream_t stream, size_t n, uint32_t n_samples, const void* weights, void* current_sample, void* average) {
 	if (n == 0) return;
 	hipLaunchKernelGGL(k_average_step, dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, n_samples, (const half_t*)weights, (half_t*)current_sample, (half_t*)average);
 }
-void batched_accumulate(hipStream_t stream, size_t n, bool first, uint32_t multiplier, const void* gradients, float* pool) {
+void batched_accumulate(hipStream_t stream, size_t n, bool first, uint32_t multiplier, const void* gradients, float* pool, GradientPrecision precision) {
 	if (n == 0) return;
-	hipLaunchKernelGGL(k_batched_accumulate, dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, first ? 1 : 0, multiplier, (const half_t*)gradients, pool);
+	if (precision == GradientPrecision::Fp32) hipLaunchKernelGGL(k_batched_accumulate<float>, dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, first ? 1 : 0, multiplier, (const float*)gradients, pool);
+	else hipLaunchKernelGGL(k_batched_accumulate<half_t>, dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, first ? 1 : 0, multiplier, (const half_t*)gradients, pool);
 }
 void novograd_layer_step(hipStream_t stream, size_t n, float relative_decay, float absolute_decay, float loss_scale, float learning_rate, float beta1, float beta2, float epsilon,
-                         float* weights_full_precision, void* weights, const void* gradients, float* first_moments, float* layer_second_moment) {
+                         float* weights_full_precision, void* weights, const void* gradients, float* first_moments, float* layer_second_moment, GradientPrecision precision) {
 	if (n == 0) return;
-	hipLaunchKernelGGL(k_novo_second_moment, dim3(1), dim3(1024), 0, stream, n, loss_scale, beta2, (const half_t*)gradients, layer_second_moment);
-	hipLaunchKernelGGL(k_novo_step, dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, relative_decay, absolute_decay, loss_scale, learning_rate, beta1, epsilon, weights_full_precision,
+	if (precision == GradientPrecision::Fp32) {
+		hipLaunchKernelGGL(k_novo_second_moment<float>, dim3(1), dim3(1024), 0, stream, n, loss_scale, beta2, (const float*)gradients, layer_second_moment);
+		hipLaunchKernelGGL(k_novo_step<float>, dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, relative_decay, absolute_decay, loss_scale, learning_rate, beta1, epsilon, weights_full_precision,
+		                   (half_t*)weights, (const float*)gradients, first_moments, layer_second_moment);
+		return;
+	}
+	hipLaunchKernelGGL(k_novo_second_moment<half_t>, dim3(1), dim3(1024), 0, stream, n, loss_scale, beta2, (const half_t*)gradients, layer_second_moment);
+	hipLaunchKernelGGL(k_novo_step<half_t>, dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, relative_decay, absolute_decay, loss_scale, learning_rate, beta1, epsilon, weights_full_precision,
 	                   (half_t*)weights, (const half_t*)gradients, first_moments, layer_second_moment);
 }
 void lookahead_step(hipStream_t stream, size_t n, float alpha, float* weights_full_precision, void* weights, void* weights_lookahead) {

@@ -2709,7 +2709,9 @@ class Optimizer {
 public:
 	virtual ~Optimizer() {}
 	virtual void allocate(size_t n_weights, const std::vector<std::pair<uint32_t, uint32_t>>& layer_sizes) = 0;
-	virtual void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients) = 0;
+	// gradients: n_weights values in `precision` -- the trainer's half gradients (scaled by loss_scale), or fp32 ones a caller computed itself
+	// (a PyTorch parameter's .grad; loss_scale 1 when they are unscaled already).  The weights stay what they are: fp32 master, half working copy.
+	virtual void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients, GradientPrecision precision = GradientPrecision::Fp16) = 0;
 	// A step in two parts, for gradient kernels that can apply the update to the parameters they own (AdamInFlush): begin_split_step
 	// starts the step and describes it (false: this optimizer cannot be split, nothing has happened -- call step()); finish_split_step
 	// updates every parameter outside `done`.  Together they equal step() bit for bit.
@@ -2813,12 +2815,12 @@ public:
 		m_h.learning_rate = (float)data["base_learning_rate"].as_double();
 	}
 
-	void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients) override { // adam.h:150-188
+	void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients, GradientPrecision precision = GradientPrecision::Fp16) override { // adam.h:150-188
 		++m_current_step;
 		ensure_debias_table(stream);
 		ensure_step_width(stream);
 		adam_step(stream, m_h, m_n_weights, m_n_matrix, loss_scale, m_current_step, weights_full_precision, weights, gradients,
-		          m_first_moments.as<float>(), m_second_moments.as<float>(), m_param_steps.data(), m_steps16, m_debias.as<float>());
+		          m_first_moments.as<float>(), m_second_moments.as<float>(), m_param_steps.data(), m_steps16, m_debias.as<float>(), precision);
 	}
 
 	bool takes_prologue() const override { return true; }
@@ -2953,9 +2955,9 @@ class SgdOptimizer : public Optimizer {
 public:
 	explicit SgdOptimizer(const Json& params) { update_hyperparams(params); }
 	void allocate(size_t n_weights, const std::vector<std::pair<uint32_t, uint32_t>>&) override { m_n_weights = n_weights; }
-	void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients) override {
+	void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients, GradientPrecision precision = GradientPrecision::Fp16) override {
 		++m_current_step;
-		sgd_step(stream, m_n_weights, loss_scale, m_learning_rate, m_l2_reg, weights_full_precision, weights, gradients);
+		sgd_step(stream, m_n_weights, loss_scale, m_learning_rate, m_l2_reg, weights_full_precision, weights, gradients, precision);
 	}
 	float learning_rate() const override { return m_learning_rate; }
 	void set_learning_rate(float val) override { m_learning_rate = val; }
@@ -3000,11 +3002,11 @@ public:
 		m_base_learning_rate = m_nested->learning_rate();
 	}
 	void allocate(size_t n_weights, const std::vector<std::pair<uint32_t, uint32_t>>& layer_sizes) override { m_nested->allocate(n_weights, layer_sizes); }
-	void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients) override { // :60-71
+	void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients, GradientPrecision precision = GradientPrecision::Fp16) override { // :60-71
 		if (step_count() == 0) m_learning_rate_factor = 1.0f;
 		if (step_count() >= m_decay_start && (step_count() - m_decay_start) % m_decay_interval == 0 && step_count() <= m_decay_end) m_learning_rate_factor *= m_decay_base;
 		m_nested->set_learning_rate(m_base_learning_rate * m_learning_rate_factor);
-		m_nested->step(stream, loss_scale, weights_full_precision, weights, gradients);
+		m_nested->step(stream, loss_scale, weights_full_precision, weights, gradients, precision);
 	}
 	float learning_rate() const override { return m_base_learning_rate * m_learning_rate_factor; }
 	void set_learning_rate(float val) override {
@@ -3068,8 +3070,8 @@ public:
 			m_tmp.memset(0);
 		}
 	}
-	void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients) override { // :98-132
-		m_nested->step(stream, loss_scale, weights_full_precision, weights, gradients);
+	void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients, GradientPrecision precision = GradientPrecision::Fp16) override { // :98-132
+		m_nested->step(stream, loss_scale, weights_full_precision, weights, gradients, precision);
 		const uint32_t current_step = m_nested->step_count();
 		const float ema_debias_old = 1 - (float)std::pow(m_ema_decay, current_step - 1);
 		const float ema_debias_new = 1.0f / (1 - (float)std::pow(m_ema_decay, current_step));
@@ -3136,13 +3138,14 @@ public:
 		m_per_layer_second_moments.resize(m_layers.size() * sizeof(float));
 		m_per_layer_second_moments.memset(0);
 	}
-	void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients) override { // :126-167
+	void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients, GradientPrecision precision = GradientPrecision::Fp16) override { // :126-167
 		++m_current_step;
 		size_t offset = 0;
+		const size_t gradient_bytes = precision == GradientPrecision::Fp32 ? sizeof(float) : 2;
 		for (size_t i = 0; i < m_layers.size(); ++i) {
 			novograd_layer_step(stream, m_layers[i], m_relative_decay, m_absolute_decay, loss_scale, m_learning_rate, m_current_step == 1 ? 0.0f : m_beta1, // exact values on the first step
-			                    m_current_step == 1 ? 0.0f : m_beta2, m_epsilon, weights_full_precision + offset, (char*)weights + 2 * offset, (const char*)gradients + 2 * offset,
-			                    m_first_moments.as<float>() + offset, m_per_layer_second_moments.as<float>() + i);
+			                    m_current_step == 1 ? 0.0f : m_beta2, m_epsilon, weights_full_precision + offset, (char*)weights + 2 * offset, (const char*)gradients + gradient_bytes * offset,
+			                    m_first_moments.as<float>() + offset, m_per_layer_second_moments.as<float>() + i, precision);
 			offset += m_layers[i];
 		}
 	}
@@ -3216,8 +3219,8 @@ public:
 		m_weights_average.resize(n_weights * 2);
 		m_weights_average.memset(0);
 	}
-	void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients) override { // :82-92
-		m_nested->step(stream, loss_scale, weights_full_precision, weights, gradients);
+	void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients, GradientPrecision precision = GradientPrecision::Fp16) override { // :82-92
+		m_nested->step(stream, loss_scale, weights_full_precision, weights, gradients, precision);
 		char* current = (char*)m_weights_samples.data() + (size_t)(step_count() % m_n_samples) * m_n_weights * 2; // the slot of the step just taken
 		average_step(stream, m_n_weights, m_n_samples, weights, current, m_weights_average.data());
 	}
@@ -3282,10 +3285,14 @@ public:
 		m_averaged_gradients.memset(0);
 		m_averaged_gradients_half.memset(0);
 	}
-	void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients) override { // :77-89
-		batched_accumulate(stream, n_weights(), m_current_step % m_batch_size_multiplier == 0, m_batch_size_multiplier, gradients, m_averaged_gradients.as<float>());
+	void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients, GradientPrecision precision = GradientPrecision::Fp16) override { // :77-89
+		batched_accumulate(stream, n_weights(), m_current_step % m_batch_size_multiplier == 0, m_batch_size_multiplier, gradients, m_averaged_gradients.as<float>(), precision);
 		++m_current_step;
 		if (m_current_step % m_batch_size_multiplier == 0) {
+			if (precision == GradientPrecision::Fp32) { // the nested optimizer reads the fp32 mean as it is: no rounding to half on the way
+				m_nested->step(stream, loss_scale, weights_full_precision, weights, m_averaged_gradients.data(), precision);
+				return;
+			}
 			cast_float_to_half(stream, n_weights(), m_averaged_gradients.as<float>(), m_averaged_gradients_half.data());
 			m_nested->step(stream, loss_scale, weights_full_precision, weights, m_averaged_gradients_half.data());
 		}
@@ -3349,11 +3356,11 @@ public:
 		m_weights_lookahead.resize(n_weights * 2);
 		m_weights_lookahead.memset(0);
 	}
-	void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients) override { // :78-98
+	void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients, GradientPrecision precision = GradientPrecision::Fp16) override { // :78-98
 		const uint32_t current_step = m_nested->step_count();
 		if (current_step == 0) HIP_CHECK_THROW(hipMemcpyAsync(m_weights_lookahead.data(), weights, n_weights() * 2, hipMemcpyDeviceToDevice, stream));
 		if (current_step % m_n_steps == 0) lookahead_step(stream, n_weights(), m_alpha, weights_full_precision, weights, m_weights_lookahead.data());
-		m_nested->step(stream, loss_scale, weights_full_precision, weights, gradients);
+		m_nested->step(stream, loss_scale, weights_full_precision, weights, gradients, precision);
 	}
 	float learning_rate() const override { return m_nested->learning_rate(); }
 	void set_learning_rate(float val) override { m_nested->set_learning_rate(val); }
@@ -3441,10 +3448,11 @@ public:
 			m_custom_weights.memset(0);
 		}
 	}
-	void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients) override {
+	void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients, GradientPrecision precision = GradientPrecision::Fp16) override {
+		const size_t gradient_bytes = precision == GradientPrecision::Fp32 ? sizeof(float) : 2;
 		for (size_t i = 0; i < m_nested.size(); ++i) {
 			const size_t offset = m_offsets[i];
-			m_nested[i]->step(stream, loss_scale, weights_full_precision + offset, (_Float16*)weights + offset, (const _Float16*)gradients + offset);
+			m_nested[i]->step(stream, loss_scale, weights_full_precision + offset, (_Float16*)weights + offset, (const char*)gradients + gradient_bytes * offset, precision);
 		}
 		weights_restored(stream, weights);
 	}

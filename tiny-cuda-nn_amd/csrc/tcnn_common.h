@@ -20,6 +20,8 @@ enum class HashType : uint32_t { Prime = 0, CoherentPrime = 1, ReversedPrime = 2
 enum class InterpolationType : uint32_t { Nearest = 0, Linear = 1, Smoothstep = 2 };
 enum class LossType : uint32_t { L2 = 0, RelativeL2 = 1, L1 = 2, RelativeL1 = 3, Mape = 4, Smape = 5, CrossEntropy = 6, Variance = 7, RelativeL2Luminance = 8 }; // src/loss.cu:57-65
 enum class Precision : uint32_t { Fp32 = 0, Fp16 = 1 };      // cpp_api.h:69-72
+// what an optimizer's `gradients` pointer holds: the trainer's half gradients, or a caller's own fp32 ones (same values as Precision)
+enum class GradientPrecision : uint32_t { Fp32 = 0, Fp16 = 1 };
 enum class GradientMode : uint32_t { Ignore = 0, Overwrite = 1, Accumulate = 2 }; // common.h GradientMode
 
 constexpr uint32_t BATCH_SIZE_GRANULARITY = 256; // common.h:235
@@ -508,22 +510,25 @@ bool adam_step_with_prologue(hipStream_t stream, const AdamHyper& h, size_t n, s
 // steps: the per-parameter update counts, uint32 or -- steps16 -- uint16 (what the optimizer keeps while every count fits:
 // 4 of the 36 bytes per parameter the kernel moves are the counts' upper halves otherwise)
 void adam_step(hipStream_t stream, const AdamHyper& h, size_t n, size_t n_matrix, float loss_scale, uint32_t current_step,
-               float* w_fp, void* w_half, const void* g_half, float* m1, float* m2, void* steps, bool steps16, const float* debias_table);
+               float* w_fp, void* w_half, const void* gradients, float* m1, float* m2, void* steps, bool steps16, const float* debias_table,
+               GradientPrecision precision = GradientPrecision::Fp16);
 void adam_widen_steps(hipStream_t stream, size_t n, const void* steps16, void* steps32); // uint16 -> uint32
 // debias_table[t] = sqrtf(1 - powf(beta2, t)) / (1 - powf(beta1, t)) (adam.h:97-98), evaluated on the device, for t in [from, to)
 void adam_fill_debias_table(hipStream_t stream, float beta1, float beta2, uint32_t from, uint32_t to, float* table);
 // dst[i][dst_col + j] = src[i][src_col + j] for j < width; elements of 2 or 4 bytes (Composite encoding)
 void copy_columns(hipStream_t stream, size_t elem_bytes, uint32_t n, const void* src, uint32_t src_stride, uint32_t src_col, void* dst, uint32_t dst_stride, uint32_t dst_col, uint32_t width);
-// optimizers/sgd.h:44-72 and optimizers/ema.h:44-78 (half parameters)
-void sgd_step(hipStream_t stream, size_t n, float loss_scale, float learning_rate, float l2_reg, float* weights_full_precision, void* weights, const void* gradients);
+// optimizers/sgd.h:44-72 and optimizers/ema.h:44-78 (half parameters; gradients in `precision`, here and below)
+void sgd_step(hipStream_t stream, size_t n, float loss_scale, float learning_rate, float l2_reg, float* weights_full_precision, void* weights, const void* gradients,
+              GradientPrecision precision = GradientPrecision::Fp16);
 void ema_step(hipStream_t stream, size_t n, float decay, float debias_old, float debias_new, const void* weights, void* weights_ema, float* tmp);
 // optimizers/average.h:44-60, batched.h:44-61, lookahead.h:44-59 (half parameters)
 void average_step(hipStream_t stream, size_t n, uint32_t n_samples, const void* weights, void* current_sample, void* average);
-void batched_accumulate(hipStream_t stream, size_t n, bool first, uint32_t multiplier, const void* gradients, float* pool);
+void batched_accumulate(hipStream_t stream, size_t n, bool first, uint32_t multiplier, const void* gradients, float* pool, GradientPrecision precision = GradientPrecision::Fp16);
 void lookahead_step(hipStream_t stream, size_t n, float alpha, float* weights_full_precision, void* weights, void* weights_lookahead);
 // optimizers/novograd.h:44-94 for ONE layer of n weights: the layer's second moment from the sum of its squared gradients, then the step
 void novograd_layer_step(hipStream_t stream, size_t n, float relative_decay, float absolute_decay, float loss_scale, float learning_rate, float beta1, float beta2, float epsilon,
-                         float* weights_full_precision, void* weights, const void* gradients, float* first_moments, float* layer_second_moment);
+                         float* weights_full_precision, void* weights, const void* gradients, float* first_moments, float* layer_second_moment,
+                         GradientPrecision precision = GradientPrecision::Fp16);
 
 // random.h:40-70: strided uniform fill from a pcg32 state; advances (state, inc) on the host copy by n
 void generate_random_uniform(hipStream_t stream, uint64_t* state_inc_host, size_t n, float* out, float lower, float upper);

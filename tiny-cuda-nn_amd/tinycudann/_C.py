@@ -127,6 +127,20 @@ _SIGNATURES = {
     "tcnn_trainer_profile_collect": (_int, [_vp, _vp, C.POINTER(C.c_float), C.POINTER(_u32)]),
     "tcnn_trainer_serialize": (_int, [_vp, _int, _pp, C.POINTER(_sz)]),
     "tcnn_trainer_deserialize": (_int, [_vp, _vp, _sz]),
+    "tcnn_module_layer_sizes": (_int, [_vp, C.POINTER(_u32), _sz, C.POINTER(_sz)]),
+    "tcnn_optimizer_create": (_int, [_cp, _sz, C.POINTER(_u32), _sz, _pp]),
+    "tcnn_optimizer_destroy": (None, [_vp]),
+    "tcnn_optimizer_step": (_int, [_vp, _vp, _f32, _vp, _vp, _vp, _int]),
+    "tcnn_optimizer_step_count": (_u32, [_vp]),
+    "tcnn_optimizer_n_params": (_sz, [_vp]),
+    "tcnn_optimizer_learning_rate": (_f32, [_vp]),
+    "tcnn_optimizer_set_learning_rate": (_int, [_vp, _f32]),
+    "tcnn_optimizer_update_hyperparams": (_int, [_vp, _cp]),
+    "tcnn_optimizer_hyperparams": (_cp, [_vp]),
+    "tcnn_optimizer_custom_weights": (_vp, [_vp]),
+    "tcnn_optimizer_weights_restored": (_int, [_vp, _vp, _vp]),
+    "tcnn_optimizer_serialize": (_int, [_vp, _pp, C.POINTER(_sz)]),
+    "tcnn_optimizer_deserialize": (_int, [_vp, _vp, _sz]),
 }
 
 for _name, (_res, _args) in _SIGNATURES.items():

@@ -2,7 +2,9 @@
 
 Public surface (same as the reference's bindings/torch/tinycudann/__init__.py:9-11):
     Encoding, Network, NetworkWithInputEncoding, free_temporary_memory
-plus `native.create_from_config` (the C++ user API of the reference, reachable from Python here).
+plus `native.create_from_config` (the C++ user API of the reference, reachable from Python here) and `optimizers.Optimizer`
+(the library's optimizers as a torch.optim.Optimizer for the modules above).
 """
 from .modules import Encoding, Module, Network, NetworkWithInputEncoding, free_temporary_memory  # noqa: F401
 from .native import Trainer, create_from_config  # noqa: F401
+from . import optimizers  # noqa: F401,E402

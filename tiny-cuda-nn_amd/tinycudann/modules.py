@@ -320,7 +320,8 @@ class _WorkingCopy(torch.autograd.Function):
     (`module.reuse_working_copy = True`): it is then rebuilt when the fp32 master's version counter or address changes -- optimizer
     steps, `load_state_dict`, `copy_` on the parameter, a replaced `.data`.  Writes THROUGH `.data` (`p.data.copy_(ema)`, as
     torch_ema's copy_to / restore do, `p.data.clamp_()`) change neither: after such a write call `invalidate_working_copy()`, or
-    leave the reuse off.  The gradient goes back as a plain cast to fp32."""
+    leave the reuse off.  `tcnn.optimizers.Optimizer` turns the reuse on for its modules and installs the half weights its step wrote as the
+    copy (same key), so that no cast runs at all.  The gradient goes back as a plain cast to fp32."""
 
     @staticmethod
     def forward(ctx, params, owner):
