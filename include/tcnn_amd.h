@@ -189,9 +189,9 @@ uint32_t tcnn_trainer_optimizer_step_count(tcnn_trainer_t t);     /* optimizer->
 int  tcnn_trainer_profile_next_step(tcnn_trainer_t t);
 int  tcnn_trainer_profile_collect(tcnn_trainer_t t, tcnn_stream_t stream, float* ms_per_piece /* [4] */, uint32_t* n_steps);
 /* Introspection (no counterpart in the reference): how many parameters of the last training_step() had their optimizer update
- * applied by the gradient kernels themselves (k_grid_scatter's flush) instead of by the optimizer kernel; 0 when the step ran
- * the optimizer the usual way (the default; TCNN_AMD_ADAM_IN_FLUSH=1 asks for the fused form, which needs plain Adam, GradientMode
- * Overwrite, run_optimizer=true and a grid whose scatter runs in record form). */
+ * applied by the launch that finished their gradients -- the reduction of the network's weight gradients -- instead of by the
+ * optimizer kernel.  Either every parameter or none: n_params for a fused step with run_optimizer=true, plain Adam, GradientMode
+ * Overwrite, a model without encoding parameters and no dL_dinput asked for (TCNN_AMD_ADAM_IN_REDUCE=0 turns it off), else 0. */
 size_t tcnn_trainer_params_updated_in_flush(tcnn_trainer_t t);
 /* Introspection (no counterpart in the reference): how many times training_step() calls of this trainer have launched the kernel
  * that rearranges the network's weights into matrix-instruction fragments.  A model without encoding parameters trained with plain

@@ -1221,6 +1221,40 @@ def test_finalize_pass_inside_the_optimizer_launch_is_bit_identical(tcnn, oracle
         assert opt_a[key] == opt_b[key], key
 
 
+def test_scalar_max_level_declines_the_optimizer_prologue(tcnn, oracle, monkeypatch):
+    """A scalar max_level below the level count (here 8 of config_hash.json's 16 levels): the grid's backward pass settles the off levels'
+    gradients behind its kernels, so it does not pass the optimizer's offer on -- no step runs k_adam_prologue
+    (optimizer_prologue_steps() stays 0) and the finalize pass and k_adam are the two launches they are under TCNN_AMD_ADAM_PROLOGUE=0:
+    gradients, weights (fp32 master and half), both moments and the step counts agree bit for bit with that run."""
+    import msgpack
+
+    n = 4096
+    batches = [oracle.synthetic_batch(n, 2, 3, seed=80 + i) for i in range(3)]
+
+    def run(env):
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        tr = tcnn.Trainer(2, 3, CONFIG_C3B, seed=1337)
+        tr.set_max_level(0.5)
+        for x, t in batches:
+            tr.training_step(_t(x), _t(t))
+            assert tr.optimizer_prologue_steps() == 0 and tr.params_updated_in_flush() == 0
+        state = msgpack.unpackb(tr.serialize(True), raw=False)
+        for k in env:
+            monkeypatch.delenv(k)
+        return _bits(tr.params()), tr.params_full_precision().cpu().numpy().view(np.uint32), state["optimizer"], _bits(tr.param_gradients())
+
+    half_a, fp_a, opt_a, g_a = run({})
+    half_b, fp_b, opt_b, g_b = run({"TCNN_AMD_ADAM_PROLOGUE": "0"})
+    n_net = oracle.Trainer(2, 3, CONFIG_C3B, seed=1337).model.network.n_params
+    # (the finest level is hashed: the last 2^15 entries of two features are its gradients)
+    assert np.any(g_a[n_net:] & 0x7FFF) and not np.any(g_a[-2 * 32768:] & 0x7FFF), "the coarse levels are on, the finest is off"
+    assert np.array_equal(g_a, g_b) and np.array_equal(fp_a, fp_b) and np.array_equal(half_a, half_b)
+    assert opt_a["current_step"] == opt_b["current_step"] == len(batches)
+    for key in ("first_moments_binary", "second_moments_binary", "param_steps_binary"):
+        assert opt_a[key] == opt_b[key], key
+
+
 @pytest.mark.parametrize("cfg,n", [(CONFIG_C2, 8192), (CONFIG_C1, 4096)])
 def test_adam_behind_the_slab_reduction_is_bit_identical(tcnn, oracle, cfg, n, monkeypatch):
     """Models without encoding parameters (BASELINE configs 2 and 1): the optimizer's update of the network's weights is applied by the
@@ -1247,6 +1281,40 @@ def test_adam_behind_the_slab_reduction_is_bit_identical(tcnn, oracle, cfg, n, m
     # config 1's 32-wide network does not take the fused step (no slabs to ride on): both runs are then the same path
     assert n_b == 0 and n_a == (len(half_a) if cfg is CONFIG_C2 else n_a), "which kernel applied the update is not what this run asked for"
     assert np.array_equal(g_a, g_b) and np.any(g_a != 0)
+    assert np.array_equal(fp_a, fp_b) and np.array_equal(half_a, half_b)
+    assert opt_a["current_step"] == opt_b["current_step"] == len(batches)
+    for key in ("first_moments_binary", "second_moments_binary", "param_steps_binary"):
+        assert opt_a[key] == opt_b[key], key
+
+
+def test_input_gradients_keep_the_optimizer_out_of_the_slab_reduction(tcnn, oracle, monkeypatch):
+    """BASELINE config 2 with dL_dinput asked for: the step's backward pass goes on behind the slab reduction (the encoding's input
+    gradients), and the trainer decides before the step that the reduction does not carry the optimizer's update
+    (params_updated_in_flush() == 0, as under TCNN_AMD_ADAM_IN_REDUCE=0) and that no fragment image is kept current: k_mlp_prep runs in
+    every step.  Weights (fp32 master and half), both moments, step counts, gradients and dL_dinput agree bit for bit with that run."""
+    import msgpack
+    import torch
+
+    n = 2048
+    batches = [oracle.synthetic_batch(n, 2, 3, seed=50 + i) for i in range(3)]
+
+    def run(env):
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        tr = tcnn.Trainer(2, 3, CONFIG_C2, seed=1337)
+        dx = torch.zeros((n, 2), dtype=torch.float32, device="cuda")
+        for i, (x, t) in enumerate(batches):
+            tr.training_step(_t(x), _t(t), dL_dinput=dx)
+            assert tr.last_step_kernel() != "unfused"
+            assert tr.params_updated_in_flush() == 0 and tr.image_preps() == i + 1
+        state = msgpack.unpackb(tr.serialize(True), raw=False)
+        for k in env:
+            monkeypatch.delenv(k)
+        return _bits(tr.params()), tr.params_full_precision().cpu().numpy().view(np.uint32), state["optimizer"], _bits(tr.param_gradients()), dx.cpu().numpy().view(np.uint32)
+
+    half_a, fp_a, opt_a, g_a, dx_a = run({})
+    half_b, fp_b, opt_b, g_b, dx_b = run({"TCNN_AMD_ADAM_IN_REDUCE": "0"})
+    assert np.array_equal(g_a, g_b) and np.any(g_a != 0) and np.array_equal(dx_a, dx_b) and np.any(dx_a != 0)
     assert np.array_equal(fp_a, fp_b) and np.array_equal(half_a, half_b)
     assert opt_a["current_step"] == opt_b["current_step"] == len(batches)
     for key in ("first_moments_binary", "second_moments_binary", "param_steps_binary"):

@@ -1,6 +1,6 @@
-// adam_device.h -- one Adam update (optimizers/adam.h:48-119), shared by k_adam (k_misc.hip) and by the gradient kernels that apply
-// the update to the chunk they own as they flush it (k_grid_scatter.hip).  One source for both, so that the two routes produce the
-// same bits.
+// adam_device.h -- one Adam update (optimizers/adam.h:48-119), shared by k_adam, k_adam_prologue (k_misc.hip) and by the slab reduction
+// that applies the update to the weights whose gradients it finishes (k_wgrad_reduce_adam, k_mlp.hip).  One source for all, so that every
+// route produces the same bits.
 #pragma once
 #include "tcnn_common.h"
 
@@ -9,8 +9,7 @@ namespace tcnn_amd {
 // One parameter, branch-free (selects instead of early returns, so that a wave whose lanes disagree about "skipped" does not
 // execute the body twice).  common_debias = debias_table[common_step]; parameters with their own step count look theirs up.
 // `updated` reports whether adam.h:76-84 lets this parameter through.
-// debias_of(t): the debiasing factor of step t <= common_step (a table lookup: k_adam reads the global table, the gradient kernels a
-// window of it they keep in LDS).
+// debias_of(t): the debiasing factor of step t <= common_step (a lookup in the optimizer's table).
 // G: the type the gradient was loaded as, _Float16 (the trainer's gradient vector) or float (a caller's own fp32 gradients, standalone
 // optimizers): the value is taken to float as it is and unscaled the same way -- no rounding in between for either type.
 template <typename DebiasOf, typename G>

@@ -25,7 +25,6 @@
 // Arithmetic per contribution is the reference's: (half) weight * dL_dy in fp16 (grid.h:254), weights as fp32 products in dimension
 // order; the sum is exact (integers), rounded to fp16 once -- bit-identical to k_grid_scatter and to the oracle's orc_grid_backward_exact.
 #include "grid_fixed.h"
-#include "adam_device.h"
 #include "mlp_side_jobs.h"
 
 #include <algorithm>
@@ -826,11 +825,11 @@ void grid_scatter_lists_plan(const GridMeta& meta, uint32_t n, std::vector<GridS
 	while (!tasks.empty() && tasks.back().n_entries == 0) tasks.pop_back();
 }
 
-void grid_backward_lists(hipStream_t stream, const GridMeta& meta, const GridMeta* dev_meta, const GridScatterTask* dev_tasks, uint32_t n_tasks,
+bool grid_backward_lists(hipStream_t stream, const GridMeta& meta, const GridMeta* dev_meta, const GridScatterTask* dev_tasks, uint32_t n_tasks,
                          const GridScatterRange* dev_ranges, uint32_t n_ranges, uint64_t* scratch, uint32_t n, MatView x,
                          const void* dL_dy, uint32_t dy_stride_sample, uint32_t dy_stride_level, void* grad, const GridHitLists& lists, void* gvals, bool accumulate,
                          const MlpReduceJob* reduce_job, uint32_t* fallback_count) {
-	if (n_tasks == 0) return;
+	if (n_tasks == 0) return false;
 	CHECK_THROW(lists.elems != nullptr && lists.sidx != nullptr && lists.heads != nullptr && lists.stragglers != nullptr && lists.counts != nullptr && lists.n_items > 0 && gvals != nullptr);
 	CHECK_THROW(lists.item_capacity % 8 == 0 && lists.item_samples <= 65536 && lists.item_samples * meta.n_features_per_level * 2 * 2 <= 64 * 1024); // (k_grid_list_gradients: the slices of two items in LDS)
 	CHECK_THROW(n > 0 && n <= grid_hit_max_samples(meta) && meta.hash_type != (uint32_t)HashType::Rng);
@@ -873,7 +872,7 @@ void grid_backward_lists(hipStream_t stream, const GridMeta& meta, const GridMet
 		case 3: dispatch_lists<3>(stream, meta.n_features_per_level, a, n_tasks); break;
 		default: throw std::runtime_error{"grid_backward_lists: 2 or 3 input dims"};
 	}
-	grid_scatter_finalize(stream, dev_ranges, n_ranges, scratch, grad, accumulate, reduce_job);
+	return grid_scatter_finalize(stream, dev_ranges, n_ranges, scratch, grad, accumulate, reduce_job);
 }
 
 } // namespace tcnn_amd

@@ -763,12 +763,12 @@ __global__ void __launch_bounds__(WR_ELEMS * WR_GROUPS) k_wgrad_reduce_jobs(cons
 	mlp_reduce_block(part, blockIdx.x, threadIdx.x, n_elems, cols, jobs.ldg[blockIdx.y], n_slabs, jobs.slabs[blockIdx.y], jobs.grad[blockIdx.y], accumulate);
 }
 
-// The same reduction with the optimizer's update behind it (AdamInFlush, tcnn_common.h): a matrix weight's gradient is final the moment
+// The same reduction with the optimizer's update behind it (AdamInReduce, tcnn_common.h): a matrix weight's gradient is final the moment
 // its slabs are summed, so adam.h:48-119 runs on it at once -- the same adam_one as k_adam, on the same half-rounded gradient: the same
 // bits.  For networks without encoding parameters (BASELINE config 2) this IS the optimizer step: one ~4 us launch less.
 template <typename STEP_T>
 __global__ void __launch_bounds__(WR_ELEMS * WR_GROUPS) k_wgrad_reduce_adam(const uint32_t n_elems, const uint32_t n_slabs, const float* __restrict__ slabs, half_t* __restrict__ grad,
-                                                                            const AdamInFlush adam) {
+                                                                            const AdamInReduce adam) {
 	__shared__ float part[WR_GROUPS * WR_ELEMS];
 	mlp_reduce_block(part, blockIdx.x, threadIdx.x, n_elems, n_elems, n_elems, n_slabs, slabs, grad, 0);
 	const uint32_t e = threadIdx.x & (WR_ELEMS - 1), grp = threadIdx.x / WR_ELEMS;
@@ -788,7 +788,7 @@ __global__ void __launch_bounds__(WR_ELEMS * WR_GROUPS) k_wgrad_reduce_adam(cons
 		adam.m1[i] = m1;
 		adam.m2[i] = m2;
 		steps[i] = (STEP_T)step;
-		if (adam.image) { // keep the fragment images current (AdamInFlush::image): what k_mlp_prep would gather at the start of the next step
+		if (adam.image) { // keep the fragment images current (AdamInReduce::image): what k_mlp_prep would gather at the start of the next step
 			const uint4 where = *(const uint4*)(adam.image_inv + (size_t)IMAGE_INV_WIDTH * i);
 			half_t* image = (half_t*)adam.image;
 			if (where.x != 0xffffffffu) image[where.x] = w_h;
@@ -928,7 +928,7 @@ void mlp_activation_backward_output(hipStream_t stream, uint32_t n_elems, uint32
 	hipLaunchKernelGGL(k_act_bwd_output, dim3(div_round_up(n_elems, 256)), dim3(256), 0, stream, n_elems, activation, (const half_t*)dL_dout, (const half_t*)out, (half_t*)result);
 }
 
-void mlp_reduce_slabs(hipStream_t stream, uint32_t n_params, uint32_t n_slabs, const float* slabs, void* grad_half, bool accumulate, const AdamInFlush* adam) {
+void mlp_reduce_slabs(hipStream_t stream, uint32_t n_params, uint32_t n_slabs, const float* slabs, void* grad_half, bool accumulate, const AdamInReduce* adam) {
 	if (n_params == 0) return;
 	const dim3 grid(div_round_up(n_params, (uint32_t)WR_ELEMS)), block(WR_ELEMS * WR_GROUPS);
 	if (adam && !accumulate) {

@@ -156,7 +156,6 @@ struct MlpReduceJob {
 	const float* slabs = nullptr;
 	void* grad = nullptr; // half
 	int accumulate = 0;
-	mutable bool taken = false; // set by the launch that carried the job
 };
 
 } // namespace tcnn_amd

@@ -221,18 +221,17 @@ struct EncodingContext {
 	uint64_t hit_generation = 0; // the encoding's list counters are reused by later forward passes: lists are valid while this is the latest one on its stream
 	const void* hit_stream = nullptr;
 	uint32_t n = 0;
-	mutable bool dy_records = false; // the level planes handed to backward() hold 16-byte scatter records {coordinates, gradients} (MlpTrainRequest::dx_record_dims); set by the caller of backward()
-	// Set by the caller of backward() for a step whose optimizer update may ride on the gradient kernel (AdamInFlush, arrays
-	// indexed from this encoding's first parameter).  An encoding that takes the offer reports in adam_done which of its
-	// parameters it has updated; whatever is not listed there is still the optimizer's to do.
-	mutable const AdamInFlush* adam = nullptr;
-	mutable ParamRanges adam_done;
-	// likewise: a small job the backward pass may carry on one of its launches (MlpReduceJob::taken reports it)
-	mutable const MlpReduceJob* reduce_job = nullptr;
-	// likewise: the optimizer's launch offers to run the scatter's finalize pass (and the reduce job) as its prologue (AdamPrologue,
-	// tcnn_common.h).  A backward pass that takes the offer fills it in, sets ->pending and launches no finalize pass of its own.
-	mutable AdamPrologue* prologue = nullptr;
 	std::vector<EncodingContext> nested; // Composite: one context per nested encoding
+};
+
+// What the caller of Encoding::backward() offers to that one call, and what the call reports back.  An encoding is free to ignore all of it.
+struct BackwardHandoff {
+	bool dy_records = false;                  // the level planes hold 16-byte scatter records {coordinates, gradients} (MlpTrainRequest::dx_record_dims)
+	const MlpReduceJob* reduce_job = nullptr; // a small job the pass may carry on one of its launches, or pass on with the prologue
+	// the optimizer's launch offers to run the scatter's finalize pass (and the reduce job) as its prologue (AdamPrologue, tcnn_common.h):
+	// a backward pass that takes the offer fills it in, sets ->pending and launches no finalize pass of its own
+	AdamPrologue* prologue = nullptr;
+	bool reduce_carried = false;              // reported: reduce_job went with a launch of this pass or with the prologue -- it is no longer the caller's to run
 };
 
 class Encoding {
@@ -257,7 +256,8 @@ public:
 	virtual EncodingContext forward(hipStream_t stream, uint32_t n, MatView x, const void* params, void* out, bool prepare_input_gradients, bool prepare_param_gradients) = 0;
 	// dL_dy [n][padded] T; grads: T[n_params] or nullptr (Ignore)
 	// dy_planes: dL_dy is laid out as level planes [padded / F][n][F] (only if level_plane_features() allowed it), else AoS
-	virtual void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes) = 0;
+	// handoff (optional): what the fused step offers to this pass (BackwardHandoff)
+	virtual void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes, BackwardHandoff* handoff = nullptr) = 0;
 	// second-order input gradients (object.h:278-288), with v = dL_ddLdx [n][d_in] fp32 and d = dL_dy [n][padded] T:
 	//   dL_ddLdy [n][padded] T = J v (the tangent; exactly zero in the padding columns), dL_dx = d/dx <v, J^T d> in fp32 through the view,
 	//   grads = d/dparams of the same by `mode`.  Null results (and Ignore) are not computed; dL_dy may be null when only dL_ddLdy is asked for.
@@ -531,35 +531,37 @@ public:
 		return ctx;
 	}
 
-	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes) override {
+	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes, BackwardHandoff* handoff) override {
 		if ((!dL_dx && mode == GradientMode::Ignore) || n == 0) return;
+		BackwardHandoff offer = handoff ? *handoff : BackwardHandoff{};
+		const auto all_levels = [&](const void* dy) { // (reports through the caller's hand-off, if there is one)
+			const bool carried = backward_all_levels(stream, ctx, n, x, dy, dL_dx, params, grads, mode, dy_planes, offer);
+			if (handoff) handoff->reduce_carried = carried;
+		};
 		const uint32_t l_bwd = m_max_level_gpu ? m_meta.n_levels : levels_on(true); // (a per-sample array overrides the scalar)
-		if (!m_max_level_gpu && l_bwd == m_meta.n_levels) return backward_all_levels(stream, ctx, n, x, dL_dy, dL_dx, params, grads, mode, dy_planes);
+		if (!m_max_level_gpu && l_bwd == m_meta.n_levels) return all_levels(dL_dy);
 		if (m_max_level_gpu) { // per sample: dL/dy of the skipped (sample, level) pairs zeroed -- the exact sums add nothing for a zero product
-			CHECK_THROW(!ctx.dy_records); // (scatter_records_usable() is false while a per-sample array is set)
+			CHECK_THROW(!offer.dy_records); // (scatter_records_usable() is false while a per-sample array is set)
 			const uint32_t F = m_meta.n_features_per_level;
 			const size_t elem = dy_planes ? 2 : (m_fp32 ? 4 : 2);
 			ArenaBuf masked{stream, (size_t)n * padded_output_width() * elem};
 			if (dy_planes) zero_levels(stream, 2, n, F, F, (uint64_t)n * F, masked.data(), true, dL_dy);
 			else zero_levels(stream, elem, n, F, padded_output_width(), F, masked.data(), true, dL_dy);
-			return backward_all_levels(stream, ctx, n, x, masked.data(), dL_dx, params, grads, mode, dy_planes);
+			return all_levels(masked.data());
 		}
-		// scalar (grid.h:237-245): the optimizer's offers to ride on this pass are declined -- the off levels' gradients are settled below,
-		// after the kernels, and the optimizer's own launch sees every parameter
-		const AdamInFlush* adam = ctx.adam;
-		AdamPrologue* prologue = ctx.prologue;
-		ctx.adam = nullptr;
-		ctx.prologue = nullptr;
+		// scalar (grid.h:237-245): the optimizer's offer of its prologue is declined by not passing it on -- the off levels' gradients are
+		// settled below, after the kernels, and the optimizer's own launch sees every parameter
+		offer.prologue = nullptr;
 		GradientTail tail{*this, stream, grads, mode, l_bwd};
-		backward_all_levels(stream, ctx, n, x, dL_dy, dL_dx, params, grads, mode, dy_planes);
+		all_levels(dL_dy);
 		tail.settle();
-		ctx.adam_done.clear();
-		ctx.adam = adam;
-		ctx.prologue = prologue;
 	}
 
-	void backward_all_levels(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes) {
+	// returns whether offer.reduce_job was carried: by a launch of this pass, or handed on with the prologue
+	bool backward_all_levels(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes,
+	                         const BackwardHandoff& offer) {
 		const size_t elem = m_fp32 ? 4 : 2;
+		bool carried = false;
 		if (mode != GradientMode::Ignore) {
 			CHECK_THROW(grads != nullptr);
 			const bool scratch32 = !m_fp32 && m_meta.n_features_per_level == 1; // grid.h:660: F == 1 accumulates in fp32
@@ -574,7 +576,7 @@ public:
 				// hit lists of this very batch, their counters not yet handed to a later forward pass of this stream
 				const bool lists = ctx.hit_elems && ctx.n == n && ctx.hit_stream == (const void*)stream && hit_counters(stream).generation == ctx.hit_generation;
 				if (lists) { // k_grid_scatter_lists.hip: a static plan, nothing to tune
-					CHECK_THROW(!ctx.dy_records); // the listed elements bring entries and weights along: dL/dy is gathered from plain level planes (or rows)
+					CHECK_THROW(!offer.dy_records); // the listed elements bring entries and weights along: dL/dy is gathered from plain level planes (or rows)
 					ListsPlan& lp = lists_plan(n, stream);
 					const uint32_t F = m_meta.n_features_per_level;
 					// dL/dy as rows (a caller's own network): into level planes first -- the streamed tasks read a level's gradients sample after
@@ -587,20 +589,20 @@ public:
 					const bool planes_now = dy_planes || dy_as_planes;
 					const void* dy_src = dy_as_planes ? dy_as_planes.data() : dL_dy;
 					const uint32_t dy_stride_sample = planes_now ? F : padded_output_width(), dy_stride_level = planes_now ? n * F : F;
-					ctx.adam_done.clear(); // (this kernel does not carry the optimizer's update: measured 20 % slower in round 4)
 					++m_list_scatters;
 					// the finalize pass (and the reduce job with it) may be left to the optimizer's launch: no ranges, no job -> no launch here
-					const bool defer = take_prologue(ctx, lp.dev_ranges.as<GridScatterRange>(), lp.host_ranges, lp.scratch.as<uint64_t>(), grads, mode);
+					const bool defer = take_prologue(offer, lp.dev_ranges.as<GridScatterRange>(), lp.host_ranges, lp.scratch.as<uint64_t>(), grads, mode);
 					ArenaBuf gvals{stream, grid_list_gradients_bytes(m_meta, ctx.hit_lists)}; // dL/dy in list order: written and read by the two kernels of this call
-					grid_backward_lists(stream, m_meta, dev_meta(), lp.dev_tasks.as<GridScatterTask>(), lp.n_tasks,
+					carried = grid_backward_lists(stream, m_meta, dev_meta(), lp.dev_tasks.as<GridScatterTask>(), lp.n_tasks,
 					                    lp.dev_ranges.as<GridScatterRange>(), defer ? 0u : lp.n_ranges, lp.scratch.as<uint64_t>(), n, x, dy_src, dy_stride_sample, dy_stride_level, grads, ctx.hit_lists,
-					                    gvals.data(), mode == GradientMode::Accumulate, defer ? nullptr : ctx.reduce_job, hit_counters(stream).fallbacks.as<uint32_t>());
+					                    gvals.data(), mode == GradientMode::Accumulate, defer ? nullptr : offer.reduce_job, hit_counters(stream).fallbacks.as<uint32_t>());
+					if (defer && offer.reduce_job) carried = true; // (it went with the prologue)
 					if (dL_dx) {
 						CHECK_THROW(ctx.dy_dx);
 						CHECK_THROW(!dy_planes);
 						grid_backward_input(stream, m_meta, m_fp32, n, dL_dy, padded_output_width(), ctx.dy_dx.as<float>(), *dL_dx);
 					}
-					return;
+					return carried;
 				}
 				ScatterPlan& plan = scatter_plan(n, stream);
 				const uint32_t F = m_meta.n_features_per_level;
@@ -614,19 +616,14 @@ public:
 					times.memset(0);
 				}
 				const uint32_t dy_stride_sample = dy_planes ? F : padded_output_width(), dy_stride_level = dy_planes ? n * F : F;
-				const AdamInFlush* adam = nullptr;
-				ctx.adam_done.clear();
-				if (ctx.adam && mode == GradientMode::Overwrite) {
-					if (dy_planes && ctx.dy_records) ctx.adam_done = plan.adam_ranges;
-					if (!ctx.adam_done.empty()) adam = ctx.adam;
-				}
 				// (not in the step whose launch is timed for the tuner: the plan, ranges and scratch included, is rebuilt right after it)
-				const bool defer = !tune && take_prologue(ctx, plan.dev_ranges.as<GridScatterRange>(), plan.host_ranges, plan.scratch.as<uint64_t>(), grads, mode);
-				grid_backward_lds(stream, m_meta, dev_meta(), plan.dev_tasks.as<GridScatterTask>(), plan.n_tasks, plan.dev_ranges.as<GridScatterRange>(), defer ? 0u : plan.n_ranges,
+				const bool defer = !tune && take_prologue(offer, plan.dev_ranges.as<GridScatterRange>(), plan.host_ranges, plan.scratch.as<uint64_t>(), grads, mode);
+				carried = grid_backward_lds(stream, m_meta, dev_meta(), plan.dev_tasks.as<GridScatterTask>(), plan.n_tasks, plan.dev_ranges.as<GridScatterRange>(), defer ? 0u : plan.n_ranges,
 				                  plan.scratch.as<uint64_t>(), n, x, dL_dy, dy_stride_sample, dy_stride_level, grads, mask,
-				                  mode == GradientMode::Accumulate, dy_planes && ctx.dy_records, tune ? times.as<uint64_t>() : nullptr, adam, defer ? nullptr : ctx.reduce_job);
+				                  mode == GradientMode::Accumulate, dy_planes && offer.dy_records, tune ? times.as<uint64_t>() : nullptr, defer ? nullptr : offer.reduce_job);
+				if (defer && offer.reduce_job) carried = true; // (it went with the prologue)
 				if (m_any_binned) { // levels cut into more than 64 chunks (k_grid_bin.hip)
-					CHECK_THROW(!(dy_planes && ctx.dy_records));
+					CHECK_THROW(!(dy_planes && offer.dy_records));
 					ArenaBuf workspace{stream, grid_bin_workspace_bytes(m_meta, n)};
 					grid_backward_binned(stream, m_meta, dev_meta(), n, x, dL_dy, dy_stride_sample, dy_stride_level, grads, mode == GradientMode::Accumulate, workspace.data(),
 					                     hit_counters(stream).fallbacks.as<uint32_t>());
@@ -650,6 +647,7 @@ public:
 			CHECK_THROW(!dy_planes);
 			grid_backward_input(stream, m_meta, m_fp32, n, dL_dy, padded_output_width(), ctx.dy_dx.as<float>(), *dL_dx);
 		}
+		return carried;
 	}
 
 	// grid.h:902-1026
@@ -717,24 +715,23 @@ public:
 	// TCNN_AMD_GRID_SCATTER=atomic selects the reference-shaped global-atomic kernel (kept for A/B runs and as the fp32 / F==1 path)
 	static bool use_lds_scatter() { return switches().grid_scatter_lds; }
 
-	// The optimizer's launch has offered to run this backward pass's finalize pass (ctx.prologue): hand it the shared ranges, their scratch
-	// and the reduce job.  Only where the gradient kernel does not apply the optimizer step itself (AdamInFlush) and a finalize pass exists.
-	bool take_prologue(const EncodingContext& ctx, const GridScatterRange* dev_ranges, const std::vector<GridScatterRange>& ranges, uint64_t* scratch, void* grads, GradientMode mode) const {
-		AdamPrologue* p = ctx.prologue;
-		if (!p || !p->offered || p->pending || ctx.adam || (ranges.empty() && !ctx.reduce_job) || m_any_binned) return false;
+	// The optimizer's launch has offered to run this backward pass's finalize pass (offer.prologue): hand it the shared ranges, their scratch
+	// and the reduce job.  Only where there is something to finish: shared ranges or the job.
+	bool take_prologue(const BackwardHandoff& offer, const GridScatterRange* dev_ranges, const std::vector<GridScatterRange>& ranges, uint64_t* scratch, void* grads, GradientMode mode) const {
+		AdamPrologue* p = offer.prologue;
+		if (!p || p->pending || (ranges.empty() && !offer.reduce_job) || m_any_binned) return false;
 		p->dev_ranges = dev_ranges;
 		p->ranges = ranges;
 		p->scratch = scratch;
 		p->grad_base = grads;
 		p->accumulate = mode == GradientMode::Accumulate;
 		p->has_reduce = false;
-		if (ctx.reduce_job) {
+		if (offer.reduce_job) {
 			p->has_reduce = true;
-			p->reduce_elems = ctx.reduce_job->n_elems;
-			p->reduce_slabs = ctx.reduce_job->n_slabs;
-			p->slabs = ctx.reduce_job->slabs;
-			p->reduce_accumulate = ctx.reduce_job->accumulate;
-			ctx.reduce_job->taken = true;
+			p->reduce_elems = offer.reduce_job->n_elems;
+			p->reduce_slabs = offer.reduce_job->n_slabs;
+			p->slabs = offer.reduce_job->slabs;
+			p->reduce_accumulate = offer.reduce_job->accumulate;
 		}
 		p->pending = true;
 		return true;
@@ -747,7 +744,6 @@ public:
 		uint32_t n_tasks = 0, n_ranges = 0;
 		uint32_t launches = 0;
 		bool tuned = false;
-		ParamRanges adam_ranges; // what a launch of this plan in record form updates itself when it is handed an AdamInFlush
 	};
 	// TCNN_AMD_SCATTER_TUNE=0 keeps the untuned task list (A/B runs)
 	static bool scatter_tuning_enabled() { return switches().scatter_tune; }
@@ -759,7 +755,6 @@ public:
 		plan.n_tasks = (uint32_t)plan.host_tasks.size();
 		plan.n_ranges = (uint32_t)ranges.size();
 		plan.host_ranges = ranges;
-		plan.adam_ranges = grid_scatter_adam_ranges(m_meta, plan.host_tasks, true);
 		plan.dev_tasks.resize(plan.host_tasks.size() * sizeof(GridScatterTask));
 		if (!plan.host_tasks.empty()) HIP_CHECK_THROW(hipMemcpy(plan.dev_tasks.data(), plan.host_tasks.data(), plan.host_tasks.size() * sizeof(GridScatterTask), hipMemcpyHostToDevice));
 		plan.dev_ranges.resize(ranges.size() * sizeof(GridScatterRange));
@@ -966,7 +961,7 @@ public:
 		if (out && padded_output_width() > 0) oneblob_forward(stream, m_fp32, n, m_n_dims, m_n_bins, x, out, padded_output_width());
 		return {};
 	}
-	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes) override {
+	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes, BackwardHandoff*) override {
 		if (!dL_dx) return;
 		oneblob_backward_input(stream, m_fp32, n, m_n_dims, m_n_bins, x, dL_dy, padded_output_width(), *dL_dx);
 	}
@@ -1004,7 +999,7 @@ public:
 		if (out && padded_output_width() > 0) identity_forward(stream, m_fp32, n, 0, 1.0f, 0.0f, x, out, padded_output_width()); // no live columns: all padding
 		return {};
 	}
-	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes) override {
+	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes, BackwardHandoff*) override {
 		if (dL_dx) zero_input_gradient(stream, n, m_n_dims, *dL_dx);
 	}
 	// the output is constant: a zero tangent over the padding and no Hessian term
@@ -1064,7 +1059,7 @@ public:
 		}
 		return {};
 	}
-	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes) override {
+	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes, BackwardHandoff*) override {
 		CHECK_THROW(!dy_planes);
 		if (dL_dx) {
 			// PPNG1 / PPNG2: the reference leaves dL_dinput untouched (ppng_1.h:268-321 never writes it); PPNG3: ppng_3.h:586-607
@@ -1139,7 +1134,7 @@ public:
 		if (out && padded_output_width() > 0) identity_forward(stream, m_fp32, n, m_n_dims, m_scale, m_offset, x, out, padded_output_width());
 		return {};
 	}
-	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes) override {
+	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes, BackwardHandoff*) override {
 		if (!dL_dx) return;
 		identity_backward_input(stream, m_fp32, n, m_n_dims, m_scale, dL_dy, padded_output_width(), *dL_dx);
 	}
@@ -1178,7 +1173,7 @@ public:
 		periodic_forward(stream, m_triangle, m_fp32, n, m_n_dims, m_n_frequencies, x, out, padded_output_width(), ctx.dy_dx.as<float>());
 		return ctx;
 	}
-	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes) override {
+	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes, BackwardHandoff*) override {
 		if (!dL_dx || n == 0) return;
 		CHECK_THROW(ctx.dy_dx); // frequency.h:150-152: needs a forward pass with prepare_input_gradients
 		periodic_backward_input(stream, m_fp32, n, m_n_dims, outputs_per_input(), dL_dy, padded_output_width(), ctx.dy_dx.as<float>(), *dL_dx);
@@ -1218,7 +1213,7 @@ public:
 		if (out && padded_output_width() > 0) sh_forward(stream, m_fp32, n, m_degree, x, out, padded_output_width());
 		return {};
 	}
-	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes) override {
+	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes, BackwardHandoff*) override {
 		if (!dL_dx) return;
 		sh_backward_input(stream, m_fp32, n, m_degree, x, dL_dy, padded_output_width(), *dL_dx);
 	}
@@ -1369,7 +1364,7 @@ public:
 		}
 		return ctx;
 	}
-	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes) override {
+	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes, BackwardHandoff*) override {
 		if (n == 0) return;
 		CHECK_THROW(!dy_planes && ctx.nested.size() == m_nested.size());
 		const size_t elem = m_fp32 ? 4 : 2;
@@ -1741,7 +1736,7 @@ public:
 
 	// ---- A fragment image that lives across training steps, for models whose optimizer step rides on the weight gradients' slab
 	// reduction (BASELINE config 2).  k_wgrad_reduce_adam writes every weight it updates into the image elements that hold it
-	// (AdamInFlush::image / image_inv), so the next step starts with a current image instead of a k_mlp_prep launch -- 4.5 of config 2's
+	// (AdamInReduce::image / image_inv), so the next step starts with a current image instead of a k_mlp_prep launch -- 4.5 of config 2's
 	// 27 us.  The image is current for the parameter vector `live_params()`; whoever changes those parameters any other way calls
 	// invalidate_live_image() (the Trainer does, and stops using the image for good once it has handed out a pointer to its parameters).
 	struct LiveImage {
@@ -2194,6 +2189,35 @@ struct StepProfile {
 	}
 };
 
+// The data of one fused training step (NetworkWithInputEncoding::fused_step / fused_mlp_and_scatter).  target == nullptr requires
+// external_dL_dy; out / dL_dout / L: [n][padded_out], or the compact [n][dims] matrices with compact_context (any may be null).
+struct FusedStepData {
+	const float* target = nullptr;
+	const float* data_pdf = nullptr;
+	const void* external_dL_dy = nullptr;
+	LossType loss = LossType::L2;
+	float loss_scale = 1.0f;
+	void* out = nullptr;
+	void* dL_dout = nullptr;
+	float* L = nullptr;
+	bool compact_context = false;
+	MatViewMut* dL_dinput = nullptr;
+	const void* params = nullptr;
+	void* gradients = nullptr;
+	GradientMode mode = GradientMode::Overwrite;
+	StepProfile* profile = nullptr;
+};
+// Where the optimizer's update of a fused training step runs: decided once per step, by Trainer::training_step.
+enum class OptimizerPlace { None, InReduce, Prologue, OwnLaunch };
+// What that decision hands to the step -- at most one of the two:
+struct OptimizerOffer {
+	// InReduce: the slab reduction applies this update (k_wgrad_reduce_adam).  Binding: the step must be one whose reduction carries
+	// it (NetworkWithInputEncoding::reduction_carries_update), and the caller launches no optimizer afterwards.
+	const AdamInReduce* in_reduce = nullptr;
+	// Prologue: the optimizer's launch offers to finish the gradients itself.  ->pending reports whether the backward pass took the offer.
+	AdamPrologue* prologue = nullptr;
+};
+
 class NetworkWithInputEncoding : public Model {
 public:
 	NetworkWithInputEncoding(uint32_t n_dims_to_encode, uint32_t n_output_dims, const Json& encoding, const Json& network) {
@@ -2322,7 +2346,12 @@ public:
 		_Float16* g = (_Float16*)gradients;
 		if (ctx.fused) {
 			if (dL_dinput) throw std::runtime_error{"NetworkWithInputEncoding::backward: input gradients were not prepared by forward()"};
-			fused_mlp_and_scatter(stream, ctx, n, input, nullptr, nullptr, dL_doutput, LossType::L2, 1.0f, nullptr, nullptr, nullptr, false, nullptr, params, gradients, mode);
+			FusedStepData step;
+			step.external_dL_dy = dL_doutput;
+			step.params = params;
+			step.gradients = gradients;
+			step.mode = mode;
+			fused_mlp_and_scatter(stream, ctx, n, input, step, OptimizerOffer{});
 			return;
 		}
 		ArenaBuf dL_dnetwork_input;
@@ -2397,8 +2426,9 @@ public:
 	// TCNN_AMD_SIDE_JOBS=0: k_mlp_prep stays a launch of its own (A/B runs; read per step so that tests cover both)
 	static bool side_jobs_enabled() { return switches().side_jobs; }
 	bool fused_step_supported(uint32_t n) const { return use_fused_step() && !m_network->layerwise() && mlp_train_any_kernel(m_network->desc(), n); }
-	// the fused step of a model without encoding parameters hands its weight gradients to the optimizer inside the slab reduction
-	bool optimizer_rides_on_reduce() const { return m_encoding->n_params() == 0; }
+	// exactly when the slab reduction of a fused step is a launch of its own that finishes EVERY gradient of the model, so that it can apply
+	// the optimizer's update behind it (OptimizerOffer::in_reduce): no encoding parameters, no dL/dinput asked for, gradients overwritten
+	bool reduction_carries_update(bool want_dL_dinput, GradientMode mode) const { return m_encoding->n_params() == 0 && !want_dL_dinput && mode == GradientMode::Overwrite; }
 	// TCNN_AMD_LIVE_IMAGE=0: every step builds its fragment images with k_mlp_prep again instead of keeping one current (Network::live_image;
 	// bit-identical, one ~4.5 us launch more per step of a model without encoding parameters)
 	static bool live_image_enabled() { return switches().live_image; }
@@ -2428,21 +2458,17 @@ public:
 	}
 
 	// forward + loss + backward of a training step with the MLP part as ONE kernel (k_train.hip): same results as
-	// forward() -> loss_evaluate() -> backward(), activations never leave the CU.  out / dL_dout / L: [n][padded_out].
-	std::unique_ptr<ModelContext> fused_step(hipStream_t stream, uint32_t n, MatView input, const float* target, const float* data_pdf, const void* external_dL_dy,
-	                                         LossType loss, float loss_scale, void* out, void* dL_dout, float* L, bool compact_context, MatViewMut* dL_dinput, const void* params,
-	                                         void* gradients, GradientMode mode, StepProfile* profile = nullptr, const AdamInFlush* adam = nullptr, ParamRanges* adam_done = nullptr,
-	                                         AdamPrologue* prologue = nullptr) {
+	// forward() -> loss_evaluate() -> backward(), activations never leave the CU.
+	std::unique_ptr<ModelContext> fused_step(hipStream_t stream, uint32_t n, MatView input, const FusedStepData& step, const OptimizerOffer& optimizer) {
 		check_batch(n);
 		auto ctx = std::make_unique<Ctx>();
 		// Everything in order on the caller's stream.  Running the two small kernels around the MLP kernel (k_mlp_prep, k_wgrad_reduce,
 		// ~5 us each, independent of the encoding kernels) on a side stream was measured and lost 13-15 us per step on every
 		// workload: a cross-stream event dependency costs more here than the kernels it hides (the same happened with Adam).
-		if (profile) profile->mark(stream, StepProfile::Encode, false);
-		fused_encode(stream, *ctx, n, input, params, dL_dinput != nullptr, mode != GradientMode::Ignore, side_jobs_enabled());
-		if (profile) profile->mark(stream, StepProfile::Encode, true);
-		fused_mlp_and_scatter(stream, *ctx, n, input, target, data_pdf, external_dL_dy, loss, loss_scale, out, dL_dout, L, compact_context, dL_dinput, params, gradients, mode, profile,
-		                      adam, adam_done, prologue);
+		if (step.profile) step.profile->mark(stream, StepProfile::Encode, false);
+		fused_encode(stream, *ctx, n, input, step.params, step.dL_dinput != nullptr, step.mode != GradientMode::Ignore, side_jobs_enabled());
+		if (step.profile) step.profile->mark(stream, StepProfile::Encode, true);
+		fused_mlp_and_scatter(stream, *ctx, n, input, step, optimizer);
 		return ctx;
 	}
 
@@ -2474,12 +2500,14 @@ public:
 	}
 
 	// second half: ONE MLP kernel (forward recomputed in registers, loss or external dL/doutput, backward, weight gradients),
-	// the slab reduction and the encoding's backward pass.  target == nullptr requires external_dL_dy.
-	void fused_mlp_and_scatter(hipStream_t stream, const Ctx& ctx, uint32_t n, MatView input, const float* target, const float* data_pdf, const void* external_dL_dy,
-	                           LossType loss, float loss_scale, void* out, void* dL_dout, float* L, bool compact_context, MatViewMut* dL_dinput, const void* params, void* gradients,
-	                           GradientMode mode, StepProfile* profile = nullptr, const AdamInFlush* adam = nullptr, ParamRanges* adam_done = nullptr, AdamPrologue* prologue = nullptr) {
+	// the slab reduction and the encoding's backward pass.
+	void fused_mlp_and_scatter(hipStream_t stream, const Ctx& ctx, uint32_t n, MatView input, const FusedStepData& step, const OptimizerOffer& optimizer) {
+		const void* params = step.params;
+		MatViewMut* dL_dinput = step.dL_dinput;
+		const GradientMode mode = step.mode;
+		StepProfile* profile = step.profile;
 		const _Float16* p = (const _Float16*)params;
-		_Float16* g = (_Float16*)gradients;
+		_Float16* g = (_Float16*)step.gradients;
 		const uint32_t n_net = (uint32_t)m_network->n_params();
 		const uint32_t x_plane_f = ctx.x_plane_f;
 		const bool need_dx = m_encoding->n_params() > 0 || dL_dinput;
@@ -2489,12 +2517,12 @@ public:
 		// (not with hit lists: their elements carry entries and weights, the scatter gathers dL/dy alone from plain level planes)
 		const bool records = plane_f > 0 && !ctx.encoding_ctx.hit_elems && m_encoding->padded_output_width() == m_encoding->output_width() && m_encoding->scatter_records_usable(input);
 		if (need_dx) dL_dnetwork_input = ArenaBuf{stream, records ? (size_t)n * m_encoding->scatter_record_planes() * 16 : (size_t)n * m_encoding->padded_output_width() * 2};
-		ctx.encoding_ctx.dy_records = records;
 
 		const MlpDesc& d = m_network->desc();
 		// a model whose only parameters are the network's: the optimizer's update rides on the slab reduction (k_wgrad_reduce_adam), which
 		// then also keeps the network's live image current (Network::live_image)
-		const bool with_adam = adam && adam_done && !need_dx && m_encoding->n_params() == 0 && mode == GradientMode::Overwrite;
+		const bool with_adam = optimizer.in_reduce != nullptr;
+		CHECK_THROW(!with_adam || reduction_carries_update(dL_dinput != nullptr, mode)); // the caller's decision binds
 		Network::LiveImage* live = with_adam && !ctx.image && live_image_enabled() ? m_network->live_image() : nullptr;
 		m_live_image_kept = false;
 		ArenaBuf prepared;
@@ -2518,18 +2546,18 @@ public:
 		request.oneblob_bins = ctx.oneblob_bins;
 		request.oneblob_dims = ctx.oneblob_bins ? m_encoding->input_width() : 0u;
 		request.dims = m_network->output_width();
-		request.loss = loss;
-		request.external_dL_dy = external_dL_dy != nullptr;
-		request.data_pdf = data_pdf != nullptr;
-		request.out = out != nullptr;
+		request.loss = step.loss;
+		request.external_dL_dy = step.external_dL_dy != nullptr;
+		request.data_pdf = step.data_pdf != nullptr;
+		request.out = step.out != nullptr;
 		request.dL_dx = need_dx;
 		request.dx_plane_features = plane_f;
 		request.dx_record_dims = records ? m_encoding->input_width() : 0u;
 		request.gradients = mode != GradientMode::Ignore;
-		request.compact_context = compact_context;
+		request.compact_context = step.compact_context;
 		const MlpTrainPlan plan = mlp_train_plan(d, request);
 		if (!plan.ok) throw std::runtime_error{"NetworkWithInputEncoding: no fused training kernel for this network, batch and set of options"};
-		CHECK_THROW(gradients != nullptr || !request.gradients);
+		CHECK_THROW(g != nullptr || !request.gradients);
 		const uint32_t n_slabs = request.gradients ? plan.grid : 0u;
 		ArenaBuf slabs;
 		if (n_slabs) slabs = ArenaBuf{stream, (size_t)n_slabs * n_net * sizeof(float)};
@@ -2537,9 +2565,9 @@ public:
 		args.image = image_data;
 		args.x = ctx.network_input.data();
 		if (ctx.oneblob_bins) args.oneblob_x = input;
-		args.target = target, args.data_pdf = data_pdf, args.external_dL_dy = external_dL_dy;
-		args.loss_scale = loss_scale;
-		args.out = out, args.dL_dout = dL_dout, args.L = L;
+		args.target = step.target, args.data_pdf = step.data_pdf, args.external_dL_dy = step.external_dL_dy;
+		args.loss_scale = step.loss_scale;
+		args.out = step.out, args.dL_dout = step.dL_dout, args.L = step.L;
 		args.dL_dx = dL_dnetwork_input.data();
 		args.dx_record_x = records ? input.data : nullptr;
 		args.slabs = slabs.as<float>();
@@ -2554,6 +2582,9 @@ public:
 		// The slab reduction rides on the scatter's finalize launch when the encoding's backward pass has one (two ~4.5 us launches
 		// become one); otherwise, or with TCNN_AMD_SIDE_JOBS=0, it is a launch of its own.
 		MlpReduceJob reduce_job;
+		BackwardHandoff offer; // to the encoding's backward pass
+		offer.dy_records = records;
+		offer.prologue = optimizer.prologue;
 		if (mode != GradientMode::Ignore) {
 			reduce_job.n_elems = n_net;
 			reduce_job.n_slabs = n_slabs;
@@ -2561,45 +2592,27 @@ public:
 			reduce_job.grad = g;
 			reduce_job.accumulate = mode == GradientMode::Accumulate ? 1 : 0;
 			if (!(need_dx && side_jobs_enabled())) {
-				AdamInFlush adam_here;
+				AdamInReduce adam_here;
 				if (with_adam) {
-					adam_here = *adam;
+					adam_here = *optimizer.in_reduce;
 					if (live) {
 						adam_here.image = live->image.data();
 						adam_here.image_inv = live->inverse.as<uint32_t>();
 					}
 				}
 				mlp_reduce_slabs(stream, n_net, n_slabs, slabs.as<float>(), g, mode == GradientMode::Accumulate, with_adam ? &adam_here : nullptr);
-				if (with_adam) {
-					adam_done->clear();
-					adam_done->emplace_back((size_t)0, (size_t)n_net);
-					if (live) {
-						live->params = params; // current again once this launch has run
-						m_live_image_kept = true;
-					}
+				if (live) {
+					live->params = params; // current again once this launch has run
+					m_live_image_kept = true;
 				}
-			} else ctx.encoding_ctx.reduce_job = &reduce_job;
+			} else offer.reduce_job = &reduce_job;
 		}
 		if (need_dx) {
 			if (profile) profile->mark(stream, StepProfile::EncodingBackward, false);
-			// the optimizer's offer to have its update applied by the gradient kernel, re-based to the encoding's parameters
-			AdamInFlush enc_adam;
-			if (adam && adam_done) {
-				enc_adam = adam->advanced(n_net);
-				ctx.encoding_ctx.adam = &enc_adam;
-			}
-			ctx.encoding_ctx.prologue = prologue;
-			m_encoding->backward(stream, ctx.encoding_ctx, n, input, dL_dnetwork_input.data(), dL_dinput, p + n_net, g ? g + n_net : nullptr, mode, plane_f > 0);
-			ctx.encoding_ctx.prologue = nullptr;
-			ctx.encoding_ctx.adam = nullptr;
-			if (ctx.encoding_ctx.reduce_job) {
-				ctx.encoding_ctx.reduce_job = nullptr;
-				if (!reduce_job.taken) mlp_reduce_slabs(stream, n_net, n_slabs, slabs.as<float>(), g, mode == GradientMode::Accumulate);
-				else if (prologue && prologue->pending && prologue->has_reduce) ctx.slabs_kept = std::move(slabs); // read by the optimizer's launch
-			}
-			if (adam_done) {
-				adam_done->clear();
-				for (const auto& r : ctx.encoding_ctx.adam_done) adam_done->emplace_back(r.first + n_net, r.second + n_net);
+			m_encoding->backward(stream, ctx.encoding_ctx, n, input, dL_dnetwork_input.data(), dL_dinput, p + n_net, g ? g + n_net : nullptr, mode, plane_f > 0, &offer);
+			if (offer.reduce_job) {
+				if (!offer.reduce_carried) mlp_reduce_slabs(stream, n_net, n_slabs, slabs.as<float>(), g, mode == GradientMode::Accumulate);
+				else if (offer.prologue && offer.prologue->pending && offer.prologue->has_reduce) ctx.slabs_kept = std::move(slabs); // read by the optimizer's launch
 			}
 			if (profile) profile->mark(stream, StepProfile::EncodingBackward, true);
 		}
@@ -2712,17 +2725,17 @@ public:
 	// gradients: n_weights values in `precision` -- the trainer's half gradients (scaled by loss_scale), or fp32 ones a caller computed itself
 	// (a PyTorch parameter's .grad; loss_scale 1 when they are unscaled already).  The weights stay what they are: fp32 master, half working copy.
 	virtual void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients, GradientPrecision precision = GradientPrecision::Fp16) = 0;
-	// A step in two parts, for gradient kernels that can apply the update to the parameters they own (AdamInFlush): begin_split_step
-	// starts the step and describes it (false: this optimizer cannot be split, nothing has happened -- call step()); finish_split_step
-	// updates every parameter outside `done`.  Together they equal step() bit for bit.
-	virtual bool begin_split_step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, AdamInFlush& out) { return false; }
-	virtual void finish_split_step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients, const ParamRanges& done) {
-		throw std::runtime_error{"Optimizer: finish_split_step without begin_split_step"};
-	}
 	// step() with the backward pass's finalize pass as the prologue of the same launch (AdamPrologue).  takes_prologue(): this optimizer
 	// can; step_with_prologue returns false when this prologue's shapes do not fit -- nothing has happened then, the caller runs the
 	// finalize pass and step() itself.
 	virtual bool takes_prologue() const { return false; }
+	// The step applied by the reduction of the weight gradients (AdamInReduce).  can_step_in_reduce(): this optimizer can;
+	// begin_step_in_reduce starts a step and describes it for the launch that will apply it to EVERY parameter: that launch then equals
+	// step() bit for bit, and nothing more is to be launched for this step.
+	virtual bool can_step_in_reduce() const { return false; }
+	virtual AdamInReduce begin_step_in_reduce(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights) {
+		throw std::runtime_error{"Optimizer: this optimizer's step cannot be applied by the slab reduction"};
+	}
 	virtual bool step_with_prologue(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, void* gradients, const AdamPrologue& prologue) { return false; }
 	virtual float learning_rate() const = 0;
 	virtual void set_learning_rate(float val) = 0;
@@ -2853,10 +2866,12 @@ public:
 		m_steps16 = false;
 	}
 
-	bool begin_split_step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, AdamInFlush& out) override {
+	bool can_step_in_reduce() const override { return true; } // (k_wgrad_reduce_adam)
+	AdamInReduce begin_step_in_reduce(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights) override {
 		++m_current_step;
 		ensure_debias_table(stream);
 		ensure_step_width(stream);
+		AdamInReduce out;
 		out.args = make_adam_args(m_h, loss_scale, m_current_step);
 		out.w_fp = weights_full_precision;
 		out.w_half = weights;
@@ -2865,22 +2880,7 @@ public:
 		out.steps = m_param_steps.data();
 		out.steps16 = m_steps16 ? 1u : 0u;
 		out.debias_table = m_debias.as<float>();
-		return true;
-	}
-	void finish_split_step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients, const ParamRanges& done) override {
-		size_t begin = 0;
-		auto update = [&](size_t b, size_t e) { // parameters [b, e) the usual way; the matrix weights are the first m_n_matrix of the vector
-			if (e <= b) return;
-			const size_t n_matrix = m_n_matrix > b ? std::min(m_n_matrix - b, e - b) : 0;
-			adam_step(stream, m_h, e - b, n_matrix, loss_scale, m_current_step, weights_full_precision + b, (char*)weights + 2 * b, (const char*)gradients + 2 * b,
-			          m_first_moments.as<float>() + b, m_second_moments.as<float>() + b, (char*)m_param_steps.data() + b * step_bytes(), m_steps16, m_debias.as<float>());
-		};
-		for (const auto& r : done) {
-			CHECK_THROW(r.first >= begin && r.second <= m_n_weights);
-			update(begin, r.first);
-			begin = r.second;
-		}
-		update(begin, m_n_weights);
+		return out;
 	}
 
 	// debias factors for steps [0, m_debias_filled), computed ahead in blocks of 4096 steps; refilled when the betas change
@@ -3635,12 +3635,21 @@ public:
 
 	size_t params_updated_in_flush() const { return m_params_updated_in_flush; }
 	size_t m_prologue_steps = 0;
-	// TCNN_AMD_ADAM_IN_FLUSH=1: the optimizer's update is applied by the gradient kernels where they can carry it.  Off by default:
-	// bit-identical and measured equal in time on C3a (0.229 / 0.230 vs 0.230 / 0.225 ms per step; DESIGN.md "Adam in the scatter").
-	static bool adam_in_flush_enabled() { return switches().adam_in_flush; }
-	// TCNN_AMD_ADAM_IN_REDUCE=0: models without encoding parameters (BASELINE config 2) run the optimizer as a launch of its own again
-	// instead of behind the weight gradients' slab reduction (k_wgrad_reduce_adam; bit-identical, one ~4 us launch less per step)
-	static bool adam_in_reduce_enabled() { return switches().adam_in_reduce; }
+
+	// Where the optimizer's update of a fused step runs (OptimizerPlace), decided once, before the step, and binding except that an offered
+	// prologue may come back not taken (the tuner's timed step, binned levels, a scalar max_level, a Composite encoding, shapes the
+	// optimizer's launch refuses): then the finalize pass and the optimizer are the two launches they were.
+	//   InReduce (TCNN_AMD_ADAM_IN_REDUCE=0 turns it off): models without encoding parameters (BASELINE config 2) -- the update runs behind
+	//     the weight gradients' slab reduction (k_wgrad_reduce_adam; bit-identical, one ~4 us launch less per step);
+	//   Prologue (TCNN_AMD_ADAM_PROLOGUE=0 turns it off): the scatter's finalize pass and the MLP's slab reduction as the prologue of the
+	//     optimizer's launch (k_adam_prologue; one launch and one kernel boundary less per step).
+	OptimizerPlace optimizer_place(bool run_optimizer, GradientMode mode, bool want_dL_dinput) const {
+		if (!run_optimizer) return OptimizerPlace::None;
+		const Switches sw = switches();
+		if (sw.adam_in_reduce && m_optimizer->can_step_in_reduce() && m_model->reduction_carries_update(want_dL_dinput, mode)) return OptimizerPlace::InReduce;
+		if (sw.adam_prologue && mode != GradientMode::Ignore && m_optimizer->takes_prologue()) return OptimizerPlace::Prologue;
+		return OptimizerPlace::OwnLaunch;
+	}
 
 	// the finalize pass and the slab reduction an AdamPrologue holds, as the launches they were
 	void run_prologue_alone(hipStream_t stream, const AdamPrologue& p) {
@@ -3693,38 +3702,40 @@ public:
 			}
 			m_params_updated_in_flush = 0;
 			m_profile.begin_step();
-			// TCNN_AMD_ADAM_IN_FLUSH=1: the optimizer's update rides on the gradient kernels where they can carry it (k_grid_scatter:
-			// the owner of a chunk updates its parameters as it flushes); what they did not take is done afterwards.
-			AdamInFlush adam;
-			ParamRanges adam_done;
-			const bool split = run_optimizer && mode == GradientMode::Overwrite && (adam_in_flush_enabled() || (adam_in_reduce_enabled() && m_model->optimizer_rides_on_reduce())) &&
-			                   m_optimizer->begin_split_step(stream, loss_scale, m_params_fp.as<float>(), m_params.data(), adam);
-			if (m_params_exposed) m_model->invalidate_live_image(); // somebody holds a pointer to the parameters: no image outlives a step
-			// the optimizer's launch offers to finish the backward pass's gradients itself (AdamPrologue: the scatter's finalize pass and the
-			// MLP's slab reduction as the prologue of k_adam's launch -- one launch and one kernel boundary less per step)
+			const OptimizerPlace place = optimizer_place(run_optimizer, mode, dL_dinput != nullptr);
+			AdamInReduce in_reduce;
 			AdamPrologue prologue;
-			prologue.offered = run_optimizer && !split && mode != GradientMode::Ignore && switches().adam_prologue && m_optimizer->takes_prologue();
-			ctx->model_ctx = m_model->fused_step(stream, n, input, target, data_pdf, external_dL_dy, m_loss, loss_scale, ctx->output.data(),
-			                                     ctx->compact ? ctx->compact_dL_doutput.data() : ctx->dL_doutput.data(),
-			                                     ctx->compact ? ctx->compact_L.as<float>() : ctx->L.as<float>(), ctx->compact, dL_dinput, m_params.data(), m_grads.data(), mode,
-			                                     &m_profile, split ? &adam : nullptr, split ? &adam_done : nullptr, prologue.offered ? &prologue : nullptr);
-			if (run_optimizer) {
+			OptimizerOffer offer;
+			if (place == OptimizerPlace::InReduce) {
+				in_reduce = m_optimizer->begin_step_in_reduce(stream, loss_scale, m_params_fp.as<float>(), m_params.data());
+				offer.in_reduce = &in_reduce;
+			} else if (place == OptimizerPlace::Prologue) offer.prologue = &prologue;
+			FusedStepData step;
+			step.target = target, step.data_pdf = data_pdf, step.external_dL_dy = external_dL_dy;
+			step.loss = m_loss;
+			step.loss_scale = loss_scale;
+			step.out = ctx->output.data();
+			step.dL_dout = ctx->compact ? ctx->compact_dL_doutput.data() : ctx->dL_doutput.data();
+			step.L = ctx->compact ? ctx->compact_L.as<float>() : ctx->L.as<float>();
+			step.compact_context = ctx->compact;
+			step.dL_dinput = dL_dinput;
+			step.params = m_params.data(), step.gradients = m_grads.data();
+			step.mode = mode;
+			step.profile = &m_profile;
+			ctx->model_ctx = m_model->fused_step(stream, n, input, step, offer);
+			// The network's live fragment image outlives the step only if its weights are what they were, or the launch that updated them
+			// kept the image current (InReduce, Network::live_image) -- and never once somebody holds a pointer to the parameters.
+			if (m_params_exposed || (place != OptimizerPlace::None && !m_model->live_image_kept())) m_model->invalidate_live_image();
+			if (place != OptimizerPlace::None) {
 				m_profile.mark(stream, StepProfile::Optimizer, false);
-				m_params_updated_in_flush = 0;
-				for (const auto& r : adam_done) m_params_updated_in_flush += r.second - r.first;
-				if (split) {
-					if (!m_model->live_image_kept()) m_model->invalidate_live_image(); // the update below (or the gradient kernels') changes network weights
-					m_optimizer->finish_split_step(stream, loss_scale, m_params_fp.as<float>(), m_params.data(), m_grads.data(), adam_done);
-				} else if (prologue.pending) {
-					m_model->invalidate_live_image();
-					if (m_optimizer->step_with_prologue(stream, loss_scale, m_params_fp.as<float>(), m_params.data(), m_grads.data(), prologue)) ++m_prologue_steps;
-					else {
-						run_prologue_alone(stream, prologue); // shapes the fused launch does not take: the two launches of before
-						m_optimizer->step(stream, loss_scale, m_params_fp.as<float>(), m_params.data(), m_grads.data());
-					}
-				} else optimizer_step(stream, loss_scale);
+				if (place == OptimizerPlace::InReduce) m_params_updated_in_flush = m_model->n_params(); // the reduction has applied the update: nothing more to launch
+				else if (prologue.pending && m_optimizer->step_with_prologue(stream, loss_scale, m_params_fp.as<float>(), m_params.data(), m_grads.data(), prologue)) ++m_prologue_steps;
+				else {
+					if (prologue.pending) run_prologue_alone(stream, prologue); // shapes the fused launch does not take: the two launches of before
+					m_optimizer->step(stream, loss_scale, m_params_fp.as<float>(), m_params.data(), m_grads.data());
+				}
 				m_profile.mark(stream, StepProfile::Optimizer, true);
-			} else if (prologue.pending) run_prologue_alone(stream, prologue); // (never: nothing is offered without an optimizer step)
+			}
 			m_profile.end_step();
 			m_last_step_kernel = m_model->last_train_kernel();
 			return ctx;

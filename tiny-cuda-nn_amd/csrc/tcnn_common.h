@@ -55,7 +55,6 @@ struct Switches {
 	bool side_jobs = true;        // TCNN_AMD_SIDE_JOBS=0: k_mlp_prep and the slab reduction as launches of their own
 	bool live_image = true;       // TCNN_AMD_LIVE_IMAGE=0: k_mlp_prep every step
 	bool adam_steps32 = false;    // TCNN_AMD_ADAM_STEPS32=1: uint32 update counts from the start
-	bool adam_in_flush = false;   // laboratory build only (TCNN_AMD_ADAM_IN_FLUSH=1): Adam applied by k_grid_scatter's chunk owners -- measured slower, not in the product
 	bool adam_in_reduce = true;   // TCNN_AMD_ADAM_IN_REDUCE=0: k_adam as a launch of its own for models without encoding parameters
 	bool adam_prologue = true;    // TCNN_AMD_ADAM_PROLOGUE=0: the scatter's finalize pass (+ slab reduction) as a launch of its own in front of k_adam
 	bool adam_prologue_refused = false; // TCNN_AMD_ADAM_PROLOGUE=refuse (tests): the optimizer is offered the prologue and turns it down, as it does for shapes its launch does not take
@@ -181,9 +180,7 @@ struct GridScatterTask {
 	uint32_t pad;
 };
 struct GridScatterRange { size_t grad_begin; uint32_t n_elems; uint32_t scratch_begin; uint32_t pad; }; // shared chunks, for the finalize pass
-struct AdamInFlush;                                          // below, with the optimizer kernels
-struct MlpReduceJob;                                         // mlp_side_jobs.h
-typedef std::vector<std::pair<size_t, size_t>> ParamRanges; // sorted, disjoint [begin, end) of the parameter vector
+struct MlpReduceJob;                                // mlp_side_jobs.h
 constexpr uint32_t GRID_FILTER_MAX_CHUNKS = 64;     // chunks per level the sample filter can describe (bit planes per level)
 uint32_t grid_scatter_max_chunks();                 // = GRID_FILTER_MAX_CHUNKS
 void grid_scatter_setup_levels(GridMeta& meta);     // fills GridLevel::scatter_* (how each level's table is cut into chunks)
@@ -199,29 +196,26 @@ void grid_mask_to_bits(hipStream_t stream, const GridMeta& meta, const GridMeta*
 // dL_dy element (sample i, level l, feature f) at dL_dy[i * dy_stride_sample + l * dy_stride_level + f].
 // chunk_bits: optional filter derived from grid_forward's masks for the SAME batch (n samples); nullptr -> every sample is examined in full.
 // scratch: uint64[scratch_elems], zero on entry, zero again on return.  Writes EVERY gradient element (no memset needed);
-// accumulate = GradientMode::Accumulate.
-void grid_backward_lds(hipStream_t stream, const GridMeta& meta, const GridMeta* dev_meta, const GridScatterTask* dev_tasks, uint32_t n_tasks,
+// accumulate = GradientMode::Accumulate.  Returns whether reduce_job was carried (by the finalize launch, when there is one).
+bool grid_backward_lds(hipStream_t stream, const GridMeta& meta, const GridMeta* dev_meta, const GridScatterTask* dev_tasks, uint32_t n_tasks,
                        const GridScatterRange* dev_ranges, uint32_t n_ranges, uint64_t* scratch, uint32_t n, MatView x,
                        const void* dL_dy, uint32_t dy_stride_sample, uint32_t dy_stride_level, void* grad, const uint64_t* chunk_bits, bool accumulate, bool dy_records = false,
                        uint64_t* task_times = nullptr, // task_times (optional): device uint64[n_tasks][8], per-task timestamps for the plan tuner
-                       const AdamInFlush* adam = nullptr, // adam (optional, record form only): arrays indexed like grad; see grid_scatter_adam_ranges
-                       const MlpReduceJob* reduce_job = nullptr); // (optional) carried by the finalize launch when there is one; ->taken says so
+                       const MlpReduceJob* reduce_job = nullptr);
 // ---- the same scatter fed by hit lists (k_grid_scatter_lists.hip): two workgroups per CU with 64 KiB of accumulators each -- both features
 // of an entry in ONE 64-bit LDS add as 2 x int32 while a per-task bound proves that no half can overflow, 64-bit accumulators in two
 // passes otherwise -- tasks of its own plan (GridScatterTask::pad = split s | n_splits << 16: which share of a chunk's list), same scratch, same results.
 uint32_t grid_scatter_lists_lds_bytes();
 // the kernel's tasks in launch order (one workgroup each; block b runs on XCD b % 8: k_grid_scatter_lists.hip)
 void grid_scatter_lists_plan(const GridMeta& meta, uint32_t n, std::vector<GridScatterTask>& tasks, std::vector<GridScatterRange>& shared_ranges, size_t& scratch_elems);
-void grid_backward_lists(hipStream_t stream, const GridMeta& meta, const GridMeta* dev_meta, const GridScatterTask* dev_tasks, uint32_t n_tasks,
+bool grid_backward_lists(hipStream_t stream, const GridMeta& meta, const GridMeta* dev_meta, const GridScatterTask* dev_tasks, uint32_t n_tasks,
                          const GridScatterRange* dev_ranges, uint32_t n_ranges, uint64_t* scratch, uint32_t n, MatView x,
                          const void* dL_dy, uint32_t dy_stride_sample, uint32_t dy_stride_level, void* grad, const GridHitLists& lists, void* gvals, bool accumulate,
                          const MlpReduceJob* reduce_job, uint32_t* fallback_count = nullptr);
 // gvals: workspace of grid_list_gradients_bytes(): dL/dy in list order, half [n_levels][n_items][item_capacity][F], written by the launch's first kernel
 size_t grid_list_gradients_bytes(const GridMeta& meta, const GridHitLists& lists);
-// the finalize pass of the shared chunks (+ the MLP's slab reduction), shared by both scatter kernels
-void grid_scatter_finalize(hipStream_t stream, const GridScatterRange* dev_ranges, uint32_t n_ranges, uint64_t* scratch, void* grad, bool accumulate, const MlpReduceJob* reduce_job);
-// the parameter ranges (relative to grad) a launch of `tasks` with `adam` updates itself; empty = this plan cannot carry the optimizer step
-ParamRanges grid_scatter_adam_ranges(const GridMeta& meta, const std::vector<GridScatterTask>& tasks, bool dy_records);
+// the finalize pass of the shared chunks (+ the MLP's slab reduction), shared by both scatter kernels; false: no ranges, nothing was launched
+bool grid_scatter_finalize(hipStream_t stream, const GridScatterRange* dev_ranges, uint32_t n_ranges, uint64_t* scratch, void* grad, bool accumulate, const MlpReduceJob* reduce_job);
 // dy_records: dL_dy is float4 [grid_scatter_record_planes()][n] scatter records {coordinates, gradient halves} (mlp_device.h
 // store_dx_record; D = 2 with F = 2 packs two levels into one record); x is then not read
 bool grid_scatter_records_supported(const GridMeta& meta);
@@ -400,8 +394,8 @@ bool mlp_train_compact_context(const MlpDesc& d, uint32_t n);                   
 void mlp_expand_context(hipStream_t stream, uint32_t n, uint32_t dims, const void* compact_dL_dout, const float* compact_L, void* dL_dout, float* L);
 // grad[i] (=|+=) sum_k slabs[k][i], fixed order, rounded to half once
 // adam (optional, not with accumulate): the optimizer's update of these (matrix) weights is applied behind the reduction, bit-identical to adam_step run afterwards
-struct AdamInFlush;
-void mlp_reduce_slabs(hipStream_t stream, uint32_t n_params, uint32_t n_slabs, const float* slabs, void* grad_half, bool accumulate, const AdamInFlush* adam = nullptr);
+struct AdamInReduce;
+void mlp_reduce_slabs(hipStream_t stream, uint32_t n_params, uint32_t n_slabs, const float* slabs, void* grad_half, bool accumulate, const AdamInReduce* adam = nullptr);
 // fully_fused_mlp.cu:757-762: result = dL_dout * act'(out), elementwise over n_elems halfs
 void mlp_activation_backward_output(hipStream_t stream, uint32_t n_elems, uint32_t activation, const void* dL_dout, const void* out, void* result);
 // dW[rows x cols] = sum_i dO[i][rows]^T In[i][cols]; result written as half into grad (overwrite or accumulate). workspace: float[wgrad_workspace_floats()]
@@ -462,11 +456,10 @@ struct AdamArgs {
 	uint32_t common_step; // the optimizer's own step count: the per-parameter count of every parameter that was updated in every step
 };
 AdamArgs make_adam_args(const AdamHyper& h, float loss_scale, uint32_t current_step);
-// Adam applied by a gradient kernel: the owner of a chunk of the gradient has its final value in LDS when it flushes and updates
-// those parameters on the spot (k_grid_scatter.hip) -- the 34 B/param of optimizer state stream under the latency-bound phases of
-// the other workgroups instead of in a kernel of their own.  Arrays are indexed like the gradient array the kernel writes.
+// The optimizer's update carried by the slab reduction (k_wgrad_reduce_adam, k_mlp.hip): a matrix weight's gradient is final the moment
+// its slabs are summed, so adam.h:48-119 runs on it at once.  Arrays are indexed like the gradient array the kernel writes.
 constexpr uint32_t IMAGE_INV_WIDTH = 4; // a weight sits in at most 4 image elements: forward and transposed fragments of the 16x16x32 and of the 32x32x16 sections
-struct AdamInFlush {
+struct AdamInReduce {
 	AdamArgs args;
 	float* w_fp = nullptr;
 	void* w_half = nullptr;
@@ -475,15 +468,10 @@ struct AdamInFlush {
 	void* steps = nullptr; // uint32, or uint16 if steps16
 	uint32_t steps16 = 0;
 	const float* debias_table = nullptr;
-	// k_wgrad_reduce_adam only (Network::live_image): the network's fragment images and, per parameter, the IMAGE_INV_WIDTH image elements that
-	// hold it (0xffffffff: none) -- the kernel writes an updated weight there too, so that the next step needs no k_mlp_prep launch
+	// Network::live_image: the network's fragment images and, per parameter, the IMAGE_INV_WIDTH image elements that hold it
+	// (0xffffffff: none) -- the kernel writes an updated weight there too, so that the next step needs no k_mlp_prep launch
 	void* image = nullptr;
 	const uint32_t* image_inv = nullptr;
-	AdamInFlush advanced(size_t n) const { // the same arrays seen from parameter n on
-		AdamInFlush r = *this;
-		r.w_fp += n; r.w_half = (char*)w_half + 2 * n; r.m1 += n; r.m2 += n; r.steps = (char*)steps + (steps16 ? 2 : 4) * n;
-		return r;
-	}
 };
 // What the backward pass of a fused step leaves for the optimizer's launch to finish (k_adam_prologue, k_misc.hip): the scatter's finalize
 // pass -- the shared chunks' exact sums in `scratch` are rounded into the gradient, the scratch left zero -- and the fixed-order sum of the
@@ -491,7 +479,6 @@ struct AdamInFlush {
 // finishes a gradient updates its parameters at once, every other workgroup does what k_adam does, and the step has one ~5 us launch
 // (k_grid_scatter_finalize) and one kernel boundary less.  Same rounding, same adam_one: gradients, weights, moments, counts bit-identical.
 struct AdamPrologue {
-	bool offered = false;                      // the trainer will run an optimizer that can take it (set by the trainer)
 	bool pending = false;                      // the backward pass left its finalize pass here instead of launching it
 	const GridScatterRange* dev_ranges = nullptr;
 	std::vector<GridScatterRange> ranges;      // host copy; grad_begin relative to grad_base

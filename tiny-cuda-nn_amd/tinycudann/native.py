@@ -97,7 +97,7 @@ class Trainer:
         _C.check(_C.lib.tcnn_trainer_profile_next_step(self._h))
 
     def params_updated_in_flush(self):
-        """parameters whose optimizer update the last training_step's gradient kernels applied themselves (0: the usual k_adam)"""
+        """parameters whose optimizer update the last training_step applied inside the reduction of the weight gradients: all of them, or 0 (tcnn_amd.h)"""
         return int(_C.lib.tcnn_trainer_params_updated_in_flush(self._h))
 
     def image_preps(self):
