@@ -213,6 +213,10 @@ size_t tcnn_trainer_optimizer_prologue_steps(tcnn_trainer_t t);
  * which kernel produced the gradients they compare with the oracle (replaces kernel_grid_backward, grid.h:215-320). */
 size_t tcnn_trainer_list_scatters(tcnn_trainer_t t);
 size_t tcnn_module_list_scatters(tcnn_module_t m); /* the same count for a module's grid encoding(s) (callers with their own network) */
+/* Introspection (no counterpart in the reference): training steps of this trainer whose fused MLP kernel also stored dL/d(encoding) in
+ * the order of the grid encoding's hit lists, as its tail, instead of a k_grid_list_gradients launch in front of the list-fed gradient
+ * kernel (same results; TCNN_AMD_LISTGRAD_IN_MLP=0 keeps the separate launch). */
+size_t tcnn_trainer_list_gradient_tails(tcnn_trainer_t t);
 /* Introspection (no counterpart in the reference): a short, stable name of the MLP training kernel the last training_step() of this
  * trainer launched -- "r32", "r32a", "r32w", "r32ob", "regs_fast", "regs", "train<W,NB,NW,MAXT>/relu", "train<W,NB,NW,MAXT>/act",
  * "train_pw28/...", "train_pw32/...", "train_regw/...", "train_ob/..." (/act: the hidden activation is chosen at run time) or "unfused"

@@ -101,6 +101,7 @@ void switches_reload() {
 	w.mlp_regs = !env_is("TCNN_AMD_MLP_REGS", '0');
 	w.mlp_fast = !env_is("TCNN_AMD_MLP_FAST", '0');
 	if (const char* e = getenv("TCNN_AMD_MLP_PRIO")) w.mlp_prio = (uint32_t)atoi(e);
+	w.listgrad_in_mlp = !env_is("TCNN_AMD_LISTGRAD_IN_MLP", '0');
 	w.mlp_layerwise = env_is("TCNN_AMD_MLP_LAYERWISE", '1');
 	std::lock_guard<std::mutex> lock{g_switches_mutex};
 	g_switches = w;
@@ -401,6 +402,7 @@ size_t tcnn_trainer_scatter_wide_fallbacks(tcnn_trainer_t t) {
 	try { return (size_t)t->trainer->scatter_wide_fallbacks(); } catch (const std::exception& e) { g_last_error = e.what(); return (size_t)-1; }
 }
 size_t tcnn_trainer_list_scatters(tcnn_trainer_t t) { return (size_t)t->trainer->list_scatters(); }
+size_t tcnn_trainer_list_gradient_tails(tcnn_trainer_t t) { return (size_t)t->trainer->list_gradient_tails(); }
 const char* tcnn_trainer_last_step_kernel(tcnn_trainer_t t) { return t->trainer->last_step_kernel(); }
 int tcnn_trainer_set_max_level(tcnn_trainer_t t, float max_level) {
 	return guarded([&] {

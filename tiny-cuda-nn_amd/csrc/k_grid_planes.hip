@@ -98,7 +98,9 @@ __global__ void __launch_bounds__(LISTS ? FP_LIST_THREADS : FP_THREADS) k_grid_f
 	for (uint32_t it = slot; it < n_items; it += blocks_per_xcd) {
 		const uint32_t w = items[it];
 		const uint32_t level = w >> 24;
-		const uint32_t base = (w & 0xffffffu) * FP_ITEM_SAMPLES + wave * FP_WAVE_SAMPLES; // first sample of this wave
+		// first sample of this wave: a wave's FP_WAVE_SAMPLES positions lie inside one window of the item (GridItemMap), a dense run of samples
+		uint32_t base = (w & 0xffffffu) * FP_ITEM_SAMPLES + wave * FP_WAVE_SAMPLES;
+		if constexpr (LISTS) base = grid_item_sample(lists.map, w & 0xffffffu, wave * FP_WAVE_SAMPLES);
 		if constexpr (!LISTS) { if (base >= n) continue; } // (LISTS: the waves of a workgroup meet at barriers; a wave past the end recomputes the last sample and emits nothing)
 		const GridLevel lv = meta->levels[level];
 		const half_t* __restrict__ lgrid = grid + (size_t)lv.offset * F;
@@ -490,6 +492,11 @@ void grid_forward_planes(hipStream_t stream, const GridMeta& meta, const GridMet
 	CHECK_THROW(!hit_lists || (hit_lists->elems && hit_lists->heads && hit_lists->stragglers && hit_lists->counts && n <= grid_hit_max_samples(meta) &&
 	                           hit_lists->item_samples == grid_hit_item_samples(meta) && hit_lists->n_items == div_round_up(n, hit_lists->item_samples) &&
 	                           hit_lists->sidx && hit_lists->item_capacity >= (hit_lists->item_samples << (meta.n_pos_dims - 1)) && hit_lists->item_capacity % 8 == 0));
+	if (hit_lists) { // the item map: whole items only unless the items are runs of consecutive samples; a wave's positions inside one window
+		const GridItemMap& m = hit_lists->map;
+		CHECK_THROW(m.window > 0 && m.window == (1u << m.window_shift) && m.window * m.n_windows == hit_lists->item_samples && m.window % (64 * grid_planes_spt(meta)) == 0);
+		CHECK_THROW(m.n_windows == 1 || (n % hit_lists->item_samples == 0 && m.stride == hit_lists->n_items * m.window));
+	}
 	const uint32_t F = meta.n_features_per_level;
 #define TCNN_PLANES_F(D, SPT) \
 	switch (F) { \

@@ -389,8 +389,8 @@ __device__ inline float sl_pass(const ScatterCtx<D, F>& c, lds_u64* acc, const u
 }
 
 // ---------------------------------------------------------------------------------------------------------------- dL/dy into list order
-// One workgroup per (item, level) of a listed level: the item's slice of the level's gradient plane (item_samples x F halves: 2 KB) goes
-// into LDS with dense loads, then every element of the item -- all chunks' runs, front to back -- takes its sample's F halves from there
+// One workgroup per (item, level) of a listed level: the item's slice of the level's gradient plane (item_samples x F halves: 2 KB; the
+// item's samples by its map, GridItemMap) goes into LDS with dense loads, then every element of the item -- all chunks' runs, front to back -- takes its sample's F halves from there
 // and stores them at the element's own position in `gvals`.  Dense loads, dense stores, 2 + 2 F bytes in and 2 F bytes out per element; what
 // the owners' gathers cost (a 128-byte line from the L2 per element) is paid here once per 32 samples instead.
 constexpr uint32_t LG_THREADS = 256;
@@ -438,10 +438,10 @@ __global__ void __launch_bounds__(LG_THREADS) k_grid_list_gradients(const ListGr
 #pragma unroll
 	for (uint32_t it = 0; it < LG_ITEMS; ++it) {
 		vecF* g = (vecF*)smem + it * hl.item_samples;
-		const uint32_t first = (blockIdx.x * LG_ITEMS + it) * hl.item_samples;
+		const uint32_t item = blockIdx.x * LG_ITEMS + it;
 		if (total[it] == 0) continue; // (workgroup-uniform)
 		for (uint32_t s = threadIdx.x; s < hl.item_samples; s += LG_THREADS) {
-			const uint32_t i = min(first + s, a.n - 1);
+			const uint32_t i = min(grid_item_sample(hl.map, item, s), a.n - 1);
 			g[s] = *(const vecF*)&dy[(size_t)i * a.dy_stride_sample];
 		}
 	}
@@ -828,7 +828,7 @@ void grid_scatter_lists_plan(const GridMeta& meta, uint32_t n, std::vector<GridS
 bool grid_backward_lists(hipStream_t stream, const GridMeta& meta, const GridMeta* dev_meta, const GridScatterTask* dev_tasks, uint32_t n_tasks,
                          const GridScatterRange* dev_ranges, uint32_t n_ranges, uint64_t* scratch, uint32_t n, MatView x,
                          const void* dL_dy, uint32_t dy_stride_sample, uint32_t dy_stride_level, void* grad, const GridHitLists& lists, void* gvals, bool accumulate,
-                         const MlpReduceJob* reduce_job, uint32_t* fallback_count) {
+                         const MlpReduceJob* reduce_job, uint32_t* fallback_count, bool gvals_filled) {
 	if (n_tasks == 0) return false;
 	CHECK_THROW(lists.elems != nullptr && lists.sidx != nullptr && lists.heads != nullptr && lists.stragglers != nullptr && lists.counts != nullptr && lists.n_items > 0 && gvals != nullptr);
 	CHECK_THROW(lists.item_capacity % 8 == 0 && lists.item_samples <= 65536 && lists.item_samples * meta.n_features_per_level * 2 * 2 <= 64 * 1024); // (k_grid_list_gradients: the slices of two items in LDS)
@@ -858,7 +858,7 @@ bool grid_backward_lists(hipStream_t stream, const GridMeta& meta, const GridMet
 #ifdef TCNN_AMD_DEV
 	if (const char* e = getenv("TCNN_AMD_SCATTER_DEV")) a.dev_flags = (uint32_t)atoi(e);
 #endif
-	{ // dL/dy into list order, then the owners
+	if (!gvals_filled) { // dL/dy into list order (unless the MLP kernel's tail has done that: GridListTail), then the owners
 		ListGradArgs lg{dev_meta, lists, (const half_t*)dL_dy, dy_stride_sample, dy_stride_level, n, (half_t*)gvals};
 		switch (meta.n_features_per_level) {
 			case 2: launch_list_gradients<2>(stream, lg, meta.n_levels); break;

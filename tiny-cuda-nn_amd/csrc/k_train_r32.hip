@@ -436,6 +436,60 @@ __global__ void __launch_bounds__(R32_NW * 64, 2) k_mlp_train_r32(const R32Args 
 	if (a.dbg && lane == 0) a.dbg[gridDim.x * 4 + blockIdx.x * R32_NW + wave] = __builtin_readcyclecounter();
 	if (a.dbg && tid == 0) a.dbg[blockIdx.x * 4 + 2] = __builtin_readcyclecounter();
 
+	// ---- dL/dy of the grid encoding into list order (GridListTail; the work of k_grid_list_gradients, k_grid_scatter_lists.hip).  This
+	// workgroup's samples are exactly item blockIdx.x of every level (GridItemMap): it has written their gradient planes itself, above.
+	// Everything is requested at once -- per listed level the item's element count, four 16-bit positions per thread (capacity <= 2048) and
+	// 8 bytes of the item's own plane windows (out of the L2: they were stored microseconds ago) --, the windows go into LDS (4 bytes per
+	// position and level: the images and fragments are dead; the slab reduction below waits at its barrier and then runs while these stores drain), and every element's gradient leaves for the element's position in `gvals`, a
+	// 16-byte store per thread and level.  Raw buffer loads without branches: what is not wanted is asked for beyond the descriptor's
+	// range (no access, zeros).  The barrier in front (release / acquire at workgroup scope) orders the waves' plane stores before the loads.
+	if constexpr (!REC) {
+		if (a.tail.gvals) { // (workgroup-uniform)
+			constexpr int TL = 16;            // level planes of this network's input
+			constexpr uint32_t OOB = 0xffffffe0u;
+			const GridListTail& t = a.tail;
+			const uint32_t item = blockIdx.x, n_pos = t.map.window * t.map.n_windows;
+			const uint32_t cap = t.item_capacity;
+			const auto rs_si = __builtin_amdgcn_make_buffer_rsrc((void*)t.sidx, 0, (int)(t.n_levels * t.n_items * cap * 2u), 0x00020000);
+			const auto rs_hd = __builtin_amdgcn_make_buffer_rsrc((void*)t.heads, 0, (int)(t.n_levels * GRID_HIT_HEADS * t.n_items * 4u), 0x00020000);
+			const auto rs_gv = __builtin_amdgcn_make_buffer_rsrc(t.gvals, 0, (int)(t.n_levels * t.n_items * cap * 4u), 0x00020000);
+			typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+			const uint32_t p0 = 2 * tid;     // this thread's two positions of the item: consecutive samples of one window
+			const uint32_t my_sample = grid_item_sample(t.map, item, p0);
+			const bool have_pos = p0 < n_pos, have_el = 4 * tid < cap;
+			u32x2 sv[TL], pv[TL];
+			uint32_t tot[TL];
+#pragma unroll
+			for (int l = 0; l < TL; ++l) { // what the forward kernel wrote: asked for while the workgroup's other waves finish their trips
+				const bool listed = (t.level_mask >> l) & 1u; // (workgroup-uniform)
+				const uint32_t region = ((uint32_t)l * t.n_items + item) * cap;
+				tot[l] = __builtin_amdgcn_raw_buffer_load_b32(rs_hd, listed ? (((uint32_t)l * GRID_HIT_HEADS + GRID_FILTER_MAX_CHUNKS) * t.n_items + item) * 4u : OOB, 0, 0);
+				sv[l] = __builtin_amdgcn_raw_buffer_load_b64(rs_si, listed && have_el ? (region + 4 * tid) * 2u : OOB, 0, 0);
+			}
+			__syncthreads();
+#pragma unroll
+			for (int l = 0; l < TL; ++l) {
+				const bool listed = (t.level_mask >> l) & 1u;
+				pv[l] = __builtin_amdgcn_raw_buffer_load_b64(rs_rec, listed && have_pos ? (uint32_t)l * n4 + my_sample * 4u : OOB, 0, 0);
+			}
+			uint32_t* win = (uint32_t*)smem; // [TL][n_pos]
+#pragma unroll
+			for (int l = 0; l < TL; ++l) {
+				if (have_pos) *(u32x2*)(win + (uint32_t)l * n_pos + p0) = pv[l];
+			}
+			__syncthreads();
+#pragma unroll
+			for (int l = 0; l < TL; ++l) {
+				if (4 * tid < tot[l]) { // (an unlisted level: 0.  A quad's positions beyond the item's last element hold stale numbers: clamped, stored where nobody reads)
+					const uint32_t* wl = win + (uint32_t)l * n_pos;
+					const uint32_t last = n_pos - 1;
+					const uint32_t s0 = sv[l].x, s1 = sv[l].y;
+					const u32x4 v = u32x4{wl[min(s0 & 0xffffu, last)], wl[min(s0 >> 16, last)], wl[min(s1 & 0xffffu, last)], wl[min(s1 >> 16, last)]};
+					__builtin_amdgcn_raw_buffer_store_b128(v, rs_gv, (((uint32_t)l * t.n_items + item) * cap + 4 * tid) * 4u, 0, 0);
+				}
+			}
+		}
+	}
 	// ---- weight gradients: the 8 waves' accumulators -> the workgroup's slab, through LDS (the images and fragments are dead: barrier
 	// first), in two passes of 14 register quads: every wave dumps its quads, then wave w adds up the eight copies of the quads
 	// q = w (mod 8) in a fixed tree (bitwise reproducible) and stores them.  All eight waves write and read in every phase.
@@ -518,6 +572,17 @@ bool r32_plan(const MlpDesc& d, const MlpTrainRequest& r, const Switches& sw, Ml
 	return true;
 }
 
+bool mlp_train_item_map(const MlpTrainPlan& p, GridItemMap& map) {
+	// k_mlp_train_r32: wave w of workgroup b takes the 32-sample blocks b R32_NW + w + k grid R32_NW, k = 0, 1, ..: the workgroup's trip k
+	// covers the 256 samples from (b + k grid) 256 on.  (k_mlp_train_r32a deals its blocks out in its own way and has no tail.)
+	constexpr uint32_t WINDOW = R32_NW * 32;
+	if (!p.ok || p.kernel != MlpTrainKernel::R32 || p.request.dx_record_dims != 0 || p.request.dx_plane_features != 2 || p.grid == 0) return false;
+	const uint32_t n = p.request.n;
+	if (n % (p.grid * WINDOW) != 0) return false; // every wave the same number of trips
+	map = grid_item_map(WINDOW, p.grid * WINDOW, n / (p.grid * WINDOW));
+	return true;
+}
+
 void r32_launch(hipStream_t stream, const MlpDesc& d, const MlpTrainPlan& p, const MlpTrainArgs& in) {
 	const uint32_t n = p.request.n, grid = p.grid;
 	const bool r32a = p.kernel == MlpTrainKernel::R32a;
@@ -537,6 +602,14 @@ void r32_launch(hipStream_t stream, const MlpDesc& d, const MlpTrainPlan& p, con
 	a.n_params = in.n_params;
 	for (int l = 0; l < 3; ++l) a.w_off[l] = d.layers[l].w_off;
 	a.loss_scale = in.loss_scale;
+	if (in.list_tail) { // the tail's premises, and its 32-bit byte offsets
+		const GridListTail& t = *in.list_tail;
+		GridItemMap map;
+		CHECK_THROW(mlp_train_item_map(p, map) && map == t.map && t.n_items == grid && t.gvals && t.sidx && t.heads);
+		CHECK_THROW(t.n_levels <= 16 && (t.level_mask >> t.n_levels) == 0 && t.item_capacity <= 4 * R32_NW * 64 && t.item_capacity % 4 == 0 && map.window * map.n_windows <= 2 * R32_NW * 64);
+		CHECK_THROW((uint64_t)t.n_levels * t.n_items * std::max<uint64_t>(t.item_capacity * 4u, GRID_HIT_HEADS * 4u) < (1ull << 31) && 16u * map.window * map.n_windows * 4u <= (uint32_t)R32_LDS_BYTES);
+		a.tail = t;
+	}
 	auto go = [&](auto kernel) { launch_with_lds(kernel, stream, grid, R32_NW * 64, R32_LDS_BYTES, a); };
 	a.prio_mode = switches().mlp_prio;
 #ifndef TCNN_AMD_DEV

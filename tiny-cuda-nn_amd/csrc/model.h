@@ -231,6 +231,9 @@ struct BackwardHandoff {
 	// the optimizer's launch offers to run the scatter's finalize pass (and the reduce job) as its prologue (AdamPrologue, tcnn_common.h):
 	// a backward pass that takes the offer fills it in, sets ->pending and launches no finalize pass of its own
 	AdamPrologue* prologue = nullptr;
+	// the MLP kernel's tail has already stored dL_dy in the order of this batch's hit lists (GridListTail, Encoding::list_gradient_tail): the
+	// workspace it filled, which the list-fed gradient kernel reads instead of launching k_grid_list_gradients
+	void* list_gradients = nullptr;
 	bool reduce_carried = false;              // reported: reduce_job went with a launch of this pass or with the prologue -- it is no longer the caller's to run
 };
 
@@ -285,10 +288,15 @@ public:
 	// > 0: forward_planes() can write the encoded batch as level planes [padded / F][n][F] (no input gradients in that form)
 	virtual uint32_t forward_plane_features(uint32_t n) { return 0; }
 	// prep_job (optional): a side job the forward kernel carries along -- the fragment images of the network behind the encoding
+	// item_map (optional): the samples the fused MLP kernel's workgroups will work on (mlp_train_item_map); a grid that writes hit lists
+	// forms its work items from them where its item size allows, so that list_gradient_tail() can hold later
 	virtual EncodingContext forward_planes(hipStream_t stream, uint32_t n, MatView x, const void* params, void* out_planes, bool prepare_param_gradients,
-	                                       const MlpPrepJob* prep_job = nullptr) {
+	                                       const MlpPrepJob* prep_job = nullptr, const GridItemMap* item_map = nullptr) {
 		throw std::runtime_error{"Encoding: level-plane output is not available"};
 	}
+	// true: ctx holds hit lists whose items are `map`'s and whose gradient pass over all levels will run on `stream` -- `tail` is filled in
+	// (all but gvals: the caller's workspace of gvals_bytes, handed back through BackwardHandoff::list_gradients)
+	virtual bool list_gradient_tail(hipStream_t stream, const EncodingContext& ctx, uint32_t n, const GridItemMap& map, GridListTail& tail, size_t& gvals_bytes) { return false; }
 	virtual Json hyperparams() const = 0;
 	bool fp32() const { return m_fp32; }
 	// max_level of the grid encodings (grid_interface.h:101-123), read at call time.  false: no grid encoding here to take it.
@@ -485,7 +493,7 @@ public:
 	}
 
 	EncodingContext forward_planes(hipStream_t stream, uint32_t n, MatView x, const void* params, void* out_planes, bool prepare_param_gradients,
-	                               const MlpPrepJob* prep_job = nullptr) override {
+	                               const MlpPrepJob* prep_job = nullptr, const GridItemMap* item_map = nullptr) override {
 		EncodingContext ctx;
 		CHECK_THROW(forward_plane_features(n) > 0);
 		const bool want_filter = prepare_param_gradients && lds_scatter_usable();
@@ -499,6 +507,10 @@ public:
 			hl.n_items = div_round_up(n, hl.item_samples);
 			hl.item_capacity = hl.item_samples << (m_meta.n_pos_dims - 1);
 			hl.straggler_capacity = n << (m_meta.n_pos_dims - 1);
+			// an item is what one workgroup of the MLP kernel produces where the two sizes agree, else item_samples consecutive samples
+			hl.map = grid_item_map(hl.item_samples, 0, 1);
+			if (item_map && item_map->n_windows > 1 && item_map->window * item_map->n_windows == hl.item_samples && n % hl.item_samples == 0 &&
+			    item_map->stride == hl.n_items * item_map->window && item_map->window % (64 * grid_planes_spt(m_meta)) == 0) hl.map = *item_map;
 			const size_t L = m_meta.n_levels;
 			const size_t elems_bytes = L * hl.n_items * hl.item_capacity * GRID_HIT_WORDS * sizeof(uint32_t), sidx_bytes = next_multiple_sz(L * hl.n_items * hl.item_capacity * sizeof(uint16_t), 256);
 			const size_t heads_bytes = next_multiple_sz(L * hl.n_items * GRID_HIT_HEADS * sizeof(uint32_t), 256);
@@ -542,6 +554,7 @@ public:
 		if (!m_max_level_gpu && l_bwd == m_meta.n_levels) return all_levels(dL_dy);
 		if (m_max_level_gpu) { // per sample: dL/dy of the skipped (sample, level) pairs zeroed -- the exact sums add nothing for a zero product
 			CHECK_THROW(!offer.dy_records); // (scatter_records_usable() is false while a per-sample array is set)
+			CHECK_THROW(!offer.list_gradients); // (list_gradient_tail() is false too: the gradients in list order would be the unmasked ones)
 			const uint32_t F = m_meta.n_features_per_level;
 			const size_t elem = dy_planes ? 2 : (m_fp32 ? 4 : 2);
 			ArenaBuf masked{stream, (size_t)n * padded_output_width() * elem};
@@ -552,6 +565,7 @@ public:
 		// scalar (grid.h:237-245): the optimizer's offer of its prologue is declined by not passing it on -- the off levels' gradients are
 		// settled below, after the kernels, and the optimizer's own launch sees every parameter
 		offer.prologue = nullptr;
+		CHECK_THROW(!offer.list_gradients); // (list_gradient_tail() is false under a cut-off)
 		GradientTail tail{*this, stream, grads, mode, l_bwd};
 		all_levels(dL_dy);
 		tail.settle();
@@ -592,10 +606,14 @@ public:
 					++m_list_scatters;
 					// the finalize pass (and the reduce job with it) may be left to the optimizer's launch: no ranges, no job -> no launch here
 					const bool defer = take_prologue(offer, lp.dev_ranges.as<GridScatterRange>(), lp.host_ranges, lp.scratch.as<uint64_t>(), grads, mode);
-					ArenaBuf gvals{stream, grid_list_gradients_bytes(m_meta, ctx.hit_lists)}; // dL/dy in list order: written and read by the two kernels of this call
+					// dL/dy in list order: written and read by the two kernels of this call -- or written by the MLP kernel's tail already
+					const bool filled = offer.list_gradients != nullptr;
+					CHECK_THROW(!filled || (dy_planes && F == 2));
+					ArenaBuf gvals;
+					if (!filled) gvals = ArenaBuf{stream, grid_list_gradients_bytes(m_meta, ctx.hit_lists)};
 					carried = grid_backward_lists(stream, m_meta, dev_meta(), lp.dev_tasks.as<GridScatterTask>(), lp.n_tasks,
 					                    lp.dev_ranges.as<GridScatterRange>(), defer ? 0u : lp.n_ranges, lp.scratch.as<uint64_t>(), n, x, dy_src, dy_stride_sample, dy_stride_level, grads, ctx.hit_lists,
-					                    gvals.data(), mode == GradientMode::Accumulate, defer ? nullptr : offer.reduce_job, hit_counters(stream).fallbacks.as<uint32_t>());
+					                    filled ? offer.list_gradients : gvals.data(), mode == GradientMode::Accumulate, defer ? nullptr : offer.reduce_job, hit_counters(stream).fallbacks.as<uint32_t>(), filled);
 					if (defer && offer.reduce_job) carried = true; // (it went with the prologue)
 					if (dL_dx) {
 						CHECK_THROW(ctx.dy_dx);
@@ -852,6 +870,28 @@ public:
 	}
 
 	uint64_t list_scatters() const override { return m_list_scatters; }
+
+	bool list_gradient_tail(hipStream_t stream, const EncodingContext& ctx, uint32_t n, const GridItemMap& map, GridListTail& tail, size_t& gvals_bytes) override {
+		// the very conditions under which backward() will run the list-fed kernel over all levels on the caller's dL/dy itself (a max_level
+		// cut-off masks or settles gradients around the kernels: the separate pass then)
+		const bool lists = ctx.hit_elems && ctx.n == n && n % 64 == 0 && ctx.hit_stream == (const void*)stream && hit_counters(stream).generation == ctx.hit_generation && lds_scatter_usable();
+		if (!lists || m_fp32 || m_meta.n_features_per_level != 2 || m_max_level_gpu || levels_on(true) != m_meta.n_levels) return false;
+		const GridHitLists& hl = ctx.hit_lists;
+		if (!(hl.map == map) || map.n_windows < 2 || hl.n_items * hl.item_samples != n) return false;
+		tail = GridListTail{};
+		tail.sidx = hl.sidx;
+		tail.heads = hl.heads;
+		tail.n_items = hl.n_items;
+		tail.item_capacity = hl.item_capacity;
+		tail.n_levels = m_meta.n_levels;
+		tail.map = map;
+		for (uint32_t l = 0; l < m_meta.n_levels; ++l) {
+			const GridLevel& lv = m_meta.levels[l];
+			if (lv.scatter_n_chunks > 1 && lv.scatter_n_chunks <= GRID_FILTER_MAX_CHUNKS && !lv.scatter_binned) tail.level_mask |= 1u << l;
+		}
+		gvals_bytes = grid_list_gradients_bytes(m_meta, hl);
+		return m_meta.n_levels <= 16 && hl.item_capacity <= 2048;
+	}
 
 	// grid_interface.h:101-123 (not part of the hyperparameters or snapshots, as there)
 	bool set_max_level(float max_level) override { m_max_level = max_level; return true; }
@@ -2102,6 +2142,7 @@ public:
 	virtual std::vector<std::pair<uint32_t, uint32_t>> layer_sizes() const = 0;
 	virtual void initialize_params(Pcg32& rng, float* params_full_precision, float scale) = 0;
 	virtual uint64_t list_scatters() const { return 0; } // backward passes of the model's grid encoding(s) that ran the list-fed gradient kernel
+	virtual uint64_t list_gradient_tails() const { return 0; } // fused steps whose MLP kernel stored dL/dy in list order itself (no k_grid_list_gradients launch)
 	// max_level of the model's grid encoding(s) (Encoding::set_max_level); false: the model has none
 	virtual Encoding* input_encoding() { return nullptr; }
 	bool set_max_level(float max_level) { Encoding* e = input_encoding(); return e && e->set_max_level(max_level); }
@@ -2438,6 +2479,7 @@ public:
 	const char* last_train_kernel() const { return m_last_train_kernel; } // short name of the MLP kernel the last fused step launched (MlpTrainPlan::name)
 	uint64_t scatter_wide_fallbacks() { return m_encoding->scatter_wide_fallbacks(); }
 	uint64_t list_scatters() const override { return m_encoding->list_scatters(); }
+	uint64_t list_gradient_tails() const override { return m_list_gradient_tails; }
 	bool context_keeps_slabs(const ModelContext& c) const { const Ctx* x = dynamic_cast<const Ctx*>(&c); return x && (bool)x->slabs_kept; }
 	// the register-resident fused kernel (k_train_regs.hip) writes dL_doutput / L as compact [n][dims] matrices (TrainContext::compact)
 	bool fused_compact_context_supported(uint32_t n) const {
@@ -2466,14 +2508,24 @@ public:
 		// ~5 us each, independent of the encoding kernels) on a side stream was measured and lost 13-15 us per step on every
 		// workload: a cross-stream event dependency costs more here than the kernels it hides (the same happened with Adam).
 		if (step.profile) step.profile->mark(stream, StepProfile::Encode, false);
-		fused_encode(stream, *ctx, n, input, step.params, step.dL_dinput != nullptr, step.mode != GradientMode::Ignore, side_jobs_enabled());
+		// The MLP kernel is known before the encoding runs (mlp_train_plan on the step's request): where its workgroups each produce one whole
+		// work item of a grid's hit lists, the grid forms its items from those samples and the kernel's tail stores dL/dy in list order itself
+		// (list_gradient_tails; TCNN_AMD_LISTGRAD_IN_MLP=0: k_grid_list_gradients as a launch of its own, items of consecutive samples).
+		GridItemMap item_map;
+		bool mapped = false;
+		if (switches().listgrad_in_mlp && step.mode != GradientMode::Ignore && !step.dL_dinput && !m_network->layerwise() && m_encoding->n_params() > 0) {
+			const uint32_t x_plane_f = m_encoding->forward_plane_features(n), plane_f = m_encoding->level_plane_features(false, step.mode);
+			if (x_plane_f && plane_f) mapped = mlp_train_item_map(mlp_train_plan(m_network->desc(), step_request(n, step, x_plane_f, 0, true, plane_f, false)), item_map);
+		}
+		fused_encode(stream, *ctx, n, input, step.params, step.dL_dinput != nullptr, step.mode != GradientMode::Ignore, side_jobs_enabled(), mapped ? &item_map : nullptr);
 		if (step.profile) step.profile->mark(stream, StepProfile::Encode, true);
 		fused_mlp_and_scatter(stream, *ctx, n, input, step, optimizer);
 		return ctx;
 	}
 
 	// first half of the fused step: the encoding, as level planes where the encoding can produce them
-	void fused_encode(hipStream_t stream, Ctx& ctx, uint32_t n, MatView input, const void* params, bool prepare_input_gradients, bool prepare_param_gradients, bool prep_image = false) {
+	void fused_encode(hipStream_t stream, Ctx& ctx, uint32_t n, MatView input, const void* params, bool prepare_input_gradients, bool prepare_param_gradients, bool prep_image = false,
+	                  const GridItemMap* item_map = nullptr) {
 		const _Float16* p = (const _Float16*)params;
 		const uint32_t n_net = (uint32_t)m_network->n_params();
 		if (m_network->layerwise()) throw std::runtime_error{"NetworkWithInputEncoding::fused_encode: a layer-by-layer network has no fused training step"};
@@ -2493,10 +2545,30 @@ public:
 			job.desc = m_network->desc();
 			job.params = params;
 			job.image = ctx.image.data();
-			ctx.encoding_ctx = m_encoding->forward_planes(stream, n, input, p + n_net, ctx.network_input.data(), prepare_param_gradients, &job);
-		} else if (ctx.x_plane_f) ctx.encoding_ctx = m_encoding->forward_planes(stream, n, input, p + n_net, ctx.network_input.data(), prepare_param_gradients);
+			ctx.encoding_ctx = m_encoding->forward_planes(stream, n, input, p + n_net, ctx.network_input.data(), prepare_param_gradients, &job, item_map);
+		} else if (ctx.x_plane_f) ctx.encoding_ctx = m_encoding->forward_planes(stream, n, input, p + n_net, ctx.network_input.data(), prepare_param_gradients, nullptr, item_map);
 		else ctx.encoding_ctx = m_encoding->forward(stream, n, input, p + n_net, ctx.network_input.data(), prepare_input_gradients, prepare_param_gradients);
 		ctx.fused = true;
+	}
+
+	// what a fused step asks of the MLP kernel (mlp_train_plan)
+	MlpTrainRequest step_request(uint32_t n, const FusedStepData& step, uint32_t x_plane_f, uint32_t oneblob_bins, bool need_dx, uint32_t plane_f, bool records) const {
+		MlpTrainRequest request;
+		request.n = n;
+		request.x_plane_features = x_plane_f;
+		request.oneblob_bins = oneblob_bins;
+		request.oneblob_dims = oneblob_bins ? m_encoding->input_width() : 0u;
+		request.dims = m_network->output_width();
+		request.loss = step.loss;
+		request.external_dL_dy = step.external_dL_dy != nullptr;
+		request.data_pdf = step.data_pdf != nullptr;
+		request.out = step.out != nullptr;
+		request.dL_dx = need_dx;
+		request.dx_plane_features = plane_f;
+		request.dx_record_dims = records ? m_encoding->input_width() : 0u;
+		request.gradients = step.mode != GradientMode::Ignore;
+		request.compact_context = step.compact_context;
+		return request;
 	}
 
 	// second half: ONE MLP kernel (forward recomputed in registers, loss or external dL/doutput, backward, weight gradients),
@@ -2540,21 +2612,7 @@ public:
 			image_data = prepared.data();
 		}
 		// which kernel, and over how many workgroups: decided once, here (mlp_train_plan); each workgroup writes one weight-gradient slab
-		MlpTrainRequest request;
-		request.n = n;
-		request.x_plane_features = x_plane_f;
-		request.oneblob_bins = ctx.oneblob_bins;
-		request.oneblob_dims = ctx.oneblob_bins ? m_encoding->input_width() : 0u;
-		request.dims = m_network->output_width();
-		request.loss = step.loss;
-		request.external_dL_dy = step.external_dL_dy != nullptr;
-		request.data_pdf = step.data_pdf != nullptr;
-		request.out = step.out != nullptr;
-		request.dL_dx = need_dx;
-		request.dx_plane_features = plane_f;
-		request.dx_record_dims = records ? m_encoding->input_width() : 0u;
-		request.gradients = mode != GradientMode::Ignore;
-		request.compact_context = step.compact_context;
+		const MlpTrainRequest request = step_request(n, step, x_plane_f, ctx.oneblob_bins, need_dx, plane_f, records);
 		const MlpTrainPlan plan = mlp_train_plan(d, request);
 		if (!plan.ok) throw std::runtime_error{"NetworkWithInputEncoding: no fused training kernel for this network, batch and set of options"};
 		CHECK_THROW(g != nullptr || !request.gradients);
@@ -2572,6 +2630,20 @@ public:
 		args.dx_record_x = records ? input.data : nullptr;
 		args.slabs = slabs.as<float>();
 		args.n_params = n_net;
+		// the kernel's tail stores dL/dy in the order of the grid's hit lists where the forward pass formed its items from this plan's workgroups
+		GridListTail list_tail;
+		ArenaBuf list_gradients;
+		{
+			GridItemMap item_map;
+			size_t gvals_bytes = 0;
+			if (need_dx && !dL_dinput && request.gradients && !records && plane_f > 0 && switches().listgrad_in_mlp && mlp_train_item_map(plan, item_map) &&
+			    m_encoding->list_gradient_tail(stream, ctx.encoding_ctx, n, item_map, list_tail, gvals_bytes)) {
+				list_gradients = ArenaBuf{stream, gvals_bytes};
+				list_tail.gvals = list_gradients.data();
+				args.list_tail = &list_tail;
+				++m_list_gradient_tails;
+			}
+		}
 		if (profile) profile->mark(stream, StepProfile::MlpKernel, false);
 		mlp_train_launch(stream, d, plan, args);
 		m_last_train_kernel = plan.name;
@@ -2585,6 +2657,7 @@ public:
 		BackwardHandoff offer; // to the encoding's backward pass
 		offer.dy_records = records;
 		offer.prologue = optimizer.prologue;
+		offer.list_gradients = list_gradients.data();
 		if (mode != GradientMode::Ignore) {
 			reduce_job.n_elems = n_net;
 			reduce_job.n_slabs = n_slabs;
@@ -2629,6 +2702,7 @@ public:
 private:
 	bool m_live_image_kept = false;
 	size_t m_image_preps = 0;
+	uint64_t m_list_gradient_tails = 0;
 	const char* m_last_train_kernel = "";
 	std::unique_ptr<Encoding> m_encoding;
 	std::unique_ptr<Network> m_network;
@@ -3849,6 +3923,7 @@ public:
 	size_t image_preps() const { return m_model->image_preps(); }
 	uint64_t scatter_wide_fallbacks() { return m_model->scatter_wide_fallbacks(); }
 	uint64_t list_scatters() const { return m_model->list_scatters(); }
+	uint64_t list_gradient_tails() const { return m_model->list_gradient_tails(); }
 	size_t prologue_steps() const { return m_prologue_steps; }
 	// short name of the MLP training kernel the last training_step launched ("unfused": k_mlp_fwd -> k_loss -> k_mlp_bwd -> k_wgrad*; "" before the first)
 	const char* last_step_kernel() const { return m_last_step_kernel; }

@@ -34,6 +34,7 @@ struct R32Args {
 	float loss_scale;
 	uint32_t stagger;        // TCNN_AMD_MLP_STAGGER: waves 4..7 start their first trip this many times 64 clocks late
 	uint32_t prio_mode;      // TCNN_AMD_MLP_PRIO: 0 no priorities, 1 the two waves of a SIMD alternate their priority per trip, 2 the younger half at priority 1, 3 a trip's matrix regions above its loss
+	GridListTail tail;       // k_mlp_train_r32, plain level planes: dL/d(encoded input) is also stored in the grid's list order (gvals != nullptr)
 	unsigned long long* dbg; // TCNN_AMD_MLP_TIMING: per workgroup wave 0's clock at start / loop start / loop end / end, then every wave's loop end
 };
 

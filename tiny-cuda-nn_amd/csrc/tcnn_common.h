@@ -63,6 +63,7 @@ struct Switches {
 	bool mlp_regs = true;         // TCNN_AMD_MLP_REGS=0: the LDS-image kernels of k_train.hip
 	bool mlp_fast = true;         // TCNN_AMD_MLP_FAST=0: k_mlp_train_regs with run-time formats
 	uint32_t mlp_prio = 1;        // TCNN_AMD_MLP_PRIO: wave priorities of the MLP kernels (0 none, 1 alternating per trip, 2, 3)
+	bool listgrad_in_mlp = true;  // TCNN_AMD_LISTGRAD_IN_MLP=0: k_grid_list_gradients as a launch of its own instead of the tail of k_mlp_train_r32
 	bool mlp_layerwise = false;   // TCNN_AMD_MLP_LAYERWISE=1: every network of a model created now runs the layer-by-layer kernels (k_mlp_layers.hip)
 };
 Switches switches(); // a copy of the process-wide set, taken under its lock
@@ -139,7 +140,8 @@ struct MlpPrepJob;
 //     sidx  [..]   : the sample, relative to the item's first one (16 bits).
 // After the MLP kernel a streaming pass (k_grid_list_gradients, k_grid_scatter_lists.hip) brings dL/dy into the same order: per item it
 // loads the item's slice of the level's gradient plane into LDS (2 KB) and writes gvals [..] = dL/dy of element's sample, position
-// for position.  The chunk's owner then walks the items' runs of its chunk reading elems and gvals side by side -- dense loads, no
+// for position (where a workgroup of the fused MLP kernel produces exactly one item -- GridItemMap below -- that kernel's tail does this
+// itself and the pass is not launched: GridListTail).  The chunk's owner then walks the items' runs of its chunk reading elems and gvals side by side -- dense loads, no
 // gather, no coordinates, no pos_fract, no hash.  (Round 4: 4-byte elements {sample, corner bits}; the owner gathered a 16-byte record
 // per element from a 4 MB plane per level pair.  Each such gather costs the CU a whole 128-byte line from its L2, ~3 clocks per lane
 // whatever the bytes used -- 40 us of the kernel's 59 - 66 at 2^18 samples, profiles/r05_scatter_timeline.txt -- and needs the plane
@@ -150,6 +152,26 @@ inline constexpr uint32_t grid_hit_mask_shift(uint32_t n_pos_dims) { return 32u 
 constexpr uint32_t GRID_HIT_COUNT_STRIDE = 64;   // uint32 per level between the straggler counts (one memory channel each)
 constexpr uint32_t GRID_HIT_HEADS = 65;          // offsets per item: GRID_FILTER_MAX_CHUNKS + 1
 constexpr uint32_t GRID_HIT_WORDS = 2;           // uint32 per element
+// Which samples form work item j: n_windows runs of `window` consecutive samples, `stride` samples apart --
+//     position p of item j (p = s * window + t, t < window) is sample j * window + t + s * stride.
+// {item_samples, 0, 1}: item_samples consecutive samples.  {256, grid * 256, trips}: exactly the samples workgroup j of k_mlp_train_r32
+// works on (it deals 32-sample blocks out block-cyclically), so that the kernel's tail can bring its own dL/dy into list order
+// (GridListTail).  `window` is a power of two and a multiple of what one wave of the forward kernel covers: every run a wave loads or
+// stores stays dense.  Every kernel that turns (item, position) into a sample goes through grid_item_sample().
+struct GridItemMap {
+	uint32_t window = 0, window_shift = 0, stride = 0, n_windows = 0;
+	bool operator==(const GridItemMap& o) const { return window == o.window && window_shift == o.window_shift && stride == o.stride && n_windows == o.n_windows; }
+};
+inline GridItemMap grid_item_map(uint32_t window, uint32_t stride, uint32_t n_windows) {
+	GridItemMap m;
+	m.window = window, m.stride = stride, m.n_windows = n_windows;
+	while ((1u << m.window_shift) < window) ++m.window_shift;
+	return m;
+}
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline uint32_t grid_item_sample(const GridItemMap& m, uint32_t item, uint32_t pos) { return (item << m.window_shift) + (pos & (m.window - 1u)) + (pos >> m.window_shift) * m.stride; }
 struct GridHitLists {
 	uint32_t* elems = nullptr;       // [n_levels][n_items][item_capacity][GRID_HIT_WORDS]
 	uint16_t* sidx = nullptr;        // [n_levels][n_items][item_capacity]
@@ -158,7 +180,17 @@ struct GridHitLists {
 	uint32_t* counts = nullptr;      // [n_levels][GRID_HIT_COUNT_STRIDE]: stragglers per level; all zero when the forward kernel starts
 	uint32_t* zero_counts = nullptr; // the counter set of the NEXT forward launch on this stream: zeroed by this one
 	uint32_t n_items = 0, item_samples = 0, item_capacity = 0, straggler_capacity = 0;
+	GridItemMap map;                 // the samples of an item (item_samples = map.window * map.n_windows)
 	uint32_t dev_flags = 0;          // laboratory build only (TCNN_AMD_FWD_LISTS_DEV): timing-only variants of the list output
+};
+// What the tail of k_mlp_train_r32 needs to store the dL/dy it has just written in list order itself (the work of k_grid_list_gradients):
+// workgroup j's samples are item j's (lists.map), F = 2, plain level planes.  level_mask: bit l set <=> level l is listed.
+struct GridListTail {
+	const uint16_t* sidx = nullptr;
+	const uint32_t* heads = nullptr;
+	void* gvals = nullptr;           // [n_levels][n_items][item_capacity] half2; nullptr: no tail
+	uint32_t n_items = 0, item_capacity = 0, n_levels = 0, level_mask = 0;
+	GridItemMap map;
 };
 uint32_t grid_hit_item_samples(const GridMeta& meta); // samples per work item of the forward kernel shape used for this grid (k_grid_planes.hip)
 // the kernels address the pool (12 bytes x 2^(D-1) rows per sample and level) and the straggler masks with 32 bits
@@ -211,8 +243,9 @@ void grid_scatter_lists_plan(const GridMeta& meta, uint32_t n, std::vector<GridS
 bool grid_backward_lists(hipStream_t stream, const GridMeta& meta, const GridMeta* dev_meta, const GridScatterTask* dev_tasks, uint32_t n_tasks,
                          const GridScatterRange* dev_ranges, uint32_t n_ranges, uint64_t* scratch, uint32_t n, MatView x,
                          const void* dL_dy, uint32_t dy_stride_sample, uint32_t dy_stride_level, void* grad, const GridHitLists& lists, void* gvals, bool accumulate,
-                         const MlpReduceJob* reduce_job, uint32_t* fallback_count = nullptr);
-// gvals: workspace of grid_list_gradients_bytes(): dL/dy in list order, half [n_levels][n_items][item_capacity][F], written by the launch's first kernel
+                         const MlpReduceJob* reduce_job, uint32_t* fallback_count = nullptr, bool gvals_filled = false);
+// gvals: workspace of grid_list_gradients_bytes(): dL/dy in list order, half [n_levels][n_items][item_capacity][F], written by the launch's first
+// kernel -- or, gvals_filled, by the MLP kernel's tail already (GridListTail): that first kernel is then not launched
 size_t grid_list_gradients_bytes(const GridMeta& meta, const GridHitLists& lists);
 // the finalize pass of the shared chunks (+ the MLP's slab reduction), shared by both scatter kernels; false: no ranges, nothing was launched
 bool grid_scatter_finalize(hipStream_t stream, const GridScatterRange* dev_ranges, uint32_t n_ranges, uint64_t* scratch, void* grad, bool accumulate, const MlpReduceJob* reduce_job);
@@ -384,7 +417,11 @@ struct MlpTrainArgs {
 	float *L = nullptr, *slabs = nullptr;
 	const float* dx_record_x = nullptr;
 	uint32_t n_params = 0;                                 // floats per slab
+	const GridListTail* list_tail = nullptr;               // the kernel also stores dL_dx in the grid's list order (mlp_train_item_map() must hold for the plan)
 };
+// The item map under which workgroup j of plan's kernel produces exactly item j's dL/dx (k_mlp_train_r32 with plain level planes, every
+// wave the same number of trips); false: this plan has none.
+bool mlp_train_item_map(const MlpTrainPlan& plan, GridItemMap& map);
 // launches plan.grid workgroups of plan's kernel; args must be what plan.request describes (checked)
 void mlp_train_launch(hipStream_t stream, const MlpDesc& d, const MlpTrainPlan& plan, const MlpTrainArgs& args);
 // what a caller asks before it knows the whole request -- the kernels' own predicates, as mlp_train_plan applies them:

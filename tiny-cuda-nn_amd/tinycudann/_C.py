@@ -118,6 +118,7 @@ _SIGNATURES = {
     "tcnn_trainer_scatter_wide_fallbacks": (C.c_size_t, [_vp]),
     "tcnn_trainer_optimizer_prologue_steps": (C.c_size_t, [_vp]),
     "tcnn_trainer_list_scatters": (C.c_size_t, [_vp]),
+    "tcnn_trainer_list_gradient_tails": (C.c_size_t, [_vp]),
     "tcnn_trainer_last_step_kernel": (_cp, [_vp]),
     "tcnn_trainer_set_max_level": (_int, [_vp, _f32]),
     "tcnn_trainer_set_max_level_gpu": (_int, [_vp, _vp]),

@@ -112,6 +112,11 @@ class Trainer:
         """backward passes of the grid encoding that ran the list-fed gradient kernel (tcnn_amd.h: tcnn_trainer_list_scatters)"""
         return int(_C.lib.tcnn_trainer_list_scatters(self._h))
 
+    def list_gradient_tails(self):
+        """training steps whose MLP kernel stored dL/dy in the order of the grid's hit lists itself, so that no k_grid_list_gradients
+        launch ran (tcnn_amd.h: tcnn_trainer_list_gradient_tails)"""
+        return int(_C.lib.tcnn_trainer_list_gradient_tails(self._h))
+
     def last_step_kernel(self):
         """short name of the MLP training kernel the last training_step launched, e.g. "r32", "regs", "train<64,1,8,8>/act" or "unfused"
         (tcnn_amd.h: tcnn_trainer_last_step_kernel)"""
