@@ -233,6 +233,61 @@ def test_encoded_matrix_backward_of_an_earlier_forward_pass(tcnn, oracle):
     assert native.list_scatters() == 1
 
 
+def test_backward_follows_its_context_not_the_process_switches(tcnn, oracle, monkeypatch):
+    """The A/B switches are process-wide and reloaded by every tcnn_create_*: a module created between another module's forward and backward
+    pass must not change the gradient kernel of that pass -- the context's forward route binds (GridForwardRoute in the EncodingContext).
+    The 3-D grid of 6 levels x 2 features, T = 2^18, at 4096 samples (ROWS_CASES[6]; the default takes the hit lists for it).
+      1. forward under the default, then a second module created under TCNN_AMD_GRID_SCATTER=atomic, then the first one's backward: the
+         list-fed kernel (list_scatters() == 1), the oracle's exact gradient bit for bit;
+      2. the two switch sets exchanged: the atomic kernel (list_scatters() stays 0), the gradient of the same sequence without the second
+         module within the aggregate bound test_grid_gradient_exact has for the order-dependent fp16 atomics (2 % of the gradient's norm).
+    In both the second module's own passes follow its own switch set."""
+    n_in, enc_cfg, n = ROWS_CASES[6][:3]
+    ref = oracle.create_encoding(n_in, enc_cfg, alignment=0)
+    params_h = oracle.half_bits(oracle.Pcg32(3).uniform_strided(ref.n_params, -1.0, 1.0))
+    x = oracle.Pcg32(42).uniform_strided(n * n_in).reshape(n, n_in)
+    width = ref.padded_output_width
+    dy = oracle.half_bits(oracle.Pcg32(9).uniform_strided(n * width, -2.0, 2.0).reshape(n, width))
+    want = np.zeros(ref.n_params, dtype=np.uint16)
+    ref.backward_exact(x, dy, want)
+    xt, pt, dyt = _t(x), _t(params_h.view(np.float16)).requires_grad_(True), _t(dy.view(np.float16))
+    atomic = {"TCNN_AMD_GRID_SCATTER": "atomic"}
+
+    def create(env):  # (the process switches stay what this creation loaded until the next one)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        native = tcnn.Encoding(n_in, enc_cfg).native_tcnn_module
+        for k in env:
+            monkeypatch.delenv(k)
+        return native
+
+    def backward(native, forward):
+        return _bits(native.bwd(forward[0], xt, pt, forward[1], dyt)[1]).copy()
+
+    def close(g, other):
+        a, b = _f32(g), _f32(other)
+        return float(np.linalg.norm(a - b)) <= 2e-2 * float(np.linalg.norm(b))
+
+    first = create({})
+    forward = first.fwd(xt, pt)
+    second = create(atomic)
+    g = backward(first, forward)
+    assert first.list_scatters() == 1 and np.array_equal(g, want)
+    g = backward(second, second.fwd(xt, pt))
+    assert second.list_scatters() == 0 and close(g, want)
+
+    alone = create(atomic)
+    g_alone = backward(alone, alone.fwd(xt, pt))
+    assert alone.list_scatters() == 0 and close(g_alone, want)
+    first = create(atomic)
+    forward = first.fwd(xt, pt)
+    second = create({})
+    g = backward(first, forward)
+    assert first.list_scatters() == 0 and close(g, g_alone)
+    g = backward(second, second.fwd(xt, pt))
+    assert second.list_scatters() == 1 and np.array_equal(g, want)
+
+
 @pytest.mark.parametrize("n_in,enc_cfg,n", SCATTER_CASES)
 @pytest.mark.parametrize("accumulate", [False, True])
 def test_grid_gradient_exact(tcnn, oracle, n_in, enc_cfg, n, accumulate):

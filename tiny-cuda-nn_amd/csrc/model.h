@@ -221,20 +221,27 @@ struct EncodingContext {
 	uint64_t hit_generation = 0; // the encoding's list counters are reused by later forward passes: lists are valid while this is the latest one on its stream
 	const void* hit_stream = nullptr;
 	uint32_t n = 0;
+	GridForwardRoute route; // grid only: how this batch was produced, and the gradient kernels that follow from it (grid_forward_route)
 	std::vector<EncodingContext> nested; // Composite: one context per nested encoding
 };
 
 // What the caller of Encoding::backward() offers to that one call, and what the call reports back.  An encoding is free to ignore all of it.
 struct BackwardHandoff {
-	bool dy_records = false;                  // the level planes hold 16-byte scatter records {coordinates, gradients} (MlpTrainRequest::dx_record_dims)
 	const MlpReduceJob* reduce_job = nullptr; // a small job the pass may carry on one of its launches, or pass on with the prologue
 	// the optimizer's launch offers to run the scatter's finalize pass (and the reduce job) as its prologue (AdamPrologue, tcnn_common.h):
 	// a backward pass that takes the offer fills it in, sets ->pending and launches no finalize pass of its own
 	AdamPrologue* prologue = nullptr;
-	// the MLP kernel's tail has already stored dL_dy in the order of this batch's hit lists (GridListTail, Encoding::list_gradient_tail): the
-	// workspace it filled, which the list-fed gradient kernel reads instead of launching k_grid_list_gradients
-	void* list_gradients = nullptr;
+	void* list_gradients = nullptr;           // GridBackwardRoute::tail was taken: the workspace the MLP kernel's tail filled, read instead of launching k_grid_list_gradients
 	bool reduce_carried = false;              // reported: reduce_job went with a launch of this pass or with the prologue -- it is no longer the caller's to run
+};
+
+// What a caller that asked Encoding::forward_route() itself hands to forward(): the route (kernel Planes: `out` is level planes [padded / F][n][F]),
+// a side job the plane kernel carries (the fragment images of the network behind the encoding) and the samples the fused MLP kernel's workgroups
+// will work on (mlp_train_item_map): a grid that writes hit lists forms its items from them where its item size allows (GridBackwardRoute::tail)
+struct ForwardPlan {
+	GridForwardRoute route;
+	const MlpPrepJob* prep_job = nullptr;
+	const GridItemMap* item_map = nullptr;
 };
 
 class Encoding {
@@ -255,12 +262,16 @@ public:
 	virtual size_t n_params() const { return 0; }
 	virtual void initialize_params(Pcg32& rng, float* params_full_precision, float scale) {}
 	// out: [n][padded_output_width] T (T = float if fp32 else half)
-	// prepare_param_gradients: a backward pass with parameter gradients will follow (lets the grid record its scatter filter)
-	virtual EncodingContext forward(hipStream_t stream, uint32_t n, MatView x, const void* params, void* out, bool prepare_input_gradients, bool prepare_param_gradients) = 0;
+	// prepare_param_gradients: a backward pass with parameter gradients will follow (lets the grid record its scatter filter); plan (optional): ForwardPlan
+	virtual EncodingContext forward(hipStream_t stream, uint32_t n, MatView x, const void* params, void* out, bool prepare_input_gradients, bool prepare_param_gradients, const ForwardPlan* plan = nullptr) = 0;
 	// dL_dy [n][padded] T; grads: T[n_params] or nullptr (Ignore)
-	// dy_planes: dL_dy is laid out as level planes [padded / F][n][F] (only if level_plane_features() allowed it), else AoS
-	// handoff (optional): what the fused step offers to this pass (BackwardHandoff)
-	virtual void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes, BackwardHandoff* handoff = nullptr) = 0;
+	// route: this encoding's backward_route() for this pass -- the form dL_dy has and, for a grid, its gradient kernel; handoff (optional): BackwardHandoff
+	virtual void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, const GridBackwardRoute& route, BackwardHandoff* handoff = nullptr) = 0;
+	// How backward() will run for this context, asked once per pass in front of whatever produces dL_dy; offer: the richest form the caller can deliver it in
+	virtual GridBackwardRoute backward_route(const Switches& sw, hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, GridDyForm offer, bool want_dL_dx, GradientMode mode) { return {}; }
+	void backward_rows(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode) {
+		backward(stream, ctx, n, x, dL_dy, dL_dx, params, grads, mode, backward_route(switches(), stream, ctx, n, x, GridDyForm::Rows, dL_dx != nullptr, mode));
+	}
 	// second-order input gradients (object.h:278-288), with v = dL_ddLdx [n][d_in] fp32 and d = dL_dy [n][padded] T:
 	//   dL_ddLdy [n][padded] T = J v (the tangent; exactly zero in the padding columns), dL_dx = d/dx <v, J^T d> in fp32 through the view,
 	//   grads = d/dparams of the same by `mode`.  Null results (and Ignore) are not computed; dL_dy may be null when only dL_ddLdy is asked for.
@@ -274,29 +285,14 @@ public:
 	// the error comes before anything of its own is allocated or launched (NetworkWithInputEncoding).
 	virtual bool has_second_order() const { return false; }
 	virtual bool second_order_reads_dL_dy() const { return true; } // false: backward_backward_input() needs no dL_dy (dL/dx is linear in x)
-	// > 0: this encoding's backward prefers dL_dy in level planes with that many features per plane (see k_grid_bwd_lds)
-	virtual uint32_t level_plane_features(bool need_dL_dx, GradientMode mode) const { return 0; }
 	// true: the encoding is half(x * scale + offset) padded with ones -- cheap enough to apply inside the consumer's load
 	virtual bool as_identity(float& scale, float& offset) const { return false; }
 	// n_bins if this is a half-precision OneBlob encoding the MLP kernels can evaluate inside their input load (MlpIo::x_oneblob_bins), else 0
 	virtual uint32_t as_oneblob() const { return 0; }
-	// true: backward() (with level planes allowed) prefers 16-byte records {coordinates, gradients} per (level, sample)
-	virtual bool scatter_records_usable(MatView x) const { return false; }
-	virtual uint32_t scatter_record_planes() const { return 0; } // 16-byte records per sample when scatter_records_usable()
 	virtual uint64_t scatter_wide_fallbacks() { return 0; }      // grid only: tasks of the list-fed scatter that had to take the 64-bit passes
 	virtual uint64_t list_scatters() const { return 0; }         // grid only: backward passes that ran the list-fed scatter (k_grid_scatter_lists)
-	// > 0: forward_planes() can write the encoded batch as level planes [padded / F][n][F] (no input gradients in that form)
-	virtual uint32_t forward_plane_features(uint32_t n) { return 0; }
-	// prep_job (optional): a side job the forward kernel carries along -- the fragment images of the network behind the encoding
-	// item_map (optional): the samples the fused MLP kernel's workgroups will work on (mlp_train_item_map); a grid that writes hit lists
-	// forms its work items from them where its item size allows, so that list_gradient_tail() can hold later
-	virtual EncodingContext forward_planes(hipStream_t stream, uint32_t n, MatView x, const void* params, void* out_planes, bool prepare_param_gradients,
-	                                       const MlpPrepJob* prep_job = nullptr, const GridItemMap* item_map = nullptr) {
-		throw std::runtime_error{"Encoding: level-plane output is not available"};
-	}
-	// true: ctx holds hit lists whose items are `map`'s and whose gradient pass over all levels will run on `stream` -- `tail` is filled in
-	// (all but gvals: the caller's workspace of gvals_bytes, handed back through BackwardHandoff::list_gradients)
-	virtual bool list_gradient_tail(hipStream_t stream, const EncodingContext& ctx, uint32_t n, const GridItemMap& map, GridListTail& tail, size_t& gvals_bytes) { return false; }
+	// How a batch will be produced, asked before the forward pass (grid_forward_route; as_planes: the caller takes level planes where the kernel is Planes, through a ForwardPlan)
+	virtual GridForwardRoute forward_route(const Switches& sw, uint32_t n, bool as_planes, bool prepare_input_gradients, bool prepare_param_gradients) const { return {}; }
 	virtual Json hyperparams() const = 0;
 	bool fp32() const { return m_fp32; }
 	// max_level of the grid encodings (grid_interface.h:101-123), read at call time.  false: no grid encoding here to take it.
@@ -439,20 +435,23 @@ public:
 		generate_random_uniform(nullptr, rng.st, n_params(), params_full_precision, -1e-4f * scale, 1e-4f * scale);
 	}
 
-	EncodingContext forward(hipStream_t stream, uint32_t n, MatView x, const void* params, void* out, bool prepare_input_gradients, bool prepare_param_gradients) override {
+	EncodingContext forward(hipStream_t stream, uint32_t n, MatView x, const void* params, void* out, bool prepare_input_gradients, bool prepare_param_gradients, const ForwardPlan* plan) override {
 		EncodingContext ctx;
 		if ((!out && !prepare_input_gradients) || padded_output_width() == 0 || n == 0) return ctx;
 		// The encoded batch as a matrix (callers with their own network: the PyTorch Encoding module, a grid nested in a Composite): the level-plane
 		// kernel -- XCD-aware, and the one that writes the hit lists the fast gradient kernel reads -- and a transposition behind it, instead of
 		// the AoS kernel and the bit-plane gradient kernel (3-D, F = 2, 2^18 samples through the PyTorch module: 1.74 -> 0.42 ms forward + backward; a Composite of such a grid and spherical harmonics in front of a 64x2 network: 1.89 -> 0.49 ms per training step).
-		if (out && !prepare_input_gradients && switches().grid_rows_planes && forward_plane_features(n) > 0 && grid_planes_to_rows_supported(m_meta, n, padded_output_width())) {
+		const GridForwardRoute route = plan ? plan->route : forward_route(switches(), n, false, prepare_input_gradients, prepare_param_gradients);
+		if (route.kernel == GridForwardKernel::Planes) return forward_planes(stream, route, n, x, params, out, plan->prep_job, plan->item_map);
+		if (route.kernel == GridForwardKernel::PlanesToRows) {
 			ArenaBuf planes{stream, (size_t)n * padded_output_width() * sizeof(uint16_t)};
-			ctx = forward_planes(stream, n, x, params, planes.data(), prepare_param_gradients);
+			ctx = forward_planes(stream, route, n, x, params, planes.data());
 			grid_planes_to_rows(stream, m_meta, n, padded_output_width(), planes.data(), out, padded_output_width()); // (the planes of zeros behind the levels' included)
 			return ctx;
 		}
+		ctx.route = route;
 		if (prepare_input_gradients) ctx.dy_dx = ArenaBuf{stream, (size_t)n * m_n_features * m_meta.n_pos_dims * sizeof(float)};
-		const bool want_filter = prepare_param_gradients && lds_scatter_usable() && n % 64 == 0;
+		const bool want_filter = route.recorded == GridRecorded::BitPlanes;
 		ArenaBuf mask;
 		if (want_filter) mask = ArenaBuf{stream, (size_t)m_meta.n_levels * n * (GRID_FILTER_MAX_CHUNKS / 64) * sizeof(uint64_t)};
 		grid_forward(stream, m_meta, dev_meta(), m_fp32, n, x, params, out, padded_output_width(), ctx.dy_dx.as<float>(), mask.as<uint64_t>());
@@ -469,11 +468,9 @@ public:
 		return ctx;
 	}
 
-	// TCNN_AMD_GRID_PLANES=0 keeps the AoS forward kernel inside the fused training step (A/B runs)
-	static bool use_planes() { return switches().grid_planes; }
-	uint32_t forward_plane_features(uint32_t n) override {
-		// (a padded encoding -- 12 levels x 2 features in front of a 16-aligned network -- has whole planes of zeros behind its levels' planes)
-		return (!m_fp32 && use_planes() && m_n_to_pad % m_meta.n_features_per_level == 0 && grid_planes_supported(m_meta, n)) ? m_meta.n_features_per_level : 0;
+	GridFacts facts() const { return GridFacts{&m_meta, m_fp32, m_scatter_levels_ok, m_any_binned, m_n_to_pad}; }
+	GridForwardRoute forward_route(const Switches& sw, uint32_t n, bool as_planes, bool prepare_input_gradients, bool prepare_param_gradients) const override {
+		return grid_forward_route(facts(), sw, n, as_planes, prepare_input_gradients, prepare_param_gradients);
 	}
 
 	struct PlanesPlan {
@@ -492,12 +489,12 @@ public:
 		return *(m_planes_plans[n] = std::move(plan));
 	}
 
-	EncodingContext forward_planes(hipStream_t stream, uint32_t n, MatView x, const void* params, void* out_planes, bool prepare_param_gradients,
-	                               const MlpPrepJob* prep_job = nullptr, const GridItemMap* item_map = nullptr) override {
+	EncodingContext forward_planes(hipStream_t stream, const GridForwardRoute& route, uint32_t n, MatView x, const void* params, void* out_planes,
+	                               const MlpPrepJob* prep_job = nullptr, const GridItemMap* item_map = nullptr) {
 		EncodingContext ctx;
-		CHECK_THROW(forward_plane_features(n) > 0);
-		const bool want_filter = prepare_param_gradients && lds_scatter_usable();
-		const bool want_lists = want_filter && hit_lists_usable(n);
+		CHECK_THROW(route.planned && route.kernel != GridForwardKernel::Rows);
+		ctx.route = route;
+		const bool want_lists = route.recorded == GridRecorded::HitLists;
 		if (want_lists) {
 			// Hit lists (k_grid_scatter_lists.hip): the storage is this pass's own; the stragglers' counts live in one of the stream's two
 			// counter sets -- this launch counts in one and zeroes the other for the next forward pass, so no memset sits between the steps.
@@ -528,7 +525,7 @@ public:
 			ctx.hit_generation = ++hc.generation;
 			ctx.hit_stream = (const void*)stream;
 			ctx.n = n;
-		} else if (want_filter) {
+		} else if (route.recorded == GridRecorded::BitPlanes) {
 			ctx.chunk_mask = ArenaBuf{stream, (size_t)m_meta.n_levels * grid_scatter_max_chunks() * (n / 64) * sizeof(uint64_t)};
 			ctx.n = n;
 		}
@@ -543,126 +540,122 @@ public:
 		return ctx;
 	}
 
-	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes, BackwardHandoff* handoff) override {
+	// hit lists of this very batch, their counters not yet handed to a later forward pass of this stream
+	bool lists_current(hipStream_t stream, const EncodingContext& ctx, uint32_t n) { return ctx.hit_elems && ctx.n == n && ctx.hit_stream == (const void*)stream && hit_counters(stream).generation == ctx.hit_generation; }
+	// (a per-sample array overrides the scalar)
+	GridMaxLevel max_level_state() const { return m_max_level_gpu ? GridMaxLevel::PerSample : (levels_on(true) < m_meta.n_levels ? GridMaxLevel::Scalar : GridMaxLevel::None); }
+	GridBackwardRoute backward_route(const Switches& sw, hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, GridDyForm offer, bool want_dL_dx, GradientMode mode) override {
+		GridBackwardRoute r = grid_backward_route(facts(), sw, ctx.route, lists_current(stream, ctx, n), n, offer, want_dL_dx, mode, max_level_state(), x.stride_dim == 1 && x.stride_sample == m_meta.n_pos_dims);
+		const GridHitLists& hl = ctx.hit_lists;
+		r.tail = r.tail && hl.map.n_windows >= 2 && hl.n_items * hl.item_samples == n; // (items formed from an MLP kernel's workgroups: forward_planes)
+		if (r.tail) {
+			r.list_tail.sidx = hl.sidx, r.list_tail.heads = hl.heads, r.list_tail.map = hl.map;
+			r.list_tail.n_items = hl.n_items, r.list_tail.item_capacity = hl.item_capacity;
+			r.tail_bytes = grid_list_gradients_bytes(m_meta, hl);
+		}
+		return r;
+	}
+
+	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, const GridBackwardRoute& route, BackwardHandoff* handoff) override {
 		if ((!dL_dx && mode == GradientMode::Ignore) || n == 0) return;
-		BackwardHandoff offer = handoff ? *handoff : BackwardHandoff{};
+		const BackwardHandoff offer = handoff ? *handoff : BackwardHandoff{};
 		const auto all_levels = [&](const void* dy) { // (reports through the caller's hand-off, if there is one)
-			const bool carried = backward_all_levels(stream, ctx, n, x, dy, dL_dx, params, grads, mode, dy_planes, offer);
+			const bool carried = backward_all_levels(stream, ctx, n, x, dy, dL_dx, params, grads, mode, route, offer);
 			if (handoff) handoff->reduce_carried = carried;
 		};
-		const uint32_t l_bwd = m_max_level_gpu ? m_meta.n_levels : levels_on(true); // (a per-sample array overrides the scalar)
-		if (!m_max_level_gpu && l_bwd == m_meta.n_levels) return all_levels(dL_dy);
-		if (m_max_level_gpu) { // per sample: dL/dy of the skipped (sample, level) pairs zeroed -- the exact sums add nothing for a zero product
-			CHECK_THROW(!offer.dy_records); // (scatter_records_usable() is false while a per-sample array is set)
-			CHECK_THROW(!offer.list_gradients); // (list_gradient_tail() is false too: the gradients in list order would be the unmasked ones)
+		const GridMaxLevel max_level = max_level_state();
+		if (max_level == GridMaxLevel::None) return all_levels(dL_dy);
+		if (max_level == GridMaxLevel::PerSample) { // dL/dy of the skipped (sample, level) pairs zeroed -- the exact sums add nothing for a zero product
 			const uint32_t F = m_meta.n_features_per_level;
+			const bool dy_planes = route.dy == GridDyForm::Planes; // (never records, never the MLP kernel's tail: the route sees the array)
 			const size_t elem = dy_planes ? 2 : (m_fp32 ? 4 : 2);
 			ArenaBuf masked{stream, (size_t)n * padded_output_width() * elem};
-			if (dy_planes) zero_levels(stream, 2, n, F, F, (uint64_t)n * F, masked.data(), true, dL_dy);
-			else zero_levels(stream, elem, n, F, padded_output_width(), F, masked.data(), true, dL_dy);
+			zero_levels(stream, elem, n, F, dy_planes ? F : padded_output_width(), dy_planes ? (uint64_t)n * F : F, masked.data(), true, dL_dy);
 			return all_levels(masked.data());
 		}
-		// scalar (grid.h:237-245): the optimizer's offer of its prologue is declined by not passing it on -- the off levels' gradients are
+		// scalar (grid.h:237-245): the route declines the optimizer's prologue and the MLP kernel's tail -- the off levels' gradients are
 		// settled below, after the kernels, and the optimizer's own launch sees every parameter
-		offer.prologue = nullptr;
-		CHECK_THROW(!offer.list_gradients); // (list_gradient_tail() is false under a cut-off)
-		GradientTail tail{*this, stream, grads, mode, l_bwd};
+		GradientTail tail{*this, stream, grads, mode, levels_on(true)};
 		all_levels(dL_dy);
 		tail.settle();
 	}
 
-	// returns whether offer.reduce_job was carried: by a launch of this pass, or handed on with the prologue
-	bool backward_all_levels(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes,
-	                         const BackwardHandoff& offer) {
-		const size_t elem = m_fp32 ? 4 : 2;
+	// a dispatch on the route's kernel; returns whether offer.reduce_job was carried: by a launch of this pass, or handed on with the prologue
+	bool backward_all_levels(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode,
+	                         const GridBackwardRoute& route, const BackwardHandoff& offer) {
+		const uint32_t F = m_meta.n_features_per_level;
+		const bool dy_planes = route.dy != GridDyForm::Rows, accumulate = mode == GradientMode::Accumulate;
+		uint32_t dy_stride_sample = dy_planes ? F : padded_output_width(), dy_stride_level = dy_planes ? n * F : F;
 		bool carried = false;
-		if (mode != GradientMode::Ignore) {
-			CHECK_THROW(grads != nullptr);
-			const bool scratch32 = !m_fp32 && m_meta.n_features_per_level == 1; // grid.h:660: F == 1 accumulates in fp32
-			if (scratch32) {
-				ArenaBuf tmp{stream, n_params() * sizeof(float)};
-				if (mode == GradientMode::Overwrite) HIP_CHECK_THROW(hipMemsetAsync(tmp.data(), 0, n_params() * sizeof(float), stream));
-				else cast_half_to_float(stream, n_params(), grads, tmp.as<float>());
-				grid_backward(stream, m_meta, dev_meta(), true, n, x, dL_dy, false, padded_output_width(), tmp.data());
-				cast_float_to_half(stream, n_params(), tmp.as<float>(), grads);
-			} else if (lds_scatter_usable() && n % 64 == 0) {
-				// MI355X path: LDS owner-computes scatter with exact integer accumulation; writes every element (k_grid_scatter.hip)
-				// hit lists of this very batch, their counters not yet handed to a later forward pass of this stream
-				const bool lists = ctx.hit_elems && ctx.n == n && ctx.hit_stream == (const void*)stream && hit_counters(stream).generation == ctx.hit_generation;
-				if (lists) { // k_grid_scatter_lists.hip: a static plan, nothing to tune
-					CHECK_THROW(!offer.dy_records); // the listed elements bring entries and weights along: dL/dy is gathered from plain level planes (or rows)
-					ListsPlan& lp = lists_plan(n, stream);
-					const uint32_t F = m_meta.n_features_per_level;
-					// dL/dy as rows (a caller's own network): into level planes first -- the streamed tasks read a level's gradients sample after
-					// sample, 4 bytes out of every row's 64 otherwise (2^18 samples: the owners 82 us from rows, 42 from planes; the transposition 12)
-					ArenaBuf dy_as_planes;
-					if (!dy_planes && grid_planes_to_rows_supported(m_meta, n, m_n_features)) {
-						dy_as_planes = ArenaBuf{stream, (size_t)n * m_n_features * sizeof(uint16_t)};
-						grid_rows_to_planes(stream, m_meta, n, m_n_features, dL_dy, padded_output_width(), dy_as_planes.data());
-					}
-					const bool planes_now = dy_planes || dy_as_planes;
-					const void* dy_src = dy_as_planes ? dy_as_planes.data() : dL_dy;
-					const uint32_t dy_stride_sample = planes_now ? F : padded_output_width(), dy_stride_level = planes_now ? n * F : F;
-					++m_list_scatters;
-					// the finalize pass (and the reduce job with it) may be left to the optimizer's launch: no ranges, no job -> no launch here
-					const bool defer = take_prologue(offer, lp.dev_ranges.as<GridScatterRange>(), lp.host_ranges, lp.scratch.as<uint64_t>(), grads, mode);
-					// dL/dy in list order: written and read by the two kernels of this call -- or written by the MLP kernel's tail already
-					const bool filled = offer.list_gradients != nullptr;
-					CHECK_THROW(!filled || (dy_planes && F == 2));
-					ArenaBuf gvals;
-					if (!filled) gvals = ArenaBuf{stream, grid_list_gradients_bytes(m_meta, ctx.hit_lists)};
-					carried = grid_backward_lists(stream, m_meta, dev_meta(), lp.dev_tasks.as<GridScatterTask>(), lp.n_tasks,
-					                    lp.dev_ranges.as<GridScatterRange>(), defer ? 0u : lp.n_ranges, lp.scratch.as<uint64_t>(), n, x, dy_src, dy_stride_sample, dy_stride_level, grads, ctx.hit_lists,
-					                    filled ? offer.list_gradients : gvals.data(), mode == GradientMode::Accumulate, defer ? nullptr : offer.reduce_job, hit_counters(stream).fallbacks.as<uint32_t>(), filled);
-					if (defer && offer.reduce_job) carried = true; // (it went with the prologue)
-					if (dL_dx) {
-						CHECK_THROW(ctx.dy_dx);
-						CHECK_THROW(!dy_planes);
-						grid_backward_input(stream, m_meta, m_fp32, n, dL_dy, padded_output_width(), ctx.dy_dx.as<float>(), *dL_dx);
-					}
-					return carried;
-				}
-				ScatterPlan& plan = scatter_plan(n, stream);
-				const uint32_t F = m_meta.n_features_per_level;
-				const uint64_t* mask = (ctx.chunk_mask && ctx.n == n) ? ctx.chunk_mask.as<uint64_t>() : nullptr;
-				// The second filtered launch at this batch size is timed per task and the plan re-cut from the measured
-				// per-level work (grid_scatter_plan): one stream synchronisation, once per (encoding, batch size).
-				const bool tune = !plan.tuned && mask && plan.n_tasks > 0 && scatter_tuning_enabled() && ++plan.launches == 2;
-				DeviceBuf times;
-				if (tune) {
-					times.resize((size_t)plan.n_tasks * 8 * sizeof(uint64_t));
-					times.memset(0);
-				}
-				const uint32_t dy_stride_sample = dy_planes ? F : padded_output_width(), dy_stride_level = dy_planes ? n * F : F;
-				// (not in the step whose launch is timed for the tuner: the plan, ranges and scratch included, is rebuilt right after it)
-				const bool defer = !tune && take_prologue(offer, plan.dev_ranges.as<GridScatterRange>(), plan.host_ranges, plan.scratch.as<uint64_t>(), grads, mode);
-				carried = grid_backward_lds(stream, m_meta, dev_meta(), plan.dev_tasks.as<GridScatterTask>(), plan.n_tasks, plan.dev_ranges.as<GridScatterRange>(), defer ? 0u : plan.n_ranges,
-				                  plan.scratch.as<uint64_t>(), n, x, dL_dy, dy_stride_sample, dy_stride_level, grads, mask,
-				                  mode == GradientMode::Accumulate, dy_planes && offer.dy_records, tune ? times.as<uint64_t>() : nullptr, defer ? nullptr : offer.reduce_job);
-				if (defer && offer.reduce_job) carried = true; // (it went with the prologue)
-				if (m_any_binned) { // levels cut into more than 64 chunks (k_grid_bin.hip)
-					CHECK_THROW(!(dy_planes && offer.dy_records));
-					ArenaBuf workspace{stream, grid_bin_workspace_bytes(m_meta, n)};
-					grid_backward_binned(stream, m_meta, dev_meta(), n, x, dL_dy, dy_stride_sample, dy_stride_level, grads, mode == GradientMode::Accumulate, workspace.data(),
-					                     hit_counters(stream).fallbacks.as<uint32_t>());
-				}
-				if (tune) {
-					HIP_CHECK_THROW(hipStreamSynchronize(stream));
-					std::vector<uint64_t> h((size_t)plan.n_tasks * 8);
-					HIP_CHECK_THROW(hipMemcpy(h.data(), times.data(), h.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-					const std::vector<float> level_us = grid_scatter_level_costs(m_meta, plan.host_tasks, h);
-					build_scatter_plan(plan, n, &level_us);
-					plan.tuned = true;
-				}
-			} else {
-				CHECK_THROW(!dy_planes);
-				if (mode == GradientMode::Overwrite) HIP_CHECK_THROW(hipMemsetAsync(grads, 0, n_params() * elem, stream)); // grid.h:858
-				grid_backward(stream, m_meta, dev_meta(), m_fp32, n, x, dL_dy, m_fp32, padded_output_width(), grads);
+		if (mode != GradientMode::Ignore) CHECK_THROW(grads != nullptr && route.kernel != GridGradientKernel::None); // (a route of backward_route())
+		switch (mode == GradientMode::Ignore ? GridGradientKernel::None : route.kernel) {
+		case GridGradientKernel::None: break;
+		case GridGradientKernel::AtomicScratch32: { // grid.h:660: F == 1 accumulates in fp32
+			ArenaBuf tmp{stream, n_params() * sizeof(float)};
+			if (mode == GradientMode::Overwrite) HIP_CHECK_THROW(hipMemsetAsync(tmp.data(), 0, n_params() * sizeof(float), stream));
+			else cast_half_to_float(stream, n_params(), grads, tmp.as<float>());
+			grid_backward(stream, m_meta, dev_meta(), true, n, x, dL_dy, false, padded_output_width(), tmp.data());
+			cast_float_to_half(stream, n_params(), tmp.as<float>(), grads);
+		} break;
+		case GridGradientKernel::Atomic:
+			if (mode == GradientMode::Overwrite) HIP_CHECK_THROW(hipMemsetAsync(grads, 0, n_params() * (m_fp32 ? 4 : 2), stream)); // grid.h:858
+			grid_backward(stream, m_meta, dev_meta(), m_fp32, n, x, dL_dy, m_fp32, padded_output_width(), grads);
+			break;
+		case GridGradientKernel::Lists: { // k_grid_scatter_lists.hip: a static plan, nothing to tune
+			ScatterPlan& plan = scatter_plan(n, stream, true);
+			// dL/dy as rows (a caller's own network): into level planes first -- the streamed tasks read a level's gradients sample after
+			// sample, 4 bytes out of every row's 64 otherwise (2^18 samples: the owners 82 us from rows, 42 from planes; the transposition 12)
+			ArenaBuf dy_as_planes;
+			const void* dy_src = dL_dy;
+			if (!dy_planes && grid_planes_to_rows_supported(m_meta, n, m_n_features)) {
+				dy_as_planes = ArenaBuf{stream, (size_t)n * m_n_features * sizeof(uint16_t)};
+				grid_rows_to_planes(stream, m_meta, n, m_n_features, dL_dy, padded_output_width(), dy_as_planes.data());
+				dy_src = dy_as_planes.data(), dy_stride_sample = F, dy_stride_level = n * F;
 			}
+			++m_list_scatters;
+			const bool defer = take_prologue(route, offer, plan, grads, mode);
+			// dL/dy in list order: written and read by the two kernels of this call -- or written by the MLP kernel's tail already
+			const bool filled = offer.list_gradients != nullptr;
+			ArenaBuf gvals;
+			if (!filled) gvals = ArenaBuf{stream, grid_list_gradients_bytes(m_meta, ctx.hit_lists)};
+			carried = grid_backward_lists(stream, m_meta, dev_meta(), plan.dev_tasks.as<GridScatterTask>(), plan.n_tasks, plan.dev_ranges.as<GridScatterRange>(), defer ? 0u : plan.n_ranges,
+			                              plan.scratch.as<uint64_t>(), n, x, dy_src, dy_stride_sample, dy_stride_level, grads, ctx.hit_lists, filled ? offer.list_gradients : gvals.data(), accumulate,
+			                              defer ? nullptr : offer.reduce_job, hit_counters(stream).fallbacks.as<uint32_t>(), filled) ||
+			          (defer && offer.reduce_job); // (it went with the prologue)
+		} break;
+		case GridGradientKernel::BitPlanes: { // k_grid_scatter.hip
+			ScatterPlan& plan = scatter_plan(n, stream, false);
+			const uint64_t* mask = (ctx.chunk_mask && ctx.n == n) ? ctx.chunk_mask.as<uint64_t>() : nullptr;
+			// The second filtered launch at this batch size is timed per task and the plan re-cut from the measured
+			// per-level work (grid_scatter_plan): one stream synchronisation, once per (encoding, batch size).
+			const bool tune = route.tune && !plan.tuned && mask && plan.n_tasks > 0 && ++plan.launches == 2;
+			DeviceBuf times;
+			if (tune) {
+				times.resize((size_t)plan.n_tasks * 8 * sizeof(uint64_t));
+				times.memset(0);
+			}
+			// (not in the step whose launch is timed for the tuner: the plan, ranges and scratch included, is rebuilt right after it)
+			const bool defer = !tune && take_prologue(route, offer, plan, grads, mode);
+			carried = grid_backward_lds(stream, m_meta, dev_meta(), plan.dev_tasks.as<GridScatterTask>(), plan.n_tasks, plan.dev_ranges.as<GridScatterRange>(), defer ? 0u : plan.n_ranges,
+			                            plan.scratch.as<uint64_t>(), n, x, dL_dy, dy_stride_sample, dy_stride_level, grads, mask, accumulate, route.dy == GridDyForm::Records,
+			                            tune ? times.as<uint64_t>() : nullptr, defer ? nullptr : offer.reduce_job) ||
+			          (defer && offer.reduce_job); // (it went with the prologue)
+			if (route.binned) { // levels cut into more than 64 chunks (k_grid_bin.hip)
+				ArenaBuf workspace{stream, grid_bin_workspace_bytes(m_meta, n)};
+				grid_backward_binned(stream, m_meta, dev_meta(), n, x, dL_dy, dy_stride_sample, dy_stride_level, grads, accumulate, workspace.data(), hit_counters(stream).fallbacks.as<uint32_t>());
+			}
+			if (tune) {
+				HIP_CHECK_THROW(hipStreamSynchronize(stream));
+				std::vector<uint64_t> h((size_t)plan.n_tasks * 8);
+				HIP_CHECK_THROW(hipMemcpy(h.data(), times.data(), h.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+				const std::vector<float> level_us = grid_scatter_level_costs(m_meta, plan.host_tasks, h);
+				build_scatter_plan(plan, n, &level_us);
+				plan.tuned = true;
+			}
+		} break;
 		}
 		if (dL_dx) {
 			CHECK_THROW(ctx.dy_dx);
-			CHECK_THROW(!dy_planes);
 			grid_backward_input(stream, m_meta, m_fp32, n, dL_dy, padded_output_width(), ctx.dy_dx.as<float>(), *dL_dx);
 		}
 		return carried;
@@ -714,38 +707,29 @@ public:
 		}
 	}
 
-	uint32_t level_plane_features(bool need_dL_dx, GradientMode mode) const override {
-		const uint32_t F = m_meta.n_features_per_level;
-		return (lds_scatter_usable() && !need_dL_dx && mode != GradientMode::Ignore) ? F : 0;
-	}
-
-	// The MLP kernel writes {coordinates, gradient} records and the scatter does one gather per hit instead of two: measured on
-	// C3a the scatter gains 12 us and the MLP kernel loses 6 us (4x the dX bytes).  TCNN_AMD_SCATTER_RECORDS=0 turns it off.
-	bool scatter_records_usable(MatView x) const override {
-		return !m_max_level_gpu && switches().scatter_records && lds_scatter_usable() && !m_any_binned && grid_scatter_records_supported(m_meta) && x.stride_dim == 1 && x.stride_sample == m_meta.n_pos_dims;
-	}
-
-	uint32_t scatter_record_planes() const override { return grid_scatter_record_planes(m_meta); }
-
-	// half precision, F >= 2, and every level's table either cut into at most 64 chunks (the sample filter) or binned
-	bool lds_scatter_usable() const { return !m_fp32 && m_meta.n_features_per_level >= 2 && use_lds_scatter() && m_scatter_levels_ok; }
-
-	// TCNN_AMD_GRID_SCATTER=atomic selects the reference-shaped global-atomic kernel (kept for A/B runs and as the fp32 / F==1 path)
-	static bool use_lds_scatter() { return switches().grid_scatter_lds; }
-
-	// The optimizer's launch has offered to run this backward pass's finalize pass (offer.prologue): hand it the shared ranges, their scratch
-	// and the reduce job.  Only where there is something to finish: shared ranges or the job.
-	bool take_prologue(const BackwardHandoff& offer, const GridScatterRange* dev_ranges, const std::vector<GridScatterRange>& ranges, uint64_t* scratch, void* grads, GradientMode mode) const {
+	// the tasks of a gradient kernel and what goes with them; like the kernels it owns device state a launch leaves behind for the next one on
+	// the same stream (the zeroed scratch table)
+	struct ScatterPlan {
+		DeviceBuf dev_tasks, dev_ranges, scratch;
+		std::vector<GridScatterTask> host_tasks;
+		std::vector<GridScatterRange> host_ranges;
+		uint32_t n_tasks = 0, n_ranges = 0;
+		uint32_t launches = 0;
+		bool lists = false; // the list-fed kernel's plan: static, nothing to tune
+		bool tuned = false;
+	};
+	// The optimizer's launch has offered to run this backward pass's finalize pass (offer.prologue): hand it the plan's shared ranges, their
+	// scratch and the reduce job.  Only where the route allows it and there is something to finish: shared ranges or the job.
+	bool take_prologue(const GridBackwardRoute& route, const BackwardHandoff& offer, const ScatterPlan& plan, void* grads, GradientMode mode) const {
 		AdamPrologue* p = offer.prologue;
-		if (!p || p->pending || (ranges.empty() && !offer.reduce_job) || m_any_binned) return false;
-		p->dev_ranges = dev_ranges;
-		p->ranges = ranges;
-		p->scratch = scratch;
+		if (!route.prologue || !p || p->pending || (plan.host_ranges.empty() && !offer.reduce_job)) return false;
+		p->dev_ranges = plan.dev_ranges.as<GridScatterRange>();
+		p->ranges = plan.host_ranges;
+		p->scratch = plan.scratch.as<uint64_t>();
 		p->grad_base = grads;
 		p->accumulate = mode == GradientMode::Accumulate;
-		p->has_reduce = false;
+		p->has_reduce = offer.reduce_job != nullptr;
 		if (offer.reduce_job) {
-			p->has_reduce = true;
 			p->reduce_elems = offer.reduce_job->n_elems;
 			p->reduce_slabs = offer.reduce_job->n_slabs;
 			p->slabs = offer.reduce_job->slabs;
@@ -755,90 +739,37 @@ public:
 		return true;
 	}
 
-	struct ScatterPlan {
-		DeviceBuf dev_tasks, dev_ranges, scratch;
-		std::vector<GridScatterTask> host_tasks;
-		std::vector<GridScatterRange> host_ranges;
-		uint32_t n_tasks = 0, n_ranges = 0;
-		uint32_t launches = 0;
-		bool tuned = false;
-	};
-	// TCNN_AMD_SCATTER_TUNE=0 keeps the untuned task list (A/B runs)
-	static bool scatter_tuning_enabled() { return switches().scatter_tune; }
-	// (re)builds the device-side plan; the caller guarantees that no launch using the old one is still running
+	// (re)builds the device-side plan -- the bit-plane kernel's tasks (grid_scatter_plan, re-cut once by the tuner) or the list-fed kernel's
+	// (grid_scatter_lists_plan); the caller guarantees that no launch using the old one is still running
 	void build_scatter_plan(ScatterPlan& plan, uint32_t n, const std::vector<float>* measured_level_us) {
-		std::vector<GridScatterRange> ranges;
 		size_t scratch_elems = 0;
-		grid_scatter_plan(m_meta, n, plan.host_tasks, ranges, scratch_elems, measured_level_us);
+		if (plan.lists) grid_scatter_lists_plan(m_meta, n, plan.host_tasks, plan.host_ranges, scratch_elems);
+		else grid_scatter_plan(m_meta, n, plan.host_tasks, plan.host_ranges, scratch_elems, measured_level_us);
 		plan.n_tasks = (uint32_t)plan.host_tasks.size();
-		plan.n_ranges = (uint32_t)ranges.size();
-		plan.host_ranges = ranges;
-		plan.dev_tasks.resize(plan.host_tasks.size() * sizeof(GridScatterTask));
-		if (!plan.host_tasks.empty()) HIP_CHECK_THROW(hipMemcpy(plan.dev_tasks.data(), plan.host_tasks.data(), plan.host_tasks.size() * sizeof(GridScatterTask), hipMemcpyHostToDevice));
-		plan.dev_ranges.resize(ranges.size() * sizeof(GridScatterRange));
-		if (!ranges.empty()) HIP_CHECK_THROW(hipMemcpy(plan.dev_ranges.data(), ranges.data(), ranges.size() * sizeof(GridScatterRange), hipMemcpyHostToDevice));
-		plan.scratch.resize(0);
-		plan.scratch.resize(scratch_elems * sizeof(uint64_t));
-		plan.scratch.memset(0); // the finalize pass leaves it zeroed again after every step
-	}
-	// One plan per (batch size, stream): a plan owns mutable device state -- the scratch table of the shared chunks, which a step
-	// leaves zeroed for the next one, and the task list the tuner replaces after a stream synchronisation -- so two streams that
-	// run backward passes of this encoding at the same time must not share one.  Steps on ONE stream are ordered and may.
-	ScatterPlan& scatter_plan(uint32_t n, hipStream_t stream) {
-		const auto key = std::make_pair(n, (const void*)stream);
-		auto it = m_scatter_plans.find(key);
-		if (it != m_scatter_plans.end()) return *it->second;
-		auto plan = std::make_unique<ScatterPlan>();
-		build_scatter_plan(*plan, n, nullptr);
-		return *(m_scatter_plans[key] = std::move(plan));
-	}
-
-	// the list-fed kernel's tasks (grid_scatter_lists_plan), per (batch size, stream, record form): like ScatterPlan it owns device state a
-	// launch leaves behind for the next one on the same stream (the zeroed scratch table)
-	struct ListsPlan {
-		DeviceBuf dev_tasks, dev_ranges, scratch;
-		std::vector<GridScatterRange> host_ranges;
-		uint32_t n_tasks = 0, n_ranges = 0;
-	};
-	ListsPlan& lists_plan(uint32_t n, hipStream_t stream) {
-		const auto key = std::make_pair(n, (const void*)stream);
-		auto it = m_lists_plans.find(key);
-		if (it != m_lists_plans.end()) return *it->second;
-		auto plan = std::make_unique<ListsPlan>();
-		std::vector<GridScatterTask> tasks;
-		std::vector<GridScatterRange> ranges;
-		size_t scratch_elems = 0;
-		grid_scatter_lists_plan(m_meta, n, tasks, ranges, scratch_elems);
-		plan->n_tasks = (uint32_t)tasks.size();
-		plan->n_ranges = (uint32_t)ranges.size();
-		plan->host_ranges = ranges;
+		plan.n_ranges = (uint32_t)plan.host_ranges.size();
 		auto upload = [](DeviceBuf& b, const void* src, size_t bytes) {
 			b.resize(bytes);
 			if (bytes) HIP_CHECK_THROW(hipMemcpy(b.data(), src, bytes, hipMemcpyHostToDevice));
 		};
-		upload(plan->dev_tasks, tasks.data(), tasks.size() * sizeof(GridScatterTask));
-		upload(plan->dev_ranges, ranges.data(), ranges.size() * sizeof(GridScatterRange));
-		plan->scratch.resize(scratch_elems * sizeof(uint64_t));
-		plan->scratch.memset(0); // the finalize pass leaves it zeroed again after every step
-		return *(m_lists_plans[key] = std::move(plan));
+		upload(plan.dev_tasks, plan.host_tasks.data(), plan.host_tasks.size() * sizeof(GridScatterTask));
+		upload(plan.dev_ranges, plan.host_ranges.data(), plan.host_ranges.size() * sizeof(GridScatterRange));
+		plan.scratch.resize(0);
+		plan.scratch.resize(scratch_elems * sizeof(uint64_t));
+		plan.scratch.memset(0); // the finalize pass leaves it zeroed again after every step
+	}
+	// One plan per (batch size, stream, kernel): a plan owns mutable device state -- the scratch table of the shared chunks, which a step
+	// leaves zeroed for the next one, and the task list the tuner replaces after a stream synchronisation -- so two streams that
+	// run backward passes of this encoding at the same time must not share one.  Steps on ONE stream are ordered and may.
+	ScatterPlan& scatter_plan(uint32_t n, hipStream_t stream, bool lists) {
+		const auto key = std::make_pair(n | (lists ? 0x80000000u : 0u), (const void*)stream); // (n itself is below 2^24 + 1)
+		auto it = m_scatter_plans.find(key);
+		if (it != m_scatter_plans.end()) return *it->second;
+		auto plan = std::make_unique<ScatterPlan>();
+		plan->lists = lists;
+		build_scatter_plan(*plan, n, nullptr);
+		return *(m_scatter_plans[key] = std::move(plan));
 	}
 
-	// Hit lists: TCNN_AMD_SCATTER_LISTS=0 keeps the bit planes (A/B runs, tests; read per step so that one process can cover both)
-	bool hit_lists_usable(uint32_t n) const {
-		const int want = switches().scatter_lists; // 0: never; 1: wherever the kernel can take the grid (tests); -1: where it pays (grid_scatter_prefers_lists)
-		if (want == 0) return false;
-		if (m_any_binned || n > grid_hit_max_samples(m_meta) || m_meta.n_pos_dims > 3 || m_meta.hash_type == (uint32_t)HashType::Rng) return false; // (Rng: its hash is a loop)
-		if (want == 1) return true;
-		// Where it pays: grids with levels of many chunks, at every batch size -- nothing in the list-fed form depends on what an L2 holds
-		// (round 4's gathered 16-byte records from one plane per XCD and was kept to 2^17 .. 2^19 samples).  C3a, step with lists / with
-		// bit planes in ms (profiles/r05_sweep.txt): 2^14 0.086 / 0.088, 2^16 0.120 / 0.128, 2^18 0.194 / 0.222, 2^20 0.474 / 0.584, 2^21 0.862 / 1.123.
-		// Below 2^16 samples a 2-D grid's bit planes are level with them or ahead -- two launches and 64 KiB of accumulators per task for a hundred
-		// elements; other 2-D grids at 2^12 / 2^14 / 2^16 (profiles/r05_shape_sweep.txt): T = 2^17 0.057 / 0.047, 0.056 / 0.051, 0.079 / 0.079;
-		// F = 4 0.063 / 0.034, 0.050 / 0.040, 0.060 / 0.058.  In 3-D the bit-plane form tests four rows per sample and chunk and loses everywhere
-		// (2^12: 0.098 / 0.147, 2^18: 0.33 / 1.44).
-		if (m_meta.n_pos_dims == 2 && n < (1u << 16)) return false;
-		return grid_scatter_prefers_lists(m_meta);
-	}
 	static size_t next_multiple_sz(size_t v, size_t m) { return (v + m - 1) / m * m; }
 	struct HitCounters {
 		DeviceBuf sets[2], fallbacks; // two sets of list tails [n_levels][GRID_HIT_COUNT_STRIDE]; how many tasks took the 64-bit passes
@@ -870,28 +801,6 @@ public:
 	}
 
 	uint64_t list_scatters() const override { return m_list_scatters; }
-
-	bool list_gradient_tail(hipStream_t stream, const EncodingContext& ctx, uint32_t n, const GridItemMap& map, GridListTail& tail, size_t& gvals_bytes) override {
-		// the very conditions under which backward() will run the list-fed kernel over all levels on the caller's dL/dy itself (a max_level
-		// cut-off masks or settles gradients around the kernels: the separate pass then)
-		const bool lists = ctx.hit_elems && ctx.n == n && n % 64 == 0 && ctx.hit_stream == (const void*)stream && hit_counters(stream).generation == ctx.hit_generation && lds_scatter_usable();
-		if (!lists || m_fp32 || m_meta.n_features_per_level != 2 || m_max_level_gpu || levels_on(true) != m_meta.n_levels) return false;
-		const GridHitLists& hl = ctx.hit_lists;
-		if (!(hl.map == map) || map.n_windows < 2 || hl.n_items * hl.item_samples != n) return false;
-		tail = GridListTail{};
-		tail.sidx = hl.sidx;
-		tail.heads = hl.heads;
-		tail.n_items = hl.n_items;
-		tail.item_capacity = hl.item_capacity;
-		tail.n_levels = m_meta.n_levels;
-		tail.map = map;
-		for (uint32_t l = 0; l < m_meta.n_levels; ++l) {
-			const GridLevel& lv = m_meta.levels[l];
-			if (lv.scatter_n_chunks > 1 && lv.scatter_n_chunks <= GRID_FILTER_MAX_CHUNKS && !lv.scatter_binned) tail.level_mask |= 1u << l;
-		}
-		gvals_bytes = grid_list_gradients_bytes(m_meta, hl);
-		return m_meta.n_levels <= 16 && hl.item_capacity <= 2048;
-	}
 
 	// grid_interface.h:101-123 (not part of the hyperparameters or snapshots, as there)
 	bool set_max_level(float max_level) override { m_max_level = max_level; return true; }
@@ -972,7 +881,6 @@ private:
 	DeviceBuf m_dev_meta;
 	std::map<std::pair<uint32_t, const void*>, std::unique_ptr<ScatterPlan>> m_scatter_plans;
 	std::map<const void*, std::unique_ptr<HitCounters>> m_hit_counters;
-	std::map<std::pair<uint32_t, const void*>, std::unique_ptr<ListsPlan>> m_lists_plans;
 	std::map<uint32_t, std::unique_ptr<PlanesPlan>> m_planes_plans;
 	bool m_scatter_levels_ok = true;
 	bool m_any_binned = false;
@@ -997,11 +905,11 @@ public:
 		const char* e = getenv("TCNN_AMD_FUSE_ONEBLOB");
 		return (!m_fp32 && m_n_bins >= 32 && !(e && e[0] == '0')) ? m_n_bins : 0;
 	}
-	EncodingContext forward(hipStream_t stream, uint32_t n, MatView x, const void* params, void* out, bool prepare_input_gradients, bool prepare_param_gradients) override {
+	EncodingContext forward(hipStream_t stream, uint32_t n, MatView x, const void* params, void* out, bool prepare_input_gradients, bool prepare_param_gradients, const ForwardPlan* plan) override {
 		if (out && padded_output_width() > 0) oneblob_forward(stream, m_fp32, n, m_n_dims, m_n_bins, x, out, padded_output_width());
 		return {};
 	}
-	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes, BackwardHandoff*) override {
+	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, const GridBackwardRoute&, BackwardHandoff*) override {
 		if (!dL_dx) return;
 		oneblob_backward_input(stream, m_fp32, n, m_n_dims, m_n_bins, x, dL_dy, padded_output_width(), *dL_dx);
 	}
@@ -1035,11 +943,11 @@ public:
 	EmptyEncoding(uint32_t n_dims_to_encode, bool fp32) : Encoding{fp32}, m_n_dims{n_dims_to_encode} {}
 	uint32_t input_width() const override { return m_n_dims; }
 	uint32_t output_width() const override { return 0; }
-	EncodingContext forward(hipStream_t stream, uint32_t n, MatView x, const void* params, void* out, bool prepare_input_gradients, bool prepare_param_gradients) override {
+	EncodingContext forward(hipStream_t stream, uint32_t n, MatView x, const void* params, void* out, bool prepare_input_gradients, bool prepare_param_gradients, const ForwardPlan* plan) override {
 		if (out && padded_output_width() > 0) identity_forward(stream, m_fp32, n, 0, 1.0f, 0.0f, x, out, padded_output_width()); // no live columns: all padding
 		return {};
 	}
-	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes, BackwardHandoff*) override {
+	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, const GridBackwardRoute&, BackwardHandoff*) override {
 		if (dL_dx) zero_input_gradient(stream, n, m_n_dims, *dL_dx);
 	}
 	// the output is constant: a zero tangent over the padding and no Hessian term
@@ -1092,15 +1000,14 @@ public:
 		const float range = m_variant == 3 ? 1e-4f : 0.7f;
 		generate_random_uniform(nullptr, rng.st, n_params(), params_full_precision, -range * scale, range * scale);
 	}
-	EncodingContext forward(hipStream_t stream, uint32_t n, MatView x, const void* params, void* out, bool prepare_input_gradients, bool prepare_param_gradients) override {
+	EncodingContext forward(hipStream_t stream, uint32_t n, MatView x, const void* params, void* out, bool prepare_input_gradients, bool prepare_param_gradients, const ForwardPlan* plan) override {
 		if (out && padded_output_width() > 0 && n > 0) {
 			if (m_variant == 3) ppng3_forward(stream, false, n, m_n_frequencies, m_n_quants, m_n_features, m_log2_min_freq, m_log2_max_freq, x, params, out, padded_output_width());
 			else (m_variant == 2 ? ppng2_forward : ppng1_forward)(stream, false, n, m_n_frequencies, m_n_quants, m_n_features, m_rank, m_log2_min_freq, m_log2_max_freq, x, params, out, padded_output_width());
 		}
 		return {};
 	}
-	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes, BackwardHandoff*) override {
-		CHECK_THROW(!dy_planes);
+	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, const GridBackwardRoute&, BackwardHandoff*) override {
 		if (dL_dx) {
 			// PPNG1 / PPNG2: the reference leaves dL_dinput untouched (ppng_1.h:268-321 never writes it); PPNG3: ppng_3.h:586-607
 			if (m_variant == 3 && padded_output_width() > 0) ppng3_backward_input(stream, false, n, m_n_frequencies, m_n_quants, m_n_features, m_log2_min_freq, m_log2_max_freq, x, params, dL_dy, padded_output_width(), *dL_dx);
@@ -1170,11 +1077,11 @@ public:
 		offset = m_offset;
 		return !m_fp32;
 	}
-	EncodingContext forward(hipStream_t stream, uint32_t n, MatView x, const void* params, void* out, bool prepare_input_gradients, bool prepare_param_gradients) override {
+	EncodingContext forward(hipStream_t stream, uint32_t n, MatView x, const void* params, void* out, bool prepare_input_gradients, bool prepare_param_gradients, const ForwardPlan* plan) override {
 		if (out && padded_output_width() > 0) identity_forward(stream, m_fp32, n, m_n_dims, m_scale, m_offset, x, out, padded_output_width());
 		return {};
 	}
-	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes, BackwardHandoff*) override {
+	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, const GridBackwardRoute&, BackwardHandoff*) override {
 		if (!dL_dx) return;
 		identity_backward_input(stream, m_fp32, n, m_n_dims, m_scale, dL_dy, padded_output_width(), *dL_dx);
 	}
@@ -1206,14 +1113,14 @@ public:
 	uint32_t input_width() const override { return m_n_dims; }
 	uint32_t outputs_per_input() const { return m_n_frequencies * (m_triangle ? 1u : 2u); }
 	uint32_t output_width() const override { return m_n_dims * outputs_per_input(); }
-	EncodingContext forward(hipStream_t stream, uint32_t n, MatView x, const void* params, void* out, bool prepare_input_gradients, bool prepare_param_gradients) override {
+	EncodingContext forward(hipStream_t stream, uint32_t n, MatView x, const void* params, void* out, bool prepare_input_gradients, bool prepare_param_gradients, const ForwardPlan* plan) override {
 		EncodingContext ctx;
 		if (!out || padded_output_width() == 0 || n == 0) return ctx;
 		if (prepare_input_gradients) ctx.dy_dx = ArenaBuf{stream, (size_t)n * output_width() * sizeof(float)};
 		periodic_forward(stream, m_triangle, m_fp32, n, m_n_dims, m_n_frequencies, x, out, padded_output_width(), ctx.dy_dx.as<float>());
 		return ctx;
 	}
-	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes, BackwardHandoff*) override {
+	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, const GridBackwardRoute&, BackwardHandoff*) override {
 		if (!dL_dx || n == 0) return;
 		CHECK_THROW(ctx.dy_dx); // frequency.h:150-152: needs a forward pass with prepare_input_gradients
 		periodic_backward_input(stream, m_fp32, n, m_n_dims, outputs_per_input(), dL_dy, padded_output_width(), ctx.dy_dx.as<float>(), *dL_dx);
@@ -1249,11 +1156,11 @@ public:
 	}
 	uint32_t input_width() const override { return 3; }
 	uint32_t output_width() const override { return m_degree * m_degree; }
-	EncodingContext forward(hipStream_t stream, uint32_t n, MatView x, const void* params, void* out, bool prepare_input_gradients, bool prepare_param_gradients) override {
+	EncodingContext forward(hipStream_t stream, uint32_t n, MatView x, const void* params, void* out, bool prepare_input_gradients, bool prepare_param_gradients, const ForwardPlan* plan) override {
 		if (out && padded_output_width() > 0) sh_forward(stream, m_fp32, n, m_degree, x, out, padded_output_width());
 		return {};
 	}
-	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes, BackwardHandoff*) override {
+	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, const GridBackwardRoute&, BackwardHandoff*) override {
 		if (!dL_dx) return;
 		sh_backward_input(stream, m_fp32, n, m_degree, x, dL_dy, padded_output_width(), *dL_dx);
 	}
@@ -1372,7 +1279,7 @@ public:
 			offset += e->n_params();
 		}
 	}
-	EncodingContext forward(hipStream_t stream, uint32_t n, MatView x, const void* params, void* out, bool prepare_input_gradients, bool prepare_param_gradients) override {
+	EncodingContext forward(hipStream_t stream, uint32_t n, MatView x, const void* params, void* out, bool prepare_input_gradients, bool prepare_param_gradients, const ForwardPlan* plan) override {
 		EncodingContext ctx;
 		if (!out || n == 0) return ctx;
 		const size_t elem = m_fp32 ? 4 : 2;
@@ -1404,9 +1311,9 @@ public:
 		}
 		return ctx;
 	}
-	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, bool dy_planes, BackwardHandoff*) override {
+	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, const GridBackwardRoute&, BackwardHandoff*) override {
 		if (n == 0) return;
-		CHECK_THROW(!dy_planes && ctx.nested.size() == m_nested.size());
+		CHECK_THROW(ctx.nested.size() == m_nested.size());
 		const size_t elem = m_fp32 ? 4 : 2;
 		// input dims no nested encoding looks at have zero gradient
 		if (dL_dx) zero_input_gradient(stream, n, m_n_dims, *dL_dx);
@@ -1423,8 +1330,8 @@ public:
 				const MatView xs{x.data + (size_t)m_begin[i] * x.stride_dim, x.stride_sample, x.stride_dim};
 				MatViewMut dxs{};
 				if (dL_dx) dxs = MatViewMut{dL_dx->data + (size_t)m_begin[i] * dL_dx->stride_dim, dL_dx->stride_sample, dL_dx->stride_dim};
-				e.backward(stream, ctx.nested[i], n, xs, (const char*)dnested.data() + i * block_bytes, dL_dx ? &dxs : nullptr, (const char*)params + p_off * elem,
-				           grads ? (char*)grads + p_off * elem : nullptr, mode, false);
+				e.backward_rows(stream, ctx.nested[i], n, xs, (const char*)dnested.data() + i * block_bytes, dL_dx ? &dxs : nullptr, (const char*)params + p_off * elem,
+				                grads ? (char*)grads + p_off * elem : nullptr, mode);
 				p_off += e.n_params();
 			}
 			return;
@@ -1437,7 +1344,7 @@ public:
 			const MatView xs{x.data + (size_t)m_begin[i] * x.stride_dim, x.stride_sample, x.stride_dim};
 			MatViewMut dxs{};
 			if (dL_dx) dxs = MatViewMut{dL_dx->data + (size_t)m_begin[i] * dL_dx->stride_dim, dL_dx->stride_sample, dL_dx->stride_dim};
-			e.backward(stream, ctx.nested[i], n, xs, block.data(), dL_dx ? &dxs : nullptr, (const char*)params + p_off * elem, grads ? (char*)grads + p_off * elem : nullptr, mode, false);
+			e.backward_rows(stream, ctx.nested[i], n, xs, block.data(), dL_dx ? &dxs : nullptr, (const char*)params + p_off * elem, grads ? (char*)grads + p_off * elem : nullptr, mode);
 			col += w;
 			p_off += e.n_params();
 		}
@@ -1542,8 +1449,8 @@ public:
 			MatViewMut dxs{};
 			if (dL_dx) dxs = slice_mut(dx_view, k);
 			const bool grads_k = want_grads && e.n_params() > 0;
-			e.backward(stream, ctx.nested[k], n, slice(x, k), (const char*)q.data() + k * block_bytes, dL_dx ? &dxs : nullptr, (const char*)params + p_off * elem,
-			           grads_k ? (char*)grads + p_off * elem : nullptr, grads_k ? GradientMode::Accumulate : GradientMode::Ignore, false);
+			e.backward_rows(stream, ctx.nested[k], n, slice(x, k), (const char*)q.data() + k * block_bytes, dL_dx ? &dxs : nullptr, (const char*)params + p_off * elem,
+			                grads_k ? (char*)grads + p_off * elem : nullptr, grads_k ? GradientMode::Accumulate : GradientMode::Ignore);
 			p_off += e.n_params();
 		}
 		if (dL_dx) add_input_gradient(stream, n, m_n_dims, MatView{dx_view.data, dx_view.stride_sample, dx_view.stride_dim}, *dL_dx);
@@ -2327,18 +2234,17 @@ public:
 		} else {
 			network_input = ArenaBuf{stream, (size_t)n * m_encoding->padded_output_width() * 2};
 			io.x_half = network_input.data();
-			io.x_plane_features = m_encoding->forward_plane_features(n);
-			if (io.x_plane_features) m_encoding->forward_planes(stream, n, input, p + m_network->n_params(), network_input.data(), false);
-			else m_encoding->forward(stream, n, input, p + m_network->n_params(), network_input.data(), false, false);
+			const ForwardPlan plan{m_encoding->forward_route(switches(), n, true, false, false)};
+			io.x_plane_features = plan.route.plane_features;
+			m_encoding->forward(stream, n, input, p + m_network->n_params(), network_input.data(), false, false, &plan);
 		}
 		m_network->inference_io(stream, n, io, p);
 	}
 
 	struct Ctx : public ModelContext {
-		ArenaBuf network_input;     // AoS [n][padded], or level planes when x_plane_f > 0
+		ArenaBuf network_input;     // AoS [n][padded], or level planes (encoding_ctx.route.plane_features > 0)
 		EncodingContext encoding_ctx;
 		NetworkContext network_ctx; // hidden activations; empty for fused contexts
-		uint32_t x_plane_f = 0;
 		bool fused = false;         // produced by fused_encode(): backward() goes through the fused MLP kernel
 		bool input_gradients = false; // forward() ran with prepare_input_gradients
 		uint32_t oneblob_bins = 0;  // > 0: no encoded batch was written -- the MLP kernels evaluate the OneBlob encoding of the input themselves
@@ -2358,7 +2264,7 @@ public:
 		if (n == 0) return ctx;
 		const _Float16* p = (const _Float16*)params;
 		if (!prepare_input_gradients && fused_step_supported(n)) {
-			fused_encode(stream, *ctx, n, input, params, false, true);
+			fused_encode(stream, *ctx, n, input, params, m_encoding->forward_route(switches(), n, true, false, true), false, true);
 			MlpIo io{};
 			if (ctx->oneblob_bins) {
 				io.x_f32 = input;
@@ -2366,7 +2272,7 @@ public:
 				io.x_oneblob_bins = ctx->oneblob_bins;
 			} else {
 				io.x_half = ctx->network_input.data();
-				io.x_plane_features = ctx->x_plane_f;
+				io.x_plane_features = ctx->encoding_ctx.route.plane_features;
 			}
 			io.out_half = output;
 			m_network->inference_io(stream, n, io, p);
@@ -2392,7 +2298,7 @@ public:
 			step.params = params;
 			step.gradients = gradients;
 			step.mode = mode;
-			fused_mlp_and_scatter(stream, ctx, n, input, step, OptimizerOffer{});
+			fused_mlp_and_scatter(stream, switches(), ctx, n, input, step, OptimizerOffer{});
 			return;
 		}
 		ArenaBuf dL_dnetwork_input;
@@ -2400,11 +2306,11 @@ public:
 			dL_dnetwork_input = ArenaBuf{stream, (size_t)n * m_encoding->padded_output_width() * 2};
 		}
 		// the grid scatter reads dL/d(encoding) with unit stride when the MLP writes it as level planes
-		const uint32_t plane_f = dL_dnetwork_input && !m_network->layerwise() ? m_encoding->level_plane_features(dL_dinput != nullptr, mode) : 0;
-		m_network->backward(stream, ctx.network_ctx, n, ctx.network_input.data(), output, dL_doutput, dL_dnetwork_input.data(), p, g, mode, plane_f);
+		const GridDyForm offer = dL_dnetwork_input && !m_network->layerwise() ? GridDyForm::Planes : GridDyForm::Rows;
+		const GridBackwardRoute route = m_encoding->backward_route(switches(), stream, ctx.encoding_ctx, n, input, offer, dL_dinput != nullptr, mode);
+		m_network->backward(stream, ctx.network_ctx, n, ctx.network_input.data(), output, dL_doutput, dL_dnetwork_input.data(), p, g, mode, route.plane_features);
 		if (dL_dnetwork_input) {
-			m_encoding->backward(stream, ctx.encoding_ctx, n, input, dL_dnetwork_input.data(), dL_dinput, p + m_network->n_params(),
-			                     g ? g + m_network->n_params() : nullptr, mode, plane_f > 0);
+			m_encoding->backward(stream, ctx.encoding_ctx, n, input, dL_dnetwork_input.data(), dL_dinput, p + m_network->n_params(), g ? g + m_network->n_params() : nullptr, mode, route);
 		}
 	}
 
@@ -2457,22 +2363,17 @@ public:
 			dx_more = ArenaBuf{stream, (size_t)n * m_encoding->input_width() * sizeof(float)};
 			dx_view.data = dx_more.as<float>();
 		}
-		m_encoding->backward(stream, ctx.encoding_ctx, n, input, q.data(), dL_dinput ? &dx_view : nullptr, p + n_net, enc_grads ? g + n_net : nullptr,
-		                     enc_grads ? GradientMode::Accumulate : GradientMode::Ignore, false);
+		m_encoding->backward_rows(stream, ctx.encoding_ctx, n, input, q.data(), dL_dinput ? &dx_view : nullptr, p + n_net, enc_grads ? g + n_net : nullptr,
+		                          enc_grads ? GradientMode::Accumulate : GradientMode::Ignore);
 		if (dL_dinput) add_input_gradient(stream, n, m_encoding->input_width(), MatView{dx_view.data, dx_view.stride_sample, dx_view.stride_dim}, *dL_dinput);
 	}
 
 	// TCNN_AMD_FUSED_STEP=0 selects the reference-shaped kernel sequence (forward / loss / backward / wgrad) for A/B runs
 	static bool use_fused_step() { return switches().fused_step; }
-	// TCNN_AMD_SIDE_JOBS=0: k_mlp_prep stays a launch of its own (A/B runs; read per step so that tests cover both)
-	static bool side_jobs_enabled() { return switches().side_jobs; }
 	bool fused_step_supported(uint32_t n) const { return use_fused_step() && !m_network->layerwise() && mlp_train_any_kernel(m_network->desc(), n); }
 	// exactly when the slab reduction of a fused step is a launch of its own that finishes EVERY gradient of the model, so that it can apply
 	// the optimizer's update behind it (OptimizerOffer::in_reduce): no encoding parameters, no dL/dinput asked for, gradients overwritten
 	bool reduction_carries_update(bool want_dL_dinput, GradientMode mode) const { return m_encoding->n_params() == 0 && !want_dL_dinput && mode == GradientMode::Overwrite; }
-	// TCNN_AMD_LIVE_IMAGE=0: every step builds its fragment images with k_mlp_prep again instead of keeping one current (Network::live_image;
-	// bit-identical, one ~4.5 us launch more per step of a model without encoding parameters)
-	static bool live_image_enabled() { return switches().live_image; }
 	bool live_image_kept() const { return m_live_image_kept; }           // the last fused step's optimizer launch left the live image current
 	void invalidate_live_image() { m_network->invalidate_live_image(); } // the parameters change(d) some other way
 	size_t image_preps() const { return m_image_preps; }                 // k_mlp_prep launches of fused steps so far (a test's view of the above)
@@ -2511,21 +2412,21 @@ public:
 		// The MLP kernel is known before the encoding runs (mlp_train_plan on the step's request): where its workgroups each produce one whole
 		// work item of a grid's hit lists, the grid forms its items from those samples and the kernel's tail stores dL/dy in list order itself
 		// (list_gradient_tails; TCNN_AMD_LISTGRAD_IN_MLP=0: k_grid_list_gradients as a launch of its own, items of consecutive samples).
+		const Switches sw = switches(); // one copy for the whole step
+		const GridForwardRoute route = m_encoding->forward_route(sw, n, true, step.dL_dinput != nullptr, step.mode != GradientMode::Ignore);
 		GridItemMap item_map;
-		bool mapped = false;
-		if (switches().listgrad_in_mlp && step.mode != GradientMode::Ignore && !step.dL_dinput && !m_network->layerwise() && m_encoding->n_params() > 0) {
-			const uint32_t x_plane_f = m_encoding->forward_plane_features(n), plane_f = m_encoding->level_plane_features(false, step.mode);
-			if (x_plane_f && plane_f) mapped = mlp_train_item_map(mlp_train_plan(m_network->desc(), step_request(n, step, x_plane_f, 0, true, plane_f, false)), item_map);
-		}
-		fused_encode(stream, *ctx, n, input, step.params, step.dL_dinput != nullptr, step.mode != GradientMode::Ignore, side_jobs_enabled(), mapped ? &item_map : nullptr);
+		const bool mapped = sw.listgrad_in_mlp && route.recorded == GridRecorded::HitLists && route.plane_features && // (hit lists: dL/dy will be plain level planes of that F)
+		                    mlp_train_item_map(mlp_train_plan(m_network->desc(), step_request(n, step, route.plane_features, 0, true, route.plane_features, false)), item_map);
+		fused_encode(stream, *ctx, n, input, step.params, route, step.dL_dinput != nullptr, step.mode != GradientMode::Ignore, sw.side_jobs, mapped ? &item_map : nullptr);
 		if (step.profile) step.profile->mark(stream, StepProfile::Encode, true);
-		fused_mlp_and_scatter(stream, *ctx, n, input, step, optimizer);
+		fused_mlp_and_scatter(stream, sw, *ctx, n, input, step, optimizer);
 		return ctx;
 	}
 
 	// first half of the fused step: the encoding, as level planes where the encoding can produce them
-	void fused_encode(hipStream_t stream, Ctx& ctx, uint32_t n, MatView input, const void* params, bool prepare_input_gradients, bool prepare_param_gradients, bool prep_image = false,
-	                  const GridItemMap* item_map = nullptr) {
+	// route: the encoding's forward_route(), asked as_planes by the caller (with its prepare_input_gradients / prepare_param_gradients)
+	void fused_encode(hipStream_t stream, Ctx& ctx, uint32_t n, MatView input, const void* params, const GridForwardRoute& route, bool prepare_input_gradients, bool prepare_param_gradients,
+	                  bool prep_image = false, const GridItemMap* item_map = nullptr) {
 		const _Float16* p = (const _Float16*)params;
 		const uint32_t n_net = (uint32_t)m_network->n_params();
 		if (m_network->layerwise()) throw std::runtime_error{"NetworkWithInputEncoding::fused_encode: a layer-by-layer network has no fused training step"};
@@ -2538,16 +2439,16 @@ public:
 		}
 		ctx.network_input = ArenaBuf{stream, (size_t)n * m_encoding->padded_output_width() * 2};
 		// grids hand the encoded batch over as level planes (XCD-aware forward kernel, scatter filter produced on the way)
-		ctx.x_plane_f = prepare_input_gradients ? 0 : m_encoding->forward_plane_features(n);
-		if (ctx.x_plane_f && prep_image) { // the forward kernel also builds the network's fragment images (k_mlp_prep as a side job)
+		ForwardPlan plan{route, nullptr, item_map};
+		MlpPrepJob job;
+		if (route.plane_features && prep_image) { // the forward kernel also builds the network's fragment images (k_mlp_prep as a side job)
 			ctx.image = ArenaBuf{stream, mlp_image_bytes(m_network->desc())};
-			MlpPrepJob job;
 			job.desc = m_network->desc();
 			job.params = params;
 			job.image = ctx.image.data();
-			ctx.encoding_ctx = m_encoding->forward_planes(stream, n, input, p + n_net, ctx.network_input.data(), prepare_param_gradients, &job, item_map);
-		} else if (ctx.x_plane_f) ctx.encoding_ctx = m_encoding->forward_planes(stream, n, input, p + n_net, ctx.network_input.data(), prepare_param_gradients, nullptr, item_map);
-		else ctx.encoding_ctx = m_encoding->forward(stream, n, input, p + n_net, ctx.network_input.data(), prepare_input_gradients, prepare_param_gradients);
+			plan.prep_job = &job;
+		}
+		ctx.encoding_ctx = m_encoding->forward(stream, n, input, p + n_net, ctx.network_input.data(), prepare_input_gradients, prepare_param_gradients, &plan);
 		ctx.fused = true;
 	}
 
@@ -2573,7 +2474,7 @@ public:
 
 	// second half: ONE MLP kernel (forward recomputed in registers, loss or external dL/doutput, backward, weight gradients),
 	// the slab reduction and the encoding's backward pass.
-	void fused_mlp_and_scatter(hipStream_t stream, const Ctx& ctx, uint32_t n, MatView input, const FusedStepData& step, const OptimizerOffer& optimizer) {
+	void fused_mlp_and_scatter(hipStream_t stream, const Switches& sw, const Ctx& ctx, uint32_t n, MatView input, const FusedStepData& step, const OptimizerOffer& optimizer) {
 		const void* params = step.params;
 		MatViewMut* dL_dinput = step.dL_dinput;
 		const GradientMode mode = step.mode;
@@ -2581,21 +2482,19 @@ public:
 		const _Float16* p = (const _Float16*)params;
 		_Float16* g = (_Float16*)step.gradients;
 		const uint32_t n_net = (uint32_t)m_network->n_params();
-		const uint32_t x_plane_f = ctx.x_plane_f;
 		const bool need_dx = m_encoding->n_params() > 0 || dL_dinput;
 		ArenaBuf dL_dnetwork_input;
-		const uint32_t plane_f = need_dx ? m_encoding->level_plane_features(dL_dinput != nullptr, mode) : 0;
-		// scatter records: the MLP kernel interleaves the samples' coordinates with dL/d(encoding) so that the grid scatter needs one gather per hit
-		// (not with hit lists: their elements carry entries and weights, the scatter gathers dL/dy alone from plain level planes)
-		const bool records = plane_f > 0 && !ctx.encoding_ctx.hit_elems && m_encoding->padded_output_width() == m_encoding->output_width() && m_encoding->scatter_records_usable(input);
-		if (need_dx) dL_dnetwork_input = ArenaBuf{stream, records ? (size_t)n * m_encoding->scatter_record_planes() * 16 : (size_t)n * m_encoding->padded_output_width() * 2};
+		// how the encoding's backward pass will run, and with it the form the MLP kernel writes dL/d(encoding) in: asked once, here
+		const GridBackwardRoute route = need_dx ? m_encoding->backward_route(sw, stream, ctx.encoding_ctx, n, input, GridDyForm::Records, dL_dinput != nullptr, mode) : GridBackwardRoute{};
+		const bool records = route.dy == GridDyForm::Records;
+		if (need_dx) dL_dnetwork_input = ArenaBuf{stream, records ? (size_t)n * route.record_planes * 16 : (size_t)n * m_encoding->padded_output_width() * 2};
 
 		const MlpDesc& d = m_network->desc();
 		// a model whose only parameters are the network's: the optimizer's update rides on the slab reduction (k_wgrad_reduce_adam), which
 		// then also keeps the network's live image current (Network::live_image)
 		const bool with_adam = optimizer.in_reduce != nullptr;
 		CHECK_THROW(!with_adam || reduction_carries_update(dL_dinput != nullptr, mode)); // the caller's decision binds
-		Network::LiveImage* live = with_adam && !ctx.image && live_image_enabled() ? m_network->live_image() : nullptr;
+		Network::LiveImage* live = with_adam && !ctx.image && sw.live_image ? m_network->live_image() : nullptr;
 		m_live_image_kept = false;
 		ArenaBuf prepared;
 		const void* image_data;
@@ -2612,7 +2511,7 @@ public:
 			image_data = prepared.data();
 		}
 		// which kernel, and over how many workgroups: decided once, here (mlp_train_plan); each workgroup writes one weight-gradient slab
-		const MlpTrainRequest request = step_request(n, step, x_plane_f, ctx.oneblob_bins, need_dx, plane_f, records);
+		const MlpTrainRequest request = step_request(n, step, ctx.encoding_ctx.route.plane_features, ctx.oneblob_bins, need_dx, route.plane_features, records);
 		const MlpTrainPlan plan = mlp_train_plan(d, request);
 		if (!plan.ok) throw std::runtime_error{"NetworkWithInputEncoding: no fused training kernel for this network, batch and set of options"};
 		CHECK_THROW(g != nullptr || !request.gradients);
@@ -2631,18 +2530,14 @@ public:
 		args.slabs = slabs.as<float>();
 		args.n_params = n_net;
 		// the kernel's tail stores dL/dy in the order of the grid's hit lists where the forward pass formed its items from this plan's workgroups
-		GridListTail list_tail;
+		GridListTail list_tail = route.list_tail;
 		ArenaBuf list_gradients;
-		{
-			GridItemMap item_map;
-			size_t gvals_bytes = 0;
-			if (need_dx && !dL_dinput && request.gradients && !records && plane_f > 0 && switches().listgrad_in_mlp && mlp_train_item_map(plan, item_map) &&
-			    m_encoding->list_gradient_tail(stream, ctx.encoding_ctx, n, item_map, list_tail, gvals_bytes)) {
-				list_gradients = ArenaBuf{stream, gvals_bytes};
-				list_tail.gvals = list_gradients.data();
-				args.list_tail = &list_tail;
-				++m_list_gradient_tails;
-			}
+		GridItemMap item_map;
+		if (route.tail && mlp_train_item_map(plan, item_map) && item_map == list_tail.map) {
+			list_gradients = ArenaBuf{stream, route.tail_bytes};
+			list_tail.gvals = list_gradients.data();
+			args.list_tail = &list_tail;
+			++m_list_gradient_tails;
 		}
 		if (profile) profile->mark(stream, StepProfile::MlpKernel, false);
 		mlp_train_launch(stream, d, plan, args);
@@ -2655,7 +2550,6 @@ public:
 		// become one); otherwise, or with TCNN_AMD_SIDE_JOBS=0, it is a launch of its own.
 		MlpReduceJob reduce_job;
 		BackwardHandoff offer; // to the encoding's backward pass
-		offer.dy_records = records;
 		offer.prologue = optimizer.prologue;
 		offer.list_gradients = list_gradients.data();
 		if (mode != GradientMode::Ignore) {
@@ -2664,7 +2558,7 @@ public:
 			reduce_job.slabs = slabs.as<float>();
 			reduce_job.grad = g;
 			reduce_job.accumulate = mode == GradientMode::Accumulate ? 1 : 0;
-			if (!(need_dx && side_jobs_enabled())) {
+			if (!(need_dx && sw.side_jobs)) {
 				AdamInReduce adam_here;
 				if (with_adam) {
 					adam_here = *optimizer.in_reduce;
@@ -2682,7 +2576,7 @@ public:
 		}
 		if (need_dx) {
 			if (profile) profile->mark(stream, StepProfile::EncodingBackward, false);
-			m_encoding->backward(stream, ctx.encoding_ctx, n, input, dL_dnetwork_input.data(), dL_dinput, p + n_net, g ? g + n_net : nullptr, mode, plane_f > 0, &offer);
+			m_encoding->backward(stream, ctx.encoding_ctx, n, input, dL_dnetwork_input.data(), dL_dinput, p + n_net, g ? g + n_net : nullptr, mode, route, &offer);
 			if (offer.reduce_job) {
 				if (!offer.reduce_carried) mlp_reduce_slabs(stream, n_net, n_slabs, slabs.as<float>(), g, mode == GradientMode::Accumulate);
 				else if (offer.prologue && offer.prologue->pending && offer.prologue->has_reduce) ctx.slabs_kept = std::move(slabs); // read by the optimizer's launch
@@ -2741,7 +2635,7 @@ public:
 	              MatViewMut* dL_dinput, const void* params, void* gradients, GradientMode mode) override {
 		check_batch(n);
 		const Ctx& ctx = dynamic_cast<const Ctx&>(mctx);
-		m_encoding->backward(stream, ctx.encoding_ctx, n, input, dL_doutput, dL_dinput, params, gradients, mode, false);
+		m_encoding->backward_rows(stream, ctx.encoding_ctx, n, input, dL_doutput, dL_dinput, params, gradients, mode);
 	}
 	void backward_backward_input(hipStream_t stream, const ModelContext& mctx, uint32_t n, MatView input, MatView dL_ddLdinput, const void* dL_doutput,
 	                             void* dL_ddLdoutput, MatViewMut* dL_dinput, const void* params, void* gradients, GradientMode mode) override {

@@ -41,8 +41,8 @@ inline uint32_t div_round_up(uint32_t v, uint32_t d) { return (v + d - 1) / d; }
 // The A/B switches of the training step and of inference (DESIGN.md "Switches"): every one defaults to the fast path, none changes a result
 // beyond what is stated there.  They are read from the environment when create_from_config / a module constructor runs (switches_reload,
 // capi.cpp) -- not per step -- and the set is PROCESS-WIDE: creating a model under another environment changes the kernels of every live
-// model from its next call on (reads and the reload are serialised by a lock).  A process that wants another setting sets the variable and
-// creates its models afterwards; tests that compare two settings build one model at a time.
+// model from its next pass on (reads and the reload are serialised by a lock; a grid's backward pass follows its forward pass: GridForwardRoute).
+// A process that wants another setting sets the variable and creates its models afterwards; tests that compare two settings build one model at a time.
 struct Switches {
 	bool grid_planes = true;      // TCNN_AMD_GRID_PLANES=0: the AoS forward kernel inside the fused training step
 	bool grid_rows_planes = true; // TCNN_AMD_GRID_ROWS_PLANES=0: callers that want the encoded batch as a matrix get k_grid_fwd (AoS) instead of the plane kernel + a transposition
@@ -253,6 +253,112 @@ bool grid_scatter_finalize(hipStream_t stream, const GridScatterRange* dev_range
 // store_dx_record; D = 2 with F = 2 packs two levels into one record); x is then not read
 bool grid_scatter_records_supported(const GridMeta& meta);
 uint32_t grid_scatter_record_planes(const GridMeta& meta);
+
+// ---- The grid encoding's two routes: how a batch is produced and how its parameter gradients are accumulated, each decided ONCE per pass by
+// a pure host function (no GPU call, no environment, no switches(): the Switches set is an argument).  The forward route is kept in the
+// EncodingContext and the backward route FOLLOWS IT, whatever the process-wide switches say by the time the backward pass runs.
+struct GridFacts { // what a GridEncoding knows from its construction (and its padding) on
+	const GridMeta* meta;
+	bool fp32, scatter_levels_ok, any_binned; // levels_ok: every level is cut into at most GRID_FILTER_MAX_CHUNKS chunks or binned (k_grid_bin.hip)
+	uint32_t n_to_pad;                        // padding features behind the levels'
+};
+enum class GridForwardKernel : uint32_t { Rows, Planes, PlanesToRows }; // k_grid_fwd (AoS); k_grid_fwd_planes; the latter + a transposition into rows
+enum class GridRecorded : uint32_t { Nothing, BitPlanes, HitLists };    // what the forward pass leaves for the gradient kernel
+struct GridForwardRoute {
+	bool planned = false; // false: a default-constructed context -- its backward route is planned from the switches of that moment
+	GridForwardKernel kernel = GridForwardKernel::Rows;
+	GridRecorded recorded = GridRecorded::Nothing;
+	bool lds = false;            // a later backward pass with parameter gradients runs the LDS owner-computes kernels, else the global-atomic one
+	uint32_t plane_features = 0; // Planes: the encoded batch is level planes [padded / F][n][F] of this F
+};
+// half precision, F >= 2, every level's table cut into at most 64 chunks (the sample filter) or binned; TCNN_AMD_GRID_SCATTER=atomic: never
+inline bool grid_lds_gradients(const GridFacts& g, const Switches& sw, uint32_t n) {
+	return !g.fp32 && g.meta->n_features_per_level >= 2 && sw.grid_scatter_lds && g.scatter_levels_ok && n % 64 == 0;
+}
+// Hit lists instead of bit planes: TCNN_AMD_SCATTER_LISTS=0 never, =1 wherever the kernel can take the grid (tests), unset where it pays
+inline bool grid_hit_lists_wanted(const GridFacts& g, const Switches& sw, uint32_t n) {
+	const GridMeta& meta = *g.meta;
+	if (sw.scatter_lists == 0) return false;
+	if (g.any_binned || n > grid_hit_max_samples(meta) || meta.n_pos_dims > 3 || meta.hash_type == (uint32_t)HashType::Rng) return false; // (Rng: its hash is a loop)
+	if (sw.scatter_lists == 1) return true;
+	// Where it pays (DESIGN.md "Batch sizes", "Away from the BASELINE configurations"; profiles/r05_sweep.txt, r05_shape_sweep.txt): grids with
+	// levels of many chunks, at every batch size; below 2^16 samples a 2-D grid's bit planes are level with the lists or ahead, in 3-D they lose everywhere
+	if (meta.n_pos_dims == 2 && n < (1u << 16)) return false;
+	return grid_scatter_prefers_lists(meta);
+}
+// as_planes: the caller takes the encoded batch as level planes where the grid can write them (the fused step, fused inference), else it
+// wants the matrix [n][padded].  The plane kernel writes no dy_dx: input gradients keep the AoS kernel.
+inline GridForwardRoute grid_forward_route(const GridFacts& g, const Switches& sw, uint32_t n, bool as_planes, bool input_gradients, bool param_gradients) {
+	const GridMeta& meta = *g.meta;
+	const uint32_t F = meta.n_features_per_level;
+	GridForwardRoute r;
+	r.planned = true;
+	r.lds = grid_lds_gradients(g, sw, n);
+	// (a padded encoding -- 12 levels x 2 features in front of a 16-aligned network -- has whole planes of zeros behind its levels' planes)
+	const bool planes = !input_gradients && !g.fp32 && sw.grid_planes && g.n_to_pad % F == 0 && grid_planes_supported(meta, n);
+	if (planes && as_planes) r.kernel = GridForwardKernel::Planes;
+	else if (planes && sw.grid_rows_planes && grid_planes_to_rows_supported(meta, n, meta.n_levels * F + g.n_to_pad)) r.kernel = GridForwardKernel::PlanesToRows;
+	if (r.kernel == GridForwardKernel::Planes) r.plane_features = F;
+	if (param_gradients && r.lds) r.recorded = (r.kernel != GridForwardKernel::Rows && grid_hit_lists_wanted(g, sw, n)) ? GridRecorded::HitLists : GridRecorded::BitPlanes;
+	return r;
+}
+
+enum class GridDyForm : uint32_t { Rows, Planes, Records }; // dL/dy as [n][padded]; level planes [padded / F][n][F]; 16-byte records {coordinates, gradients}
+enum class GridGradientKernel : uint32_t { None, Atomic, AtomicScratch32, BitPlanes, Lists }; // BitPlanes: k_grid_scatter (unfiltered where nothing was recorded)
+enum class GridMaxLevel : uint32_t { None, Scalar, PerSample };                               // the max_level state when the backward pass runs
+struct GridBackwardRoute { // the default: dL/dy as rows, nothing else -- every encoding but the grid
+	GridDyForm dy = GridDyForm::Rows;
+	uint32_t plane_features = 0, record_planes = 0; // Planes, Records: the F of [padded / F][n][F]; Records: 16-byte records per sample (grid_scatter_record_planes)
+	GridGradientKernel kernel = GridGradientKernel::None;
+	// binned: k_grid_bin.hip follows for the levels cut into more than 64 chunks; tune: the bit-plane kernel's plan may be re-cut from a timed launch
+	// (TCNN_AMD_SCATTER_TUNE); prologue: the finalize pass may be left to the optimizer's launch where that offers it (AdamPrologue)
+	bool binned = false, tune = false, prologue = false;
+	// the fused MLP kernel's tail may store dL/dy in list order itself where its workgroups' samples are the lists' items (mlp_train_item_map() ==
+	// list_tail.map): what it needs for that, all but gvals -- the caller's workspace of tail_bytes, handed back as BackwardHandoff::list_gradients
+	bool tail = false;
+	GridListTail list_tail;
+	size_t tail_bytes = 0;
+};
+// fwd, lists_current: the context's forward route, and whether its hit lists are still their stream's latest (GridEncoding::lists_current)
+// offer: the richest form the caller can deliver dL/dy in -- Rows (a caller's own network), Planes (the unfused network kernels), Records (the fused step)
+inline GridBackwardRoute grid_backward_route(const GridFacts& g, const Switches& sw, const GridForwardRoute& fwd, bool lists_current, uint32_t n, GridDyForm offer, bool want_dL_dx,
+                                             GradientMode mode, GridMaxLevel max_level, bool x_contiguous) {
+	const GridMeta& meta = *g.meta;
+	const uint32_t F = meta.n_features_per_level;
+	GridBackwardRoute r;
+	if (mode == GradientMode::Ignore) return r;
+	if (!(fwd.planned ? fwd.lds : grid_lds_gradients(g, sw, n))) { // the reference-shaped kernel; half with F == 1 accumulates in fp32 (grid.h:660)
+		r.kernel = (!g.fp32 && F == 1) ? GridGradientKernel::AtomicScratch32 : GridGradientKernel::Atomic;
+		return r;
+	}
+	// LDS owner-computes scatter with exact integer accumulation.  Stale lists (a later forward pass took their counters): the unfiltered bit-plane kernel.
+	const bool lists = fwd.recorded == GridRecorded::HitLists && lists_current;
+	r.kernel = lists ? GridGradientKernel::Lists : GridGradientKernel::BitPlanes;
+	r.binned = !lists && g.any_binned;
+	r.tune = !lists && sw.scatter_tune;
+	// (not under a scalar cut-off: the off levels' gradients are settled after the kernels, and the optimizer's own launch sees every parameter)
+	r.prologue = max_level != GridMaxLevel::Scalar && !g.any_binned;
+	if (offer == GridDyForm::Rows || want_dL_dx) return r;
+	r.dy = GridDyForm::Planes, r.plane_features = F;
+	// Scatter records: the MLP kernel interleaves the coordinates with dL/d(encoding) and the scatter does one gather per hit instead of two (C3a: the scatter gains
+	// 12 us, the MLP kernel loses 6 to 4x the dX bytes).  Not with hit lists, current or stale (their elements carry entries and weights), nor with a per-sample max_level.
+	if (offer == GridDyForm::Records && fwd.recorded != GridRecorded::HitLists && g.n_to_pad == 0 && max_level != GridMaxLevel::PerSample && sw.scatter_records && !g.any_binned &&
+	    grid_scatter_records_supported(meta) && x_contiguous) {
+		r.dy = GridDyForm::Records, r.record_planes = grid_scatter_record_planes(meta);
+		return r;
+	}
+	// (a max_level cut-off masks or settles gradients around the kernels: k_grid_list_gradients as a pass of its own then)
+	r.tail = offer == GridDyForm::Records && lists && F == 2 && max_level == GridMaxLevel::None && sw.listgrad_in_mlp && meta.n_levels <= 16 &&
+	         (grid_hit_item_samples(meta) << (meta.n_pos_dims - 1)) <= 2048;
+	if (r.tail) {
+		r.list_tail.n_levels = meta.n_levels;
+		for (uint32_t l = 0; l < meta.n_levels; ++l) {
+			const GridLevel& lv = meta.levels[l];
+			if (lv.scatter_n_chunks > 1 && lv.scatter_n_chunks <= GRID_FILTER_MAX_CHUNKS && !lv.scatter_binned) r.list_tail.level_mask |= 1u << l;
+		}
+	}
+	return r;
+}
 
 // ---- PPNG1 (k_ppng.hip; encodings/ppng_1.h): features half [F][2][3][C][Q][R]; out / dL_dy AoS with row stride out_stride;
 // scratch: uint64[n_params], zero on entry, zero again on return (exact integer sums of the fp16 products, rounded once)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """usage (GPU box): python tools/r05_shape_sweep.py [--steps 40] > profiles/...txt
 
-Does the dispatch between the grid gradient kernels (model.h `hit_lists_usable` -> k_grid_scatter.hip `grid_scatter_prefers_lists`; the
+Does the dispatch between the grid gradient kernels (tcnn_common.h `grid_hit_lists_wanted` -> k_grid_scatter.hip `grid_scatter_prefers_lists`; the
 binned form per level in `grid_scatter_setup_levels`) hold on grids OTHER than the bench's?  For each shape: the training step of
 HashGrid + 64x2 FullyFusedMLP + RelativeL2 + Adam at 2^18 samples with the default dispatch, with hit lists wherever the kernel can take
 the grid (TCNN_AMD_SCATTER_LISTS=1) and with bit planes only (=0), one process per run (the switches are read once per process).
