@@ -25,6 +25,7 @@ ACT = {"none": 0, "relu": 1, "leakyrelu": 2, "exponential": 3, "sine": 4, "sigmo
 GRID_TYPE = {"hash": 0, "dense": 1, "tiled": 2}
 HASH_TYPE = {"prime": 0, "coherentprime": 1, "reversedprime": 2, "rng": 3}
 INTERP = {"nearest": 0, "linear": 1, "smoothstep": 2}
+PRODUCT_FP32, PRODUCT_SCRATCH32, PRODUCT_HALF = 0, 1, 2  # how orc_grid_backward_terms forms one contribution
 LOSS = {"l2": 0, "relativel2": 1, "l1": 2, "relativel1": 3, "mape": 4, "smape": 5, "crossentropy": 6, "variance": 7, "relativel2luminance": 8}
 ACC_FP32, ACC_FP16 = 0, 1
 MAX_LEVELS = 128
@@ -90,6 +91,9 @@ def lib():
             "orc_grid_backward_input": (None, [vp, u32, vp, u32, vp, vp]),
             "orc_grid_backward_backward_input": (None, [vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]),
             "orc_grid_backward_exact": (None, [vp, u32, vp, vp, u32, vp, C.c_int]),
+            "orc_grid_forward_f32": (None, [vp, u32, vp, vp, vp, u32, vp, vp]),
+            "orc_grid_backward_input_f32": (None, [vp, u32, vp, u32, vp, vp]),
+            "orc_grid_backward_terms": (None, [vp, u32, vp, vp, u32, u32, vp, vp, vp, vp]),
             "orc_oneblob_forward": (None, [u32, u32, u32, vp, vp, u32]), "orc_oneblob_backward_input": (None, [u32, u32, u32, vp, vp, u32, vp]),
             "orc_identity_forward": (None, [u32, u32, f32, f32, vp, vp, u32]), "orc_identity_backward_input": (None, [u32, u32, f32, vp, u32, vp]),
             "orc_frequency_forward": (None, [u32, u32, u32, vp, vp, u32, vp]), "orc_trianglewave_forward": (None, [u32, u32, u32, vp, vp, u32, vp]),
@@ -299,6 +303,41 @@ class GridEncoding:
         dL_dy = np.ascontiguousarray(dL_dy)
         lib().orc_grid_backward_exact(C.byref(self.g), x.shape[0], _p(x), _p(dL_dy), dL_dy.shape[1], _p(grad_half), int(accumulate))
         return grad_half
+
+    # --- the reference's T = float instantiation (fp32 grids) and the terms of the atomic gradient kernels
+    def forward_f32(self, x, params_f32, want_indices=False, want_dy_dx=False):
+        """grid.h:49-212 with T = float.  params_f32: float32[n_params]; returns (float32 [n][padded], ctx) like forward()."""
+        n = x.shape[0]
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        params_f32 = np.ascontiguousarray(params_f32, dtype=np.float32)
+        assert params_f32.shape == (self.n_params,)
+        out = np.empty((n, self.padded_output_width), dtype=np.float32)
+        idx = np.empty((n, self.g.n_levels, 1 << self.n_in), dtype=np.uint32) if want_indices else None
+        dy_dx = np.empty((n, self.n_output_dims, self.n_in), dtype=np.float32) if want_dy_dx else None
+        lib().orc_grid_forward_f32(C.byref(self.g), n, _p(x), _p(params_f32), _p(out), out.shape[1], _p(idx), _p(dy_dx))
+        return out, {"dy_dx": dy_dx, "indices": idx}
+
+    def backward_input_f32(self, ctx, dL_dy):
+        """grid.h:323-349 with T = float.  dL_dy: float32 [n][>= n_output_dims]; ctx from forward_f32(want_dy_dx=True)."""
+        dL_dy = np.ascontiguousarray(dL_dy, dtype=np.float32)
+        n = dL_dy.shape[0]
+        dL_dx = np.empty((n, self.n_in), dtype=np.float32)
+        lib().orc_grid_backward_input_f32(C.byref(self.g), n, _p(dL_dy), dL_dy.shape[1], _p(ctx["dy_dx"]), _p(dL_dx))
+        return dL_dx
+
+    def backward_terms(self, x, dL_dy, product):
+        """grid.h:215-320 without the additions' order: per parameter the double sum of the contributions, the double sum of their
+        magnitudes and their count; product (PRODUCT_FP32 / _SCRATCH32 / _HALF) selects how a contribution is formed and the type of
+        dL_dy (float32 for PRODUCT_FP32, half bits otherwise).  Also the smallest non-zero magnitude among all contributions."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        dL_dy = np.ascontiguousarray(dL_dy)
+        assert dL_dy.dtype == (np.float32 if product == PRODUCT_FP32 else np.uint16) and dL_dy.shape[1] >= self.n_output_dims
+        s = np.empty(self.n_params, dtype=np.float64)
+        a = np.empty(self.n_params, dtype=np.float64)
+        k = np.empty(self.n_params, dtype=np.uint32)
+        smallest = C.c_double(0.0)
+        lib().orc_grid_backward_terms(C.byref(self.g), x.shape[0], _p(x), _p(dL_dy), dL_dy.shape[1], int(product), _p(s), _p(a), _p(k), C.byref(smallest))
+        return {"sum": s, "abs_sum": a, "hits": k, "min_nonzero": float(smallest.value)}
 
     def hyperparams(self):
         r = {"otype": "Grid", "type": ["Hash", "Dense", "Tiled"][self.g.grid_type], "n_levels": int(self.g.n_levels),

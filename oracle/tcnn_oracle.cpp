@@ -262,6 +262,44 @@ inline float quartic_cdf(float x, float inv_radius) {
 	return fmaxf(0.0f, fminf(1.0f, ((float)15 / 16) * u * (1 - ((float)2 / 3) * u2 + ((float)1 / 5) * u4) + 0.5f));
 }
 
+// one level at one sample: cell and fraction per dimension, then the 2^D corners in the order of grid.h:147-160 (Nearest: the cell, weight 1)
+struct LevelWalk {
+	const orc_grid_t* g;
+	uint32_t level, hashmap_size, resolution;
+	float scale;
+	float pos[8], pos_derivative[8];
+	uint32_t pos_grid[8];
+
+	LevelWalk(const orc_grid_t* g_, uint32_t level_, const float* xrow) : g{g_}, level{level_} {
+		hashmap_size = g->offsets[level + 1] - g->offsets[level];
+		resolution = g->resolutions[level];
+		scale = g->scales[level];
+		for (uint32_t dim = 0; dim < g->n_pos_dims; ++dim) pos_grid[dim] = pos_fract(xrow[dim], scale, g->interpolation, &pos[dim], &pos_derivative[dim]);
+	}
+	uint32_t index(const uint32_t* local) const { return grid_index(g->n_pos_dims, g->hash_type, g->grid_type, hashmap_size, resolution, local); }
+	template <typename Fn> void corners(Fn&& fn) const { // fn(corner number, entry index, fp32 weight)
+		const uint32_t D = g->n_pos_dims;
+		if (g->interpolation == ORC_INTERP_NEAREST) {
+			fn(0u, index(pos_grid), 1.0f);
+			return;
+		}
+		for (uint32_t idx = 0; idx < (1u << D); ++idx) {
+			float weight = 1;
+			uint32_t local[8];
+			for (uint32_t dim = 0; dim < D; ++dim) {
+				if ((idx & (1u << dim)) == 0) {
+					weight *= 1 - pos[dim];
+					local[dim] = pos_grid[dim];
+				} else {
+					weight *= pos[dim];
+					local[dim] = pos_grid[dim] + 1;
+				}
+			}
+			fn(idx, index(local), weight);
+		}
+	}
+};
+
 struct MlpLayout {
 	std::vector<uint32_t> rows, cols;
 	std::vector<size_t> offset;
@@ -618,6 +656,111 @@ void orc_grid_backward_input(const orc_grid_t* g, uint32_t n, const uint16_t* dL
 		}
 		for (uint32_t d = 0; d < D; ++d) dL_dx[(size_t)i * D + d] = result[d];
 	}
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// T = float instantiation of grid.h: fp32 grids, and what an atomic gradient kernel adds before the order of the additions matters
+// ---------------------------------------------------------------------------------------------------------
+void orc_grid_forward_f32(const orc_grid_t* g, uint32_t n, const float* x, const float* grid, float* out, uint32_t out_stride,
+                          uint32_t* indices, float* dy_dx) {
+	const uint32_t D = g->n_pos_dims, F = g->n_features_per_level, L = g->n_levels;
+	const uint32_t n_corners = 1u << D;
+#pragma omp parallel for schedule(static)
+	for (uint32_t i = 0; i < n; ++i) {
+		for (uint32_t level = 0; level < L; ++level) {
+			const float* lgrid = grid + (size_t)g->offsets[level] * F;
+			const LevelWalk w{g, level, x + (size_t)i * D};
+			float* o = out ? out + (size_t)i * out_stride + level * F : nullptr;
+			float* dyl = dy_dx ? dy_dx + ((size_t)i * L * F + level * F) * D : nullptr;
+
+			// grid.h:121-169: Nearest copies the entry; else fma((T)weight, value, result) with T = float, in corner order
+			float result[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+			w.corners([&](uint32_t idx, uint32_t index, float weight) {
+				if (indices) indices[((size_t)i * L + level) * n_corners + idx] = index;
+				for (uint32_t f = 0; f < F; ++f) {
+					const float v = lgrid[(size_t)index * F + f];
+					result[f] = g->interpolation == ORC_INTERP_NEAREST ? v : fmaf(weight, v, result[f]);
+				}
+			});
+			if (o) for (uint32_t f = 0; f < F; ++f) o[f] = result[f];
+
+			if (dyl) { // grid.h:172-211 (zeros for Nearest, grid.h:132-137)
+				for (uint32_t k = 0; k < F * D; ++k) dyl[k] = 0.0f;
+				if (g->interpolation == ORC_INTERP_NEAREST) continue;
+				for (uint32_t grad_dim = 0; grad_dim < D; ++grad_dim) {
+					for (uint32_t idx = 0; idx < (1u << (D - 1)); ++idx) {
+						float weight = w.scale;
+						uint32_t local[8];
+						for (uint32_t ngd = 0; ngd < D - 1; ++ngd) {
+							const uint32_t dim = ngd >= grad_dim ? (ngd + 1) : ngd;
+							if ((idx & (1u << ngd)) == 0) {
+								weight *= 1 - w.pos[dim];
+								local[dim] = w.pos_grid[dim];
+							} else {
+								weight *= w.pos[dim];
+								local[dim] = w.pos_grid[dim] + 1;
+							}
+						}
+						local[grad_dim] = w.pos_grid[grad_dim];
+						const uint32_t il = w.index(local);
+						local[grad_dim] = w.pos_grid[grad_dim] + 1;
+						const uint32_t ir = w.index(local);
+						for (uint32_t f = 0; f < F; ++f) {
+							dyl[f * D + grad_dim] += weight * (lgrid[(size_t)ir * F + f] - lgrid[(size_t)il * F + f]) * w.pos_derivative[grad_dim];
+						}
+					}
+				}
+			}
+		}
+		if (out) for (uint32_t j = L * F; j < out_stride; ++j) out[(size_t)i * out_stride + j] = 0.0f; // grid.h:749-758
+	}
+}
+
+void orc_grid_backward_input_f32(const orc_grid_t* g, uint32_t n, const float* dL_dy, uint32_t dy_stride, const float* dy_dx, float* dL_dx) {
+	const uint32_t D = g->n_pos_dims, NF = g->n_levels * g->n_features_per_level;
+#pragma omp parallel for schedule(static)
+	for (uint32_t i = 0; i < n; ++i) {
+		float result[8] = {0};
+		for (uint32_t k = 0; k < NF; ++k) {
+			const float dl = dL_dy[(size_t)i * dy_stride + k];
+			for (uint32_t d = 0; d < D; ++d) result[d] += dl * dy_dx[((size_t)i * NF + k) * D + d];
+		}
+		for (uint32_t d = 0; d < D; ++d) dL_dx[(size_t)i * D + d] = result[d];
+	}
+}
+
+void orc_grid_backward_terms(const orc_grid_t* g, uint32_t n, const float* x, const void* dL_dy, uint32_t dy_stride, uint32_t product,
+                             double* sum, double* abs_sum, uint32_t* hits, double* min_nonzero) {
+	const uint32_t D = g->n_pos_dims, F = g->n_features_per_level, L = g->n_levels;
+	for (size_t k = 0; k < g->n_params; ++k) { sum[k] = 0.0; abs_sum[k] = 0.0; hits[k] = 0; }
+	double smallest = std::numeric_limits<double>::infinity();
+	// levels are independent; inside a level the rows come in order, so the double sums are reproducible
+#pragma omp parallel for schedule(dynamic, 1) reduction(min : smallest)
+	for (uint32_t level = 0; level < L; ++level) {
+		const size_t base = (size_t)g->offsets[level] * F;
+		for (uint32_t i = 0; i < n; ++i) {
+			const LevelWalk w{g, level, x + (size_t)i * D};
+			const size_t at = (size_t)i * dy_stride + level * F;
+			w.corners([&](uint32_t, uint32_t index, float weight) {
+				for (uint32_t f = 0; f < F; ++f) {
+					double term;
+					if (product == ORC_PRODUCT_FP32) {
+						term = (double)(weight * ((const float*)dL_dy)[at + f]);
+					} else if (product == ORC_PRODUCT_SCRATCH32) {
+						term = (double)(weight * h2f(((const uint16_t*)dL_dy)[at + f]));
+					} else {
+						term = (double)h2f(hmul(f2h(weight), ((const uint16_t*)dL_dy)[at + f]));
+					}
+					const size_t k = base + (size_t)index * F + f;
+					sum[k] += term;
+					abs_sum[k] += std::fabs(term);
+					hits[k] += 1;
+					if (term != 0.0 && std::fabs(term) < smallest) smallest = std::fabs(term);
+				}
+			});
+		}
+	}
+	if (min_nonzero) *min_nonzero = smallest;
 }
 
 // Second-order terms of dL/dx = sum_k dL_dy_k * dy_k/dx (GridEncodingTemplated::backward_backward_input_impl, grid.h:902-1026):

@@ -102,6 +102,24 @@ void orc_grid_backward_input(const orc_grid_t* g, uint32_t n, const uint16_t* dL
 void orc_grid_backward_backward_input(const orc_grid_t* g, uint32_t n, const float* x, const float* dL_ddLdx, const uint16_t* dL_dy, uint32_t dy_stride,
                                       const uint16_t* grid, const float* dy_dx, uint16_t* grad, float* grad_f32, uint16_t* dL_ddLdy, float* dL_dx);
 
+/* ---- the reference's T = float instantiation of grid.h (fp32 grids, and the fp32 scratch of F = 1 half grids) ---- */
+/* grid.h:49-212 with T = float: the weight product in fp32 in dimension order, fmaf(weight, value, acc) in corner order; Nearest copies
+ * the entry; columns >= L*F are written 0.  x, out, indices, dy_dx laid out as in orc_grid_forward; dy_dx comes from the fp32 entries. */
+void orc_grid_forward_f32(const orc_grid_t* g, uint32_t n, const float* x, const float* grid, float* out, uint32_t out_stride,
+                          uint32_t* indices, float* dy_dx);
+/* grid.h:323-349 with T = float: the summation order of orc_grid_backward_input */
+void orc_grid_backward_input_f32(const orc_grid_t* g, uint32_t n, const float* dL_dy, uint32_t dy_stride, const float* dy_dx, float* dL_dx);
+/* grid.h:215-320, every atomic form: what is added to a parameter, without the order-dependent addition itself.  product selects how one
+ * contribution is formed (grid.h:254 for the three instantiations of T / GRAD_T):
+ *   ORC_PRODUCT_FP32       weight * dy in fp32, dL_dy float [n][dy_stride]              (T = GRAD_T = float)
+ *   ORC_PRODUCT_SCRATCH32  weight * (float)dy in fp32, dL_dy half [n][dy_stride]        (T = half, GRAD_T = float: F = 1, grid.h:660)
+ *   ORC_PRODUCT_HALF       (half)weight * dy in fp16, dL_dy half [n][dy_stride]         (T = GRAD_T = half)
+ * Per parameter: sum (the contributions added in double), abs_sum (their magnitudes added in double), hits (how many there were, zero
+ * ones included).  min_nonzero (optional, one double): the smallest magnitude among the non-zero contributions, +inf without any. */
+enum { ORC_PRODUCT_FP32 = 0, ORC_PRODUCT_SCRATCH32 = 1, ORC_PRODUCT_HALF = 2 };
+void orc_grid_backward_terms(const orc_grid_t* g, uint32_t n, const float* x, const void* dL_dy, uint32_t dy_stride, uint32_t product,
+                             double* sum, double* abs_sum, uint32_t* hits, double* min_nonzero);
+
 /* ---- OneBlob (oneblob.h:47-164, definition form) and Identity (identity.h:46-85) ---- */
 void orc_oneblob_forward(uint32_t n, uint32_t n_dims, uint32_t n_bins, const float* x, uint16_t* out, uint32_t out_stride);
 void orc_oneblob_backward_input(uint32_t n, uint32_t n_dims, uint32_t n_bins, const float* x, const uint16_t* dL_dy, uint32_t dy_stride, float* dL_dx);

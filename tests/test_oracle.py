@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 
 from conftest import CONFIG_C1, CONFIG_C2, CONFIG_C3A, CONFIG_C3B
+from grid_reference import (MIN_CONTRIBUTION, REFERENCE_KERNEL_CASES, U16, U32, case_id, check_rounded_sum_per_level, check_sum_per_level,
+                            level_slices, reference_inputs, summation_bound)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 KAT = json.load(open(os.path.join(HERE, "golden", "reference_kat.json")))
@@ -97,6 +99,14 @@ def test_hash_and_grid_index_known_answers(oracle):
         size = int(g.offsets[lv + 1] - g.offsets[lv])
         got = L.orc_grid_index(2, 1, 0, size, int(g.resolutions[lv]), cell.ctypes.data)
         assert got == want, (level, got, want)  # levels 12 and 15 exercise the uint32 stride wrap-around quirk
+    # ReversedPrime (common_device.h:657-661: the Prime factors in reverse order), by hand from the constants, uint32 wrap-around:
+    #   3 * 2165219737 = 2200691915, 5 * 1434869437 = 2879379889, 7 * 2097192037 = 1795442371 (mod 2^32)
+    #   2200691915 ^ 2879379889 = 682900858;  682900858 ^ 1795442371 = 1135639481
+    reversed_prime = oracle.HASH_TYPE["reversedprime"]
+    assert L.orc_grid_hash(2, reversed_prime, np.array([3, 5], dtype=np.uint32).ctypes.data) == 682900858
+    assert L.orc_grid_hash(3, reversed_prime, np.array([3, 5, 7], dtype=np.uint32).ctypes.data) == 1135639481
+    #   1 * 2165219737 ^ 2 * 1434869437 ^ 3 * 2097192037 ^ 4 * 3674653429 (mod 2^32) = 823706136
+    assert L.orc_grid_hash(4, reversed_prime, np.array([1, 2, 3, 4], dtype=np.uint32).ctypes.data) == 823706136
     fr = C.c_float()
     pk = KAT["pos_fract"]
     assert L.orc_pos_fract(pk["input"], pk["scale"], 1, C.byref(fr), None) == pk["cell"] and fr.value == pk["frac"]
@@ -181,6 +191,182 @@ def test_grid_forward_against_numpy_restatement(oracle):
     res0 = int(g.resolutions[0])
     c = np.floor((np.float32(g.scales[0]) * x + np.float32(0.5)).astype(np.float32)).astype(np.int64)
     assert np.array_equal(ctx["indices"][:, 0, 0], (c[:, 0] + c[:, 1] * res0) % 256)
+
+
+# ------------------------------------------------------------------------------------------------- the fp32 grid oracle
+class _Float64Grid:
+    """Independent float64 restatement of grid.h:49-349 for one case of REFERENCE_KERNEL_CASES.  Cell, fraction and the fraction's derivative
+    come from orc_pos_fract, entry indices from forward_f32(want_indices): only the interpolation and the gradients are restated here."""
+
+    def __init__(self, oracle, case):
+        n_in, cfg = case
+        self.ref = ref = oracle.create_encoding(n_in, cfg, alignment=0)
+        self.x, self.params, self.dy = reference_inputs(oracle, ref)
+        n, D, L, F = self.x.shape[0], n_in, ref.g.n_levels, ref.g.n_features_per_level
+        self.out32, ctx = ref.forward_f32(self.x, self.params, want_indices=True, want_dy_dx=True)
+        self.ctx = ctx
+        self.nearest = ref.g.interpolation == oracle.INTERP["nearest"]
+        Lib = oracle.lib()
+        frac = np.empty((L, n, D))
+        dfrac = np.empty((L, n, D))
+        f, df = C.c_float(), C.c_float()
+        for lv in range(L):
+            scale = float(ref.scales[lv])
+            for i in range(n):
+                for d in range(D):
+                    Lib.orc_pos_fract(float(self.x[i, d]), scale, int(ref.g.interpolation), C.byref(f), C.byref(df))
+                    frac[lv, i, d], dfrac[lv, i, d] = f.value, df.value
+        self.frac, self.dfrac = frac, dfrac
+        table = self.params.astype(np.float64).reshape(-1, F)
+        corners = 1 if self.nearest else 1 << D
+        # weights [L][n][corner], global entry rows [L][n][corner]
+        self.w = np.ones((L, n, corners))
+        if not self.nearest:
+            for c in range(corners):
+                for d in range(D):
+                    self.w[:, :, c] *= frac[:, :, d] if (c >> d) & 1 else 1.0 - frac[:, :, d]
+        self.rows = np.stack([ctx["indices"][:, lv, :corners].astype(np.int64) + int(ref.offsets[lv]) for lv in range(L)])
+        v = table[self.rows]  # [L][n][corner][F]
+        terms = self.w[..., None] * v
+        self.out = terms.sum(axis=2).transpose(1, 0, 2).reshape(n, L * F)
+        self.out_abs = np.abs(terms).sum(axis=2).transpose(1, 0, 2).reshape(n, L * F)
+        # dy/dx [n][L*F][D] and the sum of the magnitudes of its terms (grid.h:172-211)
+        self.dy_dx = np.zeros((n, L * F, D))
+        self.dy_dx_abs = np.zeros((n, L * F, D))
+        if not self.nearest:
+            for lv in range(L):
+                scale = float(ref.scales[lv])
+                for gd in range(D):
+                    for c in range(corners):
+                        if (c >> gd) & 1:
+                            continue  # the left corner of each pair along gd
+                        wgt = np.full(n, scale)
+                        for d in range(D):
+                            if d != gd:
+                                wgt = wgt * (frac[lv, :, d] if (c >> d) & 1 else 1.0 - frac[lv, :, d])
+                        t = wgt[:, None] * (v[lv, :, c | (1 << gd), :] - v[lv, :, c, :]) * dfrac[lv, :, gd][:, None]
+                        self.dy_dx[:, lv * F : (lv + 1) * F, gd] += t
+                        self.dy_dx_abs[:, lv * F : (lv + 1) * F, gd] += np.abs(t)
+
+    def gradient_terms(self, dy):
+        """(sum, abs_sum, hits) per parameter of w * dy in float64, dy [n][L*F] float64"""
+        ref = self.ref
+        L, F = ref.g.n_levels, ref.g.n_features_per_level
+        n = self.x.shape[0]
+        S, A, K = np.zeros(ref.n_params), np.zeros(ref.n_params), np.zeros(ref.n_params, dtype=np.int64)
+        for lv in range(L):
+            for f in range(F):
+                t = self.w[lv] * dy[:, lv * F + f][:, None]  # [n][corner]
+                at = self.rows[lv] * F + f
+                np.add.at(S, at, t)
+                np.add.at(A, at, np.abs(t))
+                np.add.at(K, at, 1)
+        assert n * self.w.shape[2] * L * F == int(K.sum())
+        return S, A, K
+
+
+_FLOAT64_GRIDS = {}
+
+
+def _float64_grid(oracle, case):
+    key = case_id(case)
+    if key not in _FLOAT64_GRIDS:
+        _FLOAT64_GRIDS[key] = _Float64Grid(oracle, case)
+    return _FLOAT64_GRIDS[key]
+
+
+@pytest.mark.parametrize("case", REFERENCE_KERNEL_CASES, ids=case_id)
+def test_grid_f32_oracle_against_float64_restatement(oracle, case):
+    """orc_grid_forward_f32 (output and dy_dx), orc_grid_backward_input_f32 and orc_grid_backward_terms against float64, each within the
+    roundings the fp32 expression has: the count stands next to each assertion."""
+    r = _float64_grid(oracle, case)
+    ref, D = r.ref, case[0]
+    NF = ref.n_output_dims
+    # forward: a weight is D - 1 products of D factors of which each may carry the rounding of (1 - pos): at most 2 D - 1 roundings;
+    # the fmaf chain rounds once per corner: 2^D; one unit to spare for the second-order terms.  Nearest copies: no rounding at all.
+    if r.nearest:
+        assert np.array_equal(r.out32.astype(np.float64), r.out)
+    else:
+        assert np.all(np.abs(r.out32.astype(np.float64) - r.out) <= (2 * D + (1 << D)) * U32 * r.out_abs)
+    # dy_dx: per term the weight (scale times D - 1 factors: D - 1 products, D - 1 roundings of (1 - pos)), the difference (1), two more
+    # products (2): 2 D + 1; the running sum of 2^(D - 1) terms: 2^(D - 1); one to spare
+    n_dy_dx = 2 * D + 1 + (1 << (D - 1)) + 1
+    assert np.all(np.abs(r.ctx["dy_dx"].astype(np.float64) - r.dy_dx) <= n_dy_dx * U32 * r.dy_dx_abs)
+    if r.nearest:
+        assert not np.any(r.ctx["dy_dx"])
+    # dL/dx = sum_k dL/dy_k * dy_k/dx: the roundings of dy_k/dx above, one product and NF additions per term; one to spare
+    got = ref.backward_input_f32(r.ctx, r.dy)
+    dy64 = r.dy.astype(np.float64)[:, :NF]
+    want = np.einsum("nk,nkd->nd", dy64, r.dy_dx)
+    abs_terms = np.einsum("nk,nkd->nd", np.abs(dy64), r.dy_dx_abs)
+    n_dl_dx = n_dy_dx + 1 + NF + 1
+    assert np.all(np.abs(got.astype(np.float64) - want) <= n_dl_dx * U32 * abs_terms)
+    assert np.any(want != 0) or r.nearest
+    # contributions to dL/dparams: weight (2 D - 1 roundings) times dL/dy (1): 2 D roundings each, one to spare
+    dy_h = oracle.half_bits(r.dy)
+    for product, dy_used in ((oracle.PRODUCT_FP32, r.dy), (oracle.PRODUCT_SCRATCH32, dy_h)):
+        t = ref.backward_terms(r.x, dy_used, product)
+        dy_values = (r.dy if product == oracle.PRODUCT_FP32 else oracle.half_to_f32(dy_h)).astype(np.float64)
+        S, A, K = r.gradient_terms(dy_values[:, :NF])
+        assert np.array_equal(t["hits"].astype(np.int64), K)
+        assert np.all(np.abs(t["sum"] - S) <= (2 * D + 1) * U32 * A)  # every contribution within its own roundings ...
+        assert np.all(np.abs(t["sum"] - S) <= t["hits"] * (2 * D + 1) * U32 * t["abs_sum"])  # ... which implies the coarser form
+        assert np.all(np.abs(t["abs_sum"] - A) <= (2 * D + 1) * U32 * A)
+        assert t["min_nonzero"] >= MIN_CONTRIBUTION  # what the GPU tests of these cases rely on
+
+
+@pytest.mark.parametrize("case", REFERENCE_KERNEL_CASES, ids=case_id)
+def test_grid_f32_oracle_against_half_oracle(oracle, case):
+    """With half-representable parameters the fp32 grid and the half grid differ by the half one's roundings only; the terms of the
+    packed-fp16 form, rounded once, ARE the exact half gradient; the F = 1 half gradient lies in the interval the GPU test uses."""
+    n_in, cfg = case
+    ref = oracle.create_encoding(n_in, cfg, alignment=0)
+    x, params, dy = reference_inputs(oracle, ref)
+    params_h, dy_h = oracle.half_bits(params), oracle.half_bits(dy)
+    params_r = oracle.half_to_f32(params_h)
+    out32, _ = ref.forward_f32(x, params_r)
+    out16, _ = ref.forward(x, params_h)
+    abs_terms, _ = ref.forward_f32(x, np.abs(params_r))  # the weights are >= 0: sum_c |w_c v_c|
+    rounded = oracle.half_to_f32(oracle.half_bits(out32)).astype(np.float64)
+    # one rounding per corner of the half grid's hfma chain: 2^D
+    assert np.all(np.abs(rounded - oracle.half_to_f32(out16).astype(np.float64)) <= (1 << n_in) * U16 * abs_terms.astype(np.float64))
+    if ref.g.interpolation == oracle.INTERP["nearest"]:
+        assert np.array_equal(oracle.half_bits(out32), out16)
+
+    t = ref.backward_terms(x, dy_h, oracle.PRODUCT_HALF)
+    exact = np.zeros(ref.n_params, dtype=np.uint16)
+    ref.backward_exact(x, dy_h, exact)
+    assert np.array_equal(t["sum"].astype(np.float16).view(np.uint16), exact)
+    assert np.array_equal(np.array([oracle.lib().orc_double_to_half(float(v)) for v in t["sum"][:: max(1, ref.n_params // 997)]], dtype=np.uint16),
+                          exact[:: max(1, ref.n_params // 997)])
+    # the 5 % cap of the packed-fp16 test: entries whose gamma(k - 1) is undefined at u = 2^-11
+    if ref.g.n_features_per_level >= 2:
+        for level, sl in enumerate(level_slices(ref)):
+            hit = t["hits"][sl] > 0
+            assert np.count_nonzero(~np.isfinite(summation_bound(t, U16)[sl]) & hit) <= 0.05 * np.count_nonzero(hit), level
+    else:
+        seq = np.zeros(ref.n_params, dtype=np.uint16)
+        ref.backward(x, {}, dy_h, grad_half=seq)
+        check_rounded_sum_per_level(ref, seq, ref.backward_terms(x, dy_h, oracle.PRODUCT_SCRATCH32), label=case_id(case))
+
+
+def test_summation_bound_is_what_it_says(oracle):
+    """gamma(k - 1) * A on a hand-made case, and check_sum_per_level's verdicts on values placed just inside and just outside it."""
+    ref = oracle.create_encoding(2, {"otype": "DenseGrid", "n_levels": 1, "n_features_per_level": 1, "base_resolution": 2, "per_level_scale": 2.0}, alignment=0)
+    terms = {"sum": np.zeros(ref.n_params), "abs_sum": np.zeros(ref.n_params), "hits": np.zeros(ref.n_params, dtype=np.uint32)}
+    terms["sum"][:3], terms["abs_sum"][:3], terms["hits"][:3] = (1.0, 3.0, -2.0), (1.0, 5.0, 8.0), (1, 3, 2049)
+    e = summation_bound(terms, U32)
+    assert e[0] == 0.0 and e[1] == 2 * U32 / (1 - 2 * U32) * 5.0 and e[3] == 0.0
+    assert np.isinf(summation_bound(terms, U16)[2]) and np.isfinite(summation_bound(terms, U32)[2])
+    inside = terms["sum"].copy()
+    inside[1] += 0.999 * e[1]
+    assert check_sum_per_level(ref, (inside, inside.view(np.uint64)), terms, U32)[0][1] == pytest.approx(0.999, rel=1e-6)
+    for wrong in (np.where(np.arange(ref.n_params) == 1, 3.0 + 1.001 * e[1], terms["sum"]), np.where(np.arange(ref.n_params) == 0, np.nextafter(1.0, 2.0), terms["sum"]),
+                  np.where(np.arange(ref.n_params) == 5, -0.0, terms["sum"])):
+        with pytest.raises(AssertionError):
+            check_sum_per_level(ref, (wrong, wrong.view(np.uint64)), terms, U32)
+    with pytest.raises(AssertionError):  # 2049 hits have no fp16 bound: one of three hit entries is more than 5 %
+        check_sum_per_level(ref, (terms["sum"], terms["sum"].view(np.uint64)), terms, U16, max_excluded=0.05)
 
 
 def test_grid_backward_modes_agree(oracle):

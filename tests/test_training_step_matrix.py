@@ -12,6 +12,7 @@ import pytest
 
 from conftest import CONFIG_C2, CONFIG_C3A, CONFIG_C3B, CONFIG_C5_SMALL
 from grad_checks import assert_structural_zeros, assert_weight_grads_close, layer_slices, subnormal_share
+from grid_reference import edge_x
 from test_gpu_parity import _bits, _exact_external_dy, _f32, _linear_net_params, _t, elem_close, rel_err
 from test_losses import _assert_fused_loss_close
 
@@ -377,15 +378,6 @@ ENC_DX_CASES = [  # (n_in, encoding)
 ]
 
 
-def _edge_x(n, n_in):
-    specials = [0.0, 1.0, np.nextafter(np.float32(1.0), np.float32(0.0)), 0.5, -0.25, 1.5, 1e-8, 0.999]
-    x = np.zeros((n, n_in), dtype=np.float32)
-    for i in range(n):
-        for d in range(n_in):
-            x[i, d] = specials[(i // len(specials) ** d) % len(specials)]
-    return x
-
-
 @pytest.mark.parametrize("dtype", ["half", "float"])
 @pytest.mark.parametrize("n_in,enc_cfg", ENC_DX_CASES)
 def test_grid_input_gradient_through_encoding(tcnn, oracle, n_in, enc_cfg, dtype):
@@ -399,7 +391,7 @@ def test_grid_input_gradient_through_encoding(tcnn, oracle, n_in, enc_cfg, dtype
     ref = oracle.create_encoding(n_in, enc_cfg, alignment=0)
     params_h = oracle.half_bits(oracle.Pcg32(3).uniform_strided(ref.n_params, -1.0, 1.0))
     n = 1024
-    x = np.concatenate([oracle.Pcg32(42).uniform_strided((n - 256) * n_in).reshape(n - 256, n_in), _edge_x(256, n_in)]).astype(np.float32)
+    x = np.concatenate([oracle.Pcg32(42).uniform_strided((n - 256) * n_in).reshape(n - 256, n_in), edge_x(256, n_in)]).astype(np.float32)
     width = enc.n_output_dims
     dy = oracle.half_bits(oracle.Pcg32(9).uniform_strided(n * width, -2.0, 2.0).reshape(n, width))
     _, ctx = ref.forward(x, params_h, want_dy_dx=True)
