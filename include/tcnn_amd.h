@@ -88,6 +88,13 @@ int tcnn_generate_random_uniform(tcnn_stream_t stream, uint64_t rng_state_inc[2]
 int  tcnn_create_network_with_input_encoding(uint32_t n_input_dims, uint32_t n_output_dims, const char* encoding_json, const char* network_json, tcnn_module_t* out);
 int  tcnn_create_network(uint32_t n_input_dims, uint32_t n_output_dims, const char* network_json, tcnn_module_t* out);
 int  tcnn_create_encoding(uint32_t n_input_dims, const char* encoding_json, int precision, tcnn_module_t* out);
+/* The two network factories with the module's precision as an argument (TCNN_PRECISION_*; the two above are the FP16 case).  FP32 is the
+ * reference's build without TCNN_HALF_PRECISION as a choice per module: the encoding in its fp32 form in front of a CutlassMLP<float>
+ * that runs layer by layer.  params, output, dL_doutput, dL_dparams and dL_ddLdoutput of such a module are float, and
+ * tcnn_module_param_precision / tcnn_module_output_precision answer TCNN_PRECISION_FP32 (tcnn_preferred_precision() stays FP16).  "otype":
+ * "FullyFusedMLP" with FP32 reports "FullyFusedMLP can only be used if the network precision is set to __half." (network.cu:102-103). */
+int  tcnn_create_network_with_input_encoding_precision(uint32_t n_input_dims, uint32_t n_output_dims, const char* encoding_json, const char* network_json, int precision, tcnn_module_t* out);
+int  tcnn_create_network_precision(uint32_t n_input_dims, uint32_t n_output_dims, const char* network_json, int precision, tcnn_module_t* out);
 void tcnn_module_destroy(tcnn_module_t module);
 
 /* ---- Module methods, cpp_api.h:91-106 / cpp_api.cu:72-139 ----

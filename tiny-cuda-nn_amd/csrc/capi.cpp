@@ -164,19 +164,29 @@ void tcnn_set_log_callback(void (*callback)(int, const char*, void*), void* user
 	log_sink().user = user;
 }
 
-int tcnn_create_network_with_input_encoding(uint32_t n_input_dims, uint32_t n_output_dims, const char* encoding_json, const char* network_json, tcnn_module_t* out) {
+int tcnn_create_network_with_input_encoding_precision(uint32_t n_input_dims, uint32_t n_output_dims, const char* encoding_json, const char* network_json, int precision, tcnn_module_t* out) {
 	switches_reload(); // the A/B switches are read once per model (tcnn_common.h: Switches)
 	return guarded([&] {
 		CHECK_THROW(out != nullptr);
+		if (precision != TCNN_PRECISION_FP32 && precision != TCNN_PRECISION_FP16) throw std::runtime_error{"Unknown precision " + std::to_string(precision)};
 		auto m = std::make_unique<tcnn_module_s>();
-		m->model.reset(new NetworkWithInputEncoding{n_input_dims, n_output_dims, parse_or_empty(encoding_json), parse_or_empty(network_json)});
+		m->model.reset(new NetworkWithInputEncoding{n_input_dims, n_output_dims, parse_or_empty(encoding_json), parse_or_empty(network_json),
+		                                            precision == TCNN_PRECISION_FP32 ? Precision::Fp32 : Precision::Fp16});
 		*out = m.release();
 	});
 }
 
-int tcnn_create_network(uint32_t n_input_dims, uint32_t n_output_dims, const char* network_json, tcnn_module_t* out) {
+int tcnn_create_network_with_input_encoding(uint32_t n_input_dims, uint32_t n_output_dims, const char* encoding_json, const char* network_json, tcnn_module_t* out) {
+	return tcnn_create_network_with_input_encoding_precision(n_input_dims, n_output_dims, encoding_json, network_json, TCNN_PRECISION_FP16, out);
+}
+
+int tcnn_create_network_precision(uint32_t n_input_dims, uint32_t n_output_dims, const char* network_json, int precision, tcnn_module_t* out) {
 	// cpp_api.cu:151-153: Identity encoding + network
-	return tcnn_create_network_with_input_encoding(n_input_dims, n_output_dims, "{\"otype\": \"Identity\"}", network_json, out);
+	return tcnn_create_network_with_input_encoding_precision(n_input_dims, n_output_dims, "{\"otype\": \"Identity\"}", network_json, precision, out);
+}
+
+int tcnn_create_network(uint32_t n_input_dims, uint32_t n_output_dims, const char* network_json, tcnn_module_t* out) {
+	return tcnn_create_network_precision(n_input_dims, n_output_dims, network_json, TCNN_PRECISION_FP16, out);
 }
 
 int tcnn_create_encoding(uint32_t n_input_dims, const char* encoding_json, int precision, tcnn_module_t* out) {

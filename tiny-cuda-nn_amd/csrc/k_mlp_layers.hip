@@ -27,8 +27,6 @@ namespace {
 constexpr uint32_t LG_BK = 32;          // K per staged step (one 16x16x32 k-step)
 constexpr uint32_t LG_LDK = LG_BK + 8;  // halfs per LDS row: 16 bytes of padding break the power-of-two row stride
 
-enum : uint32_t { LG_FWD = 0, LG_BWD = 1, LG_TANGENT = 2, LG_BWD_KEEP = 3, LG_CURVATURE = 4 };
-
 struct LayerGemmArgs {
 	const half_t* x;   // [n][ldx], columns 0..k-1 read
 	const half_t* w;   // [rows][k]
@@ -40,33 +38,6 @@ struct LayerGemmArgs {
 	// or G (backward, keep), optional; all [n][ldy]
 	const half_t* aux2;
 };
-
-// a'(z) and a''(z) in fp32 (the functions of activation_fwd).  x: the stored pre-activation; for ReLU / LeakyReLU the stored output
-// serves as well (same sign), and None takes no argument at all.
-__device__ inline float act_d1(const uint32_t act, const float x) {
-	switch (act) {
-		case (uint32_t)Activation::ReLU: return x > 0.0f ? 1.0f : 0.0f;
-		case (uint32_t)Activation::LeakyReLU: return x > 0.0f ? 1.0f : 0.01f;
-		case (uint32_t)Activation::Exponential: return expf(x);
-		case (uint32_t)Activation::Sine: return cosf(x);
-		case (uint32_t)Activation::Sigmoid: { const float s = logistic(x); return s * (1.0f - s); }
-		case (uint32_t)Activation::Squareplus: { const float y = x * K_ACT; return 0.5f * (1.0f + y / sqrtf(y * y + 4)); }
-		case (uint32_t)Activation::Softplus: return logistic(x * K_ACT);
-		case (uint32_t)Activation::Tanh: { const float t = tanhf(x); return 1.0f - t * t; }
-		default: return 1.0f;
-	}
-}
-__device__ inline float act_d2(const uint32_t act, const float x) {
-	switch (act) {
-		case (uint32_t)Activation::Exponential: return expf(x);
-		case (uint32_t)Activation::Sine: return -sinf(x);
-		case (uint32_t)Activation::Sigmoid: { const float s = logistic(x); return s * (1.0f - s) * (1.0f - 2.0f * s); }
-		case (uint32_t)Activation::Squareplus: { const float y = x * K_ACT, q = y * y + 4; return 2.0f * K_ACT / (q * sqrtf(q)); }
-		case (uint32_t)Activation::Softplus: { const float s = logistic(x * K_ACT); return K_ACT * s * (1.0f - s); }
-		case (uint32_t)Activation::Tanh: { const float t = tanhf(x); return -2.0f * t * (1.0f - t * t); }
-		default: return 0.0f; // None, ReLU, LeakyReLU: piecewise linear
-	}
-}
 
 // the second-order epilogues on one 4-output piece of the accumulator (what y gets is returned; R or G go to a.pre on the way)
 __device__ inline h4 second_order_epilogue(const LayerGemmArgs& a, const size_t at, const f4 acc) {

@@ -18,36 +18,70 @@ constexpr float K_ACT = 10.0f;
 
 __device__ inline float logistic(float x) { return 1.0f / (1.0f + expf(-x)); }
 
-// common_device.h:102-160, applied to the fp16-rounded accumulator like the reference's warp_activation
-__device__ inline half_t activation_fwd(uint32_t act, half_t pre) {
+// common_device.h:102-160, applied to the fp16-rounded accumulator like the reference's warp_activation.  T: the network's precision --
+// half_t, or float for the full-precision layers (k_mlp_layers_f32.hip), where every (T) below is no rounding at all
+template <typename T>
+__device__ inline T activation_fwd(uint32_t act, T pre) {
 	const float x = (float)pre;
 	switch (act) {
-		case (uint32_t)Activation::ReLU: return x > 0.0f ? pre : (half_t)0.0f;
-		case (uint32_t)Activation::LeakyReLU: return pre * (half_t)(x > 0.0f ? 1.0f : 0.01f);
-		case (uint32_t)Activation::Exponential: return (half_t)expf(x);
-		case (uint32_t)Activation::Sine: return (half_t)sinf(x);
-		case (uint32_t)Activation::Sigmoid: return (half_t)logistic(x);
-		case (uint32_t)Activation::Squareplus: { const float y = x * K_ACT; return (half_t)(0.5f * (y + sqrtf(y * y + 4)) / K_ACT); }
-		case (uint32_t)Activation::Softplus: return (half_t)(logf(expf(x * K_ACT) + 1.0f) / K_ACT);
-		case (uint32_t)Activation::Tanh: return (half_t)tanhf(x);
+		case (uint32_t)Activation::ReLU: return x > 0.0f ? pre : (T)0.0f;
+		case (uint32_t)Activation::LeakyReLU: return pre * (T)(x > 0.0f ? 1.0f : 0.01f);
+		case (uint32_t)Activation::Exponential: return (T)expf(x);
+		case (uint32_t)Activation::Sine: return (T)sinf(x);
+		case (uint32_t)Activation::Sigmoid: return (T)logistic(x);
+		case (uint32_t)Activation::Squareplus: { const float y = x * K_ACT; return (T)(0.5f * (y + sqrtf(y * y + 4)) / K_ACT); }
+		case (uint32_t)Activation::Softplus: return (T)(logf(expf(x * K_ACT) + 1.0f) / K_ACT);
+		case (uint32_t)Activation::Tanh: return (T)tanhf(x);
 		default: return pre;
 	}
 }
 
 // common_device.h:241-297: derivative from the forward OUTPUT
-__device__ inline half_t activation_bwd(uint32_t act, half_t grad, half_t fwd) {
+template <typename T>
+__device__ inline T activation_bwd(uint32_t act, T grad, T fwd) {
 	const float y = (float)fwd;
 	switch (act) {
-		case (uint32_t)Activation::ReLU: return y > 0.0f ? grad : grad * (half_t)0.0f;
-		case (uint32_t)Activation::LeakyReLU: return grad * (half_t)(y > 0.0f ? 1.0f : 0.01f);
+		case (uint32_t)Activation::ReLU: return y > 0.0f ? grad : grad * (T)0.0f;
+		case (uint32_t)Activation::LeakyReLU: return grad * (T)(y > 0.0f ? 1.0f : 0.01f);
 		case (uint32_t)Activation::Exponential: return grad * fwd;
-		case (uint32_t)Activation::Sigmoid: return grad * (half_t)(fwd * (half_t)(1.0f - y));
-		case (uint32_t)Activation::Squareplus: { const float t = y * K_ACT; return grad * (half_t)(t * t / (t * t + 1)); }
-		case (uint32_t)Activation::Softplus: return grad * (half_t)(1.0f - expf(-y * K_ACT));
-		case (uint32_t)Activation::Tanh: return grad * (half_t)(1.0f - (y * y));
+		case (uint32_t)Activation::Sigmoid: return grad * (T)(fwd * (T)(1.0f - y));
+		case (uint32_t)Activation::Squareplus: { const float t = y * K_ACT; return grad * (T)(t * t / (t * t + 1)); }
+		case (uint32_t)Activation::Softplus: return grad * (T)(1.0f - expf(-y * K_ACT));
+		case (uint32_t)Activation::Tanh: return grad * (T)(1.0f - (y * y));
 		default: return grad; // None; Sine is unsupported from outputs (common_device.h:261-265)
 	}
 }
+
+// a'(z) and a''(z) in fp32 (the functions of activation_fwd), for the layer-by-layer kernels of either precision (k_mlp_layers.hip,
+// k_mlp_layers_f32.hip).  x: the stored pre-activation; for ReLU / LeakyReLU the stored output serves as well (same sign), and None
+// takes no argument at all.
+__device__ inline float act_d1(const uint32_t act, const float x) {
+	switch (act) {
+		case (uint32_t)Activation::ReLU: return x > 0.0f ? 1.0f : 0.0f;
+		case (uint32_t)Activation::LeakyReLU: return x > 0.0f ? 1.0f : 0.01f;
+		case (uint32_t)Activation::Exponential: return expf(x);
+		case (uint32_t)Activation::Sine: return cosf(x);
+		case (uint32_t)Activation::Sigmoid: { const float s = logistic(x); return s * (1.0f - s); }
+		case (uint32_t)Activation::Squareplus: { const float y = x * K_ACT; return 0.5f * (1.0f + y / sqrtf(y * y + 4)); }
+		case (uint32_t)Activation::Softplus: return logistic(x * K_ACT);
+		case (uint32_t)Activation::Tanh: { const float t = tanhf(x); return 1.0f - t * t; }
+		default: return 1.0f;
+	}
+}
+__device__ inline float act_d2(const uint32_t act, const float x) {
+	switch (act) {
+		case (uint32_t)Activation::Exponential: return expf(x);
+		case (uint32_t)Activation::Sine: return -sinf(x);
+		case (uint32_t)Activation::Sigmoid: { const float s = logistic(x); return s * (1.0f - s) * (1.0f - 2.0f * s); }
+		case (uint32_t)Activation::Squareplus: { const float y = x * K_ACT, q = y * y + 4; return 2.0f * K_ACT / (q * sqrtf(q)); }
+		case (uint32_t)Activation::Softplus: { const float s = logistic(x * K_ACT); return K_ACT * s * (1.0f - s); }
+		case (uint32_t)Activation::Tanh: { const float t = tanhf(x); return -2.0f * t * (1.0f - t * t); }
+		default: return 0.0f; // None, ReLU, LeakyReLU: piecewise linear
+	}
+}
+
+// what a layer GEMM of the layer-by-layer path computes (its epilogue), in either precision
+enum : uint32_t { LG_FWD = 0, LG_BWD = 1, LG_TANGENT = 2, LG_BWD_KEEP = 3, LG_CURVATURE = 4 };
 
 template <int ACT> __device__ inline half_t act_fwd_t(uint32_t act, half_t v) {
 	if constexpr (ACT == (int)Activation::ReLU) return v > (half_t)0.0f ? v : (half_t)0.0f;

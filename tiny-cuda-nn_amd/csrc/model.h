@@ -1574,7 +1574,7 @@ inline const char* to_string(Activation a) {
 }
 
 struct NetworkContext {
-	ArenaBuf hidden; // half [n_hidden][n][width]
+	ArenaBuf hidden; // [n_hidden][n][width] in the network's precision
 	ArenaBuf pre;    // layer-by-layer Sine networks: the hidden layers' pre-activations, laid out as `hidden` (cutlass_mlp.cu:53)
 };
 
@@ -1582,11 +1582,15 @@ class Network {
 public:
 	static constexpr uint32_t REQUIRED_ALIGNMENT = 16; // fully_fused_mlp.h:108-110, cutlass_mlp.h:115-121
 
-	explicit Network(const Json& net) { // network.cu:48-137
+	// precision Fp32: the reference's build without TCNN_HALF_PRECISION (common.h:99-123) as a choice per network -- CutlassMLP<float>.
+	// Parameters, activations, gradients and every second-order intermediate are floats, and the network always runs layer by layer
+	// (k_mlp_layers_f32.hip): no fragment images, no fused training plan.
+	explicit Network(const Json& net, Precision precision = Precision::Fp16) : m_fp32{precision == Precision::Fp32} { // network.cu:48-137
 		const std::string otype = net.value("otype", "MLP");
 		m_fully_fused = equals_case_insensitive(otype, "MegakernelMLP") || equals_case_insensitive(otype, "FullyFusedMLP");
 		const bool cutlass = equals_case_insensitive(otype, "MLP") || equals_case_insensitive(otype, "CutlassMLP");
 		if (!m_fully_fused && !cutlass) throw std::runtime_error{"Invalid network type: " + otype};
+		if (m_fully_fused && m_fp32) throw std::runtime_error{"FullyFusedMLP can only be used if the network precision is set to __half."}; // network.cu:102-103
 		if (!net.contains("n_input_dims") || !net.contains("n_output_dims")) throw std::runtime_error{"network config needs n_input_dims and n_output_dims"};
 		m_input_width = net.value("n_input_dims", 0u);
 		m_output_width = net.value("n_output_dims", 0u);
@@ -1612,7 +1616,7 @@ public:
 		}
 		if (m_n_hidden + 1 > MAX_MLP_LAYERS) throw std::runtime_error{"MLP: too many layers for this build"};
 		if (m_input_width % 16 != 0) throw std::runtime_error{"MLP: input width must be a multiple of 16"};
-		m_layerwise = m_layerwise || switches().mlp_layerwise; // TCNN_AMD_MLP_LAYERWISE=1: the A/B form for any shape
+		m_layerwise = m_layerwise || m_fp32 || switches().mlp_layerwise; // TCNN_AMD_MLP_LAYERWISE=1: the A/B form for any shape
 		m_padded_output_width = next_multiple(m_output_width, REQUIRED_ALIGNMENT);
 
 		// matrices: fully_fused_mlp.cu:659-671
@@ -1652,6 +1656,8 @@ public:
 	bool layerwise() const { return m_layerwise; }
 	bool has_output_activation() const { return m_output_activation != Activation::None; }
 	bool fully_fused() const { return m_fully_fused; } // otype FullyFusedMLP: no second-order pass (as in the reference); CutlassMLP has one
+	Precision precision() const { return m_fp32 ? Precision::Fp32 : Precision::Fp16; }
+	size_t element_size() const { return m_fp32 ? sizeof(float) : sizeof(_Float16); } // bytes of a parameter, an activation, a gradient
 
 	uint32_t input_width() const { return m_input_width; }
 	uint32_t output_width() const { return m_output_width; }
@@ -1740,9 +1746,9 @@ public:
 
 	NetworkContext forward(hipStream_t stream, uint32_t n, const void* input, void* output, const void* params) const {
 		NetworkContext ctx;
-		ctx.hidden = ArenaBuf{stream, (size_t)m_n_hidden * n * m_width * 2};
+		ctx.hidden = ArenaBuf{stream, (size_t)m_n_hidden * n * m_width * element_size()};
 		if (m_layerwise) {
-			if (m_activation == Activation::Sine) ctx.pre = ArenaBuf{stream, (size_t)m_n_hidden * n * m_width * 2};
+			if (m_activation == Activation::Sine) ctx.pre = ArenaBuf{stream, (size_t)m_n_hidden * n * m_width * element_size()};
 			forward_layers(stream, n, input, output, params, ctx.hidden.data(), ctx.pre.data());
 			return ctx;
 		}
@@ -1751,7 +1757,7 @@ public:
 		return ctx;
 	}
 
-	// dL_dinput: optional half [n][in_width]; gradients: half[n_params] or nullptr
+	// dL_dinput: optional [n][in_width]; gradients: [n_params] or nullptr (both in the network's precision)
 	void backward(hipStream_t stream, const NetworkContext& ctx, uint32_t n, const void* input, const void* output, const void* dL_doutput,
 	              void* dL_dinput, const void* params, void* gradients, GradientMode mode, uint32_t dx_plane_features = 0) const {
 		// output-activation transfer, computed once up front like the reference (fully_fused_mlp.cu:757-762)
@@ -1759,8 +1765,9 @@ public:
 		ArenaBuf dY_tmp;
 		MlpDesc desc = m_desc;
 		if (m_output_activation != Activation::None) {
-			dY_tmp = ArenaBuf{stream, (size_t)n * m_padded_output_width * 2};
-			mlp_activation_backward_output(stream, n * m_padded_output_width, (uint32_t)m_output_activation, dL_doutput, output, dY_tmp.data());
+			dY_tmp = ArenaBuf{stream, (size_t)n * m_padded_output_width * element_size()};
+			if (m_fp32) mlp_activation_backward_output_f32(stream, (size_t)n * m_padded_output_width, (uint32_t)m_output_activation, (const float*)dL_doutput, (const float*)output, dY_tmp.as<float>());
+			else mlp_activation_backward_output(stream, n * m_padded_output_width, (uint32_t)m_output_activation, dL_doutput, output, dY_tmp.data());
 			dY = dY_tmp.data();
 			desc.output_activation = (uint32_t)Activation::None;
 		}
@@ -1815,7 +1822,7 @@ public:
 	bool any_curvature() const { return has_curvature((uint32_t)m_output_activation) || (m_n_hidden > 0 && has_curvature((uint32_t)m_activation)); }
 
 	struct SecondOrderPass {
-		ArenaBuf h, z, g, d, wt; // [n_layers] slots of n x max(width, padded output width) halfs each (wt: laid out as the parameters)
+		ArenaBuf h, z, g, d, wt; // [n_layers] slots of n x max(width, padded output width) elements each (wt: laid out as the parameters)
 		size_t slot = 0;
 		const void* input = nullptr;
 		const void* dL_doutput = nullptr;
@@ -1831,37 +1838,37 @@ public:
 		s.input = input;
 		s.dL_doutput = dL_doutput;
 		const bool curved = any_curvature();
-		const _Float16* p = (const _Float16*)params;
-		s.h = ArenaBuf{stream, K * s.slot * 2};
-		if (curved) s.z = ArenaBuf{stream, K * s.slot * 2};
-		const _Float16* in = (const _Float16*)input;
+		const void* p = params;
+		s.h = ArenaBuf{stream, K * s.slot * element_size()};
+		if (curved) s.z = ArenaBuf{stream, K * s.slot * element_size()};
+		const void* in = input;
 		uint32_t ldi = m_input_width;
 		for (uint32_t l = 0; l < K; ++l) {
 			const MlpLayer& L = m_desc.layers[l];
-			_Float16* out = s.h.as<_Float16>() + s.slot * l;
-			mlp_layer_forward(stream, n, in, ldi, p + L.w_off, L.rows, L.cols, layer_act(l), out, layer_ld(l), has_curvature(layer_act(l)) ? s.z.as<_Float16>() + s.slot * l : nullptr);
+			void* out = at(s.h.data(), s.slot * l);
+			layer_forward(stream, n, in, ldi, at(p, L.w_off), L.rows, L.cols, layer_act(l), out, layer_ld(l), has_curvature(layer_act(l)) ? at(s.z.data(), s.slot * l) : nullptr);
 			in = out;
 			ldi = m_width;
 		}
 		if (!need_d) return s;
 		s.have_d = true;
-		s.d = ArenaBuf{stream, K * s.slot * 2};
-		if (curved) s.g = ArenaBuf{stream, K * s.slot * 2};
-		s.wt = ArenaBuf{stream, m_n_params * 2};
-		for (uint32_t l = 1; l < K; ++l) mlp_layer_transpose(stream, m_desc.layers[l].rows, m_desc.layers[l].cols, p + m_desc.layers[l].w_off, s.wt.as<_Float16>() + m_desc.layers[l].w_off);
+		s.d = ArenaBuf{stream, K * s.slot * element_size()};
+		if (curved) s.g = ArenaBuf{stream, K * s.slot * element_size()};
+		s.wt = ArenaBuf{stream, m_n_params * element_size()};
+		for (uint32_t l = 1; l < K; ++l) layer_transpose(stream, m_desc.layers[l].rows, m_desc.layers[l].cols, at(p, m_desc.layers[l].w_off), at(s.wt.data(), m_desc.layers[l].w_off));
 		if (layer_act(K - 1) != (uint32_t)Activation::None) { // d_K = a_K'(z_K) g_K
-			mlp_layer_delta(stream, (size_t)n * m_padded_output_width, layer_act(K - 1), dL_doutput, aux_of(s, K - 1), s.d.as<_Float16>() + s.slot * (K - 1));
+			layer_delta(stream, (size_t)n * m_padded_output_width, layer_act(K - 1), dL_doutput, aux_of(s, K - 1), at(s.d.data(), s.slot * (K - 1)));
 		}
 		for (uint32_t l = K - 1; l > 0; --l) {
 			const MlpLayer& L = m_desc.layers[l];
 			const uint32_t act = layer_act(l - 1);
-			mlp_layer_backward_keep(stream, n, d_of(s, l), layer_ld(l), s.wt.as<_Float16>() + L.w_off, L.rows, L.cols, act, aux_of(s, l - 1),
-			                        has_curvature(act) ? s.g.as<_Float16>() + s.slot * (l - 1) : nullptr, s.d.as<_Float16>() + s.slot * (l - 1), m_width);
+			layer_backward_keep(stream, n, d_of(s, l), layer_ld(l), at(s.wt.data(), L.w_off), L.rows, L.cols, act, aux_of(s, l - 1),
+			                    has_curvature(act) ? at(s.g.data(), s.slot * (l - 1)) : nullptr, at(s.d.data(), s.slot * (l - 1)), m_width);
 		}
 		return s;
 	}
 
-	// v: half [n][in_width].  Optional results: dL_ddLdoutput half [n][padded output width]; dS_dinput half [n][in_width], written only if
+	// (all in the network's precision)  v: [n][in_width].  Optional results: dL_ddLdoutput [n][padded output width]; dS_dinput [n][in_width], written only if
 	// any_curvature() (else it is zero and nothing is launched for it); gradients per mode.
 	void second_order_finish(hipStream_t stream, SecondOrderPass& s, uint32_t n, const void* v, void* dL_ddLdoutput, void* dS_dinput, const void* params, void* gradients,
 	                         GradientMode mode) const {
@@ -1872,17 +1879,17 @@ public:
 		if (!dL_ddLdoutput && !want_grads && !(curved && dS_dinput)) return;
 		if (want_grads) CHECK_THROW(gradients != nullptr);
 		if (want_grads || want_p) CHECK_THROW(s.have_d);
-		const _Float16* p = (const _Float16*)params;
-		ArenaBuf u{stream, K * s.slot * 2}, r;
-		if (want_p) r = ArenaBuf{stream, K * s.slot * 2};
-		auto u_of = [&](uint32_t l) { return l == K - 1 && dL_ddLdoutput ? (_Float16*)dL_ddLdoutput : u.as<_Float16>() + s.slot * l; };
-		const _Float16* in = (const _Float16*)v;
+		const void* p = params;
+		ArenaBuf u{stream, K * s.slot * element_size()}, r;
+		if (want_p) r = ArenaBuf{stream, K * s.slot * element_size()};
+		auto u_of = [&](uint32_t l) { return l == K - 1 && dL_ddLdoutput ? dL_ddLdoutput : at(u.data(), s.slot * l); };
+		const void* in = v;
 		uint32_t ldi = m_input_width;
 		for (uint32_t l = 0; l < K; ++l) {
 			const MlpLayer& L = m_desc.layers[l];
 			const bool curv = want_p && has_curvature(layer_act(l));
-			const _Float16* g = l == K - 1 ? (const _Float16*)s.dL_doutput : s.g.as<_Float16>() + s.slot * l;
-			mlp_layer_tangent(stream, n, in, ldi, p + L.w_off, L.rows, L.cols, layer_act(l), aux_of(s, l), curv ? g : nullptr, u_of(l), curv ? r.as<_Float16>() + s.slot * l : nullptr, layer_ld(l));
+			const void* g = l == K - 1 ? s.dL_doutput : at((const void*)s.g.data(), s.slot * l);
+			layer_tangent(stream, n, in, ldi, at(p, L.w_off), L.rows, L.cols, layer_act(l), aux_of(s, l), curv ? g : nullptr, u_of(l), curv ? at(r.data(), s.slot * l) : nullptr, layer_ld(l));
 			in = u_of(l);
 			ldi = m_width;
 		}
@@ -1890,30 +1897,30 @@ public:
 		for (uint32_t l = 0; l < K; ++l) if (has_curvature(layer_act(l))) top = l;
 		if (want_p) {
 			if (dS_dinput && !s.have_wt0) {
-				mlp_layer_transpose(stream, m_desc.layers[0].rows, m_desc.layers[0].cols, p, s.wt.as<_Float16>());
+				layer_transpose(stream, m_desc.layers[0].rows, m_desc.layers[0].cols, p, s.wt.data());
 				s.have_wt0 = true;
 			}
 			for (uint32_t l = top; l > 0; --l) {
 				const MlpLayer& L = m_desc.layers[l];
-				_Float16* below = r.as<_Float16>() + s.slot * (l - 1);
-				mlp_layer_curvature_backward(stream, n, r.as<_Float16>() + s.slot * l, layer_ld(l), s.wt.as<_Float16>() + L.w_off, L.rows, L.cols, layer_act(l - 1), aux_of(s, l - 1),
-				                             has_curvature(layer_act(l - 1)) ? below : nullptr, below, m_width);
+				void* below = at(r.data(), s.slot * (l - 1));
+				layer_curvature_backward(stream, n, at(r.data(), s.slot * l), layer_ld(l), at(s.wt.data(), L.w_off), L.rows, L.cols, layer_act(l - 1), aux_of(s, l - 1),
+				                         has_curvature(layer_act(l - 1)) ? below : nullptr, below, m_width);
 			}
 			if (dS_dinput) {
 				const MlpLayer& L = m_desc.layers[0];
-				mlp_layer_backward(stream, n, r.as<_Float16>(), layer_ld(0), s.wt.as<_Float16>(), L.rows, L.cols, (uint32_t)Activation::None, nullptr, dS_dinput, m_input_width);
+				layer_backward(stream, n, r.data(), layer_ld(0), s.wt.data(), L.rows, L.cols, (uint32_t)Activation::None, nullptr, dS_dinput, m_input_width);
 			}
 		}
 		if (!want_grads) return;
-		// dS/dW_k = d_k^T u_{k-1}, then += p_k^T h_{k-1} for the layers up to `top` (the sum is rounded to half once per term)
+		// dS/dW_k = d_k^T u_{k-1}, then += p_k^T h_{k-1} for the layers up to `top` (the sum is rounded to the network's precision once per term)
 		std::vector<WgradPanel> panels;
 		for (uint32_t pass = 0; pass < (want_p ? 2u : 1u); ++pass) {
 			panels.clear();
 			for (uint32_t l = 0; l < (pass ? top + 1 : K); ++l) {
 				const MlpLayer& L = m_desc.layers[l];
-				const _Float16* dO = pass ? r.as<_Float16>() + s.slot * l : d_of(s, l);
-				const _Float16* In = l == 0 ? (const _Float16*)(pass ? s.input : v) : pass ? s.h.as<_Float16>() + s.slot * (l - 1) : u.as<_Float16>() + s.slot * (l - 1);
-				add_wgrad_panels(panels, L, dO, layer_ld(l), In, l == 0 ? m_input_width : m_width, (_Float16*)gradients + L.w_off);
+				const void* dO = pass ? at((const void*)r.data(), s.slot * l) : d_of(s, l);
+				const void* In = l == 0 ? (pass ? s.input : v) : pass ? at((const void*)s.h.data(), s.slot * (l - 1)) : at((const void*)u.data(), s.slot * (l - 1));
+				add_wgrad_panels(panels, L, dO, layer_ld(l), In, l == 0 ? m_input_width : m_width, at(gradients, L.w_off));
 			}
 			launch_wgrad_panels(stream, n, panels, pass ? true : mode == GradientMode::Accumulate);
 		}
@@ -1930,7 +1937,42 @@ public:
 	}
 
 private:
-	// ---- the layer-by-layer path (cutlass_mlp.cu:140-300): activations [n][width] half in memory, one GEMM launch per layer
+	// ---- the layer-by-layer path (cutlass_mlp.cu:140-300): activations [n][width] in memory, one GEMM launch per layer
+	// `elems` elements of the network's precision behind base (null stays null)
+	const void* at(const void* base, size_t elems) const { return base ? (const char*)base + elems * element_size() : nullptr; }
+	void* at(void* base, size_t elems) const { return base ? (char*)base + elems * element_size() : nullptr; }
+	// the layer kernels of the network's precision (k_mlp_layers.hip / k_mlp_layers_f32.hip)
+	void layer_forward(hipStream_t stream, uint32_t n, const void* x, uint32_t ldx, const void* w, uint32_t rows, uint32_t cols, uint32_t act, void* y, uint32_t ldy, void* pre) const {
+		if (m_fp32) mlp_layer_forward_f32(stream, n, (const float*)x, ldx, (const float*)w, rows, cols, act, (float*)y, ldy, (float*)pre);
+		else mlp_layer_forward(stream, n, x, ldx, w, rows, cols, act, y, ldy, pre);
+	}
+	void layer_backward(hipStream_t stream, uint32_t n, const void* dL_dout, uint32_t ldo, const void* wt, uint32_t rows, uint32_t cols, uint32_t act, const void* aux, void* dL_din, uint32_t ldi) const {
+		if (m_fp32) mlp_layer_backward_f32(stream, n, (const float*)dL_dout, ldo, (const float*)wt, rows, cols, act, (const float*)aux, (float*)dL_din, ldi);
+		else mlp_layer_backward(stream, n, dL_dout, ldo, wt, rows, cols, act, aux, dL_din, ldi);
+	}
+	void layer_transpose(hipStream_t stream, uint32_t rows, uint32_t cols, const void* w, void* wt) const {
+		if (m_fp32) mlp_layer_transpose_f32(stream, rows, cols, (const float*)w, (float*)wt);
+		else mlp_layer_transpose(stream, rows, cols, w, wt);
+	}
+	void layer_tangent(hipStream_t stream, uint32_t n, const void* u_in, uint32_t ldu, const void* w, uint32_t rows, uint32_t cols, uint32_t act, const void* aux, const void* g, void* u_out,
+	                   void* r_out, uint32_t ldy) const {
+		if (m_fp32) mlp_layer_tangent_f32(stream, n, (const float*)u_in, ldu, (const float*)w, rows, cols, act, (const float*)aux, (const float*)g, (float*)u_out, (float*)r_out, ldy);
+		else mlp_layer_tangent(stream, n, u_in, ldu, w, rows, cols, act, aux, g, u_out, r_out, ldy);
+	}
+	void layer_backward_keep(hipStream_t stream, uint32_t n, const void* d_out, uint32_t ldo, const void* wt, uint32_t rows, uint32_t cols, uint32_t act, const void* aux, void* g_in, void* d_in,
+	                         uint32_t ldi) const {
+		if (m_fp32) mlp_layer_backward_keep_f32(stream, n, (const float*)d_out, ldo, (const float*)wt, rows, cols, act, (const float*)aux, (float*)g_in, (float*)d_in, ldi);
+		else mlp_layer_backward_keep(stream, n, d_out, ldo, wt, rows, cols, act, aux, g_in, d_in, ldi);
+	}
+	void layer_curvature_backward(hipStream_t stream, uint32_t n, const void* p_out, uint32_t ldo, const void* wt, uint32_t rows, uint32_t cols, uint32_t act, const void* aux, const void* r_in,
+	                              void* p_in, uint32_t ldi) const {
+		if (m_fp32) mlp_layer_curvature_backward_f32(stream, n, (const float*)p_out, ldo, (const float*)wt, rows, cols, act, (const float*)aux, (const float*)r_in, (float*)p_in, ldi);
+		else mlp_layer_curvature_backward(stream, n, p_out, ldo, wt, rows, cols, act, aux, r_in, p_in, ldi);
+	}
+	void layer_delta(hipStream_t stream, size_t n_elems, uint32_t act, const void* g, const void* aux, void* delta) const {
+		if (m_fp32) mlp_layer_delta_f32(stream, n_elems, act, (const float*)g, (const float*)aux, (float*)delta);
+		else mlp_layer_delta(stream, n_elems, act, g, aux, delta);
+	}
 	uint32_t layer_act(uint32_t l) const { return (uint32_t)(l == m_desc.n_layers - 1 ? m_output_activation : m_activation); }
 	uint32_t layer_ld(uint32_t l) const { return l == m_desc.n_layers - 1 ? m_padded_output_width : m_width; } // of the layer's output
 
@@ -1938,15 +1980,15 @@ private:
 	void forward_layers(hipStream_t stream, uint32_t n, const void* input, void* output, const void* params, void* hidden, void* pre) const {
 		const size_t hstride = (size_t)n * m_width;
 		ArenaBuf rotate;
-		if (!hidden && m_n_hidden > 0) rotate = ArenaBuf{stream, std::min<size_t>(m_n_hidden, 2) * hstride * 2};
-		const _Float16* in = (const _Float16*)input;
+		if (!hidden && m_n_hidden > 0) rotate = ArenaBuf{stream, std::min<size_t>(m_n_hidden, 2) * hstride * element_size()};
+		const void* in = input;
 		uint32_t ldi = m_input_width;
 		for (uint32_t l = 0; l < m_desc.n_layers; ++l) {
 			const MlpLayer& L = m_desc.layers[l];
 			const bool last = l == m_desc.n_layers - 1;
-			_Float16* out = last ? (_Float16*)output : hidden ? (_Float16*)hidden + hstride * l : rotate.as<_Float16>() + hstride * (l & 1);
-			_Float16* p = !last && pre ? (_Float16*)pre + hstride * l : nullptr;
-			mlp_layer_forward(stream, n, in, ldi, (const _Float16*)params + L.w_off, L.rows, L.cols, layer_act(l), out, layer_ld(l), p);
+			void* out = last ? output : hidden ? at(hidden, hstride * l) : at(rotate.data(), hstride * (l & 1));
+			void* p = !last && pre ? at(pre, hstride * l) : nullptr;
+			layer_forward(stream, n, in, ldi, at(params, L.w_off), L.rows, L.cols, layer_act(l), out, layer_ld(l), p);
 			in = out;
 			ldi = m_width;
 		}
@@ -1956,73 +1998,74 @@ private:
 	                     GradientMode mode) const {
 		const size_t hstride = (size_t)n * m_width;
 		const bool sine = m_activation == Activation::Sine;
-		const _Float16* hidden = ctx.hidden.as<_Float16>();
-		const _Float16* aux = sine ? ctx.pre.as<_Float16>() : hidden; // what act' reads: cos of the pre-activation for Sine, else the output
-		ArenaBuf dhidden{stream, (size_t)m_n_hidden * hstride * 2};
+		const void* hidden = ctx.hidden.data();
+		const void* aux = sine ? ctx.pre.data() : hidden; // what act' reads: cos of the pre-activation for Sine, else the output
+		ArenaBuf dhidden{stream, (size_t)m_n_hidden * hstride * element_size()};
 		// W^T of every layer that passes a gradient on: layer 0 only when dL/dinput is wanted
-		ArenaBuf wt{stream, m_n_params * 2};
-		const _Float16* p = (const _Float16*)params;
+		ArenaBuf wt{stream, m_n_params * element_size()};
+		const void* p = params;
 		for (uint32_t l = dL_dinput ? 0 : 1; l < m_desc.n_layers; ++l) {
 			const MlpLayer& L = m_desc.layers[l];
-			mlp_layer_transpose(stream, L.rows, L.cols, p + L.w_off, wt.as<_Float16>() + L.w_off);
+			layer_transpose(stream, L.rows, L.cols, at(p, L.w_off), at(wt.data(), L.w_off));
 		}
 		for (uint32_t l = m_desc.n_layers; l-- > 0;) {
 			const MlpLayer& L = m_desc.layers[l];
-			const _Float16* dO = l == m_desc.n_layers - 1 ? (const _Float16*)dY : dhidden.as<_Float16>() + hstride * l;
+			const void* dO = l == m_desc.n_layers - 1 ? dY : at((const void*)dhidden.data(), hstride * l);
 			const uint32_t ldo = layer_ld(l);
 			if (l > 0) { // dL/d(hidden l - 1), through the derivative of its activation
-				mlp_layer_backward(stream, n, dO, ldo, wt.as<_Float16>() + L.w_off, L.rows, L.cols, (uint32_t)m_activation, aux + hstride * (l - 1),
-				                   dhidden.as<_Float16>() + hstride * (l - 1), m_width);
+				layer_backward(stream, n, dO, ldo, at(wt.data(), L.w_off), L.rows, L.cols, (uint32_t)m_activation, at(aux, hstride * (l - 1)), at(dhidden.data(), hstride * (l - 1)), m_width);
 			} else if (dL_dinput) {
-				mlp_layer_backward(stream, n, dO, ldo, wt.as<_Float16>() + L.w_off, L.rows, L.cols, (uint32_t)Activation::None, nullptr, dL_dinput, m_input_width);
+				layer_backward(stream, n, dO, ldo, at(wt.data(), L.w_off), L.rows, L.cols, (uint32_t)Activation::None, nullptr, dL_dinput, m_input_width);
 			}
 		}
 		if (mode == GradientMode::Ignore) return;
 		CHECK_THROW(gradients != nullptr);
-		// weight gradients: mlp_wgrad_panels on the row-major buffers, panels of at most 128 x 128, launched in groups whose fp32 slabs
+		// weight gradients: mlp_wgrad_panels (fp32: mlp_wgrad_panels_f32) on the row-major buffers, panels of at most 128 x 128, launched in groups whose fp32 slabs
 		// fit a bounded workspace (a 1024-wide layer is 64 panels of up to 256 slabs each; the groups run in stream order and share it)
 		std::vector<WgradPanel> panels;
 		for (uint32_t l = 0; l < m_desc.n_layers; ++l) {
 			const MlpLayer& L = m_desc.layers[l];
-			const _Float16* dO = l == m_desc.n_layers - 1 ? (const _Float16*)dY : dhidden.as<_Float16>() + hstride * l;
-			const _Float16* In = l == 0 ? (const _Float16*)input : hidden + hstride * (l - 1);
-			add_wgrad_panels(panels, L, dO, layer_ld(l), In, l == 0 ? m_input_width : m_width, (_Float16*)gradients + L.w_off);
+			const void* dO = l == m_desc.n_layers - 1 ? dY : at((const void*)dhidden.data(), hstride * l);
+			const void* In = l == 0 ? input : at(hidden, hstride * (l - 1));
+			add_wgrad_panels(panels, L, dO, layer_ld(l), In, l == 0 ? m_input_width : m_width, at(gradients, L.w_off));
 		}
 		launch_wgrad_panels(stream, n, panels, mode == GradientMode::Accumulate);
 	}
 
 	// what a' (and a'') of layer l are evaluated from in the second-order pass: z_l where the layer has curvature, else h_l (the sign)
-	const _Float16* aux_of(const SecondOrderPass& s, uint32_t l) const {
+	const void* aux_of(const SecondOrderPass& s, uint32_t l) const {
 		if (layer_act(l) == (uint32_t)Activation::None) return nullptr;
-		return (has_curvature(layer_act(l)) ? s.z.as<_Float16>() : s.h.as<_Float16>()) + s.slot * l;
+		return at((const void*)(has_curvature(layer_act(l)) ? s.z.data() : s.h.data()), s.slot * l);
 	}
-	const _Float16* d_of(const SecondOrderPass& s, uint32_t l) const { // d_K = g_K for an output layer without activation
-		return l == m_desc.n_layers - 1 && layer_act(l) == (uint32_t)Activation::None ? (const _Float16*)s.dL_doutput : s.d.as<_Float16>() + s.slot * l;
+	const void* d_of(const SecondOrderPass& s, uint32_t l) const { // d_K = g_K for an output layer without activation
+		return l == m_desc.n_layers - 1 && layer_act(l) == (uint32_t)Activation::None ? s.dL_doutput : at((const void*)s.d.data(), s.slot * l);
 	}
 
 	// row-major operands: panels of at most 128 x 128 of one layer's weight gradient
-	static void add_wgrad_panels(std::vector<WgradPanel>& panels, const MlpLayer& L, const _Float16* dO, uint32_t ldo, const _Float16* In, uint32_t ldi, _Float16* g) {
+	void add_wgrad_panels(std::vector<WgradPanel>& panels, const MlpLayer& L, const void* dO, uint32_t ldo, const void* In, uint32_t ldi, void* g) const {
 		for (uint32_t r0 = 0; r0 < L.rows; r0 += 128)
 			for (uint32_t c0 = 0; c0 < L.cols; c0 += 128)
-				panels.push_back(WgradPanel{dO + r0, ldo, std::min(128u, L.rows - r0), In + c0, ldi, std::min(128u, L.cols - c0), g + (size_t)r0 * L.cols + c0, L.cols, false, false});
+				panels.push_back(WgradPanel{at(dO, r0), ldo, std::min(128u, L.rows - r0), at(In, c0), ldi, std::min(128u, L.cols - c0), at(g, (size_t)r0 * L.cols + c0), L.cols, false, false});
 	}
 
 	void launch_wgrad_panels(hipStream_t stream, uint32_t n, const std::vector<WgradPanel>& panels, bool accumulate) const {
 		constexpr size_t WORKSPACE_FLOATS = (size_t)64 << 20; // 256 MB
+		const auto workspace_floats = m_fp32 ? wgrad_panels_workspace_floats_f32 : wgrad_panels_workspace_floats;
 		size_t max_floats = 0;
-		for (const WgradPanel& q : panels) max_floats = std::max(max_floats, wgrad_panels_workspace_floats(&q, 1, n));
-		ArenaBuf ws{stream, std::max(max_floats, std::min(WORKSPACE_FLOATS, wgrad_panels_workspace_floats(panels.data(), (uint32_t)panels.size(), n))) * sizeof(float)};
+		for (const WgradPanel& q : panels) max_floats = std::max(max_floats, workspace_floats(&q, 1, n));
+		ArenaBuf ws{stream, std::max(max_floats, std::min(WORKSPACE_FLOATS, workspace_floats(panels.data(), (uint32_t)panels.size(), n))) * sizeof(float)};
 		const size_t ws_floats = ws.bytes() / sizeof(float);
 		for (size_t i = 0; i < panels.size();) {
 			size_t j = i, floats = 0;
-			while (j < panels.size() && floats + wgrad_panels_workspace_floats(&panels[j], 1, n) <= ws_floats) floats += wgrad_panels_workspace_floats(&panels[j++], 1, n);
-			mlp_wgrad_panels(stream, n, panels.data() + i, (uint32_t)(j - i), accumulate, ws.as<float>());
+			while (j < panels.size() && floats + workspace_floats(&panels[j], 1, n) <= ws_floats) floats += workspace_floats(&panels[j++], 1, n);
+			(m_fp32 ? mlp_wgrad_panels_f32 : mlp_wgrad_panels)(stream, n, panels.data() + i, (uint32_t)(j - i), accumulate, ws.as<float>());
 			i = j;
 		}
 	}
 
 	bool m_fully_fused;
 	bool m_layerwise = false;
+	bool m_fp32 = false;
 	uint32_t m_input_width, m_output_width, m_padded_output_width, m_width, m_n_hidden;
 	Activation m_activation, m_output_activation;
 	MlpDesc m_desc;
@@ -2168,20 +2211,22 @@ struct OptimizerOffer {
 
 class NetworkWithInputEncoding : public Model {
 public:
-	NetworkWithInputEncoding(uint32_t n_dims_to_encode, uint32_t n_output_dims, const Json& encoding, const Json& network) {
+	// precision: of the whole module -- Fp32 creates the encoding in its fp32 form and the network as Network{json, Precision::Fp32}, so that
+	// parameters, the encoded batch, output and every gradient are floats (mixed modules do not exist)
+	NetworkWithInputEncoding(uint32_t n_dims_to_encode, uint32_t n_output_dims, const Json& encoding, const Json& network, Precision precision = Precision::Fp16) {
 		// network_with_input_encoding.h:45-56: encoding aligned to the network's minimum alignment (16), network sized from it
-		m_encoding = create_encoding(n_dims_to_encode, encoding, Network::REQUIRED_ALIGNMENT, false);
+		m_encoding = create_encoding(n_dims_to_encode, encoding, Network::REQUIRED_ALIGNMENT, precision == Precision::Fp32);
 		Json local = network.is_object() ? network : Json::object();
 		local["n_input_dims"] = m_encoding->padded_output_width();
 		local["n_output_dims"] = n_output_dims;
-		m_network.reset(new Network{local});
+		m_network.reset(new Network{local, precision});
 	}
 
 	uint32_t input_width() const override { return m_encoding->input_width(); }
 	uint32_t output_width() const override { return m_network->output_width(); }
 	uint32_t padded_output_width() const override { return m_network->padded_output_width(); }
 	size_t n_params() const override { return m_network->n_params() + m_encoding->n_params(); }
-	Precision precision() const override { return Precision::Fp16; }
+	Precision precision() const override { return m_network->precision(); }
 	std::vector<std::pair<uint32_t, uint32_t>> layer_sizes() const override { return m_network->layer_sizes(); }
 	Encoding& encoding() { return *m_encoding; }
 	Encoding* input_encoding() override { return m_encoding.get(); }
@@ -2207,11 +2252,12 @@ public:
 		if (n == 0) return;
 		const _Float16* p = (const _Float16*)params;
 		if (m_network->layerwise()) { // no fused input or output forms: the encoding's own kernel writes the batch, a trim casts the output
-			ArenaBuf network_input{stream, (size_t)n * m_encoding->padded_output_width() * 2}, out_tmp;
-			m_encoding->forward(stream, n, input, p + m_network->n_params(), network_input.data(), false, false);
-			if (!output_half) out_tmp = ArenaBuf{stream, (size_t)n * m_network->padded_output_width() * 2};
-			m_network->inference(stream, n, network_input.data(), output_half ? output_half : out_tmp.data(), p);
-			if (output_f32) trim_and_cast(stream, false, n, m_network->padded_output_width(), m_network->output_width(), output_half ? output_half : out_tmp.data(), *output_f32);
+			// (output_half: the output in the module's precision)
+			ArenaBuf network_input{stream, (size_t)n * m_encoding->padded_output_width() * elem()}, out_tmp;
+			m_encoding->forward(stream, n, input, encoding_params(params), network_input.data(), false, false);
+			if (!output_half) out_tmp = ArenaBuf{stream, (size_t)n * m_network->padded_output_width() * elem()};
+			m_network->inference(stream, n, network_input.data(), output_half ? output_half : out_tmp.data(), params);
+			if (output_f32) trim_and_cast(stream, elem() == 4, n, m_network->padded_output_width(), m_network->output_width(), output_half ? output_half : out_tmp.data(), *output_f32);
 			return;
 		}
 		MlpIo io{};
@@ -2278,9 +2324,9 @@ public:
 			m_network->inference_io(stream, n, io, p);
 			return ctx;
 		}
-		ctx->network_input = ArenaBuf{stream, (size_t)n * m_encoding->padded_output_width() * 2};
-		ctx->encoding_ctx = m_encoding->forward(stream, n, input, p + m_network->n_params(), ctx->network_input.data(), prepare_input_gradients, true);
-		ctx->network_ctx = m_network->forward(stream, n, ctx->network_input.data(), output, p);
+		ctx->network_input = ArenaBuf{stream, (size_t)n * m_encoding->padded_output_width() * elem()};
+		ctx->encoding_ctx = m_encoding->forward(stream, n, input, encoding_params(params), ctx->network_input.data(), prepare_input_gradients, true);
+		ctx->network_ctx = m_network->forward(stream, n, ctx->network_input.data(), output, params);
 		return ctx;
 	}
 
@@ -2289,8 +2335,6 @@ public:
 		check_batch(n);
 		if (n == 0) return;
 		const Ctx& ctx = dynamic_cast<const Ctx&>(mctx);
-		const _Float16* p = (const _Float16*)params;
-		_Float16* g = (_Float16*)gradients;
 		if (ctx.fused) {
 			if (dL_dinput) throw std::runtime_error{"NetworkWithInputEncoding::backward: input gradients were not prepared by forward()"};
 			FusedStepData step;
@@ -2303,14 +2347,14 @@ public:
 		}
 		ArenaBuf dL_dnetwork_input;
 		if (m_encoding->n_params() > 0 || dL_dinput) { // :93-96
-			dL_dnetwork_input = ArenaBuf{stream, (size_t)n * m_encoding->padded_output_width() * 2};
+			dL_dnetwork_input = ArenaBuf{stream, (size_t)n * m_encoding->padded_output_width() * elem()};
 		}
 		// the grid scatter reads dL/d(encoding) with unit stride when the MLP writes it as level planes
 		const GridDyForm offer = dL_dnetwork_input && !m_network->layerwise() ? GridDyForm::Planes : GridDyForm::Rows;
 		const GridBackwardRoute route = m_encoding->backward_route(switches(), stream, ctx.encoding_ctx, n, input, offer, dL_dinput != nullptr, mode);
-		m_network->backward(stream, ctx.network_ctx, n, ctx.network_input.data(), output, dL_doutput, dL_dnetwork_input.data(), p, g, mode, route.plane_features);
+		m_network->backward(stream, ctx.network_ctx, n, ctx.network_input.data(), output, dL_doutput, dL_dnetwork_input.data(), params, gradients, mode, route.plane_features);
 		if (dL_dnetwork_input) {
-			m_encoding->backward(stream, ctx.encoding_ctx, n, input, dL_dnetwork_input.data(), dL_dinput, p + m_network->n_params(), g ? g + m_network->n_params() : nullptr, mode, route);
+			m_encoding->backward(stream, ctx.encoding_ctx, n, input, dL_dnetwork_input.data(), dL_dinput, encoding_params(params), encoding_params(gradients), mode, route);
 		}
 	}
 
@@ -2334,10 +2378,9 @@ public:
 		const bool want_grads = mode != GradientMode::Ignore;
 		if (n == 0 || (!dL_ddLdoutput && !dL_dinput && !want_grads)) return;
 		CHECK_THROW(!want_grads || gradients != nullptr);
-		const _Float16* p = (const _Float16*)params;
-		_Float16* g = want_grads ? (_Float16*)gradients : nullptr;
-		const size_t n_net = m_network->n_params();
-		const size_t enc_bytes = (size_t)n * m_encoding->padded_output_width() * 2;
+		const void* p = params;
+		void* g = want_grads ? gradients : nullptr;
+		const size_t enc_bytes = (size_t)n * m_encoding->padded_output_width() * elem();
 		const bool enc_grads = want_grads && m_encoding->n_params() > 0;
 		// q feeds the encoding's parameter gradients and dL_dinput only
 		const bool want_q = m_network->any_curvature() && (enc_grads || dL_dinput);
@@ -2347,13 +2390,13 @@ public:
 			g_e = ArenaBuf{stream, enc_bytes};
 			ArenaBuf output; // backward() reads it for the output activation's derivative only
 			if (m_network->has_output_activation()) {
-				output = ArenaBuf{stream, (size_t)n * m_network->padded_output_width() * 2};
+				output = ArenaBuf{stream, (size_t)n * m_network->padded_output_width() * elem()};
 				m_network->inference(stream, n, ctx.network_input.data(), output.data(), p);
 			}
 			m_network->backward(stream, ctx.network_ctx, n, ctx.network_input.data(), output.data(), dL_doutput, g_e.data(), p, nullptr, GradientMode::Ignore);
 		}
 		Network::SecondOrderPass pass = m_network->second_order_begin(stream, n, ctx.network_input.data(), dL_doutput, p, want_grads || want_q);
-		m_encoding->backward_backward_input(stream, ctx.encoding_ctx, n, input, dL_ddLdinput, g_e.data(), t.data(), dL_dinput, p + n_net, g ? g + n_net : nullptr, mode);
+		m_encoding->backward_backward_input(stream, ctx.encoding_ctx, n, input, dL_ddLdinput, g_e.data(), t.data(), dL_dinput, encoding_params(p), encoding_params(g), mode);
 		if (want_q) q = ArenaBuf{stream, enc_bytes};
 		m_network->second_order_finish(stream, pass, n, t.data(), dL_ddLdoutput, q.data(), p, g, mode);
 		if (!want_q) return;
@@ -2363,7 +2406,7 @@ public:
 			dx_more = ArenaBuf{stream, (size_t)n * m_encoding->input_width() * sizeof(float)};
 			dx_view.data = dx_more.as<float>();
 		}
-		m_encoding->backward_rows(stream, ctx.encoding_ctx, n, input, q.data(), dL_dinput ? &dx_view : nullptr, p + n_net, enc_grads ? g + n_net : nullptr,
+		m_encoding->backward_rows(stream, ctx.encoding_ctx, n, input, q.data(), dL_dinput ? &dx_view : nullptr, encoding_params(p), enc_grads ? encoding_params(g) : nullptr,
 		                          enc_grads ? GradientMode::Accumulate : GradientMode::Ignore);
 		if (dL_dinput) add_input_gradient(stream, n, m_encoding->input_width(), MatView{dx_view.data, dx_view.stride_sample, dx_view.stride_dim}, *dL_dinput);
 	}
@@ -2594,6 +2637,11 @@ public:
 	}
 
 private:
+	size_t elem() const { return m_network->element_size(); } // bytes of a parameter, an encoded feature, an output, a gradient
+	// the encoding's part of a parameter or gradient vector of the module (the network's comes first); null stays null
+	const void* encoding_params(const void* params) const { return params ? (const char*)params + m_network->n_params() * elem() : nullptr; }
+	void* encoding_params(void* params) const { return params ? (char*)params + m_network->n_params() * elem() : nullptr; }
+
 	bool m_live_image_kept = false;
 	size_t m_image_preps = 0;
 	uint64_t m_list_gradient_tails = 0;

@@ -575,6 +575,24 @@ void mlp_layer_curvature_backward(hipStream_t stream, uint32_t n, const void* p_
                                   const void* r_in, void* p_in, uint32_t ldi);
 void mlp_layer_delta(hipStream_t stream, size_t n_elems, uint32_t activation, const void* g, const void* aux, void* delta); // delta = a'(aux) g, element by element
 void add_input_gradient(hipStream_t stream, uint32_t n, uint32_t dims, MatView src, MatViewMut dst);                          // dst += src, [n][dims] floats
+// ---- the same path in full precision (k_mlp_layers_f32.hip; Network{json, Precision::Fp32}): row-major float matrices, the weights read
+// from the fp32 parameter vector as they are, leading dimensions multiples of 4.  Every product is one ascending-k fmaf chain per
+// element from +0 (the contract at the top of that file); the epilogues are those above with float in place of half.
+void mlp_layer_forward_f32(hipStream_t stream, uint32_t n, const float* x, uint32_t ldx, const float* w, uint32_t rows, uint32_t cols, uint32_t activation, float* y, uint32_t ldy, float* pre);
+void mlp_layer_backward_f32(hipStream_t stream, uint32_t n, const float* dL_dout, uint32_t ldo, const float* wt, uint32_t rows, uint32_t cols, uint32_t activation, const float* aux,
+                            float* dL_din, uint32_t ldi);
+void mlp_layer_transpose_f32(hipStream_t stream, uint32_t rows, uint32_t cols, const float* w, float* wt);
+void mlp_layer_tangent_f32(hipStream_t stream, uint32_t n, const float* u_in, uint32_t ldu, const float* w, uint32_t rows, uint32_t cols, uint32_t activation, const float* aux,
+                           const float* g, float* u_out, float* r_out, uint32_t ldy);
+void mlp_layer_backward_keep_f32(hipStream_t stream, uint32_t n, const float* d_out, uint32_t ldo, const float* wt, uint32_t rows, uint32_t cols, uint32_t activation, const float* aux,
+                                 float* g_in, float* d_in, uint32_t ldi);
+void mlp_layer_curvature_backward_f32(hipStream_t stream, uint32_t n, const float* p_out, uint32_t ldo, const float* wt, uint32_t rows, uint32_t cols, uint32_t activation,
+                                      const float* aux, const float* r_in, float* p_in, uint32_t ldi);
+void mlp_layer_delta_f32(hipStream_t stream, size_t n_elems, uint32_t activation, const float* g, const float* aux, float* delta);
+void mlp_activation_backward_output_f32(hipStream_t stream, size_t n_elems, uint32_t activation, const float* dL_dout, const float* out, float* result);
+// weight gradients of row-major float operands into float grad (panels of at most 128 x 128, never tiled): fp32 slabs summed in a fixed order
+size_t wgrad_panels_workspace_floats_f32(const WgradPanel* panels, uint32_t count, uint32_t n);
+void mlp_wgrad_panels_f32(hipStream_t stream, uint32_t n, const WgradPanel* panels, uint32_t count, bool accumulate, float* workspace);
 
 // ------------------------------------------------------------------------------------------------------------------
 // loss / reduction / optimizer / init plumbing

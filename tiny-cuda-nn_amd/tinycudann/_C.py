@@ -67,6 +67,8 @@ _SIGNATURES = {
     "tcnn_create_network_with_input_encoding": (_int, [_u32, _u32, _cp, _cp, _pp]),
     "tcnn_create_network": (_int, [_u32, _u32, _cp, _pp]),
     "tcnn_create_encoding": (_int, [_u32, _cp, _int, _pp]),
+    "tcnn_create_network_with_input_encoding_precision": (_int, [_u32, _u32, _cp, _cp, _int, _pp]),
+    "tcnn_create_network_precision": (_int, [_u32, _u32, _cp, _int, _pp]),
     "tcnn_module_destroy": (None, [_vp]),
     "tcnn_module_inference": (_int, [_vp, _vp, _u32, _vp, _vp, _vp]),
     "tcnn_module_forward": (_int, [_vp, _vp, _u32, _vp, _vp, _vp, _int, _pp]),

@@ -431,44 +431,62 @@ class Module(torch.nn.Module):
                 f"hyperparams={self.native_tcnn_module.hyperparams()}")
 
 
+_PRECISIONS = {None: None, torch.float32: _C.Precision.Fp32, torch.float16: _C.Precision.Fp16}
+
+
+def _network_precision(what, dtype):
+    """The precision of a module with a network: half unless dtype says torch.float32 (None: half, whatever the preferred precision)."""
+    if dtype not in _PRECISIONS:
+        raise ValueError(f"{what} only supports fp32 or fp16 precision, but got {dtype}")
+    return _C.Precision.Fp16 if dtype is None else _PRECISIONS[dtype]
+
+
 def _needs_networks(what):
     if not _C.has_networks():
         raise RuntimeError(f"Cannot create `{what}` because tiny-cuda-nn was not compiled with neural network support.")
 
 
 class NetworkWithInputEncoding(Module):
-    """Input encoding followed by a neural network: [:, n_input_dims] float -> [:, n_output_dims] (half).
-    Arguments as in the reference (modules.py:219-260): dimensions, the `encoding` and `network` configuration dicts, seed."""
+    """Input encoding followed by a neural network: [:, n_input_dims] float -> [:, n_output_dims] in `dtype` (None: half).
+    Arguments as in the reference (modules.py:219-260): dimensions, the `encoding` and `network` configuration dicts, seed.
+    dtype=torch.float32 is the reference's full-precision build as a choice per module: the encoding's fp32 form in front of a
+    CutlassMLP that computes in fp32 throughout -- no working copy of the parameters, no cast, loss scale 1, float32 output
+    (`"otype": "FullyFusedMLP"` is refused as in that build).  Train such a module with torch.optim."""
 
-    def __init__(self, n_input_dims, n_output_dims, encoding_config, network_config, seed=1337):
+    def __init__(self, n_input_dims, n_output_dims, encoding_config, network_config, seed=1337, dtype=None):
         _needs_networks("NetworkWithInputEncoding")
+        self.precision = _network_precision("NetworkWithInputEncoding", dtype)
         self.n_input_dims, self.n_output_dims = n_input_dims, n_output_dims
         self.encoding_config, self.network_config = encoding_config, network_config
         super().__init__(seed=seed)
 
     def _native_tcnn_module(self):
-        return _create(_C.lib.tcnn_create_network_with_input_encoding, self.n_input_dims, self.n_output_dims,
-                       _C.to_json_bytes(self.encoding_config), _C.to_json_bytes(self.network_config))
+        # (a module pickled before `dtype` existed carries no precision: half)
+        return _create(_C.lib.tcnn_create_network_with_input_encoding_precision, self.n_input_dims, self.n_output_dims,
+                       _C.to_json_bytes(self.encoding_config), _C.to_json_bytes(self.network_config), getattr(self, "precision", _C.Precision.Fp16))
 
 
 class Network(Module):
-    """Neural network on raw inputs (an Identity encoding inside, cpp_api.cu:151-153); arguments as modules.py:262-292."""
+    """Neural network on raw inputs (an Identity encoding inside, cpp_api.cu:151-153); arguments as modules.py:262-292, and
+    `dtype` as for NetworkWithInputEncoding (None: half; torch.float32: a CutlassMLP in full precision)."""
 
-    def __init__(self, n_input_dims, n_output_dims, network_config, seed=1337):
+    def __init__(self, n_input_dims, n_output_dims, network_config, seed=1337, dtype=None):
         _needs_networks("Network")
+        self.precision = _network_precision("Network", dtype)
         self.n_input_dims, self.n_output_dims = n_input_dims, n_output_dims
         self.network_config = network_config
         super().__init__(seed=seed)
 
     def _native_tcnn_module(self):
-        return _create(_C.lib.tcnn_create_network, self.n_input_dims, self.n_output_dims, _C.to_json_bytes(self.network_config))
+        return _create(_C.lib.tcnn_create_network_precision, self.n_input_dims, self.n_output_dims, _C.to_json_bytes(self.network_config),
+                       getattr(self, "precision", _C.Precision.Fp16))
 
 
 class Encoding(Module):
     """Input encoding: [:, n_input_dims] float -> [:, n_output_dims] in `dtype` (default: the preferred precision, half);
     arguments as modules.py:294-329.  n_output_dims is what the native encoding reports."""
 
-    _PRECISIONS = {None: None, torch.float32: _C.Precision.Fp32, torch.float16: _C.Precision.Fp16}
+    _PRECISIONS = _PRECISIONS
 
     def __init__(self, n_input_dims, encoding_config, seed=1337, dtype=None):
         if dtype not in self._PRECISIONS:
