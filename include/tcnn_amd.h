@@ -136,10 +136,22 @@ const char* tcnn_module_name(tcnn_module_t m);             /* cpp_api.cu:139 */
 /* ---- boundary A: create_from_config / Trainer (config.h:53-63, trainer.h:48-363) ---- */
 int  tcnn_create_from_config(uint32_t n_input_dims, uint32_t n_output_dims, const char* config_json, tcnn_trainer_t* out);          /* seed 1337, trainer.h:50 */
 int  tcnn_create_from_config_seeded(uint32_t n_input_dims, uint32_t n_output_dims, const char* config_json, uint32_t seed, tcnn_trainer_t* out);
+/* The trainer's precision as an argument (TCNN_PRECISION_*; the two factories above are the FP16 case).  FP32 is Trainer<float, float, float>
+ * of the reference's build without TCNN_HALF_PRECISION: the fp32 module (tcnn_create_network_with_input_encoding_precision), the loss on float
+ * predictions, an optimizer with fp32 weights, loss scale tcnn_default_loss_scale(TCNN_PRECISION_FP32) = 1.  Such a trainer has ONE float
+ * parameter vector -- tcnn_trainer_params == tcnn_trainer_params_full_precision -- and every training_step is the unfused sequence
+ * (tcnn_trainer_last_step_kernel: "unfused").  Every pointer typed void* below -- tcnn_trainer_params, _params_inference, _param_gradients,
+ * tcnn_train_ctx_output, _dL_doutput -- points at elements of the trainer's precision; tcnn_trainer_set_params and external_dL_dy take that
+ * precision, and tcnn_trainer_inference_mixed_precision writes it.  The initial parameters are the same floats for either precision and the
+ * same seed.  Configuration errors ("FullyFusedMLP can only be used if the network precision is set to __half.", an invalid loss or
+ * optimizer type, "Unknown precision N") are reported before anything is allocated on the device. */
+int  tcnn_create_from_config_precision(uint32_t n_input_dims, uint32_t n_output_dims, const char* config_json, uint32_t seed, int precision, tcnn_trainer_t* out);
+int  tcnn_trainer_precision(tcnn_trainer_t t);                    /* TCNN_PRECISION_*; -1 + tcnn_last_error() for a NULL handle */
 void tcnn_trainer_destroy(tcnn_trainer_t t);
 
 /* Trainer::training_step (trainer.h:163-190).  input: float, n_input_dims x n in `input_layout`; target: float [n][n_output_dims];
- * data_pdf (optional) like target; dL_dinput (optional) float in input_layout; external_dL_dy (optional) half [n][padded_out].
+ * data_pdf (optional) like target; dL_dinput (optional) float in input_layout; external_dL_dy (optional) [n][padded_out] in the trainer's
+ * precision (half, or float for an FP32 trainer).
  * Returns the forward context (caller destroys it) -- loss is fetched with tcnn_trainer_loss like trainer->loss(stream, *ctx). */
 int  tcnn_trainer_training_step(tcnn_trainer_t t, tcnn_stream_t stream, uint32_t n_elements, const float* input, int input_layout,
                                 const float* target, const float* data_pdf, int run_optimizer, float* dL_dinput, int use_inference_params,
@@ -156,26 +168,27 @@ void tcnn_train_ctx_destroy(tcnn_train_ctx_t ctx);
 /* ForwardContext members (trainer.h:89-95): device pointers valid until the context is destroyed.
  * The fused training step keeps dL_doutput and L as dense [n][n_output_dims] matrices (the padding columns are zeros) and forms
  * the padded ones on the FIRST call of their accessor, on the step's stream. */
-const void*  tcnn_train_ctx_output(tcnn_train_ctx_t ctx);      /* half  [n][padded_out] */
-const void*  tcnn_train_ctx_dL_doutput(tcnn_train_ctx_t ctx);  /* half  [n][padded_out]; NULL + tcnn_last_error() on failure */
+const void*  tcnn_train_ctx_output(tcnn_train_ctx_t ctx);      /* half  [n][padded_out] (float from an FP32 trainer) */
+const void*  tcnn_train_ctx_dL_doutput(tcnn_train_ctx_t ctx);  /* half  [n][padded_out] (float from an FP32 trainer); NULL + tcnn_last_error() on failure */
 const float* tcnn_train_ctx_L(tcnn_train_ctx_t ctx);           /* float [n][padded_out]; NULL + tcnn_last_error() on failure */
 
 /* network->inference(stream, input, output) (object.h:147-176): float in, float out [n_output_dims x n] in output_layout */
 int  tcnn_trainer_inference(tcnn_trainer_t t, tcnn_stream_t stream, uint32_t n_elements, const float* input, int input_layout,
                             float* output, int output_layout, int use_inference_params);
 /* network->inference_mixed_precision(stream, input, output) (object.h:133-145): the network's own output, half
- * [n_elements][padded_output_width] -- what inference() casts to float; half the bytes for a caller that gathers row shards */
+ * [n_elements][padded_output_width] -- what inference() casts to float; half the bytes for a caller that gathers row shards.
+ * An FP32 trainer writes floats. */
 int  tcnn_trainer_inference_mixed_precision(tcnn_trainer_t t, tcnn_stream_t stream, uint32_t n_elements, const float* input, int input_layout,
                                             void* output_half, int use_inference_params);
 
 size_t   tcnn_trainer_n_params(tcnn_trainer_t t);                 /* trainer.h:338 */
 uint32_t tcnn_trainer_padded_output_width(tcnn_trainer_t t);
 float*   tcnn_trainer_params_full_precision(tcnn_trainer_t t);    /* trainer.h:226 */
-void*    tcnn_trainer_params(tcnn_trainer_t t);                   /* trainer.h:230 (half) */
+void*    tcnn_trainer_params(tcnn_trainer_t t);                   /* trainer.h:230 (half; an FP32 trainer: its float vector, = params_full_precision) */
 void*    tcnn_trainer_params_inference(tcnn_trainer_t t);         /* trainer.h:234 */
-void*    tcnn_trainer_param_gradients(tcnn_trainer_t t);          /* trainer.h:238 (half) */
+void*    tcnn_trainer_param_gradients(tcnn_trainer_t t);          /* trainer.h:238 (half; float for an FP32 trainer) */
 int      tcnn_trainer_set_params_full_precision(tcnn_trainer_t t, const float* params, size_t n_params, int device_ptr); /* trainer.h:242 */
-int      tcnn_trainer_set_params(tcnn_trainer_t t, const void* params_half, size_t n_params, int device_ptr);            /* trainer.h:256 */
+int      tcnn_trainer_set_params(tcnn_trainer_t t, const void* params_half, size_t n_params, int device_ptr);            /* trainer.h:256 (floats for an FP32 trainer) */
 int      tcnn_trainer_initialize_params(tcnn_trainer_t t);        /* trainer.h:68-87 (re-initialise, continues the rng stream) */
 int      tcnn_trainer_update_hyperparams(tcnn_trainer_t t, const char* json); /* trainer.h:213 */
 const char* tcnn_trainer_hyperparams(tcnn_trainer_t t);           /* trainer.h:218; JSON text owned by the trainer */
@@ -184,7 +197,10 @@ const char* tcnn_trainer_hyperparams(tcnn_trainer_t t);           /* trainer.h:2
  * {"current_step", "base_learning_rate", "first_moments_binary", "second_moments_binary", "param_steps_binary"}]} as
  * MessagePack bytes, encoded the way nlohmann::json::to_msgpack encodes it (what instant-ngp-style callers write to disk).
  * serialize: the buffer belongs to the trainer and stays valid until its next serialize call or its destruction.
- * deserialize: accepts "params_type" "__half" or "float", binary values or their text form {"bytes": [...]}. */
+ * An FP32 trainer writes "params_type": "float" and 4 n_params bytes, and the custom-weight blobs of its optimizer (Ema, Average, Lookahead)
+ * hold floats.
+ * deserialize: accepts "params_type" "__half" or "float" in a trainer of either precision (cast as trainer.h:296-305 does), binary values or
+ * their text form {"bytes": [...]}.  Optimizer state whose blobs are of the other weight precision is an error, never reinterpreted. */
 int      tcnn_trainer_serialize(tcnn_trainer_t t, int serialize_optimizer, const void** out_bytes, size_t* out_size);
 int      tcnn_trainer_deserialize(tcnn_trainer_t t, const void* bytes, size_t size);
 const char* tcnn_trainer_network_hyperparams(tcnn_trainer_t t);   /* network->hyperparams() */
@@ -271,9 +287,18 @@ int tcnn_train_ctx_keeps_weight_gradient_slabs(tcnn_trainer_t t, tcnn_train_ctx_
  * custom_weights: half[n_params] the optimizer keeps for inference (Ema, Average, Lookahead; Composite when a nested one has any), or NULL.
  * The getters return 0 / NaN / NULL and leave a message in tcnn_last_error() when given a NULL handle.
  * weights_restored: call after overwriting params_half by other means, and after deserialize (optimizers that assemble their custom
- * weights from several sources -- Composite -- rebuild them from params_half; a snapshot does not carry them). */
+ * weights from several sources -- Composite -- rebuild them from params_half; a snapshot does not carry them).
+ * tcnn_optimizer_create_precision: the weights' precision as an argument (tcnn_optimizer_create is the FP16 case).  TCNN_PRECISION_FP32 is
+ * Optimizer<float>: ONE float weight vector -- the master vector is the working vector, read and stored once per step.  tcnn_optimizer_step
+ * then takes params_half == NULL or == params_full_precision and gradient_precision == TCNN_PRECISION_FP32 (anything else is an error);
+ * custom_weights points at float[n_params]; weights_restored takes the float vector; the snapshot's custom-weight blobs hold floats, and a
+ * blob of another size than n_params elements of the optimizer's weight precision is an error.  The master-weight arithmetic is the same:
+ * Adam, SGD, Novograd, ExponentialDecay, Batched and a Composite of those leave master weights, moments and step counts bit-identical to
+ * the FP16-weight optimizer stepped on the same fp32 gradients.  "Unknown precision N" for any other value. */
 int         tcnn_module_layer_sizes(tcnn_module_t m, uint32_t* rows_cols, size_t capacity, size_t* n_layers_out);
 int         tcnn_optimizer_create(const char* optimizer_json, size_t n_params, const uint32_t* layer_sizes, size_t n_layers, tcnn_optimizer_t* out);
+int         tcnn_optimizer_create_precision(const char* optimizer_json, size_t n_params, const uint32_t* layer_sizes, size_t n_layers, int weight_precision, tcnn_optimizer_t* out);
+int         tcnn_optimizer_weight_precision(tcnn_optimizer_t o);                                /* TCNN_PRECISION_*; -1 + tcnn_last_error() for a NULL handle */
 void        tcnn_optimizer_destroy(tcnn_optimizer_t o);
 int         tcnn_optimizer_step(tcnn_optimizer_t o, tcnn_stream_t stream, float loss_scale, float* params_full_precision, void* params_half,
                                 const void* gradients, int gradient_precision);                 /* optimizer.h:49 */

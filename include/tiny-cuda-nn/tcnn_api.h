@@ -11,6 +11,8 @@
 //   tcnn::NetworkWithInputEncoding<T>              network_with_input_encoding.h:40-180
 //   tcnn::Trainer<T, PARAMS_T, COMPUTE_T>          trainer.h:48-363  (training_step, loss, inference via the network, params)
 //   tcnn::TrainableModel, create_from_config       config.h:46-63
+//   tcnn::TrainableModelT<T>, create_from_config_as<T>   the same for a chosen precision: <float> is the reference's build without
+//                                                  TCNN_HALF_PRECISION (Trainer<float, float, float>, Loss<float>, Optimizer<float>)
 //   tcnn::free_all_gpu_memory_arenas               gpu_memory.h:751
 // Errors are std::runtime_error carrying the library's message, as in the reference (common_host.h:71-110).
 // The objects are thin: a Trainer owns the native trainer handle; the NetworkWithInputEncoding, Loss and Optimizer objects
@@ -27,6 +29,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -49,10 +52,16 @@ namespace detail {
 inline void check(int rc) {
 	if (rc != TCNN_OK) throw std::runtime_error{tcnn_last_error()};
 }
+// the TCNN_PRECISION_* of an element type: half or float, nothing else
+template <typename T> struct precision_of { static_assert(sizeof(T) == 0, "tcnn: the precision is half or float"); };
+template <> struct precision_of<half> { static constexpr int value = TCNN_PRECISION_FP16; };
+template <> struct precision_of<float> { static constexpr int value = TCNN_PRECISION_FP32; };
 inline std::string to_text(const json& j) { return j.dump(); }
 inline std::string to_text(const std::string& s) { return s; }
 inline std::string to_text(const char* s) { return s; }
 template <typename J> auto to_text(const J& j) -> decltype(j.dump()) { return j.dump(); } // e.g. nlohmann::json
+inline json to_json(const json& j) { return j; }
+template <typename J> json to_json(const J& j) { return json::parse(to_text(j)); } // text, or another json type
 } // namespace detail
 
 inline void free_all_gpu_memory_arenas() { tcnn_free_temporary_memory(); }
@@ -165,7 +174,9 @@ private:
 template <typename T> Loss<T>* create_loss(const json& params) { return new Loss<T>{params}; }
 
 // optimizer.h:40-66.  Configuration only until allocate(), which makes the native optimizer (tcnn_optimizer_t); a Trainer does not
-// need that -- it builds its own optimizer from hyperparams().  T is the type of the working weights and of the gradients: half.
+// need that -- it builds its own optimizer from hyperparams().  T is the type of the working weights and of the gradients: half, or
+// float -- then there is ONE weight vector: step() takes weights == weights_full_precision (or nullptr) and fp32 gradients, and
+// custom_weights() points at floats.
 template <typename T>
 class Optimizer {
 public:
@@ -175,20 +186,22 @@ public:
 	~Optimizer() { if (m_handle) tcnn_optimizer_destroy(m_handle); }
 
 	void allocate(size_t n_weights, const std::vector<std::pair<uint32_t, uint32_t>>& layer_sizes = {}) {
-		static_assert(sizeof(T) == 2, "tcnn::Optimizer<T>: the working weights are half precision");
+		static_assert(std::is_same<T, half>::value || std::is_same<T, float>::value, "tcnn::Optimizer<T>: the working weights are half or float");
 		std::vector<uint32_t> flat;
 		for (const auto& ls : layer_sizes) { flat.push_back(ls.first); flat.push_back(ls.second); }
 		tcnn_optimizer_t fresh = nullptr;
-		detail::check(tcnn_optimizer_create(m_params.dump().c_str(), n_weights, flat.data(), layer_sizes.size(), &fresh));
+		detail::check(tcnn_optimizer_create_precision(m_params.dump().c_str(), n_weights, flat.data(), layer_sizes.size(), detail::precision_of<T>::value, &fresh));
 		if (m_handle) tcnn_optimizer_destroy(m_handle);
 		m_handle = fresh;
 	}
 	// gradients: scaled by loss_scale, like the ones a Trainer's backward pass writes
 	void step(stream_t stream, float loss_scale, float* weights_full_precision, T* weights, const T* gradients) {
-		detail::check(tcnn_optimizer_step(allocated("step"), stream, loss_scale, weights_full_precision, weights, gradients, TCNN_PRECISION_FP16));
+		detail::check(tcnn_optimizer_step(allocated("step"), stream, loss_scale, weights_full_precision, weights, gradients, detail::precision_of<T>::value));
 	}
-	// the same on fp32 gradients (no counterpart in the reference): read as they are, never rounded to half
-	void step(stream_t stream, float loss_scale, float* weights_full_precision, T* weights, const float* gradients) {
+	// the same on fp32 gradients (no counterpart in the reference): read as they are, never rounded to half.  (Optimizer<float>: the
+	// overload above already is this one.)
+	template <typename U = T>
+	void step(stream_t stream, float loss_scale, float* weights_full_precision, typename std::enable_if<!std::is_same<U, float>::value, U>::type* weights, const float* gradients) {
 		detail::check(tcnn_optimizer_step(allocated("step"), stream, loss_scale, weights_full_precision, weights, gradients, TCNN_PRECISION_FP32));
 	}
 	float learning_rate() const { return tcnn_optimizer_learning_rate(allocated("learning_rate")); }
@@ -289,8 +302,13 @@ private:
 };
 
 // ---------------------------------------------------------------------------------------------------------------- Trainer
+// <float, half, half>: the mixed-precision trainer.  <float, float, float>: the full-precision one -- params() == params_full_precision(),
+// float output / dL_doutput / gradients, loss scale 1, every training_step unfused.
 template <typename T, typename PARAMS_T, typename COMPUTE_T = T>
 class Trainer {
+	static_assert(std::is_same<T, float>::value, "tcnn::Trainer<T, PARAMS_T, COMPUTE_T>: the input type T is float");
+	static_assert(std::is_same<PARAMS_T, COMPUTE_T>::value && (std::is_same<COMPUTE_T, half>::value || std::is_same<COMPUTE_T, float>::value),
+	              "tcnn::Trainer<T, PARAMS_T, COMPUTE_T>: parameters and compute are both half or both float");
 public:
 	struct ForwardContext { // trainer.h:89-95
 		tcnn_train_ctx_t handle = nullptr;
@@ -308,7 +326,7 @@ public:
 		config["network"] = m_model->network_config();
 		config["optimizer"] = m_optimizer->hyperparams();
 		config["loss"] = m_loss->hyperparams();
-		detail::check(tcnn_create_from_config_seeded(m_model->input_width(), m_model->output_width(), config.dump().c_str(), seed, &m_handle));
+		detail::check(tcnn_create_from_config_precision(m_model->input_width(), m_model->output_width(), config.dump().c_str(), seed, detail::precision_of<COMPUTE_T>::value, &m_handle));
 		try {
 			m_model->bind(m_handle);
 		} catch (...) {
@@ -381,23 +399,31 @@ private:
 };
 
 // ----------------------------------------------------------------------------------------------------- config.h:46-63
-struct TrainableModel {
-	std::shared_ptr<Loss<network_precision_t>> loss;
-	std::shared_ptr<Optimizer<network_precision_t>> optimizer;
-	std::shared_ptr<NetworkWithInputEncoding<network_precision_t>> network;
-	std::shared_ptr<Trainer<float, network_precision_t, network_precision_t>> trainer;
+template <typename T>
+struct TrainableModelT {
+	std::shared_ptr<Loss<T>> loss;
+	std::shared_ptr<Optimizer<T>> optimizer;
+	std::shared_ptr<NetworkWithInputEncoding<T>> network;
+	std::shared_ptr<Trainer<float, T, T>> trainer;
 };
+typedef TrainableModelT<network_precision_t> TrainableModel;
 
-inline TrainableModel create_from_config(uint32_t n_input_dims, uint32_t n_output_dims, json config) {
+// create_from_config for a chosen precision: create_from_config_as<float>(...) trains in full precision
+template <typename T, typename J>
+inline TrainableModelT<T> create_from_config_as(uint32_t n_input_dims, uint32_t n_output_dims, const J& config_in) {
+	const json config = detail::to_json(config_in);
 	const json encoding_opts = config.value("encoding", json::object());
 	const json loss_opts = config.value("loss", json::object());
 	const json optimizer_opts = config.value("optimizer", json::object());
 	const json network_opts = config.value("network", json::object());
-	std::shared_ptr<Loss<network_precision_t>> loss{create_loss<network_precision_t>(loss_opts)};
-	std::shared_ptr<Optimizer<network_precision_t>> optimizer{create_optimizer<network_precision_t>(optimizer_opts)};
-	auto network = std::make_shared<NetworkWithInputEncoding<network_precision_t>>(n_input_dims, n_output_dims, encoding_opts, network_opts);
-	auto trainer = std::make_shared<Trainer<float, network_precision_t, network_precision_t>>(network, optimizer, loss);
+	std::shared_ptr<Loss<T>> loss{create_loss<T>(loss_opts)};
+	std::shared_ptr<Optimizer<T>> optimizer{create_optimizer<T>(optimizer_opts)};
+	auto network = std::make_shared<NetworkWithInputEncoding<T>>(n_input_dims, n_output_dims, encoding_opts, network_opts);
+	auto trainer = std::make_shared<Trainer<float, T, T>>(network, optimizer, loss);
 	return {loss, optimizer, network, trainer};
+}
+inline TrainableModel create_from_config(uint32_t n_input_dims, uint32_t n_output_dims, json config) {
+	return create_from_config_as<network_precision_t>(n_input_dims, n_output_dims, config);
 }
 template <typename J>
 inline TrainableModel create_from_config(uint32_t n_input_dims, uint32_t n_output_dims, const J& config) { return create_from_config(n_input_dims, n_output_dims, json::parse(detail::to_text(config))); }

@@ -12,8 +12,9 @@ namespace tcnn_amd {
 // debias_of(t): the debiasing factor of step t <= common_step (a lookup in the optimizer's table).
 // G: the type the gradient was loaded as, _Float16 (the trainer's gradient vector) or float (a caller's own fp32 gradients, standalone
 // optimizers): the value is taken to float as it is and unscaled the same way -- no rounding in between for either type.
-template <typename DebiasOf, typename G>
-__device__ inline void adam_one(const AdamArgs& a, DebiasOf&& debias_of, const float common_debias, const bool is_matrix, const G g_in, float& w_fp, _Float16& w_h,
+// W: the working weights' type, _Float16, or float for an optimizer whose master vector is its working vector (w_h then equals w_fp's new value).
+template <typename DebiasOf, typename G, typename W>
+__device__ inline void adam_one(const AdamArgs& a, DebiasOf&& debias_of, const float common_debias, const bool is_matrix, const G g_in, float& w_fp, W& w_h,
                                 float& m1, float& m2, uint32_t& step, bool& updated) {
 	const float g = (float)g_in;
 	// loss_scale is a power of two in practice (128): the reciprocal multiply is then exact, i.e. identical to the division
@@ -36,7 +37,7 @@ __device__ inline void adam_one(const AdamArgs& a, DebiasOf&& debias_of, const f
 	float new_weight = decayed_weight - effective_learning_rate * first_moment;
 	if (a.weight_clipping_magnitude != 0.0f) new_weight = fminf(fmaxf(new_weight, -a.weight_clipping_magnitude), a.weight_clipping_magnitude);
 	w_fp = updated ? new_weight : weight_fp;
-	w_h = (_Float16)new_weight; // stored only if updated
+	w_h = (W)new_weight; // stored only if updated
 	m1 = updated ? first_moment : m1;
 	m2 = updated ? second_moment : m2;
 	step = updated ? current_step : step;

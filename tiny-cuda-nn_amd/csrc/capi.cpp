@@ -306,14 +306,25 @@ const char* tcnn_module_name(tcnn_module_t m) {
 }
 
 // ---------------------------------------------------------------------------------------------------------- trainer
-int tcnn_create_from_config_seeded(uint32_t n_input_dims, uint32_t n_output_dims, const char* config_json, uint32_t seed, tcnn_trainer_t* out) {
+int tcnn_create_from_config_precision(uint32_t n_input_dims, uint32_t n_output_dims, const char* config_json, uint32_t seed, int precision, tcnn_trainer_t* out) {
 	switches_reload(); // the A/B switches are read once per model (tcnn_common.h: Switches)
 	return guarded([&] {
 		CHECK_THROW(out != nullptr);
+		if (precision != TCNN_PRECISION_FP32 && precision != TCNN_PRECISION_FP16) throw std::runtime_error{"Unknown precision " + std::to_string(precision)};
 		auto t = std::make_unique<tcnn_trainer_s>();
-		t->trainer.reset(new Trainer{n_input_dims, n_output_dims, parse_or_empty(config_json), seed});
+		t->trainer.reset(new Trainer{n_input_dims, n_output_dims, parse_or_empty(config_json), seed, precision == TCNN_PRECISION_FP32 ? Precision::Fp32 : Precision::Fp16});
 		*out = t.release();
 	});
+}
+
+int tcnn_create_from_config_seeded(uint32_t n_input_dims, uint32_t n_output_dims, const char* config_json, uint32_t seed, tcnn_trainer_t* out) {
+	return tcnn_create_from_config_precision(n_input_dims, n_output_dims, config_json, seed, TCNN_PRECISION_FP16, out);
+}
+
+int tcnn_trainer_precision(tcnn_trainer_t t) {
+	int v = -1;
+	guarded([&] { CHECK_THROW(t && t->trainer); v = (int)t->trainer->precision(); });
+	return v;
 }
 
 int tcnn_create_from_config(uint32_t n_input_dims, uint32_t n_output_dims, const char* config_json, tcnn_trainer_t* out) {
@@ -520,9 +531,20 @@ int tcnn_module_layer_sizes(tcnn_module_t m, uint32_t* rows_cols, size_t capacit
 }
 
 int tcnn_optimizer_create(const char* optimizer_json, size_t n_params, const uint32_t* layer_sizes, size_t n_layers, tcnn_optimizer_t* out) {
+	return tcnn_optimizer_create_precision(optimizer_json, n_params, layer_sizes, n_layers, TCNN_PRECISION_FP16, out);
+}
+
+int tcnn_optimizer_weight_precision(tcnn_optimizer_t o) {
+	int v = -1;
+	guarded([&] { CHECK_THROW(o && o->optimizer); v = (int)o->optimizer->weight_precision(); });
+	return v;
+}
+
+int tcnn_optimizer_create_precision(const char* optimizer_json, size_t n_params, const uint32_t* layer_sizes, size_t n_layers, int weight_precision, tcnn_optimizer_t* out) {
 	switches_reload(); // the A/B switches are read once per model (tcnn_common.h: Switches)
 	return guarded([&] {
 		CHECK_THROW(out != nullptr && (layer_sizes != nullptr || n_layers == 0));
+		if (weight_precision != TCNN_PRECISION_FP32 && weight_precision != TCNN_PRECISION_FP16) throw std::runtime_error{"Unknown precision " + std::to_string(weight_precision)};
 		auto o = std::make_unique<tcnn_optimizer_s>();
 		o->optimizer = create_optimizer(parse_or_empty(optimizer_json)); // the configuration is checked here: nothing on the device yet
 		std::vector<std::pair<uint32_t, uint32_t>> sizes;
@@ -532,7 +554,7 @@ int tcnn_optimizer_create(const char* optimizer_json, size_t n_params, const uin
 			n_matrix += (size_t)layer_sizes[2 * i] * layer_sizes[2 * i + 1];
 		}
 		if (n_matrix > n_params) throw std::runtime_error{"Optimizer: the layer sizes hold more weights than n_params."};
-		o->optimizer->allocate(n_params, sizes);
+		o->optimizer->allocate(n_params, sizes, weight_precision == TCNN_PRECISION_FP32 ? Precision::Fp32 : Precision::Fp16);
 		o->n_params = n_params;
 		HIP_CHECK_THROW(hipDeviceSynchronize()); // the state's memsets ran on the null stream; steps run on the caller's
 		*out = o.release();
@@ -545,7 +567,7 @@ int tcnn_optimizer_step(tcnn_optimizer_t o, tcnn_stream_t stream, float loss_sca
 	return guarded([&] {
 		CHECK_THROW(o && o->optimizer);
 		CHECK_THROW(gradient_precision == TCNN_PRECISION_FP32 || gradient_precision == TCNN_PRECISION_FP16);
-		CHECK_THROW(o->n_params == 0 || (params_full_precision && params_half && gradients));
+		CHECK_THROW(o->n_params == 0 || (params_full_precision && (params_half || o->optimizer->fp32_weights()) && gradients)); // (fp32 weights: ONE vector)
 		o->optimizer->step((hipStream_t)stream, loss_scale, params_full_precision, params_half, gradients, (GradientPrecision)gradient_precision);
 		HIP_CHECK_THROW(hipGetLastError());
 	});

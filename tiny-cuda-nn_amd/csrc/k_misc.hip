@@ -203,8 +203,10 @@ __global__ void __launch_bounds__(256) k_identity_bwd_bwd_input(const uint32_t n
 
 // ---- loss: l2.h:40-74 / relative_l2.h:40-75 and the other element-wise losses.  One element: the reference's expressions, term for term.
 // (row: the sample's padded prediction row -- RelativeL2Luminance reads the pixel's other channels from it)
+// P: the predictions' and gradients' type, half_t, or float (Loss<float>: the cast of the gradient is then no rounding)
+template <typename P>
 __device__ inline void loss_element(const uint32_t type, const float prediction, const float target, const float pdf, const uint32_t n_total, const float loss_scale,
-                                    const half_t* __restrict__ row, const uint32_t dims, float& value_out, half_t& grad_out) {
+                                    const P* __restrict__ row, const uint32_t dims, float& value_out, P& grad_out) {
 	const float difference = prediction - target;
 	float value, gradient;
 	switch ((LossType)type) {
@@ -215,7 +217,7 @@ __device__ inline void loss_element(const uint32_t type, const float prediction,
 			break;
 		}
 		case LossType::RelativeL2Luminance: { // relative_l2_luminance.h:40-85: the divisor is the squared luminance of the pixel
-			const half_t* px = row;
+			const P* px = row;
 			float r = (float)px[0], g = (float)px[1], b = (float)px[2];
 			if (dims >= 6) {
 				r += (float)px[3];
@@ -253,13 +255,13 @@ __device__ inline void loss_element(const uint32_t type, const float prediction,
 		case LossType::CrossEntropy: { // cross_entropy.h:40-72: the gradient already carries 1 / n_total
 			const float factor = -target / pdf / n_total;
 			value_out = factor * logf(prediction);
-			grad_out = (half_t)(loss_scale * (factor / prediction));
+			grad_out = (P)(loss_scale * (factor / prediction));
 			return;
 		}
 		case LossType::Variance: { // variance_is.h:40-72
 			const float factor = target * target / pdf / n_total;
 			value_out = factor / prediction - factor / pdf;
-			grad_out = (half_t)(loss_scale * (-factor / (prediction * prediction)));
+			grad_out = (P)(loss_scale * (-factor / (prediction * prediction)));
 			return;
 		}
 		default: // L2, l2.h:60-72
@@ -268,13 +270,14 @@ __device__ inline void loss_element(const uint32_t type, const float prediction,
 			break;
 	}
 	value_out = value;
-	grad_out = (half_t)(loss_scale * gradient / n_total);
+	grad_out = (P)(loss_scale * gradient / n_total);
 }
 
 // one thread per padded output element (any stride)
+template <typename P>
 __global__ void __launch_bounds__(256) k_loss(
 	const uint32_t type, const uint32_t n_elements, const uint32_t stride, const uint32_t dims, const float loss_scale,
-	const half_t* __restrict__ predictions, const float* __restrict__ targets, float* __restrict__ values, half_t* __restrict__ gradients, const float* __restrict__ data_pdf
+	const P* __restrict__ predictions, const float* __restrict__ targets, float* __restrict__ values, P* __restrict__ gradients, const float* __restrict__ data_pdf
 ) {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n_elements) return;
@@ -282,7 +285,7 @@ __global__ void __launch_bounds__(256) k_loss(
 	const uint32_t inter = i / stride;
 	if (intra >= dims) {
 		values[i] = 0;
-		gradients[i] = (half_t)0.0f;
+		gradients[i] = (P)0.0f;
 		return;
 	}
 	const uint32_t target_idx = inter * dims + intra;
@@ -290,7 +293,7 @@ __global__ void __launch_bounds__(256) k_loss(
 	const float prediction = (float)predictions[i];
 	const float pdf = data_pdf ? data_pdf[target_idx] : 1;
 	float value;
-	half_t grad;
+	P grad;
 	loss_element(type, prediction, targets[target_idx], pdf, n_total, loss_scale, predictions + (i - intra), dims, value, grad);
 	values[i] = value;
 	gradients[i] = grad;
@@ -325,6 +328,33 @@ __global__ void __launch_bounds__(256) k_loss8(
 	*(float4*)(values + i0) = float4{v[0], v[1], v[2], v[3]};
 	*(float4*)(values + i0 + 4) = float4{v[4], v[5], v[6], v[7]};
 	*(h8*)(gradients + i0) = g;
+}
+
+// Float predictions, strides that are multiples of 4 (every network's padded output): four consecutive elements per thread -- one 16-byte
+// load of predictions, one 16-byte store of values, one of gradients.  Same expressions per element as k_loss<float>, same bits.
+__global__ void __launch_bounds__(256) k_loss4_f32(
+	const uint32_t type, const uint32_t n_elements, const uint32_t stride, const uint32_t dims, const uint32_t n_total, const float loss_scale,
+	const float* __restrict__ predictions, const float* __restrict__ targets, float* __restrict__ values, float* __restrict__ gradients, const float* __restrict__ data_pdf
+) {
+	const uint32_t i0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
+	if (i0 >= n_elements) return;
+	const uint32_t inter = i0 / stride, intra0 = i0 - inter * stride;
+	const float4 pv4 = *(const float4*)(predictions + i0);
+	const float pv[4] = {pv4.x, pv4.y, pv4.z, pv4.w};
+	float v[4], g[4];
+#pragma unroll
+	for (int k = 0; k < 4; ++k) {
+		const uint32_t intra = intra0 + k;
+		v[k] = 0;
+		g[k] = 0;
+		if (intra < dims) {
+			const uint32_t target_idx = inter * dims + intra;
+			const float pdf = data_pdf ? data_pdf[target_idx] : 1;
+			loss_element(type, pv[k], targets[target_idx], pdf, n_total, loss_scale, predictions + (i0 - intra0), dims, v[k], g[k]);
+		}
+	}
+	*(float4*)(values + i0) = float4{v[0], v[1], v[2], v[3]};
+	*(float4*)(gradients + i0) = float4{g[0], g[1], g[2], g[3]};
 }
 
 // ---- deterministic two-stage sum: stage 1 = one partial per block (fixed grid), stage 2 = one block sums the partials
@@ -399,10 +429,12 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 template <typename G> struct GradQuad;
 template <> struct GradQuad<half_t> { typedef h4 type; };
 template <> struct GradQuad<float> { typedef f4 type; };
-template <bool QUAD_UNIFORM, typename STEP_T, typename G>
+// W: the working weights' type.  half_t: w is the half copy of w_fp.  float: w_fp is the optimizer's one weight vector -- read once, stored
+// once, w is not touched (30 - 32 B/param instead of 32 - 36) -- and G is float.
+template <bool QUAD_UNIFORM, typename STEP_T, typename G, typename W>
 __global__ void __launch_bounds__(256) k_adam(
 	const AdamArgs a, const size_t n, const size_t n_matrix,
-	float* __restrict__ w_fp, half_t* __restrict__ w, const G* __restrict__ g, float* __restrict__ m1, float* __restrict__ m2, STEP_T* __restrict__ steps,
+	float* __restrict__ w_fp, W* __restrict__ w, const G* __restrict__ g, float* __restrict__ m1, float* __restrict__ m2, STEP_T* __restrict__ steps,
 	const float* __restrict__ debias_table
 ) {
 	const size_t base = (size_t)blockIdx.x * (256 * 4 * ADAM_Q) + threadIdx.x * 4;
@@ -442,7 +474,7 @@ __global__ void __launch_bounds__(256) k_adam(
 	for (int q = 0; q < ADAM_Q; ++q) {
 		const size_t i4 = base + (size_t)q * 1024;
 		if (live[q]) {
-			half_t wh[4];
+			W wh[4];
 			bool up[4];
 			const bool quad_matrix = i4 < n_matrix;
 			adam_one(a, from_table, debias, QUAD_UNIFORM ? quad_matrix : i4 + 0 < n_matrix, gv[q][0], wf[q].x, wh[0], a1[q].x, a2[q].x, st[q].x, up[0]);
@@ -453,20 +485,22 @@ __global__ void __launch_bounds__(256) k_adam(
 			*(float4*)(m1 + i4) = a1[q];
 			*(float4*)(m2 + i4) = a2[q];
 			adam_store_steps(steps + i4, st[q]);
-			if (up[0] && up[1] && up[2] && up[3]) {
-				*(h4*)(w + i4) = h4{wh[0], wh[1], wh[2], wh[3]};
-			} else { // skipped parameters keep their half value, whatever it is: only the updated ones are stored
+			if constexpr (sizeof(W) == 2) {
+				if (up[0] && up[1] && up[2] && up[3]) {
+					*(h4*)(w + i4) = h4{wh[0], wh[1], wh[2], wh[3]};
+				} else { // skipped parameters keep their half value, whatever it is: only the updated ones are stored
 #pragma unroll
-				for (int e = 0; e < 4; ++e) if (up[e]) w[i4 + e] = wh[e];
+					for (int e = 0; e < 4; ++e) if (up[e]) w[i4 + e] = wh[e];
+				}
 			}
 		} else if (i4 < n && i4 + 4 > n) { // ragged tail
 			for (size_t i = i4; i < n; ++i) {
 				bool up;
-				half_t wh;
+				W wh;
 				uint32_t st1 = steps[i];
 				adam_one(a, from_table, debias, i < n_matrix, g[i], w_fp[i], wh, m1[i], m2[i], st1, up);
 				steps[i] = (STEP_T)st1;
-				if (up) w[i] = wh;
+				if constexpr (sizeof(W) == 2) { if (up) w[i] = wh; }
 			}
 		}
 	}
@@ -474,10 +508,10 @@ __global__ void __launch_bounds__(256) k_adam(
 
 // One parameter per thread, no vector accesses: for parameter ranges that do not start on a 16-byte boundary (a Composite
 // optimizer hands its nested optimizers slices at arbitrary offsets, optimizers/composite.h:126-135)
-template <typename STEP_T, typename G>
+template <typename STEP_T, typename G, typename W>
 __global__ void __launch_bounds__(256) k_adam_scalar(
 	const AdamArgs a, const size_t n, const size_t n_matrix,
-	float* __restrict__ w_fp, half_t* __restrict__ w, const G* __restrict__ g, float* __restrict__ m1, float* __restrict__ m2, STEP_T* __restrict__ steps,
+	float* __restrict__ w_fp, W* __restrict__ w, const G* __restrict__ g, float* __restrict__ m1, float* __restrict__ m2, STEP_T* __restrict__ steps,
 	const float* __restrict__ debias_table
 ) {
 	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -485,11 +519,11 @@ __global__ void __launch_bounds__(256) k_adam_scalar(
 	const float debias = debias_table[a.common_step];
 	const auto from_table = [&](const uint32_t t) { return debias_table[t]; };
 	bool up;
-	half_t wh;
+	W wh;
 	uint32_t st1 = steps[i];
 	adam_one(a, from_table, debias,  i < n_matrix, g[i], w_fp[i], wh, m1[i], m2[i], st1, up);
 	steps[i] = (STEP_T)st1;
-	if (up) w[i] = wh;
+	if constexpr (sizeof(W) == 2) { if (up) w[i] = wh; }
 }
 
 // ---- pcg32 strided uniform fill, random.h:40-55 (N_TO_GENERATE = 4, thread i advances a copy of the rng by 4 i)
@@ -634,16 +668,26 @@ void identity_backward_backward_input(hipStream_t stream, bool fp32, uint32_t n,
 }
 
 void loss_evaluate(hipStream_t stream, LossType type, uint32_t n, uint32_t stride, uint32_t dims, float loss_scale,
-                   const void* pred_half, const float* target, float* values, void* grads_half, const float* data_pdf) {
+                   const void* pred_half, const float* target, float* values, void* grads_half, const float* data_pdf, Precision precision) {
 	const uint64_t total = (uint64_t)n * stride;
 	if (total == 0) return;
 	CHECK_THROW(total < (1ull << 32));
+	if (precision == Precision::Fp32) { // (pred_half / grads_half: floats)
+		if (stride % 4 == 0 && ((uintptr_t)pred_half | (uintptr_t)values | (uintptr_t)grads_half) % 16 == 0) {
+			hipLaunchKernelGGL(k_loss4_f32, dim3(blocks_for(total / 4, 256)), dim3(256), 0, stream, (uint32_t)type, (uint32_t)total, stride, dims, (uint32_t)(total / stride * dims), loss_scale,
+			                   (const float*)pred_half, target, values, (float*)grads_half, data_pdf);
+			return;
+		}
+		hipLaunchKernelGGL(k_loss<float>, dim3(blocks_for(total, 256)), dim3(256), 0, stream, (uint32_t)type, (uint32_t)total, stride, dims, loss_scale,
+		                   (const float*)pred_half, target, values, (float*)grads_half, data_pdf);
+		return;
+	}
 	if (stride % 8 == 0 && ((uintptr_t)pred_half | (uintptr_t)values | (uintptr_t)grads_half) % 16 == 0) {
 		hipLaunchKernelGGL(k_loss8, dim3(blocks_for(total / 8, 256)), dim3(256), 0, stream, (uint32_t)type, (uint32_t)total, stride, dims, (uint32_t)(total / stride * dims), loss_scale,
 		                   (const half_t*)pred_half, target, values, (half_t*)grads_half, data_pdf);
 		return;
 	}
-	hipLaunchKernelGGL(k_loss, dim3(blocks_for(total, 256)), dim3(256), 0, stream, (uint32_t)type, (uint32_t)total, stride, dims, loss_scale,
+	hipLaunchKernelGGL(k_loss<half_t>, dim3(blocks_for(total, 256)), dim3(256), 0, stream, (uint32_t)type, (uint32_t)total, stride, dims, loss_scale,
 	                   (const half_t*)pred_half, target, values, (half_t*)grads_half, data_pdf);
 }
 
@@ -687,22 +731,22 @@ __global__ void __launch_bounds__(256) k_adam_widen_steps(const size_t n, const 
 	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i < n) out[i] = in[i];
 }
-template <typename STEP_T, typename G>
-void adam_launch(hipStream_t stream, const AdamArgs& a, size_t n, size_t n_matrix, float* w_fp, void* w_half, const G* g, float* m1, float* m2, STEP_T* steps, const float* debias_table) {
-	// the quad kernel reads float4 / 4 step counts / half4 / 4 gradients: every base pointer must allow that
+template <typename STEP_T, typename G, typename W>
+void adam_launch(hipStream_t stream, const AdamArgs& a, size_t n, size_t n_matrix, float* w_fp, W* w, const G* g, float* m1, float* m2, STEP_T* steps, const float* debias_table) {
+	// the quad kernel reads float4 / 4 step counts / half4 / 4 gradients: every base pointer must allow that (W = float: w is not touched)
 	const auto aligned = [](const void* p, size_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; };
-	if (!(aligned(w_fp, 16) && aligned(m1, 16) && aligned(m2, 16) && aligned(steps, 4 * sizeof(STEP_T)) && aligned(w_half, 8) && aligned(g, 4 * sizeof(G)))) {
-		hipLaunchKernelGGL((k_adam_scalar<STEP_T, G>), dim3(blocks_for(n, 256)), dim3(256), 0, stream, a, n, n_matrix, w_fp, (half_t*)w_half, g, m1, m2, steps, debias_table);
+	if (!(aligned(w_fp, 16) && aligned(m1, 16) && aligned(m2, 16) && aligned(steps, 4 * sizeof(STEP_T)) && (sizeof(W) == 4 || aligned(w, 8)) && aligned(g, 4 * sizeof(G)))) {
+		hipLaunchKernelGGL((k_adam_scalar<STEP_T, G, W>), dim3(blocks_for(n, 256)), dim3(256), 0, stream, a, n, n_matrix, w_fp, w, g, m1, m2, steps, debias_table);
 		return;
 	}
 	const dim3 grid(blocks_for((n + 3) / 4, 256 * ADAM_Q));
-	if (n_matrix % 4 == 0) hipLaunchKernelGGL((k_adam<true, STEP_T, G>), grid, dim3(256), 0, stream, a, n, n_matrix, w_fp, (half_t*)w_half, g, m1, m2, steps, debias_table);
-	else hipLaunchKernelGGL((k_adam<false, STEP_T, G>), grid, dim3(256), 0, stream, a, n, n_matrix, w_fp, (half_t*)w_half, g, m1, m2, steps, debias_table);
+	if (n_matrix % 4 == 0) hipLaunchKernelGGL((k_adam<true, STEP_T, G, W>), grid, dim3(256), 0, stream, a, n, n_matrix, w_fp, w, g, m1, m2, steps, debias_table);
+	else hipLaunchKernelGGL((k_adam<false, STEP_T, G, W>), grid, dim3(256), 0, stream, a, n, n_matrix, w_fp, w, g, m1, m2, steps, debias_table);
 }
-template <typename G>
-void adam_launch_steps(hipStream_t stream, const AdamArgs& a, size_t n, size_t n_matrix, float* w_fp, void* w_half, const G* g, float* m1, float* m2, void* steps, bool steps16, const float* debias_table) {
-	if (steps16) adam_launch<uint16_t, G>(stream, a, n, n_matrix, w_fp, w_half, g, m1, m2, (uint16_t*)steps, debias_table);
-	else adam_launch<uint32_t, G>(stream, a, n, n_matrix, w_fp, w_half, g, m1, m2, (uint32_t*)steps, debias_table);
+template <typename G, typename W>
+void adam_launch_steps(hipStream_t stream, const AdamArgs& a, size_t n, size_t n_matrix, float* w_fp, W* w, const G* g, float* m1, float* m2, void* steps, bool steps16, const float* debias_table) {
+	if (steps16) adam_launch<uint16_t, G, W>(stream, a, n, n_matrix, w_fp, w, g, m1, m2, (uint16_t*)steps, debias_table);
+	else adam_launch<uint32_t, G, W>(stream, a, n, n_matrix, w_fp, w, g, m1, m2, (uint32_t*)steps, debias_table);
 }
 } // namespace
 
@@ -712,11 +756,14 @@ void adam_widen_steps(hipStream_t stream, size_t n, const void* steps16, void* s
 }
 
 void adam_step(hipStream_t stream, const AdamHyper& h, size_t n, size_t n_matrix, float loss_scale, uint32_t current_step,
-               float* w_fp, void* w_half, const void* gradients, float* m1, float* m2, void* steps, bool steps16, const float* debias_table, GradientPrecision precision) {
+               float* w_fp, void* w_half, const void* gradients, float* m1, float* m2, void* steps, bool steps16, const float* debias_table, GradientPrecision precision, Precision weight_precision) {
 	if (n == 0) return;
 	const AdamArgs a = make_adam_args(h, loss_scale, current_step);
-	if (precision == GradientPrecision::Fp32) adam_launch_steps(stream, a, n, n_matrix, w_fp, w_half, (const float*)gradients, m1, m2, steps, steps16, debias_table);
-	else adam_launch_steps(stream, a, n, n_matrix, w_fp, w_half, (const half_t*)gradients, m1, m2, steps, steps16, debias_table);
+	if (weight_precision == Precision::Fp32) {
+		CHECK_THROW(precision == GradientPrecision::Fp32);
+		adam_launch_steps(stream, a, n, n_matrix, w_fp, (float*)nullptr, (const float*)gradients, m1, m2, steps, steps16, debias_table);
+	} else if (precision == GradientPrecision::Fp32) adam_launch_steps(stream, a, n, n_matrix, w_fp, (half_t*)w_half, (const float*)gradients, m1, m2, steps, steps16, debias_table);
+	else adam_launch_steps(stream, a, n, n_matrix, w_fp, (half_t*)w_half, (const half_t*)gradients, m1, m2, steps, steps16, debias_table);
 }
 
 // ---- Adam with the backward pass's last two reductions in front (AdamPrologue, tcnn_common.h): workgroups [0, n_reduce_blocks) sum the MLP's
@@ -914,8 +961,8 @@ void adam_fill_debias_table(hipStream_t stream, float beta1, float beta2, uint32
 
 namespace {
 // optimizers/sgd.h:44-72
-template <typename G>
-__global__ void __launch_bounds__(256) k_sgd(const size_t n, const float loss_scale, const float learning_rate, const float l2_reg, float* __restrict__ w_fp, half_t* __restrict__ w,
+template <typename G, typename W>
+__global__ void __launch_bounds__(256) k_sgd(const size_t n, const float loss_scale, const float learning_rate, const float l2_reg, float* __restrict__ w_fp, W* __restrict__ w,
                                              const G* __restrict__ g) {
 	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
@@ -924,25 +971,27 @@ __global__ void __launch_bounds__(256) k_sgd(const size_t n, const float loss_sc
 	gradient += l2_reg * weight_fp;
 	const float new_weight = weight_fp - learning_rate * gradient;
 	w_fp[i] = new_weight;
-	w[i] = (half_t)new_weight;
+	if constexpr (sizeof(W) == 2) w[i] = (W)new_weight;
 }
 
 // optimizers/ema.h:44-78: tmp != nullptr keeps the average in fp32 (full_precision), else it lives in the half weights themselves
-__global__ void __launch_bounds__(256) k_ema(const size_t n, const float decay, const float debias_old, const float debias_new, const half_t* __restrict__ weights, half_t* __restrict__ weights_ema,
+template <typename W>
+__global__ void __launch_bounds__(256) k_ema(const size_t n, const float decay, const float debias_old, const float debias_new, const W* __restrict__ weights, W* __restrict__ weights_ema,
                                              float* __restrict__ tmp) {
 	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
 	const float previous = tmp ? tmp[i] : (float)weights_ema[i];
 	const float filtered = (previous * decay * debias_old + (float)weights[i] * (1 - decay)) * debias_new;
 	if (tmp) tmp[i] = filtered;
-	weights_ema[i] = (half_t)filtered;
+	weights_ema[i] = (W)filtered;
 }
 // optimizers/average.h:44-60: running mean of the last n_samples weight vectors; `current` is the slot the new weights replace
-__global__ void __launch_bounds__(256) k_average_step(const size_t n, const uint32_t n_samples, const half_t* __restrict__ weights, half_t* __restrict__ current, half_t* __restrict__ average) {
+template <typename W>
+__global__ void __launch_bounds__(256) k_average_step(const size_t n, const uint32_t n_samples, const W* __restrict__ weights, W* __restrict__ current, W* __restrict__ average) {
 	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
-	const half_t weight = weights[i];
-	average[i] = (half_t)((float)average[i] + ((float)weight - (float)current[i]) / (float)n_samples);
+	const W weight = weights[i];
+	average[i] = (W)((float)average[i] + ((float)weight - (float)current[i]) / (float)n_samples);
 	current[i] = weight;
 }
 // optimizers/batched.h:44-61: pool (+)= gradient / batch_size_multiplier, restarted with the first gradient of a group
@@ -972,9 +1021,9 @@ __global__ void __launch_bounds__(1024) k_novo_second_moment(const size_t n, con
 	}
 	if (threadIdx.x == 0) *moment = beta2 * *moment + (1 - beta2) * part[0] / loss_scale / loss_scale;
 }
-template <typename G>
+template <typename G, typename W>
 __global__ void __launch_bounds__(256) k_novo_step(const size_t n, const float relative_weight_decay, const float absolute_weight_decay, const float loss_scale, const float learning_rate,
-                                                   const float beta1, const float epsilon, float* __restrict__ weights_fp, half_t* __restrict__ weights, const G* __restrict__ gradients,
+                                                   const float beta1, const float epsilon, float* __restrict__ weights_fp, W* __restrict__ weights, const G* __restrict__ gradients,
                                                    float* __restrict__ first_moments, const float* __restrict__ layer_second_moment) {
 	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
@@ -986,17 +1035,18 @@ __global__ void __launch_bounds__(256) k_novo_step(const size_t n, const float r
 	const float decayed_weight = (1 - relative_weight_decay * learning_rate) * weight_fp - copysignf(absolute_weight_decay * learning_rate, weight_fp);
 	const float new_weight = decayed_weight - learning_rate * first_moment;
 	weights_fp[i] = new_weight;
-	weights[i] = (half_t)new_weight;
+	if constexpr (sizeof(W) == 2) weights[i] = (W)new_weight;
 }
 // optimizers/lookahead.h:44-59: slow weights <- slow * (1 - alpha) + fast * alpha, and the fast weights restart from them
-__global__ void __launch_bounds__(256) k_lookahead_step(const size_t n, const float alpha, float* __restrict__ weights_fp, half_t* __restrict__ weights, half_t* __restrict__ lookahead) {
+template <typename W>
+__global__ void __launch_bounds__(256) k_lookahead_step(const size_t n, const float alpha, float* __restrict__ weights_fp, W* __restrict__ weights, W* __restrict__ lookahead) {
 	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
 	const float new_weight = (float)lookahead[i] * (1.0f - alpha) + weights_fp[i] * alpha;
 	weights_fp[i] = new_weight;
-	const half_t h = (half_t)new_weight;
+	const W h = (W)new_weight;
 	lookahead[i] = h;
-	weights[i] = h;
+	if constexpr (sizeof(W) == 2) weights[i] = h;
 }
 } // namespace
 
@@ -1021,15 +1071,19 @@ void copy_columns(hipStream_t stream, size_t elem_bytes, uint32_t n, const void*
 	else hipLaunchKernelGGL((k_copy_columns<uint32_t>), blocks, dim3(256), 0, stream, (uint32_t)total, width, (const uint32_t*)src, src_stride, src_col, (uint32_t*)dst, dst_stride, dst_col);
 }
 
-void sgd_step(hipStream_t stream, size_t n, float loss_scale, float learning_rate, float l2_reg, float* weights_full_precision, void* weights, const void* gradients, GradientPrecision precision) {
+void sgd_step(hipStream_t stream, size_t n, float loss_scale, float learning_rate, float l2_reg, float* weights_full_precision, void* weights, const void* gradients, GradientPrecision precision, Precision weight_precision) {
 	if (n == 0) return;
-	if (precision == GradientPrecision::Fp32) hipLaunchKernelGGL(k_sgd<float>, dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, loss_scale, learning_rate, l2_reg, weights_full_precision, (half_t*)weights, (const float*)gradients);
-	else hipLaunchKernelGGL(k_sgd<half_t>, dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, loss_scale, learning_rate, l2_reg, weights_full_precision, (half_t*)weights, (const half_t*)gradients);
+	if (weight_precision == Precision::Fp32) {
+		CHECK_THROW(precision == GradientPrecision::Fp32);
+		hipLaunchKernelGGL((k_sgd<float, float>), dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, loss_scale, learning_rate, l2_reg, weights_full_precision, (float*)nullptr, (const float*)gradients);
+	} else if (precision == GradientPrecision::Fp32) hipLaunchKernelGGL((k_sgd<float, half_t>), dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, loss_scale, learning_rate, l2_reg, weights_full_precision, (half_t*)weights, (const float*)gradients);
+	else hipLaunchKernelGGL((k_sgd<half_t, half_t>), dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, loss_scale, learning_rate, l2_reg, weights_full_precision, (half_t*)weights, (const half_t*)gradients);
 }
 
-void average_step(hipStream_t stream, size_t n, uint32_t n_samples, const void* weights, void* current_sample, void* average) {
+void average_step(hipStream_t stream, size_t n, uint32_t n_samples, const void* weights, void* current_sample, void* average, Precision weight_precision) {
 	if (n == 0) return;
-	hipLaunchKernelGGL(k_average_step, dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, n_samples, (const half_t*)weights, (half_t*)current_sample, (half_t*)average);
+	if (weight_precision == Precision::Fp32) hipLaunchKernelGGL(k_average_step<float>, dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, n_samples, (const float*)weights, (float*)current_sample, (float*)average);
+	else hipLaunchKernelGGL(k_average_step<half_t>, dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, n_samples, (const half_t*)weights, (half_t*)current_sample, (half_t*)average);
 }
 void batched_accumulate(hipStream_t stream, size_t n, bool first, uint32_t multiplier, const void* gradients, float* pool, GradientPrecision precision) {
 	if (n == 0) return;
@@ -1037,26 +1091,35 @@ void batched_accumulate(hipStream_t stream, size_t n, bool first, uint32_t multi
 	else hipLaunchKernelGGL(k_batched_accumulate<half_t>, dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, first ? 1 : 0, multiplier, (const half_t*)gradients, pool);
 }
 void novograd_layer_step(hipStream_t stream, size_t n, float relative_decay, float absolute_decay, float loss_scale, float learning_rate, float beta1, float beta2, float epsilon,
-                         float* weights_full_precision, void* weights, const void* gradients, float* first_moments, float* layer_second_moment, GradientPrecision precision) {
+                         float* weights_full_precision, void* weights, const void* gradients, float* first_moments, float* layer_second_moment, GradientPrecision precision, Precision weight_precision) {
 	if (n == 0) return;
+	if (weight_precision == Precision::Fp32) {
+		CHECK_THROW(precision == GradientPrecision::Fp32);
+		hipLaunchKernelGGL(k_novo_second_moment<float>, dim3(1), dim3(1024), 0, stream, n, loss_scale, beta2, (const float*)gradients, layer_second_moment);
+		hipLaunchKernelGGL((k_novo_step<float, float>), dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, relative_decay, absolute_decay, loss_scale, learning_rate, beta1, epsilon, weights_full_precision,
+		                   (float*)nullptr, (const float*)gradients, first_moments, layer_second_moment);
+		return;
+	}
 	if (precision == GradientPrecision::Fp32) {
 		hipLaunchKernelGGL(k_novo_second_moment<float>, dim3(1), dim3(1024), 0, stream, n, loss_scale, beta2, (const float*)gradients, layer_second_moment);
-		hipLaunchKernelGGL(k_novo_step<float>, dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, relative_decay, absolute_decay, loss_scale, learning_rate, beta1, epsilon, weights_full_precision,
+		hipLaunchKernelGGL((k_novo_step<float, half_t>), dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, relative_decay, absolute_decay, loss_scale, learning_rate, beta1, epsilon, weights_full_precision,
 		                   (half_t*)weights, (const float*)gradients, first_moments, layer_second_moment);
 		return;
 	}
 	hipLaunchKernelGGL(k_novo_second_moment<half_t>, dim3(1), dim3(1024), 0, stream, n, loss_scale, beta2, (const half_t*)gradients, layer_second_moment);
-	hipLaunchKernelGGL(k_novo_step<half_t>, dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, relative_decay, absolute_decay, loss_scale, learning_rate, beta1, epsilon, weights_full_precision,
+	hipLaunchKernelGGL((k_novo_step<half_t, half_t>), dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, relative_decay, absolute_decay, loss_scale, learning_rate, beta1, epsilon, weights_full_precision,
 	                   (half_t*)weights, (const half_t*)gradients, first_moments, layer_second_moment);
 }
-void lookahead_step(hipStream_t stream, size_t n, float alpha, float* weights_full_precision, void* weights, void* weights_lookahead) {
+void lookahead_step(hipStream_t stream, size_t n, float alpha, float* weights_full_precision, void* weights, void* weights_lookahead, Precision weight_precision) {
 	if (n == 0) return;
-	hipLaunchKernelGGL(k_lookahead_step, dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, alpha, weights_full_precision, (half_t*)weights, (half_t*)weights_lookahead);
+	if (weight_precision == Precision::Fp32) hipLaunchKernelGGL(k_lookahead_step<float>, dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, alpha, weights_full_precision, (float*)nullptr, (float*)weights_lookahead);
+	else hipLaunchKernelGGL(k_lookahead_step<half_t>, dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, alpha, weights_full_precision, (half_t*)weights, (half_t*)weights_lookahead);
 }
 
-void ema_step(hipStream_t stream, size_t n, float decay, float debias_old, float debias_new, const void* weights, void* weights_ema, float* tmp) {
+void ema_step(hipStream_t stream, size_t n, float decay, float debias_old, float debias_new, const void* weights, void* weights_ema, float* tmp, Precision weight_precision) {
 	if (n == 0) return;
-	hipLaunchKernelGGL(k_ema, dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, decay, debias_old, debias_new, (const half_t*)weights, (half_t*)weights_ema, tmp);
+	if (weight_precision == Precision::Fp32) hipLaunchKernelGGL(k_ema<float>, dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, decay, debias_old, debias_new, (const float*)weights, (float*)weights_ema, tmp);
+	else hipLaunchKernelGGL(k_ema<half_t>, dim3(blocks_for(n, 256)), dim3(256), 0, stream, n, decay, debias_old, debias_new, (const half_t*)weights, (half_t*)weights_ema, tmp);
 }
 
 namespace {

@@ -2738,8 +2738,19 @@ class Optimizer {
 public:
 	virtual ~Optimizer() {}
 	virtual void allocate(size_t n_weights, const std::vector<std::pair<uint32_t, uint32_t>>& layer_sizes) = 0;
+	// Weight precision Fp32 (Optimizer<float> of the reference's build without TCNN_HALF_PRECISION): ONE float weight vector -- the master
+	// vector is the working vector -- fp32 gradients, and float custom weights.  Chosen before the state is allocated; nested optimizers follow.
+	void allocate(size_t n_weights, const std::vector<std::pair<uint32_t, uint32_t>>& layer_sizes, Precision weight_precision) {
+		set_weight_precision(weight_precision);
+		allocate(n_weights, layer_sizes);
+	}
+	virtual void set_weight_precision(Precision p) { m_weight_precision = p; }
+	Precision weight_precision() const { return m_weight_precision; }
+	bool fp32_weights() const { return m_weight_precision == Precision::Fp32; }
+	size_t weight_bytes() const { return fp32_weights() ? sizeof(float) : 2; } // of one working / custom weight
 	// gradients: n_weights values in `precision` -- the trainer's half gradients (scaled by loss_scale), or fp32 ones a caller computed itself
 	// (a PyTorch parameter's .grad; loss_scale 1 when they are unscaled already).  The weights stay what they are: fp32 master, half working copy.
+	// With fp32 weights: `weights` is null or weights_full_precision itself, and the gradients are fp32.
 	virtual void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients, GradientPrecision precision = GradientPrecision::Fp16) = 0;
 	// step() with the backward pass's finalize pass as the prologue of the same launch (AdamPrologue).  takes_prologue(): this optimizer
 	// can; step_with_prologue returns false when this prologue's shapes do not fit -- nothing has happened then, the caller runs the
@@ -2764,6 +2775,16 @@ public:
 	virtual void deserialize(const Json& data, size_t n_weights) = 0;
 	// after a snapshot was loaded into `weights`: optimizers that assemble custom weights from several sources rebuild them
 	virtual void weights_restored(hipStream_t stream, const void* weights) {}
+protected:
+	// every step() starts here: an fp32-weight optimizer has no second weight vector and reads no half gradients.  Returns the working
+	// weights (the master vector itself with fp32 weights).
+	void* checked_weights(float* weights_full_precision, void* weights, GradientPrecision precision) const {
+		if (!fp32_weights()) return weights;
+		if (weights != nullptr && weights != (void*)weights_full_precision) throw std::runtime_error{"Optimizer: with fp32 weights there is one weight vector (weights must be null or weights_full_precision)."};
+		if (precision != GradientPrecision::Fp32) throw std::runtime_error{"Optimizer: with fp32 weights the gradients must be fp32."};
+		return weights_full_precision;
+	}
+	Precision m_weight_precision = Precision::Fp16;
 };
 inline std::unique_ptr<Optimizer> create_optimizer(const Json& params);
 
@@ -2845,16 +2866,18 @@ public:
 	}
 
 	void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients, GradientPrecision precision = GradientPrecision::Fp16) override { // adam.h:150-188
+		weights = checked_weights(weights_full_precision, weights, precision);
 		++m_current_step;
 		ensure_debias_table(stream);
 		ensure_step_width(stream);
 		adam_step(stream, m_h, m_n_weights, m_n_matrix, loss_scale, m_current_step, weights_full_precision, weights, gradients,
-		          m_first_moments.as<float>(), m_second_moments.as<float>(), m_param_steps.data(), m_steps16, m_debias.as<float>(), precision);
+		          m_first_moments.as<float>(), m_second_moments.as<float>(), m_param_steps.data(), m_steps16, m_debias.as<float>(), precision, m_weight_precision);
 	}
 
-	bool takes_prologue() const override { return true; }
+	// (the prologue and the in-reduce form finish half gradients and store a half working copy: not with fp32 weights)
+	bool takes_prologue() const override { return !fp32_weights(); }
 	bool step_with_prologue(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, void* gradients, const AdamPrologue& prologue) override {
-		if (switches().adam_prologue_refused) return false; // (tests: the caller's path for a prologue this launch does not take)
+		if (fp32_weights() || switches().adam_prologue_refused) return false; // (tests: the caller's path for a prologue this launch does not take)
 		++m_current_step;
 		ensure_debias_table(stream);
 		ensure_step_width(stream);
@@ -2882,8 +2905,9 @@ public:
 		m_steps16 = false;
 	}
 
-	bool can_step_in_reduce() const override { return true; } // (k_wgrad_reduce_adam)
+	bool can_step_in_reduce() const override { return !fp32_weights(); } // (k_wgrad_reduce_adam)
 	AdamInReduce begin_step_in_reduce(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights) override {
+		if (fp32_weights()) return Optimizer::begin_step_in_reduce(stream, loss_scale, weights_full_precision, weights);
 		++m_current_step;
 		ensure_debias_table(stream);
 		ensure_step_width(stream);
@@ -2972,8 +2996,9 @@ public:
 	explicit SgdOptimizer(const Json& params) { update_hyperparams(params); }
 	void allocate(size_t n_weights, const std::vector<std::pair<uint32_t, uint32_t>>&) override { m_n_weights = n_weights; }
 	void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients, GradientPrecision precision = GradientPrecision::Fp16) override {
+		weights = checked_weights(weights_full_precision, weights, precision);
 		++m_current_step;
-		sgd_step(stream, m_n_weights, loss_scale, m_learning_rate, m_l2_reg, weights_full_precision, weights, gradients, precision);
+		sgd_step(stream, m_n_weights, loss_scale, m_learning_rate, m_l2_reg, weights_full_precision, weights, gradients, precision, m_weight_precision);
 	}
 	float learning_rate() const override { return m_learning_rate; }
 	void set_learning_rate(float val) override { m_learning_rate = val; }
@@ -3018,7 +3043,9 @@ public:
 		m_base_learning_rate = m_nested->learning_rate();
 	}
 	void allocate(size_t n_weights, const std::vector<std::pair<uint32_t, uint32_t>>& layer_sizes) override { m_nested->allocate(n_weights, layer_sizes); }
+	void set_weight_precision(Precision p) override { m_weight_precision = p; m_nested->set_weight_precision(p); }
 	void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients, GradientPrecision precision = GradientPrecision::Fp16) override { // :60-71
+		weights = checked_weights(weights_full_precision, weights, precision);
 		if (step_count() == 0) m_learning_rate_factor = 1.0f;
 		if (step_count() >= m_decay_start && (step_count() - m_decay_start) % m_decay_interval == 0 && step_count() <= m_decay_end) m_learning_rate_factor *= m_decay_base;
 		m_nested->set_learning_rate(m_base_learning_rate * m_learning_rate_factor);
@@ -3078,21 +3105,23 @@ public:
 	}
 	void allocate(size_t n_weights, const std::vector<std::pair<uint32_t, uint32_t>>& layer_sizes) override {
 		m_nested->allocate(n_weights, layer_sizes);
-		if (n_weights * 2 <= m_weights_ema.bytes()) return;
-		m_weights_ema.resize(n_weights * 2);
+		if (n_weights * weight_bytes() <= m_weights_ema.bytes()) return;
+		m_weights_ema.resize(n_weights * weight_bytes());
 		m_weights_ema.memset(0);
-		if (m_full_precision) {
+		if (m_full_precision && !fp32_weights()) { // (float EMA weights are their own fp32 copy)
 			m_tmp.resize(n_weights * sizeof(float));
 			m_tmp.memset(0);
 		}
 	}
+	void set_weight_precision(Precision p) override { m_weight_precision = p; m_nested->set_weight_precision(p); }
 	void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients, GradientPrecision precision = GradientPrecision::Fp16) override { // :98-132
+		weights = checked_weights(weights_full_precision, weights, precision);
 		m_nested->step(stream, loss_scale, weights_full_precision, weights, gradients, precision);
 		const uint32_t current_step = m_nested->step_count();
 		const float ema_debias_old = 1 - (float)std::pow(m_ema_decay, current_step - 1);
 		const float ema_debias_new = 1.0f / (1 - (float)std::pow(m_ema_decay, current_step));
 		if (void* nested_custom = m_nested->custom_weights()) weights = nested_custom;
-		ema_step(stream, n_weights(), m_ema_decay, ema_debias_old, ema_debias_new, weights, m_weights_ema.data(), m_full_precision ? m_tmp.as<float>() : nullptr);
+		ema_step(stream, n_weights(), m_ema_decay, ema_debias_old, ema_debias_new, weights, m_weights_ema.data(), m_full_precision && !fp32_weights() ? m_tmp.as<float>() : nullptr, m_weight_precision);
 	}
 	float learning_rate() const override { return m_nested->learning_rate(); }
 	void set_learning_rate(float val) override { m_nested->set_learning_rate(val); }
@@ -3116,15 +3145,15 @@ public:
 	Json serialize() const override {
 		Json data = Json::object();
 		data["nested"] = m_nested->serialize();
-		data["weights_ema_binary"] = device_to_binary(m_weights_ema.data(), n_weights() * 2);
+		data["weights_ema_binary"] = device_to_binary(m_weights_ema.data(), n_weights() * weight_bytes());
 		return data;
 	}
 	void deserialize(const Json& data, size_t n_weights) override {
 		const std::vector<uint8_t> bytes = binary_of(data["weights_ema_binary"]);
-		if (bytes.size() != n_weights * 2) throw std::runtime_error{"EMA: snapshot state has the wrong size."};
+		if (bytes.size() != n_weights * weight_bytes()) throw std::runtime_error{"EMA: snapshot state has the wrong size."}; // (never reinterpreted in the other precision)
 		m_weights_ema.resize(bytes.size());
 		HIP_CHECK_THROW(hipMemcpy(m_weights_ema.data(), bytes.data(), bytes.size(), hipMemcpyHostToDevice));
-		if (m_full_precision) {
+		if (m_full_precision && !fp32_weights()) {
 			m_tmp.resize(n_weights * sizeof(float));
 			cast_half_to_float(nullptr, n_weights, m_weights_ema.data(), m_tmp.as<float>());
 			HIP_CHECK_THROW(hipDeviceSynchronize());
@@ -3155,13 +3184,14 @@ public:
 		m_per_layer_second_moments.memset(0);
 	}
 	void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients, GradientPrecision precision = GradientPrecision::Fp16) override { // :126-167
+		weights = checked_weights(weights_full_precision, weights, precision);
 		++m_current_step;
 		size_t offset = 0;
 		const size_t gradient_bytes = precision == GradientPrecision::Fp32 ? sizeof(float) : 2;
 		for (size_t i = 0; i < m_layers.size(); ++i) {
 			novograd_layer_step(stream, m_layers[i], m_relative_decay, m_absolute_decay, loss_scale, m_learning_rate, m_current_step == 1 ? 0.0f : m_beta1, // exact values on the first step
-			                    m_current_step == 1 ? 0.0f : m_beta2, m_epsilon, weights_full_precision + offset, (char*)weights + 2 * offset, (const char*)gradients + gradient_bytes * offset,
-			                    m_first_moments.as<float>() + offset, m_per_layer_second_moments.as<float>() + i, precision);
+			                    m_current_step == 1 ? 0.0f : m_beta2, m_epsilon, weights_full_precision + offset, (char*)weights + weight_bytes() * offset, (const char*)gradients + gradient_bytes * offset,
+			                    m_first_moments.as<float>() + offset, m_per_layer_second_moments.as<float>() + i, precision, m_weight_precision);
 			offset += m_layers[i];
 		}
 	}
@@ -3229,16 +3259,18 @@ public:
 		m_allocated = true;
 		m_nested->allocate(n_weights, layer_sizes);
 		m_weights_samples.resize(0);
-		m_weights_samples.resize(n_weights * m_n_samples * 2);
+		m_weights_samples.resize(n_weights * m_n_samples * weight_bytes());
 		m_weights_samples.memset(0);
 		m_weights_average.resize(0);
-		m_weights_average.resize(n_weights * 2);
+		m_weights_average.resize(n_weights * weight_bytes());
 		m_weights_average.memset(0);
 	}
+	void set_weight_precision(Precision p) override { m_weight_precision = p; m_nested->set_weight_precision(p); }
 	void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients, GradientPrecision precision = GradientPrecision::Fp16) override { // :82-92
+		weights = checked_weights(weights_full_precision, weights, precision);
 		m_nested->step(stream, loss_scale, weights_full_precision, weights, gradients, precision);
-		char* current = (char*)m_weights_samples.data() + (size_t)(step_count() % m_n_samples) * m_n_weights * 2; // the slot of the step just taken
-		average_step(stream, m_n_weights, m_n_samples, weights, current, m_weights_average.data());
+		char* current = (char*)m_weights_samples.data() + (size_t)(step_count() % m_n_samples) * m_n_weights * weight_bytes(); // the slot of the step just taken
+		average_step(stream, m_n_weights, m_n_samples, weights, current, m_weights_average.data(), m_weight_precision);
 	}
 	float learning_rate() const override { return m_nested->learning_rate(); }
 	void set_learning_rate(float val) override { m_nested->set_learning_rate(val); }
@@ -3264,13 +3296,13 @@ public:
 	Json serialize() const override {
 		Json data = Json::object();
 		data["nested"] = m_nested->serialize();
-		data["weights_samples_binary"] = device_to_binary(m_weights_samples.data(), m_n_weights * m_n_samples * 2);
-		data["weights_average_binary"] = device_to_binary(m_weights_average.data(), m_n_weights * 2);
+		data["weights_samples_binary"] = device_to_binary(m_weights_samples.data(), m_n_weights * m_n_samples * weight_bytes());
+		data["weights_average_binary"] = device_to_binary(m_weights_average.data(), m_n_weights * weight_bytes());
 		return data;
 	}
 	void deserialize(const Json& data, size_t n_weights) override {
 		const std::vector<uint8_t> samples = binary_of(data["weights_samples_binary"]), average = binary_of(data["weights_average_binary"]);
-		if (average.size() != n_weights * 2 || samples.size() != n_weights * 2 * m_n_samples) throw std::runtime_error{"Average: snapshot state has the wrong size."};
+		if (average.size() != n_weights * weight_bytes() || samples.size() != n_weights * weight_bytes() * m_n_samples) throw std::runtime_error{"Average: snapshot state has the wrong size."};
 		m_n_weights = n_weights;
 		m_weights_samples.resize(samples.size());
 		m_weights_average.resize(average.size());
@@ -3297,11 +3329,14 @@ public:
 	void allocate(size_t n_weights, const std::vector<std::pair<uint32_t, uint32_t>>& layer_sizes) override {
 		m_nested->allocate(n_weights, layer_sizes);
 		m_averaged_gradients.resize(n_weights * sizeof(float));
-		m_averaged_gradients_half.resize(n_weights * 2);
 		m_averaged_gradients.memset(0);
+		if (fp32_weights()) return; // (fp32 gradients reach the nested optimizer as the fp32 mean: no half pool, in memory or in snapshots)
+		m_averaged_gradients_half.resize(n_weights * 2);
 		m_averaged_gradients_half.memset(0);
 	}
+	void set_weight_precision(Precision p) override { m_weight_precision = p; m_nested->set_weight_precision(p); }
 	void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients, GradientPrecision precision = GradientPrecision::Fp16) override { // :77-89
+		weights = checked_weights(weights_full_precision, weights, precision);
 		batched_accumulate(stream, n_weights(), m_current_step % m_batch_size_multiplier == 0, m_batch_size_multiplier, gradients, m_averaged_gradients.as<float>(), precision);
 		++m_current_step;
 		if (m_current_step % m_batch_size_multiplier == 0) {
@@ -3338,13 +3373,14 @@ public:
 		Json data = Json::object();
 		data["nested"] = m_nested->serialize();
 		data["averaged_gradients_binary"] = device_to_binary(m_averaged_gradients.data(), n_weights() * sizeof(float));
-		data["averaged_gradients_half_binary"] = device_to_binary(m_averaged_gradients_half.data(), n_weights() * 2);
+		if (!fp32_weights()) data["averaged_gradients_half_binary"] = device_to_binary(m_averaged_gradients_half.data(), n_weights() * 2);
 		data["current_step"] = Json((uint32_t)m_current_step);
 		return data;
 	}
 	void deserialize(const Json& data, size_t n_weights) override {
-		const std::vector<uint8_t> pool = binary_of(data["averaged_gradients_binary"]), half = binary_of(data["averaged_gradients_half_binary"]);
-		if (pool.size() != n_weights * sizeof(float) || half.size() != n_weights * 2) throw std::runtime_error{"Batched: snapshot state has the wrong size."};
+		const std::vector<uint8_t> pool = binary_of(data["averaged_gradients_binary"]);
+		const std::vector<uint8_t> half = fp32_weights() ? std::vector<uint8_t>{} : binary_of(data["averaged_gradients_half_binary"]);
+		if (pool.size() != n_weights * sizeof(float) || half.size() != (fp32_weights() ? 0 : n_weights * 2)) throw std::runtime_error{"Batched: snapshot state has the wrong size."};
 		m_current_step = (uint32_t)data["current_step"].as_double();
 		m_averaged_gradients.resize(pool.size());
 		m_averaged_gradients_half.resize(half.size());
@@ -3368,14 +3404,16 @@ public:
 	}
 	void allocate(size_t n_weights, const std::vector<std::pair<uint32_t, uint32_t>>& layer_sizes) override {
 		m_nested->allocate(n_weights, layer_sizes);
-		if (n_weights * 2 <= m_weights_lookahead.bytes()) return;
-		m_weights_lookahead.resize(n_weights * 2);
+		if (n_weights * weight_bytes() <= m_weights_lookahead.bytes()) return;
+		m_weights_lookahead.resize(n_weights * weight_bytes());
 		m_weights_lookahead.memset(0);
 	}
+	void set_weight_precision(Precision p) override { m_weight_precision = p; m_nested->set_weight_precision(p); }
 	void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients, GradientPrecision precision = GradientPrecision::Fp16) override { // :78-98
+		weights = checked_weights(weights_full_precision, weights, precision);
 		const uint32_t current_step = m_nested->step_count();
-		if (current_step == 0) HIP_CHECK_THROW(hipMemcpyAsync(m_weights_lookahead.data(), weights, n_weights() * 2, hipMemcpyDeviceToDevice, stream));
-		if (current_step % m_n_steps == 0) lookahead_step(stream, n_weights(), m_alpha, weights_full_precision, weights, m_weights_lookahead.data());
+		if (current_step == 0) HIP_CHECK_THROW(hipMemcpyAsync(m_weights_lookahead.data(), weights, n_weights() * weight_bytes(), hipMemcpyDeviceToDevice, stream));
+		if (current_step % m_n_steps == 0) lookahead_step(stream, n_weights(), m_alpha, weights_full_precision, weights, m_weights_lookahead.data(), m_weight_precision);
 		m_nested->step(stream, loss_scale, weights_full_precision, weights, gradients, precision);
 	}
 	float learning_rate() const override { return m_nested->learning_rate(); }
@@ -3403,12 +3441,12 @@ public:
 	Json serialize() const override {
 		Json data = Json::object();
 		data["nested"] = m_nested->serialize();
-		data["weights_lookahead_binary"] = device_to_binary(m_weights_lookahead.data(), n_weights() * 2);
+		data["weights_lookahead_binary"] = device_to_binary(m_weights_lookahead.data(), n_weights() * weight_bytes());
 		return data;
 	}
 	void deserialize(const Json& data, size_t n_weights) override {
 		const std::vector<uint8_t> bytes = binary_of(data["weights_lookahead_binary"]);
-		if (bytes.size() != n_weights * 2) throw std::runtime_error{"Lookahead: snapshot state has the wrong size."};
+		if (bytes.size() != n_weights * weight_bytes()) throw std::runtime_error{"Lookahead: snapshot state has the wrong size."};
 		m_weights_lookahead.resize(bytes.size());
 		if (!bytes.empty()) HIP_CHECK_THROW(hipMemcpy(m_weights_lookahead.data(), bytes.data(), bytes.size(), hipMemcpyHostToDevice));
 		m_nested->deserialize(data["nested"], n_weights);
@@ -3460,30 +3498,36 @@ public:
 		}
 		m_n_total = n_weights;
 		if (m_need_custom_weights) { // sized for the whole vector: the trainer runs inference from it (the reference sizes it to the optimized part only)
-			m_custom_weights.resize(n_weights * 2);
+			m_custom_weights.resize(n_weights * weight_bytes());
 			m_custom_weights.memset(0);
 		}
 	}
+	void set_weight_precision(Precision p) override {
+		m_weight_precision = p;
+		for (auto& n : m_nested) n->set_weight_precision(p);
+	}
 	void step(hipStream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients, GradientPrecision precision = GradientPrecision::Fp16) override {
+		weights = checked_weights(weights_full_precision, weights, precision);
 		const size_t gradient_bytes = precision == GradientPrecision::Fp32 ? sizeof(float) : 2;
 		for (size_t i = 0; i < m_nested.size(); ++i) {
 			const size_t offset = m_offsets[i];
-			m_nested[i]->step(stream, loss_scale, weights_full_precision + offset, (_Float16*)weights + offset, (const char*)gradients + gradient_bytes * offset, precision);
+			m_nested[i]->step(stream, loss_scale, weights_full_precision + offset, (char*)weights + weight_bytes() * offset, (const char*)gradients + gradient_bytes * offset, precision);
 		}
 		weights_restored(stream, weights);
 	}
 	// composite.h:86-93: the custom weights are the nested optimizers' custom weights where they have any, else the weights
 	void weights_restored(hipStream_t stream, const void* weights) override {
 		if (!m_need_custom_weights) return;
+		const size_t wb = weight_bytes();
 		for (size_t i = 0; i < m_nested.size(); ++i) {
 			const size_t offset = m_offsets[i];
-			m_nested[i]->weights_restored(stream, (const _Float16*)weights + offset);
-			const void* src = m_nested[i]->custom_weights() ? m_nested[i]->custom_weights() : (const void*)((const _Float16*)weights + offset);
-			HIP_CHECK_THROW(hipMemcpyAsync((_Float16*)m_custom_weights.data() + offset, src, m_nested[i]->n_weights() * 2, hipMemcpyDeviceToDevice, stream));
+			m_nested[i]->weights_restored(stream, (const char*)weights + wb * offset);
+			const void* src = m_nested[i]->custom_weights() ? m_nested[i]->custom_weights() : (const void*)((const char*)weights + wb * offset);
+			HIP_CHECK_THROW(hipMemcpyAsync((char*)m_custom_weights.data() + wb * offset, src, m_nested[i]->n_weights() * wb, hipMemcpyDeviceToDevice, stream));
 		}
 		if (m_n_total > m_offsets.back()) {
 			const size_t done = m_offsets.back();
-			HIP_CHECK_THROW(hipMemcpyAsync((_Float16*)m_custom_weights.data() + done, (const _Float16*)weights + done, (m_n_total - done) * 2, hipMemcpyDeviceToDevice, stream));
+			HIP_CHECK_THROW(hipMemcpyAsync((char*)m_custom_weights.data() + wb * done, (const char*)weights + wb * done, (m_n_total - done) * wb, hipMemcpyDeviceToDevice, stream));
 		}
 	}
 	float learning_rate() const override { return m_learning_rate_factor; }
@@ -3554,6 +3598,7 @@ inline std::unique_ptr<Optimizer> create_optimizer(const Json& params) {
 // Trainer (trainer.h:48-363) + create_from_config (config.h:53-63)
 // ------------------------------------------------------------------------------------------------------------------
 struct TrainContext { // Trainer::ForwardContext, trainer.h:89-95
+	// (an fp32 trainer's output and dL_doutput are floats, and its contexts never take the compact form)
 	ArenaBuf output;      // half  [n][padded_out]
 	ArenaBuf dL_doutput;  // half  [n][padded_out]
 	const void* dL_doutput_ptr = nullptr; // = dL_doutput or the caller's external_dL_dy
@@ -3591,7 +3636,10 @@ inline MatViewMut make_view_mut(float* data, uint32_t width, uint32_t n, int lay
 
 class Trainer {
 public:
-	Trainer(uint32_t n_input_dims, uint32_t n_output_dims, const Json& config, uint32_t seed) {
+	// precision Fp32: Trainer<float, float, float> of the reference's build without TCNN_HALF_PRECISION -- the fp32 module, Loss<float>,
+	// Optimizer<float>, loss scale 1.  ONE float parameter vector (params() == params_full_precision()), float gradients, float output and
+	// dL_doutput; every training step is the unfused sequence forward -> loss -> backward -> optimizer.
+	Trainer(uint32_t n_input_dims, uint32_t n_output_dims, const Json& config, uint32_t seed, Precision precision = Precision::Fp16) : m_fp32{precision == Precision::Fp32} {
 		// config.h:53-63
 		const Json encoding = config.value("encoding", Json::object());
 		const Json loss = config.value("loss", Json::object());
@@ -3599,7 +3647,13 @@ public:
 		const Json network = config.value("network", Json::object());
 		m_loss = create_loss(loss);
 		m_optimizer = create_optimizer(optimizer);
-		m_model.reset(new NetworkWithInputEncoding{n_input_dims, n_output_dims, encoding, network});
+		if (m_fp32) { // what the configuration alone decides is reported before anything is allocated on the device (network.cu:102-103)
+			const std::string otype = network.is_object() ? network.value("otype", "MLP") : std::string{"MLP"};
+			if (equals_case_insensitive(otype, "MegakernelMLP") || equals_case_insensitive(otype, "FullyFusedMLP")) {
+				throw std::runtime_error{"FullyFusedMLP can only be used if the network precision is set to __half."};
+			}
+		}
+		m_model.reset(new NetworkWithInputEncoding{n_input_dims, n_output_dims, encoding, network, precision});
 		// trainer.h:52-55
 		std::seed_seq seq{seed};
 		std::vector<uint32_t> seeds(2);
@@ -3611,15 +3665,17 @@ public:
 
 	void initialize_params() { // trainer.h:68-87
 		const size_t n = m_model->n_params();
-		m_optimizer->allocate(n, m_model->layer_sizes());
+		m_optimizer->allocate(n, m_model->layer_sizes(), precision());
 		m_params_fp.resize(n * sizeof(float));
-		m_params.resize(n * 2);
-		m_grads.resize(n * 2);
+		m_grads.resize(n * elem());
 		m_params_fp.memset(0);
-		m_params.memset(0);
 		m_grads.memset(0);
 		m_model->initialize_params(m_rng, m_params_fp.as<float>(), 1.0f);
-		cast_float_to_half(nullptr, n, m_params_fp.as<float>(), m_params.data());
+		if (!m_fp32) { // (fp32: the master vector is the working vector)
+			m_params.resize(n * 2);
+			m_params.memset(0);
+			cast_float_to_half(nullptr, n, m_params_fp.as<float>(), m_params.data());
+		}
 		HIP_CHECK_THROW(hipDeviceSynchronize());
 	}
 
@@ -3628,8 +3684,8 @@ public:
 		auto ctx = std::make_unique<TrainContext>();
 		ctx->n = n;
 		const uint32_t pw = m_model->padded_output_width();
-		ctx->output = ArenaBuf{stream, (size_t)n * pw * 2};
-		ctx->model_ctx = m_model->forward(stream, n, input, ctx->output.data(), use_inference_params ? params_inference() : m_params.data(), prepare_input_gradients);
+		ctx->output = ArenaBuf{stream, (size_t)n * pw * elem()};
+		ctx->model_ctx = m_model->forward(stream, n, input, ctx->output.data(), use_inference_params ? params_inference() : working_params(), prepare_input_gradients);
 		ctx->L = ArenaBuf{stream, (size_t)n * pw * sizeof(float)};
 		if (external_dL_dy) {
 			ctx->dL_doutput_ptr = external_dL_dy;
@@ -3637,16 +3693,16 @@ public:
 			HIP_CHECK_THROW(hipMemsetAsync(ctx->L.data(), 0, ctx->L.bytes(), stream));
 		} else {
 			CHECK_THROW(target != nullptr);
-			ctx->dL_doutput = ArenaBuf{stream, (size_t)n * pw * 2};
+			ctx->dL_doutput = ArenaBuf{stream, (size_t)n * pw * elem()};
 			ctx->dL_doutput_ptr = ctx->dL_doutput.data();
-			loss_evaluate(stream, m_loss, n, pw, m_model->output_width(), loss_scale, ctx->output.data(), target, ctx->L.as<float>(), ctx->dL_doutput.data(), data_pdf);
+			loss_evaluate(stream, m_loss, n, pw, m_model->output_width(), loss_scale, ctx->output.data(), target, ctx->L.as<float>(), ctx->dL_doutput.data(), data_pdf, precision());
 		}
 		return ctx;
 	}
 
 	void backward(hipStream_t stream, const TrainContext& ctx, uint32_t n, MatView input, MatViewMut* dL_dinput, bool use_inference_params, GradientMode mode) { // trainer.h:147-149
 		const_cast<TrainContext&>(ctx).materialize(); // a context of the fused step keeps dL_doutput compact until somebody asks for it
-		m_model->backward(stream, *ctx.model_ctx, n, input, ctx.output.data(), ctx.dL_doutput_ptr, dL_dinput, use_inference_params ? params_inference() : m_params.data(), m_grads.data(), mode);
+		m_model->backward(stream, *ctx.model_ctx, n, input, ctx.output.data(), ctx.dL_doutput_ptr, dL_dinput, use_inference_params ? params_inference() : working_params(), m_grads.data(), mode);
 	}
 
 	size_t params_updated_in_flush() const { return m_params_updated_in_flush; }
@@ -3683,15 +3739,15 @@ public:
 
 	void optimizer_step(hipStream_t stream, float loss_scale) { // trainer.h:155-157
 		m_model->invalidate_live_image();
-		m_optimizer->step(stream, loss_scale, m_params_fp.as<float>(), m_params.data(), m_grads.data());
+		m_optimizer->step(stream, loss_scale, m_params_fp.as<float>(), working_params(), m_grads.data(), m_fp32 ? GradientPrecision::Fp32 : GradientPrecision::Fp16);
 	}
 
 	std::unique_ptr<TrainContext> training_step(hipStream_t stream, uint32_t n, MatView input, const float* target, const float* data_pdf, bool run_optimizer,
 	                                            MatViewMut* dL_dinput, bool use_inference_params, GradientMode mode, const void* external_dL_dy) { // trainer.h:163-190
-		const float loss_scale = LOSS_SCALE_FP16;
+		const float loss_scale = m_fp32 ? 1.0f : LOSS_SCALE_FP16; // (tcnn_default_loss_scale)
 		std::unique_ptr<TrainContext> ctx;
-		const bool other_weights = use_inference_params && params_inference() != m_params.data(); // EMA weights requested for this step
-		if (m_model->fused_step_supported(n) && (external_dL_dy || loss_in_fused_kernel(m_loss)) && !other_weights) {
+		const bool other_weights = use_inference_params && params_inference() != working_params(); // EMA weights requested for this step
+		if (!m_fp32 && m_model->fused_step_supported(n) && (external_dL_dy || loss_in_fused_kernel(m_loss)) && !other_weights) {
 			// MI355X path: encoding -> ONE fused MLP kernel (forward + loss + backward + weight gradients) -> grid scatter
 			ctx = std::make_unique<TrainContext>();
 			ctx->n = n;
@@ -3779,27 +3835,29 @@ public:
 	void inference(hipStream_t stream, uint32_t n, MatView input, MatViewMut output, bool use_inference_params) { // object.h:147-176
 		Model::check_batch(n);
 		if (n == 0) return;
-		m_model->inference_f32(stream, n, input, output, use_inference_params ? params_inference() : m_params.data());
+		m_model->inference_f32(stream, n, input, output, use_inference_params ? params_inference() : working_params());
 	}
 
-	// object.h:133-145, inference_mixed_precision: the network's own output, half [n][padded_output_width] (what inference() casts)
+	// object.h:133-145, inference_mixed_precision: the network's own output, half [n][padded_output_width] (what inference() casts); floats from an fp32 trainer
 	void inference_mixed_precision(hipStream_t stream, uint32_t n, MatView input, void* output_half, bool use_inference_params) {
 		Model::check_batch(n);
 		if (n == 0) return;
-		m_model->inference(stream, n, input, output_half, use_inference_params ? params_inference() : m_params.data());
+		m_model->inference(stream, n, input, output_half, use_inference_params ? params_inference() : working_params());
 	}
 
 	void set_params_full_precision(const float* params, size_t n_params, bool device_ptr) { // trainer.h:242-254
 		if (n_params != m_model->n_params()) throw std::runtime_error{"Can't set fp params because buffer has the wrong size."};
 		m_model->invalidate_live_image();
 		HIP_CHECK_THROW(hipMemcpy(m_params_fp.data(), params, sizeof(float) * n_params, device_ptr ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-		cast_float_to_half(nullptr, n_params, m_params_fp.as<float>(), m_params.data());
-		if (params_inference() != m_params.data()) HIP_CHECK_THROW(hipMemcpy(params_inference(), m_params.data(), 2 * n_params, hipMemcpyDeviceToDevice));
+		if (!m_fp32) cast_float_to_half(nullptr, n_params, m_params_fp.as<float>(), m_params.data());
+		if (params_inference() != working_params()) HIP_CHECK_THROW(hipMemcpy(params_inference(), working_params(), elem() * n_params, hipMemcpyDeviceToDevice));
 		HIP_CHECK_THROW(hipDeviceSynchronize());
 	}
 
+	// params: in the trainer's precision (an fp32 trainer's parameters ARE the full-precision ones)
 	void set_params(const void* params, size_t n_params, bool device_ptr) { // trainer.h:256-269
 		if (n_params != m_model->n_params()) throw std::runtime_error{"Can't set params because buffer has the wrong size."};
+		if (m_fp32) return set_params_full_precision((const float*)params, n_params, device_ptr);
 		m_model->invalidate_live_image();
 		HIP_CHECK_THROW(hipMemcpy(m_params.data(), params, 2 * n_params, device_ptr ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
 		cast_half_to_float(nullptr, n_params, m_params.data(), m_params_fp.as<float>());
@@ -3818,8 +3876,8 @@ public:
 		const size_t n = m_model->n_params();
 		Json data = Json::object();
 		data["n_params"] = Json((uint64_t)n);
-		data["params_type"] = "__half"; // type_to_string<__half>() of the reference: the name snapshots carry
-		data["params_binary"] = device_to_binary(params_inference(), 2 * n); // trainer.h:281: the inference parameters (EMA weights if there are any)
+		data["params_type"] = m_fp32 ? "float" : "__half"; // type_to_string<T>() of the reference: the name snapshots carry
+		data["params_binary"] = device_to_binary(params_inference(), elem() * n); // trainer.h:281: the inference parameters (EMA weights if there are any)
 		if (serialize_optimizer) data["optimizer"] = m_optimizer->serialize();
 		return data;
 	}
@@ -3828,15 +3886,27 @@ public:
 		const std::string type = data.value("params_type", "__half");
 		const std::vector<uint8_t> bytes = binary_of(data["params_binary"]);
 		if (type == "float") {
+			if (bytes.size() % sizeof(float) != 0) throw std::runtime_error{"Can't set fp params because buffer has the wrong size."};
 			set_params_full_precision((const float*)bytes.data(), bytes.size() / sizeof(float), false);
+		} else if (type == "__half" && m_fp32) { // trainer.h:303-305: cast to the trainer's type
+			if (bytes.size() != 2 * m_model->n_params()) throw std::runtime_error{"Can't set params because buffer has the wrong size."};
+			DeviceBuf half;
+			half.resize(bytes.size());
+			DeviceBuf wide;
+			wide.resize(bytes.size() * 2);
+			if (!bytes.empty()) HIP_CHECK_THROW(hipMemcpy(half.data(), bytes.data(), bytes.size(), hipMemcpyHostToDevice));
+			cast_half_to_float(nullptr, bytes.size() / 2, half.data(), wide.as<float>());
+			HIP_CHECK_THROW(hipDeviceSynchronize());
+			set_params_full_precision(wide.as<float>(), bytes.size() / 2, true);
 		} else if (type == "__half") {
+			if (bytes.size() % 2 != 0) throw std::runtime_error{"Can't set params because buffer has the wrong size."};
 			set_params(bytes.data(), bytes.size() / 2, false);
 		} else {
 			throw std::runtime_error{"Trainer: snapshot parameters must be of type float of __half"};
 		}
 		if (data.contains("optimizer")) {
 			m_optimizer->deserialize(data["optimizer"], m_model->n_params());
-			m_optimizer->weights_restored(nullptr, m_params.data());
+			m_optimizer->weights_restored(nullptr, working_params());
 		}
 		HIP_CHECK_THROW(hipDeviceSynchronize());
 	}
@@ -3855,13 +3925,17 @@ public:
 	Optimizer& optimizer() { return *m_optimizer; }
 	StepProfile& profile() { return m_profile; }
 	// trainer.h:329-333: the optimizer's own weights (EMA) if it keeps any, else the training parameters
-	void* params_inference() const { void* custom = m_optimizer->custom_weights(); return custom ? custom : m_params.data(); }
+	void* params_inference() const { void* custom = m_optimizer->custom_weights(); return custom ? custom : working_params(); }
+	Precision precision() const { return m_fp32 ? Precision::Fp32 : Precision::Fp16; }
+	size_t elem() const { return m_fp32 ? sizeof(float) : 2; } // bytes of a parameter, an output element, a gradient
+	// the parameters training runs with: the half copy, or the one float vector of an fp32 trainer
+	void* working_params() const { return m_fp32 ? m_params_fp.data() : m_params.data(); }
 	size_t n_params() const { return m_model->n_params(); }
 	// The reference hands out mutable pointers here (trainer.h:226-232).  A caller may write through them at any later time, so from the
 	// first call on no fragment image of the half parameters is trusted beyond the step that built it (Network::live_image)
 	float* params_full_precision() { expose_params(); return m_params_fp.as<float>(); }
-	void* params() { expose_params(); return m_params.data(); }
-	const void* params_unexposed() const { return m_params.data(); } // for comparisons only
+	void* params() { expose_params(); return working_params(); }
+	const void* params_unexposed() const { return working_params(); } // for comparisons only
 	size_t image_preps() const { return m_model->image_preps(); }
 	uint64_t scatter_wide_fallbacks() { return m_model->scatter_wide_fallbacks(); }
 	uint64_t list_scatters() const { return m_model->list_scatters(); }
@@ -3881,6 +3955,7 @@ private:
 	size_t m_params_updated_in_flush = 0;
 	const char* m_last_step_kernel = "";
 	bool m_params_exposed = false;
+	const bool m_fp32 = false;
 	void expose_params() {
 		m_params_exposed = true;
 		m_model->invalidate_live_image();

@@ -598,7 +598,7 @@ void mlp_wgrad_panels_f32(hipStream_t stream, uint32_t n, const WgradPanel* pane
 // loss / reduction / optimizer / init plumbing
 // ------------------------------------------------------------------------------------------------------------------
 void loss_evaluate(hipStream_t stream, LossType type, uint32_t n, uint32_t stride, uint32_t dims, float loss_scale,
-                   const void* pred_half, const float* target, float* values, void* grads_half, const float* data_pdf);
+                   const void* pred_half, const float* target, float* values, void* grads_half, const float* data_pdf, Precision precision = Precision::Fp16);
 // sum of n floats -> *result_dev (device float, overwritten). workspace-free: uses a two-stage reduction through `partials` (>= 1024 floats)
 void reduce_sum(hipStream_t stream, size_t n, const float* values, float* partials, float* result_dev);
 
@@ -659,7 +659,7 @@ bool adam_step_with_prologue(hipStream_t stream, const AdamHyper& h, size_t n, s
 // 4 of the 36 bytes per parameter the kernel moves are the counts' upper halves otherwise)
 void adam_step(hipStream_t stream, const AdamHyper& h, size_t n, size_t n_matrix, float loss_scale, uint32_t current_step,
                float* w_fp, void* w_half, const void* gradients, float* m1, float* m2, void* steps, bool steps16, const float* debias_table,
-               GradientPrecision precision = GradientPrecision::Fp16);
+               GradientPrecision precision = GradientPrecision::Fp16, Precision weight_precision = Precision::Fp16);
 void adam_widen_steps(hipStream_t stream, size_t n, const void* steps16, void* steps32); // uint16 -> uint32
 // debias_table[t] = sqrtf(1 - powf(beta2, t)) / (1 - powf(beta1, t)) (adam.h:97-98), evaluated on the device, for t in [from, to)
 void adam_fill_debias_table(hipStream_t stream, float beta1, float beta2, uint32_t from, uint32_t to, float* table);
@@ -667,16 +667,18 @@ void adam_fill_debias_table(hipStream_t stream, float beta1, float beta2, uint32
 void copy_columns(hipStream_t stream, size_t elem_bytes, uint32_t n, const void* src, uint32_t src_stride, uint32_t src_col, void* dst, uint32_t dst_stride, uint32_t dst_col, uint32_t width);
 // optimizers/sgd.h:44-72 and optimizers/ema.h:44-78 (half parameters; gradients in `precision`, here and below)
 void sgd_step(hipStream_t stream, size_t n, float loss_scale, float learning_rate, float l2_reg, float* weights_full_precision, void* weights, const void* gradients,
-              GradientPrecision precision = GradientPrecision::Fp16);
-void ema_step(hipStream_t stream, size_t n, float decay, float debias_old, float debias_new, const void* weights, void* weights_ema, float* tmp);
+              GradientPrecision precision = GradientPrecision::Fp16, Precision weight_precision = Precision::Fp16);
+// weight_precision Fp32 (here and below): the optimizer's weights are ONE float vector -- weights_full_precision is read and stored, `weights` is
+// not touched -- its gradients are fp32, and the buffers an optimizer keeps beside them (EMA, samples, average, lookahead) are floats
+void ema_step(hipStream_t stream, size_t n, float decay, float debias_old, float debias_new, const void* weights, void* weights_ema, float* tmp, Precision weight_precision = Precision::Fp16);
 // optimizers/average.h:44-60, batched.h:44-61, lookahead.h:44-59 (half parameters)
-void average_step(hipStream_t stream, size_t n, uint32_t n_samples, const void* weights, void* current_sample, void* average);
+void average_step(hipStream_t stream, size_t n, uint32_t n_samples, const void* weights, void* current_sample, void* average, Precision weight_precision = Precision::Fp16);
 void batched_accumulate(hipStream_t stream, size_t n, bool first, uint32_t multiplier, const void* gradients, float* pool, GradientPrecision precision = GradientPrecision::Fp16);
-void lookahead_step(hipStream_t stream, size_t n, float alpha, float* weights_full_precision, void* weights, void* weights_lookahead);
+void lookahead_step(hipStream_t stream, size_t n, float alpha, float* weights_full_precision, void* weights, void* weights_lookahead, Precision weight_precision = Precision::Fp16);
 // optimizers/novograd.h:44-94 for ONE layer of n weights: the layer's second moment from the sum of its squared gradients, then the step
 void novograd_layer_step(hipStream_t stream, size_t n, float relative_decay, float absolute_decay, float loss_scale, float learning_rate, float beta1, float beta2, float epsilon,
                          float* weights_full_precision, void* weights, const void* gradients, float* first_moments, float* layer_second_moment,
-                         GradientPrecision precision = GradientPrecision::Fp16);
+                         GradientPrecision precision = GradientPrecision::Fp16, Precision weight_precision = Precision::Fp16);
 
 // random.h:40-70: strided uniform fill from a pcg32 state; advances (state, inc) on the host copy by n
 void generate_random_uniform(hipStream_t stream, uint64_t* state_inc_host, size_t n, float* out, float lower, float upper);

@@ -90,6 +90,8 @@ _SIGNATURES = {
     "tcnn_module_name": (_cp, [_vp]),
     "tcnn_create_from_config": (_int, [_u32, _u32, _cp, _pp]),
     "tcnn_create_from_config_seeded": (_int, [_u32, _u32, _cp, _u32, _pp]),
+    "tcnn_create_from_config_precision": (_int, [_u32, _u32, _cp, _u32, _int, _pp]),
+    "tcnn_trainer_precision": (_int, [_vp]),
     "tcnn_trainer_destroy": (None, [_vp]),
     "tcnn_trainer_training_step": (_int, [_vp, _vp, _u32, _vp, _int, _vp, _vp, _int, _vp, _int, _int, _vp, _pp]),
     "tcnn_trainer_loss": (_int, [_vp, _vp, _vp, C.POINTER(C.c_float)]),
@@ -132,6 +134,8 @@ _SIGNATURES = {
     "tcnn_trainer_deserialize": (_int, [_vp, _vp, _sz]),
     "tcnn_module_layer_sizes": (_int, [_vp, C.POINTER(_u32), _sz, C.POINTER(_sz)]),
     "tcnn_optimizer_create": (_int, [_cp, _sz, C.POINTER(_u32), _sz, _pp]),
+    "tcnn_optimizer_create_precision": (_int, [_cp, _sz, C.POINTER(_u32), _sz, _int, _pp]),
+    "tcnn_optimizer_weight_precision": (_int, [_vp]),
     "tcnn_optimizer_destroy": (None, [_vp]),
     "tcnn_optimizer_step": (_int, [_vp, _vp, _f32, _vp, _vp, _vp, _int]),
     "tcnn_optimizer_step_count": (_u32, [_vp]),

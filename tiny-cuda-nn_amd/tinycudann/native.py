@@ -15,6 +15,16 @@ LAYOUT_SOA, LAYOUT_AOS = 0, 1
 GRADIENT_IGNORE, GRADIENT_OVERWRITE, GRADIENT_ACCUMULATE = 0, 1, 2
 
 
+_PRECISIONS = {None: _C.Precision.Fp16, torch.float16: _C.Precision.Fp16, torch.float32: _C.Precision.Fp32}
+
+
+def _trainer_precision(dtype):
+    """The precision of a trainer: half unless dtype says torch.float32 (checked before the GPU is asked for)."""
+    if dtype not in _PRECISIONS:
+        raise ValueError(f"Trainer only supports fp32 or fp16 precision, but got {dtype}")
+    return _PRECISIONS[dtype]
+
+
 def _ptr(t):
     return None if t is None else t.data_ptr()
 
@@ -28,10 +38,11 @@ def _stream(stream=None):
 class ForwardContext:
     """Trainer::ForwardContext (trainer.h:89-95)."""
 
-    def __init__(self, handle, n, padded_out):
+    def __init__(self, handle, n, padded_out, dtype=torch.half):
         self._h = handle
         self.n = n
         self.padded_out = padded_out
+        self.dtype = dtype  # of output and dL_doutput: the trainer's
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -50,25 +61,29 @@ class ForwardContext:
         return out
 
     def output(self):
-        return self._view(_C.lib.tcnn_train_ctx_output, torch.half, 2)
+        return self._view(_C.lib.tcnn_train_ctx_output, self.dtype, self.dtype.itemsize)
 
     def dL_doutput(self):
-        return self._view(_C.lib.tcnn_train_ctx_dL_doutput, torch.half, 2)
+        return self._view(_C.lib.tcnn_train_ctx_dL_doutput, self.dtype, self.dtype.itemsize)
 
     def L(self):
         return self._view(_C.lib.tcnn_train_ctx_L, torch.float32, 4)
 
 
 class Trainer:
-    """tcnn::Trainer<float, half, half> + the NetworkWithInputEncoding it drives."""
+    """tcnn::Trainer<float, half, half> + the NetworkWithInputEncoding it drives.  dtype=torch.float32: Trainer<float, float, float> --
+    the fp32 module, one float parameter vector, float output / dL_doutput / gradients, loss scale 1, every step unfused."""
 
-    def __init__(self, n_input_dims, n_output_dims, config, seed=1337):
+    def __init__(self, n_input_dims, n_output_dims, config, seed=1337, dtype=None):
+        precision = _trainer_precision(dtype)
         if not torch.cuda.is_available():
             raise EnvironmentError("tcnn_amd needs a ROCm GPU (gfx950): torch.cuda.is_available() is False.")
         torch.cuda.init()
         h = C.c_void_p()
-        _C.check(_C.lib.tcnn_create_from_config_seeded(n_input_dims, n_output_dims, _C.to_json_bytes(config), seed, C.byref(h)))
+        _C.check(_C.lib.tcnn_create_from_config_precision(n_input_dims, n_output_dims, _C.to_json_bytes(config), seed, precision, C.byref(h)))
         self._h = h
+        self.dtype = torch.float32 if precision == _C.Precision.Fp32 else torch.half
+        self.default_loss_scale = _C.default_loss_scale(precision)
         self.n_input_dims = n_input_dims
         self.n_output_dims = n_output_dims
         self.padded_output_width = int(_C.lib.tcnn_trainer_padded_output_width(h))
@@ -87,8 +102,14 @@ class Trainer:
         ctx = C.c_void_p()
         _C.check(_C.lib.tcnn_trainer_training_step(self._h, _stream(stream), n, _ptr(input), input_layout, _ptr(target), _ptr(data_pdf),
                                                    int(run_optimizer), _ptr(dL_dinput), int(use_inference_params), gradient_mode,
-                                                   _ptr(external_dL_dy), C.byref(ctx)))
-        return ForwardContext(ctx, n, self.padded_output_width)
+                                                   _ptr(self._checked_dy(external_dL_dy)), C.byref(ctx)))
+        return ForwardContext(ctx, n, self.padded_output_width, self.dtype)
+
+    def _checked_dy(self, external_dL_dy):
+        # (an fp32 trainer reads floats; what a half trainer is given passes through as it always did)
+        if external_dL_dy is not None and self.dtype == torch.float32 and external_dL_dy.dtype != torch.float32:
+            raise TypeError(f"tcnn: external_dL_dy must be {self.dtype}, the trainer's precision, not {external_dL_dy.dtype}")
+        return external_dL_dy
 
     # -- measurement hook (include/tcnn_amd.h): HIP events around the pieces of the next fused training step
     PROFILE_PIECES = ("encode", "mlp_kernel", "encoding_backward", "optimizer")
@@ -144,19 +165,21 @@ class Trainer:
         _C.check(_C.lib.tcnn_trainer_loss(self._h, _stream(stream), ctx._h, C.byref(out)))
         return out.value
 
-    def forward(self, input, target, loss_scale=128.0, data_pdf=None, prepare_input_gradients=False, external_dL_dy=None, input_layout=LAYOUT_AOS, stream=None):
+    def forward(self, input, target, loss_scale=None, data_pdf=None, prepare_input_gradients=False, external_dL_dy=None, input_layout=LAYOUT_AOS, stream=None):
         n = input.shape[0] if input_layout == LAYOUT_AOS else input.shape[1]
         self._check_max_level_rows(n)
         ctx = C.c_void_p()
+        loss_scale = self.default_loss_scale if loss_scale is None else loss_scale  # (128 for half, 1 for an fp32 trainer)
         _C.check(_C.lib.tcnn_trainer_forward(self._h, _stream(stream), loss_scale, n, _ptr(input), input_layout, _ptr(target), _ptr(data_pdf), 0,
-                                             int(prepare_input_gradients), _ptr(external_dL_dy), C.byref(ctx)))
-        return ForwardContext(ctx, n, self.padded_output_width)
+                                             int(prepare_input_gradients), _ptr(self._checked_dy(external_dL_dy)), C.byref(ctx)))
+        return ForwardContext(ctx, n, self.padded_output_width, self.dtype)
 
     def backward(self, ctx, input, dL_dinput=None, gradient_mode=GRADIENT_OVERWRITE, input_layout=LAYOUT_AOS, stream=None):
         self._check_max_level_rows(ctx.n)
         _C.check(_C.lib.tcnn_trainer_backward(self._h, _stream(stream), ctx._h, ctx.n, _ptr(input), input_layout, _ptr(dL_dinput), 0, gradient_mode))
 
-    def optimizer_step(self, loss_scale=128.0, stream=None):
+    def optimizer_step(self, loss_scale=None, stream=None):
+        loss_scale = self.default_loss_scale if loss_scale is None else loss_scale
         _C.check(_C.lib.tcnn_trainer_optimizer_step(self._h, _stream(stream), loss_scale))
 
     # -- object.h:147-176: network->inference(stream, input, output)
@@ -171,6 +194,8 @@ class Trainer:
 
     # -- object.h:133-145: network->inference_mixed_precision(stream, input, output): half [n][padded_output_width]
     def inference_half(self, input, output=None, input_layout=LAYOUT_AOS, stream=None):
+        if self.dtype != torch.half:
+            raise TypeError("tcnn: inference_half is the half trainer's; an fp32 trainer's own output is what inference() returns")
         n = input.shape[0] if input_layout == LAYOUT_AOS else input.shape[1]
         if output is None:
             output = torch.empty((n, self.padded_output_width), dtype=torch.half, device=input.device)
@@ -223,21 +248,22 @@ class Trainer:
         return self._copy_out(_C.lib.tcnn_trainer_params_full_precision(self._h), torch.float32, 4)
 
     def params(self):
-        return self._copy_out(_C.lib.tcnn_trainer_params(self._h), torch.half, 2)
+        return self._copy_out(_C.lib.tcnn_trainer_params(self._h), self.dtype, self.dtype.itemsize)
 
     def params_inference(self):
         """trainer.h:234: the parameters inference runs with (the optimizer's EMA weights if it keeps any)."""
-        return self._copy_out(_C.lib.tcnn_trainer_params_inference(self._h), torch.half, 2)
+        return self._copy_out(_C.lib.tcnn_trainer_params_inference(self._h), self.dtype, self.dtype.itemsize)
 
     def param_gradients(self):
-        return self._copy_out(_C.lib.tcnn_trainer_param_gradients(self._h), torch.half, 2)
+        return self._copy_out(_C.lib.tcnn_trainer_param_gradients(self._h), self.dtype, self.dtype.itemsize)
 
     def set_params_full_precision(self, params):
         params = params.contiguous().float()
         _C.check(_C.lib.tcnn_trainer_set_params_full_precision(self._h, _ptr(params), params.numel(), int(params.is_cuda)))
 
     def set_params(self, params_half):
-        params_half = params_half.contiguous().half()
+        """params_half: in the trainer's dtype (half; float32 for an fp32 trainer)"""
+        params_half = params_half.contiguous().to(self.dtype)
         _C.check(_C.lib.tcnn_trainer_set_params(self._h, _ptr(params_half), params_half.numel(), int(params_half.is_cuda)))
 
     def update_hyperparams(self, cfg):
@@ -272,6 +298,6 @@ class TrainableModel:
         self.network = trainer
 
 
-def create_from_config(n_input_dims, n_output_dims, config, seed=1337):
-    """tcnn::create_from_config (config.h:53-63)."""
-    return TrainableModel(Trainer(n_input_dims, n_output_dims, config, seed))
+def create_from_config(n_input_dims, n_output_dims, config, seed=1337, dtype=None):
+    """tcnn::create_from_config (config.h:53-63); dtype=torch.float32: the fp32 trainer."""
+    return TrainableModel(Trainer(n_input_dims, n_output_dims, config, seed, dtype))

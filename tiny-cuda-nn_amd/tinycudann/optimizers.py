@@ -35,17 +35,21 @@ GRADIENT_PRECISION = {torch.float32: _C.Precision.Fp32, torch.float16: _C.Precis
 
 
 class NativeOptimizer:
-    """One tcnn_optimizer_t handle: tcnn::Optimizer<half> (optimizer.h) on caller-owned parameter and gradient vectors."""
+    """One tcnn_optimizer_t handle: tcnn::Optimizer<half> (optimizer.h) on caller-owned parameter and gradient vectors.
+    weight_dtype=torch.float32: Optimizer<float> -- ONE float weight vector, `step(params_fp32, None, gradients_fp32)`, float custom weights."""
 
-    def __init__(self, config, n_params, layer_sizes=(), device=None):
+    def __init__(self, config, n_params, layer_sizes=(), device=None, weight_dtype=torch.half):
         """device: where the optimizer's state lives (the parameters' device); None: the current one, once the configuration is accepted"""
+        if weight_dtype not in GRADIENT_PRECISION:
+            raise ValueError(f"NativeOptimizer only supports fp32 or fp16 precision, but got {weight_dtype}")
+        self.weight_dtype = weight_dtype
         flat = [int(v) for pair in layer_sizes for v in pair]
         sizes = (C.c_uint32 * max(len(flat), 1))(*flat)
         h = C.c_void_p()
         self._h = None
         self.device = None if device is None else torch.device(device)
         with self._on_device():
-            _C.check(_C.lib.tcnn_optimizer_create(_C.to_json_bytes(config), int(n_params), sizes, len(flat) // 2, C.byref(h)))
+            _C.check(_C.lib.tcnn_optimizer_create_precision(_C.to_json_bytes(config), int(n_params), sizes, len(flat) // 2, GRADIENT_PRECISION[weight_dtype], C.byref(h)))
         self._h = h
         self.n_params = int(n_params)
         if self.device is None:
@@ -62,14 +66,16 @@ class NativeOptimizer:
 
     def step(self, params_fp32, params_half, gradients, loss_scale=1.0, stream=None):
         """One step on `stream` (default: the current torch stream).  gradients: float32 or float16, n_params values."""
-        for t, dtype in ((params_fp32, torch.float32), (params_half, torch.float16)):
-            if not (t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.numel() == self.n_params):
+        # (fp32 weights: ONE weight vector -- params_half is None, or params_fp32 again; the library refuses any other pointer)
+        checked = ((params_fp32, torch.float32),) if self.weight_dtype == torch.float32 else ((params_fp32, torch.float32), (params_half, torch.float16))
+        for t, dtype in checked:
+            if not (t is not None and t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.numel() == self.n_params):
                 raise RuntimeError(f"tcnn: the optimizer needs contiguous device tensors of {self.n_params} values: float32 master weights and float16 working weights")
         if gradients.dtype not in GRADIENT_PRECISION:
             raise RuntimeError(f"tcnn: gradients must be float32 or float16, not {gradients.dtype}")
         if not (gradients.is_cuda and gradients.is_contiguous() and gradients.numel() == self.n_params):
             raise RuntimeError(f"tcnn: gradients must be a contiguous device tensor of {self.n_params} values")
-        if not (params_fp32.device == params_half.device == gradients.device == self.device):
+        if not (params_fp32.device == gradients.device == self.device and (params_half is None or params_half.device == self.device)):
             raise RuntimeError(f"tcnn: the optimizer's state lives on {self.device}; weights and gradients must live there too")
         self.step_unchecked(params_fp32, params_half, gradients, loss_scale, stream)
 
@@ -81,7 +87,8 @@ class NativeOptimizer:
         if device.index != torch.cuda.current_device():
             with torch.cuda.device(device):
                 return self.step_unchecked(params_fp32, params_half, gradients, loss_scale, stream)
-        if _C.lib.tcnn_optimizer_step(self._h, stream, loss_scale, params_fp32.data_ptr(), params_half.data_ptr(), gradients.data_ptr(), GRADIENT_PRECISION[gradients.dtype]):
+        if _C.lib.tcnn_optimizer_step(self._h, stream, loss_scale, params_fp32.data_ptr(), None if params_half is None else params_half.data_ptr(), gradients.data_ptr(),
+                                      GRADIENT_PRECISION[gradients.dtype]):
             _C.check(1)
 
     def step_count(self):
@@ -112,14 +119,14 @@ class NativeOptimizer:
             _C.check(_C.lib.tcnn_optimizer_deserialize(self._h, data, len(data)))
 
     def custom_weights(self):
-        """A half tensor copy (on the optimizer's device) of its inference weights (Ema, Average, Lookahead), or None."""
+        """A tensor copy (on the optimizer's device, in its weight dtype) of its inference weights (Ema, Average, Lookahead), or None."""
         ptr = _C.lib.tcnn_optimizer_custom_weights(self._h)
         if not ptr:
             return None
         with self._on_device():
             torch.cuda.synchronize()
-            out = torch.empty(self.n_params, dtype=torch.half, device=self.device)
-            _C.memcpy_dtod(out.data_ptr(), ptr, self.n_params * 2)
+            out = torch.empty(self.n_params, dtype=self.weight_dtype, device=self.device)
+            _C.memcpy_dtod(out.data_ptr(), ptr, self.n_params * self.weight_dtype.itemsize)
         return out
 
     def weights_restored(self, params_half, stream=None):
