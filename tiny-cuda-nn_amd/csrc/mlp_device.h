@@ -18,6 +18,18 @@ constexpr float K_ACT = 10.0f;
 
 __device__ inline float logistic(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// expf where a cancellation magnifies its last bit: 1 - expf(-10 y) in Softplus' for small outputs y, 1 - 2 s in Sigmoid'' for small z.  The
+// reference's results come from a correctly rounded expf; ocml's is one ulp off for 5 % of the arguments, which these differences turn into 2
+// and 8 half steps.  Below 2^-6 the series 1 + x + x^2/2 + .. + x^5/120, its low part carried beside 1 + x, is correctly rounded but for one
+// argument in 40 000; elsewhere expf's last bit is far below half precision.
+__device__ inline float expf_near_zero(float x) {
+	if (!(fabsf(x) < 0x1p-6f)) return expf(x);
+	const float lo = x * x * (0.5f + x * (1.0f / 6 + x * (1.0f / 24 + x * (1.0f / 120))));
+	const float s = 1.0f + x;
+	const float e = x - (s - 1.0f); // exact: what 1 + x rounded away
+	return s + (e + lo);
+}
+
 // common_device.h:102-160, applied to the fp16-rounded accumulator like the reference's warp_activation.  T: the network's precision --
 // half_t, or float for the full-precision layers (k_mlp_layers_f32.hip), where every (T) below is no rounding at all
 template <typename T>
@@ -46,7 +58,7 @@ __device__ inline T activation_bwd(uint32_t act, T grad, T fwd) {
 		case (uint32_t)Activation::Exponential: return grad * fwd;
 		case (uint32_t)Activation::Sigmoid: return grad * (T)(fwd * (T)(1.0f - y));
 		case (uint32_t)Activation::Squareplus: { const float t = y * K_ACT; return grad * (T)(t * t / (t * t + 1)); }
-		case (uint32_t)Activation::Softplus: return grad * (T)(1.0f - expf(-y * K_ACT));
+		case (uint32_t)Activation::Softplus: return grad * (T)(1.0f - expf_near_zero(-y * K_ACT));
 		case (uint32_t)Activation::Tanh: return grad * (T)(1.0f - (y * y));
 		default: return grad; // None; Sine is unsupported from outputs (common_device.h:261-265)
 	}
@@ -61,7 +73,7 @@ __device__ inline float act_d1(const uint32_t act, const float x) {
 		case (uint32_t)Activation::LeakyReLU: return x > 0.0f ? 1.0f : 0.01f;
 		case (uint32_t)Activation::Exponential: return expf(x);
 		case (uint32_t)Activation::Sine: return cosf(x);
-		case (uint32_t)Activation::Sigmoid: { const float s = logistic(x); return s * (1.0f - s); }
+		case (uint32_t)Activation::Sigmoid: { const float s = 1.0f / (1.0f + expf_near_zero(-x)); return s * (1.0f - s); }
 		case (uint32_t)Activation::Squareplus: { const float y = x * K_ACT; return 0.5f * (1.0f + y / sqrtf(y * y + 4)); }
 		case (uint32_t)Activation::Softplus: return logistic(x * K_ACT);
 		case (uint32_t)Activation::Tanh: { const float t = tanhf(x); return 1.0f - t * t; }
@@ -72,7 +84,7 @@ __device__ inline float act_d2(const uint32_t act, const float x) {
 	switch (act) {
 		case (uint32_t)Activation::Exponential: return expf(x);
 		case (uint32_t)Activation::Sine: return -sinf(x);
-		case (uint32_t)Activation::Sigmoid: { const float s = logistic(x); return s * (1.0f - s) * (1.0f - 2.0f * s); }
+		case (uint32_t)Activation::Sigmoid: { const float s = 1.0f / (1.0f + expf_near_zero(-x)); return s * (1.0f - s) * (1.0f - 2.0f * s); }
 		case (uint32_t)Activation::Squareplus: { const float y = x * K_ACT, q = y * y + 4; return 2.0f * K_ACT / (q * sqrtf(q)); }
 		case (uint32_t)Activation::Softplus: { const float s = logistic(x * K_ACT); return K_ACT * s * (1.0f - s); }
 		case (uint32_t)Activation::Tanh: { const float t = tanhf(x); return -2.0f * t * (1.0f - t * t); }
