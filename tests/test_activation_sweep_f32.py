@@ -89,11 +89,14 @@ def test_dL_dy_and_the_tangent_stay_in_range():
 
 
 def test_the_allowances_are_the_measured_ones():
-    """K_f of activation_sweep_f32 is what profiles/libm_f32_ulp.txt records, and no more than the few ulp test_fp32_network.py allows"""
+    """K_f of activation_sweep_f32 is what profiles/libm_f32_ulp.txt records, and no more than the few ulp test_fp32_network.py allows; the
+    profile's one other constant, powf in Adam's debiasing factor, is the K_POWF of adam_reference"""
+    import adam_reference
+
     text = open(os.path.join(ROOT, "profiles", "libm_f32_ulp.txt")).read()
     measured = {name: int(k) for name, k in re.findall(r"^K_(\w+)\s*= (\d+)$", text, flags=re.M)}
     mine = {"EXPF": s32.K_EXPF, "LOGF": s32.K_LOGF, "SINF": s32.K_SINF, "COSF": s32.K_COSF, "TANHF": s32.K_TANHF}
-    assert measured == mine
+    assert measured == {**mine, "POWF": adam_reference.K_POWF}
     assert all(0 <= k <= s32.MAX_K for k in mine.values())
 
 

@@ -1427,6 +1427,96 @@ def test_live_fragment_image_is_kept_current_by_the_optimizer_kernel(tcnn, oracl
     assert preps_a == [1, 1, 2, 3, 4, 4, 4, 5, 6], preps_a
 
 
+# The optimizer's routes under Adam's options (tests/adam_reference.py: every numeric option at once, and each class of parameters frozen;
+# tests/test_adam_options.py holds the stand-alone kernels to the oracle under the same sets, test_standalone_optimizer.py the trainer's own
+# launch to the stand-alone one).  clipping_magnitude 0.2 instead of the sets' 0.3: the networks' weights start within Xavier's bound, sqrt(6 / 128) =
+# 0.217 for a 64 x 64 matrix, and four steps of at most about the learning rate do not carry them to 0.3; 0.2 binds from the first step in
+# every model below, as the run with the optimizer's own launch shows (each FULL case asserts it from that run).
+ROUTE_CLIP = 0.2
+
+
+def _route_optimizer(name):
+    import adam_reference as ar
+
+    cfg = dict(ar.OPTION_SETS[name])
+    if name == "full":
+        cfg["clipping_magnitude"] = ROUTE_CLIP
+    return cfg
+
+
+def _route_run(tcnn, monkeypatch, cfg, n_in, batches, env):
+    """(what is compared bit for bit, what is not) after one training step per batch under the switches of env"""
+    import msgpack
+
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    half0 = _bits(tcnn.Trainer(n_in, 3, cfg, seed=1337).params()).copy()  # (of a twin: a parameter pointer handed out ends the trust in a live image)
+    tr = tcnn.Trainer(n_in, 3, cfg, seed=1337)
+    for x, t in batches:
+        tr.training_step(_t(x), _t(t))
+    opt = msgpack.unpackb(tr.serialize(True), raw=False)["optimizer"]
+    for k in env:
+        monkeypatch.delenv(k)
+    same = {"gradients": _bits(tr.param_gradients()).copy(), "half": _bits(tr.params()).copy(), "fp": tr.params_full_precision().cpu().numpy().view(np.uint32).copy(),
+            "m1": opt["first_moments_binary"], "m2": opt["second_moments_binary"], "steps": opt["param_steps_binary"], "current_step": opt["current_step"]}
+    return same, {"half0": half0, "prologue_steps": tr.optimizer_prologue_steps(), "in_flush": tr.params_updated_in_flush(), "image_preps": tr.image_preps()}
+
+
+def _assert_route_pair(oracle, name, cfg, n_in, a, b, info_a):
+    """two routes' results are the same bits; the options did something on these gradients"""
+    for key in a:
+        assert np.array_equal(a[key], b[key]) if isinstance(a[key], np.ndarray) else a[key] == b[key], f"{name}: {key} differs between the routes"
+    assert np.any(a["gradients"] & 0x7FFF)
+    n_net = oracle.Trainer(n_in, 3, cfg, seed=1337).model.network.n_params
+    moved = a["half"] != info_a["half0"]
+    counts = np.frombuffer(a["steps"], dtype=np.uint32)
+    if name == "full":
+        w = a["fp"].view(np.float32)
+        assert np.any(np.abs(w) == np.float32(ROUTE_CLIP)), "no weight sits on the clip"
+        assert np.all(np.abs(w) <= np.float32(ROUTE_CLIP))
+    elif name == "frozen_matrix":
+        assert not moved[:n_net].any() and not counts[:n_net].any(), "a frozen matrix weight moved"
+        assert n_net == a["half"].size or moved[n_net:].any()
+    else:
+        assert not moved[n_net:].any() and not counts[n_net:].any(), "a frozen grid entry moved"
+        assert moved[:n_net].any()
+
+
+@pytest.mark.parametrize("name", ["full", "frozen_matrix", "frozen_grid"])
+@pytest.mark.parametrize("base,n_in,n", [(CONFIG_C3A, 2, 16384), (CONFIG_3D_F2, 3, 8192)], ids=["c3a", "3d_f2"])
+def test_optimizer_prologue_under_adam_options_is_bit_identical(tcnn, oracle, monkeypatch, base, n_in, n, name):
+    """k_adam_prologue's three kinds of blocks (slab reduction, shared ranges, bulk) against the finalize pass and k_adam as launches of their
+    own (TCNN_AMD_ADAM_PROLOGUE=0), with decay, clipping, adabound, the non-matrix factor and a large epsilon all on, and with either class
+    of parameters frozen: gradients, master and half weights, both moments and the counts agree bit for bit."""
+    cfg = {**base, "optimizer": _route_optimizer(name)}
+    batches = [oracle.synthetic_batch(n, n_in, 3, seed=90 + i) for i in range(4)]
+    a, info_a = _route_run(tcnn, monkeypatch, cfg, n_in, batches, {})
+    b, info_b = _route_run(tcnn, monkeypatch, cfg, n_in, batches, {"TCNN_AMD_ADAM_PROLOGUE": "0"})
+    assert info_b["prologue_steps"] == 0 and info_a["prologue_steps"] >= len(batches) - 1, "which launch ran the finalize pass is not what this run asked for"
+    assert a["current_step"] == len(batches)
+    _assert_route_pair(oracle, name, cfg, n_in, b, a, info_b)
+
+
+@pytest.mark.parametrize("name", ["full", "frozen_matrix"])
+def test_adam_in_the_slab_reduction_under_adam_options_is_bit_identical(tcnn, oracle, monkeypatch, name):
+    """k_wgrad_reduce_adam (BASELINE config 2) against a k_adam launch behind the reduction (TCNN_AMD_ADAM_IN_REDUCE=0) and against
+    k_mlp_prep in every step (TCNN_AMD_LIVE_IMAGE=0), under the options: bit-identical as above -- a fragment image that missed a clipped or
+    a frozen weight would show in the next step's gradients.  With the matrices frozen the network's weights keep their initial bits."""
+    n = 8192
+    cfg = {**CONFIG_C2, "optimizer": _route_optimizer(name)}
+    batches = [oracle.synthetic_batch(n, 2, 3, seed=95 + i) for i in range(4)]
+    a, info_a = _route_run(tcnn, monkeypatch, cfg, 2, batches, {})
+    b, info_b = _route_run(tcnn, monkeypatch, cfg, 2, batches, {"TCNN_AMD_ADAM_IN_REDUCE": "0"})
+    c, info_c = _route_run(tcnn, monkeypatch, cfg, 2, batches, {"TCNN_AMD_LIVE_IMAGE": "0"})
+    assert info_b["in_flush"] == 0 and info_a["in_flush"] == a["half"].size, "which kernel applied the update is not what this run asked for"
+    assert info_a["image_preps"] == 1 and info_c["image_preps"] == len(batches)
+    assert a["current_step"] == len(batches)
+    _assert_route_pair(oracle, name, cfg, 2, b, a, info_b)
+    _assert_route_pair(oracle, name, cfg, 2, b, c, info_b)
+    if name == "frozen_matrix":
+        assert np.array_equal(a["half"], info_a["half0"]) and np.array_equal(c["half"], info_c["half0"])
+
+
 def test_adam_step_counts_are_kept_narrow_and_widened_losslessly(tcnn, oracle, monkeypatch):
     """The per-parameter update counts live as uint16 while the optimizer's own step count is below 65 535 and are widened to uint32
     before one could overflow (AdamOptimizer::ensure_step_width): weights, moments and the counts a snapshot reports are bit-identical

@@ -103,7 +103,10 @@ def _configs(oracle):
         {**adam, "n_params_to_optimize": 333},
         {**adam, "learning_rate": 5e-3, "n_params_to_optimize": n - n_net - 333 - 5},
     ]}
-    return {"adam": (ADAM, 4), "sgd": (SGD, 4), "nested": (NESTED, 5), "composite": (_composite(n_net, n - n_net), 4), "unaligned": (unaligned, 3), "novograd": (NOVOGRAD, 4)}
+    import adam_reference as ar
+
+    # (the options of tests/test_adam_options.py, which holds the stand-alone kernels to the oracle per element: here the trainer's launch to them)
+    return {"adam": (ADAM, 4), "adam_full": (ar.FULL, 4), "adam_frozen_grid": (ar.OPTION_SETS["frozen_grid"], 4), "sgd": (SGD, 4), "nested": (NESTED, 5), "composite": (_composite(n_net, n - n_net), 4), "unaligned": (unaligned, 3), "novograd": (NOVOGRAD, 4)}
 
 
 class _State:
@@ -153,7 +156,7 @@ def _run(tcnn, oracle, name):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["adam", "sgd", "nested", "composite", "unaligned", "novograd"])
+@pytest.mark.parametrize("name", ["adam", "adam_full", "adam_frozen_grid", "sgd", "nested", "composite", "unaligned", "novograd"])
 def test_standalone_steps_equal_the_trainers_bitwise(tcnn, oracle, name):
     from test_gpu_parity import _bits
 

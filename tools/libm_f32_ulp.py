@@ -1,10 +1,12 @@
-"""How far the device's expf, logf, sinf, cosf and tanhf are from correctly rounded, in float steps: the K_f of tests/activation_sweep_f32.py.
+"""How far the device's expf, logf, sinf, cosf and tanhf are from correctly rounded, in float steps: the K_f of tests/activation_sweep_f32.py --
+and its powf(beta, t), the one libm call of Adam's debiasing factor: the K_POWF of tests/adam_reference.py.
 
-    python tools/libm_f32_ulp.py arguments ARGS.f32            # the arguments: the sweep, and what the expressions of mlp_device.h pass
-    tools/ubench/libm_f32 ARGS.f32 RESULTS.f32                 # on the GPU (tools/ubench/libm_f32.hip)
-    python tools/libm_f32_ulp.py report RESULTS.f32 [PROFILE]  # largest distance and a histogram per function -> profiles/libm_f32_ulp.txt
+    python tools/libm_f32_ulp.py arguments ARGS.f32 POW_ARGS.f32       # the arguments: the sweep, what the expressions of mlp_device.h pass, and (beta, t)
+    tools/ubench/libm_f32 ARGS.f32 RESULTS.f32 POW_ARGS.f32 POW.f32    # on the GPU (tools/ubench/libm_f32.hip)
+    python tools/libm_f32_ulp.py report RESULTS.f32 POW.f32 [PROFILE]  # largest distance and a histogram per function -> profiles/libm_f32_ulp.txt
 
-The yardstick is the float64 value rounded once to float32 (activation_sweep._rounded); no kernel of the project takes part.
+The yardstick is the float64 value rounded once to float32 (activation_sweep._rounded; adam_reference.pow_rounded); no kernel of the project
+takes part.
 """
 import os
 import sys
@@ -15,6 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import activation_sweep as sw  # noqa: E402
+import adam_reference as ar  # noqa: E402
 import activation_sweep_f32 as s32  # noqa: E402
 
 F = np.float32
@@ -39,10 +42,33 @@ def segments():
     ]
 
 
-def write_arguments(path):
+def write_arguments(path, pow_path):
     a = np.concatenate([s[1] for s in segments()]).astype(F)
     a.tofile(path)
     print(f"{a.size} arguments -> {path}")
+    p = ar.pow_arguments()
+    p.tofile(pow_path)
+    print(f"{p.shape[0]} (beta, t) pairs -> {pow_path}")
+
+
+def pow_report(pow_results_path):
+    """(K_POWF, the table's rows): powf(beta, t) for every beta of tests/adam_reference.py, t = 1 .. 64"""
+    args = ar.pow_arguments()
+    got = np.fromfile(pow_results_path, dtype=F)
+    assert got.size == args.shape[0], (got.size, args.shape[0])
+    unlike_all = ~np.isfinite(got) | (got <= 0)
+    d_all = ar.float_steps(np.where(unlike_all, F(1), got), ar.pow_rounded(args))
+    rows = []
+    for beta in ar.BETAS:
+        sel = args[:, 0] == F(beta)
+        d, unlike = d_all[sel], unlike_all[sel]
+        d_like = d[~unlike]
+        worst = int(d_like.max()) if d_like.size else 0
+        hist = np.bincount(np.minimum(d_like, 9), minlength=10)
+        where = f"t = {int(args[sel][int(np.argmax(np.where(unlike, 0, d))), 1])}" if worst else ""
+        rows.append(f"{'powf':<6} {f'({beta!r}, 1 .. {ar.POW_STEPS[-1]})':<16} {'yes':<5} {int(sel.sum()):>8} {worst:>6} {int(unlike.sum()):>7}  " + " ".join(f"{int(h):>7}" for h in hist) + f"  {where}")
+    k = (1 << 30) if unlike_all.any() else int(d_all.max())
+    return k, rows
 
 
 def distances(fn, args, got):
@@ -56,7 +82,7 @@ def distances(fn, args, got):
     return d, unlike
 
 
-def report(results_path, profile_path):
+def report(results_path, pow_results_path, profile_path):
     segs = segments()
     n = sum(s[1].size for s in segs)
     res = np.fromfile(results_path, dtype=F)
@@ -66,6 +92,8 @@ def report(results_path, profile_path):
              "compiled with build.py's FLAGS, over the sweep of tests/activation_sweep_f32.py (x) and over the arguments the expressions of mlp_device.h",
              "pass (tools/libm_f32_ulp.py).  K_f: the largest distance over the sweep and the arguments the function is called with; the other rows are",
              "for the record.  unlike: results that are finite on one side only (or NaN on one side only), none of which a distance describes.",
+             "powf: powf(beta, t) as Adam's debiasing factor calls it (adam_debias, k_misc.hip), for every beta of tests/adam_reference.py and t = 1 .. 64:",
+             "K_POWF is the tolerance constant of that file.",
              ""]
     ks = {}
     table = []
@@ -88,7 +116,9 @@ def report(results_path, profile_path):
                 j = int(np.argmax(np.where(unlike, 0, d)))
                 where = f"{float(args[j])!r}"
             table.append(f"{name:<6} {seg:<16} {'yes' if used else 'no':<5} {args.size:>8} {worst:>6} {int(unlike.sum()):>7}  " + " ".join(f"{int(h):>7}" for h in hist) + f"  {where}")
-    for name, _ in FUNCTIONS:
+    ks["powf"], pow_rows = pow_report(pow_results_path)
+    table += pow_rows
+    for name in [f[0] for f in FUNCTIONS] + ["powf"]:
         lines.append(f"K_{name.upper():<6} = {ks[name]}")
     lines += ["", f"{'libm':<6} {'arguments':<16} {'K_f?':<5} {'count':>8} {'worst':>6} {'unlike':>7}  " + " ".join(f"{'=' + str(k):>7}" for k in range(9)) + f" {'>=9':>7}  worst at"]
     lines += table
@@ -101,9 +131,9 @@ def report(results_path, profile_path):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) >= 3 and sys.argv[1] == "arguments":
-        write_arguments(sys.argv[2])
-    elif len(sys.argv) >= 3 and sys.argv[1] == "report":
-        report(sys.argv[2], sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "libm_f32_ulp.txt"))
+    if len(sys.argv) == 4 and sys.argv[1] == "arguments":
+        write_arguments(sys.argv[2], sys.argv[3])
+    elif len(sys.argv) >= 4 and sys.argv[1] == "report":
+        report(sys.argv[2], sys.argv[3], sys.argv[4] if len(sys.argv) > 4 else os.path.join(ROOT, "profiles", "libm_f32_ulp.txt"))
     else:
         sys.exit(__doc__)

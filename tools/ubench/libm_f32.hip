@@ -2,8 +2,9 @@
 // the yardstick of tests/activation_sweep_f32.py allows each of them K_f float steps around the correctly rounded value, and K_f is
 // measured here against float64, never against a kernel of the project (tools/libm_f32_ulp.py writes the arguments and reads the results).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-pass-failed -Wno-unused-result -munsafe-fp-atomics -o libm_f32 libm_f32.hip
-//   ./libm_f32 arguments.f32 results.f32
+//   ./libm_f32 arguments.f32 results.f32 [pow_arguments.f32 pow_results.f32]
 // results.f32: [5][n] floats -- expf, logf, sinf, cosf, tanhf of the n arguments, in that order.
+// pow_arguments.f32: [m][2] floats (base, exponent); pow_results.f32: [m] floats, powf(base, exponent) -- what adam_debias (k_misc.hip) calls.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
@@ -29,9 +30,55 @@ __global__ void __launch_bounds__(256) k_libm_f32(const uint32_t n, const float*
 	y[(size_t)4 * n + i] = tanhf(v);
 }
 
+__global__ void __launch_bounds__(256) k_powf(const uint32_t m, const float* __restrict__ args, float* __restrict__ y) {
+	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+	if (i < m) y[i] = powf(args[2 * i], args[2 * i + 1]);
+}
+
+static int run_powf(const char* in_path, const char* out_path) {
+	FILE* f = fopen(in_path, "rb");
+	if (!f) {
+		perror(in_path);
+		return 1;
+	}
+	fseek(f, 0, SEEK_END);
+	const long bytes = ftell(f);
+	fseek(f, 0, SEEK_SET);
+	if (bytes <= 0 || bytes % 8 != 0 || bytes / 8 >= (1l << 24)) {
+		fprintf(stderr, "%s: expected between 1 and 2^24 pairs of floats\n", in_path);
+		return 1;
+	}
+	const uint32_t m = (uint32_t)(bytes / 8);
+	std::vector<float> args((size_t)2 * m), y(m);
+	if (fread(args.data(), 4, args.size(), f) != args.size()) {
+		fprintf(stderr, "%s: short read\n", in_path);
+		return 1;
+	}
+	fclose(f);
+	float *da = nullptr, *dy = nullptr;
+	CHECK(hipMalloc(&da, args.size() * 4));
+	CHECK(hipMalloc(&dy, (size_t)m * 4));
+	CHECK(hipMemcpy(da, args.data(), args.size() * 4, hipMemcpyHostToDevice));
+	hipLaunchKernelGGL(k_powf, dim3((m + 255) / 256), dim3(256), 0, 0, m, da, dy);
+	CHECK(hipGetLastError());
+	CHECK(hipDeviceSynchronize());
+	CHECK(hipMemcpy(y.data(), dy, (size_t)m * 4, hipMemcpyDeviceToHost));
+	FILE* o = fopen(out_path, "wb");
+	if (!o) {
+		perror(out_path);
+		return 1;
+	}
+	if (fwrite(y.data(), 4, y.size(), o) != y.size() || fclose(o) != 0) {
+		fprintf(stderr, "%s: short write\n", out_path);
+		return 1;
+	}
+	printf("%u pairs, powf -> %s\n", m, out_path);
+	return 0;
+}
+
 int main(int argc, char** argv) {
-	if (argc != 3) {
-		fprintf(stderr, "usage: %s arguments.f32 results.f32\n", argv[0]);
+	if (argc != 3 && argc != 5) {
+		fprintf(stderr, "usage: %s arguments.f32 results.f32 [pow_arguments.f32 pow_results.f32]\n", argv[0]);
 		return 2;
 	}
 	FILE* f = fopen(argv[1], "rb");
@@ -71,5 +118,5 @@ int main(int argc, char** argv) {
 		return 1;
 	}
 	printf("%u arguments, 5 functions -> %s\n", n, argv[2]);
-	return 0;
+	return argc == 5 ? run_powf(argv[3], argv[4]) : 0;
 }
