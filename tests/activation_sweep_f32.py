@@ -2,10 +2,10 @@
 tests/test_activation_sweep_f32.py.
 
 A plain module the tests import (no fixtures, no GPU), in the setting of tests/activation_sweep.py: a CutlassMLP of 16 inputs, hidden layers
-of width W and 16 outputs created with precision fp32 (k_mlp_layers_f32.hip), every weight matrix zero except for sixteen ones, so that every
+of width W and 16 outputs created with precision fp32 (k_mlp_layers.hip), every weight matrix zero except for sixteen ones, so that every
 matrix product is one value times one plus zeros and every tensor is an elementwise function of x, dL/dy and the tangent v.
 
-The yardstick restates every expression of mlp_device.h and of the epilogues of k_mlp_layers_f32.hip in float32 numpy, one IEEE operation after
+The yardstick restates every expression of mlp_device.h and of the epilogues of k_mlp_layers.hip in float32 numpy, one IEEE operation after
 the other in the kernels' order (the file is built with -ffp-contract=off: a product and a sum are two roundings).  *, +, / and sqrtf are
 correctly rounded on both sides.  A call of expf, logf, sinf, cosf or tanhf is not: it yields 2 K_f + 1 CANDIDATES, the correctly rounded
 value (the float64 value rounded once) moved j float steps, j = -K_f .. K_f, and the candidates are carried through the rest of the expression.
@@ -34,7 +34,7 @@ K_COSF = 2
 K_TANHF = 1
 MAX_K = 4  # the "few ulp" tests/test_fp32_network.py allows the device's libm in its factor 4
 
-WIDTHS = (48, 144)  # k_layer_gemm_f32<1,4,4,4> and <2,2,4,4>
+WIDTHS = (48, 144)  # k_layer_gemm<float,1,4,4,4> and <float,2,2,4,4>
 CURVATURE = ("Exponential", "Sine", "Sigmoid", "Squareplus", "Softplus", "Tanh")
 MAX_SHARE_OUTSIDE = {"Exponential": 0.15, "Softplus": 0.15}  # of the rows; 0.02 for the others
 DENSE_BINADES = range(-12, 7)  # the dense part: 2^-12 <= |x| < 2^7
@@ -259,7 +259,7 @@ def activation_bwd(m, act, grad, y):
 
 @_quiet
 def sine_bwd(m, grad, z):
-    """a Sine hidden layer: from the stored pre-activation (the LG_BWD epilogue of k_layer_gemm_f32)"""
+    """a Sine hidden layer: from the stored pre-activation (the LG_BWD epilogue of k_layer_gemm<float>)"""
     return grad * m.cosf(z)
 
 
@@ -348,7 +348,7 @@ def forward(m, case, x, hidden=1):
 @_quiet
 def backward(m, case, x, g, hidden=1, own_output=None):
     """Network::backward's dL/dinput.  own_output: the device's forward output, which then stands for the activations the derivative is taken
-    from -- the output layer's (k_act_bwd_output_f32) or, with an output activation of None behind one hidden layer, the hidden layer's: the
+    from -- the output layer's (k_act_bwd_output<float>) or, with an output activation of None behind one hidden layer, the hidden layer's: the
     output is their product with the identity, the same values wherever its row is finite; on its other rows the hidden activations cannot
     be seen, and the restatement's candidates stand for them"""
     acts = _acts(case, hidden)
@@ -368,7 +368,7 @@ def backward(m, case, x, g, hidden=1, own_output=None):
 
 @_quiet
 def delta(m, act, g, aux):
-    """k_layer_delta_f32"""
+    """k_layer_delta<float>"""
     return act_d1(m, act, aux) * g
 
 

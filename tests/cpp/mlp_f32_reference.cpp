@@ -1,4 +1,4 @@
-// mlp_f32_reference.cpp -- the numerical contract of the full-precision layer kernels (tiny-cuda-nn_amd/csrc/k_mlp_layers_f32.hip)
+// mlp_f32_reference.cpp -- the numerical contract of the full-precision layer kernels (tiny-cuda-nn_amd/csrc/k_mlp_layers.hip, LayerElem<float>)
 // restated on the CPU with std::fmaf: every element of a layer product is one fp32 accumulator that starts at +0 and receives its
 // products in ascending k, one fmaf each.  tests/test_fp32_network.py compiles this file with g++ (-ffp-contract=off) and compares the
 // GPU's results with what it writes, bit for bit.

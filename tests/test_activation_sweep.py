@@ -27,7 +27,7 @@ the first application and the second magnifies it, which no bar on single roundi
 applications are then the oracle's, bit for bit) and every output activation behind two None layers.
 
 NOT reachable in this setting: r32, r32a, r32w and regs_fast (a grid input, and a loss instead of an external dL/dy), r32ob and train_ob (a
-OneBlob input).  The fp32 networks of k_mlp_layers_f32.hip have a sweep of their own, over a wide float32 range and with a per-element yardstick of
+OneBlob input).  The fp32 networks (k_layer_gemm<float>, k_mlp_layers.hip) have a sweep of their own, over a wide float32 range and with a per-element yardstick of
 another kind (candidate sets): tests/test_activation_sweep_f32.py.  Not covered: weight gradients, which are sums of wide-range terms here and are
 held by test_weight_gradients_exact.py.
 """

@@ -1,8 +1,8 @@
-"""Every activation over a wide float32 range, in the fp32 MLP kernels (k_mlp_layers_f32.hip).
+"""Every activation over a wide float32 range, in the fp32 MLP kernels (k_mlp_layers.hip).
 
 The fp32 networks instantiate activation_fwd<float>, activation_bwd<float>, act_d1, act_d2 and expf_near_zero of mlp_device.h in
-k_layer_gemm_f32 (the narrow tile <1,4,4,4> and the wide one <2,2,4,4>, the first-order and the second-order epilogue of each),
-k_layer_delta_f32 and k_act_bwd_output_f32.  tests/test_fp32_network.py feeds them pre-activations within about |z| < 2 and judges a tensor
+k_layer_gemm<float> (the narrow tile <1,4,4,4> and the wide one <2,2,4,4>, the first-order and the second-order epilogue of each),
+k_layer_delta<float> and k_act_bwd_output<float>.  tests/test_fp32_network.py feeds them pre-activations within about |z| < 2 and judges a tensor
 by its maximum; here 65 536 floats from the smallest subnormal to the largest finite float go through each activation, in the setting of
 tests/activation_sweep_f32.py (identity weights: every tensor is an elementwise function of x, dL/dy and the tangent v), and every single
 float is judged: expf's overflow at 88.72 (8.872 for Softplus), its subnormal results and its underflow, the 2^-6 switch inside
@@ -20,7 +20,7 @@ restatement; on the other rows the class (finite, +inf, -inf, NaN) of every elem
 Squareplus in two hidden layers runs through bwd_bwd_input as well: the only curved activation without a libm call, so the only one that
 holds LG_CURVATURE's c + d1 * acc with a curved d1 bit for bit through A(A(x)).
 
-Not judged: parameter gradients, sums over the 4096 rows here (tests/test_fp32_network.py bounds them).  k_layer_delta_f32 runs in every
+Not judged: parameter gradients, sums over the 4096 rows here (tests/test_fp32_network.py bounds them).  k_layer_delta<float> runs in every
 (None, B) case and is restated (activation_sweep_f32.delta, held against float64 below), but its result d_K = a'(z_K) dL/dy reaches only the
 parameter gradients; what it calls, act_d1, is judged through dL/d(dL/doutput).  The fp32 Trainer is held bit for bit against the module
 (tests/test_fp32_training.py), so it is covered by this sweep.  Measured shares: profiles/activation_sweep_f32.txt.
@@ -199,7 +199,7 @@ def _assert_close(what, got, want, x, ranges):
 @pytest.mark.parametrize("act", sw.ACTIVATIONS)
 def test_restatement_is_the_mathematical_function(act):
     """the j = 0 restatement of activation_fwd, activation_bwd (from the restated output; a Sine hidden layer from the pre-activation), act_d1,
-    act_d2, k_layer_delta_f32 and the epilogue's products against float64, so that a restatement that copies a kernel's bug does not pass"""
+    act_d2, k_layer_delta<float> and the epilogue's products against float64, so that a restatement that copies a kernel's bug does not pass"""
     m = s32.ONE_CANDIDATE
     x32, g32, v32 = s32.sweep_x(), s32.dy(), s32.tangent()
     x, g, v = (a.astype(np.float64) for a in (x32, g32, v32))

@@ -1,6 +1,6 @@
 """Full-precision (fp32) networks: tcnn_create_network_precision / tcnn_create_network_with_input_encoding_precision and
-tcnn.Network / tcnn.NetworkWithInputEncoding(dtype=torch.float32) -- Network{json, Precision::Fp32} on the kernels of
-tiny-cuda-nn_amd/csrc/k_mlp_layers_f32.hip.
+tcnn.Network / tcnn.NetworkWithInputEncoding(dtype=torch.float32) -- Network{json, Precision::Fp32} on the fp32 instantiation of
+the layer kernels (tiny-cuda-nn_amd/csrc/k_mlp_layers.hip, LayerElem<float>) and the fp32 weight gradients (k_mlp_layers_f32.hip).
 
 Three yardsticks, none of them the kernels themselves:
   * activations None and ReLU: tests/cpp/mlp_f32_reference.cpp, the kernels' contract restated with std::fmaf (one accumulator per

@@ -799,13 +799,6 @@ __global__ void __launch_bounds__(WR_ELEMS * WR_GROUPS) k_wgrad_reduce_adam(cons
 	}
 }
 
-// kernel_activation_backward_output (common_device.h:748): dL/d(pre-activation output) from the forward OUTPUT values
-__global__ void __launch_bounds__(256) k_act_bwd_output(const uint32_t n_elems, const uint32_t act, const half_t* __restrict__ dL_dout, const half_t* __restrict__ out, half_t* __restrict__ result) {
-	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n_elems) return;
-	result[i] = activation_bwd(act, dL_dout[i], out[i]);
-}
-
 inline uint32_t wgrad_grid(uint32_t n) {
 	const uint32_t n_chunks = n / WG_CHUNK;
 	return n_chunks < 256 ? (n_chunks ? n_chunks : 1) : 256;
@@ -923,11 +916,6 @@ void mlp_backward(hipStream_t stream, const MlpDesc& d, const void* image, uint3
 	}
 }
 
-void mlp_activation_backward_output(hipStream_t stream, uint32_t n_elems, uint32_t activation, const void* dL_dout, const void* out, void* result) {
-	if (n_elems == 0) return;
-	hipLaunchKernelGGL(k_act_bwd_output, dim3(div_round_up(n_elems, 256)), dim3(256), 0, stream, n_elems, activation, (const half_t*)dL_dout, (const half_t*)out, (half_t*)result);
-}
-
 void mlp_reduce_slabs(hipStream_t stream, uint32_t n_params, uint32_t n_slabs, const float* slabs, void* grad_half, bool accumulate, const AdamInReduce* adam) {
 	if (n_params == 0) return;
 	const dim3 grid(div_round_up(n_params, (uint32_t)WR_ELEMS)), block(WR_ELEMS * WR_GROUPS);
@@ -972,10 +960,11 @@ static void launch_wgrad_jobs(hipStream_t stream, uint32_t n, uint32_t rows, uin
 void mlp_wgrad(hipStream_t stream, uint32_t n, const void* dO, uint32_t ldo, uint32_t rows, const void* In, uint32_t ldi, uint32_t cols,
                void* grad_half, uint32_t ldg, bool accumulate, float* workspace) {
 	const WgradPanel p{dO, ldo, rows, In, ldi, cols, grad_half, ldg, false, false};
-	mlp_wgrad_panels(stream, n, &p, 1, accumulate, workspace);
+	mlp_wgrad_panels(stream, Precision::Fp16, n, &p, 1, accumulate, workspace);
 }
 
-size_t wgrad_panels_workspace_floats(const WgradPanel* panels, uint32_t count, uint32_t n) {
+size_t wgrad_panels_workspace_floats(Precision precision, const WgradPanel* panels, uint32_t count, uint32_t n) {
+	if (precision == Precision::Fp32) return wgrad_panels_workspace_floats_f32(panels, count, n); // (k_mlp_layers_f32.hip: another algorithm)
 	size_t total = 0;
 	for (uint32_t i = 0; i < count; ++i) total += wgrad_workspace_floats(panels[i].rows, panels[i].cols, n);
 	return total;
@@ -984,7 +973,8 @@ size_t wgrad_panels_workspace_floats(const WgradPanel* panels, uint32_t count, u
 // Several products over the same n samples (a network's layers): those of one shape the fast kernels take share a launch (and one launch of
 // the slab reduction) -- they are independent, and 2 x 6 launches of ~5 - 35 us were a fifth of a 128 x 5 step at 2^16 samples.  Every
 // product keeps its own slabs, its chunks and their order: the same bits as one launch per product.
-void mlp_wgrad_panels(hipStream_t stream, uint32_t n, const WgradPanel* panels, uint32_t count, bool accumulate, float* workspace) {
+void mlp_wgrad_panels(hipStream_t stream, Precision precision, uint32_t n, const WgradPanel* panels, uint32_t count, bool accumulate, float* workspace) {
+	if (precision == Precision::Fp32) return mlp_wgrad_panels_f32(stream, n, panels, count, accumulate, workspace);
 	CHECK_THROW(n % WG_CHUNK == 0);
 	std::vector<bool> done(count, false);
 	std::vector<float*> slabs(count);

@@ -7,6 +7,11 @@
 #include <hip/hip_fp16.h>
 
 namespace tcnn_amd {
+
+// the fp32 weight gradients (k_mlp_layers_f32.hip) behind wgrad_panels_workspace_floats / mlp_wgrad_panels (k_mlp.hip), which hand Precision::Fp32 on
+size_t wgrad_panels_workspace_floats_f32(const WgradPanel* panels, uint32_t count, uint32_t n);
+void mlp_wgrad_panels_f32(hipStream_t stream, uint32_t n, const WgradPanel* panels, uint32_t count, bool accumulate, float* workspace);
+
 namespace {
 
 typedef _Float16 half_t;
@@ -31,7 +36,7 @@ __device__ inline float expf_near_zero(float x) {
 }
 
 // common_device.h:102-160, applied to the fp16-rounded accumulator like the reference's warp_activation.  T: the network's precision --
-// half_t, or float for the full-precision layers (k_mlp_layers_f32.hip), where every (T) below is no rounding at all
+// half_t, or float for the full-precision layers (k_mlp_layers.hip), where every (T) below is no rounding at all
 template <typename T>
 __device__ inline T activation_fwd(uint32_t act, T pre) {
 	const float x = (float)pre;
@@ -64,9 +69,8 @@ __device__ inline T activation_bwd(uint32_t act, T grad, T fwd) {
 	}
 }
 
-// a'(z) and a''(z) in fp32 (the functions of activation_fwd), for the layer-by-layer kernels of either precision (k_mlp_layers.hip,
-// k_mlp_layers_f32.hip).  x: the stored pre-activation; for ReLU / LeakyReLU the stored output serves as well (same sign), and None
-// takes no argument at all.
+// a'(z) and a''(z) in fp32 (the functions of activation_fwd), for the layer-by-layer kernels of either precision (k_mlp_layers.hip).
+// x: the stored pre-activation; for ReLU / LeakyReLU the stored output serves as well (same sign), and None takes no argument at all.
 __device__ inline float act_d1(const uint32_t act, const float x) {
 	switch (act) {
 		case (uint32_t)Activation::ReLU: return x > 0.0f ? 1.0f : 0.0f;
@@ -109,6 +113,8 @@ template <int ACT> __device__ inline half_t act_bwd_t(uint32_t act, half_t g, ha
 __device__ inline f4 mfma(h8 a, h8 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
 // k = 16: A lane l holds A[row = l & 15][k = 4 (l >> 4) + j], B lane l holds B[k = 4 (l >> 4) + j][col = l & 15], j = 0..3
 __device__ inline f4 mfma16(h4 a, h4 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0); }
+// k = 4 in fp32: lane l holds A[row = l & 15][k = l >> 4] and B[k = l >> 4][col = l & 15]; one fmaf per k, in ascending k
+__device__ inline f4 mfma_f32(const float a, const float b, const f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 // k index of element j of a chained-layer fragment
 __host__ __device__ inline uint32_t k_chain(uint32_t s, uint32_t q, uint32_t j) { return 32 * s + 16 * (j >> 2) + 4 * q + (j & 3); }

@@ -1584,7 +1584,7 @@ public:
 
 	// precision Fp32: the reference's build without TCNN_HALF_PRECISION (common.h:99-123) as a choice per network -- CutlassMLP<float>.
 	// Parameters, activations, gradients and every second-order intermediate are floats, and the network always runs layer by layer
-	// (k_mlp_layers_f32.hip): no fragment images, no fused training plan.
+	// (k_mlp_layers.hip; weight gradients: k_mlp_layers_f32.hip): no fragment images, no fused training plan.
 	explicit Network(const Json& net, Precision precision = Precision::Fp16) : m_fp32{precision == Precision::Fp32} { // network.cu:48-137
 		const std::string otype = net.value("otype", "MLP");
 		m_fully_fused = equals_case_insensitive(otype, "MegakernelMLP") || equals_case_insensitive(otype, "FullyFusedMLP");
@@ -1766,8 +1766,7 @@ public:
 		MlpDesc desc = m_desc;
 		if (m_output_activation != Activation::None) {
 			dY_tmp = ArenaBuf{stream, (size_t)n * m_padded_output_width * element_size()};
-			if (m_fp32) mlp_activation_backward_output_f32(stream, (size_t)n * m_padded_output_width, (uint32_t)m_output_activation, (const float*)dL_doutput, (const float*)output, dY_tmp.as<float>());
-			else mlp_activation_backward_output(stream, n * m_padded_output_width, (uint32_t)m_output_activation, dL_doutput, output, dY_tmp.data());
+			mlp_activation_backward_output(stream, precision(), (size_t)n * m_padded_output_width, (uint32_t)m_output_activation, dL_doutput, output, dY_tmp.data());
 			dY = dY_tmp.data();
 			desc.output_activation = (uint32_t)Activation::None;
 		}
@@ -1784,26 +1783,15 @@ public:
 		const bool accumulate = mode == GradientMode::Accumulate;
 		const size_t hstride = (size_t)n * m_width; // elements per hidden layer
 		std::vector<WgradPanel> panels;
-		for (uint32_t l = 0; l < m_desc.n_layers; ++l) {
+		for (uint32_t l = 0; l < m_desc.n_layers; ++l) { // (the hidden layers' activations and gradients are tiled, k_mlp.hip hidden_tile_off)
 			const MlpLayer& L = m_desc.layers[l];
-			const _Float16* dO = l == m_desc.n_layers - 1 ? (const _Float16*)dY : dhidden.as<_Float16>() + hstride * l;
-			const uint32_t ldo = l == m_desc.n_layers - 1 ? m_padded_output_width : m_width;
-			const _Float16* In = l == 0 ? (const _Float16*)input : ctx.hidden.as<_Float16>() + hstride * (l - 1);
-			const uint32_t ldi = l == 0 ? m_input_width : m_width;
-			_Float16* g = (_Float16*)gradients + L.w_off;
-			for (uint32_t r0 = 0; r0 < L.rows; r0 += 128) {
-				const uint32_t rr = std::min(128u, L.rows - r0);
-				for (uint32_t c0 = 0; c0 < L.cols; c0 += 128) { // column panels of at most 128
-					const uint32_t cc = std::min(128u, L.cols - c0);
-					// (the hidden layers' activations and gradients are tiled, k_mlp.hip hidden_tile_off: a panel's first column is whole tiles in)
-					const bool dO_tiled = l != m_desc.n_layers - 1, In_tiled = l != 0;
-					panels.push_back(WgradPanel{dO_tiled ? dO + (size_t)(r0 / 16) * 256 : dO + r0, ldo, rr, In_tiled ? In + (size_t)(c0 / 16) * 256 : In + c0, ldi, cc,
-					                            g + (size_t)r0 * L.cols + c0, L.cols, dO_tiled, In_tiled});
-				}
-			}
+			const bool dO_tiled = l != m_desc.n_layers - 1, In_tiled = l != 0;
+			const void* dO = dO_tiled ? at((const void*)dhidden.data(), hstride * l) : dY;
+			const void* In = In_tiled ? at((const void*)ctx.hidden.data(), hstride * (l - 1)) : input;
+			add_wgrad_panels(panels, L, dO, layer_ld(l), In, l == 0 ? m_input_width : m_width, at(gradients, L.w_off), dO_tiled, In_tiled);
 		}
-		ArenaBuf ws{stream, wgrad_panels_workspace_floats(panels.data(), (uint32_t)panels.size(), n) * sizeof(float)};
-		mlp_wgrad_panels(stream, n, panels.data(), (uint32_t)panels.size(), accumulate, ws.as<float>()); // (layers of one shape share a launch)
+		ArenaBuf ws{stream, wgrad_panels_workspace_floats(precision(), panels.data(), (uint32_t)panels.size(), n) * sizeof(float)};
+		mlp_wgrad_panels(stream, precision(), n, panels.data(), (uint32_t)panels.size(), accumulate, ws.as<float>()); // (layers of one shape share a launch)
 	}
 
 	// ---- Second-order input gradients of a CutlassMLP: the gradients of S = <v, dL/dinput> for a given v = dL2/d(dL/dinput).
@@ -1846,7 +1834,7 @@ public:
 		for (uint32_t l = 0; l < K; ++l) {
 			const MlpLayer& L = m_desc.layers[l];
 			void* out = at(s.h.data(), s.slot * l);
-			layer_forward(stream, n, in, ldi, at(p, L.w_off), L.rows, L.cols, layer_act(l), out, layer_ld(l), has_curvature(layer_act(l)) ? at(s.z.data(), s.slot * l) : nullptr);
+			mlp_layer_forward(stream, precision(), n, in, ldi, at(p, L.w_off), L.rows, L.cols, layer_act(l), out, layer_ld(l), has_curvature(layer_act(l)) ? at(s.z.data(), s.slot * l) : nullptr);
 			in = out;
 			ldi = m_width;
 		}
@@ -1855,14 +1843,14 @@ public:
 		s.d = ArenaBuf{stream, K * s.slot * element_size()};
 		if (curved) s.g = ArenaBuf{stream, K * s.slot * element_size()};
 		s.wt = ArenaBuf{stream, m_n_params * element_size()};
-		for (uint32_t l = 1; l < K; ++l) layer_transpose(stream, m_desc.layers[l].rows, m_desc.layers[l].cols, at(p, m_desc.layers[l].w_off), at(s.wt.data(), m_desc.layers[l].w_off));
+		for (uint32_t l = 1; l < K; ++l) mlp_layer_transpose(stream, precision(), m_desc.layers[l].rows, m_desc.layers[l].cols, at(p, m_desc.layers[l].w_off), at(s.wt.data(), m_desc.layers[l].w_off));
 		if (layer_act(K - 1) != (uint32_t)Activation::None) { // d_K = a_K'(z_K) g_K
-			layer_delta(stream, (size_t)n * m_padded_output_width, layer_act(K - 1), dL_doutput, aux_of(s, K - 1), at(s.d.data(), s.slot * (K - 1)));
+			mlp_layer_delta(stream, precision(), (size_t)n * m_padded_output_width, layer_act(K - 1), dL_doutput, aux_of(s, K - 1), at(s.d.data(), s.slot * (K - 1)));
 		}
 		for (uint32_t l = K - 1; l > 0; --l) {
 			const MlpLayer& L = m_desc.layers[l];
 			const uint32_t act = layer_act(l - 1);
-			layer_backward_keep(stream, n, d_of(s, l), layer_ld(l), at(s.wt.data(), L.w_off), L.rows, L.cols, act, aux_of(s, l - 1),
+			mlp_layer_backward_keep(stream, precision(), n, d_of(s, l), layer_ld(l), at(s.wt.data(), L.w_off), L.rows, L.cols, act, aux_of(s, l - 1),
 			                    has_curvature(act) ? at(s.g.data(), s.slot * (l - 1)) : nullptr, at(s.d.data(), s.slot * (l - 1)), m_width);
 		}
 		return s;
@@ -1889,7 +1877,7 @@ public:
 			const MlpLayer& L = m_desc.layers[l];
 			const bool curv = want_p && has_curvature(layer_act(l));
 			const void* g = l == K - 1 ? s.dL_doutput : at((const void*)s.g.data(), s.slot * l);
-			layer_tangent(stream, n, in, ldi, at(p, L.w_off), L.rows, L.cols, layer_act(l), aux_of(s, l), curv ? g : nullptr, u_of(l), curv ? at(r.data(), s.slot * l) : nullptr, layer_ld(l));
+			mlp_layer_tangent(stream, precision(), n, in, ldi, at(p, L.w_off), L.rows, L.cols, layer_act(l), aux_of(s, l), curv ? g : nullptr, u_of(l), curv ? at(r.data(), s.slot * l) : nullptr, layer_ld(l));
 			in = u_of(l);
 			ldi = m_width;
 		}
@@ -1897,18 +1885,18 @@ public:
 		for (uint32_t l = 0; l < K; ++l) if (has_curvature(layer_act(l))) top = l;
 		if (want_p) {
 			if (dS_dinput && !s.have_wt0) {
-				layer_transpose(stream, m_desc.layers[0].rows, m_desc.layers[0].cols, p, s.wt.data());
+				mlp_layer_transpose(stream, precision(), m_desc.layers[0].rows, m_desc.layers[0].cols, p, s.wt.data());
 				s.have_wt0 = true;
 			}
 			for (uint32_t l = top; l > 0; --l) {
 				const MlpLayer& L = m_desc.layers[l];
 				void* below = at(r.data(), s.slot * (l - 1));
-				layer_curvature_backward(stream, n, at(r.data(), s.slot * l), layer_ld(l), at(s.wt.data(), L.w_off), L.rows, L.cols, layer_act(l - 1), aux_of(s, l - 1),
+				mlp_layer_curvature_backward(stream, precision(), n, at(r.data(), s.slot * l), layer_ld(l), at(s.wt.data(), L.w_off), L.rows, L.cols, layer_act(l - 1), aux_of(s, l - 1),
 				                         has_curvature(layer_act(l - 1)) ? below : nullptr, below, m_width);
 			}
 			if (dS_dinput) {
 				const MlpLayer& L = m_desc.layers[0];
-				layer_backward(stream, n, r.data(), layer_ld(0), s.wt.data(), L.rows, L.cols, (uint32_t)Activation::None, nullptr, dS_dinput, m_input_width);
+				mlp_layer_backward(stream, precision(), n, r.data(), layer_ld(0), s.wt.data(), L.rows, L.cols, (uint32_t)Activation::None, nullptr, dS_dinput, m_input_width);
 			}
 		}
 		if (!want_grads) return;
@@ -1941,38 +1929,6 @@ private:
 	// `elems` elements of the network's precision behind base (null stays null)
 	const void* at(const void* base, size_t elems) const { return base ? (const char*)base + elems * element_size() : nullptr; }
 	void* at(void* base, size_t elems) const { return base ? (char*)base + elems * element_size() : nullptr; }
-	// the layer kernels of the network's precision (k_mlp_layers.hip / k_mlp_layers_f32.hip)
-	void layer_forward(hipStream_t stream, uint32_t n, const void* x, uint32_t ldx, const void* w, uint32_t rows, uint32_t cols, uint32_t act, void* y, uint32_t ldy, void* pre) const {
-		if (m_fp32) mlp_layer_forward_f32(stream, n, (const float*)x, ldx, (const float*)w, rows, cols, act, (float*)y, ldy, (float*)pre);
-		else mlp_layer_forward(stream, n, x, ldx, w, rows, cols, act, y, ldy, pre);
-	}
-	void layer_backward(hipStream_t stream, uint32_t n, const void* dL_dout, uint32_t ldo, const void* wt, uint32_t rows, uint32_t cols, uint32_t act, const void* aux, void* dL_din, uint32_t ldi) const {
-		if (m_fp32) mlp_layer_backward_f32(stream, n, (const float*)dL_dout, ldo, (const float*)wt, rows, cols, act, (const float*)aux, (float*)dL_din, ldi);
-		else mlp_layer_backward(stream, n, dL_dout, ldo, wt, rows, cols, act, aux, dL_din, ldi);
-	}
-	void layer_transpose(hipStream_t stream, uint32_t rows, uint32_t cols, const void* w, void* wt) const {
-		if (m_fp32) mlp_layer_transpose_f32(stream, rows, cols, (const float*)w, (float*)wt);
-		else mlp_layer_transpose(stream, rows, cols, w, wt);
-	}
-	void layer_tangent(hipStream_t stream, uint32_t n, const void* u_in, uint32_t ldu, const void* w, uint32_t rows, uint32_t cols, uint32_t act, const void* aux, const void* g, void* u_out,
-	                   void* r_out, uint32_t ldy) const {
-		if (m_fp32) mlp_layer_tangent_f32(stream, n, (const float*)u_in, ldu, (const float*)w, rows, cols, act, (const float*)aux, (const float*)g, (float*)u_out, (float*)r_out, ldy);
-		else mlp_layer_tangent(stream, n, u_in, ldu, w, rows, cols, act, aux, g, u_out, r_out, ldy);
-	}
-	void layer_backward_keep(hipStream_t stream, uint32_t n, const void* d_out, uint32_t ldo, const void* wt, uint32_t rows, uint32_t cols, uint32_t act, const void* aux, void* g_in, void* d_in,
-	                         uint32_t ldi) const {
-		if (m_fp32) mlp_layer_backward_keep_f32(stream, n, (const float*)d_out, ldo, (const float*)wt, rows, cols, act, (const float*)aux, (float*)g_in, (float*)d_in, ldi);
-		else mlp_layer_backward_keep(stream, n, d_out, ldo, wt, rows, cols, act, aux, g_in, d_in, ldi);
-	}
-	void layer_curvature_backward(hipStream_t stream, uint32_t n, const void* p_out, uint32_t ldo, const void* wt, uint32_t rows, uint32_t cols, uint32_t act, const void* aux, const void* r_in,
-	                              void* p_in, uint32_t ldi) const {
-		if (m_fp32) mlp_layer_curvature_backward_f32(stream, n, (const float*)p_out, ldo, (const float*)wt, rows, cols, act, (const float*)aux, (const float*)r_in, (float*)p_in, ldi);
-		else mlp_layer_curvature_backward(stream, n, p_out, ldo, wt, rows, cols, act, aux, r_in, p_in, ldi);
-	}
-	void layer_delta(hipStream_t stream, size_t n_elems, uint32_t act, const void* g, const void* aux, void* delta) const {
-		if (m_fp32) mlp_layer_delta_f32(stream, n_elems, act, (const float*)g, (const float*)aux, (float*)delta);
-		else mlp_layer_delta(stream, n_elems, act, g, aux, delta);
-	}
 	uint32_t layer_act(uint32_t l) const { return (uint32_t)(l == m_desc.n_layers - 1 ? m_output_activation : m_activation); }
 	uint32_t layer_ld(uint32_t l) const { return l == m_desc.n_layers - 1 ? m_padded_output_width : m_width; } // of the layer's output
 
@@ -1988,7 +1944,7 @@ private:
 			const bool last = l == m_desc.n_layers - 1;
 			void* out = last ? output : hidden ? at(hidden, hstride * l) : at(rotate.data(), hstride * (l & 1));
 			void* p = !last && pre ? at(pre, hstride * l) : nullptr;
-			layer_forward(stream, n, in, ldi, at(params, L.w_off), L.rows, L.cols, layer_act(l), out, layer_ld(l), p);
+			mlp_layer_forward(stream, precision(), n, in, ldi, at(params, L.w_off), L.rows, L.cols, layer_act(l), out, layer_ld(l), p);
 			in = out;
 			ldi = m_width;
 		}
@@ -2006,21 +1962,21 @@ private:
 		const void* p = params;
 		for (uint32_t l = dL_dinput ? 0 : 1; l < m_desc.n_layers; ++l) {
 			const MlpLayer& L = m_desc.layers[l];
-			layer_transpose(stream, L.rows, L.cols, at(p, L.w_off), at(wt.data(), L.w_off));
+			mlp_layer_transpose(stream, precision(), L.rows, L.cols, at(p, L.w_off), at(wt.data(), L.w_off));
 		}
 		for (uint32_t l = m_desc.n_layers; l-- > 0;) {
 			const MlpLayer& L = m_desc.layers[l];
 			const void* dO = l == m_desc.n_layers - 1 ? dY : at((const void*)dhidden.data(), hstride * l);
 			const uint32_t ldo = layer_ld(l);
 			if (l > 0) { // dL/d(hidden l - 1), through the derivative of its activation
-				layer_backward(stream, n, dO, ldo, at(wt.data(), L.w_off), L.rows, L.cols, (uint32_t)m_activation, at(aux, hstride * (l - 1)), at(dhidden.data(), hstride * (l - 1)), m_width);
+				mlp_layer_backward(stream, precision(), n, dO, ldo, at(wt.data(), L.w_off), L.rows, L.cols, (uint32_t)m_activation, at(aux, hstride * (l - 1)), at(dhidden.data(), hstride * (l - 1)), m_width);
 			} else if (dL_dinput) {
-				layer_backward(stream, n, dO, ldo, at(wt.data(), L.w_off), L.rows, L.cols, (uint32_t)Activation::None, nullptr, dL_dinput, m_input_width);
+				mlp_layer_backward(stream, precision(), n, dO, ldo, at(wt.data(), L.w_off), L.rows, L.cols, (uint32_t)Activation::None, nullptr, dL_dinput, m_input_width);
 			}
 		}
 		if (mode == GradientMode::Ignore) return;
 		CHECK_THROW(gradients != nullptr);
-		// weight gradients: mlp_wgrad_panels (fp32: mlp_wgrad_panels_f32) on the row-major buffers, panels of at most 128 x 128, launched in groups whose fp32 slabs
+		// weight gradients: mlp_wgrad_panels on the row-major buffers, panels of at most 128 x 128, launched in groups whose fp32 slabs
 		// fit a bounded workspace (a 1024-wide layer is 64 panels of up to 256 slabs each; the groups run in stream order and share it)
 		std::vector<WgradPanel> panels;
 		for (uint32_t l = 0; l < m_desc.n_layers; ++l) {
@@ -2041,24 +1997,27 @@ private:
 		return l == m_desc.n_layers - 1 && layer_act(l) == (uint32_t)Activation::None ? s.dL_doutput : at((const void*)s.d.data(), s.slot * l);
 	}
 
-	// row-major operands: panels of at most 128 x 128 of one layer's weight gradient
-	void add_wgrad_panels(std::vector<WgradPanel>& panels, const MlpLayer& L, const void* dO, uint32_t ldo, const void* In, uint32_t ldi, void* g) const {
+	// panels of at most 128 x 128 of one layer's weight gradient.  Row-major operands: a panel's first column is that many elements in; tiled
+	// ones (the fused kernels' hidden matrices, k_mlp.hip hidden_tile_off): whole tiles of 16 columns x 16 samples = 256 elements in
+	void add_wgrad_panels(std::vector<WgradPanel>& panels, const MlpLayer& L, const void* dO, uint32_t ldo, const void* In, uint32_t ldi, void* g, bool dO_tiled = false,
+	                      bool In_tiled = false) const {
 		for (uint32_t r0 = 0; r0 < L.rows; r0 += 128)
 			for (uint32_t c0 = 0; c0 < L.cols; c0 += 128)
-				panels.push_back(WgradPanel{at(dO, r0), ldo, std::min(128u, L.rows - r0), at(In, c0), ldi, std::min(128u, L.cols - c0), at(g, (size_t)r0 * L.cols + c0), L.cols, false, false});
+				panels.push_back(WgradPanel{at(dO, dO_tiled ? (size_t)(r0 / 16) * 256 : r0), ldo, std::min(128u, L.rows - r0), at(In, In_tiled ? (size_t)(c0 / 16) * 256 : c0), ldi,
+				                            std::min(128u, L.cols - c0), at(g, (size_t)r0 * L.cols + c0), L.cols, dO_tiled, In_tiled});
 	}
 
 	void launch_wgrad_panels(hipStream_t stream, uint32_t n, const std::vector<WgradPanel>& panels, bool accumulate) const {
 		constexpr size_t WORKSPACE_FLOATS = (size_t)64 << 20; // 256 MB
-		const auto workspace_floats = m_fp32 ? wgrad_panels_workspace_floats_f32 : wgrad_panels_workspace_floats;
+		auto workspace_floats = [&](const WgradPanel* p, size_t count) { return wgrad_panels_workspace_floats(precision(), p, (uint32_t)count, n); };
 		size_t max_floats = 0;
-		for (const WgradPanel& q : panels) max_floats = std::max(max_floats, workspace_floats(&q, 1, n));
-		ArenaBuf ws{stream, std::max(max_floats, std::min(WORKSPACE_FLOATS, workspace_floats(panels.data(), (uint32_t)panels.size(), n))) * sizeof(float)};
+		for (const WgradPanel& q : panels) max_floats = std::max(max_floats, workspace_floats(&q, 1));
+		ArenaBuf ws{stream, std::max(max_floats, std::min(WORKSPACE_FLOATS, workspace_floats(panels.data(), panels.size()))) * sizeof(float)};
 		const size_t ws_floats = ws.bytes() / sizeof(float);
 		for (size_t i = 0; i < panels.size();) {
 			size_t j = i, floats = 0;
-			while (j < panels.size() && floats + workspace_floats(&panels[j], 1, n) <= ws_floats) floats += workspace_floats(&panels[j++], 1, n);
-			(m_fp32 ? mlp_wgrad_panels_f32 : mlp_wgrad_panels)(stream, n, panels.data() + i, (uint32_t)(j - i), accumulate, ws.as<float>());
+			while (j < panels.size() && floats + workspace_floats(&panels[j], 1) <= ws_floats) floats += workspace_floats(&panels[j++], 1);
+			mlp_wgrad_panels(stream, precision(), n, panels.data() + i, (uint32_t)(j - i), accumulate, ws.as<float>());
 			i = j;
 		}
 	}

@@ -539,60 +539,46 @@ void mlp_expand_context(hipStream_t stream, uint32_t n, uint32_t dims, const voi
 // adam (optional, not with accumulate): the optimizer's update of these (matrix) weights is applied behind the reduction, bit-identical to adam_step run afterwards
 struct AdamInReduce;
 void mlp_reduce_slabs(hipStream_t stream, uint32_t n_params, uint32_t n_slabs, const float* slabs, void* grad_half, bool accumulate, const AdamInReduce* adam = nullptr);
-// fully_fused_mlp.cu:757-762: result = dL_dout * act'(out), elementwise over n_elems halfs
-void mlp_activation_backward_output(hipStream_t stream, uint32_t n_elems, uint32_t activation, const void* dL_dout, const void* out, void* result);
 // dW[rows x cols] = sum_i dO[i][rows]^T In[i][cols]; result written as half into grad (overwrite or accumulate). workspace: float[wgrad_workspace_floats()]
 size_t wgrad_workspace_floats(uint32_t rows, uint32_t cols, uint32_t n);
 // several such products over the same n samples (a network's layers): same results as one mlp_wgrad() each, fewer launches
 // (dO_tiled / In_tiled: the operand is a hidden layer's stored activations or gradients in k_mlp_fwd / k_mlp_bwd's tiled form, ld = the full
 // width of that matrix and a panel's first column c0 absorbed by the pointer as + (c0 / 16) * 256 halves; k_mlp.hip hidden_tile_off)
+// Fp32 (k_mlp_layers_f32.hip): row-major float operands into float grad, panels of at most 128 x 128, never tiled: fp32 slabs summed in a fixed order
 struct WgradPanel { const void* dO; uint32_t ldo, rows; const void* In; uint32_t ldi, cols; void* grad; uint32_t ldg; bool dO_tiled, In_tiled; };
-size_t wgrad_panels_workspace_floats(const WgradPanel* panels, uint32_t count, uint32_t n);
-void mlp_wgrad_panels(hipStream_t stream, uint32_t n, const WgradPanel* panels, uint32_t count, bool accumulate, float* workspace);
+size_t wgrad_panels_workspace_floats(Precision precision, const WgradPanel* panels, uint32_t count, uint32_t n);
+void mlp_wgrad_panels(hipStream_t stream, Precision precision, uint32_t n, const WgradPanel* panels, uint32_t count, bool accumulate, float* workspace);
 void mlp_wgrad(hipStream_t stream, uint32_t n, const void* dO, uint32_t ldo, uint32_t rows, const void* In, uint32_t ldi, uint32_t cols,
                void* grad_half, uint32_t ldg, bool accumulate, float* workspace);
-// ---- the layer-by-layer path (k_mlp_layers.hip; Network::layerwise): one GEMM per layer on row-major half matrices, n % 256 == 0,
-// rows / cols multiples of 16, leading dimensions multiples of 8 (x) and 4 (y).
-// forward: y[s][r] = act((half) sum_c x[s][c] w[r][c]) for r < rows; w [rows][cols]; pre (optional): the half pre-activation, laid out as y
-void mlp_layer_forward(hipStream_t stream, uint32_t n, const void* x, uint32_t ldx, const void* w, uint32_t rows, uint32_t cols, uint32_t activation, void* y, uint32_t ldy,
-                       void* pre);
-// backward data: dL_din[s][c] = act'((half) sum_r dL_dout[s][r] w[r][c]) for c < cols, from wt = w^T [cols][rows] (mlp_layer_transpose);
+// ---- the layer-by-layer path (k_mlp_layers.hip; Network::layerwise): one GEMM per layer on row-major matrices of `precision` (T below:
+// half, or float with the weights read from the fp32 parameter vector as they are), n % 256 == 0, rows / cols multiples of 16, the leading
+// dimension of x a whole 16-byte piece (8 halfs, 4 floats), that of y a multiple of 4.  Fp16: the fp32 accumulator is rounded to half, then
+// the activation is applied.  Fp32: every product is one ascending-k fmaf chain per element from +0 (the contract at LayerElem<float> in
+// that file) and (T) is no rounding at all.
+// forward: y[s][r] = act((T) sum_c x[s][c] w[r][c]) for r < rows; w [rows][cols]; pre (optional): the pre-activation, laid out as y
+void mlp_layer_forward(hipStream_t stream, Precision precision, uint32_t n, const void* x, uint32_t ldx, const void* w, uint32_t rows, uint32_t cols, uint32_t activation, void* y,
+                       uint32_t ldy, void* pre);
+// backward data: dL_din[s][c] = act'((T) sum_r dL_dout[s][r] w[r][c]) for c < cols, from wt = w^T [cols][rows] (mlp_layer_transpose);
 // aux (laid out as dL_din): the forward output of the layer that produced the input -- its pre-activation for Sine; activation None: unused
-void mlp_layer_backward(hipStream_t stream, uint32_t n, const void* dL_dout, uint32_t ldo, const void* wt, uint32_t rows, uint32_t cols, uint32_t activation, const void* aux,
-                        void* dL_din, uint32_t ldi);
-void mlp_layer_transpose(hipStream_t stream, uint32_t rows, uint32_t cols, const void* w, void* wt); // wt [cols][rows] = w [rows][cols]^T
+void mlp_layer_backward(hipStream_t stream, Precision precision, uint32_t n, const void* dL_dout, uint32_t ldo, const void* wt, uint32_t rows, uint32_t cols, uint32_t activation,
+                        const void* aux, void* dL_din, uint32_t ldi);
+void mlp_layer_transpose(hipStream_t stream, Precision precision, uint32_t rows, uint32_t cols, const void* w, void* wt); // wt [cols][rows] = w [rows][cols]^T
 // ---- the three products of the second-order pass (Network::second_order_begin / _finish).  a', a'' are evaluated in fp32 from aux: the
-// layer's half pre-activation, or its output for ReLU / LeakyReLU; unused for None.  One rounding to half per stored matrix.
+// layer's pre-activation, or its output for ReLU / LeakyReLU; unused for None.  One rounding to T per stored matrix.
 // tangent: acc = sum_c u_in[s][c] w[r][c];  u_out = a'(aux) acc;  r_out (optional, needs g) = a''(aux) g acc.  aux, g, u_out, r_out: [n][ldy]
-void mlp_layer_tangent(hipStream_t stream, uint32_t n, const void* u_in, uint32_t ldu, const void* w, uint32_t rows, uint32_t cols, uint32_t activation, const void* aux, const void* g,
-                       void* u_out, void* r_out, uint32_t ldy);
-// backward data, keeping the gradient from before the derivative: acc = sum_r d_out[s][r] w[r][c] (from wt);  g_in (optional) = (half) acc;
+void mlp_layer_tangent(hipStream_t stream, Precision precision, uint32_t n, const void* u_in, uint32_t ldu, const void* w, uint32_t rows, uint32_t cols, uint32_t activation,
+                       const void* aux, const void* g, void* u_out, void* r_out, uint32_t ldy);
+// backward data, keeping the gradient from before the derivative: acc = sum_r d_out[s][r] w[r][c] (from wt);  g_in (optional) = (T) acc;
 // d_in = a'(aux) g_in.  aux, g_in, d_in: [n][ldi]
-void mlp_layer_backward_keep(hipStream_t stream, uint32_t n, const void* d_out, uint32_t ldo, const void* wt, uint32_t rows, uint32_t cols, uint32_t activation, const void* aux,
-                             void* g_in, void* d_in, uint32_t ldi);
+void mlp_layer_backward_keep(hipStream_t stream, Precision precision, uint32_t n, const void* d_out, uint32_t ldo, const void* wt, uint32_t rows, uint32_t cols, uint32_t activation,
+                             const void* aux, void* g_in, void* d_in, uint32_t ldi);
 // curvature: acc = sum_r p_out[s][r] w[r][c] (from wt);  p_in = r_in + a'(aux) acc (r_in optional: zero; p_in may be r_in).  [n][ldi]
-void mlp_layer_curvature_backward(hipStream_t stream, uint32_t n, const void* p_out, uint32_t ldo, const void* wt, uint32_t rows, uint32_t cols, uint32_t activation, const void* aux,
-                                  const void* r_in, void* p_in, uint32_t ldi);
-void mlp_layer_delta(hipStream_t stream, size_t n_elems, uint32_t activation, const void* g, const void* aux, void* delta); // delta = a'(aux) g, element by element
-void add_input_gradient(hipStream_t stream, uint32_t n, uint32_t dims, MatView src, MatViewMut dst);                          // dst += src, [n][dims] floats
-// ---- the same path in full precision (k_mlp_layers_f32.hip; Network{json, Precision::Fp32}): row-major float matrices, the weights read
-// from the fp32 parameter vector as they are, leading dimensions multiples of 4.  Every product is one ascending-k fmaf chain per
-// element from +0 (the contract at the top of that file); the epilogues are those above with float in place of half.
-void mlp_layer_forward_f32(hipStream_t stream, uint32_t n, const float* x, uint32_t ldx, const float* w, uint32_t rows, uint32_t cols, uint32_t activation, float* y, uint32_t ldy, float* pre);
-void mlp_layer_backward_f32(hipStream_t stream, uint32_t n, const float* dL_dout, uint32_t ldo, const float* wt, uint32_t rows, uint32_t cols, uint32_t activation, const float* aux,
-                            float* dL_din, uint32_t ldi);
-void mlp_layer_transpose_f32(hipStream_t stream, uint32_t rows, uint32_t cols, const float* w, float* wt);
-void mlp_layer_tangent_f32(hipStream_t stream, uint32_t n, const float* u_in, uint32_t ldu, const float* w, uint32_t rows, uint32_t cols, uint32_t activation, const float* aux,
-                           const float* g, float* u_out, float* r_out, uint32_t ldy);
-void mlp_layer_backward_keep_f32(hipStream_t stream, uint32_t n, const float* d_out, uint32_t ldo, const float* wt, uint32_t rows, uint32_t cols, uint32_t activation, const float* aux,
-                                 float* g_in, float* d_in, uint32_t ldi);
-void mlp_layer_curvature_backward_f32(hipStream_t stream, uint32_t n, const float* p_out, uint32_t ldo, const float* wt, uint32_t rows, uint32_t cols, uint32_t activation,
-                                      const float* aux, const float* r_in, float* p_in, uint32_t ldi);
-void mlp_layer_delta_f32(hipStream_t stream, size_t n_elems, uint32_t activation, const float* g, const float* aux, float* delta);
-void mlp_activation_backward_output_f32(hipStream_t stream, size_t n_elems, uint32_t activation, const float* dL_dout, const float* out, float* result);
-// weight gradients of row-major float operands into float grad (panels of at most 128 x 128, never tiled): fp32 slabs summed in a fixed order
-size_t wgrad_panels_workspace_floats_f32(const WgradPanel* panels, uint32_t count, uint32_t n);
-void mlp_wgrad_panels_f32(hipStream_t stream, uint32_t n, const WgradPanel* panels, uint32_t count, bool accumulate, float* workspace);
+void mlp_layer_curvature_backward(hipStream_t stream, Precision precision, uint32_t n, const void* p_out, uint32_t ldo, const void* wt, uint32_t rows, uint32_t cols,
+                                  uint32_t activation, const void* aux, const void* r_in, void* p_in, uint32_t ldi);
+void mlp_layer_delta(hipStream_t stream, Precision precision, size_t n_elems, uint32_t activation, const void* g, const void* aux, void* delta); // delta = a'(aux) g, element by element
+// fully_fused_mlp.cu:757-762: result = dL_dout * act'(out), element by element, from the forward OUTPUT values (fused networks too)
+void mlp_activation_backward_output(hipStream_t stream, Precision precision, size_t n_elems, uint32_t activation, const void* dL_dout, const void* out, void* result);
+void add_input_gradient(hipStream_t stream, uint32_t n, uint32_t dims, MatView src, MatViewMut dst);                                           // dst += src, [n][dims] floats
 
 // ------------------------------------------------------------------------------------------------------------------
 // loss / reduction / optimizer / init plumbing

@@ -1,4 +1,4 @@
-"""Full-precision networks (k_mlp_layers_f32.hip): forward + backward time of tcnn.Network(dtype=torch.float32) at 2^18 rows beside what a
+"""Full-precision networks (k_mlp_layers.hip; weight gradients: k_mlp_layers_f32.hip): forward + backward time of tcnn.Network(dtype=torch.float32) at 2^18 rows beside what a
 user had before it existed -- a torch.nn.Sequential of bias-free Linear layers in fp32 -- and beside the half tcnn.Network, for scale.
 
     python tools/bench_fp32_network.py [--reps 7] [--steps 20] [--txt out.txt] [--json out.json] [--only-tcnn-fp32]
