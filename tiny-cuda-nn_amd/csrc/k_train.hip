@@ -838,20 +838,11 @@ void mlp_train_launch(hipStream_t stream, const MlpDesc& d, const MlpTrainPlan& 
 		a.ob_dims = r.oneblob_dims;
 		while ((1u << a.ob_log2) < r.oneblob_bins) ++a.ob_log2;
 	}
-#ifdef TCNN_AMD_DEV // laboratory build (build.py --dev): in-kernel clocks of the 5th launch
-	static const bool timing = getenv("TCNN_AMD_MLP_TIMING") != nullptr;
-	static int timing_left = 5;
-	if (timing && timing_left > 0) HIP_CHECK_THROW(hipMalloc(&a.dbg, 64));
-#else
-	int timing_left = 0; (void)timing_left;
-#endif
+	static DevClocks clocks; // (laboratory build)
+	a.dbg = clocks.alloc(64);
 	dispatch_train(true, stream, d, a, cfg, r.oneblob_bins != 0, p.grid);
-	if (a.dbg) {
-		unsigned long long h[8];
-		HIP_CHECK_THROW(hipMemcpy(h, a.dbg, 64, hipMemcpyDeviceToHost));
-		if (--timing_left == 0) fprintf(stderr, "k_mlp_train wave 0 clocks over its trips: fwd %llu loss %llu bwd %llu dX+stores %llu barrier1 %llu wgrad %llu barrier2 %llu\n", h[0], h[1], h[2], h[3], h[4], h[5], h[6]);
-		(void)hipFree(a.dbg);
-	}
+	unsigned long long h[8];
+	if (clocks.fetch(a.dbg, h, 8)) fprintf(stderr, "k_mlp_train wave 0 clocks over its trips: fwd %llu loss %llu bwd %llu dX+stores %llu barrier1 %llu wgrad %llu barrier2 %llu\n", h[0], h[1], h[2], h[3], h[4], h[5], h[6]);
 }
 
 } // namespace tcnn_amd

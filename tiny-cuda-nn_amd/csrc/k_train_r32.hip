@@ -34,21 +34,11 @@ namespace {
 
 
 constexpr int R32_NW = 8;                 // waves per workgroup
-constexpr int R32_NF = 30;                // weight fragments (R32Frags of 32 -> 64 -> 64 -> 16)
+constexpr int R32_NF = R32Slots<32, 64>::N; // 30 weight fragments (32 -> 64 -> 64 -> 16)
 constexpr int R32_WAVE0 = R32_NF * 1024;
 constexpr int R32_WAVE_BYTES = 15 * 1024; // X 2 K | H0 4 K | H1 4 K | dH 4 K | dY 1 K
 constexpr int IMG_X = 0, IMG_H0 = 2048, IMG_H1 = 6144, IMG_DH = 10240, IMG_DY = 14336;
 constexpr int R32_LDS_BYTES = R32_WAVE0 + R32_NW * R32_WAVE_BYTES; // 153 600
-
-template <typename V> __device__ inline V ld32(const void* base, const uint32_t byte_off) { return *(const V*)((const char*)base + byte_off); }
-template <typename V> __device__ inline void st32(void* base, const uint32_t byte_off, const V v) { *(V*)((char*)base + byte_off) = v; }
-template <typename V> __device__ inline void st32_stream(void* base, const uint32_t byte_off, const V v) {
-	typedef uint32_t nt4 __attribute__((ext_vector_type(4)));
-	char* p = (char*)base + byte_off;
-	if constexpr (sizeof(V) == 16) __builtin_nontemporal_store(__builtin_bit_cast(nt4, v), (nt4*)p);
-	else if constexpr (sizeof(V) == 4) __builtin_nontemporal_store(__builtin_bit_cast(uint32_t, v), (uint32_t*)p);
-	else __builtin_nontemporal_store(__builtin_bit_cast(uint16_t, v), (uint16_t*)p);
-}
 
 // LOSS 1: L2, 2: RelativeL2
 // DIAG (timing-only builds, TCNN_AMD_MLP_DIAG; results are wrong; bit 5: no weight-gradient products): bit 0: weight fragments are not read from LDS, bit 1: the transposing
@@ -60,11 +50,8 @@ template <typename V> __device__ inline void st32_stream(void* base, const uint3
 // previous instructions finished) and the LDS reads of the operands of the region after, so that in program order vector
 // instructions sit between matrix instructions (a wave issues in order: behind two back-to-back matrix instructions nothing of it
 // issues until the second one has the pipe) and every LDS operand is requested one region (64 .. 256 clocks) before its use.
-#define R32_SB() __builtin_amdgcn_sched_barrier(0)
 #define R32_STAMP(i) do { if constexpr ((DIAG & 64) != 0) { const unsigned long long now_ = __builtin_readcyclecounter(); ph[i] += now_ - ph_prev; ph_prev = now_; } } while (0)
 constexpr int R32_REGIONS = 15;
-// within a region: one matrix instruction, then V vector and D LDS instructions (sched_group_barrier masks: 0x8 MFMA, 0x2 VALU, 0x80 DS)
-#define R32_MVD(V, D) do { __builtin_amdgcn_sched_group_barrier(0x8, 1, 0); __builtin_amdgcn_sched_group_barrier(0x2, V, 0); __builtin_amdgcn_sched_group_barrier(0x80, D, 0); } while (0)
 // REC: dL/d(encoded input) leaves as 16-byte scatter records {x, y, gradients of a level pair} (the bit-plane scatter, k_grid_scatter.hip);
 // else as plain level planes half2 [16][n] -- half the bytes -- for the list-fed scatter, whose elements know entries and weights (k_grid_scatter_lists.hip)
 template <int LOSS, bool REC, int DIAG = 0>
@@ -85,59 +72,22 @@ __global__ void __launch_bounds__(R32_NW * 64, 2) k_mlp_train_r32(const R32Args 
 	const LossScales lsc = loss_scales(n_total, a.loss_scale);
 	const uint32_t n4 = a.n * 4;
 
-	// ---- global addressing: raw buffer accesses -- descriptor (scalar, per matrix) + a lane offset that never changes + a scalar offset of the
-	// trip's 32-sample block: the trip loop spends one scalar addition per stream on addresses and no vector instruction (as plain
-	// pointers the compiler carried 64-bit vector addresses: ~40 vector and ~50 scalar instructions per trip).  Offsets are 32-bit
-	// (r32_plan caps n); an access beyond a matrix would be dropped by the range check instead of faulting.
-	// STORES of 16 bytes take the block's offset in the vector offset (one addition) and no scalar offset: with a scalar-register
-	// offset the compiler assumes the hardware needs no wait state between such a store and a vector instruction that overwrites
-	// its data registers (GCNHazardRecognizer: "only if the instruction is not using a register in the soffset field"); on gfx950 it
-	// does -- measured: the third dword of two of a trip's four records came out as whatever the next conversion wrote there.
-	const auto rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, (int)(a.n * 64), 0x00020000);
-	const auto rs_t = __builtin_amdgcn_make_buffer_rsrc((void*)a.target, 0, (int)(a.n * a.dims * 4), 0x00020000);
-	const auto rs_xs = __builtin_amdgcn_make_buffer_rsrc((void*)a.rec_x, 0, (int)(a.n * 8), 0x00020000);
-	const auto rs_out = __builtin_amdgcn_make_buffer_rsrc((void*)a.out, 0, (int)(a.n * 32), 0x00020000);
-	const auto rs_g = __builtin_amdgcn_make_buffer_rsrc((void*)a.dL_dout, 0, (int)(a.n * a.dims * 2), 0x00020000);
-	const auto rs_l = __builtin_amdgcn_make_buffer_rsrc((void*)a.L, 0, (int)(a.n * a.dims * 4), 0x00020000);
-	const auto rs_rec = __builtin_amdgcn_make_buffer_rsrc((void*)a.rec, 0, (int)(a.n * (REC ? 128 : 64)), 0x00020000);
-	const uint32_t x_off = (4 * h * a.n + c) * 4; // levels 8 s + 4 h + i at + (8 s + i) n 4
-	struct In { h8 x[2]; float t[2]; float2 xs; };
-	uint32_t t_off[2];
-#pragma unroll
-	for (int r = 0; r < 2; ++r) t_off[r] = (c * a.dims + min(2 * r + h, a.dims - 1)) * 4; // outputs >= dims re-read the last one (masked where used)
-	auto load_in = [&](const uint32_t blk_) -> In {
-		// scalar for the compiler too: it is the scalar offset of every access below (left to the compiler the trip's block number lived in a
-		// vector register and every one of these loads and stores sat in a waterfall loop of its own -- v_readfirstlane, compare, branch: 22 per trip)
-		const uint32_t blk = __builtin_amdgcn_readfirstlane(blk_);
-		In r;
-#pragma unroll
-		for (int s = 0; s < 2; ++s) {
-			u32x4 v;
-#pragma unroll
-			for (int i = 0; i < 4; ++i) v[i] = __builtin_amdgcn_raw_buffer_load_b32(rs_x, x_off, blk * 128 + n4 * (8 * s + i), 0); // features 16 s + 8 h + 2 i, + 1
-			r.x[s] = __builtin_bit_cast(h8, v);
-		}
-		const uint32_t tb = blk * (128 * a.dims);
-		r.t[0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_t, t_off[0], tb, 0));
-		r.t[1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_t, t_off[1], tb, 0));
-		if constexpr (REC) r.xs = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rs_xs, c * 8, blk * 256, 0));
-		else r.xs = float2{0, 0};
-		return r;
-	};
-	In pre{};
+	// ---- global addressing: raw buffer accesses (r32_device.h: r32_buffer; the 16-byte stores' offsets: r32_store_dx_records)
+	const auto rs_x = r32_buffer(a.x, a.n * 64);
+	const auto rs_t = r32_buffer(a.target, a.n * a.dims * 4);
+	const auto rs_xs = r32_buffer(a.rec_x, a.n * 8);
+	const auto rs_out = r32_buffer(a.out, a.n * 32);
+	const auto rs_g = r32_buffer(a.dL_dout, a.n * a.dims * 2);
+	const auto rs_l = r32_buffer(a.L, a.n * a.dims * 4);
+	const auto rs_rec = r32_buffer(a.rec, a.n * (REC ? 128 : 64));
+	R32_DEFINE_LOAD_IN(REC); // x_off, t_off, load_in(block) -> R32In
+	R32In pre{};
 	if (first < n_blocks) pre = load_in(first);
 
 	// ---- weight fragments into LDS
 	{
-		constexpr uint32_t N16 = R32_NF * 64;
-		constexpr int FILL = (N16 + R32_NW * 64 - 1) / (R32_NW * 64);
-		h8 tmp[FILL];
-#pragma unroll
-		for (int k = 0; k < FILL; ++k) tmp[k] = a.image[min(tid + k * R32_NW * 64, N16 - 1)];
-#pragma unroll
-		for (int k = 0; k < FILL; ++k) {
-			if (tid + k * R32_NW * 64 < N16) ((h8*)smem)[tid + k * R32_NW * 64] = tmp[k];
-		}
+		R32_STAGE_LOAD(tmp, R32_NF, R32_NW);
+		R32_STAGE_STORE(tmp, R32_NF, R32_NW);
 	}
 	__syncthreads();
 	if (a.dbg && tid == 0) a.dbg[blockIdx.x * 4 + 1] = __builtin_readcyclecounter();
@@ -150,48 +100,20 @@ __global__ void __launch_bounds__(R32_NW * 64, 2) k_mlp_train_r32(const R32Args 
 		if constexpr (DIAG & 1) { asm volatile("" : "+v"(fake)); return fake; }
 		return *(const h8*)(smem + lane16 + f * 1024);
 	};
-	// Images, per wave and 32-feature tile (2 KiB): plane g (4 features) at 256 g, sample n inside it at 8 ((n + 4 g) & 31) -- the
-	// rotation makes the transposing reads (4 samples x 8 planes per 32 lanes) and the plane-wise writes both conflict-free.
-	//   writes: this lane holds, per k-step s and half e of a chain fragment, the 4 features of plane 4 s + 2 e + h of sample c
-	//   (of the natural-order input fragment: plane 4 s + 2 h + e).
+	// Images, per wave and 32-feature tile 2 KiB; layout and lane maps w_chain, w_nat, r_tr, r_16: r32_device.h
 	const uint32_t wbase = R32_WAVE0 + wave * R32_WAVE_BYTES;
-	uint32_t w_chain[4], w_nat[4]; // [2 s + e]
-#pragma unroll
-	for (int k = 0; k < 4; ++k) {
-		const uint32_t gc = 4 * (k >> 1) + 2 * (k & 1) + h, gn = 4 * (k >> 1) + 2 * h + (k & 1);
-		w_chain[k] = wbase + gc * 256 + ((c + 4 * gc) & 31) * 8;
-		w_nat[k] = wbase + gn * 256 + ((c + 4 * gn) & 31) * 8;
-	}
-	//   transposing reads (ds_read_b64_tr_b16: per 16 lanes a block of 4 rows x 16 columns; lane 4 q + p supplies the address of row q,
-	//   columns 4 p .. 4 p + 3, and receives column (lane & 15) of the 4 rows)
-	//   32x32x16 operand of sample k-step s': element j = sample 16 s' + 8 hh + j of feature (lane & 31), hh = lane >> 5: reads e = 0, 1 of 4 samples
-	//   16x16x32 operand (all 32 samples): element j = sample 8 (lane >> 4) + j of feature 16 half + (lane & 15)
-	uint32_t r_tr[4], r_16[4]; // [2 s' + e], [2 half + e]
-	{
-		const uint32_t grp = lane >> 4, li = lane & 15, q = li >> 2, p = li & 3, hh = grp >> 1;
-		const uint32_t g = 4 * (grp & 1) + p;
-#pragma unroll
-		for (int k = 0; k < 4; ++k) {
-			const uint32_t row = 16 * (k >> 1) + 8 * hh + 4 * (k & 1) + q;
-			r_tr[k] = wbase + g * 256 + ((row + 4 * g) & 31) * 8;
-			const uint32_t g16 = 4 * (k >> 1) + p, row16 = 8 * grp + 4 * (k & 1) + q;
-			r_16[k] = wbase + g16 * 256 + ((row16 + 4 * g16) & 31) * 8;
-		}
-	}
+	R32_IMAGE_MAPS(wbase, wbase);
 	auto img_write = [&](const int img, const uint32_t (&w)[4], const int s, const h8 v) {
 		if constexpr (DIAG & 4) { asm volatile("" :: "v"(v)); return; }
-		*(h4*)(smem + w[2 * s + 0] + img) = h4{v[0], v[1], v[2], v[3]};
-		*(h4*)(smem + w[2 * s + 1] + img) = h4{v[4], v[5], v[6], v[7]};
+		r32_img_write(smem, w[2 * s + 0] + img, w[2 * s + 1] + img, v);
 	};
 	auto img_own = [&](const int img, const int s) -> h8 { // this lane's own chain fragment back from an image
 		if constexpr (DIAG & 2) { asm volatile("" : "+v"(fake)); return fake; }
-		const h4 lo = *(const h4*)(smem + w_chain[2 * s + 0] + img), hi = *(const h4*)(smem + w_chain[2 * s + 1] + img);
-		return h8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+		return r32_img_read(smem, w_chain[2 * s + 0] + img, w_chain[2 * s + 1] + img);
 	};
 	auto tr2 = [&](const uint32_t a0, const uint32_t a1) -> h8 {
 		if constexpr (DIAG & 2) { asm volatile("" : "+v"(fake)); return fake; }
-		const h4 lo = lds_read_tr((const half_t*)(smem + a0)), hi = lds_read_tr((const half_t*)(smem + a1));
-		return h8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+		return r32_img_read_tr(smem, a0, a1);
 	};
 	auto tr_frag = [&](const int img, const int sp) -> h8 { return tr2(r_tr[2 * sp] + img, r_tr[2 * sp + 1] + img); };   // 32x32x16 operand
 	auto tr_frag16 = [&](const int img, const int half) -> h8 { return tr2(r_16[2 * half] + img, r_16[2 * half + 1] + img); }; // 16x16x32 operand
@@ -210,8 +132,8 @@ __global__ void __launch_bounds__(R32_NW * 64, 2) k_mlp_train_r32(const R32Args 
 #pragma unroll
 	for (int i = 0; i < 4; ++i) wout[i] = f4{0, 0, 0, 0};
 
-	// fragment slots (R32Frags of this network)
-	constexpr int F0 = 0, F1 = 4, FO = 12, BO = 16, B1 = 18, B0 = 26;
+	typedef R32Slots<32, 64> S; // fragment slots (mlp_side_jobs.h)
+	constexpr int F0 = S::F0, F1 = S::F1, FO = S::FO, BO = S::BO, B1 = S::B1, B0 = S::B0;
 	const f16v Z = zero16();
 
 	unsigned long long ph[R32_REGIONS] = {}, ph_prev = 0;
@@ -235,7 +157,7 @@ __global__ void __launch_bounds__(R32_NW * 64, 2) k_mlp_train_r32(const R32Args 
 		if (a.prio_mode == 3) __builtin_amdgcn_s_setprio(1); // the regions with matrix instructions above the loss (vector only)
 		asm volatile("" : "+v"(lane16));
 		if constexpr ((DIAG & 64) != 0) ph_prev = __builtin_readcyclecounter();
-		const In in = pre;
+		const R32In in = pre;
 		// ------------------------------------------------------------------------------------------------ forward
 		{ // unconditionally (the last trip re-reads its own block): no branch between a trip's loads and its stores, so that the
 		  // compiler's wait for these loads at the top of the next trip is a counted one that leaves the stores in flight
@@ -297,44 +219,9 @@ __global__ void __launch_bounds__(R32_NW * 64, 2) k_mlp_train_r32(const R32Args 
 		// ------------------------------------------------------------------------------------------------ loss on the result tile
 		if (a.prio_mode == 3) __builtin_amdgcn_s_setprio(0);
 		const h8 ov = pack8(o, 0); // element g: output 2 g + h (output activation None)
-		h8 dyf = h8{0, 0, 0, 0, 0, 0, 0, 0}; // dL/doutput, the B fragment of the first backward product (k = position)
-		{
-			// l2.h:40-74 / relative_l2.h:40-75 on one refined reciprocal (loss_l2_fused, mlp_device.h), the two output slots of a lane side by
-			// side; values and gradients of the live outputs go to the compact context matrices [n][dims]
-			float value[2];
-			half_t grad[2];
-#pragma unroll
-			for (int r = 0; r < 2; ++r) {
-				const float prediction = (float)ov[r];
-				if constexpr (DIAG & 8) {
-					value[r] = prediction - in.t[r];
-					grad[r] = (half_t)(a.loss_scale * prediction / n_total);
-				} else loss_l2_fused<LOSS == 2>(prediction, in.t[r], lsc, value[r], grad[r]);
-			}
-			asm volatile("" : "+v"(value[0]), "+v"(value[1])); // both chains are evaluated here, in one block, not inside the masked stores below
-#pragma unroll
-			for (int r = 0; r < 2; ++r) {
-				const bool live = 2 * r + h < a.dims;
-				dyf[r] = live ? grad[r] : (half_t)0.0f;
-				if (live) {
-					__builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(uint16_t, grad[r]), rs_g, cg_off0 + 4 * r, blk * (64 * a.dims), 2);
-					__builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, value[r]), rs_l, 2 * cg_off0 + 8 * r, blk * (128 * a.dims), 2);
-				}
-			}
-		}
-		{ // out [n][16]: words (2 g, 2 g + 1) of this lane and of its partner lane (the other half) interleave into the row
-			const u32x4 u = __builtin_bit_cast(u32x4, ov); // u[k] = outputs (4 k + h, 4 k + 2 + h)
-			uint32_t w[4];
-#pragma unroll
-			for (int k = 0; k < 2; ++k) {
-				// lanes < 32 keep u[k] and receive the partner's u[k]; lanes >= 32 receive the partner's u[k + 2] and keep their own
-				const auto sw = __builtin_amdgcn_permlane32_swap(u[k], u[k + 2], false, false);
-				const uint32_t even = sw[0], odd = sw[1]; // outputs (4 k' + 0, 4 k' + 2) and (4 k' + 1, 4 k' + 3), k' = k + 2 h
-				w[2 * k + 0] = __builtin_amdgcn_perm(odd, even, 0x05040100u); // (even.lo, odd.lo)
-				w[2 * k + 1] = __builtin_amdgcn_perm(odd, even, 0x07060302u); // (even.hi, odd.hi)
-			}
-			__builtin_amdgcn_raw_buffer_store_b128(u32x4{w[0], w[1], w[2], w[3]}, rs_out, o_off + blk * 1024, 0, R32_OUT_AUX);
-		}
+		R32_LOSS_COMPACT(dyf, LOSS == 2, (DIAG & 8) != 0, ov, in.t); // dyf: dL/doutput, the B fragment of the first backward product (k = position)
+		R32_OUT_ROW(orow, ov); // out [n][16]
+		__builtin_amdgcn_raw_buffer_store_b128(orow, rs_out, o_off + blk * 1024, 0, R32_OUT_AUX);
 		img_write(IMG_DY, w_chain, 0, dyf); // positions 4 h .. 4 h + 3 (plane h) and 8 + 4 h .. (plane 2 + h)
 		const h8 aY = tr_frag16(IMG_DY, 0);  // dY^T: 16 positions x 32 samples
 		if (a.prio_mode == 3) __builtin_amdgcn_s_setprio(1);
@@ -411,21 +298,8 @@ __global__ void __launch_bounds__(R32_NW * 64, 2) k_mlp_train_r32(const R32Args 
 			wacc[tr] = mfma32(tA[2 * tr + 1], tB[1], wacc[tr]);
 			}
 		}
-		// scatter records {x, y, gradients of levels 2 p, 2 p + 1}: registers 4 g .. 4 g + 3 are features 8 g + 4 h .. + 3, i.e. level pair p = 2 g + h
-		if constexpr (REC) {
-			const u32x4 lo = __builtin_bit_cast(u32x4, pack8(dx, 0)), hi = __builtin_bit_cast(u32x4, pack8(dx, 1));
-			const uint32_t x0 = __builtin_bit_cast(uint32_t, in.xs.x), x1 = __builtin_bit_cast(uint32_t, in.xs.y);
-			const uint32_t rb = blk * 512, pair2 = a.n * 32; // pair2: two level pairs further
-			__builtin_amdgcn_raw_buffer_store_b128(u32x4{x0, x1, lo[0], lo[1]}, rs_rec, rec_off + rb, 0, R32_REC_AUX);
-			__builtin_amdgcn_raw_buffer_store_b128(u32x4{x0, x1, lo[2], lo[3]}, rs_rec, rec_off + (rb + pair2), 0, R32_REC_AUX);
-			__builtin_amdgcn_raw_buffer_store_b128(u32x4{x0, x1, hi[0], hi[1]}, rs_rec, rec_off + (rb + 2 * pair2), 0, R32_REC_AUX);
-			__builtin_amdgcn_raw_buffer_store_b128(u32x4{x0, x1, hi[2], hi[3]}, rs_rec, rec_off + (rb + 3 * pair2), 0, R32_REC_AUX);
-		} else { // level planes: word 2 g + j of the tile's 8 is level 4 g + 2 h + j of sample c -- eight dense 128-byte runs per half wave
-			const u32x4 lo = __builtin_bit_cast(u32x4, pack8(dx, 0)), hi = __builtin_bit_cast(u32x4, pack8(dx, 1));
-			const uint32_t w[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-#pragma unroll
-			for (int k = 0; k < 8; ++k) __builtin_amdgcn_raw_buffer_store_b32(w[k], rs_rec, rec_off, blk * 128 + n4 * (4 * (k >> 1) + (k & 1)), R32_REC_AUX);
-		}
+		if constexpr (REC) r32_store_dx_records(rs_rec, rec_off, blk, a.n, dx, in.xs);
+		else R32_STORE_DX_PLANES(rs_rec, rec_off, blk, n4, dx);
 		R32_SB(); R32_STAMP(14);
 	}
 	if constexpr ((DIAG & 64) != 0) {
@@ -450,9 +324,9 @@ __global__ void __launch_bounds__(R32_NW * 64, 2) k_mlp_train_r32(const R32Args 
 			const GridListTail& t = a.tail;
 			const uint32_t item = blockIdx.x, n_pos = t.map.window * t.map.n_windows;
 			const uint32_t cap = t.item_capacity;
-			const auto rs_si = __builtin_amdgcn_make_buffer_rsrc((void*)t.sidx, 0, (int)(t.n_levels * t.n_items * cap * 2u), 0x00020000);
-			const auto rs_hd = __builtin_amdgcn_make_buffer_rsrc((void*)t.heads, 0, (int)(t.n_levels * GRID_HIT_HEADS * t.n_items * 4u), 0x00020000);
-			const auto rs_gv = __builtin_amdgcn_make_buffer_rsrc(t.gvals, 0, (int)(t.n_levels * t.n_items * cap * 4u), 0x00020000);
+			const auto rs_si = r32_buffer(t.sidx, t.n_levels * t.n_items * cap * 2u);
+			const auto rs_hd = r32_buffer(t.heads, t.n_levels * GRID_HIT_HEADS * t.n_items * 4u);
+			const auto rs_gv = r32_buffer(t.gvals, t.n_levels * t.n_items * cap * 4u);
 			typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 			const uint32_t p0 = 2 * tid;     // this thread's two positions of the item: consecutive samples of one window
 			const uint32_t my_sample = grid_item_sample(t.map, item, p0);
@@ -538,9 +412,7 @@ __global__ void __launch_bounds__(R32_NW * 64, 2) k_mlp_train_r32(const R32Args 
 		if (a.dbg && tid == 0) a.dbg[(size_t)gridDim.x * (4 + R32_NW) + (size_t)blockIdx.x * 2 * R32_REGIONS + 1] = __builtin_amdgcn_s_memrealtime();
 	}
 }
-#undef R32_SB
 #undef R32_STAMP
-#undef R32_MVD
 
 } // namespace
 
@@ -619,21 +491,16 @@ void r32_launch(hipStream_t stream, const MlpDesc& d, const MlpTrainPlan& p, con
 #else
 	// ---- laboratory build (build.py --dev): in-kernel clocks (TCNN_AMD_MLP_TIMING), timing-only kernel variants (TCNN_AMD_MLP_DIAG), start
 	// delays (TCNN_AMD_MLP_STAGGER), workgroup placement (TCNN_AMD_MLP_WHERE).  None of this is in the product library.
-	static const bool timing = getenv("TCNN_AMD_MLP_TIMING") != nullptr;
-	static int timing_left = 5;
-	if (timing && timing_left > 0) {
-		HIP_CHECK_THROW(hipMalloc(&a.dbg, (size_t)grid * 1024));
-		HIP_CHECK_THROW(hipMemset(a.dbg, 0, (size_t)grid * 1024));
-	}
+	static DevClocks clocks;
+	a.dbg = clocks.alloc((size_t)grid * 1024);
 	if (const char* e = getenv("TCNN_AMD_MLP_STAGGER")) a.stagger = (uint32_t)atoi(e);
 	static const int diag_env = getenv("TCNN_AMD_MLP_DIAG") ? atoi(getenv("TCNN_AMD_MLP_DIAG")) : 0;
 	const int diag = a.rec_x ? diag_env : 0; // (the timing-only variants exist in the record form)
 	if (r32a) {
 		r32a_launch(stream, a, grid, loss == LossType::L2 ? 1 : 2);
-		if (a.dbg) {
-			std::vector<unsigned long long> hst((size_t)grid * (7 + 4 * R32A_NW));
-			HIP_CHECK_THROW(hipMemcpy(hst.data(), a.dbg, hst.size() * 8, hipMemcpyDeviceToHost));
-			if (--timing_left == 0) {
+		{
+			std::vector<unsigned long long> hst(a.dbg ? (size_t)grid * (7 + 4 * R32A_NW) : 0);
+			if (clocks.fetch(a.dbg, hst.data(), hst.size())) {
 				double fill = 0, loop = 0, tail = 0;
 				unsigned long long s0 = ~0ull, s1 = 0, e0 = ~0ull, e1 = 0;
 				for (uint32_t g = 0; g < grid; ++g) {
@@ -676,7 +543,6 @@ void r32_launch(hipStream_t stream, const MlpDesc& d, const MlpTrainPlan& p, con
 					fprintf(stderr, "\n");
 				}
 			}
-			(void)hipFree(a.dbg);
 		}
 		return;
 	}
@@ -691,10 +557,9 @@ void r32_launch(hipStream_t stream, const MlpDesc& d, const MlpTrainPlan& p, con
 	else if (diag == 34) go(k_mlp_train_r32<2, true, 34>); // the chain wave of a role split: no weight-gradient products, no transposing reads
 	else if (loss == LossType::L2) { if (a.rec_x) go(k_mlp_train_r32<1, true>); else go(k_mlp_train_r32<1, false>); }
 	else { if (a.rec_x) go(k_mlp_train_r32<2, true>); else go(k_mlp_train_r32<2, false>); }
-	if (a.dbg) {
-		std::vector<unsigned long long> hst((size_t)grid * (4 + R32_NW + 2 * R32_REGIONS));
-		HIP_CHECK_THROW(hipMemcpy(hst.data(), a.dbg, hst.size() * 8, hipMemcpyDeviceToHost));
-		if (--timing_left == 0) {
+	{
+		std::vector<unsigned long long> hst(a.dbg ? (size_t)grid * (4 + R32_NW + 2 * R32_REGIONS) : 0);
+		if (clocks.fetch(a.dbg, hst.data(), hst.size())) {
 			double fill = 0, loop = 0, tail = 0;
 			for (uint32_t g = 0; g < grid; ++g) {
 				fill += (double)(hst[g * 4 + 1] - hst[g * 4]);
@@ -730,7 +595,6 @@ void r32_launch(hipStream_t stream, const MlpDesc& d, const MlpTrainPlan& p, con
 				}
 			}
 		}
-		(void)hipFree(a.dbg);
 	}
 #endif
 }

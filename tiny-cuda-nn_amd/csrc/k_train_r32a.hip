@@ -35,13 +35,8 @@ constexpr int A_IMG_X = 0, A_IMG_H0 = 2048, A_IMG_H1 = 6144, A_IMG_DH1 = 10240, 
 constexpr int A_WAVE_BYTES = 19 * 1024;              // X 2 K | H0 4 K | H1 4 K | dH1 4 K | dH0 4 K | dY 1 K
 constexpr int A_LDS_BYTES = R32A_NW * A_WAVE_BYTES + 1024; // 78 848 (the KiB: see the second tile of waves 2, 3): two workgroups per CU
 
-__device__ inline void mfma32_acc(f16v& acc, const h8 a, const h8 b) { asm("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b)); }
-
-#define A_SB() __builtin_amdgcn_sched_barrier(0)
 constexpr int A_NPH = 4; // stamps (each costs ~200 clocks): [0] chain, [1] barrier, [2] weight gradients, [3] barrier
 #define A_STAMP(i) do { if (a.dbg) { const unsigned long long now_ = __builtin_readcyclecounter(); ph[i] += now_ - ph_prev; ph_prev = now_; } } while (0)
-// within a region: one matrix instruction, then V vector and D LDS instructions (sched_group_barrier masks: 0x8 MFMA, 0x2 VALU, 0x80 DS)
-#define A_MVD(V, D) do { __builtin_amdgcn_sched_group_barrier(0x8, 1, 0); __builtin_amdgcn_sched_group_barrier(0x2, V, 0); __builtin_amdgcn_sched_group_barrier(0x80, D, 0); } while (0)
 
 // LOSS 1: L2, 2: RelativeL2
 template <int LOSS, bool REC> // REC: scatter records out, else plain level planes (k_mlp_train_r32)
@@ -65,61 +60,35 @@ __global__ void __launch_bounds__(R32A_NW * 64, 2) k_mlp_train_r32a(const R32Arg
 	const uint32_t n4 = a.n * 4;
 
 	// ---- the weights.  Fragment slots (R32Frags of this network); resident: F1, FO, B1, B0 (24 fragments)
-	constexpr int F0 = 0, F1 = 4, FO = 12, BO = 16, B1 = 18, B0 = 26;
+	typedef R32Slots<32, 64> S; // (mlp_side_jobs.h)
+	constexpr int F0 = S::F0, F1 = S::F1, FO = S::FO, BO = S::BO, B1 = S::B1, B0 = S::B0;
 	// The workgroup's four waves bring the 30 KiB from global memory ONCE, through LDS (the image area, not in use yet): every wave
 	// loading its own copy was 4 x the bytes through the L2 -> CU path, which set the length of this phase (5.4 k clocks)
-	constexpr int FILL = (30 * 64 + R32A_NW * 64 - 1) / (R32A_NW * 64);
-	h8 stage[FILL];
-#pragma unroll
-	for (int k = 0; k < FILL; ++k) stage[k] = a.image[min(tid + k * R32A_NW * 64, 30u * 64u - 1u)];
+	R32_STAGE_LOAD(stage, S::N, R32A_NW);
 	// the other six: one 16-byte load per lane and use.  An opaque per-trip copy of the lane keeps the (loop-invariant) loads inside the trip loop
 	uint32_t lane_o = lane;
 	auto frag = [&](const int f) -> h8 { return a.image[f * 64 + lane_o]; };
 
-	// ---- global addressing as in k_mlp_train_r32: raw buffer accesses, a lane offset that never changes + the scalar offset of the
-	// trip's block; 16-byte stores carry the block offset in the vector offset (the hazard described there)
-	const auto rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, (int)(a.n * 64), 0x00020000);
-	const auto rs_t = __builtin_amdgcn_make_buffer_rsrc((void*)a.target, 0, (int)(a.n * a.dims * 4), 0x00020000);
-	const auto rs_xs = __builtin_amdgcn_make_buffer_rsrc((void*)a.rec_x, 0, (int)(a.n * 8), 0x00020000);
-	const auto rs_out = __builtin_amdgcn_make_buffer_rsrc((void*)a.out, 0, (int)(a.n * 32), 0x00020000);
-	const auto rs_g = __builtin_amdgcn_make_buffer_rsrc((void*)a.dL_dout, 0, (int)(a.n * a.dims * 2), 0x00020000);
-	const auto rs_l = __builtin_amdgcn_make_buffer_rsrc((void*)a.L, 0, (int)(a.n * a.dims * 4), 0x00020000);
-	const auto rs_rec = __builtin_amdgcn_make_buffer_rsrc((void*)a.rec, 0, (int)(a.n * (REC ? 128 : 64)), 0x00020000);
-	const uint32_t x_off = (4 * h * a.n + c) * 4; // levels 8 s + 4 h + i at + (8 s + i) n 4
-	struct In { h8 x[2]; float t[2]; float2 xs; };
-	uint32_t t_off[2];
-#pragma unroll
-	for (int r = 0; r < 2; ++r) t_off[r] = (c * a.dims + min(2 * r + h, a.dims - 1)) * 4; // outputs >= dims re-read the last one (masked where used)
-	auto load_in = [&](const uint32_t blk_) -> In {
-		const uint32_t blk = __builtin_amdgcn_readfirstlane(blk_); // the scalar offsets below stay scalar (behind the trip's branch the compiler had moved them to the vector unit: a waterfall loop per load)
-		In r;
-#pragma unroll
-		for (int s = 0; s < 2; ++s) {
-			u32x4 v;
-#pragma unroll
-			for (int i = 0; i < 4; ++i) v[i] = __builtin_amdgcn_raw_buffer_load_b32(rs_x, x_off, blk * 128 + n4 * (8 * s + i), 0);
-			r.x[s] = __builtin_bit_cast(h8, v);
-		}
-		const uint32_t tb = blk * (128 * a.dims);
-		r.t[0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_t, t_off[0], tb, 0));
-		r.t[1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_t, t_off[1], tb, 0));
-		if constexpr (REC) r.xs = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rs_xs, c * 8, blk * 256, 0));
-		else r.xs = float2{0, 0};
-		return r;
-	};
+	// ---- global addressing: raw buffer accesses, a lane offset that never changes + the scalar offset of the trip's block (r32_device.h:
+	// r32_buffer; the 16-byte stores' offsets: r32_store_dx_records)
+	const auto rs_x = r32_buffer(a.x, a.n * 64);
+	const auto rs_t = r32_buffer(a.target, a.n * a.dims * 4);
+	const auto rs_xs = r32_buffer(a.rec_x, a.n * 8);
+	const auto rs_out = r32_buffer(a.out, a.n * 32);
+	const auto rs_g = r32_buffer(a.dL_dout, a.n * a.dims * 2);
+	const auto rs_l = r32_buffer(a.L, a.n * a.dims * 4);
+	const auto rs_rec = r32_buffer(a.rec, a.n * (REC ? 128 : 64));
+	R32_DEFINE_LOAD_IN(REC); // x_off, t_off, load_in(block) -> R32In
 	const uint32_t first = blockIdx.x * R32A_NW + wave;
-	In pre = load_in(min(first, n_blocks - 1));
+	R32In pre = load_in(min(first, n_blocks - 1));
 	h8 f0[4]; // layer 0's fragments: requested at the end of the trip before
 #pragma unroll
 	for (int i = 0; i < 4; ++i) f0[i] = frag(F0 + i);
-#pragma unroll
-	for (int k = 0; k < FILL; ++k) {
-		if (tid + k * R32A_NW * 64 < 30u * 64u) ((h8*)smem)[tid + k * R32A_NW * 64] = stage[k];
-	}
+	R32_STAGE_STORE(stage, S::N, R32A_NW);
 	__syncthreads();
-	h8 w[30];
+	h8 w[S::N];
 #pragma unroll
-	for (int f = 0; f < 30; ++f) {
+	for (int f = 0; f < S::N; ++f) {
 		if ((f >= F0 && f < F1) || (f >= BO && f < B1)) continue;
 		w[f] = ((const h8*)smem)[f * 64 + lane];
 		asm volatile("" : "+a"(w[f]));
@@ -127,41 +96,14 @@ __global__ void __launch_bounds__(R32A_NW * 64, 2) k_mlp_train_r32a(const R32Arg
 	__syncthreads(); // the first trip's images overwrite the staging copy
 	const unsigned long long t_fill = a.dbg ? __builtin_readcyclecounter() : 0ull;
 
-	// ---- images (k_train_r32.hip): per wave and 32-feature tile 2 KiB, plane g (4 features) at 256 g, sample n inside it at 8 ((n + 4 g) & 31)
+	// ---- images, per wave and 32-feature tile 2 KiB; layout and lane maps w_chain, w_nat, r_tr: r32_device.h
 	const uint32_t wbase = wave * A_WAVE_BYTES;
-	uint32_t w_chain[4], w_nat[4]; // [2 s + e]
-#pragma unroll
-	for (int k = 0; k < 4; ++k) {
-		const uint32_t gc = 4 * (k >> 1) + 2 * (k & 1) + h, gn = 4 * (k >> 1) + 2 * h + (k & 1);
-		w_chain[k] = wbase + gc * 256 + ((c + 4 * gc) & 31) * 8;
-		w_nat[k] = wbase + gn * 256 + ((c + 4 * gn) & 31) * 8;
-	}
-	uint32_t r_tr[4], r_16[4]; // [2 s' + e], [2 half + e]: relative to a tile of ANY wave's images
-	{
-		const uint32_t grp = lane >> 4, li = lane & 15, q = li >> 2, p = li & 3, hh = grp >> 1;
-		const uint32_t g = 4 * (grp & 1) + p;
-#pragma unroll
-		for (int k = 0; k < 4; ++k) {
-			const uint32_t row = 16 * (k >> 1) + 8 * hh + 4 * (k & 1) + q;
-			r_tr[k] = g * 256 + ((row + 4 * g) & 31) * 8;
-			const uint32_t g16 = 4 * (k >> 1) + p, row16 = 8 * grp + 4 * (k & 1) + q;
-			r_16[k] = g16 * 256 + ((row16 + 4 * g16) & 31) * 8;
-		}
-	}
+	R32_IMAGE_MAPS(wbase, 0); // the read maps: relative to a tile of ANY wave's images
 	auto img_write = [&](const int img, const uint32_t (&wr)[4], const int s, const h8 v) {
-		*(h4*)(smem + wr[2 * s + 0] + img) = h4{v[0], v[1], v[2], v[3]};
-		*(h4*)(smem + wr[2 * s + 1] + img) = h4{v[4], v[5], v[6], v[7]};
+		r32_img_write(smem, wr[2 * s + 0] + img, wr[2 * s + 1] + img, v);
 	};
-	auto img_own = [&](const int img, const int s) -> h8 { // this lane's own chain fragment back from an image
-		const h4 lo = *(const h4*)(smem + w_chain[2 * s + 0] + img), hi = *(const h4*)(smem + w_chain[2 * s + 1] + img);
-		return h8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-	};
-	auto tr2 = [&](const uint32_t a0, const uint32_t a1) -> h8 {
-		const h4 lo = lds_read_tr((const half_t*)(smem + a0)), hi = lds_read_tr((const half_t*)(smem + a1));
-		return h8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-	};
-	auto tr_frag = [&](const uint32_t img, const int sp) -> h8 { return tr2(r_tr[2 * sp] + img, r_tr[2 * sp + 1] + img); };       // 32x32x16 operand
-	auto tr_frag16 = [&](const uint32_t img, const int half) -> h8 { return tr2(r_16[2 * half] + img, r_16[2 * half + 1] + img); }; // 16x16x32 operand
+	auto img_own = [&](const int img, const int s) -> h8 { return r32_img_read(smem, w_chain[2 * s + 0] + img, w_chain[2 * s + 1] + img); }; // this lane's own chain fragment back from an image
+	auto tr_frag = [&](const uint32_t img, const int sp) -> h8 { return r32_img_read_tr(smem, r_tr[2 * sp] + img, r_tr[2 * sp + 1] + img); }; // 32x32x16 operand
 
 	const uint32_t cg_off0 = (c * a.dims + h) * 2;
 	const uint32_t o_off = c * 32 + h * 16;
@@ -194,7 +136,7 @@ __global__ void __launch_bounds__(R32A_NW * 64, 2) k_mlp_train_r32a(const R32Arg
 			if ((trip + (blockIdx.x >= gridDim.x / 2 ? 1u : 0u)) & 1u) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
 		}
 		asm volatile("" : "+v"(lane_o));
-		const In in = pre;
+		const R32In in = pre;
 		pre = load_in(min(blk + per_trip, n_blocks - 1)); // a whole trip ahead
 		if (valid) {
 			// ------------------------------------------------------------------------------------------------ forward
@@ -202,15 +144,15 @@ __global__ void __launch_bounds__(R32A_NW * 64, 2) k_mlp_train_r32a(const R32Arg
 			img_write(A_IMG_X, w_nat, 1, in.x[1]);
 			f16v a0 = mfma32(f0[0], in.x[0], Z);
 			a0 = mfma32(f0[1], in.x[1], a0);
-			A_SB();
+			R32_SB();
 			f16v a1 = mfma32(f0[2], in.x[0], Z);
 			a1 = mfma32(f0[3], in.x[1], a1);
 			const h8 h00 = relu8(pack8(a0, 0)), h01 = relu8(pack8(a0, 1));
 			img_write(A_IMG_H0, w_chain, 0, h00);
 			img_write(A_IMG_H0, w_chain, 1, h01);
 			const h8 wbo0 = frag(BO + 0), wbo1 = frag(BO + 1);
-			A_MVD(8, 2); A_MVD(8, 2);
-			A_SB();
+			R32_MVD(8, 2); R32_MVD(8, 2);
+			R32_SB();
 			f16v b0 = mfma32(w[F1 + 0], h00, Z);
 			b0 = mfma32(w[F1 + 1], h01, b0);
 			f16v b1 = mfma32(w[F1 + 4], h00, Z);
@@ -218,76 +160,47 @@ __global__ void __launch_bounds__(R32A_NW * 64, 2) k_mlp_train_r32a(const R32Arg
 			const h8 h02 = relu8(pack8(a1, 0)), h03 = relu8(pack8(a1, 1));
 			img_write(A_IMG_H0 + 2048, w_chain, 0, h02);
 			img_write(A_IMG_H0 + 2048, w_chain, 1, h03);
-			A_MVD(4, 1); A_MVD(4, 1); A_MVD(4, 1); A_MVD(4, 1);
-			A_SB();
+			R32_MVD(4, 1); R32_MVD(4, 1); R32_MVD(4, 1); R32_MVD(4, 1);
+			R32_SB();
 			b0 = mfma32(w[F1 + 2], h02, b0);
 			b0 = mfma32(w[F1 + 3], h03, b0);
-			A_SB();
+			R32_SB();
 			b1 = mfma32(w[F1 + 6], h02, b1);
 			b1 = mfma32(w[F1 + 7], h03, b1);
 			const h8 h10 = relu8(pack8(b0, 0)), h11 = relu8(pack8(b0, 1));
 			img_write(A_IMG_H1, w_chain, 0, h10);
 			img_write(A_IMG_H1, w_chain, 1, h11);
-			A_MVD(8, 2); A_MVD(8, 2);
-			A_SB();
+			R32_MVD(8, 2); R32_MVD(8, 2);
+			R32_SB();
 			f16v o = mfma32(w[FO + 0], h10, Z);
 			o = mfma32(w[FO + 1], h11, o);
 			const h8 h12 = relu8(pack8(b1, 0)), h13 = relu8(pack8(b1, 1));
 			img_write(A_IMG_H1 + 2048, w_chain, 0, h12);
 			img_write(A_IMG_H1 + 2048, w_chain, 1, h13);
-			A_MVD(8, 2); A_MVD(8, 2);
-			A_SB();
+			R32_MVD(8, 2); R32_MVD(8, 2);
+			R32_SB();
 			o = mfma32(w[FO + 2], h12, o);
 			o = mfma32(w[FO + 3], h13, o);
-			A_SB();
+			R32_SB();
 
 			// ------------------------------------------------------------------------------------------------ loss on the result tile
 			const h8 ov = pack8(o, 0); // element g: output 2 g + h (output activation None)
-			h8 dyf = h8{0, 0, 0, 0, 0, 0, 0, 0}; // dL/doutput, the B fragment of the first backward product (k = position)
-			{
-				// l2.h:40-74 / relative_l2.h:40-75, the same operations in the same order, the two output slots of a lane side by side
-				float value[2];
-				half_t grad[2];
-#pragma unroll
-				for (int r = 0; r < 2; ++r) {
-					loss_l2_fused<LOSS == 2>((float)ov[r], in.t[r], lsc, value[r], grad[r]); // l2.h:40-74 / relative_l2.h:40-75 on one refined reciprocal (mlp_device.h)
-				}
-				asm volatile("" : "+v"(value[0]), "+v"(value[1])); // both chains are evaluated here, in one block, not inside the masked stores below
-#pragma unroll
-				for (int r = 0; r < 2; ++r) {
-					const bool live = 2 * r + h < a.dims;
-					dyf[r] = live ? grad[r] : (half_t)0.0f;
-					if (live) {
-						__builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(uint16_t, grad[r]), rs_g, cg_off0 + 4 * r, blk * (64 * a.dims), 2);
-						__builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, value[r]), rs_l, 2 * cg_off0 + 8 * r, blk * (128 * a.dims), 2);
-					}
-				}
-			}
-			{ // out [n][16]: words (2 g, 2 g + 1) of this lane and of its partner lane (the other half) interleave into the row
-				const u32x4 u = __builtin_bit_cast(u32x4, ov); // u[k] = outputs (4 k + h, 4 k + 2 + h)
-				uint32_t wd[4];
-#pragma unroll
-				for (int k = 0; k < 2; ++k) {
-					const auto sw = __builtin_amdgcn_permlane32_swap(u[k], u[k + 2], false, false);
-					const uint32_t even = sw[0], odd = sw[1];
-					wd[2 * k + 0] = __builtin_amdgcn_perm(odd, even, 0x05040100u);
-					wd[2 * k + 1] = __builtin_amdgcn_perm(odd, even, 0x07060302u);
-				}
-				__builtin_amdgcn_raw_buffer_store_b128(u32x4{wd[0], wd[1], wd[2], wd[3]}, rs_out, o_off + blk * 1024, 0, 2);
-			}
+			R32_LOSS_COMPACT(dyf, LOSS == 2, false, ov, in.t); // dyf: dL/doutput, the B fragment of the first backward product (k = position)
+			R32_OUT_ROW(orow, ov); // out [n][16]
+			__builtin_amdgcn_raw_buffer_store_b128(orow, rs_out, o_off + blk * 1024, 0, 2);
 			img_write(A_IMG_DY, w_chain, 0, dyf); // positions 4 h .. 4 h + 3 (plane h) and 8 + 4 h .. (plane 2 + h)
-			A_SB();
+			R32_SB();
 
 			// ------------------------------------------------------------------------------------------------ backward chain
 			f16v g0 = mfma32(wbo0, dyf, Z);
 			f16v g1 = mfma32(wbo1, dyf, Z);
 			asm volatile("" : "+v"(g1)); // here, not sunk to its use
-			A_SB();
+			R32_SB();
 			// dH1 = (Wout^T dY) act'(H1) (common_device.h:241-297: from the forward OUTPUT)
 			const h8 d10 = relu_bwd8(pack8(g0, 0), img_own(A_IMG_H1, 0)), d11 = relu_bwd8(pack8(g0, 1), img_own(A_IMG_H1, 1));
 			img_write(A_IMG_DH1, w_chain, 0, d10);
 			img_write(A_IMG_DH1, w_chain, 1, d11);
-			A_SB();
+			R32_SB();
 			f16v e0 = mfma32(w[B1 + 0], d10, Z);
 			e0 = mfma32(w[B1 + 1], d11, e0);
 			f16v e1 = mfma32(w[B1 + 4], d10, Z);
@@ -295,13 +208,13 @@ __global__ void __launch_bounds__(R32A_NW * 64, 2) k_mlp_train_r32a(const R32Arg
 			const h8 d12 = relu_bwd8(pack8(g1, 0), img_own(A_IMG_H1 + 2048, 0)), d13 = relu_bwd8(pack8(g1, 1), img_own(A_IMG_H1 + 2048, 1));
 			img_write(A_IMG_DH1 + 2048, w_chain, 0, d12);
 			img_write(A_IMG_DH1 + 2048, w_chain, 1, d13);
-			A_MVD(6, 1); A_MVD(6, 1); A_MVD(6, 1); A_MVD(6, 1);
-			A_SB();
+			R32_MVD(6, 1); R32_MVD(6, 1); R32_MVD(6, 1); R32_MVD(6, 1);
+			R32_SB();
 			e0 = mfma32(w[B1 + 2], d12, e0);
 			e0 = mfma32(w[B1 + 3], d13, e0);
 			e1 = mfma32(w[B1 + 6], d12, e1);
 			e1 = mfma32(w[B1 + 7], d13, e1);
-			A_SB();
+			R32_SB();
 			const h8 d00 = relu_bwd8(pack8(e0, 0), img_own(A_IMG_H0, 0)), d01 = relu_bwd8(pack8(e0, 1), img_own(A_IMG_H0, 1));
 			img_write(A_IMG_DH0, w_chain, 0, d00);
 			img_write(A_IMG_DH0, w_chain, 1, d01);
@@ -313,22 +226,9 @@ __global__ void __launch_bounds__(R32A_NW * 64, 2) k_mlp_train_r32a(const R32Arg
 			img_write(A_IMG_DH0 + 2048, w_chain, 1, d03);
 			dx = mfma32(w[B0 + 2], d02, dx);
 			dx = mfma32(w[B0 + 3], d03, dx);
-			A_SB();
-			// scatter records {x, y, gradients of levels 2 p, 2 p + 1}: registers 4 g .. 4 g + 3 are features 8 g + 4 h .. + 3, i.e. level pair p = 2 g + h
-			if constexpr (REC) {
-				const u32x4 lo = __builtin_bit_cast(u32x4, pack8(dx, 0)), hi = __builtin_bit_cast(u32x4, pack8(dx, 1));
-				const uint32_t x0 = __builtin_bit_cast(uint32_t, in.xs.x), x1 = __builtin_bit_cast(uint32_t, in.xs.y);
-				const uint32_t rb = blk * 512, pair2 = a.n * 32; // pair2: two level pairs further
-				__builtin_amdgcn_raw_buffer_store_b128(u32x4{x0, x1, lo[0], lo[1]}, rs_rec, rec_off + rb, 0, R32_REC_AUX);
-				__builtin_amdgcn_raw_buffer_store_b128(u32x4{x0, x1, lo[2], lo[3]}, rs_rec, rec_off + (rb + pair2), 0, R32_REC_AUX);
-				__builtin_amdgcn_raw_buffer_store_b128(u32x4{x0, x1, hi[0], hi[1]}, rs_rec, rec_off + (rb + 2 * pair2), 0, R32_REC_AUX);
-				__builtin_amdgcn_raw_buffer_store_b128(u32x4{x0, x1, hi[2], hi[3]}, rs_rec, rec_off + (rb + 3 * pair2), 0, R32_REC_AUX);
-			} else { // level planes: word 2 g + j of the tile's 8 is level 4 g + 2 h + j of sample c
-				const u32x4 lo = __builtin_bit_cast(u32x4, pack8(dx, 0)), hi = __builtin_bit_cast(u32x4, pack8(dx, 1));
-				const uint32_t wd[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-#pragma unroll
-				for (int k = 0; k < 8; ++k) __builtin_amdgcn_raw_buffer_store_b32(wd[k], rs_rec, rec_off, blk * 128 + n4 * (4 * (k >> 1) + (k & 1)), R32_REC_AUX);
-			}
+			R32_SB();
+			if constexpr (REC) r32_store_dx_records(rs_rec, rec_off, blk, a.n, dx, in.xs);
+			else R32_STORE_DX_PLANES(rs_rec, rec_off, blk, n4, dx);
 		} else {
 			// no block for this wave in the last trip: images of zeros make its share of every product vanish
 			const h8 zero = h8{0, 0, 0, 0, 0, 0, 0, 0};
@@ -365,7 +265,7 @@ __global__ void __launch_bounds__(R32A_NW * 64, 2) k_mlp_train_r32a(const R32Arg
 			mfma32_acc(w1acc, a11, b11);
 			mfma32_acc(w2acc, a20, b20);
 			mfma32_acc(w2acc, a21, b21);
-			A_SB();
+			R32_SB();
 		}
 		A_STAMP(2);
 		__syncthreads(); // before the next trip overwrites the images
@@ -398,9 +298,7 @@ __global__ void __launch_bounds__(R32A_NW * 64, 2) k_mlp_train_r32a(const R32Arg
 		a.dbg[(size_t)gridDim.x * 4 + blockIdx.x * 2 + 1] = __builtin_amdgcn_s_memrealtime();
 	}
 }
-#undef A_SB
 #undef A_STAMP
-#undef A_MVD
 
 } // namespace
 

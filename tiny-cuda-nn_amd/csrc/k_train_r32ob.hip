@@ -49,18 +49,12 @@ struct ObArgs {
 };
 
 constexpr int OB_NW = 4;                  // waves per workgroup: one per SIMD
-constexpr int OB_NF = 38;                 // fragments used: layer 0 [2][8], layer 1 [2][4], output [4], Wout^T [2], W1^T [2][4] (W0^T is not needed)
+constexpr int OB_NF = R32Slots<128, 64>::B0; // 38 fragments used: layer 0 [2][8], layer 1 [2][4], output [4], Wout^T [2], W1^T [2][4] (W0^T is not needed)
 constexpr int OB_WAVE0 = OB_NF * 1024;
 constexpr int OB_IMG_X = 0, OB_IMG_H0 = 8192, OB_IMG_H1 = 12288, OB_IMG_DH1 = 16384, OB_IMG_DH0 = 20480, OB_IMG_DY = 24576;
 constexpr int OB_WAVE_BYTES = 25 * 1024;  // X 8 K | H0 4 K | H1 4 K | dH1 4 K | dH0 4 K | dY 1 K
 constexpr int OB_LDS_BYTES = OB_WAVE0 + OB_NW * OB_WAVE_BYTES + 1024; // 142 336; the last KiB: what dWout's 32-row read of the last wave's 16-row dY image runs into
 constexpr uint32_t OB_LOG2_BINS = 6;
-
-// accumulate into AGPRs (see the header comment); no hazard to pad: the operands come from LDS reads, which the compiler waits for,
-// and back-to-back accumulation into the same registers needs no wait
-__device__ inline void mfma32_acc(f16v& acc, const h8 a, const h8 b) { asm("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b)); }
-
-#define OB_SB() __builtin_amdgcn_sched_barrier(0)
 
 // LOSS 1: L2, 2: RelativeL2
 template <int LOSS>
@@ -98,15 +92,8 @@ __global__ void __launch_bounds__(OB_NW * 64, 1) k_mlp_train_r32ob(const ObArgs 
 
 	// ---- weight fragments into LDS; this wave's input image zeroed (it stays zero except for the trip's window, see below)
 	{
-		constexpr uint32_t N16 = OB_NF * 64;
-		constexpr int FILL = (N16 + OB_NW * 64 - 1) / (OB_NW * 64);
-		h8 tmp[FILL];
-#pragma unroll
-		for (int k = 0; k < FILL; ++k) tmp[k] = a.image[min(tid + k * OB_NW * 64, N16 - 1)];
-#pragma unroll
-		for (int k = 0; k < FILL; ++k) {
-			if (tid + k * OB_NW * 64 < N16) ((h8*)smem)[tid + k * OB_NW * 64] = tmp[k];
-		}
+		R32_STAGE_LOAD(tmp, OB_NF, OB_NW);
+		R32_STAGE_STORE(tmp, OB_NF, OB_NW);
 	}
 	const uint32_t wbase = OB_WAVE0 + wave * OB_WAVE_BYTES;
 #pragma unroll
@@ -117,36 +104,15 @@ __global__ void __launch_bounds__(OB_NW * 64, 1) k_mlp_train_r32ob(const ObArgs 
 
 	uint32_t lane16 = lane * 16;
 	auto frag = [&](const int f) -> h8 { return *(const h8*)(smem + lane16 + f * 1024); };
-	// images: see k_train_r32.hip (per 32-feature tile 2 KiB: plane g of 4 features at 256 g, sample n at 8 ((n + 4 g) & 31))
-	uint32_t w_chain[4], w_nat[4];
-#pragma unroll
-	for (int k = 0; k < 4; ++k) {
-		const uint32_t gc = 4 * (k >> 1) + 2 * (k & 1) + h, gn = 4 * (k >> 1) + 2 * h + (k & 1);
-		w_chain[k] = wbase + gc * 256 + ((c + 4 * gc) & 31) * 8;
-		w_nat[k] = wbase + gn * 256 + ((c + 4 * gn) & 31) * 8;
-	}
-	uint32_t r_tr[4]; // transposing reads, relative to a tile of ANY wave's images
-	{
-		const uint32_t grp = lane >> 4, li = lane & 15, q = li >> 2, p = li & 3, hh = grp >> 1;
-		const uint32_t g = 4 * (grp & 1) + p;
-#pragma unroll
-		for (int k = 0; k < 4; ++k) {
-			const uint32_t row = 16 * (k >> 1) + 8 * hh + 4 * (k & 1) + q;
-			r_tr[k] = OB_WAVE0 + g * 256 + ((row + 4 * g) & 31) * 8;
-		}
-	}
+	// images (layout and lane maps: r32_device.h); the read map r_tr: relative to a tile of ANY wave's images
+	R32_IMAGE_MAPS(wbase, OB_WAVE0);
 	auto img_write = [&](const int img, const int s, const h8 v) {
-		*(h4*)(smem + w_chain[2 * s + 0] + img) = h4{v[0], v[1], v[2], v[3]};
-		*(h4*)(smem + w_chain[2 * s + 1] + img) = h4{v[4], v[5], v[6], v[7]};
+		r32_img_write(smem, w_chain[2 * s + 0] + img, w_chain[2 * s + 1] + img, v);
 	};
 	auto img_own = [&](const int img, const uint32_t (&w)[4], const int s) -> h8 { // this lane's own fragment back from an image
-		const h4 lo = *(const h4*)(smem + w[2 * s + 0] + img), hi = *(const h4*)(smem + w[2 * s + 1] + img);
-		return h8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+		return r32_img_read(smem, w[2 * s + 0] + img, w[2 * s + 1] + img);
 	};
-	auto tr_frag = [&](const uint32_t img, const int sp) -> h8 {
-		const h4 lo = lds_read_tr((const half_t*)(smem + r_tr[2 * sp] + img)), hi = lds_read_tr((const half_t*)(smem + r_tr[2 * sp + 1] + img));
-		return h8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-	};
+	auto tr_frag = [&](const uint32_t img, const int sp) -> h8 { return r32_img_read_tr(smem, r_tr[2 * sp] + img, r_tr[2 * sp + 1] + img); };
 	// feature f (0..127) of sample c in the input image: tile f >> 5, plane (f & 31) >> 2, element f & 3
 	auto x_addr = [&](const uint32_t f) -> uint32_t {
 		const uint32_t g = (f & 31u) >> 2;
@@ -168,7 +134,8 @@ __global__ void __launch_bounds__(OB_NW * 64, 1) k_mlp_train_r32ob(const ObArgs 
 	const uint32_t img_a0 = OB_IMG_DH0 + 2048 * tr_w, img_b0 = OB_IMG_X + 4096 * tc_w, img_a2 = OB_IMG_DH1 + 2048 * tr_w, img_b2 = OB_IMG_H0 + 2048 * tc_w,
 	               img_b3 = OB_IMG_H1 + 2048 * tc_w; // wave-uniform
 
-	constexpr int F0 = 0, F1 = 16, FO = 24, BO = 28, B1 = 30;
+	typedef R32Slots<128, 64> S; // fragment slots (mlp_side_jobs.h)
+	constexpr int F0 = S::F0, F1 = S::F1, FO = S::FO, BO = S::BO, B1 = S::B1;
 	const f16v Z = zero16();
 
 	for (uint32_t trip = 0; trip < n_trips; ++trip) {
@@ -202,7 +169,7 @@ __global__ void __launch_bounds__(OB_NW * 64, 1) k_mlp_train_r32ob(const ObArgs 
 			h8 wf[8], wg[8];
 #pragma unroll
 			for (int s = 0; s < 8; ++s) wf[s] = frag(F0 + s);
-			OB_SB();
+			R32_SB();
 
 			// -------------------------------------------------------------------------------------------- forward
 			h8 xs[8];
@@ -213,7 +180,7 @@ __global__ void __launch_bounds__(OB_NW * 64, 1) k_mlp_train_r32ob(const ObArgs 
 			f16v a0 = mfma32(wf[0], xs[0], Z);
 #pragma unroll
 			for (int s = 1; s < 8; ++s) a0 = mfma32(wf[s], xs[s], a0);
-			OB_SB();
+			R32_SB();
 #pragma unroll
 			for (int s = 0; s < 8; ++s) wf[s] = frag(F1 + s);
 			f16v a1 = mfma32(wg[0], xs[0], Z);
@@ -222,7 +189,7 @@ __global__ void __launch_bounds__(OB_NW * 64, 1) k_mlp_train_r32ob(const ObArgs 
 			const h8 h00 = relu8(pack8(a0, 0)), h01 = relu8(pack8(a0, 1));
 			img_write(OB_IMG_H0, 0, h00);
 			img_write(OB_IMG_H0, 1, h01);
-			OB_SB();
+			R32_SB();
 			f16v b0 = mfma32(wf[0], h00, Z);
 			b0 = mfma32(wf[1], h01, b0);
 			f16v b1 = mfma32(wf[4], h00, Z);
@@ -232,14 +199,14 @@ __global__ void __launch_bounds__(OB_NW * 64, 1) k_mlp_train_r32ob(const ObArgs 
 			img_write(OB_IMG_H0 + 2048, 1, h03);
 #pragma unroll
 			for (int s = 0; s < 4; ++s) wg[s] = frag(FO + s);
-			OB_SB();
+			R32_SB();
 			b0 = mfma32(wf[2], h02, b0);
 			b0 = mfma32(wf[3], h03, b0);
 			b1 = mfma32(wf[6], h02, b1);
 			b1 = mfma32(wf[7], h03, b1);
 			wg[4] = frag(BO + 0);
 			wg[5] = frag(BO + 1);
-			OB_SB();
+			R32_SB();
 			const h8 h10 = relu8(pack8(b0, 0)), h11 = relu8(pack8(b0, 1));
 			img_write(OB_IMG_H1, 0, h10);
 			img_write(OB_IMG_H1, 1, h11);
@@ -252,57 +219,20 @@ __global__ void __launch_bounds__(OB_NW * 64, 1) k_mlp_train_r32ob(const ObArgs 
 			o = mfma32(wg[3], h13, o);
 #pragma unroll
 			for (int s = 0; s < 8; ++s) wf[s] = frag(B1 + s);
-			OB_SB();
+			R32_SB();
 
 			// -------------------------------------------------------------------------------------------- loss, context matrices, out
 			const h8 ov = pack8(o, 0); // element g: output 2 g + h
-			h8 dyf = h8{0, 0, 0, 0, 0, 0, 0, 0};
-			{
-				float value[2];
-				half_t grad[2];
-#pragma unroll
-				for (int r = 0; r < 2; ++r) {
-					loss_l2_fused<LOSS == 2>((float)ov[r], in.t[r], lsc, value[r], grad[r]); // l2.h:40-74 / relative_l2.h:40-75 on one refined reciprocal (mlp_device.h)
-					const bool live = 2 * r + h < a.dims;
-					if (!live) { value[r] = 0.0f; grad[r] = (half_t)0.0f; }
-					dyf[r] = grad[r];
-				}
-				// the padded matrices [n][16]: outputs 0..3 come from the two lanes of the sample (this lane: 2 r + h), the rest is zero.
-				// lanes h = 0 collect them; every lane stores its half of the row
-				typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-				const uint32_t gpk = __builtin_bit_cast(uint32_t, (h2{grad[0], grad[1]})); // (out h, out 2 + h)
-				const auto sg = __builtin_amdgcn_permlane32_swap(gpk, gpk, false, false);    // lanes < 32: [0] own, [1] the partner's
-				const auto s0 = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, value[0]), __builtin_bit_cast(uint32_t, value[0]), false, false);
-				const auto s1 = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, value[1]), __builtin_bit_cast(uint32_t, value[1]), false, false);
-				u32x4 grow = u32x4{0, 0, 0, 0}, l0 = u32x4{0, 0, 0, 0};
-				if (h == 0) {
-					grow[0] = __builtin_amdgcn_perm(sg[1], sg[0], 0x05040100u); // (g0, g1)
-					grow[1] = __builtin_amdgcn_perm(sg[1], sg[0], 0x07060302u); // (g2, g3)
-					l0 = u32x4{s0[0], s0[1], s1[0], s1[1]};                     // L0, L1, L2, L3
-				}
-				*(u32x4*)((char*)a.dL_dout + (size_t)blk * 1024 + row_off) = grow;
-				float* lrow = (float*)((char*)a.L + (size_t)blk * 2048 + 2 * row_off);
-				*(u32x4*)lrow = l0;
-				*(u32x4*)(lrow + 4) = u32x4{0, 0, 0, 0};
-			}
-			{
-				const u32x4 u = __builtin_bit_cast(u32x4, ov);
-				uint32_t w[4];
-#pragma unroll
-				for (int k = 0; k < 2; ++k) {
-					const auto sw = __builtin_amdgcn_permlane32_swap(u[k], u[k + 2], false, false);
-					w[2 * k + 0] = __builtin_amdgcn_perm(sw[1], sw[0], 0x05040100u);
-					w[2 * k + 1] = __builtin_amdgcn_perm(sw[1], sw[0], 0x07060302u);
-				}
-				*(u32x4*)((char*)a.out + (size_t)blk * 1024 + row_off) = u32x4{w[0], w[1], w[2], w[3]};
-			}
+			R32_LOSS_PADDED(dyf, LOSS == 2, ov, in.t);
+			R32_OUT_ROW(orow, ov);
+			*(u32x4*)((char*)a.out + (size_t)blk * 1024 + row_off) = orow;
 			img_write(OB_IMG_DY, 0, dyf);
-			OB_SB();
+			R32_SB();
 
 			// -------------------------------------------------------------------------------------------- backward chain
 			f16v g0 = mfma32(wg[4], dyf, Z);
 			f16v g1 = mfma32(wg[5], dyf, Z);
-			OB_SB();
+			R32_SB();
 			const h8 d10 = relu_bwd8(pack8(g0, 0), h10), d11 = relu_bwd8(pack8(g0, 1), h11);
 			img_write(OB_IMG_DH1, 0, d10);
 			img_write(OB_IMG_DH1, 1, d11);
@@ -313,12 +243,12 @@ __global__ void __launch_bounds__(OB_NW * 64, 1) k_mlp_train_r32ob(const ObArgs 
 			const h8 d12 = relu_bwd8(pack8(g1, 0), h12), d13 = relu_bwd8(pack8(g1, 1), h13);
 			img_write(OB_IMG_DH1 + 2048, 0, d12);
 			img_write(OB_IMG_DH1 + 2048, 1, d13);
-			OB_SB();
+			R32_SB();
 			e0 = mfma32(wf[2], d12, e0);
 			e0 = mfma32(wf[3], d13, e0);
 			e1 = mfma32(wf[6], d12, e1);
 			e1 = mfma32(wf[7], d13, e1);
-			OB_SB();
+			R32_SB();
 			// dH0 = (W1^T dH1) act'(H0) (no dL/dinput: the encoding has no parameters)
 			const h8 d00 = relu_bwd8(pack8(e0, 0), h00), d01 = relu_bwd8(pack8(e0, 1), h01), d02 = relu_bwd8(pack8(e1, 0), h02), d03 = relu_bwd8(pack8(e1, 1), h03);
 			img_write(OB_IMG_DH0, 0, d00);
@@ -371,7 +301,7 @@ __global__ void __launch_bounds__(OB_NW * 64, 1) k_mlp_train_r32ob(const ObArgs 
 					mfma32_acc(acc[2], A2[buf][sp], B2[buf][sp]);
 					mfma32_acc(acc[3], A3[buf][sp], B3[buf][sp]);
 				}
-				OB_SB();
+				R32_SB();
 			}
 		}
 		__syncthreads(); // before the next trip overwrites the images
@@ -416,11 +346,6 @@ constexpr int OBA_IMG_X = 0, OBA_IMG_H0 = 8192, OBA_IMG_H1 = 12288, OBA_IMG_DH =
 constexpr int OBA_WAVE_BYTES = 21 * 1024;  // X 8 K | H0 4 K | H1 4 K | dH 4 K | dY 1 K
 constexpr int OBA_LDS_BYTES = OB_WAVE0 + OB_NW * OBA_WAVE_BYTES; // 124 928
 
-// accumulate into AGPRs (see the header comment); no hazard to pad: the operands come from LDS reads, which the compiler waits for,
-// and back-to-back accumulation into the same registers needs no wait
-__device__ inline void mfma16_acc(f4& acc, const h8 a, const h8 b) { asm("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b)); }
-
-
 // LOSS 1: L2, 2: RelativeL2
 template <int LOSS>
 __global__ void __launch_bounds__(OB_NW * 64, 1) k_mlp_train_r32ob_acc(const ObArgs a) {
@@ -454,15 +379,8 @@ __global__ void __launch_bounds__(OB_NW * 64, 1) k_mlp_train_r32ob_acc(const ObA
 
 	// ---- weight fragments into LDS; this wave's input image zeroed (it stays zero except for the trip's window, see below)
 	{
-		constexpr uint32_t N16 = OB_NF * 64;
-		constexpr int FILL = (N16 + OB_NW * 64 - 1) / (OB_NW * 64);
-		h8 tmp[FILL];
-#pragma unroll
-		for (int k = 0; k < FILL; ++k) tmp[k] = a.image[min(tid + k * OB_NW * 64, N16 - 1)];
-#pragma unroll
-		for (int k = 0; k < FILL; ++k) {
-			if (tid + k * OB_NW * 64 < N16) ((h8*)smem)[tid + k * OB_NW * 64] = tmp[k];
-		}
+		R32_STAGE_LOAD(tmp, OB_NF, OB_NW);
+		R32_STAGE_STORE(tmp, OB_NF, OB_NW);
 	}
 	const uint32_t wbase = OB_WAVE0 + wave * OBA_WAVE_BYTES;
 #pragma unroll
@@ -472,40 +390,16 @@ __global__ void __launch_bounds__(OB_NW * 64, 1) k_mlp_train_r32ob_acc(const ObA
 
 	uint32_t lane16 = lane * 16;
 	auto frag = [&](const int f) -> h8 { return *(const h8*)(smem + lane16 + f * 1024); };
-	// images: see k_train_r32.hip (per 32-feature tile 2 KiB: plane g of 4 features at 256 g, sample n at 8 ((n + 4 g) & 31))
-	uint32_t w_chain[4], w_nat[4];
-#pragma unroll
-	for (int k = 0; k < 4; ++k) {
-		const uint32_t gc = 4 * (k >> 1) + 2 * (k & 1) + h, gn = 4 * (k >> 1) + 2 * h + (k & 1);
-		w_chain[k] = wbase + gc * 256 + ((c + 4 * gc) & 31) * 8;
-		w_nat[k] = wbase + gn * 256 + ((c + 4 * gn) & 31) * 8;
-	}
-	uint32_t r_tr[4], r_16[4];
-	{
-		const uint32_t grp = lane >> 4, li = lane & 15, q = li >> 2, p = li & 3, hh = grp >> 1;
-		const uint32_t g = 4 * (grp & 1) + p;
-#pragma unroll
-		for (int k = 0; k < 4; ++k) {
-			const uint32_t row = 16 * (k >> 1) + 8 * hh + 4 * (k & 1) + q;
-			r_tr[k] = wbase + g * 256 + ((row + 4 * g) & 31) * 8;
-			const uint32_t g16 = 4 * (k >> 1) + p, row16 = 8 * grp + 4 * (k & 1) + q;
-			r_16[k] = wbase + g16 * 256 + ((row16 + 4 * g16) & 31) * 8;
-		}
-	}
+	// images (layout and lane maps: r32_device.h)
+	R32_IMAGE_MAPS(wbase, wbase);
 	auto img_write = [&](const int img, const int s, const h8 v) {
-		*(h4*)(smem + w_chain[2 * s + 0] + img) = h4{v[0], v[1], v[2], v[3]};
-		*(h4*)(smem + w_chain[2 * s + 1] + img) = h4{v[4], v[5], v[6], v[7]};
+		r32_img_write(smem, w_chain[2 * s + 0] + img, w_chain[2 * s + 1] + img, v);
 	};
 	auto img_own = [&](const int img, const uint32_t (&w)[4], const int s) -> h8 { // this lane's own fragment back from an image
-		const h4 lo = *(const h4*)(smem + w[2 * s + 0] + img), hi = *(const h4*)(smem + w[2 * s + 1] + img);
-		return h8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+		return r32_img_read(smem, w[2 * s + 0] + img, w[2 * s + 1] + img);
 	};
-	auto tr2 = [&](const uint32_t a0, const uint32_t a1) -> h8 {
-		const h4 lo = lds_read_tr((const half_t*)(smem + a0)), hi = lds_read_tr((const half_t*)(smem + a1));
-		return h8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-	};
-	auto tr_frag = [&](const int img, const int sp) -> h8 { return tr2(r_tr[2 * sp] + img, r_tr[2 * sp + 1] + img); };
-	auto tr_frag16 = [&](const int img, const int half) -> h8 { return tr2(r_16[2 * half] + img, r_16[2 * half + 1] + img); };
+	auto tr_frag = [&](const int img, const int sp) -> h8 { return r32_img_read_tr(smem, r_tr[2 * sp] + img, r_tr[2 * sp + 1] + img); };
+	auto tr_frag16 = [&](const int img, const int half) -> h8 { return r32_img_read_tr(smem, r_16[2 * half] + img, r_16[2 * half + 1] + img); };
 	// feature f (0..127) of sample c in the input image: tile f >> 5, plane (f & 31) >> 2, element f & 3
 	auto x_addr = [&](const uint32_t f) -> uint32_t {
 		const uint32_t g = (f & 31u) >> 2;
@@ -521,7 +415,8 @@ __global__ void __launch_bounds__(OB_NW * 64, 1) k_mlp_train_r32ob_acc(const ObA
 #pragma unroll
 	for (int i = 0; i < 4; ++i) { w1acc[i] = zero16(); wout[i] = f4{0, 0, 0, 0}; }
 
-	constexpr int F0 = 0, F1 = 16, FO = 24, BO = 28, B1 = 30;
+	typedef R32Slots<128, 64> S; // fragment slots (mlp_side_jobs.h)
+	constexpr int F0 = S::F0, F1 = S::F1, FO = S::FO, BO = S::BO, B1 = S::B1;
 	const f16v Z = zero16();
 
 	for (uint32_t blk = first; blk < n_blocks; blk += step) {
@@ -555,7 +450,7 @@ __global__ void __launch_bounds__(OB_NW * 64, 1) k_mlp_train_r32ob_acc(const ObA
 		h8 wf[8], wg[8];
 #pragma unroll
 		for (int s = 0; s < 8; ++s) wf[s] = frag(F0 + s);
-		OB_SB();
+		R32_SB();
 
 		// ------------------------------------------------------------------------------------------------ forward
 		h8 xs[8];
@@ -566,7 +461,7 @@ __global__ void __launch_bounds__(OB_NW * 64, 1) k_mlp_train_r32ob_acc(const ObA
 		f16v a0 = mfma32(wf[0], xs[0], Z);
 #pragma unroll
 		for (int s = 1; s < 8; ++s) a0 = mfma32(wf[s], xs[s], a0);
-		OB_SB();
+		R32_SB();
 #pragma unroll
 		for (int s = 0; s < 8; ++s) wf[s] = frag(F1 + s);
 		f16v a1 = mfma32(wg[0], xs[0], Z);
@@ -575,7 +470,7 @@ __global__ void __launch_bounds__(OB_NW * 64, 1) k_mlp_train_r32ob_acc(const ObA
 		const h8 h00 = relu8(pack8(a0, 0)), h01 = relu8(pack8(a0, 1));
 		img_write(OBA_IMG_H0, 0, h00);
 		img_write(OBA_IMG_H0, 1, h01);
-		OB_SB();
+		R32_SB();
 		f16v b0 = mfma32(wf[0], h00, Z);
 		b0 = mfma32(wf[1], h01, b0);
 		f16v b1 = mfma32(wf[4], h00, Z);
@@ -585,14 +480,14 @@ __global__ void __launch_bounds__(OB_NW * 64, 1) k_mlp_train_r32ob_acc(const ObA
 		img_write(OBA_IMG_H0 + 2048, 1, h03);
 #pragma unroll
 		for (int s = 0; s < 4; ++s) wg[s] = frag(FO + s);
-		OB_SB();
+		R32_SB();
 		b0 = mfma32(wf[2], h02, b0);
 		b0 = mfma32(wf[3], h03, b0);
 		b1 = mfma32(wf[6], h02, b1);
 		b1 = mfma32(wf[7], h03, b1);
 		wg[4] = frag(BO + 0);
 		wg[5] = frag(BO + 1);
-		OB_SB();
+		R32_SB();
 		const h8 h10 = relu8(pack8(b0, 0)), h11 = relu8(pack8(b0, 1));
 		img_write(OBA_IMG_H1, 0, h10);
 		img_write(OBA_IMG_H1, 1, h11);
@@ -608,53 +503,16 @@ __global__ void __launch_bounds__(OB_NW * 64, 1) k_mlp_train_r32ob_acc(const ObA
 		for (int tc = 0; tc < 4; ++tc) bH[tc] = tr_frag16(OBA_IMG_H1 + 2048 * (tc >> 1), tc & 1);
 #pragma unroll
 		for (int s = 0; s < 8; ++s) wf[s] = frag(B1 + s);
-		OB_SB();
+		R32_SB();
 
 		// ------------------------------------------------------------------------------------------------ loss, context matrices, out
 		const h8 ov = pack8(o, 0); // element g: output 2 g + h
-		h8 dyf = h8{0, 0, 0, 0, 0, 0, 0, 0};
-		{
-			float value[2];
-			half_t grad[2];
-#pragma unroll
-			for (int r = 0; r < 2; ++r) {
-				loss_l2_fused<LOSS == 2>((float)ov[r], in.t[r], lsc, value[r], grad[r]); // l2.h:40-74 / relative_l2.h:40-75 on one refined reciprocal (mlp_device.h)
-				const bool live = 2 * r + h < a.dims;
-				if (!live) { value[r] = 0.0f; grad[r] = (half_t)0.0f; }
-				dyf[r] = grad[r];
-			}
-			// the padded matrices [n][16]: outputs 0..3 come from the two lanes of the sample (this lane: 2 r + h), the rest is zero.
-			// lanes h = 0 collect them; every lane stores its half of the row
-			typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-			const uint32_t gpk = __builtin_bit_cast(uint32_t, (h2{grad[0], grad[1]})); // (out h, out 2 + h)
-			const auto sg = __builtin_amdgcn_permlane32_swap(gpk, gpk, false, false);    // lanes < 32: [0] own, [1] the partner's
-			const auto s0 = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, value[0]), __builtin_bit_cast(uint32_t, value[0]), false, false);
-			const auto s1 = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, value[1]), __builtin_bit_cast(uint32_t, value[1]), false, false);
-			u32x4 grow = u32x4{0, 0, 0, 0}, l0 = u32x4{0, 0, 0, 0};
-			if (h == 0) {
-				grow[0] = __builtin_amdgcn_perm(sg[1], sg[0], 0x05040100u); // (g0, g1)
-				grow[1] = __builtin_amdgcn_perm(sg[1], sg[0], 0x07060302u); // (g2, g3)
-				l0 = u32x4{s0[0], s0[1], s1[0], s1[1]};                     // L0, L1, L2, L3
-			}
-			*(u32x4*)((char*)a.dL_dout + (size_t)blk * 1024 + row_off) = grow;
-			float* lrow = (float*)((char*)a.L + (size_t)blk * 2048 + 2 * row_off);
-			*(u32x4*)lrow = l0;
-			*(u32x4*)(lrow + 4) = u32x4{0, 0, 0, 0};
-		}
-		{
-			const u32x4 u = __builtin_bit_cast(u32x4, ov);
-			uint32_t w[4];
-#pragma unroll
-			for (int k = 0; k < 2; ++k) {
-				const auto sw = __builtin_amdgcn_permlane32_swap(u[k], u[k + 2], false, false);
-				w[2 * k + 0] = __builtin_amdgcn_perm(sw[1], sw[0], 0x05040100u);
-				w[2 * k + 1] = __builtin_amdgcn_perm(sw[1], sw[0], 0x07060302u);
-			}
-			*(u32x4*)((char*)a.out + (size_t)blk * 1024 + row_off) = u32x4{w[0], w[1], w[2], w[3]};
-		}
+		R32_LOSS_PADDED(dyf, LOSS == 2, ov, in.t);
+		R32_OUT_ROW(orow, ov);
+		*(u32x4*)((char*)a.out + (size_t)blk * 1024 + row_off) = orow;
 		img_write(OBA_IMG_DY, 0, dyf);
 		const h8 aY = tr_frag16(OBA_IMG_DY, 0);
-		OB_SB();
+		R32_SB();
 
 		// ------------------------------------------------------------------------------------------------ backward chain and weight gradients
 		f16v g0 = mfma32(wg[4], dyf, Z);
@@ -664,7 +522,7 @@ __global__ void __launch_bounds__(OB_NW * 64, 1) k_mlp_train_r32ob_acc(const ObA
 		h8 tB[4]; // H0^T, for dW1
 #pragma unroll
 		for (int k = 0; k < 4; ++k) tB[k] = tr_frag(OBA_IMG_H0 + 2048 * (k >> 1), k & 1);
-		OB_SB();
+		R32_SB();
 		const h8 d10 = relu_bwd8(pack8(g0, 0), h10), d11 = relu_bwd8(pack8(g0, 1), h11);
 		img_write(OBA_IMG_DH, 0, d10);
 		img_write(OBA_IMG_DH, 1, d11);
@@ -675,7 +533,7 @@ __global__ void __launch_bounds__(OB_NW * 64, 1) k_mlp_train_r32ob_acc(const ObA
 		const h8 d12 = relu_bwd8(pack8(g1, 0), h12), d13 = relu_bwd8(pack8(g1, 1), h13);
 		img_write(OBA_IMG_DH + 2048, 0, d12);
 		img_write(OBA_IMG_DH + 2048, 1, d13);
-		OB_SB();
+		R32_SB();
 		e0 = mfma32(wf[2], d12, e0);
 		e0 = mfma32(wf[3], d13, e0);
 		e1 = mfma32(wf[6], d12, e1);
@@ -683,7 +541,7 @@ __global__ void __launch_bounds__(OB_NW * 64, 1) k_mlp_train_r32ob_acc(const ObA
 		h8 tA[4]; // dH1^T
 #pragma unroll
 		for (int k = 0; k < 4; ++k) tA[k] = tr_frag(OBA_IMG_DH + 2048 * (k >> 1), k & 1);
-		OB_SB();
+		R32_SB();
 		// dW1 = dH1 H0^T beside dH0 = (W1^T dH1) act'(H0)
 #pragma unroll
 		for (int tr = 0; tr < 2; ++tr)
@@ -704,7 +562,7 @@ __global__ void __launch_bounds__(OB_NW * 64, 1) k_mlp_train_r32ob_acc(const ObA
 			wf[2 * tc] = tr_frag(OBA_IMG_X + 2048 * tc, 0);
 			wf[2 * tc + 1] = tr_frag(OBA_IMG_X + 2048 * tc, 1);
 		}
-		OB_SB();
+		R32_SB();
 		// dW0 = dH0 X^T: 2 x 4 tiles
 #pragma unroll
 		for (int tc = 0; tc < 4; ++tc)
@@ -720,7 +578,7 @@ __global__ void __launch_bounds__(OB_NW * 64, 1) k_mlp_train_r32ob_acc(const ObA
 		} else {
 			for (uint32_t bin = 0; bin < 64; ++bin) *(half_t*)(smem + x_addr(64 * h + bin)) = (half_t)0.0f;
 		}
-		OB_SB();
+		R32_SB();
 	}
 	if (a.dbg && tid == 0) a.dbg[blockIdx.x * 4 + 2] = __builtin_readcyclecounter();
 
@@ -771,8 +629,6 @@ __global__ void __launch_bounds__(OB_NW * 64, 1) k_mlp_train_r32ob_acc(const ObA
 	if (a.dbg && tid == 0) a.dbg[blockIdx.x * 4 + 3] = __builtin_readcyclecounter();
 }
 
-#undef OB_SB
-
 } // namespace
 
 // the one shape this kernel is instantiated for, padded context matrices, weight gradients wanted (TCNN_AMD_MLP_R32=0 keeps k_train.hip's kernel)
@@ -810,16 +666,8 @@ void r32ob_launch(hipStream_t stream, const MlpDesc& d, const MlpTrainPlan& p, c
 	a.n_params = in.n_params;
 	for (int l = 0; l < 3; ++l) a.w_off[l] = d.layers[l].w_off;
 	a.loss_scale = in.loss_scale;
-#ifdef TCNN_AMD_DEV // laboratory build (build.py --dev): in-kernel clocks of the 5th launch
-	static const bool timing = getenv("TCNN_AMD_MLP_TIMING") != nullptr;
-	static int timing_left = 5;
-	if (timing && timing_left > 0) {
-		HIP_CHECK_THROW(hipMalloc(&a.dbg, (size_t)grid * 48));
-		HIP_CHECK_THROW(hipMemset(a.dbg, 0, (size_t)grid * 48));
-	}
-#else
-	int timing_left = 0; (void)timing_left;
-#endif
+	static DevClocks clocks; // (laboratory build)
+	a.dbg = clocks.alloc((size_t)grid * 48);
 	if (shared) {
 		if (l2) launch_with_lds(k_mlp_train_r32ob<1>, stream, grid, OB_NW * 64, OB_LDS_BYTES, a);
 		else launch_with_lds(k_mlp_train_r32ob<2>, stream, grid, OB_NW * 64, OB_LDS_BYTES, a);
@@ -827,10 +675,9 @@ void r32ob_launch(hipStream_t stream, const MlpDesc& d, const MlpTrainPlan& p, c
 		if (l2) launch_with_lds(k_mlp_train_r32ob_acc<1>, stream, grid, OB_NW * 64, OBA_LDS_BYTES, a);
 		else launch_with_lds(k_mlp_train_r32ob_acc<2>, stream, grid, OB_NW * 64, OBA_LDS_BYTES, a);
 	}
-	if (a.dbg) {
-		std::vector<unsigned long long> hst((size_t)grid * 6);
-		HIP_CHECK_THROW(hipMemcpy(hst.data(), a.dbg, hst.size() * 8, hipMemcpyDeviceToHost));
-		if (--timing_left == 0) {
+	{
+		std::vector<unsigned long long> hst(a.dbg ? (size_t)grid * 6 : 0);
+		if (clocks.fetch(a.dbg, hst.data(), hst.size())) {
 			double fill = 0, loop = 0, tail = 0;
 			for (uint32_t g = 0; g < grid; ++g) {
 				fill += (double)(hst[g * 4 + 1] - hst[g * 4]);
@@ -847,7 +694,6 @@ void r32ob_launch(hipStream_t stream, const MlpDesc& d, const MlpTrainPlan& p, c
 			}
 			if (shared) fprintf(stderr, "  workgroup starts spread over %.2f us, ends from %.2f to %.2f us after the first start\n", (s1 - s0) * 0.01, (e0 - s0) * 0.01, (e1 - s0) * 0.01);
 		}
-		(void)hipFree(a.dbg);
 	}
 }
 

@@ -45,13 +45,10 @@ constexpr int W_NW = 4;
 constexpr int W_IMG_X = 0, W_IMG_H0 = 4096, W_IMG_H1 = 12288, W_IMG_DH1 = 20480, W_IMG_DH0 = 28672, W_IMG_DY = 36864;
 constexpr int W_WAVE_BYTES = 37 * 1024;
 constexpr int W_LDS_BYTES = W_NW * W_WAVE_BYTES; // 151 552
-// fragment slots (R32Frags of 64 -> 128 -> 128 -> 16)
-constexpr int WF0 = 0, WF1 = 16, WFO = 48, WBO = 56, WB1 = 60, WB0 = 92, W_NFRAGS = 108;
-
-__device__ inline void mfma32_acc(f16v& acc, const h8 a, const h8 b) { asm("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b)); }
-__device__ inline void mfma16_acc(f4& acc, const h8 a, const h8 b) { asm("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b)); }
-
-#define W_SB() __builtin_amdgcn_sched_barrier(0)
+// fragment slots of 64 -> 128 -> 128 -> 16 (mlp_side_jobs.h)
+typedef R32Slots<64, 128> WS;
+constexpr int WF0 = WS::F0, WF1 = WS::F1, WFO = WS::FO, WBO = WS::BO, WB1 = WS::B1, WB0 = WS::B0, W_NFRAGS = WS::N;
+static_assert(W_NFRAGS == 108, "");
 
 // LOSS 1: L2, 2: RelativeL2
 template <int LOSS>
@@ -72,41 +69,14 @@ __global__ void __launch_bounds__(W_NW * 64, 1) k_mlp_train_r32w(const WArgs a) 
 	// weight fragment f: one 16-byte load per lane from the image (L2-resident: 108 KiB read by every wave of the chip)
 	auto frag = [&](const int f) -> h8 { return a.image[f * 64 + lane]; };
 
-	// images of wave v: see k_train_r32.hip (per 32-feature tile 2 KiB: plane g of 4 features at 256 g, sample n at 8 ((n + 4 g) & 31))
+	// images of wave v (layout and lane maps w_chain, w_nat, r_tr, r_16: r32_device.h), all maps relative to a tile
 	const uint32_t wbase = wave * W_WAVE_BYTES;
-	uint32_t w_chain[4], w_nat[4];
-#pragma unroll
-	for (int k = 0; k < 4; ++k) {
-		const uint32_t gc = 4 * (k >> 1) + 2 * (k & 1) + h, gn = 4 * (k >> 1) + 2 * h + (k & 1);
-		w_chain[k] = gc * 256 + ((c + 4 * gc) & 31) * 8;
-		w_nat[k] = gn * 256 + ((c + 4 * gn) & 31) * 8;
-	}
-	uint32_t r_tr[4], r_16[4]; // transposing reads, relative to a tile (32x32x16 operand) / to the two halves of a tile (16x16x32 operand)
-	{
-		const uint32_t grp = lane >> 4, li = lane & 15, q = li >> 2, p = li & 3, hh = grp >> 1;
-		const uint32_t g = 4 * (grp & 1) + p;
-#pragma unroll
-		for (int k = 0; k < 4; ++k) {
-			const uint32_t row = 16 * (k >> 1) + 8 * hh + 4 * (k & 1) + q;
-			r_tr[k] = g * 256 + ((row + 4 * g) & 31) * 8;
-			const uint32_t g16 = 4 * (k >> 1) + p, row16 = 8 * grp + 4 * (k & 1) + q;
-			r_16[k] = g16 * 256 + ((row16 + 4 * g16) & 31) * 8;
-		}
-	}
+	R32_IMAGE_MAPS(0, 0);
 	auto img_write = [&](const uint32_t img, const uint32_t (&w)[4], const int s, const h8 v) { // img: byte offset of the tile in LDS
-		*(h4*)(smem + img + w[2 * s + 0]) = h4{v[0], v[1], v[2], v[3]};
-		*(h4*)(smem + img + w[2 * s + 1]) = h4{v[4], v[5], v[6], v[7]};
+		r32_img_write(smem, img + w[2 * s + 0], img + w[2 * s + 1], v);
 	};
-	auto img_own = [&](const uint32_t img, const int s) -> h8 {
-		const h4 lo = *(const h4*)(smem + img + w_chain[2 * s + 0]), hi = *(const h4*)(smem + img + w_chain[2 * s + 1]);
-		return h8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-	};
-	auto tr2 = [&](const uint32_t a0, const uint32_t a1) -> h8 {
-		const h4 lo = lds_read_tr((const half_t*)(smem + a0)), hi = lds_read_tr((const half_t*)(smem + a1));
-		return h8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-	};
-	auto tr_frag = [&](const uint32_t img, const int sp) -> h8 { return tr2(img + r_tr[2 * sp], img + r_tr[2 * sp + 1]); };
-	auto tr_frag16 = [&](const uint32_t img, const int half) -> h8 { return tr2(img + r_16[2 * half], img + r_16[2 * half + 1]); };
+	auto tr_frag = [&](const uint32_t img, const int sp) -> h8 { return r32_img_read_tr(smem, img + r_tr[2 * sp], img + r_tr[2 * sp + 1]); };
+	auto tr_frag16 = [&](const uint32_t img, const int half) -> h8 { return r32_img_read_tr(smem, img + r_16[2 * half], img + r_16[2 * half + 1]); };
 
 	const uint32_t x_off = (2 * h * a.n + c) * 8;  // input planes: levels 4 s + 2 h + i at + (4 s + i) n 8
 	const uint32_t row_off = c * 32 + h * 16;      // [n][16] halves: this lane's half of the row; [n][16] floats: twice that
@@ -152,7 +122,7 @@ __global__ void __launch_bounds__(W_NW * 64, 1) k_mlp_train_r32w(const WArgs a) 
 			for (int tp = 0; tp < 2; ++tp) { // two row tiles per group of eight fragments
 #pragma unroll
 				for (int k = 0; k < 8; ++k) wg[k] = tp == 0 ? frag(WF0 + 8 + k) : frag(WF1 + k);
-				W_SB();
+				R32_SB();
 #pragma unroll
 				for (int tt = 0; tt < 2; ++tt) {
 					const int t = 2 * tp + tt;
@@ -166,7 +136,7 @@ __global__ void __launch_bounds__(W_NW * 64, 1) k_mlp_train_r32w(const WArgs a) 
 				}
 #pragma unroll
 				for (int k = 0; k < 8; ++k) wf[k] = wg[k];
-				W_SB();
+				R32_SB();
 			}
 			// wf = layer 1, row tile 0
 			h8 h1[8];
@@ -174,7 +144,7 @@ __global__ void __launch_bounds__(W_NW * 64, 1) k_mlp_train_r32w(const WArgs a) 
 			for (int t = 0; t < 4; ++t) {
 #pragma unroll
 				for (int k = 0; k < 8; ++k) wg[k] = t < 3 ? frag(WF1 + 8 * (t + 1) + k) : frag(WFO + k);
-				W_SB();
+				R32_SB();
 				f16v acc = mfma32(wf[0], h0[0], Z);
 #pragma unroll
 				for (int ks = 1; ks < 8; ++ks) acc = mfma32(wf[ks], h0[ks], acc);
@@ -184,61 +154,26 @@ __global__ void __launch_bounds__(W_NW * 64, 1) k_mlp_train_r32w(const WArgs a) 
 				img_write(wbase + W_IMG_H1 + 2048 * t, w_chain, 1, h1[2 * t + 1]);
 #pragma unroll
 				for (int k = 0; k < 8; ++k) wf[k] = wg[k];
-				W_SB();
+				R32_SB();
 			}
 			// wf = output layer
 #pragma unroll
 			for (int k = 0; k < 4; ++k) wg[k] = frag(WBO + k);
-			W_SB();
+			R32_SB();
 			f16v o = mfma32(wf[0], h1[0], Z);
 #pragma unroll
 			for (int ks = 1; ks < 8; ++ks) o = mfma32(wf[ks], h1[ks], o);
 #pragma unroll
 			for (int k = 0; k < 8; ++k) wf[k] = frag(WB1 + k);
-			W_SB();
+			R32_SB();
 
 			// ------------------------------------------------------------------------------------------------ loss, context matrices, out
 			const h8 ov = pack8(o, 0); // element g: output 2 g + h
-			h8 dyf = h8{0, 0, 0, 0, 0, 0, 0, 0};
-			{
-				float value[2];
-				half_t grad[2];
-#pragma unroll
-				for (int r = 0; r < 2; ++r) {
-					loss_l2_fused<LOSS == 2>((float)ov[r], tg[r], lsc, value[r], grad[r]); // l2.h:40-74 / relative_l2.h:40-75 on one refined reciprocal (mlp_device.h)
-					const bool live = 2 * r + h < a.dims;
-					if (!live) { value[r] = 0.0f; grad[r] = (half_t)0.0f; }
-					dyf[r] = grad[r];
-				}
-				typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-				const uint32_t gpk = __builtin_bit_cast(uint32_t, (h2{grad[0], grad[1]}));
-				const auto sg = __builtin_amdgcn_permlane32_swap(gpk, gpk, false, false);
-				const auto s0 = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, value[0]), __builtin_bit_cast(uint32_t, value[0]), false, false);
-				const auto s1 = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, value[1]), __builtin_bit_cast(uint32_t, value[1]), false, false);
-				u32x4 grow = u32x4{0, 0, 0, 0}, l0 = u32x4{0, 0, 0, 0};
-				if (h == 0) {
-					grow[0] = __builtin_amdgcn_perm(sg[1], sg[0], 0x05040100u);
-					grow[1] = __builtin_amdgcn_perm(sg[1], sg[0], 0x07060302u);
-					l0 = u32x4{s0[0], s0[1], s1[0], s1[1]};
-				}
-				*(u32x4*)((char*)a.dL_dout + (size_t)blk * 1024 + row_off) = grow;
-				float* lrow = (float*)((char*)a.L + (size_t)blk * 2048 + 2 * row_off);
-				*(u32x4*)lrow = l0;
-				*(u32x4*)(lrow + 4) = u32x4{0, 0, 0, 0};
-			}
-			{
-				const u32x4 u = __builtin_bit_cast(u32x4, ov);
-				uint32_t w[4];
-#pragma unroll
-				for (int k = 0; k < 2; ++k) {
-					const auto sw = __builtin_amdgcn_permlane32_swap(u[k], u[k + 2], false, false);
-					w[2 * k + 0] = __builtin_amdgcn_perm(sw[1], sw[0], 0x05040100u);
-					w[2 * k + 1] = __builtin_amdgcn_perm(sw[1], sw[0], 0x07060302u);
-				}
-				*(u32x4*)((char*)a.out + (size_t)blk * 1024 + row_off) = u32x4{w[0], w[1], w[2], w[3]};
-			}
+			R32_LOSS_PADDED(dyf, LOSS == 2, ov, tg);
+			R32_OUT_ROW(orow, ov);
+			*(u32x4*)((char*)a.out + (size_t)blk * 1024 + row_off) = orow;
 			img_write(wbase + W_IMG_DY, w_chain, 0, dyf);
-			W_SB();
+			R32_SB();
 
 			// ------------------------------------------------------------------------------------------------ backward chain
 			// dH1 = (Wout^T dY) act'(H1) (common_device.h:241-297: from the forward OUTPUT)
@@ -257,7 +192,7 @@ __global__ void __launch_bounds__(W_NW * 64, 1) k_mlp_train_r32w(const WArgs a) 
 			for (int t = 0; t < 4; ++t) {
 #pragma unroll
 				for (int k = 0; k < 8; ++k) wg[k] = t < 3 ? frag(WB1 + 8 * (t + 1) + k) : frag(WB0 + k);
-				W_SB();
+				R32_SB();
 				f16v acc = mfma32(wf[0], d1[0], Z);
 #pragma unroll
 				for (int ks = 1; ks < 8; ++ks) acc = mfma32(wf[ks], d1[ks], acc);
@@ -267,7 +202,7 @@ __global__ void __launch_bounds__(W_NW * 64, 1) k_mlp_train_r32w(const WArgs a) 
 				img_write(wbase + W_IMG_DH0 + 2048 * t, w_chain, 1, d0[2 * t + 1]);
 #pragma unroll
 				for (int k = 0; k < 8; ++k) wf[k] = wg[k];
-				W_SB();
+				R32_SB();
 			}
 			// dX = W0^T dH0 -> level planes of 4 features: registers 4 g .. 4 g + 3 of row tile ti are features 32 ti + 8 g + 4 h .. + 3 = level 8 ti + 2 g + h
 #pragma unroll
@@ -276,7 +211,7 @@ __global__ void __launch_bounds__(W_NW * 64, 1) k_mlp_train_r32w(const WArgs a) 
 #pragma unroll
 					for (int k = 0; k < 8; ++k) wg[k] = frag(WB0 + 8 + k);
 				}
-				W_SB();
+				R32_SB();
 				f16v acc = mfma32(wf[0], d0[0], Z);
 #pragma unroll
 				for (int ks = 1; ks < 8; ++ks) acc = mfma32(wf[ks], d0[ks], acc);
@@ -289,7 +224,7 @@ __global__ void __launch_bounds__(W_NW * 64, 1) k_mlp_train_r32w(const WArgs a) 
 				*(u2*)(db + (size_t)n8 * 6) = u2{hi[2], hi[3]};
 #pragma unroll
 				for (int k = 0; k < 8; ++k) wf[k] = wg[k];
-				W_SB();
+				R32_SB();
 			}
 		} else {
 			// no block for this wave in the last trip: images of zeros make its share of every product vanish
@@ -363,7 +298,6 @@ __global__ void __launch_bounds__(W_NW * 64, 1) k_mlp_train_r32w(const WArgs a) 
 	}
 	if (a.dbg && tid == 0) a.dbg[blockIdx.x * 4 + 3] = __builtin_readcyclecounter();
 }
-#undef W_SB
 
 } // namespace
 
@@ -395,22 +329,13 @@ void r32w_launch(hipStream_t stream, const MlpDesc& d, const MlpTrainPlan& p, co
 	a.n_params = in.n_params;
 	for (int l = 0; l < 3; ++l) a.w_off[l] = d.layers[l].w_off;
 	a.loss_scale = in.loss_scale;
-#ifdef TCNN_AMD_DEV // laboratory build (build.py --dev): in-kernel clocks of the 5th launch
-	static const bool timing = getenv("TCNN_AMD_MLP_TIMING") != nullptr;
-	static int timing_left = 5;
-	if (timing && timing_left > 0) {
-		HIP_CHECK_THROW(hipMalloc(&a.dbg, (size_t)grid * 32));
-		HIP_CHECK_THROW(hipMemset(a.dbg, 0, (size_t)grid * 32));
-	}
-#else
-	int timing_left = 0; (void)timing_left;
-#endif
+	static DevClocks clocks; // (laboratory build)
+	a.dbg = clocks.alloc((size_t)grid * 32);
 	if (p.request.loss == LossType::L2) launch_with_lds(k_mlp_train_r32w<1>, stream, grid, W_NW * 64, W_LDS_BYTES, a);
 	else launch_with_lds(k_mlp_train_r32w<2>, stream, grid, W_NW * 64, W_LDS_BYTES, a);
-	if (a.dbg) {
-		std::vector<unsigned long long> hst((size_t)grid * 4);
-		HIP_CHECK_THROW(hipMemcpy(hst.data(), a.dbg, hst.size() * 8, hipMemcpyDeviceToHost));
-		if (--timing_left == 0) {
+	{
+		std::vector<unsigned long long> hst(a.dbg ? (size_t)grid * 4 : 0);
+		if (clocks.fetch(a.dbg, hst.data(), hst.size())) {
 			double loop = 0, tail = 0;
 			for (uint32_t g = 0; g < grid; ++g) {
 				loop += (double)(hst[g * 4 + 2] - hst[g * 4]);
@@ -419,7 +344,6 @@ void r32w_launch(hipStream_t stream, const MlpDesc& d, const MlpTrainPlan& p, co
 			fprintf(stderr, "k_mlp_train_r32w wave 0 clocks, mean over %u workgroups: trips %.0f (%u blocks of 32 per wave) slab stores %.0f\n", grid, loop / grid,
 			        div_round_up(n / 32, grid * W_NW), tail / grid);
 		}
-		(void)hipFree(a.dbg);
 	}
 }
 

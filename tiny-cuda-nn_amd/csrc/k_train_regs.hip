@@ -94,21 +94,7 @@ template <int ACT> __device__ inline h4 act_bwd_tile(const h4 g, const h4 fwd) {
 		return g;
 	}
 }
-// loads / stores at 32-bit byte offsets from wave-uniform bases (saddr + voffset addressing; regs_shape caps n)
-template <typename V> __device__ inline V ld32(const void* base, const uint32_t byte_off) { return *(const V*)((const char*)base + byte_off); }
-template <typename V> __device__ inline void st32(void* base, const uint32_t byte_off, const V v) { *(V*)((char*)base + byte_off) = v; }
-// the same as a streaming store, for data nobody on the GPU reads soon (the step's outputs: out, dL_doutput, L): it leaves this
-// XCD's L2 as it is written instead of waiting there, dirty, for the write-back at the end of the kernel.  NOT for the scatter
-// records: measured on C3a, streamed records cost the scatter 10 us (it finds them in the caches otherwise) for 1.4 us gained here.
-template <typename V> __device__ inline void st32_stream(void* base, const uint32_t byte_off, const V v) {
-	typedef uint32_t nt2 __attribute__((ext_vector_type(2)));
-	typedef uint32_t nt4 __attribute__((ext_vector_type(4)));
-	char* p = (char*)base + byte_off;
-	if constexpr (sizeof(V) == 16) __builtin_nontemporal_store(__builtin_bit_cast(nt4, v), (nt4*)p);
-	else if constexpr (sizeof(V) == 8) __builtin_nontemporal_store(__builtin_bit_cast(nt2, v), (nt2*)p);
-	else if constexpr (sizeof(V) == 4) __builtin_nontemporal_store(__builtin_bit_cast(uint32_t, v), (uint32_t*)p);
-	else __builtin_nontemporal_store(__builtin_bit_cast(uint16_t, v), (uint16_t*)p);
-}
+// (loads / stores at 32-bit byte offsets -- ld32, st32, st32_stream: mlp_device.h)
 
 // FAST: the common case with every format decision made at compile time -- input as level planes of 2 features, at most 4 outputs,
 // no data_pdf, `out` and scatter records {x, y, two levels} written.  Not for speed of the decisions themselves: vmcnt retires in
@@ -643,24 +629,15 @@ void regs_launch(hipStream_t stream, const MlpDesc& d, const MlpTrainPlan& p, co
 	           in.dx_record_x, n, r.dims, r.dx_record_dims, r.x_plane_features, r.dx_plane_features, in.n_params, in.loss_scale, 1u, nullptr};
 	a.prio_mode = switches().mlp_prio;
 	const int loss_id = r.external_dL_dy ? 0 : (r.loss == LossType::L2 ? 1 : 2);
-#ifdef TCNN_AMD_DEV // laboratory build (build.py --dev): in-kernel clocks of the 5th launch
-	static const bool timing = getenv("TCNN_AMD_MLP_TIMING") != nullptr;
-	static int timing_left = 5;
-	if (timing && timing_left > 0) {
-		HIP_CHECK_THROW(hipMalloc(&a.dbg, (size_t)grid * (32 + 8 * REGS_NW + 64)));
-		HIP_CHECK_THROW(hipMemset(a.dbg, 0, (size_t)grid * (32 + 8 * REGS_NW + 64)));
-	}
-#else
-	int timing_left = 0; (void)timing_left;
-#endif
+	static DevClocks clocks; // (laboratory build)
+	a.dbg = clocks.alloc((size_t)grid * (32 + 8 * REGS_NW + 64));
 	if (p.regs_in_tiles == 2 && p.regs_hidden == 2) launch_regs<2, 2>(stream, d, a, grid, loss_id, p.regs_fast);
 	else if (p.regs_in_tiles == 1 && p.regs_hidden == 2) launch_regs<1, 2>(stream, d, a, grid, loss_id, p.regs_fast);
 	else if (p.regs_in_tiles == 2 && p.regs_hidden == 1) launch_regs<2, 1>(stream, d, a, grid, loss_id, p.regs_fast);
 	else launch_regs<1, 1>(stream, d, a, grid, loss_id, p.regs_fast);
-	if (a.dbg) {
-		std::vector<unsigned long long> h((size_t)grid * (4 + REGS_NW + 8));
-		HIP_CHECK_THROW(hipMemcpy(h.data(), a.dbg, h.size() * 8, hipMemcpyDeviceToHost));
-		if (--timing_left == 0) {
+	{
+		std::vector<unsigned long long> h(a.dbg ? (size_t)grid * (4 + REGS_NW + 8) : 0);
+		if (clocks.fetch(a.dbg, h.data(), h.size())) {
 			double fill = 0, loop = 0, tail = 0, skew = 0;
 			for (uint32_t g = 0; g < grid; ++g) { // last wave's loop end - first wave's loop end
 				const unsigned long long* e = h.data() + (size_t)grid * 4 + (size_t)g * REGS_NW;
@@ -690,7 +667,6 @@ void regs_launch(hipStream_t stream, const MlpDesc& d, const MlpTrainPlan& p, co
 				for (int i = 0; i < 5; ++i) p[i] += (double)h[(size_t)grid * (4 + REGS_NW) + (size_t)g * 8 + i];
 			if (p[0] > 0) fprintf(stderr, "  phases (wave 0, summed over its trips): forward %.0f output+loss %.0f dWout %.0f backward+dW %.0f dX+stores %.0f\n", p[0] / grid, p[1] / grid, p[2] / grid, p[3] / grid, p[4] / grid);
 		}
-		(void)hipFree(a.dbg);
 	}
 }
 

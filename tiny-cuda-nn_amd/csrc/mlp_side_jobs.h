@@ -36,6 +36,12 @@ struct R32Frags {
 	__host__ __device__ uint32_t bwd0() const { return bwd_out() + wt + (nh - 1) * wt * ksw; }
 	__host__ __device__ uint32_t n_frags() const { return bwd0() + it * ksw; }
 };
+// The same slots as compile-time constants, for the kernels written for one network IN -> W -> W -> 16 (k_train_r32*.hip):
+// F0, F1, FO = fwd0, fwd_hidden(1), fwd_out; BO, B1, B0 = bwd_out, bwd_hidden(1), bwd0; N = n_frags
+template <int IN, int W> struct R32Slots {
+	static constexpr int WT = W / 32, KS0 = IN / 16, KSW = W / 16;
+	static constexpr int F0 = 0, F1 = WT * KS0, FO = F1 + WT * KSW, BO = FO + KSW, B1 = BO + WT, B0 = B1 + WT * KSW, N = B0 + ((IN + 31) / 32) * KSW;
+};
 // networks that get the section: (16 | 32 | 128) -> 64 -> [64 ->] 16 and 64 -> 128 -> 128 -> 16
 __host__ __device__ inline bool r32_shape_ok(const MlpDesc& d) {
 	if (d.out_width != 16 || d.n_hidden < 1 || d.n_hidden > 2) return false;
