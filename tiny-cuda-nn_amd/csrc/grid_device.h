@@ -33,12 +33,9 @@ __device__ inline uint32_t pos_fract(float input, float scale, uint32_t interpol
 	return cell;
 }
 
-// pcg32 pieces needed by HashType::Rng (common_device.h:663-676)
-__device__ inline uint32_t rng_hash_device(const uint32_t* pos, int n_dims) {
+// pcg32{1337} (default stream 1) after advance(step): the generator's state (pcg32.h:145-166), shared by HashType::Rng and random_val
+__device__ inline uint64_t pcg32_1337_advanced(uint64_t step) {
 	const uint64_t MULT = 0x5851f42d4c957f2dULL;
-	const uint32_t bits_per_dim = 64 / n_dims;
-	uint64_t step = 0;
-	for (int i = 0; i < n_dims; ++i) step ^= (uint64_t)pos[i] << (i * bits_per_dim);
 	// pcg32{1337}: seed()
 	uint64_t inc = (1ull << 1u) | 1u;
 	uint64_t state = 0;
@@ -57,12 +54,35 @@ __device__ inline uint32_t rng_hash_device(const uint32_t* pos, int n_dims) {
 		cur_mult *= cur_mult;
 		delta /= 2;
 	}
-	state = acc_mult * state + acc_plus;
-	// next_uint()
-	const uint64_t old = state;
+	return acc_mult * state + acc_plus;
+}
+// next_uint()'s output for the state it starts from (pcg32.h:72-78)
+__device__ inline uint32_t pcg32_output(uint64_t old) {
 	const uint32_t xorshifted = (uint32_t)(((old >> 18u) ^ old) >> 27u);
 	const uint32_t rot = (uint32_t)(old >> 59u);
 	return (xorshifted >> rot) | (xorshifted << ((~rot + 1u) & 31));
+}
+
+// pcg32 pieces needed by HashType::Rng (common_device.h:663-676)
+__device__ inline uint32_t rng_hash_device(const uint32_t* pos, int n_dims) {
+	const uint32_t bits_per_dim = 64 / n_dims;
+	uint64_t step = 0;
+	for (int i = 0; i < n_dims; ++i) step ^= (uint64_t)pos[i] << (i * bits_per_dim);
+	return pcg32_output(pcg32_1337_advanced(step));
+}
+
+// random_val(1337, idx) (common_device.h:333-337): pcg32{1337}, advance(idx), next_float() -- 23 bits of next_uint() as a float in [0, 1)
+__device__ inline float grid_random_val(uint32_t idx) {
+	return __builtin_bit_cast(float, (pcg32_output(pcg32_1337_advanced(idx)) >> 9) | 0x3f800000u) - 1.0f;
+}
+
+// stochastic_interpolation (grid.h:284-298): sample i of a batch of n puts dL/dy of level `level` on ONE corner of its cell, weight 1 --
+// one draw decides every dimension.  pos: pos_fract's fractions (smoothstepped where the grid is); the index i + level * n wraps in uint32.
+template <int D>
+__device__ inline void stochastic_corner(uint32_t i, uint32_t level, uint32_t n, const float (&pos)[D], const uint32_t (&cell)[D], uint32_t (&local)[D]) {
+	const float sample = grid_random_val(i + level * n);
+#pragma unroll
+	for (int d = 0; d < D; ++d) local[d] = sample >= pos[d] ? cell[d] : cell[d] + 1;
 }
 
 // grid_index (common_device.h:690-707) with the stride loop folded into GridLevel::stride / ::hashed on the host

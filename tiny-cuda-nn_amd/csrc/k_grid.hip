@@ -194,7 +194,8 @@ template <> __device__ inline void atomic_add_pair<half_t>(half_t* p, half_t a, 
 	unsafeAtomicAdd((__half2*)p, v);
 }
 
-template <typename T, typename GT, int D, int F>
+// STOCH: stochastic_interpolation (grid.h:284-298) -- one add per (sample, level, feature group): dL/dy with weight 1 onto the drawn corner
+template <typename T, typename GT, int D, int F, bool STOCH>
 __global__ void __launch_bounds__(256) k_grid_bwd(
 	const GridMeta* __restrict__ meta, const uint32_t n, const MatView x, const T* __restrict__ dL_dy, const uint32_t dy_stride, GT* __restrict__ grad
 ) {
@@ -239,6 +240,12 @@ __global__ void __launch_bounds__(256) k_grid_bwd(
 
 	if (interpolation == (uint32_t)InterpolationType::Nearest) {
 		add(cell, 1.0f);
+		return;
+	}
+	if constexpr (STOCH) {
+		uint32_t local[D];
+		stochastic_corner<D>(i, level, n, pos, cell, local);
+		add(local, 1.0f);
 		return;
 	}
 #pragma unroll
@@ -288,12 +295,13 @@ void launch_fwd(hipStream_t stream, const GridMeta* dev_meta, uint32_t n, MatVie
 }
 
 template <typename T, typename GT, int D, int F>
-void launch_bwd(hipStream_t stream, const GridMeta& meta, const GridMeta* dev_meta, uint32_t n, MatView x, const void* dL_dy, uint32_t dy_stride, void* grad) {
+void launch_bwd(hipStream_t stream, const GridMeta& meta, const GridMeta* dev_meta, uint32_t n, MatView x, const void* dL_dy, uint32_t dy_stride, void* grad, bool stochastic) {
 	const uint64_t total = (uint64_t)n * meta.n_levels;
 	CHECK_THROW(total < (1ull << 32));
 	const uint32_t blocks = (uint32_t)((total + 255) / 256);
 	if (blocks == 0) return;
-	hipLaunchKernelGGL((k_grid_bwd<T, GT, D, F>), dim3(blocks), dim3(256), 0, stream, dev_meta, n, x, (const T*)dL_dy, dy_stride, (GT*)grad);
+	if (stochastic) hipLaunchKernelGGL((k_grid_bwd<T, GT, D, F, true>), dim3(blocks), dim3(256), 0, stream, dev_meta, n, x, (const T*)dL_dy, dy_stride, (GT*)grad);
+	else hipLaunchKernelGGL((k_grid_bwd<T, GT, D, F, false>), dim3(blocks), dim3(256), 0, stream, dev_meta, n, x, (const T*)dL_dy, dy_stride, (GT*)grad);
 }
 
 template <typename T, int D>
@@ -308,14 +316,14 @@ void dispatch_fwd_F(hipStream_t s, uint32_t F, const GridMeta* dm, uint32_t n, M
 }
 
 template <typename T, typename GT, int D>
-void dispatch_bwd_F(hipStream_t s, const GridMeta& m, const GridMeta* dm, uint32_t n, MatView x, const void* dy, uint32_t ds, void* grad) {
+void dispatch_bwd_F(hipStream_t s, const GridMeta& m, const GridMeta* dm, uint32_t n, MatView x, const void* dy, uint32_t ds, void* grad, bool st) {
 	switch (m.n_features_per_level) {
 		case 1:
-			if constexpr (sizeof(GT) == 4) return launch_bwd<T, GT, D, 1>(s, m, dm, n, x, dy, ds, grad);
+			if constexpr (sizeof(GT) == 4) return launch_bwd<T, GT, D, 1>(s, m, dm, n, x, dy, ds, grad, st);
 			else throw std::runtime_error{"GridEncoding: F == 1 accumulates gradients in fp32"};
-		case 2: return launch_bwd<T, GT, D, 2>(s, m, dm, n, x, dy, ds, grad);
-		case 4: return launch_bwd<T, GT, D, 4>(s, m, dm, n, x, dy, ds, grad);
-		case 8: return launch_bwd<T, GT, D, 8>(s, m, dm, n, x, dy, ds, grad);
+		case 2: return launch_bwd<T, GT, D, 2>(s, m, dm, n, x, dy, ds, grad, st);
+		case 4: return launch_bwd<T, GT, D, 4>(s, m, dm, n, x, dy, ds, grad, st);
+		case 8: return launch_bwd<T, GT, D, 8>(s, m, dm, n, x, dy, ds, grad, st);
 		default: throw std::runtime_error{"GridEncoding: n_features_per_level must be 1, 2, 4, or 8."};
 	}
 }
@@ -336,12 +344,13 @@ void grid_forward(hipStream_t stream, const GridMeta& meta, const GridMeta* dev_
 #undef TCNN_GRID_FWD
 }
 
-void grid_backward(hipStream_t stream, const GridMeta& meta, const GridMeta* dev_meta, bool fp32_grad, uint32_t n, MatView x, const void* dL_dy, bool dy_fp32, uint32_t dy_stride, void* grad) {
+void grid_backward(hipStream_t stream, const GridMeta& meta, const GridMeta* dev_meta, bool fp32_grad, uint32_t n, MatView x, const void* dL_dy, bool dy_fp32, uint32_t dy_stride, void* grad,
+                   bool stochastic) {
 #define TCNN_GRID_BWD(T, GT) \
 	switch (meta.n_pos_dims) { \
-		case 2: return dispatch_bwd_F<T, GT, 2>(stream, meta, dev_meta, n, x, dL_dy, dy_stride, grad); \
-		case 3: return dispatch_bwd_F<T, GT, 3>(stream, meta, dev_meta, n, x, dL_dy, dy_stride, grad); \
-		case 4: return dispatch_bwd_F<T, GT, 4>(stream, meta, dev_meta, n, x, dL_dy, dy_stride, grad); \
+		case 2: return dispatch_bwd_F<T, GT, 2>(stream, meta, dev_meta, n, x, dL_dy, dy_stride, grad, stochastic); \
+		case 3: return dispatch_bwd_F<T, GT, 3>(stream, meta, dev_meta, n, x, dL_dy, dy_stride, grad, stochastic); \
+		case 4: return dispatch_bwd_F<T, GT, 4>(stream, meta, dev_meta, n, x, dL_dy, dy_stride, grad, stochastic); \
 		default: throw std::runtime_error{"GridEncoding: number of input dims must be 2 or 3."}; \
 	}
 	if (dy_fp32) {

@@ -48,14 +48,22 @@ struct BinArgs {
 __device__ inline void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // corners of one sample in the reference's order (grid.h:232-260), weights formed exactly as k_grid_fwd / k_grid_scatter form them
-template <int D, typename Fn>
-__device__ inline void for_each_corner(const GridLevel& lv, const uint32_t (&primes)[D], const uint32_t hash_type, const uint32_t interpolation, const float (&xin)[D], Fn&& fn) {
+// STOCH: stochastic_interpolation (grid.h:284-298) -- the one corner drawn for sample i of n on this level, weight 1 (stochastic_corner, grid_device.h)
+template <int D, bool STOCH, typename Fn>
+__device__ inline void for_each_corner(const GridLevel& lv, const uint32_t (&primes)[D], const uint32_t hash_type, const uint32_t interpolation, const float (&xin)[D],
+                                       const uint32_t i, const uint32_t level, const uint32_t n, Fn&& fn) {
 	float pos[D], unused;
 	uint32_t cell[D];
 #pragma unroll
 	for (int d = 0; d < D; ++d) cell[d] = pos_fract(xin[d], lv.scale, interpolation, &pos[d], &unused);
 	if (interpolation == (uint32_t)InterpolationType::Nearest) {
 		fn(level_index<D>(lv, primes, hash_type, cell), 1.0f);
+		return;
+	}
+	if constexpr (STOCH) {
+		uint32_t local[D];
+		stochastic_corner<D>(i, level, n, pos, cell, local);
+		fn(level_index<D>(lv, primes, hash_type, local), 1.0f);
 		return;
 	}
 #pragma unroll
@@ -84,11 +92,12 @@ __device__ inline uint32_t tile_of_block(const uint32_t b, const uint32_t n_tile
 	return (b & 7u) * (n_tiles / 8) + (b >> 3);
 }
 
-template <int D>
+template <int D, bool STOCH>
 __global__ void __launch_bounds__(BIN_COUNT_THREADS) k_bin_count(const BinArgs a, const MatView x, uint32_t* __restrict__ counts) {
 	__shared__ uint32_t hist[BIN_MAX_CHUNKS];
 	const uint32_t tid = threadIdx.x, slot = blockIdx.y, tile = tile_of_block(blockIdx.x, a.n_tiles);
-	const GridLevel lv = a.meta->levels[a.level_of_slot[slot]];
+	const uint32_t level = a.level_of_slot[slot];
+	const GridLevel lv = a.meta->levels[level];
 	const uint32_t n_chunks = lv.scatter_n_chunks;
 	for (uint32_t c = tid; c < n_chunks; c += BIN_COUNT_THREADS) hist[c] = 0;
 	__syncthreads();
@@ -100,7 +109,7 @@ __global__ void __launch_bounds__(BIN_COUNT_THREADS) k_bin_count(const BinArgs a
 	for (uint32_t i = s0 + tid; i < s1; i += BIN_COUNT_THREADS) {
 		float xin[D];
 		load_coords<D>(x, i, xin);
-		for_each_corner<D>(lv, primes, hash_type, interpolation, xin, [&](const uint32_t index, float) {
+		for_each_corner<D, STOCH>(lv, primes, hash_type, interpolation, xin, i, level, a.n, [&](const uint32_t index, float) {
 			__hip_atomic_fetch_add((__attribute__((address_space(3))) uint32_t*)&hist[scatter_chunk(lv, index)], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 		});
 	}
@@ -169,7 +178,7 @@ __global__ void __launch_bounds__(1024) k_bin_scan_chunks(const BinArgs a, const
 	}
 }
 
-template <int D, int F>
+template <int D, int F, bool STOCH>
 __global__ void __launch_bounds__(BIN_FILL_THREADS) k_bin_fill(
 	const BinArgs a, const MatView x, const half_t* __restrict__ dL_dy, const uint32_t dy_stride_sample, const uint32_t dy_stride_level,
 	const uint32_t* __restrict__ counts, const uint32_t* __restrict__ rel, const uint32_t* __restrict__ base, uint16_t* __restrict__ out_idx, half_t* __restrict__ out_val
@@ -233,7 +242,7 @@ __global__ void __launch_bounds__(BIN_FILL_THREADS) k_bin_fill(
 		float xin[D];
 		load_coords<D>(x, i, xin);
 		const vecF gv = *(const vecF*)&dy[(size_t)i * dy_stride_sample];
-		for_each_corner<D>(lv, primes, hash_type, interpolation, xin, [&](const uint32_t index, const float weight) {
+		for_each_corner<D, STOCH>(lv, primes, hash_type, interpolation, xin, i, level, a.n, [&](const uint32_t index, const float weight) {
 			const uint32_t chunk = scatter_chunk(lv, index);
 			const uint32_t entry = index - chunk * lv.scatter_per_chunk;
 			const uint32_t at = __hip_atomic_fetch_add((lds_u32*)&s_cursor[chunk], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -478,13 +487,13 @@ struct BinLayout {
 	size_t counts_off = 0, rel_off = 0, totals_off = 0, base_off = 0, idx_off = 0, val_off = 0, bytes = 0;
 };
 
-BinLayout bin_layout(const GridMeta& meta, const GridMeta* dev_meta, uint32_t n) {
+BinLayout bin_layout(const GridMeta& meta, const GridMeta* dev_meta, uint32_t n, bool stochastic = false) {
 	BinLayout l{};
 	BinArgs& a = l.args;
 	a.meta = dev_meta;
 	a.n = n;
 	const bool nearest = meta.interpolation == (uint32_t)InterpolationType::Nearest;
-	a.per_sample = nearest ? 1u : (1u << meta.n_pos_dims);
+	a.per_sample = (nearest || stochastic) ? 1u : (1u << meta.n_pos_dims); // (stochastic: the one drawn corner)
 	a.tile_contribs = BIN_TILE_CONTRIBS;
 	if (meta.n_features_per_level == 8) a.tile_contribs = BIN_TILE_CONTRIBS / 2; // (20 bytes per contribution in k_bin_fill's LDS instead of 12: half the tile)
 	if (const char* e = getenv("TCNN_AMD_BIN_TILE")) a.tile_contribs = std::min<uint32_t>(std::max(atoi(e), 512), a.tile_contribs); // A/B runs
@@ -514,7 +523,7 @@ BinLayout bin_layout(const GridMeta& meta, const GridMeta* dev_meta, uint32_t n)
 	return l;
 }
 
-template <int D, int F>
+template <int D, int F, bool STOCH>
 void launch_binned(hipStream_t s, const BinLayout& l, MatView x, const void* dy, uint32_t dss, uint32_t dsl, void* grad, bool accumulate, char* ws, uint32_t* fallback_count) {
 	const BinArgs& a = l.args;
 	uint32_t* counts = (uint32_t*)(ws + l.counts_off);
@@ -526,14 +535,14 @@ void launch_binned(hipStream_t s, const BinLayout& l, MatView x, const void* dy,
 	const uint32_t fill_lds = a.tile_contribs * (F * 2 + 4) + 3 * a.stride * 4;
 	static bool configured = false;
 	if (!configured) { // more than 64 KiB of dynamic LDS has to be opted into once per kernel
-		HIP_CHECK_THROW(hipFuncSetAttribute((const void*)k_bin_fill<D, F>, hipFuncAttributeMaxDynamicSharedMemorySize, (F == 8 ? BIN_TILE_CONTRIBS / 2 : BIN_TILE_CONTRIBS) * (F * 2 + 4) + 3 * BIN_MAX_CHUNKS * 4));
+		HIP_CHECK_THROW(hipFuncSetAttribute((const void*)k_bin_fill<D, F, STOCH>, hipFuncAttributeMaxDynamicSharedMemorySize, (F == 8 ? BIN_TILE_CONTRIBS / 2 : BIN_TILE_CONTRIBS) * (F * 2 + 4) + 3 * BIN_MAX_CHUNKS * 4));
 		HIP_CHECK_THROW(hipFuncSetAttribute((const void*)k_bin_accum<F>, hipFuncAttributeMaxDynamicSharedMemorySize, BIN_ACC_BYTES_MAX));
 		configured = true;
 	}
-	hipLaunchKernelGGL((k_bin_count<D>), dim3(a.n_tiles, l.n_slots), dim3(BIN_COUNT_THREADS), 0, s, a, x, counts);
+	hipLaunchKernelGGL((k_bin_count<D, STOCH>), dim3(a.n_tiles, l.n_slots), dim3(BIN_COUNT_THREADS), 0, s, a, x, counts);
 	hipLaunchKernelGGL(k_bin_scan_tiles, dim3(a.stride / 64, l.n_slots), dim3(1024), 0, s, a, counts, rel, totals);
 	hipLaunchKernelGGL(k_bin_scan_chunks, dim3(l.n_slots), dim3(1024), 0, s, a, totals, base);
-	hipLaunchKernelGGL((k_bin_fill<D, F>), dim3(a.n_tiles, l.n_slots), dim3(BIN_FILL_THREADS), fill_lds, s, a, x, (const half_t*)dy, dss, dsl, counts, rel, base, idx, val);
+	hipLaunchKernelGGL((k_bin_fill<D, F, STOCH>), dim3(a.n_tiles, l.n_slots), dim3(BIN_FILL_THREADS), fill_lds, s, a, x, (const half_t*)dy, dss, dsl, counts, rel, base, idx, val);
 	const uint32_t acc_bytes = grid_bin_acc_bytes();
 	const uint32_t acc_blocks = std::min(l.n_chunks_total, 256u * std::max(1u, (160u * 1024u) / (acc_bytes + 4096u)));
 	static const bool timing = getenv("TCNN_AMD_BIN_TIMING") != nullptr;
@@ -576,8 +585,9 @@ bool grid_bin_supported(const GridMeta& meta) {
 size_t grid_bin_workspace_bytes(const GridMeta& meta, uint32_t n) { return bin_layout(meta, nullptr, n).bytes; }
 
 void grid_backward_binned(hipStream_t stream, const GridMeta& meta, const GridMeta* dev_meta, uint32_t n, MatView x, const void* dL_dy, uint32_t dy_stride_sample,
-                          uint32_t dy_stride_level, void* grad, bool accumulate, void* workspace, uint32_t* fallback_count) {
-	const BinLayout l = bin_layout(meta, dev_meta, n);
+                          uint32_t dy_stride_level, void* grad, bool accumulate, void* workspace, uint32_t* fallback_count, bool stochastic) {
+	stochastic = stochastic && meta.interpolation != (uint32_t)InterpolationType::Nearest;
+	const BinLayout l = bin_layout(meta, dev_meta, n, stochastic); // (the workspace is sized for 2^D contributions per sample either way)
 	if (l.n_slots == 0 || n == 0) return;
 	CHECK_THROW(grid_bin_supported(meta) && workspace != nullptr);
 	CHECK_THROW(l.args.stride <= BIN_MAX_CHUNKS);
@@ -587,15 +597,17 @@ void grid_backward_binned(hipStream_t stream, const GridMeta& meta, const GridMe
 	}
 	const uint32_t F = meta.n_features_per_level;
 	char* ws = (char*)workspace;
-#define TCNN_BIN(D) \
-	if (F == 2) launch_binned<D, 2>(stream, l, x, dL_dy, dy_stride_sample, dy_stride_level, grad, accumulate, ws, fallback_count); \
-	else if (F == 4) launch_binned<D, 4>(stream, l, x, dL_dy, dy_stride_sample, dy_stride_level, grad, accumulate, ws, fallback_count); \
-	else launch_binned<D, 8>(stream, l, x, dL_dy, dy_stride_sample, dy_stride_level, grad, accumulate, ws, fallback_count);
+#define TCNN_BIN_F(D, S) \
+	if (F == 2) launch_binned<D, 2, S>(stream, l, x, dL_dy, dy_stride_sample, dy_stride_level, grad, accumulate, ws, fallback_count); \
+	else if (F == 4) launch_binned<D, 4, S>(stream, l, x, dL_dy, dy_stride_sample, dy_stride_level, grad, accumulate, ws, fallback_count); \
+	else launch_binned<D, 8, S>(stream, l, x, dL_dy, dy_stride_sample, dy_stride_level, grad, accumulate, ws, fallback_count);
+#define TCNN_BIN(D) if (stochastic) { TCNN_BIN_F(D, true) } else { TCNN_BIN_F(D, false) }
 	switch (meta.n_pos_dims) {
 		case 2: TCNN_BIN(2) break;
 		case 3: TCNN_BIN(3) break;
 		default: TCNN_BIN(4) break;
 	}
+#undef TCNN_BIN_F
 #undef TCNN_BIN
 }
 

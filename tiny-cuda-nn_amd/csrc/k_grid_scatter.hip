@@ -55,7 +55,10 @@ constexpr uint32_t SCATTER_MAX_CHUNKS = GRID_FILTER_MAX_CHUNKS; // bit planes pe
 
 // REC: dL_dy holds 16-byte records {D coordinates, gradient halves} written by the fused MLP kernel
 // (mlp_device.h store_dx_record; float4 [level][n], or [level / 2][n] where two levels fit one record): one gather per hit instead of two -- gathers cost ~2 clk per lane per CU whatever their width.
-template <int D, int F, bool REC>
+// STOCH: stochastic_interpolation (grid.h:284-298) -- a sample that reaches an owner brings ONE corner, drawn from its number and the level
+// (stochastic_corner, grid_device.h), and adds dL/dy itself where that corner lies in the owned chunk.  The bit planes still filter: the
+// drawn corner is one of the 2^D whose chunks the forward pass recorded.  Never with REC (grid_backward_route).
+template <int D, int F, bool REC, bool STOCH>
 __global__ void __launch_bounds__(SCATTER_THREADS) k_grid_scatter(
 	const GridMeta* __restrict__ meta, const GridScatterTask* __restrict__ tasks, const uint32_t n, const MatView x,
 	const half_t* __restrict__ dL_dy, const uint32_t dy_stride_sample, const uint32_t dy_stride_level, half_t* __restrict__ grad,
@@ -122,7 +125,8 @@ __global__ void __launch_bounds__(SCATTER_THREADS) k_grid_scatter(
 		}
 	};
 	// full treatment of one sample: recompute its corners, add those that fall into the owned chunk (grid.h:215-320)
-	auto accumulate = [&](const float (&xin)[D], const vecF& gv) {
+	// id: the sample's number (read by the stochastic form only)
+	auto accumulate = [&](const float (&xin)[D], const vecF& gv, const uint32_t id) {
 		float pos[D], unused;
 		uint32_t cell[D];
 #pragma unroll
@@ -144,6 +148,18 @@ __global__ void __launch_bounds__(SCATTER_THREADS) k_grid_scatter(
 
 		if (interpolation == (uint32_t)InterpolationType::Nearest) {
 			add(cell, 1.0f);
+			return;
+		}
+		if constexpr (STOCH) {
+			uint32_t local[D];
+			stochastic_corner<D>(id, task.level, n, pos, cell, local);
+			const uint32_t index = level_index<D>(lv, primes, hash_type, local) - task.entry_begin;
+			if (index < task.n_entries) {
+#pragma unroll
+				for (int f = 0; f < F; ++f) { // weight 1: the value added is dL/dy itself
+					__hip_atomic_fetch_add(acc_lds + index * F + f, (unsigned long long)half_to_fixed_fast(gv[f]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+				}
+			}
 			return;
 		}
 		// All 2^D corners are located first; then the wave adds "the next corner of mine that falls into the chunk" until no
@@ -194,13 +210,25 @@ __global__ void __launch_bounds__(SCATTER_THREADS) k_grid_scatter(
 	};
 
 	// the same for a task whose chunk is the whole level (coarse levels): every corner is ours, no test, no compaction
-	auto accumulate_whole = [&](const float (&xin)[D], const vecF& gv) {
+	auto accumulate_whole = [&](const float (&xin)[D], const vecF& gv, const uint32_t id) {
 		float pos[D], unused;
 		uint32_t cell[D];
 #pragma unroll
 		for (int d = 0; d < D; ++d) cell[d] = pos_fract(xin[d], lv.scale, interpolation, &pos[d], &unused);
 		constexpr int C = 1 << D;
 		const bool nearest = interpolation == (uint32_t)InterpolationType::Nearest; // grid.h:232-246: the cell's own entry, weight 1
+		if constexpr (STOCH) {
+			if (!nearest) {
+				uint32_t local[D];
+				stochastic_corner<D>(id, task.level, n, pos, cell, local);
+				const uint32_t index = level_index<D>(lv, primes, hash_type, local);
+#pragma unroll
+				for (int f = 0; f < F; ++f) {
+					__hip_atomic_fetch_add(acc_lds + index * F + f, (unsigned long long)half_to_fixed_fast(gv[f]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+				}
+				return;
+			}
+		}
 #pragma unroll
 		for (int idx = 0; idx < C; ++idx) {
 			if (idx > 0 && nearest) break;
@@ -240,9 +268,10 @@ __global__ void __launch_bounds__(SCATTER_THREADS) k_grid_scatter(
 	constexpr int SB = SCATTER_SUB_BATCHES;
 	float ax[SB][D], nx[SB][D];
 	vecF ag[SB], ng[SB];
+	uint32_t ai[SB]; // the samples' numbers (dead code unless STOCH)
 	bool a_valid[SB]; // per lane
 #pragma unroll
-	for (int s = 0; s < SB; ++s) a_valid[s] = false;
+	for (int s = 0; s < SB; ++s) a_valid[s] = false, ai[s] = 0;
 	unsigned long long t_fetch = 0, t_acc = 0, n_sub = 0; // development aid (TCNN_AMD_SCATTER_TIMING): shader clocks of wave 0
 	auto submit = [&](const uint32_t (&ids)[SB], const bool (&valid)[SB]) { // ids are in range for every lane (clamped by the caller)
 		const unsigned long long c0 = dbg_times ? __builtin_readcyclecounter() : 0;
@@ -250,7 +279,7 @@ __global__ void __launch_bounds__(SCATTER_THREADS) k_grid_scatter(
 		for (int s = 0; s < SB; ++s) fetch(ids[s], nx[s], ng[s]);
 		const unsigned long long c1 = dbg_times ? __builtin_readcyclecounter() : 0;
 #pragma unroll
-		for (int s = 0; s < SB; ++s) if (a_valid[s]) accumulate(ax[s], ag[s]);
+		for (int s = 0; s < SB; ++s) if (a_valid[s]) accumulate(ax[s], ag[s], ai[s]);
 		if (dbg_times) {
 			const unsigned long long c2 = __builtin_readcyclecounter();
 			t_fetch += c1 - c0;
@@ -262,6 +291,7 @@ __global__ void __launch_bounds__(SCATTER_THREADS) k_grid_scatter(
 #pragma unroll
 			for (int d = 0; d < D; ++d) ax[s][d] = nx[s][d];
 			ag[s] = ng[s];
+			ai[s] = ids[s];
 			a_valid[s] = valid[s];
 		}
 	};
@@ -272,17 +302,19 @@ __global__ void __launch_bounds__(SCATTER_THREADS) k_grid_scatter(
 			// the chunk is the whole level: every sample, every corner, in lockstep; one batch in flight while the previous one is added
 			float px[D], qx[D];
 			vecF pg, qg;
+			uint32_t pi = 0;
 			bool p_valid = false;
 			for (uint32_t blk = 0; blk < n_blocks; ++blk) {
 				const uint32_t i = w_begin + blk * 64 + lane;
 				fetch(min(i, w_end - 1), qx, qg);
-				if (p_valid) accumulate_whole(px, pg);
+				if (p_valid) accumulate_whole(px, pg, pi);
 #pragma unroll
 				for (int d = 0; d < D; ++d) px[d] = qx[d];
 				pg = qg;
+				pi = i;
 				p_valid = i < w_end;
 			}
-			if (p_valid) accumulate_whole(px, pg);
+			if (p_valid) accumulate_whole(px, pg, pi);
 		} else if (chunk_bits == nullptr) {
 			// no filter available: every sample gets the full treatment
 			for (uint32_t blk = 0; blk < n_blocks; blk += SB) {
@@ -353,7 +385,7 @@ __global__ void __launch_bounds__(SCATTER_THREADS) k_grid_scatter(
 			}
 		}
 #pragma unroll
-		for (int s = 0; s < SB; ++s) if (a_valid[s]) accumulate(ax[s], ag[s]);
+		for (int s = 0; s < SB; ++s) if (a_valid[s]) accumulate(ax[s], ag[s], ai[s]);
 	}
 	if (dbg_times && tid == 0) {
 		dbg_times[blockIdx.x * 8 + 4] = t_fetch;
@@ -433,12 +465,12 @@ __global__ void __launch_bounds__(256) k_grid_mask_to_bits(const GridMeta* __res
 // timestamps (slots 0..3: start / after zeroing / after accumulation / end, 100 MHz clock) -- input of the plan tuner
 thread_local unsigned long long* g_task_times = nullptr;
 
-template <int D, int F, bool REC = false>
+template <int D, int F, bool REC = false, bool STOCH = false>
 void launch_scatter(hipStream_t s, const GridMeta* dm, const GridScatterTask* tasks, uint32_t n_tasks, uint32_t n, MatView x, const void* dy, uint32_t dss, uint32_t dsl,
                     void* grad, const unsigned long long* chunk_bits, unsigned long long* scratch, bool accumulate) {
 	static bool configured = false;
 	if (!configured) { // more than 64 KiB of dynamic LDS has to be opted into once per kernel
-		HIP_CHECK_THROW(hipFuncSetAttribute((const void*)k_grid_scatter<D, F, REC>, hipFuncAttributeMaxDynamicSharedMemorySize, SCATTER_LDS_BYTES));
+		HIP_CHECK_THROW(hipFuncSetAttribute((const void*)k_grid_scatter<D, F, REC, STOCH>, hipFuncAttributeMaxDynamicSharedMemorySize, SCATTER_LDS_BYTES));
 		configured = true;
 	}
 	// development aid: TCNN_AMD_SCATTER_TIMING=1 prints per-task phase times (100 MHz constant clock) for the 3rd launch
@@ -446,7 +478,7 @@ void launch_scatter(hipStream_t s, const GridMeta* dm, const GridScatterTask* ta
 	static int timing_left = 3;
 	unsigned long long* dbg = nullptr;
 	if (timing && timing_left > 0 && !g_task_times) HIP_CHECK_THROW(hipMalloc(&dbg, (size_t)n_tasks * 8 * 8));
-	hipLaunchKernelGGL((k_grid_scatter<D, F, REC>), dim3(n_tasks), dim3(SCATTER_THREADS), SCATTER_LDS_BYTES, s, dm, tasks, n, x, (const half_t*)dy, dss, dsl, (half_t*)grad, chunk_bits,
+	hipLaunchKernelGGL((k_grid_scatter<D, F, REC, STOCH>), dim3(n_tasks), dim3(SCATTER_THREADS), SCATTER_LDS_BYTES, s, dm, tasks, n, x, (const half_t*)dy, dss, dsl, (half_t*)grad, chunk_bits,
 	                   scratch, accumulate ? 1 : 0, g_task_times ? g_task_times : dbg);
 	HIP_CHECK_THROW(hipGetLastError());
 	if (dbg) {
@@ -470,7 +502,15 @@ void launch_scatter(hipStream_t s, const GridMeta* dm, const GridScatterTask* ta
 
 template <int D>
 void dispatch_scatter(hipStream_t s, uint32_t F, const GridMeta* dm, const GridScatterTask* tasks, uint32_t n_tasks, uint32_t n, MatView x,
-                      const void* dy, uint32_t dss, uint32_t dsl, void* grad, const unsigned long long* chunk_bits, unsigned long long* scratch, bool accumulate, bool records) {
+                      const void* dy, uint32_t dss, uint32_t dsl, void* grad, const unsigned long long* chunk_bits, unsigned long long* scratch, bool accumulate, bool records, bool stochastic) {
+	if (stochastic) {
+		switch (F) {
+			case 2: return launch_scatter<D, 2, false, true>(s, dm, tasks, n_tasks, n, x, dy, dss, dsl, grad, chunk_bits, scratch, accumulate);
+			case 4: return launch_scatter<D, 4, false, true>(s, dm, tasks, n_tasks, n, x, dy, dss, dsl, grad, chunk_bits, scratch, accumulate);
+			case 8: return launch_scatter<D, 8, false, true>(s, dm, tasks, n_tasks, n, x, dy, dss, dsl, grad, chunk_bits, scratch, accumulate);
+			default: throw std::runtime_error{"grid_backward_lds: needs n_features_per_level in {2, 4, 8}"};
+		}
+	}
 	if (records) {
 		if constexpr (D == 2) {
 			if (F == 2) return launch_scatter<D, 2, true>(s, dm, tasks, n_tasks, n, x, dy, dss, dsl, grad, chunk_bits, scratch, accumulate);
@@ -771,8 +811,9 @@ std::vector<float> grid_scatter_level_costs(const GridMeta& meta, const std::vec
 bool grid_backward_lds(hipStream_t stream, const GridMeta& meta, const GridMeta* dev_meta, const GridScatterTask* dev_tasks, uint32_t n_tasks,
                        const GridScatterRange* dev_ranges, uint32_t n_ranges, uint64_t* scratch, uint32_t n, MatView x,
                        const void* dL_dy, uint32_t dy_stride_sample, uint32_t dy_stride_level, void* grad, const uint64_t* chunk_bits, bool accumulate, bool dy_records,
-                       uint64_t* task_times, const MlpReduceJob* reduce_job) {
+                       uint64_t* task_times, const MlpReduceJob* reduce_job, bool stochastic) {
 	if (n_tasks == 0) return false;
+	CHECK_THROW(!(stochastic && dy_records));
 	const unsigned long long* bits = (const unsigned long long*)chunk_bits;
 	unsigned long long* sc = (unsigned long long*)scratch;
 	CHECK_THROW(!dy_records || grid_scatter_records_supported(meta));
@@ -781,9 +822,9 @@ bool grid_backward_lds(hipStream_t stream, const GridMeta& meta, const GridMeta*
 		~TimesGuard() { g_task_times = nullptr; }
 	} guard{task_times};
 	switch (meta.n_pos_dims) {
-		case 2: dispatch_scatter<2>(stream, meta.n_features_per_level, dev_meta, dev_tasks, n_tasks, n, x, dL_dy, dy_stride_sample, dy_stride_level, grad, bits, sc, accumulate, dy_records); break;
-		case 3: dispatch_scatter<3>(stream, meta.n_features_per_level, dev_meta, dev_tasks, n_tasks, n, x, dL_dy, dy_stride_sample, dy_stride_level, grad, bits, sc, accumulate, dy_records); break;
-		case 4: dispatch_scatter<4>(stream, meta.n_features_per_level, dev_meta, dev_tasks, n_tasks, n, x, dL_dy, dy_stride_sample, dy_stride_level, grad, bits, sc, accumulate, dy_records); break;
+		case 2: dispatch_scatter<2>(stream, meta.n_features_per_level, dev_meta, dev_tasks, n_tasks, n, x, dL_dy, dy_stride_sample, dy_stride_level, grad, bits, sc, accumulate, dy_records, stochastic); break;
+		case 3: dispatch_scatter<3>(stream, meta.n_features_per_level, dev_meta, dev_tasks, n_tasks, n, x, dL_dy, dy_stride_sample, dy_stride_level, grad, bits, sc, accumulate, dy_records, stochastic); break;
+		case 4: dispatch_scatter<4>(stream, meta.n_features_per_level, dev_meta, dev_tasks, n_tasks, n, x, dL_dy, dy_stride_sample, dy_stride_level, grad, bits, sc, accumulate, dy_records, stochastic); break;
 		default: throw std::runtime_error{"GridEncoding: number of input dims must be 2 or 3."};
 	}
 	return grid_scatter_finalize(stream, dev_ranges, n_ranges, scratch, grad, accumulate, reduce_job);

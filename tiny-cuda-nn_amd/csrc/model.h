@@ -346,8 +346,7 @@ public:
 		const uint32_t base_resolution = enc.value("base_resolution", 16u);
 		const float per_level_scale = enc.value("per_level_scale", grid_type == GridType::Dense ? std::exp(std::log(256.0f / (float)base_resolution) / (n_levels - 1)) : 2.0f);
 		const HashType hash_type = string_to_hash_type(enc.value("hash", "CoherentPrime"));
-		m_stochastic_interpolation = enc.value("stochastic_interpolation", false);
-		if (m_stochastic_interpolation) throw std::runtime_error{"GridEncoding: stochastic_interpolation is not supported by this build"};
+		m_stochastic_interpolation = enc.value("stochastic_interpolation", false); // grid.h:284-298: read by the parameter-gradient pass alone (GridBackwardRoute::stochastic)
 		if (n_dims_to_encode < 2 || n_dims_to_encode > 4) throw std::runtime_error{"GridEncoding: number of input dims must be 2 or 3."};
 		if (n_levels > MAX_N_LEVELS) throw std::runtime_error{"GridEncoding: m_n_levels must be at most MAX_N_LEVELS=128"};
 		if (n_features % F != 0) throw std::runtime_error{"GridEncoding: n_features must be a multiple of N_FEATURES_PER_LEVEL"};
@@ -468,7 +467,7 @@ public:
 		return ctx;
 	}
 
-	GridFacts facts() const { return GridFacts{&m_meta, m_fp32, m_scatter_levels_ok, m_any_binned, m_n_to_pad}; }
+	GridFacts facts() const { return GridFacts{&m_meta, m_fp32, m_scatter_levels_ok, m_any_binned, m_n_to_pad, m_stochastic_interpolation}; }
 	GridForwardRoute forward_route(const Switches& sw, uint32_t n, bool as_planes, bool prepare_input_gradients, bool prepare_param_gradients) const override {
 		return grid_forward_route(facts(), sw, n, as_planes, prepare_input_gradients, prepare_param_gradients);
 	}
@@ -594,14 +593,15 @@ public:
 			ArenaBuf tmp{stream, n_params() * sizeof(float)};
 			if (mode == GradientMode::Overwrite) HIP_CHECK_THROW(hipMemsetAsync(tmp.data(), 0, n_params() * sizeof(float), stream));
 			else cast_half_to_float(stream, n_params(), grads, tmp.as<float>());
-			grid_backward(stream, m_meta, dev_meta(), true, n, x, dL_dy, false, padded_output_width(), tmp.data());
+			grid_backward(stream, m_meta, dev_meta(), true, n, x, dL_dy, false, padded_output_width(), tmp.data(), route.stochastic);
 			cast_float_to_half(stream, n_params(), tmp.as<float>(), grads);
 		} break;
 		case GridGradientKernel::Atomic:
 			if (mode == GradientMode::Overwrite) HIP_CHECK_THROW(hipMemsetAsync(grads, 0, n_params() * (m_fp32 ? 4 : 2), stream)); // grid.h:858
-			grid_backward(stream, m_meta, dev_meta(), m_fp32, n, x, dL_dy, m_fp32, padded_output_width(), grads);
+			grid_backward(stream, m_meta, dev_meta(), m_fp32, n, x, dL_dy, m_fp32, padded_output_width(), grads, route.stochastic);
 			break;
 		case GridGradientKernel::Lists: { // k_grid_scatter_lists.hip: a static plan, nothing to tune
+			CHECK_THROW(!route.stochastic); // (list elements carry all 2^D corners with their weights: grid_backward_route)
 			ScatterPlan& plan = scatter_plan(n, stream, true);
 			// dL/dy as rows (a caller's own network): into level planes first -- the streamed tasks read a level's gradients sample after
 			// sample, 4 bytes out of every row's 64 otherwise (2^18 samples: the owners 82 us from rows, 42 from planes; the transposition 12)
@@ -638,11 +638,11 @@ public:
 			const bool defer = !tune && take_prologue(route, offer, plan, grads, mode);
 			carried = grid_backward_lds(stream, m_meta, dev_meta(), plan.dev_tasks.as<GridScatterTask>(), plan.n_tasks, plan.dev_ranges.as<GridScatterRange>(), defer ? 0u : plan.n_ranges,
 			                            plan.scratch.as<uint64_t>(), n, x, dL_dy, dy_stride_sample, dy_stride_level, grads, mask, accumulate, route.dy == GridDyForm::Records,
-			                            tune ? times.as<uint64_t>() : nullptr, defer ? nullptr : offer.reduce_job) ||
+			                            tune ? times.as<uint64_t>() : nullptr, defer ? nullptr : offer.reduce_job, route.stochastic) ||
 			          (defer && offer.reduce_job); // (it went with the prologue)
 			if (route.binned) { // levels cut into more than 64 chunks (k_grid_bin.hip)
 				ArenaBuf workspace{stream, grid_bin_workspace_bytes(m_meta, n)};
-				grid_backward_binned(stream, m_meta, dev_meta(), n, x, dL_dy, dy_stride_sample, dy_stride_level, grads, accumulate, workspace.data(), hit_counters(stream).fallbacks.as<uint32_t>());
+				grid_backward_binned(stream, m_meta, dev_meta(), n, x, dL_dy, dy_stride_sample, dy_stride_level, grads, accumulate, workspace.data(), hit_counters(stream).fallbacks.as<uint32_t>(), route.stochastic);
 			}
 			if (tune) {
 				HIP_CHECK_THROW(hipStreamSynchronize(stream));

@@ -200,7 +200,9 @@ void grid_forward_planes(hipStream_t stream, const GridMeta& meta, const GridMet
                          MatView x, const void* grid, void* out_planes, uint64_t* chunk_bits, const MlpPrepJob* prep_job = nullptr, const GridHitLists* hit_lists = nullptr);
 // reference-shaped gradient scatter with global float atomics (fp32 grids, F == 1, tables too large for the LDS scheme).
 // grad: T[n_params] accumulated in place (caller zeroes it).  For F == 1 && !fp32 the caller passes an fp32 scratch as `grad`.
-void grid_backward(hipStream_t stream, const GridMeta& meta, const GridMeta* dev_meta, bool fp32_grad, uint32_t n, MatView x, const void* dL_dy, bool dy_fp32, uint32_t dy_stride, void* grad);
+// stochastic (here and in the other gradient launchers): GridBackwardRoute::stochastic -- dL/dy itself onto the one corner drawn per (sample, level)
+void grid_backward(hipStream_t stream, const GridMeta& meta, const GridMeta* dev_meta, bool fp32_grad, uint32_t n, MatView x, const void* dL_dy, bool dy_fp32, uint32_t dy_stride, void* grad,
+                   bool stochastic = false);
 
 // ---- LDS owner-computes scatter (k_grid_scatter.hip): exact 64-bit fixed-point accumulation, one task per workgroup
 struct GridScatterTask {
@@ -233,7 +235,7 @@ bool grid_backward_lds(hipStream_t stream, const GridMeta& meta, const GridMeta*
                        const GridScatterRange* dev_ranges, uint32_t n_ranges, uint64_t* scratch, uint32_t n, MatView x,
                        const void* dL_dy, uint32_t dy_stride_sample, uint32_t dy_stride_level, void* grad, const uint64_t* chunk_bits, bool accumulate, bool dy_records = false,
                        uint64_t* task_times = nullptr, // task_times (optional): device uint64[n_tasks][8], per-task timestamps for the plan tuner
-                       const MlpReduceJob* reduce_job = nullptr);
+                       const MlpReduceJob* reduce_job = nullptr, bool stochastic = false); // stochastic: not with dy_records
 // ---- the same scatter fed by hit lists (k_grid_scatter_lists.hip): two workgroups per CU with 64 KiB of accumulators each -- both features
 // of an entry in ONE 64-bit LDS add as 2 x int32 while a per-task bound proves that no half can overflow, 64-bit accumulators in two
 // passes otherwise -- tasks of its own plan (GridScatterTask::pad = split s | n_splits << 16: which share of a chunk's list), same scratch, same results.
@@ -261,7 +263,11 @@ struct GridFacts { // what a GridEncoding knows from its construction (and its p
 	const GridMeta* meta;
 	bool fp32, scatter_levels_ok, any_binned; // levels_ok: every level is cut into at most GRID_FILTER_MAX_CHUNKS chunks or binned (k_grid_bin.hip)
 	uint32_t n_to_pad;                        // padding features behind the levels'
+	bool stochastic = false;                  // the config's stochastic_interpolation (grid.h:284-298; what it changes: grid_stochastic_gradients)
 };
+// The parameter-gradient pass puts every (sample, level)'s dL/dy on ONE corner drawn per pair, with weight 1.  Nearest returns before the
+// flag is read (grid.h:279-282): such a grid is a plain Nearest grid on every route.
+inline bool grid_stochastic_gradients(const GridFacts& g) { return g.stochastic && g.meta->interpolation != (uint32_t)InterpolationType::Nearest; }
 enum class GridForwardKernel : uint32_t { Rows, Planes, PlanesToRows }; // k_grid_fwd (AoS); k_grid_fwd_planes; the latter + a transposition into rows
 enum class GridRecorded : uint32_t { Nothing, BitPlanes, HitLists };    // what the forward pass leaves for the gradient kernel
 struct GridForwardRoute {
@@ -299,7 +305,10 @@ inline GridForwardRoute grid_forward_route(const GridFacts& g, const Switches& s
 	if (planes && as_planes) r.kernel = GridForwardKernel::Planes;
 	else if (planes && sw.grid_rows_planes && grid_planes_to_rows_supported(meta, n, meta.n_levels * F + g.n_to_pad)) r.kernel = GridForwardKernel::PlanesToRows;
 	if (r.kernel == GridForwardKernel::Planes) r.plane_features = F;
-	if (param_gradients && r.lds) r.recorded = (r.kernel != GridForwardKernel::Rows && grid_hit_lists_wanted(g, sw, n)) ? GridRecorded::HitLists : GridRecorded::BitPlanes;
+	// (a stochastic grid never records hit lists: their elements carry all 2^D corners with their weights.  Bit planes stay a valid filter --
+	// the drawn corner is one of the corners whose chunks were recorded)
+	const bool lists = r.kernel != GridForwardKernel::Rows && !grid_stochastic_gradients(g) && grid_hit_lists_wanted(g, sw, n);
+	if (param_gradients && r.lds) r.recorded = lists ? GridRecorded::HitLists : GridRecorded::BitPlanes;
 	return r;
 }
 
@@ -313,6 +322,7 @@ struct GridBackwardRoute { // the default: dL/dy as rows, nothing else -- every 
 	// binned: k_grid_bin.hip follows for the levels cut into more than 64 chunks; tune: the bit-plane kernel's plan may be re-cut from a timed launch
 	// (TCNN_AMD_SCATTER_TUNE); prologue: the finalize pass may be left to the optimizer's launch where that offers it (AdamPrologue)
 	bool binned = false, tune = false, prologue = false;
+	bool stochastic = false; // every gradient kernel of this pass puts dL/dy on the one corner drawn per (sample, level) (grid_stochastic_gradients); never with Lists, Records or tail
 	// the fused MLP kernel's tail may store dL/dy in list order itself where its workgroups' samples are the lists' items (mlp_train_item_map() ==
 	// list_tail.map): what it needs for that, all but gvals -- the caller's workspace of tail_bytes, handed back as BackwardHandoff::list_gradients
 	bool tail = false;
@@ -327,12 +337,13 @@ inline GridBackwardRoute grid_backward_route(const GridFacts& g, const Switches&
 	const uint32_t F = meta.n_features_per_level;
 	GridBackwardRoute r;
 	if (mode == GradientMode::Ignore) return r;
+	r.stochastic = grid_stochastic_gradients(g);
 	if (!(fwd.planned ? fwd.lds : grid_lds_gradients(g, sw, n))) { // the reference-shaped kernel; half with F == 1 accumulates in fp32 (grid.h:660)
 		r.kernel = (!g.fp32 && F == 1) ? GridGradientKernel::AtomicScratch32 : GridGradientKernel::Atomic;
 		return r;
 	}
 	// LDS owner-computes scatter with exact integer accumulation.  Stale lists (a later forward pass took their counters): the unfiltered bit-plane kernel.
-	const bool lists = fwd.recorded == GridRecorded::HitLists && lists_current;
+	const bool lists = fwd.recorded == GridRecorded::HitLists && lists_current && !r.stochastic;
 	r.kernel = lists ? GridGradientKernel::Lists : GridGradientKernel::BitPlanes;
 	r.binned = !lists && g.any_binned;
 	r.tune = !lists && sw.scatter_tune;
@@ -342,7 +353,8 @@ inline GridBackwardRoute grid_backward_route(const GridFacts& g, const Switches&
 	r.dy = GridDyForm::Planes, r.plane_features = F;
 	// Scatter records: the MLP kernel interleaves the coordinates with dL/d(encoding) and the scatter does one gather per hit instead of two (C3a: the scatter gains
 	// 12 us, the MLP kernel loses 6 to 4x the dX bytes).  Not with hit lists, current or stale (their elements carry entries and weights), nor with a per-sample max_level.
-	if (offer == GridDyForm::Records && fwd.recorded != GridRecorded::HitLists && g.n_to_pad == 0 && max_level != GridMaxLevel::PerSample && sw.scatter_records && !g.any_binned &&
+	// Nor for a stochastic grid: its owners read dL/dy as planes beside the coordinates -- one kernel form less for a pass nobody has tuned yet.
+	if (offer == GridDyForm::Records && !r.stochastic && fwd.recorded != GridRecorded::HitLists && g.n_to_pad == 0 && max_level != GridMaxLevel::PerSample && sw.scatter_records && !g.any_binned &&
 	    grid_scatter_records_supported(meta) && x_contiguous) {
 		r.dy = GridDyForm::Records, r.record_planes = grid_scatter_record_planes(meta);
 		return r;
@@ -392,7 +404,8 @@ uint32_t grid_bin_acc_bytes();                 // LDS accumulators per workgroup
 size_t grid_bin_workspace_bytes(const GridMeta& meta, uint32_t n);
 void grid_backward_binned(hipStream_t stream, const GridMeta& meta, const GridMeta* dev_meta, uint32_t n, MatView x, const void* dL_dy, uint32_t dy_stride_sample,
                           uint32_t dy_stride_level, void* grad, bool accumulate, void* workspace,
-                          uint32_t* fallback_count = nullptr); // (optional, device) chunks whose packed 32-bit sums could not be proven and were added again in 64 bits
+                          uint32_t* fallback_count = nullptr, // (optional, device) chunks whose packed 32-bit sums could not be proven and were added again in 64 bits
+                          bool stochastic = false);
 void grid_backward_input(hipStream_t stream, const GridMeta& meta, bool fp32, uint32_t n, const void* dL_dy, uint32_t dy_stride, const float* dy_dx, MatViewMut dL_dx);
 // second-order input gradients (k_grid_bwdbwd.hip; grid.h:352-650): each of grad (accumulated in place, GT = float if fp32_grad),
 // dL_ddLdy (T [n][dy_stride], needs dy_dx) and dL_dx (overwritten, needs grid) is optional
