@@ -121,6 +121,19 @@ int  tcnn_module_backward_backward_input(tcnn_module_t m, tcnn_stream_t stream, 
 int  tcnn_module_backward_backward_input_mode(tcnn_module_t m, tcnn_stream_t stream, tcnn_context_t ctx, uint32_t n_elements, const float* dL_ddLdinput,
                                               const float* input, const void* dL_doutput, void* dL_dparams, void* dL_ddLdoutput, float* dL_dinput, const void* params,
                                               int gradient_mode);
+/* DifferentiableObject::input_gradient (object.h:342-366): d_dinput [n_elements][n_input_dims] = d output[dim] / d input with `params`, at
+ * inference -- no parameter gradient is read or written and no context is left.  dim counts the PADDED output columns (a padded column is
+ * legal); dim >= tcnn_module_n_output_dims reports "Invalid dimension to compute the input gradient for." before anything is allocated or
+ * launched, and n_elements must be a multiple of tcnn_batch_size_granularity().  The result is what forward(prepare_input_gradients) +
+ * backward with dL_doutput = (output precision)backprop_scale in column dim and +0 elsewhere give, multiplied by the float 1.0f /
+ * backprop_scale -- bit for bit, whichever route ran.  output (may be NULL): [n_elements][n_output_dims] in the output precision, the
+ * forward pass's output.  A grid encoding's max_level state applies as in any forward pass. */
+int  tcnn_module_input_gradient(tcnn_module_t m, tcnn_stream_t stream, uint32_t n_elements, uint32_t dim, const float* input, float* d_dinput, void* output,
+                                const void* params, float backprop_scale);
+/* Introspection: the route the module's last input_gradient call took -- "none" before the first call, "two-pass" (forward + backward
+ * kernels) or the fused MLP kernel's name, "k_mlp_input_grad<W,NB,NH>/relu|act" (/act: the hidden activation is chosen at run time).
+ * Owned by the module: valid until its next input_gradient call.  NULL (and tcnn_last_error) for a NULL module. */
+const char* tcnn_module_last_input_gradient_route(tcnn_module_t m);
 void tcnn_context_destroy(tcnn_context_t ctx);
 
 uint32_t    tcnn_module_n_input_dims(tcnn_module_t m);     /* cpp_api.cu:129 */
@@ -175,6 +188,10 @@ const float* tcnn_train_ctx_L(tcnn_train_ctx_t ctx);           /* float [n][padd
 /* network->inference(stream, input, output) (object.h:147-176): float in, float out [n_output_dims x n] in output_layout */
 int  tcnn_trainer_inference(tcnn_trainer_t t, tcnn_stream_t stream, uint32_t n_elements, const float* input, int input_layout,
                             float* output, int output_layout, int use_inference_params);
+/* network->input_gradient(stream, dim, input, d_dinput, backprop_scale) (object.h:342-366) on the trainer's inference parameters: see
+ * tcnn_module_input_gradient.  input and d_dinput are AoS [n_elements][n_input_dims] floats. */
+int  tcnn_trainer_input_gradient(tcnn_trainer_t t, tcnn_stream_t stream, uint32_t n_elements, uint32_t dim, const float* input, float* d_dinput, float backprop_scale);
+
 /* network->inference_mixed_precision(stream, input, output) (object.h:133-145): the network's own output, half
  * [n_elements][padded_output_width] -- what inference() casts to float; half the bytes for a caller that gathers row shards.
  * An FP32 trainer writes floats. */

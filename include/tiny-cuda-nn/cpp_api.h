@@ -75,6 +75,13 @@ public:
 		detail::ok(tcnn_module_backward_backward_input(m_handle, stream, (tcnn_context_t)ctx.ctx.get(), n_elements, dL_ddLdinput, input, dL_doutput, dL_dparams, dL_ddLdoutput, dL_dinput, params));
 	}
 
+	// DifferentiableObject::input_gradient (object.h:342-366; the reference's cpp::Module does not expose it): d_dinput [n_elements][n_input_dims]
+	// = d output[dim] / d input with `params`; output (may be nullptr): the forward pass's output.  See tcnn_module_input_gradient.
+	void input_gradient(stream_t stream, uint32_t n_elements, uint32_t dim, const float* input, float* d_dinput, void* output, const void* params, float backprop_scale) {
+		detail::ok(tcnn_module_input_gradient(m_handle, stream, n_elements, dim, input, d_dinput, output, params, backprop_scale));
+	}
+	std::string last_input_gradient_route() const { return tcnn_module_last_input_gradient_route(m_handle); } // "none" | "two-pass" | the fused kernel's name
+
 	uint32_t n_input_dims() const { return tcnn_module_n_input_dims(m_handle); }
 	uint32_t n_output_dims() const { return tcnn_module_n_output_dims(m_handle); } // padded width, cpp_api.cu:130
 	size_t n_params() const { return tcnn_module_n_params(m_handle); }

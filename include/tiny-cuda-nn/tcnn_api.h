@@ -261,6 +261,15 @@ public:
 	}
 	void inference(const GPUMatrixDynamic<float>& input, GPUMatrixDynamic<float>& output) { inference(nullptr, input, output); }
 
+	// object.h:342-366: d_dinput = d output[dim] / d input with the bound Trainer's inference parameters (dim counts padded columns); no
+	// parameter gradient is touched.  Both matrices are column-major n_dims x batch, as the reference's GPUMatrix<float> is.
+	void input_gradient(stream_t stream, uint32_t dim, const GPUMatrix<float>& input, GPUMatrix<float>& d_dinput, float backprop_scale = tcnn_default_loss_scale(detail::precision_of<T>::value)) {
+		if (!m_trainer) throw std::runtime_error{"NetworkWithInputEncoding::input_gradient: the network has no parameters yet (construct a Trainer first)"};
+		if (dim >= padded_output_width()) throw std::runtime_error{"Invalid dimension to compute the input gradient for."}; // object.h:350
+		if (input.m() != m_n_input_dims || d_dinput.m() != m_n_input_dims || input.n() != d_dinput.n()) throw std::runtime_error{"input_gradient: matrix shapes do not match the network"};
+		detail::check(tcnn_trainer_input_gradient(m_trainer, stream, input.n(), dim, input.data(), d_dinput.data(), backprop_scale));
+	}
+
 	uint32_t input_width() const { return m_n_input_dims; }
 	uint32_t output_width() const { return m_n_output_dims; }
 	uint32_t padded_output_width() const { return m_trainer ? tcnn_trainer_padded_output_width(m_trainer) : (m_n_output_dims + 15) / 16 * 16; }

@@ -248,6 +248,23 @@ int tcnn_module_backward_backward_input_mode(tcnn_module_t m, tcnn_stream_t stre
 	});
 }
 
+int tcnn_module_input_gradient(tcnn_module_t m, tcnn_stream_t stream, uint32_t n, uint32_t dim, const float* input, float* d_dinput, void* output, const void* params,
+                               float backprop_scale) {
+	return guarded([&] { // object.h:342-366
+		CHECK_THROW(m && m->model);
+		const uint32_t w = m->model->input_width();
+		m->model->input_gradient((hipStream_t)stream, n, dim, MatView{input, w, 1u}, MatViewMut{d_dinput, w, 1u}, output, params, backprop_scale);
+	});
+}
+
+const char* tcnn_module_last_input_gradient_route(tcnn_module_t m) {
+	if (!m || !m->model) {
+		g_last_error = "tcnn_module_last_input_gradient_route: null module";
+		return nullptr;
+	}
+	return m->model->last_input_gradient_route();
+}
+
 void tcnn_context_destroy(tcnn_context_t ctx) { delete ctx; }
 
 uint32_t tcnn_module_n_input_dims(tcnn_module_t m) { return m->model->input_width(); }
@@ -410,6 +427,15 @@ int tcnn_trainer_inference_mixed_precision(tcnn_trainer_t t, tcnn_stream_t strea
 		CHECK_THROW(t && t->trainer && (output_half || n == 0));
 		Trainer& tr = *t->trainer;
 		tr.inference_mixed_precision((hipStream_t)stream, n, make_view(input, tr.model().input_width(), n, input_layout), output_half, use_inference_params != 0);
+	});
+}
+
+int tcnn_trainer_input_gradient(tcnn_trainer_t t, tcnn_stream_t stream, uint32_t n, uint32_t dim, const float* input, float* d_dinput, float backprop_scale) {
+	return guarded([&] {
+		CHECK_THROW(t && t->trainer);
+		Trainer& tr = *t->trainer;
+		const uint32_t w = tr.model().input_width();
+		tr.input_gradient((hipStream_t)stream, n, dim, MatView{input, w, 1u}, MatViewMut{d_dinput, w, 1u}, backprop_scale);
 	});
 }
 

@@ -143,6 +143,87 @@ template <typename V> __device__ inline void st32_stream(void* base, const uint3
 	else __builtin_nontemporal_store(__builtin_bit_cast(uint16_t, v), (uint16_t*)p);
 }
 
+// ---- the forward chain's arguments and pieces (k_mlp_fwd in k_mlp.hip, k_mlp_input_grad in k_mlp_input_grad.hip)
+struct FwdArgs {
+	const half_t* x;      // [n][in_width], or level planes [in_width / F][n][F] when x_plane_f = F > 0; unused with x_f32
+	half_t* out;          // optional [n][out_width]
+	half_t* hidden;       // optional [n_hidden][n][width]
+	const h8* image;      // forward fragments
+	uint32_t n;
+	uint32_t x_plane_f;
+	// fused Identity encoding (identity.h:46-66): feature k = (half)(x[k] * scale + offset) for k < x_f32_dims, 1 for the padding
+	MatView x_f32;        // data == nullptr: not used
+	uint32_t x_f32_dims;
+	float x_scale, x_offset;
+	// fused OneBlob encoding (oneblob.h:47-67): x_f32 holds the coordinates, feature dim * n_bins + bin; 0 = off
+	uint32_t oneblob_log2;
+	// fused trim_and_cast (common_device.h:990-1002): float output of the first out_f32_dims outputs
+	MatViewMut out_f32;   // data == nullptr: not used
+	uint32_t out_f32_dims;
+};
+
+// 8 consecutive input features k0..k0+7 of one sample: the B operand of layer 0
+__device__ inline h8 load_mlp_input(const FwdArgs& a, const uint32_t in_w, const uint32_t sample, const uint32_t k0) {
+	if (a.x_f32.data) {
+		h8 v;
+		if (a.x_f32.stride_dim == 1 && (a.x_f32.stride_sample & 3u) == 0 && k0 + 8 <= a.x_f32_dims) { // two 16-byte loads
+			const float4* p = (const float4*)(a.x_f32.data + (size_t)sample * a.x_f32.stride_sample + k0);
+			const float4 lo = p[0], hi = p[1];
+			v[0] = (half_t)(lo.x * a.x_scale + a.x_offset); v[1] = (half_t)(lo.y * a.x_scale + a.x_offset);
+			v[2] = (half_t)(lo.z * a.x_scale + a.x_offset); v[3] = (half_t)(lo.w * a.x_scale + a.x_offset);
+			v[4] = (half_t)(hi.x * a.x_scale + a.x_offset); v[5] = (half_t)(hi.y * a.x_scale + a.x_offset);
+			v[6] = (half_t)(hi.z * a.x_scale + a.x_offset); v[7] = (half_t)(hi.w * a.x_scale + a.x_offset);
+			return v;
+		}
+#pragma unroll
+		for (int j = 0; j < 8; ++j) {
+			const uint32_t k = k0 + j;
+			v[j] = k < a.x_f32_dims ? (half_t)(a.x_f32.data[(size_t)sample * a.x_f32.stride_sample + (size_t)k * a.x_f32.stride_dim] * a.x_scale + a.x_offset) : (half_t)1.0f;
+		}
+		return v;
+	}
+	if (a.x_plane_f == 2) {
+		uint4 v;
+		v.x = *(const uint32_t*)(a.x + ((size_t)(k0 / 2 + 0) * a.n + sample) * 2);
+		v.y = *(const uint32_t*)(a.x + ((size_t)(k0 / 2 + 1) * a.n + sample) * 2);
+		v.z = *(const uint32_t*)(a.x + ((size_t)(k0 / 2 + 2) * a.n + sample) * 2);
+		v.w = *(const uint32_t*)(a.x + ((size_t)(k0 / 2 + 3) * a.n + sample) * 2);
+		return __builtin_bit_cast(h8, v);
+	}
+	if (a.x_plane_f == 4) {
+		const uint2 lo = *(const uint2*)(a.x + ((size_t)(k0 / 4) * a.n + sample) * 4);
+		const uint2 hi = *(const uint2*)(a.x + ((size_t)(k0 / 4 + 1) * a.n + sample) * 4);
+		uint4 v;
+		v.x = lo.x; v.y = lo.y; v.z = hi.x; v.w = hi.y;
+		return __builtin_bit_cast(h8, v);
+	}
+	if (a.x_plane_f == 8) return *(const h8*)(a.x + ((size_t)(k0 / 8) * a.n + sample) * 8);
+	return *(const h8*)(a.x + (size_t)sample * in_w + k0);
+}
+
+// pack NB accumulator column blocks of T row tiles into chained B fragments (KS k-steps), applying the activation
+// (activate_pack_inlined: for callers that cannot afford the call -- acc and hf are passed by reference, and where the compiler keeps
+// activate_pack as a function of its own both arrays live in scratch)
+template <int T, int KS, int NB, int ACT>
+__device__ __forceinline__ void activate_pack_inlined(const f4 (&acc)[T][NB], h8 (&hf)[KS][NB], uint32_t act) {
+#pragma unroll
+	for (int s = 0; s < KS; ++s) {
+#pragma unroll
+		for (int b = 0; b < NB; ++b) {
+			h8 v;
+#pragma unroll
+			for (int r = 0; r < 4; ++r) {
+				v[r] = act_fwd_t<ACT>(act, (half_t)acc[2 * s][b][r]);
+				if (2 * s + 1 < T) v[4 + r] = act_fwd_t<ACT>(act, (half_t)acc[(2 * s + 1 < T) ? 2 * s + 1 : 0][b][r]);
+				else v[4 + r] = (half_t)0.0f;
+			}
+			hf[s][b] = v;
+		}
+	}
+}
+template <int T, int KS, int NB, int ACT>
+__device__ inline void activate_pack(const f4 (&acc)[T][NB], h8 (&hf)[KS][NB], uint32_t act) { activate_pack_inlined<T, KS, NB, ACT>(acc, hf, act); }
+
 // Store 4 consecutive input-gradient features k0..k0+3 of sample s.  AoS: one 8-byte store.  Level planes (what the grid
 // scatter reads with unit stride): feature k lives at ((k / F) * n + s) * F + k % F.
 __device__ inline void store_dx(half_t* base, uint32_t plane_f, uint32_t n, uint32_t in_w, uint32_t s, uint32_t k0, h4 v) {

@@ -1794,6 +1794,25 @@ public:
 		mlp_wgrad_panels(stream, precision(), n, panels.data(), (uint32_t)panels.size(), accumulate, ws.as<float>()); // (layers of one shape share a launch)
 	}
 
+	// ---- input_gradient (object.h:342-366) for the network alone: dL_dinput [n][in_width] (or level planes) in the network's precision =
+	// backprop_scale * d output[dim] / d input.  The plan (mlp_input_gradient_plan, asked once per call by the caller, who needs it to choose
+	// the input's form) decides between the fused kernel and forward + backward on a one-hot dL/dy: the same bits either way.
+	// io: fused -- whatever mlp_input_gradient takes; two-pass -- x_half rows.  io.out_half: optional with the fused kernel, needed by the two passes.
+	MlpInputGradPlan input_gradient_plan(uint32_t n) const { return mlp_input_gradient_plan(m_desc, m_layerwise, n); }
+	void input_gradient(hipStream_t stream, const MlpInputGradPlan& plan, uint32_t n, const MlpIo& io, uint32_t dim, float backprop_scale, const void* params, void* dL_dinput,
+	                    uint32_t dx_plane_features) const {
+		CHECK_THROW(dim < m_padded_output_width && dL_dinput != nullptr);
+		if (plan.fused) {
+			ArenaBuf image = prepare(stream, params, true);
+			return mlp_input_gradient(stream, m_desc, plan, image.data(), n, io, dim, backprop_scale, dL_dinput, dx_plane_features);
+		}
+		CHECK_THROW(io.x_half != nullptr && io.out_half != nullptr && !io.x_plane_features && !io.x_f32.data && !io.x_oneblob_bins);
+		ArenaBuf d_doutput{stream, (size_t)n * m_padded_output_width * element_size()};
+		input_gradient_one_hot(stream, precision(), n, m_padded_output_width, dim, backprop_scale, d_doutput.data());
+		const NetworkContext ctx = forward(stream, n, io.x_half, io.out_half, params);
+		backward(stream, ctx, n, io.x_half, io.out_half, d_doutput.data(), dL_dinput, params, nullptr, GradientMode::Ignore, dx_plane_features);
+	}
+
 	// ---- Second-order input gradients of a CutlassMLP: the gradients of S = <v, dL/dinput> for a given v = dL2/d(dL/dinput).
 	// With h_0 = input, z_k = W_k h_{k-1}, h_k = a_k(z_k), g_K = dL/dy, d_k = g_k a_k'(z_k), g_{k-1} = W_k^T d_k (dL/dinput = g_0):
 	//   tangent    u_0 = v, z'_k = W_k u_{k-1}, u_k = a_k'(z_k) z'_k                  dS/d(dL/dy) = u_K
@@ -2076,8 +2095,40 @@ public:
 	                                     void* dL_ddLdoutput, MatViewMut* dL_dinput, const void* params, void* gradients, GradientMode mode) {
 		throw std::runtime_error{"DifferentiableObject::backward_backward_input_impl: not implemented error"}; // object.h:288
 	}
+	// object.h:342-366: d_dinput [n][input_width] = d output[dim] / d input with the caller's (inference) parameters; no parameter gradient is
+	// touched and no context is left.  output (optional): the forward pass's output [n][padded_output_width] in the module's precision.
+	// Every route gives what the generic one gives, bit for bit: d_doutput = (T)backprop_scale in column dim and +0 elsewhere,
+	// forward(prepare_input_gradients), backward(GradientMode::Ignore), times 1.0f / backprop_scale (formed once, the reference's `mult`).
+	void input_gradient(hipStream_t stream, uint32_t n, uint32_t dim, MatView input, MatViewMut d_dinput, void* output, const void* params, float backprop_scale) {
+		if (dim >= padded_output_width()) throw std::runtime_error{"Invalid dimension to compute the input gradient for."}; // object.h:350
+		check_batch(n);
+		CHECK_THROW(n == 0 || (input.data != nullptr && d_dinput.data != nullptr));
+		if (n == 0) return;
+		m_last_input_gradient_route = input_gradient_impl(stream, n, dim, input, d_dinput, output, params, backprop_scale);
+		input_gradient_rescale(stream, n, input_width(), 1.0f / backprop_scale, d_dinput);
+	}
+	const char* last_input_gradient_route() const { return m_last_input_gradient_route.c_str(); } // "none" before the first call
 	virtual Json hyperparams() const = 0;
 	std::string name() const { return hyperparams().value("otype", "<Unknown>"); } // object.h:51-53
+protected:
+	// writes d_dinput scaled by backprop_scale and returns the route's name.  The generic route, for every module:
+	virtual std::string input_gradient_impl(hipStream_t stream, uint32_t n, uint32_t dim, MatView input, MatViewMut d_dinput, void* output, const void* params, float backprop_scale) {
+		input_gradient_two_pass(stream, n, dim, input, d_dinput, output, params, backprop_scale);
+		return "two-pass";
+	}
+	void input_gradient_two_pass(hipStream_t stream, uint32_t n, uint32_t dim, MatView input, MatViewMut d_dinput, void* output, const void* params, float backprop_scale) {
+		const uint32_t pw = padded_output_width();
+		const size_t bytes = (size_t)n * pw * (precision() == Precision::Fp32 ? 4 : 2);
+		ArenaBuf out_tmp, d_doutput{stream, bytes};
+		if (!output) out_tmp = ArenaBuf{stream, bytes};
+		void* out = output ? output : out_tmp.data();
+		input_gradient_one_hot(stream, precision(), n, pw, dim, backprop_scale, d_doutput.data());
+		const std::unique_ptr<ModelContext> ctx = forward(stream, n, input, out, params, true);
+		backward(stream, *ctx, n, input, out, d_doutput.data(), &d_dinput, params, nullptr, GradientMode::Ignore);
+	}
+private:
+	std::string m_last_input_gradient_route = "none";
+public:
 
 	static void check_batch(uint32_t n) { // object.h:130,150,197,246
 		if (n % BATCH_SIZE_GRANULARITY != 0) throw std::runtime_error{"batch size " + std::to_string(n) + " is not a multiple of BATCH_SIZE_GRANULARITY = 256"};
@@ -2315,6 +2366,41 @@ public:
 		if (dL_dnetwork_input) {
 			m_encoding->backward(stream, ctx.encoding_ctx, n, input, dL_dnetwork_input.data(), dL_dinput, encoding_params(params), encoding_params(gradients), mode, route);
 		}
+	}
+
+	// object.h:342-366 for this model: the encoding's forward pass with dy_dx, the network's input_gradient by its plan (the fused kernel, or
+	// forward + backward), the encoding's backward pass to dL/dinput -- the kernels forward(prepare_input_gradients) and backward(Ignore) run,
+	// except that a fused network stores no activations.  An Identity encoding is applied inside the fused kernel's load, as at inference.
+	// (A OneBlob encoding in front keeps the two passes: its fused input form is not part of the kernel.)
+	std::string input_gradient_impl(hipStream_t stream, uint32_t n, uint32_t dim, MatView input, MatViewMut d_dinput, void* output, const void* params, float backprop_scale) override {
+		MlpInputGradPlan plan = m_network->input_gradient_plan(n);
+		if (m_encoding->as_oneblob()) plan = MlpInputGradPlan{};
+		const uint32_t enc_w = m_encoding->padded_output_width();
+		MlpIo io{};
+		io.out_half = output;
+		ArenaBuf network_input, out_tmp;
+		EncodingContext encoding_ctx;
+		float scale = 1, offset = 0;
+		if (plan.fused && m_encoding->as_identity(scale, offset)) {
+			io.x_f32 = input;
+			io.x_f32_dims = m_encoding->input_width();
+			io.x_scale = scale;
+			io.x_offset = offset;
+		} else {
+			network_input = ArenaBuf{stream, (size_t)n * enc_w * elem()};
+			encoding_ctx = m_encoding->forward(stream, n, input, encoding_params(params), network_input.data(), true, false);
+			io.x_half = network_input.data();
+		}
+		if (!plan.fused && !output) { // the two passes read the output back
+			out_tmp = ArenaBuf{stream, (size_t)n * m_network->padded_output_width() * elem()};
+			io.out_half = out_tmp.data();
+		}
+		ArenaBuf dL_dnetwork_input{stream, (size_t)n * enc_w * elem()};
+		const GridDyForm offer = !m_network->layerwise() ? GridDyForm::Planes : GridDyForm::Rows; // (as backward() offers it)
+		const GridBackwardRoute route = m_encoding->backward_route(switches(), stream, encoding_ctx, n, input, offer, true, GradientMode::Ignore);
+		m_network->input_gradient(stream, plan, n, io, dim, backprop_scale, params, dL_dnetwork_input.data(), route.plane_features);
+		m_encoding->backward(stream, encoding_ctx, n, input, dL_dnetwork_input.data(), &d_dinput, encoding_params(params), nullptr, GradientMode::Ignore, route);
+		return plan.name;
 	}
 
 	// Second-order input gradients through encoding and network (the network: Network::second_order_*, CutlassMLP only).  With
@@ -3795,6 +3881,11 @@ public:
 		Model::check_batch(n);
 		if (n == 0) return;
 		m_model->inference_f32(stream, n, input, output, use_inference_params ? params_inference() : working_params());
+	}
+
+	// object.h:342-366 on the inference parameters (trainer.h binds them to the model): no gradient buffer, no optimizer state is touched
+	void input_gradient(hipStream_t stream, uint32_t n, uint32_t dim, MatView input, MatViewMut d_dinput, float backprop_scale) {
+		m_model->input_gradient(stream, n, dim, input, d_dinput, nullptr, params_inference(), backprop_scale);
 	}
 
 	// object.h:133-145, inference_mixed_precision: the network's own output, half [n][padded_output_width] (what inference() casts); floats from an fp32 trainer

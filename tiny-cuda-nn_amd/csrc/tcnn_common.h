@@ -484,6 +484,30 @@ void mlp_forward_io(hipStream_t stream, const MlpDesc& d, const void* image, uin
 // dx_plane_features = 0: dL_dx is AoS [n][in_width]; = F > 0: "level planes" [in_width / F][n][F] (what the grid scatter reads)
 void mlp_backward(hipStream_t stream, const MlpDesc& d, const void* image, uint32_t n, const void* dL_dout, const void* out, const void* hidden, void* dhidden, void* dL_dx,
                   uint32_t dx_plane_features);
+// ---- input_gradient (object.h:342-366): d output[dim] / d (network input) at inference.  One kernel (k_mlp_input_grad.hip) runs the forward
+// chain, keeps every hidden layer's halves in registers, seeds backprop_scale on row `dim` and runs the backward chain: bit for bit what
+// mlp_forward (hidden stored) + mlp_activation_backward_output + mlp_backward give for a one-hot dL/dy, without the stored activations and
+// the dhidden nobody reads.  Which instantiation, with its NB and grid, or the two passes: decided once per call by mlp_input_gradient_plan.
+constexpr uint32_t MLP_INPUT_GRAD_MAX_HIDDEN = 4; // depths 1 .. 4 are instantiated
+struct MlpInputGradPlan {
+	bool fused = false;          // false: forward + backward (name "two-pass")
+	char name[48] = "two-pass";  // the route's name (tcnn_module_last_input_gradient_route): "two-pass" | "k_mlp_input_grad<W,NB,NH>/relu|act"
+	uint32_t nb = 0, grid = 0;   // fused: column blocks of 16 samples per wave and trip, workgroups of 4 waves
+	bool relu = false;           // fused: the compiled ReLU form, else the activation chosen at run time
+};
+// Pure host code: no GPU call, no allocation, no environment.  layerwise: Network::layerwise() -- fp32, Sine, zero hidden layers, widths the
+// fused kernels do not cover, TCNN_AMD_MLP_LAYERWISE=1 when the network was created.  Two-pass also for depths and widths without an
+// instantiation (256), for n that is no multiple of 16 NB, and for 128 x (3 | 4) ReLU on a full machine, where the fused kernel measured no
+// faster (DESIGN.md "input_gradient").
+MlpInputGradPlan mlp_input_gradient_plan(const MlpDesc& d, bool layerwise, uint32_t n);
+// io: the network's input as mlp_forward_io takes it (rows, level planes or the fused Identity input; no OneBlob) and, optionally, out_half;
+// dL_dx half [n][in_width] or level planes (dx_plane_features), as mlp_backward writes it; dim < d.out_width; plan.fused must hold for (d, n)
+void mlp_input_gradient(hipStream_t stream, const MlpDesc& d, const MlpInputGradPlan& plan, const void* image, uint32_t n, const MlpIo& io, uint32_t dim, float backprop_scale,
+                        void* dL_dx, uint32_t dx_plane_features);
+// the two ends of every input_gradient route (object.h:352-365): d_doutput [n][width] T = (T)backprop_scale in column dim, +0 elsewhere;
+// d_dinput[i][j] *= mult for j < dims (mult = 1.0f / backprop_scale, formed once by the caller)
+void input_gradient_one_hot(hipStream_t stream, Precision precision, uint32_t n, uint32_t width, uint32_t dim, float backprop_scale, void* d_doutput);
+void input_gradient_rescale(hipStream_t stream, uint32_t n, uint32_t dims, float mult, MatViewMut d_dinput);
 // ---- the Trainer's fused step: forward + loss + backward + weight gradients in ONE kernel, one of about twenty (k_train.hip: LDS images,
 // any 64- / 128-wide network with <= 32 outputs; k_train_regs.hip: (16 | 32) -> 64 -> [64 ->] 16 with everything in registers;
 // k_train_r32{,a}.hip, k_train_r32ob.hip, k_train_r32w.hip: BASELINE configs 3, 2 and 5 on the 32x32x16 matrix instruction).  Which one runs

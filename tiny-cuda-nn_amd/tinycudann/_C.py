@@ -75,6 +75,9 @@ _SIGNATURES = {
     "tcnn_module_backward": (_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tcnn_module_backward_backward_input": (_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tcnn_module_backward_backward_input_mode": (_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int]),
+    "tcnn_module_input_gradient": (_int, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _f32]),
+    "tcnn_module_last_input_gradient_route": (_cp, [_vp]),
+    "tcnn_trainer_input_gradient": (_int, [_vp, _vp, _u32, _u32, _vp, _vp, _f32]),
     "tcnn_context_destroy": (None, [_vp]),
     "tcnn_module_n_input_dims": (_u32, [_vp]),
     "tcnn_module_n_output_dims": (_u32, [_vp]),

@@ -145,6 +145,21 @@ class NativeModule:
                                                      _ptr(input), _ptr(output), _ptr(params)))
         return dL_dinput, dL_dparams
 
+    def input_gradient(self, input, params, dim, backprop_scale, want_output=False):  # object.h:342-366
+        """d output[dim] / d input with `params`, float32 [n, n_input_dims] (and the forward pass's padded output if asked for):
+        tcnn_amd.h tcnn_module_input_gradient.  n must be a multiple of the batch granularity."""
+        self._check_inputs(input, params)
+        with torch.cuda.device(input.device):
+            n = input.shape[0]
+            d_dinput = torch.empty((n, self.n_input_dims()), dtype=torch.float32, device=input.device)
+            output = torch.empty((n, self.n_output_dims()), dtype=_torch_precision(self.output_precision()), device=input.device) if want_output else None
+            _C.check(_C.lib.tcnn_module_input_gradient(self._h, _stream(), n, int(dim), _ptr(input), _ptr(d_dinput), _ptr(output), _ptr(params), float(backprop_scale)))
+        return d_dinput, output
+
+    def last_input_gradient_route(self):
+        """ "none" before the first input_gradient call, then "two-pass" or the fused MLP kernel's name (tcnn_amd.h: tcnn_module_last_input_gradient_route)"""
+        return _C.lib.tcnn_module_last_input_gradient_route(self._h).decode()
+
     def bwd_bwd_input(self, ctx, input, params, dL_ddLdinput, dL_doutput):  # bindings.cpp:172-245
         """from dL_ddLdinput to (dL_ddLdoutput, dL_dparams, dL_dinput); each is None unless its tensor requires grad."""
         if ctx is None or not ctx._h:
@@ -376,6 +391,27 @@ class Module(torch.nn.Module):
             working = _WorkingCopy.apply(self.params, self)
         output = _Evaluate.apply(rows, working, self.native_tcnn_module, self.loss_scale, self._max_level_of_call(n, rows))
         return output[:n, : self.n_output_dims]
+
+    def input_gradient(self, x, dim=0, backprop_scale=None, return_output=False):
+        """d output[dim] / d x at inference (the reference's DifferentiableObject::input_gradient, object.h:342-366): float32
+        [n, n_input_dims] for any n, computed outside autograd on the module's current parameters -- nothing requires or receives a
+        gradient.  dim counts the native (padded) output columns; backprop_scale (default: the module's loss scale) is the magnitude
+        the one-hot is seeded with and divided out again.  return_output=True: (gradient, output[:n, :n_output_dims]) of the same pass."""
+        with torch.no_grad():
+            x = x.detach()
+            if not x.is_cuda:
+                warnings.warn("input must be a CUDA tensor, but isn't. This indicates suboptimal performance.")
+                x = x.cuda()
+            n = x.shape[0]
+            rows = _pad_rows(x.to(torch.float), _C.batch_size_granularity()).contiguous()
+            working = self.params.detach().to(self.dtype).contiguous()
+            scale = self.loss_scale if backprop_scale is None else backprop_scale
+            native = self.native_tcnn_module
+            call = _Call(native, scale, False, False, self._max_level_of_call(n, rows))
+            with call.setting():
+                gradient, output = native.input_gradient(rows, working, dim, scale, return_output)
+            gradient = gradient[:n]
+            return (gradient, output[:n, : self.n_output_dims]) if return_output else gradient
 
     # --- max_level of the grid encoding(s) (the reference's GridEncoding::set_max_level / set_max_level_gpu, grid_interface.h:101-123).
     # Every forward call records the setting in force; its backward and double-backward passes run under that setting.

@@ -192,6 +192,18 @@ class Trainer:
         _C.check(_C.lib.tcnn_trainer_inference(self._h, _stream(stream), n, _ptr(input), input_layout, _ptr(output), output_layout, 1))
         return output
 
+    # -- object.h:342-366: network->input_gradient(stream, dim, input, d_dinput, backprop_scale) on the inference parameters
+    def input_gradient(self, input, dim=0, backprop_scale=None, d_dinput=None, stream=None):
+        """d output[dim] / d input, float32 [n, n_input_dims] (AoS, n a multiple of the batch granularity); dim counts padded columns"""
+        n = input.shape[0]
+        if d_dinput is None:
+            d_dinput = torch.empty((n, input.shape[1]), dtype=torch.float32, device=input.device)
+        assert input.dtype == torch.float32 and input.is_contiguous() and d_dinput.dtype == torch.float32 and d_dinput.is_contiguous() and d_dinput.shape == input.shape
+        self._check_max_level_rows(n)
+        scale = self.default_loss_scale if backprop_scale is None else backprop_scale
+        _C.check(_C.lib.tcnn_trainer_input_gradient(self._h, _stream(stream), n, int(dim), _ptr(input), _ptr(d_dinput), float(scale)))
+        return d_dinput
+
     # -- object.h:133-145: network->inference_mixed_precision(stream, input, output): half [n][padded_output_width]
     def inference_half(self, input, output=None, input_layout=LAYOUT_AOS, stream=None):
         if self.dtype != torch.half:
