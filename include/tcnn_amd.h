@@ -259,7 +259,7 @@ size_t tcnn_module_list_scatters(tcnn_module_t m); /* the same count for a modul
 size_t tcnn_trainer_list_gradient_tails(tcnn_trainer_t t);
 /* Introspection (no counterpart in the reference): a short, stable name of the MLP training kernel the last training_step() of this
  * trainer launched -- "r32", "r32a", "r32w", "r32ob", "regs_fast", "regs", "train<W,NB,NW,MAXT>/relu", "train<W,NB,NW,MAXT>/act",
- * "train_pw28/...", "train_pw32/...", "train_regw/...", "train_ob/..." (/act: the hidden activation is chosen at run time) or "unfused"
+ * "train_regw/...", "train_ob/..." (/act: the hidden activation is chosen at run time) or "unfused"
  * (forward, loss, backward and weight-gradient kernels of their own); "" before the first step.  A static string: do not free it. */
 const char* tcnn_trainer_last_step_kernel(tcnn_trainer_t t);
 

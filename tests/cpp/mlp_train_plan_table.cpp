@@ -42,7 +42,7 @@ static const LossCase LOSSES[] = {
 };
 static const char* SWITCH_SETS[][2] = { // the default, each A/B switch, and every instantiated (NB, NW, MAXT) of k_mlp_train forced
 	{nullptr, nullptr}, {"TCNN_AMD_MLP_REGS", "0"}, {"TCNN_AMD_MLP_R32", "0"}, {"TCNN_AMD_MLP_R32A", "0"}, {"TCNN_AMD_MLP_R32A", "1"}, {"TCNN_AMD_MLP_FAST", "0"},
-	{"TCNN_AMD_MLP_REGW", "0"}, {"TCNN_AMD_MLP_PW", "1"},
+	{"TCNN_AMD_MLP_REGW", "0"},
 	{"TCNN_AMD_MLP_VARIANT", "1,8,8"}, {"TCNN_AMD_MLP_VARIANT", "2,4,8"}, {"TCNN_AMD_MLP_VARIANT", "2,4,16"}, {"TCNN_AMD_MLP_VARIANT", "1,4,16"}, {"TCNN_AMD_MLP_VARIANT", "1,4,32"},
 	{"TCNN_AMD_MLP_VARIANT", "1,8,16"}, {"TCNN_AMD_MLP_VARIANT", "1,8,32"},
 };

@@ -17,7 +17,7 @@ other rows the class (finite, +inf, -inf, NaN) of every element is the oracle ne
 training forward's bits on every row.
 
 Covered, each asserted by Trainer.last_step_kernel: the unfused sequence k_mlp_fwd -> k_act_bwd_output -> k_mlp_bwd (widths 16, 32, 256; 64 and
-128 under TCNN_AMD_FUSED_STEP=0), train<64,1,8,8>, train<128,1,8,16>, train_pw28 and train_regw of k_train.hip (/act, and /relu for a ReLU
+128 under TCNN_AMD_FUSED_STEP=0), train<64,1,8,8>, train<128,1,8,16> and train_regw of k_train.hip (/act, and /relu for a ReLU
 hidden layer), regs of k_train_regs.hip (ReLU and None: all it accepts), the layer-by-layer path of k_mlp_layers.hip (CutlassMLP 48 and 512
 wide, Sine hidden layers included), Trainer.inference_half on each of them, tcnn.Network's inference and forward (64 and 48 wide), and the
 second-order epilogues of k_mlp_layers.hip (act_d1, act_d2) through backward_backward_input.
@@ -60,7 +60,6 @@ PATHS = [
     ("unfused256", 256, 1, {}, "unfused", FUSED_CASES),
     ("train64", 64, 1, _v(1, 8, 8), "train<64,1,8,8>/act", FUSED_CASES),
     ("train128", 128, 1, _v(1, 8, 16), "train<128,1,8,16>/act", FUSED_CASES),
-    ("pw28", 64, 1, {**R0, "TCNN_AMD_MLP_PW": "1"}, "train_pw28/act", FUSED_CASES),
     ("regw", 64, 2, {"TCNN_AMD_MLP_REGS": "0"}, "train_regw/act", REGW_CASES),
     ("regs", 64, 1, {}, "regs", REGS_CASES),
     ("layers48", 48, 1, {}, "unfused", LAYER_CASES),

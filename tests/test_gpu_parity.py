@@ -758,7 +758,8 @@ def test_oneblob_inside_the_mlp_kernel_is_bit_identical(tcnn, oracle, monkeypatc
     fused = tr.inference(_t(x))
     fused_soa = tr.inference(_t(np.ascontiguousarray(x.T)), input_layout=0)
     monkeypatch.setenv("TCNN_AMD_FUSE_ONEBLOB", "0")
-    plain = tr.inference(_t(x))
+    tr_plain = tcnn.Trainer(2, 3, cfg, seed=1337)  # the switches are read when a model is created: the other form needs a trainer of its own
+    plain = tr_plain.inference(_t(x))
     monkeypatch.delenv("TCNN_AMD_FUSE_ONEBLOB")
     assert np.array_equal(fused.cpu().numpy().view(np.uint32), plain.cpu().numpy().view(np.uint32))
     assert np.array_equal(fused_soa.cpu().numpy().view(np.uint32), plain.cpu().numpy().view(np.uint32))
@@ -989,13 +990,6 @@ def test_training_step_variants_agree_bitwise(tcnn, oracle, cfg, n_in, monkeypat
         for env in ({"TCNN_AMD_SCATTER_TUNE": "0"}, {"TCNN_AMD_SIDE_JOBS": "0"}):
             g, out = grads(env)
             assert np.array_equal(out, r32_out) and np.array_equal(g, r32_g), env
-    # the private weight-gradient form of the MLP kernel sums in another order: same forward pass and grid gradients, MLP
-    # weight gradients equal up to fp32 summation order before the one rounding to fp16
-    g, out = grads({**fixed, "TCNN_AMD_MLP_PW": "1"})
-    assert np.array_equal(out, base_out)
-    assert np.array_equal(g[n_net:], base_g[n_net:])
-    a, b = _f32(g[:n_net]), _f32(base_g[:n_net])
-    assert float(np.linalg.norm(a - b)) <= 2e-3 * float(np.linalg.norm(b))
 
 
 def test_bench_configuration_scatter_forms_agree_at_full_batch(tcnn, oracle, monkeypatch):
@@ -1600,7 +1594,8 @@ def test_wide_inference_forms_agree(tcnn, oracle, monkeypatch):
     x = oracle.Pcg32(11).uniform_strided(n * 32).reshape(n, 32)
     y_lds = tr.inference(_t(x)).cpu().numpy()
     monkeypatch.setenv("TCNN_AMD_MLP_FWD_LDS", "0")
-    y_l2 = tr.inference(_t(x)).cpu().numpy()
+    tr_l2 = tcnn.Trainer(32, 16, cfg, seed=1337)  # the switches are read when a model is created: the other form needs a trainer of its own
+    y_l2 = tr_l2.inference(_t(x)).cpu().numpy()
     monkeypatch.delenv("TCNN_AMD_MLP_FWD_LDS")
     assert np.array_equal(y_lds, y_l2)
     ref = oracle.Trainer(32, 16, cfg, seed=1337)

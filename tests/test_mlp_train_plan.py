@@ -38,4 +38,4 @@ def test_plan_reproduces_the_recorded_table(binary):
     if got != want:
         diff = list(difflib.unified_diff(want.splitlines(), got.splitlines(), "recorded", "mlp_train_plan", lineterm="", n=1))
         pytest.fail("the plan differs from the recorded table in %d lines:\n%s" % (len(diff), "\n".join(diff[:60])))
-    assert got.count("\nS ") == 15 and all(k in got for k in ("none:0", "r32ob", "r32w", "r32a", "regs", "train", "noob"))  # (the table is not empty)
+    assert got.count("\nS ") == 14 and all(k in got for k in ("none:0", "r32ob", "r32w", "r32a", "regs", "train", "noob"))  # (the table is not empty)

@@ -126,11 +126,6 @@ FORM_CASES = [
     ("v128_1_8_32_act", GRID16, 2, 128, 2, "None", "None", 8, 256 * 5, _v(1, 8, 32), "train<128,1,8,32>/act"),
     ("v128_1_4_32_relu", GRID16, 2, 128, 2, "ReLU", "None", 32, 256 * 5, _v(1, 4, 32), "train<128,1,4,32>/relu"),
     ("v128_1_4_32_act", GRID16, 2, 128, 2, "Tanh", "Sigmoid", 5, 256 * 9, _v(1, 4, 32), "train<128,1,4,32>/act"),
-    # the barrier-free private weight-gradient form: 28 tile slots up to 16 outputs, 32 beyond
-    ("pw28_relu", GRID16, 2, 64, 2, "ReLU", "None", 16, 256 * 5, {**R0, "TCNN_AMD_MLP_PW": "1"}, "train_pw28/relu"),
-    ("pw28_act", GRID16, 2, 64, 1, "Tanh", "None", 8, 256 * 7, {**R0, "TCNN_AMD_MLP_PW": "1"}, "train_pw28/act"),
-    ("pw32_relu", GRID16, 2, 64, 2, "ReLU", "None", 32, 256 * 5, {**R0, "TCNN_AMD_MLP_PW": "1"}, "train_pw32/relu"),
-    ("pw32_act", GRID16, 2, 64, 2, "Sigmoid", "Sigmoid", 17, 256 * 9, {**R0, "TCNN_AMD_MLP_PW": "1"}, "train_pw32/act"),
     # all weight fragments in registers: 64 x 2 with <= 32 inputs and 16 padded outputs; REGW=0 sends the same network to the table
     ("regw_relu", GRID32, 2, 64, 2, "ReLU", "None", 16, 256 * 5, {"TCNN_AMD_MLP_REGS": "0"}, "train_regw/relu"),
     ("regw_act", GRID32, 2, 64, 2, "Tanh", "None", 5, 256 * 7, {}, "train_regw/act"),

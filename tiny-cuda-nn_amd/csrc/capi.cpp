@@ -103,6 +103,17 @@ void switches_reload() {
 	if (const char* e = getenv("TCNN_AMD_MLP_PRIO")) w.mlp_prio = (uint32_t)atoi(e);
 	w.listgrad_in_mlp = !env_is("TCNN_AMD_LISTGRAD_IN_MLP", '0');
 	w.mlp_layerwise = env_is("TCNN_AMD_MLP_LAYERWISE", '1');
+	w.mlp_regw = !env_is("TCNN_AMD_MLP_REGW", '0');
+	if (const char* e = getenv("TCNN_AMD_MLP_VARIANT")) { // forced only when all three parse
+		int v[3] = {0, 0, 0};
+		if (sscanf(e, "%d,%d,%d", &v[0], &v[1], &v[2]) == 3) {
+			w.mlp_variant_forced = true;
+			for (int i = 0; i < 3; ++i) w.mlp_variant[i] = v[i];
+		}
+	}
+	w.wgrad_rows = !env_is("TCNN_AMD_WGRAD_ROWS", '0');
+	w.mlp_fwd_lds = !env_is("TCNN_AMD_MLP_FWD_LDS", '0');
+	w.fuse_oneblob = !env_is("TCNN_AMD_FUSE_ONEBLOB", '0');
 	std::lock_guard<std::mutex> lock{g_switches_mutex};
 	g_switches = w;
 }

@@ -496,7 +496,7 @@ BinLayout bin_layout(const GridMeta& meta, const GridMeta* dev_meta, uint32_t n,
 	a.per_sample = (nearest || stochastic) ? 1u : (1u << meta.n_pos_dims); // (stochastic: the one drawn corner)
 	a.tile_contribs = BIN_TILE_CONTRIBS;
 	if (meta.n_features_per_level == 8) a.tile_contribs = BIN_TILE_CONTRIBS / 2; // (20 bytes per contribution in k_bin_fill's LDS instead of 12: half the tile)
-	if (const char* e = getenv("TCNN_AMD_BIN_TILE")) a.tile_contribs = std::min<uint32_t>(std::max(atoi(e), 512), a.tile_contribs); // A/B runs
+	if (const char* e = lab_env("TCNN_AMD_BIN_TILE")) a.tile_contribs = std::min<uint32_t>(std::max(atoi(e), 512), a.tile_contribs); // laboratory knob
 	a.tile_samples = a.tile_contribs >> meta.n_pos_dims; // nearest: the LDS arrays are simply not filled
 	a.n_tiles = div_round_up(n, a.tile_samples);
 	uint32_t max_chunks = 0;
@@ -545,20 +545,16 @@ void launch_binned(hipStream_t s, const BinLayout& l, MatView x, const void* dy,
 	hipLaunchKernelGGL((k_bin_fill<D, F, STOCH>), dim3(a.n_tiles, l.n_slots), dim3(BIN_FILL_THREADS), fill_lds, s, a, x, (const half_t*)dy, dss, dsl, counts, rel, base, idx, val);
 	const uint32_t acc_bytes = grid_bin_acc_bytes();
 	const uint32_t acc_blocks = std::min(l.n_chunks_total, 256u * std::max(1u, (160u * 1024u) / (acc_bytes + 4096u)));
-	static const bool timing = getenv("TCNN_AMD_BIN_TIMING") != nullptr;
-	static int timing_left = 3;
-	unsigned long long* dbg = nullptr;
-	if (timing && timing_left > 0) HIP_CHECK_THROW(hipMalloc(&dbg, acc_blocks * 4 * 8));
+	static DevClocks clocks{"TCNN_AMD_BIN_TIMING", 3}; // (laboratory build: the 3rd launch's times)
+	unsigned long long* dbg = clocks.alloc((size_t)acc_blocks * 4 * 8);
 	hipLaunchKernelGGL((k_bin_accum<F>), dim3(acc_blocks), dim3(BIN_ACC_THREADS), acc_bytes, s, a, l.n_slots, acc_bytes, totals, base, idx, val, (half_t*)grad, accumulate ? 1 : 0, dbg, fallback_count, switches().scatter_wide ? 1 : 0);
 	if (dbg) {
 		std::vector<unsigned long long> h(acc_blocks * 4);
-		HIP_CHECK_THROW(hipMemcpy(h.data(), dbg, h.size() * 8, hipMemcpyDeviceToHost));
-		if (--timing_left == 0) {
+		if (clocks.fetch(dbg, h.data(), h.size())) {
 			double add = 0, flush = 0, total = 0;
 			for (uint32_t b = 0; b < acc_blocks; ++b) { add += h[b * 4] * 0.01; flush += h[b * 4 + 1] * 0.01; total += h[b * 4 + 2] * 0.01; }
 			fprintf(stderr, "k_bin_accum: %u workgroups, %u chunks; per workgroup: adds %.1f us, flush %.1f us, total %.1f us\n", acc_blocks, l.n_chunks_total, add / acc_blocks, flush / acc_blocks, total / acc_blocks);
 		}
-		(void)hipFree(dbg);
 	}
 	HIP_CHECK_THROW(hipGetLastError());
 }
@@ -567,14 +563,12 @@ void launch_binned(hipStream_t s, const BinLayout& l, MatView x, const void* dy,
 
 uint32_t grid_bin_max_chunks() { return BIN_MAX_CHUNKS; }
 
-// LDS accumulators per workgroup of k_bin_accum = chunk size of the binned levels.  TCNN_AMD_BIN_ACC_KB: A/B runs.
+// LDS accumulators per workgroup of k_bin_accum = chunk size of the binned levels.  Laboratory knob TCNN_AMD_BIN_ACC_KB: set it before the
+// encoding is built (grid_scatter_setup_levels cuts the levels by it) and leave it.
 uint32_t grid_bin_acc_bytes() {
-	static const uint32_t v = [] {
-		uint32_t kb = 128;
-		if (const char* e = getenv("TCNN_AMD_BIN_ACC_KB")) kb = (uint32_t)std::min(std::max(atoi(e), 16), 128);
-		return kb * 1024u;
-	}();
-	return v;
+	uint32_t kb = 128;
+	if (const char* e = lab_env("TCNN_AMD_BIN_ACC_KB")) kb = (uint32_t)std::min(std::max(atoi(e), 16), 128);
+	return kb * 1024u;
 }
 
 bool grid_bin_supported(const GridMeta& meta) {

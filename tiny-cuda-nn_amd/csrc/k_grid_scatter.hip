@@ -473,22 +473,19 @@ void launch_scatter(hipStream_t s, const GridMeta* dm, const GridScatterTask* ta
 		HIP_CHECK_THROW(hipFuncSetAttribute((const void*)k_grid_scatter<D, F, REC, STOCH>, hipFuncAttributeMaxDynamicSharedMemorySize, SCATTER_LDS_BYTES));
 		configured = true;
 	}
-	// development aid: TCNN_AMD_SCATTER_TIMING=1 prints per-task phase times (100 MHz constant clock) for the 3rd launch
-	static const bool timing = getenv("TCNN_AMD_SCATTER_TIMING") != nullptr;
-	static int timing_left = 3;
-	unsigned long long* dbg = nullptr;
-	if (timing && timing_left > 0 && !g_task_times) HIP_CHECK_THROW(hipMalloc(&dbg, (size_t)n_tasks * 8 * 8));
+	// laboratory build: TCNN_AMD_SCATTER_TIMING=1 prints per-task phase times (100 MHz constant clock) for the 3rd launch
+	static DevClocks clocks{"TCNN_AMD_SCATTER_TIMING", 3};
+	unsigned long long* dbg = g_task_times ? nullptr : clocks.alloc((size_t)n_tasks * 8 * 8);
 	hipLaunchKernelGGL((k_grid_scatter<D, F, REC, STOCH>), dim3(n_tasks), dim3(SCATTER_THREADS), SCATTER_LDS_BYTES, s, dm, tasks, n, x, (const half_t*)dy, dss, dsl, (half_t*)grad, chunk_bits,
 	                   scratch, accumulate ? 1 : 0, g_task_times ? g_task_times : dbg);
 	HIP_CHECK_THROW(hipGetLastError());
 	if (dbg) {
 		std::vector<unsigned long long> h((size_t)n_tasks * 8);
-		std::vector<GridScatterTask> ht(n_tasks);
-		HIP_CHECK_THROW(hipMemcpy(h.data(), dbg, h.size() * 8, hipMemcpyDeviceToHost));
-		HIP_CHECK_THROW(hipMemcpy(ht.data(), tasks, n_tasks * sizeof(GridScatterTask), hipMemcpyDeviceToHost));
-		unsigned long long t0 = ~0ull;
-		for (uint32_t i = 0; i < n_tasks; ++i) if (ht[i].n_entries) t0 = std::min(t0, h[i * 8]);
-		if (--timing_left == 0) {
+		if (clocks.fetch(dbg, h.data(), h.size())) {
+			std::vector<GridScatterTask> ht(n_tasks);
+			HIP_CHECK_THROW(hipMemcpy(ht.data(), tasks, n_tasks * sizeof(GridScatterTask), hipMemcpyDeviceToHost));
+			unsigned long long t0 = ~0ull;
+			for (uint32_t i = 0; i < n_tasks; ++i) if (ht[i].n_entries) t0 = std::min(t0, h[i * 8]);
 			for (uint32_t i = 0; i < n_tasks; ++i) {
 				if (!ht[i].n_entries) continue;
 				fprintf(stderr, "task %3u level %2u entries %6u samples %6u atomic %u: start %7.1f zero %6.1f accumulate %6.1f flush %6.1f us | wave0 clocks: fetch %llu acc %llu loop %llu submits %llu\n", i, ht[i].level, ht[i].n_entries,
@@ -496,7 +493,6 @@ void launch_scatter(hipStream_t s, const GridMeta* dm, const GridScatterTask* ta
 				        (h[i * 8 + 3] - h[i * 8 + 2]) * 0.01, h[i * 8 + 4], h[i * 8 + 5], h[i * 8 + 6], h[i * 8 + 7]);
 			}
 		}
-		(void)hipFree(dbg);
 	}
 }
 
@@ -573,15 +569,17 @@ void grid_scatter_setup_levels(GridMeta& meta) {
 		// More chunks than the sample filter describes: the level's gradients are binned instead (k_grid_bin.hip).  Where a visit
 		// of the filtered form costs several gathers (no 16-byte records: 3-D with F = 4) binning already wins from 9 chunks on
 		// (measured on C5: the 64-chunk level 2.4x faster; on C3a, with records, the filtered form is 1.5x faster at 64 chunks).
-		// TCNN_AMD_BIN_MIN_CHUNKS=k moves the threshold (levels with more than k chunks are binned), for A/B runs.
+		// Laboratory knob: TCNN_AMD_BIN_MIN_CHUNKS=k moves the threshold (levels with more than k chunks are binned).
 		uint32_t bin_above = grid_scatter_records_supported(meta) ? SCATTER_MAX_CHUNKS : SCATTER_MAX_CHUNKS / 8u;
-		if (const char* e = getenv("TCNN_AMD_BIN_MIN_CHUNKS")) bin_above = std::min<uint32_t>((uint32_t)std::max(atoi(e), 1), SCATTER_MAX_CHUNKS);
+		if (const char* e = lab_env("TCNN_AMD_BIN_MIN_CHUNKS")) bin_above = std::min<uint32_t>((uint32_t)std::max(atoi(e), 1), SCATTER_MAX_CHUNKS);
 		const uint32_t bin_capacity = grid_bin_acc_bytes() / (meta.n_features_per_level * 8); // the binned kernels have their own chunk size
 		lv.scatter_binned = (lv.scatter_n_chunks > bin_above && div_round_up(lv.size, bin_capacity) <= grid_bin_max_chunks() && grid_bin_supported(meta)) ? 1u : 0u;
 		if (lv.scatter_binned) cut(lv, bin_capacity);
 	}
 	bool any_binned = false;
 	for (uint32_t l = 0; l < meta.n_levels; ++l) any_binned |= meta.levels[l].scatter_binned != 0;
+	const char* fine_cut_env = lab_env("TCNN_AMD_SCATTER_FINE_CUT"); // laboratory knob, "0": no finer cut (below)
+	const bool fine_cut = !(fine_cut_env && fine_cut_env[0] == '0');
 	for (uint32_t l = 0; l < meta.n_levels; ++l) {
 		GridLevel& lv = meta.levels[l];
 		// Round 4: a level that fits fewer chunks than the filter can describe is cut finer anyway -- into up to 64 chunks of at least 256
@@ -594,8 +592,7 @@ void grid_scatter_setup_levels(GridMeta& meta) {
 		// 4097 .. 8191 entries was TWO chunks with one owner each, 2^18 elements per task where the others have 8192: 0.79 ms for the launch.
 		// A grid with binned levels never takes the lists (model.h hit_lists_usable), and its bit-plane tasks, split over the samples, serve
 		// such a level better as two chunks than as sixteen: 87 against 110 us.  profiles/r05_shape_sweep.txt.)
-		// TCNN_AMD_SCATTER_FINE_CUT=0: as before.
-		static const bool fine_cut = [] { const char* e = getenv("TCNN_AMD_SCATTER_FINE_CUT"); return !(e && e[0] == '0'); }();
+		// TCNN_AMD_SCATTER_FINE_CUT=0 (laboratory build): as before.
 		const uint32_t cut_from = any_binned ? std::max(capacity, 8192u) : capacity;
 		if (fine_cut && prefers_lists && !lv.scatter_binned && lv.size >= cut_from && lv.scatter_n_chunks < SCATTER_MAX_CHUNKS) {
 			const uint32_t per_chunk = std::min(capacity, std::max(256u, next_multiple(div_round_up(lv.size, SCATTER_MAX_CHUNKS), 8u)));
@@ -648,7 +645,7 @@ static void tuned_splits(const GridMeta& meta, uint32_t n, const std::vector<flo
 		task_us = std::max(w_coarse / n_cus, 4.0);
 	}
 	const uint32_t max_splits = std::max(n / 1024u, 1u);
-	if (getenv("TCNN_AMD_SCATTER_TIMING")) {
+	if (lab_env("TCNN_AMD_SCATTER_TIMING")) {
 		fprintf(stderr, "scatter tuner: n_fine %u w_fine %.1f w_coarse %.1f task_us %.1f; level_us:", n_fine, w_fine, w_coarse, task_us);
 		for (uint32_t l = 0; l < meta.n_levels; ++l) fprintf(stderr, " %.0f", level_us[l]);
 		fprintf(stderr, "\n");
@@ -713,9 +710,9 @@ void grid_scatter_plan(const GridMeta& meta, uint32_t n, std::vector<GridScatter
 	std::vector<uint32_t> tuned(meta.n_levels, 0);
 	if (measured_level_us) tuned_splits(meta, n, *measured_level_us, tuned);
 
-	// profiling aid: TCNN_AMD_SCATTER_LEVELS="lo,hi" restricts the plan to levels lo..hi (results are then incomplete!)
+	// laboratory knob: TCNN_AMD_SCATTER_LEVELS="lo,hi" restricts the plan to levels lo..hi (results are then incomplete!)
 	uint32_t dbg_lo = 0, dbg_hi = meta.n_levels;
-	if (const char* e = getenv("TCNN_AMD_SCATTER_LEVELS")) sscanf(e, "%u,%u", &dbg_lo, &dbg_hi);
+	if (const char* e = lab_env("TCNN_AMD_SCATTER_LEVELS")) sscanf(e, "%u,%u", &dbg_lo, &dbg_hi);
 
 	std::vector<std::vector<GridScatterTask>> per_level(meta.n_levels);
 	for (uint32_t l = 0; l < meta.n_levels; ++l) {

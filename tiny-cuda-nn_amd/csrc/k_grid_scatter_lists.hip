@@ -708,7 +708,7 @@ void launch_lists(hipStream_t s, ScatterListsArgs a, uint32_t n_tasks) {
 	}
 #ifdef TCNN_AMD_DEV
 	// laboratory build: TCNN_AMD_SCATTER_TIMING=1 prints per-task phase times (100 MHz constant clock) of the 3rd launch (tools/scatter_timing.py)
-	static const bool timing = getenv("TCNN_AMD_SCATTER_TIMING") != nullptr;
+	static const bool timing = lab_env("TCNN_AMD_SCATTER_TIMING") != nullptr;
 	static int timing_left = 3;
 	unsigned long long* dbg = nullptr;
 	if (timing && timing_left > 0 && !a.dbg_times) {
@@ -774,9 +774,7 @@ void grid_scatter_lists_plan(const GridMeta& meta, uint32_t n, std::vector<GridS
 	scratch_elems = 0;
 	std::vector<std::pair<double, GridScatterTask>> listed, loose; // (estimated cost, task)
 	uint32_t dbg_lo = 0, dbg_hi = meta.n_levels;
-#ifdef TCNN_AMD_DEV
-	if (const char* e = getenv("TCNN_AMD_SCATTER_LEVELS")) sscanf(e, "%u,%u", &dbg_lo, &dbg_hi); // profiling aid: levels lo..hi only (results are then incomplete!)
-#endif
+	if (const char* e = lab_env("TCNN_AMD_SCATTER_LEVELS")) sscanf(e, "%u,%u", &dbg_lo, &dbg_hi); // laboratory knob: levels lo..hi only (results are then incomplete!)
 	for (uint32_t l = 0; l < meta.n_levels; ++l) {
 		const GridLevel& lv = meta.levels[l];
 		if (lv.scatter_binned || l < dbg_lo || l > dbg_hi) continue; // (binned: grid_backward_binned serves this level)
@@ -855,9 +853,7 @@ bool grid_backward_lists(hipStream_t stream, const GridMeta& meta, const GridMet
 	a.force_wide = switches().scatter_wide ? 1 : 0; // tests: every task through the 64-bit passes
 	a.dbg_times = nullptr;
 	a.fallback_count = fallback_count;
-#ifdef TCNN_AMD_DEV
-	if (const char* e = getenv("TCNN_AMD_SCATTER_DEV")) a.dev_flags = (uint32_t)atoi(e);
-#endif
+	if (const char* e = lab_env("TCNN_AMD_SCATTER_DEV")) a.dev_flags = (uint32_t)atoi(e); // laboratory knob
 	if (!gvals_filled) { // dL/dy into list order (unless the MLP kernel's tail has done that: GridListTail), then the owners
 		ListGradArgs lg{dev_meta, lists, (const half_t*)dL_dy, dy_stride_sample, dy_stride_level, n, (half_t*)gvals};
 		switch (meta.n_features_per_level) {

@@ -801,9 +801,7 @@ void mlp_forward_io(hipStream_t stream, const MlpDesc& d, const void* image, uin
 	if (d.width == 64 && small && hidden == nullptr) return launch_fwd_act<64, 1>(stream, d, a, mlp_grid(n, 1));
 	// wide inference: fragment image in LDS, 4 column blocks per wave, persistent workgroups of 8 waves (see k_mlp_fwd)
 	const uint32_t image_bytes = d.n_frags_fwd * 1024;
-	const char* lds_env = getenv("TCNN_AMD_MLP_FWD_LDS"); // "0": the L2-resident form (A/B runs; read per call so that tests cover both)
-	const bool lds_inference = !(lds_env && lds_env[0] == '0');
-	if (lds_inference && d.width == 128 && hidden == nullptr && image_bytes <= 150 * 1024 && n >= 256 * 8 * 64) {
+	if (d.width == 128 && hidden == nullptr && image_bytes <= 150 * 1024 && n >= 256 * 8 * 64 && switches().mlp_fwd_lds) { // (switch off: the L2-resident form, A/B runs)
 		constexpr int NB = 4, THREADS = 512;
 		const uint32_t grid = std::min<uint32_t>(256, div_round_up(n / (16 * NB), THREADS / 64));
 		auto go = [&](auto kernel) {
@@ -856,11 +854,9 @@ void mlp_reduce_slabs(hipStream_t stream, uint32_t n_params, uint32_t n_slabs, c
 
 size_t wgrad_workspace_floats(uint32_t rows, uint32_t cols, uint32_t n) { return (size_t)wgrad_grid(n) * rows * cols; }
 
-// the shapes k_wgrad_rows / k_wgrad_cols are instantiated for; TCNN_AMD_WGRAD_ROWS=0: k_wgrad for every shape (A/B runs)
-static bool wgrad_fast_shape(uint32_t rows, uint32_t cols) {
-	const char* e = getenv("TCNN_AMD_WGRAD_ROWS"); // (read per call: a test compares the two settings in one process)
-	const bool rows_form = !(e && e[0] == '0');
-	return rows_form && ((rows == 128 || rows == 64) && (cols == 128 || cols == 64 || cols == 32) || (rows == 16 && (cols == 128 || cols == 64)));
+// the shapes k_wgrad_rows / k_wgrad_cols are instantiated for; Switches::wgrad_rows off: k_wgrad for every shape (A/B runs)
+static bool wgrad_fast_shape(const Switches& sw, uint32_t rows, uint32_t cols) {
+	return sw.wgrad_rows && ((rows == 128 || rows == 64) && (cols == 128 || cols == 64 || cols == 32) || (rows == 16 && (cols == 128 || cols == 64)));
 }
 
 static void launch_wgrad_jobs(hipStream_t stream, uint32_t n, uint32_t rows, uint32_t cols, const WgradJobs& jobs, uint32_t n_jobs, bool accumulate) {
@@ -902,6 +898,7 @@ size_t wgrad_panels_workspace_floats(Precision precision, const WgradPanel* pane
 void mlp_wgrad_panels(hipStream_t stream, Precision precision, uint32_t n, const WgradPanel* panels, uint32_t count, bool accumulate, float* workspace) {
 	if (precision == Precision::Fp32) return mlp_wgrad_panels_f32(stream, n, panels, count, accumulate, workspace);
 	CHECK_THROW(n % WG_CHUNK == 0);
+	const Switches sw = switches();
 	std::vector<bool> done(count, false);
 	std::vector<float*> slabs(count);
 	size_t at = 0;
@@ -914,7 +911,7 @@ void mlp_wgrad_panels(hipStream_t stream, Precision precision, uint32_t n, const
 		const WgradPanel& p = panels[i];
 		CHECK_THROW(p.rows % 16 == 0 && p.cols % 16 == 0);
 		CHECK_THROW((p.rows / 16) * (p.cols / 16) <= 4 * WG_MAX_TILES);
-		if (wgrad_fast_shape(p.rows, p.cols)) {
+		if (wgrad_fast_shape(sw, p.rows, p.cols)) {
 			WgradJobs jobs{};
 			uint32_t n_jobs = 0;
 			for (uint32_t j = i; j < count && n_jobs < WG_MAX_JOBS; ++j) {

@@ -65,17 +65,11 @@ struct TrainArgs {
 // A operand of an MFMA: register slot (REGW) or a 16-byte load from the fragment image
 #define TCNN_FRAG(slot, load_expr) ([&]() -> h8 { if constexpr (REGW) return rw[(slot)]; else return (load_expr); }())
 
-// PW ("private weight gradients"): every wave accumulates ALL weight-gradient tiles over its own 16 samples per trip
-// (v_mfma_f32_16x16x16_f16, k = the wave's 16 rows of the LDS images) instead of sharing the tiles and the k axis with the
-// other waves.  Nothing a wave reads was written by another wave, so the trip loop needs no workgroup barrier at all -- the
-// two barriers per trip were where the shared form spent most of its time.  Costs 2x the (cheap) MFMA work and 128
-// accumulator registers; the waves' partial sums are combined through LDS once, after the last trip.
-// Requires NB == 1, W == 64, n_hidden <= 2, in_width <= 32, out_width <= 32 (static tile slots: 8 + 16 + 8).
 // REGW ("weights in registers"): a 64-wide network with two hidden layers, <= 32 inputs and 16 outputs has 14 forward and
 // 16 backward weight fragments -- 120 VGPRs per lane.  Held in registers for the whole kernel, every MFMA of a trip takes its
 // A operand from a register instead of waiting on a 1 KB LDS (or L2) fetch, and the fragment images need no LDS space.
 // OB: the input is the OneBlob encoding of a.ob_x, evaluated in the layer-0 loop (see k_mlp_fwd in k_mlp.hip for the scheme)
-template <int W, int NB, int NW, int MAXT, int ACT, bool PW = false, bool REGW = false, bool OB = false>
+template <int W, int NB, int NW, int MAXT, int ACT, bool REGW = false, bool OB = false>
 __global__ void __launch_bounds__(NW * 64) k_mlp_train(const MlpDesc d, const TrainArgs a) {
 	constexpr int T = W / 16;
 	constexpr int KS = (T + 1) / 2;
@@ -503,53 +497,6 @@ __global__ void __launch_bounds__(NW * 64) k_mlp_train(const MlpDesc d, const Tr
 		}
 
 		// =================================================================== phase B: weight gradients from the LDS images
-		if constexpr (PW) {
-			if (a.slabs) {
-				// transposing reads (see the shared form below), k = this wave's 16 rows: lane (li, grp) gets rows 4 grp .. 4 grp + 3 of column li
-				const uint32_t grp = lane >> 4, li = lane & 15;
-				const uint32_t rowp = row0 + 4 * grp + (li >> 2), colo = 4 * (li & 3);
-				auto frag = [&](uint32_t image_off, uint32_t stride, uint32_t tile) { return lds_read_tr(lds + image_off + rowp * stride + 16 * tile + colo); };
-				// slots 0..7: dW0 = dH_0^T X (T x in_w/16 tiles)
-				{
-					h4 bx[2];
-#pragma unroll
-					for (int tc = 0; tc < 2; ++tc) bx[tc] = 16 * tc < (int)in_w ? frag(xs_off, xs_stride, tc) : h4{0, 0, 0, 0};
-#pragma unroll
-					for (int tr = 0; tr < T; ++tr) {
-						const h4 af = frag(dhs_off, hs_stride, tr);
-#pragma unroll
-						for (int tc = 0; tc < 2; ++tc) wacc[tr * 2 + tc] = mfma16(af, bx[tc], wacc[tr * 2 + tc]);
-					}
-				}
-				// slots 8..23: dW1 = dH_1^T H_0 (T x T tiles), only with two hidden layers
-				if (nh == 2) {
-					h4 bh[T];
-#pragma unroll
-					for (int tc = 0; tc < T; ++tc) bh[tc] = frag(hs_off, hs_stride, tc);
-#pragma unroll
-					for (int tr = 0; tr < T; ++tr) {
-						const h4 af = frag(dhs_off + S * hs_stride, hs_stride, tr);
-#pragma unroll
-						for (int tc = 0; tc < T; ++tc) wacc[8 + tr * T + tc] = mfma16(af, bh[tc], wacc[8 + tr * T + tc]);
-					}
-				}
-				// slots 24..31: dWout = dY^T H_last (out_w/16 x T tiles)
-				{
-					h4 bh[T];
-#pragma unroll
-					for (int tc = 0; tc < T; ++tc) bh[tc] = frag(hs_off + (nh - 1) * S * hs_stride, hs_stride, tc);
-#pragma unroll
-					for (int to = 0; to < (MAXT - 24) / T; ++to) {
-						if (to < (int)m_out) {
-							const h4 af = frag(dys_off, dys_stride, to);
-#pragma unroll
-							for (int tc = 0; tc < T; ++tc) wacc[24 + to * T + tc] = mfma16(af, bh[tc], wacc[24 + to * T + tc]);
-						}
-					}
-				}
-			}
-			continue; // no barrier: the next trip overwrites only this wave's own rows
-		}
 		TCNN_T(3);
 		lds_barrier();
 		TCNN_T(4);
@@ -581,50 +528,6 @@ __global__ void __launch_bounds__(NW * 64) k_mlp_train(const MlpDesc d, const Tr
 		TCNN_T(6);
 	}
 
-	if constexpr (PW) {
-		if (a.slabs) {
-			// combine the waves' partial sums in LDS (plain read-add-write, one wave at a time: LDS float atomics are slow), then
-			// write the workgroup's slab with coalesced stores
-			float* red = (float*)smem;
-			const uint32_t grp = lane >> 4, li = lane & 15;
-			__syncthreads(); // every wave is done with the images
-			for (uint32_t w = 0; w < (uint32_t)NW; ++w) {
-				if (wave == w) {
-					auto put = [&](const f4& v, uint32_t out, uint32_t ld) {
-#pragma unroll
-						for (int r = 0; r < 4; ++r) {
-							float* p = red + out + (size_t)(4 * grp + r) * ld + li;
-							*p = w == 0 ? v[r] : *p + v[r];
-						}
-					};
-					const MlpLayer L0 = d.layers[0];
-#pragma unroll
-					for (int tr = 0; tr < T; ++tr)
-#pragma unroll
-						for (int tc = 0; tc < 2; ++tc)
-							if (16 * tc < (int)in_w) put(wacc[tr * 2 + tc], L0.w_off + 16 * tr * L0.cols + 16 * tc, L0.cols);
-					if (nh == 2) {
-						const MlpLayer L1 = d.layers[1];
-#pragma unroll
-						for (int tr = 0; tr < T; ++tr)
-#pragma unroll
-							for (int tc = 0; tc < T; ++tc) put(wacc[8 + tr * T + tc], L1.w_off + 16 * tr * L1.cols + 16 * tc, L1.cols);
-					}
-					const MlpLayer Lo = d.layers[d.n_layers - 1];
-#pragma unroll
-					for (int to = 0; to < (MAXT - 24) / T; ++to)
-						if (to < (int)m_out) {
-#pragma unroll
-							for (int tc = 0; tc < T; ++tc) put(wacc[24 + to * T + tc], Lo.w_off + 16 * to * Lo.cols + 16 * tc, Lo.cols);
-						}
-				}
-				__syncthreads();
-			}
-			float* slab = a.slabs + (size_t)blockIdx.x * a.n_params;
-			for (uint32_t i = tid; i < a.n_params; i += NW * 64) slab[i] = red[i];
-		}
-		return;
-	}
 	if (a.dbg && blockIdx.x == 0 && tid == 0) {
 		for (int i = 0; i < 8; ++i) a.dbg[i] = tcnn_t[i];
 	}
@@ -642,7 +545,7 @@ __global__ void __launch_bounds__(NW * 64) k_mlp_train(const MlpDesc d, const Tr
 	}
 }
 
-using TrainConfig = MlpTrainPlan::Config; // ok, (nb, nw, maxt): the instance; s: samples per trip; pw / regw: the special forms below
+using TrainConfig = MlpTrainPlan::Config; // ok, (nb, nw, maxt): the instance; s: samples per trip; regw: the special form below
 
 // (NB, NW, MAXT) triples that are instantiated; pick_config only ever returns one of them
 struct TrainVariant { int width_class, nb, nw, maxt; }; // width_class: 64 or 128
@@ -651,7 +554,7 @@ constexpr TrainVariant TRAIN_VARIANTS[] = {
 	{128, 1, 8, 16}, {128, 1, 8, 32}, {128, 1, 4, 32},
 };
 
-inline TrainConfig pick_config(const MlpDesc& d) {
+inline TrainConfig pick_config(const MlpDesc& d, const Switches& sw) {
 	TrainConfig cfg{};
 	cfg.ok = false;
 	if (d.out_width > 32 || d.n_hidden < 1 || (d.width != 64 && d.width != 128)) return cfg;
@@ -659,31 +562,8 @@ inline TrainConfig pick_config(const MlpDesc& d) {
 	for (uint32_t l = 0; l < d.n_layers; ++l) total_tiles += (d.layers[l].rows / 16) * (d.layers[l].cols / 16);
 	const uint32_t image_bytes = (d.n_frags_fwd + d.n_frags_bwd) * 1024;
 	const uint32_t budget = 160 * 1024 - 512;
-	// TCNN_AMD_MLP_PW=1 selects the barrier-free private weight-gradient form.  Off by default: measured on C3a it takes 92 us
-	// against 78 us for the shared form -- the trips are bound by dependent LDS-read -> MFMA chains at 2 waves per SIMD, not
-	// by the barriers, and the private form doubles the MFMA and accumulator work.  Read per call so that tests can cover both.
-	const char* pw_env = getenv("TCNN_AMD_MLP_PW");
-	const bool pw_allowed = pw_env && pw_env[0] == '1';
-	if (pw_allowed && d.width == 64 && d.n_hidden <= 2 && d.in_width <= 32 && d.out_width <= 32) {
-		const uint32_t s = 8 * 16;
-		const uint32_t images = 2 * s * ((d.in_width + TR_PAD) + 2 * d.n_hidden * (d.width + hs_pad((int)d.width)) + (d.out_width + TR_PAD));
-		size_t n_params = 0;
-		for (uint32_t l = 0; l < d.n_layers; ++l) n_params += (size_t)d.layers[l].rows * d.layers[l].cols;
-		if (images + image_bytes <= budget && n_params * sizeof(float) <= images) { // the final reduction reuses the image space
-			cfg.nb = 1;
-			cfg.nw = 8;
-			cfg.maxt = d.out_width <= 16 ? 28 : 32; // 8 + 16 + 4 (or 8) tile slots
-			cfg.s = s;
-			cfg.lds_bytes = images + image_bytes;
-			cfg.image_in_lds = true;
-			cfg.pw = true;
-			cfg.ok = true;
-			return cfg;
-		}
-	}
 	// 64 x 2 networks with <= 32 inputs and 16 outputs: all 30 weight fragments live in registers (TCNN_AMD_MLP_REGW=0: A/B runs)
-	const char* regw_env = getenv("TCNN_AMD_MLP_REGW");
-	if (!(regw_env && regw_env[0] == '0') && d.width == 64 && d.n_hidden == 2 && d.in_width <= 32 && d.out_width == 16 && d.layers[0].ks_fwd == 1) {
+	if (sw.mlp_regw && d.width == 64 && d.n_hidden == 2 && d.in_width <= 32 && d.out_width == 16 && d.layers[0].ks_fwd == 1) {
 		const uint32_t s = 8 * 16;
 		cfg.nb = 1;
 		cfg.nw = 8;
@@ -699,15 +579,12 @@ inline TrainConfig pick_config(const MlpDesc& d) {
 	// at most 2) wins; among equals, the one whose weight images fit in LDS next to the activation images, then table order.
 	// (Preferring "images in LDS" outright picked a 4-wave workgroup for C2 -- 128 inputs, 56 KB of fragments -- and ran at one
 	// wave per SIMD: 84 us per step against 68 us with 8 waves and the images in L2.)
-	const char* img_env = getenv("TCNN_AMD_MLP_IMAGE_LDS"); // development aid: "0" keeps the weight images in L2
+	const char* img_env = lab_env("TCNN_AMD_MLP_IMAGE_LDS"); // laboratory knob: "0" keeps the weight images in L2
 	uint32_t best_waves = 0;
 	for (int pass = (img_env && img_env[0] == '0') ? 1 : 0; pass < 2; ++pass) {
 		for (const TrainVariant& v : TRAIN_VARIANTS) {
 			if (v.width_class != (int)d.width) continue;
-			if (const char* e = getenv("TCNN_AMD_MLP_VARIANT")) { // development aid: "nb,nw,maxt" forces one instantiated variant
-				int nb = 0, nw = 0, maxt = 0;
-				if (sscanf(e, "%d,%d,%d", &nb, &nw, &maxt) == 3 && (nb != v.nb || nw != v.nw || maxt != v.maxt)) continue;
-			}
+			if (sw.mlp_variant_forced && (sw.mlp_variant[0] != v.nb || sw.mlp_variant[1] != v.nw || sw.mlp_variant[2] != v.maxt)) continue; // one instantiated variant forced
 			const uint32_t s = v.nw * v.nb * 16;
 			const uint32_t bytes = 2 * s * ((d.in_width + TR_PAD) + 2 * d.n_hidden * (d.width + hs_pad((int)d.width)) + (d.out_width + TR_PAD)) + (pass == 0 ? image_bytes : 0);
 			const uint32_t per = (total_tiles + v.nw - 1) / v.nw;
@@ -729,21 +606,19 @@ inline TrainConfig pick_config(const MlpDesc& d) {
 
 // The instance of k_mlp_train a plan names.  run == false: only its short name (Trainer::last_step_kernel) is wanted -- a static string,
 // ".../relu" or ".../act" (ACT = -1, activation chosen at run time); nullptr: no such instance.
-template <int W, int NB, int NW, int MAXT, bool PW = false, bool REGW = false, bool OB = false>
+template <int W, int NB, int NW, int MAXT, bool REGW = false, bool OB = false>
 const char* train_instance(const char* stem, bool run, hipStream_t stream, const MlpDesc& d, const TrainArgs& a, uint32_t grid, uint32_t lds_bytes) {
 	static const std::string relu_name = (stem ? std::string{stem} : "train<" + std::to_string(W) + "," + std::to_string(NB) + "," + std::to_string(NW) + "," + std::to_string(MAXT) + ">") + "/relu";
 	static const std::string act_name = relu_name.substr(0, relu_name.size() - 4) + "act";
 	const bool relu = d.activation == (uint32_t)Activation::ReLU;
-	if (run && relu) launch_with_lds(k_mlp_train<W, NB, NW, MAXT, (int)Activation::ReLU, PW, REGW, OB>, stream, grid, NW * 64, lds_bytes, d, a);
-	else if (run) launch_with_lds(k_mlp_train<W, NB, NW, MAXT, -1, PW, REGW, OB>, stream, grid, NW * 64, lds_bytes, d, a);
+	if (run && relu) launch_with_lds(k_mlp_train<W, NB, NW, MAXT, (int)Activation::ReLU, REGW, OB>, stream, grid, NW * 64, lds_bytes, d, a);
+	else if (run) launch_with_lds(k_mlp_train<W, NB, NW, MAXT, -1, REGW, OB>, stream, grid, NW * 64, lds_bytes, d, a);
 	return (relu ? relu_name : act_name).c_str();
 }
 
 const char* dispatch_train(bool run, hipStream_t stream, const MlpDesc& d, const TrainArgs& a, const TrainConfig& cfg, bool oneblob, uint32_t grid) {
-	if (cfg.pw && cfg.maxt == 28) return train_instance<64, 1, 8, 28, true>("train_pw28", run, stream, d, a, grid, cfg.lds_bytes);
-	if (cfg.pw) return train_instance<64, 1, 8, 32, true>("train_pw32", run, stream, d, a, grid, cfg.lds_bytes);
-	if (cfg.regw) return train_instance<64, 1, 8, 8, false, true>("train_regw", run, stream, d, a, grid, cfg.lds_bytes);
-	if (oneblob) return train_instance<64, 1, 8, 8, false, false, true>("train_ob", run, stream, d, a, grid, cfg.lds_bytes); // one shape (C2's): oneblob_takes
+	if (cfg.regw) return train_instance<64, 1, 8, 8, true>("train_regw", run, stream, d, a, grid, cfg.lds_bytes);
+	if (oneblob) return train_instance<64, 1, 8, 8, false, true>("train_ob", run, stream, d, a, grid, cfg.lds_bytes); // one shape (C2's): oneblob_takes
 #define TCNN_TRAIN_CASE(W_, NB_, NW_, MAXT_) \
 	if ((int)d.width == W_ && cfg.nb == NB_ && cfg.nw == NW_ && cfg.maxt == MAXT_) return train_instance<W_, NB_, NW_, MAXT_>(nullptr, run, stream, d, a, grid, cfg.lds_bytes);
 	TCNN_TRAIN_CASE(64, 1, 8, 8)
@@ -762,7 +637,7 @@ bool train_config_takes(const TrainConfig& cfg, uint32_t n) { return cfg.ok && n
 // A OneBlob encoding of n_bins bins can be evaluated inside the kernel: by r32ob and by the one train_ob instance (C2's shape), for
 // networks and batches with that configuration of k_train.hip -- never by the family of k_train_regs.hip (regs: regs_shape)
 bool oneblob_takes(const MlpDesc& d, uint32_t n, uint32_t n_bins, bool regs, const TrainConfig& cfg) {
-	return n_bins >= 32 && (n_bins & (n_bins - 1)) == 0 && !regs && train_config_takes(cfg, n) && d.width == 64 && cfg.nb == 1 && cfg.nw == 8 && cfg.maxt == 8 && !cfg.pw && !cfg.regw;
+	return n_bins >= 32 && (n_bins & (n_bins - 1)) == 0 && !regs && train_config_takes(cfg, n) && d.width == 64 && cfg.nb == 1 && cfg.nw == 8 && cfg.maxt == 8 && !cfg.regw;
 }
 // workgroups of k_mlp_train: a trip each, up to two per CU where their LDS allows it
 uint32_t train_grid(const TrainConfig& cfg, uint32_t n) {
@@ -783,8 +658,8 @@ MlpTrainPlan mlp_train_plan(const MlpDesc& d, const MlpTrainRequest& r) {
 	const Switches sw = switches();
 	TrainConfig cfg{};
 	bool cfg_picked = false;
-	auto config = [&]() -> const TrainConfig& { // k_train.hip's configuration, read from the environment at most once and only where it is asked
-		if (!cfg_picked) cfg = pick_config(d);
+	auto config = [&]() -> const TrainConfig& { // k_train.hip's configuration, worked out at most once and only where it is asked
+		if (!cfg_picked) cfg = pick_config(d, sw);
 		cfg_picked = true;
 		return cfg;
 	};
@@ -808,9 +683,15 @@ MlpTrainPlan mlp_train_plan(const MlpDesc& d, const MlpTrainRequest& r) {
 	return p;
 }
 
-bool mlp_train_any_kernel(const MlpDesc& d, uint32_t n) { return regs_shape(d, n, switches()) || train_config_takes(pick_config(d), n); }
+bool mlp_train_any_kernel(const MlpDesc& d, uint32_t n) {
+	const Switches sw = switches();
+	return regs_shape(d, n, sw) || train_config_takes(pick_config(d, sw), n);
+}
 
-bool mlp_train_oneblob_in_kernel(const MlpDesc& d, uint32_t n, uint32_t n_bins) { return oneblob_takes(d, n, n_bins, regs_shape(d, n, switches()), pick_config(d)); }
+bool mlp_train_oneblob_in_kernel(const MlpDesc& d, uint32_t n, uint32_t n_bins) {
+	const Switches sw = switches();
+	return oneblob_takes(d, n, n_bins, regs_shape(d, n, sw), pick_config(d, sw));
+}
 
 bool mlp_train_compact_context(const MlpDesc& d, uint32_t n) { return regs_shape(d, n, switches()); }
 
@@ -838,7 +719,7 @@ void mlp_train_launch(hipStream_t stream, const MlpDesc& d, const MlpTrainPlan& 
 		a.ob_dims = r.oneblob_dims;
 		while ((1u << a.ob_log2) < r.oneblob_bins) ++a.ob_log2;
 	}
-	static DevClocks clocks; // (laboratory build)
+	static DevClocks clocks{"TCNN_AMD_MLP_TIMING"}; // (laboratory build)
 	a.dbg = clocks.alloc(64);
 	dispatch_train(true, stream, d, a, cfg, r.oneblob_bins != 0, p.grid);
 	unsigned long long h[8];

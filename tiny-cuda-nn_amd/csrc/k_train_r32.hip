@@ -435,10 +435,7 @@ bool r32_plan(const MlpDesc& d, const MlpTrainRequest& r, const Switches& sw, Ml
 	p.name = r32a ? "r32a" : "r32";
 	if (r32a) {
 		uint32_t cap = 512u;
-#ifdef TCNN_AMD_DEV
-		static const uint32_t dev_cap = getenv("TCNN_AMD_MLP_GRID") ? (uint32_t)std::max(1, atoi(getenv("TCNN_AMD_MLP_GRID"))) : 512u; // laboratory knob
-		cap = dev_cap;
-#endif
+		if (const char* e = lab_env("TCNN_AMD_MLP_GRID")) cap = (uint32_t)std::max(1, atoi(e)); // laboratory knob
 		p.grid = std::max(1u, std::min(cap, div_round_up(r.n / 32, (uint32_t)R32A_NW))); // two workgroups of four waves per CU
 	} else p.grid = std::max(1u, std::min(256u, div_round_up(r.n / 32, (uint32_t)R32_NW)));
 	return true;
@@ -491,10 +488,10 @@ void r32_launch(hipStream_t stream, const MlpDesc& d, const MlpTrainPlan& p, con
 #else
 	// ---- laboratory build (build.py --dev): in-kernel clocks (TCNN_AMD_MLP_TIMING), timing-only kernel variants (TCNN_AMD_MLP_DIAG), start
 	// delays (TCNN_AMD_MLP_STAGGER), workgroup placement (TCNN_AMD_MLP_WHERE).  None of this is in the product library.
-	static DevClocks clocks;
+	static DevClocks clocks{"TCNN_AMD_MLP_TIMING"};
 	a.dbg = clocks.alloc((size_t)grid * 1024);
-	if (const char* e = getenv("TCNN_AMD_MLP_STAGGER")) a.stagger = (uint32_t)atoi(e);
-	static const int diag_env = getenv("TCNN_AMD_MLP_DIAG") ? atoi(getenv("TCNN_AMD_MLP_DIAG")) : 0;
+	if (const char* e = lab_env("TCNN_AMD_MLP_STAGGER")) a.stagger = (uint32_t)atoi(e);
+	static const int diag_env = lab_env("TCNN_AMD_MLP_DIAG") ? atoi(lab_env("TCNN_AMD_MLP_DIAG")) : 0;
 	const int diag = a.rec_x ? diag_env : 0; // (the timing-only variants exist in the record form)
 	if (r32a) {
 		r32a_launch(stream, a, grid, loss == LossType::L2 ? 1 : 2);
@@ -522,7 +519,7 @@ void r32_launch(hipStream_t stream, const MlpDesc& d, const MlpTrainPlan& p, con
 						by_half[g >= grid / 2] += en / (grid / 2);
 						by_xcd[g % 8] += en / (grid / 8);
 					}
-					if (getenv("TCNN_AMD_MLP_WHERE")) { // one line per workgroup: XCC, SE, CU, start and end in us
+					if (lab_env("TCNN_AMD_MLP_WHERE")) { // one line per workgroup: XCC, SE, CU, start and end in us
 						for (uint32_t g = 0; g < grid; ++g) {
 							const unsigned long long hw = hst[g * 4 + 1];
 							fprintf(stderr, "  wg %u xcc %llu se %llu cu %llu start %.2f end %.2f\n", g, (hw >> 32) & 15, (hw >> 13) & 7, (hw >> 8) & 15, (hst[(size_t)grid * 4 + g * 2] - s0) * 0.01,

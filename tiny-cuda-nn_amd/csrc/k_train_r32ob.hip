@@ -644,9 +644,7 @@ bool r32ob_plan(const MlpDesc& d, const MlpTrainRequest& r, const Switches& sw, 
 	// products behind the chain instead of inside it) -- they win up to 4 trips per wave (131 072 samples), the per-wave accumulators beyond
 	// (the reference's benchmark protocol at 2^21 samples: 6.8e9 against 5.95e9 samples/s).  TCNN_AMD_MLP_R32OB_FORM=shared|acc forces one.
 	p.r32ob_shared = div_round_up(r.n / 32, p.grid * OB_NW) <= 4;
-#ifdef TCNN_AMD_DEV
-	if (const char* e = getenv("TCNN_AMD_MLP_R32OB_FORM")) p.r32ob_shared = e[0] == 's';
-#endif
+	if (const char* e = lab_env("TCNN_AMD_MLP_R32OB_FORM")) p.r32ob_shared = e[0] == 's'; // laboratory knob
 	return true;
 }
 
@@ -666,7 +664,7 @@ void r32ob_launch(hipStream_t stream, const MlpDesc& d, const MlpTrainPlan& p, c
 	a.n_params = in.n_params;
 	for (int l = 0; l < 3; ++l) a.w_off[l] = d.layers[l].w_off;
 	a.loss_scale = in.loss_scale;
-	static DevClocks clocks; // (laboratory build)
+	static DevClocks clocks{"TCNN_AMD_MLP_TIMING"}; // (laboratory build)
 	a.dbg = clocks.alloc((size_t)grid * 48);
 	if (shared) {
 		if (l2) launch_with_lds(k_mlp_train_r32ob<1>, stream, grid, OB_NW * 64, OB_LDS_BYTES, a);

@@ -329,7 +329,7 @@ void r32w_launch(hipStream_t stream, const MlpDesc& d, const MlpTrainPlan& p, co
 	a.n_params = in.n_params;
 	for (int l = 0; l < 3; ++l) a.w_off[l] = d.layers[l].w_off;
 	a.loss_scale = in.loss_scale;
-	static DevClocks clocks; // (laboratory build)
+	static DevClocks clocks{"TCNN_AMD_MLP_TIMING"}; // (laboratory build)
 	a.dbg = clocks.alloc((size_t)grid * 32);
 	if (p.request.loss == LossType::L2) launch_with_lds(k_mlp_train_r32w<1>, stream, grid, W_NW * 64, W_LDS_BYTES, a);
 	else launch_with_lds(k_mlp_train_r32w<2>, stream, grid, W_NW * 64, W_LDS_BYTES, a);

@@ -558,7 +558,7 @@ template <int IN_T, int NH> void launch_regs(hipStream_t stream, const MlpDesc& 
 	constexpr int RELU = (int)Activation::ReLU, NONE = (int)Activation::None;
 	if constexpr (IN_T == 2 && NH == 2) {
 #ifdef TCNN_AMD_DEV
-		static const bool phases = getenv("TCNN_AMD_MLP_TIMING") && getenv("TCNN_AMD_MLP_TIMING")[0] == '2';
+		static const bool phases = lab_env("TCNN_AMD_MLP_TIMING") && lab_env("TCNN_AMD_MLP_TIMING")[0] == '2';
 		if (phases && a.dbg && fast && loss == 2) return go(k_mlp_train_regs<IN_T, NH, RELU, 2, true, true>);
 #endif
 	}
@@ -600,9 +600,7 @@ bool regs_shape(const MlpDesc& d, uint32_t n, const Switches& sw) {
 
 uint32_t regs_grid(uint32_t n) {
 	uint32_t cap = 256;
-#ifdef TCNN_AMD_DEV
-	if (const char* e = getenv("TCNN_AMD_MLP_GRID")) cap = std::max(1, atoi(e)); // laboratory knob (how the trip time depends on the number of busy CUs: it does not)
-#endif
+	if (const char* e = lab_env("TCNN_AMD_MLP_GRID")) cap = std::max(1, atoi(e)); // laboratory knob (how the trip time depends on the number of busy CUs: it does not)
 	return std::max(1u, std::min(cap, div_round_up(n / 16, (uint32_t)REGS_NW)));
 }
 
@@ -629,7 +627,7 @@ void regs_launch(hipStream_t stream, const MlpDesc& d, const MlpTrainPlan& p, co
 	           in.dx_record_x, n, r.dims, r.dx_record_dims, r.x_plane_features, r.dx_plane_features, in.n_params, in.loss_scale, 1u, nullptr};
 	a.prio_mode = switches().mlp_prio;
 	const int loss_id = r.external_dL_dy ? 0 : (r.loss == LossType::L2 ? 1 : 2);
-	static DevClocks clocks; // (laboratory build)
+	static DevClocks clocks{"TCNN_AMD_MLP_TIMING"}; // (laboratory build)
 	a.dbg = clocks.alloc((size_t)grid * (32 + 8 * REGS_NW + 64));
 	if (p.regs_in_tiles == 2 && p.regs_hidden == 2) launch_regs<2, 2>(stream, d, a, grid, loss_id, p.regs_fast);
 	else if (p.regs_in_tiles == 1 && p.regs_hidden == 2) launch_regs<1, 2>(stream, d, a, grid, loss_id, p.regs_fast);

@@ -7,8 +7,6 @@
 
 #include "tcnn_common.h"
 
-#include <cstdlib>
-
 namespace tcnn_amd {
 
 // the one way these kernels are launched: raise the kernel's dynamic-LDS limit, launch, check
@@ -17,31 +15,6 @@ template <typename K, typename... A> void launch_with_lds(K kernel, hipStream_t 
 	hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds_bytes, stream, args...);
 	HIP_CHECK_THROW(hipGetLastError());
 }
-
-// Laboratory build (build.py --dev) with TCNN_AMD_MLP_TIMING set: the in-kernel clocks of a launch site's 5th launch.  A launch function
-// keeps one static DevClocks; in the product library alloc() is nullptr, fetch() is false and the printing behind it is dead code.
-struct DevClocks {
-	int left = 5;
-	// a zeroed buffer for the kernel's `dbg` argument while the site's launches are still counted, else nullptr
-	unsigned long long* alloc(size_t bytes) const {
-		unsigned long long* dbg = nullptr;
-#ifdef TCNN_AMD_DEV
-		static const bool timing = getenv("TCNN_AMD_MLP_TIMING") != nullptr;
-		if (timing && left > 0) {
-			HIP_CHECK_THROW(hipMalloc(&dbg, bytes));
-			HIP_CHECK_THROW(hipMemset(dbg, 0, bytes));
-		}
-#endif
-		return dbg;
-	}
-	// after the launch: the first `count` clocks to the host, the buffer freed; true on the launch whose clocks are to be printed
-	bool fetch(unsigned long long* dbg, unsigned long long* host, size_t count) {
-		if (!dbg) return false;
-		HIP_CHECK_THROW(hipMemcpy(host, dbg, count * 8, hipMemcpyDeviceToHost));
-		(void)hipFree(dbg);
-		return --left == 0;
-	}
-};
 
 inline bool loss_l2_or_relative(const MlpTrainRequest& r) { return !r.external_dL_dy && (r.loss == LossType::L2 || r.loss == LossType::RelativeL2); }
 

@@ -518,9 +518,7 @@ public:
 			hl.counts = hc.sets[hc.next].as<uint32_t>();
 			hl.zero_counts = hc.sets[hc.next ^ 1].as<uint32_t>();
 			hc.next ^= 1;
-#ifdef TCNN_AMD_DEV
-			if (const char* e = getenv("TCNN_AMD_FWD_LISTS_DEV")) hl.dev_flags = (uint32_t)atoi(e); // 1: no copy-out, 2: plain instead of streamed stores, 4: no offsets (1 and 4: wrong results)
-#endif
+			if (const char* e = lab_env("TCNN_AMD_FWD_LISTS_DEV")) hl.dev_flags = (uint32_t)atoi(e); // 1: no copy-out, 2: plain instead of streamed stores, 4: no offsets (1 and 4: wrong results)
 			ctx.hit_generation = ++hc.generation;
 			ctx.hit_stream = (const void*)stream;
 			ctx.n = n;
@@ -901,9 +899,8 @@ public:
 	}
 	uint32_t input_width() const override { return m_n_dims; }
 	uint32_t output_width() const override { return m_n_dims * m_n_bins; }
-	uint32_t as_oneblob() const override { // TCNN_AMD_FUSE_ONEBLOB=0: always the encoding's own kernel (A/B runs, tests)
-		const char* e = getenv("TCNN_AMD_FUSE_ONEBLOB");
-		return (!m_fp32 && m_n_bins >= 32 && !(e && e[0] == '0')) ? m_n_bins : 0;
+	uint32_t as_oneblob() const override { // Switches::fuse_oneblob off: always the encoding's own kernel (A/B runs, tests)
+		return (!m_fp32 && m_n_bins >= 32 && switches().fuse_oneblob) ? m_n_bins : 0;
 	}
 	EncodingContext forward(hipStream_t stream, uint32_t n, MatView x, const void* params, void* out, bool prepare_input_gradients, bool prepare_param_gradients, const ForwardPlan* plan) override {
 		if (out && padded_output_width() > 0) oneblob_forward(stream, m_fp32, n, m_n_dims, m_n_bins, x, out, padded_output_width());

@@ -8,6 +8,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <cstdlib>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -43,6 +44,7 @@ inline uint32_t div_round_up(uint32_t v, uint32_t d) { return (v + d - 1) / d; }
 // capi.cpp) -- not per step -- and the set is PROCESS-WIDE: creating a model under another environment changes the kernels of every live
 // model from its next pass on (reads and the reload are serialised by a lock; a grid's backward pass follows its forward pass: GridForwardRoute).
 // A process that wants another setting sets the variable and creates its models afterwards; tests that compare two settings build one model at a time.
+// switches_reload() is the ONLY reader of the environment in the product library: a consumer is handed a copy, or takes one (switches()) once per call.
 struct Switches {
 	bool grid_planes = true;      // TCNN_AMD_GRID_PLANES=0: the AoS forward kernel inside the fused training step
 	bool grid_rows_planes = true; // TCNN_AMD_GRID_ROWS_PLANES=0: callers that want the encoded batch as a matrix get k_grid_fwd (AoS) instead of the plane kernel + a transposition
@@ -65,9 +67,47 @@ struct Switches {
 	uint32_t mlp_prio = 1;        // TCNN_AMD_MLP_PRIO: wave priorities of the MLP kernels (0 none, 1 alternating per trip, 2, 3)
 	bool listgrad_in_mlp = true;  // TCNN_AMD_LISTGRAD_IN_MLP=0: k_grid_list_gradients as a launch of its own instead of the tail of k_mlp_train_r32
 	bool mlp_layerwise = false;   // TCNN_AMD_MLP_LAYERWISE=1: every network of a model created now runs the layer-by-layer kernels (k_mlp_layers.hip)
+	bool mlp_regw = true;         // TCNN_AMD_MLP_REGW=0: k_mlp_train reads its weight fragments from the images instead of holding them in registers
+	bool mlp_variant_forced = false; // TCNN_AMD_MLP_VARIANT=nb,nw,maxt (all three must parse): k_train.hip's table offers that instance of k_mlp_train alone
+	int mlp_variant[3] = {0, 0, 0};  //   nb, nw, maxt
+	bool wgrad_rows = true;       // TCNN_AMD_WGRAD_ROWS=0: mlp_wgrad_panels runs k_wgrad for every shape, never k_wgrad_rows / k_wgrad_cols
+	bool mlp_fwd_lds = true;      // TCNN_AMD_MLP_FWD_LDS=0: wide inference (128 neurons, large batches) keeps its fragment image in L2 instead of LDS
+	bool fuse_oneblob = true;     // TCNN_AMD_FUSE_ONEBLOB=0: a OneBlob encoding in front of a network is encoded into rows, never inside the MLP kernels
 };
 Switches switches(); // a copy of the process-wide set, taken under its lock
 void switches_reload();
+
+// Laboratory knobs (DESIGN.md "Switches"): environment variables that only the laboratory build (build.py --dev) reads.  In the product
+// library the answer is "unset" at compile time, and what hangs on a knob is dead code.
+#ifdef TCNN_AMD_DEV
+inline const char* lab_env(const char* name) { return getenv(name); }
+#else
+constexpr const char* lab_env(const char*) { return nullptr; }
+#endif
+
+// Laboratory build with the variable `env` set: the in-kernel clocks of a launch site's `launches`-th launch.  A launch function keeps one
+// static DevClocks; in the product library alloc() is nullptr, fetch() is false and the printing behind it is dead code.
+struct DevClocks {
+	const char* env;
+	int left;
+	explicit DevClocks(const char* env_, int launches = 5) : env{env_}, left{launches} {}
+	// a zeroed buffer for the kernel's `dbg` argument while the site's launches are still counted, else nullptr
+	unsigned long long* alloc(size_t bytes) const {
+		unsigned long long* dbg = nullptr;
+		if (lab_env(env) && left > 0) {
+			HIP_CHECK_THROW(hipMalloc(&dbg, bytes));
+			HIP_CHECK_THROW(hipMemset(dbg, 0, bytes));
+		}
+		return dbg;
+	}
+	// after the launch: the first `count` clocks to the host, the buffer freed; true on the launch whose clocks are to be printed
+	bool fetch(unsigned long long* dbg, unsigned long long* host, size_t count) {
+		if (!dbg) return false;
+		HIP_CHECK_THROW(hipMemcpy(host, dbg, count * 8, hipMemcpyDeviceToHost));
+		(void)hipFree(dbg);
+		return --left == 0;
+	}
+};
 inline uint32_t next_multiple(uint32_t v, uint32_t d) { return div_round_up(v, d) * d; }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -536,18 +576,18 @@ struct MlpTrainPlan {
 	bool ok = false;                 // false: no fused kernel takes this request (name says nothing then)
 	MlpTrainKernel kernel = MlpTrainKernel::None;
 	// the kernel's short name, a static string (Trainer::last_step_kernel): "r32", "r32a", "r32w", "r32ob", "regs_fast", "regs",
-	// "train<W,NB,NW,MAXT>/relu|act", "train_pw28|train_pw32|train_regw|train_ob/relu|act" (act: the activation chosen at run time)
+	// "train<W,NB,NW,MAXT>/relu|act", "train_regw|train_ob/relu|act" (act: the activation chosen at run time)
 	const char* name = "";
 	uint32_t grid = 0;               // workgroups of the launch = weight-gradient slabs
 	MlpTrainRequest request;
 	// what the chosen kernel's launch needs besides:
-	struct Config { int nb, nw, maxt; uint32_t lds_bytes, s; bool ok, image_in_lds, pw, regw; } config{}; // Train: the instance of k_mlp_train (pw: private weight gradients, regw: weight fragments in registers)
+	struct Config { int nb, nw, maxt; uint32_t lds_bytes, s; bool ok, image_in_lds, regw; } config{}; // Train: the instance of k_mlp_train (regw: weight fragments in registers)
 	int regs_in_tiles = 0, regs_hidden = 0; // Regs: the instance's input tiles of 16 and hidden layers
 	bool regs_fast = false;          // Regs: compile-time formats
 	bool r32ob_shared = false;       // R32ob: shared weight-gradient tiles, else per-wave accumulators
 };
-// Pure host code: no GPU call, no allocation.  Reads the process switches (switches()) and k_train.hip's per-call environment
-// variables (TCNN_AMD_MLP_PW / _REGW / _IMAGE_LDS / _VARIANT) when called -- once per step.
+// Pure host code: no GPU call, no allocation, no look at the environment (laboratory knobs aside): the plan depends on its arguments and
+// on the process switches (one copy, switches(), taken when called -- once per step) alone.
 MlpTrainPlan mlp_train_plan(const MlpDesc& d, const MlpTrainRequest& request);
 struct MlpTrainArgs {
 	const void* image = nullptr;                           // the network's fragment images

@@ -5,7 +5,9 @@
 For a refactoring of hand-scheduled kernels: the claim "nothing changed" is checked on what the compiler emits, not on the source.  Each
 file of each tree is compiled to gfx950 assembly with that tree's own build.py flags (FLAGS + EXTRA_FLAGS[file]; `-x hip
 --cuda-device-only -S`: no GPU, no linking), once as the product and once with -DTCNN_AMD_DEV.  Comments, .file / .ident / .loc lines and the
-per-compilation __hip_cuid_* symbol are dropped, then the two texts are compared:
+per-compilation __hip_cuid_* symbol are dropped, and so is the function's index in the module from its local labels (.LBB<index>_<block>,
+.Lfunc_begin<index>, .Lfunc_end<index>: removing a kernel from a file renumbers those of every kernel behind it and changes no
+instruction); then the two texts are compared:
 
   * per file: is the whole remaining assembly identical (then the code object is the parent's);
   * per kernel symbol: are the instruction stream and the resource metadata (vgpr / agpr / sgpr counts, LDS and scratch bytes) identical;
@@ -24,6 +26,7 @@ import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
 DEFAULT_FILES = ["k_train_r32.hip", "k_train_r32a.hip", "k_train_r32w.hip", "k_train_r32ob.hip", "k_train_regs.hip", "k_train.hip"]
+LOCAL_LABEL = re.compile(r"\.L(BB|func_begin|func_end)\d+")  # the block number behind it (_<block>) stays
 META_KEYS = [".vgpr_count", ".agpr_count", ".sgpr_count", ".group_segment_fixed_size", ".private_segment_fixed_size", ".vgpr_spill_count", ".sgpr_spill_count"]
 
 
@@ -51,6 +54,7 @@ def strip(text):
             s = s.split(";", 1)[0].rstrip()
         if not s or s.startswith((".file", ".ident", ".loc")) or "__hip_cuid_" in s:
             continue
+        s = LOCAL_LABEL.sub(r".L\1", s)
         lines.append(s)
     return lines
 

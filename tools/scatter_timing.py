@@ -1,5 +1,9 @@
-"""Summarise TCNN_AMD_SCATTER_TIMING output (per-task phases of the grid gradient kernels; laboratory build) by level and by XCD
-(block b runs on XCD b % 8)."""
+"""Summarise TCNN_AMD_SCATTER_TIMING output (per-task phases of the grid gradient kernels) by level and by XCD (block b runs on XCD b % 8).
+
+    python tools/scatter_timing.py <file with the run's stderr>
+
+The variable is a laboratory knob: only libtcnn_amd_dev.so reads it (`python tiny-cuda-nn_amd/build.py --dev`).  Produce the input with
+TCNN_AMD_LIB=<path to libtcnn_amd_dev.so> TCNN_AMD_SCATTER_TIMING=1 in the environment of the run; the product library prints nothing."""
 import collections, re, sys
 rows = []
 for line in open(sys.argv[1]):
