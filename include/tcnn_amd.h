@@ -134,6 +134,17 @@ int  tcnn_module_input_gradient(tcnn_module_t m, tcnn_stream_t stream, uint32_t 
  * kernels) or the fused MLP kernel's name, "k_mlp_input_grad<W,NB,NH>/relu|act" (/act: the hidden activation is chosen at run time).
  * Owned by the module: valid until its next input_gradient call.  NULL (and tcnn_last_error) for a NULL module. */
 const char* tcnn_module_last_input_gradient_route(tcnn_module_t m);
+/* input_gradient for n_dims output columns from ONE forward pass: jacobian [n_elements][n_dims][n_input_dims] floats, row-major.  For
+ * every k, rows [:, k, :] are bit for bit what tcnn_module_input_gradient(dim = dims[k]) returns for the same input, params, backprop_scale
+ * and max_level state, and output (may be NULL) is bit for bit its output -- whichever route either call takes.  dims is a HOST array of
+ * n_dims padded output columns, in any order, repeats allowed; 1 <= n_dims <= tcnn_module_n_output_dims.  Checked before anything is
+ * allocated or launched: NULL dims or an n_dims outside that range (a message that names n_dims), a dim >= tcnn_module_n_output_dims
+ * ("Invalid dimension to compute the input gradient for."), n_elements off tcnn_batch_size_granularity(). */
+int  tcnn_module_input_jacobian(tcnn_module_t m, tcnn_stream_t stream, uint32_t n_elements, const uint32_t* dims, uint32_t n_dims, const float* input, float* jacobian,
+                                void* output, const void* params, float backprop_scale);
+/* The route the module's last input_jacobian call took: "none" before the first call, "two-pass" (one forward pass, n_dims backward passes)
+ * or the fused MLP kernel's name, "k_mlp_input_jacobian<W,NB,NH>/relu|act".  Owned by the module, as tcnn_module_last_input_gradient_route. */
+const char* tcnn_module_last_input_jacobian_route(tcnn_module_t m);
 void tcnn_context_destroy(tcnn_context_t ctx);
 
 uint32_t    tcnn_module_n_input_dims(tcnn_module_t m);     /* cpp_api.cu:129 */
@@ -191,6 +202,9 @@ int  tcnn_trainer_inference(tcnn_trainer_t t, tcnn_stream_t stream, uint32_t n_e
 /* network->input_gradient(stream, dim, input, d_dinput, backprop_scale) (object.h:342-366) on the trainer's inference parameters: see
  * tcnn_module_input_gradient.  input and d_dinput are AoS [n_elements][n_input_dims] floats. */
 int  tcnn_trainer_input_gradient(tcnn_trainer_t t, tcnn_stream_t stream, uint32_t n_elements, uint32_t dim, const float* input, float* d_dinput, float backprop_scale);
+/* tcnn_module_input_jacobian on the trainer's inference parameters: jacobian [n_elements][n_dims][n_input_dims] floats; dims is a host array */
+int  tcnn_trainer_input_jacobian(tcnn_trainer_t t, tcnn_stream_t stream, uint32_t n_elements, const uint32_t* dims, uint32_t n_dims, const float* input, float* jacobian,
+                                 float backprop_scale);
 
 /* network->inference_mixed_precision(stream, input, output) (object.h:133-145): the network's own output, half
  * [n_elements][padded_output_width] -- what inference() casts to float; half the bytes for a caller that gathers row shards.

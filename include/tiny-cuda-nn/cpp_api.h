@@ -81,6 +81,12 @@ public:
 		detail::ok(tcnn_module_input_gradient(m_handle, stream, n_elements, dim, input, d_dinput, output, params, backprop_scale));
 	}
 	std::string last_input_gradient_route() const { return tcnn_module_last_input_gradient_route(m_handle); } // "none" | "two-pass" | the fused kernel's name
+	// input_gradient for n_dims output columns from one forward pass: jacobian [n_elements][n_dims][n_input_dims], rows [:, k, :] bit for bit
+	// input_gradient(dim = dims[k]).  dims is a host array.  See tcnn_module_input_jacobian.
+	void input_jacobian(stream_t stream, uint32_t n_elements, const uint32_t* dims, uint32_t n_dims, const float* input, float* jacobian, void* output, const void* params, float backprop_scale) {
+		detail::ok(tcnn_module_input_jacobian(m_handle, stream, n_elements, dims, n_dims, input, jacobian, output, params, backprop_scale));
+	}
+	std::string last_input_jacobian_route() const { return tcnn_module_last_input_jacobian_route(m_handle); } // "none" | "two-pass" | the fused kernel's name
 
 	uint32_t n_input_dims() const { return tcnn_module_n_input_dims(m_handle); }
 	uint32_t n_output_dims() const { return tcnn_module_n_output_dims(m_handle); } // padded width, cpp_api.cu:130

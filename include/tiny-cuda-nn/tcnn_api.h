@@ -269,6 +269,13 @@ public:
 		if (input.m() != m_n_input_dims || d_dinput.m() != m_n_input_dims || input.n() != d_dinput.n()) throw std::runtime_error{"input_gradient: matrix shapes do not match the network"};
 		detail::check(tcnn_trainer_input_gradient(m_trainer, stream, input.n(), dim, input.data(), d_dinput.data(), backprop_scale));
 	}
+	// The same for several output columns from one forward pass: jacobian is column-major (dims.size() * n_dims) x batch, so that sample i's
+	// block is [dims.size()][n_dims] and its row k is input_gradient(dims[k])'s column i, bit for bit.
+	void input_jacobian(stream_t stream, const std::vector<uint32_t>& dims, const GPUMatrix<float>& input, GPUMatrix<float>& jacobian, float backprop_scale = tcnn_default_loss_scale(detail::precision_of<T>::value)) {
+		if (!m_trainer) throw std::runtime_error{"NetworkWithInputEncoding::input_jacobian: the network has no parameters yet (construct a Trainer first)"};
+		if (input.m() != m_n_input_dims || jacobian.m() != dims.size() * m_n_input_dims || input.n() != jacobian.n()) throw std::runtime_error{"input_jacobian: matrix shapes do not match the network"};
+		detail::check(tcnn_trainer_input_jacobian(m_trainer, stream, input.n(), dims.data(), (uint32_t)dims.size(), input.data(), jacobian.data(), backprop_scale));
+	}
 
 	uint32_t input_width() const { return m_n_input_dims; }
 	uint32_t output_width() const { return m_n_output_dims; }

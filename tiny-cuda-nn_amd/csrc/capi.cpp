@@ -276,6 +276,22 @@ const char* tcnn_module_last_input_gradient_route(tcnn_module_t m) {
 	return m->model->last_input_gradient_route();
 }
 
+int tcnn_module_input_jacobian(tcnn_module_t m, tcnn_stream_t stream, uint32_t n, const uint32_t* dims, uint32_t n_dims, const float* input, float* jacobian, void* output,
+                               const void* params, float backprop_scale) {
+	return guarded([&] {
+		CHECK_THROW(m && m->model);
+		m->model->input_jacobian((hipStream_t)stream, n, dims, n_dims, MatView{input, m->model->input_width(), 1u}, jacobian, output, params, backprop_scale);
+	});
+}
+
+const char* tcnn_module_last_input_jacobian_route(tcnn_module_t m) {
+	if (!m || !m->model) {
+		g_last_error = "tcnn_module_last_input_jacobian_route: null module";
+		return nullptr;
+	}
+	return m->model->last_input_jacobian_route();
+}
+
 void tcnn_context_destroy(tcnn_context_t ctx) { delete ctx; }
 
 uint32_t tcnn_module_n_input_dims(tcnn_module_t m) { return m->model->input_width(); }
@@ -447,6 +463,14 @@ int tcnn_trainer_input_gradient(tcnn_trainer_t t, tcnn_stream_t stream, uint32_t
 		Trainer& tr = *t->trainer;
 		const uint32_t w = tr.model().input_width();
 		tr.input_gradient((hipStream_t)stream, n, dim, MatView{input, w, 1u}, MatViewMut{d_dinput, w, 1u}, backprop_scale);
+	});
+}
+
+int tcnn_trainer_input_jacobian(tcnn_trainer_t t, tcnn_stream_t stream, uint32_t n, const uint32_t* dims, uint32_t n_dims, const float* input, float* jacobian, float backprop_scale) {
+	return guarded([&] {
+		CHECK_THROW(t && t->trainer);
+		Trainer& tr = *t->trainer;
+		tr.input_jacobian((hipStream_t)stream, n, dims, n_dims, MatView{input, tr.model().input_width(), 1u}, jacobian, backprop_scale);
 	});
 }
 

@@ -12,7 +12,7 @@
 // padded column in front of k_mlp_bwd.
 //
 // NH (hidden layers) is a template parameter: `kept` indexed by a run-time layer number would live in scratch.
-#include "mlp_device.h"
+#include "mlp_input_grad_device.h" // pack_layer, layer_base / frag_at, Layer<l>, nb_of: shared with k_mlp_input_jacobian.hip
 
 namespace tcnn_amd {
 namespace {
@@ -25,39 +25,6 @@ struct InputGradArgs {
 	uint32_t dim;         // the output column differentiated (< out_width)
 	half_t seed;          // (half)backprop_scale
 };
-
-// The run-time activation, chosen ONCE per layer and not per element: with the switch outside the loops every
-// case is the straight-line code of a compiled form, and inlined by force, so that acc and the packed halves are never passed by
-// address (as a function of its own, activate_pack puts both into scratch: k_mlp_fwd's run-time form has 400 bytes of it).  Same functions on the same values.
-template <int T, int KS, int NB, int ACT>
-__device__ __forceinline__ void pack_layer(const f4 (&acc)[T][NB], h8 (&hf)[KS][NB], const uint32_t act) {
-	if constexpr (ACT != -1) {
-		activate_pack_inlined<T, KS, NB, ACT>(acc, hf, act);
-	} else {
-		switch (act) {
-			case (uint32_t)Activation::ReLU: activate_pack_inlined<T, KS, NB, -1>(acc, hf, (uint32_t)Activation::ReLU); break;
-			case (uint32_t)Activation::LeakyReLU: activate_pack_inlined<T, KS, NB, -1>(acc, hf, (uint32_t)Activation::LeakyReLU); break;
-			case (uint32_t)Activation::Exponential: activate_pack_inlined<T, KS, NB, -1>(acc, hf, (uint32_t)Activation::Exponential); break;
-			case (uint32_t)Activation::Sigmoid: activate_pack_inlined<T, KS, NB, -1>(acc, hf, (uint32_t)Activation::Sigmoid); break;
-			case (uint32_t)Activation::Squareplus: activate_pack_inlined<T, KS, NB, -1>(acc, hf, (uint32_t)Activation::Squareplus); break;
-			case (uint32_t)Activation::Softplus: activate_pack_inlined<T, KS, NB, -1>(acc, hf, (uint32_t)Activation::Softplus); break;
-			case (uint32_t)Activation::Tanh: activate_pack_inlined<T, KS, NB, -1>(acc, hf, (uint32_t)Activation::Tanh); break;
-			default: activate_pack_inlined<T, KS, NB, -1>(acc, hf, (uint32_t)Activation::None); break; // None (a Sine network has no fragment images: never here)
-		}
-	}
-}
-
-// A layer's fragments, as 32-bit byte offsets from the layer's wave-uniform base (saddr + voffset addressing).  The base goes through an
-// empty asm statement once per trip and layer: with every layer written out, the compiler otherwise computes all of their fragments'
-// 64-bit addresses once, in front of the sample loop, and keeps them there -- two registers per fragment, more than 500 at 128 x 4.
-__device__ inline const char* layer_base(const h8* image, const uint32_t first_frag) {
-	const char* p = (const char*)image + (size_t)first_frag * 1024;
-	asm volatile("" : "+s"(p));
-	return p;
-}
-__device__ inline h8 frag_at(const char* base, const uint32_t lane16, const uint32_t index) { return ld32<h8>(base, lane16 + index * 1024); }
-
-template <int L> struct Layer { static constexpr int value = L; }; // a compile-time layer number: kept[l] is a register, never an address
 
 template <int W, int NB, int ACT, int NH>
 __global__ void __launch_bounds__(256) k_mlp_input_grad(const MlpDesc d, const InputGradArgs a) {
@@ -255,11 +222,7 @@ __global__ void __launch_bounds__(256) k_rescale(const size_t n_elems, const uin
 	m.data[s * m.stride_sample + j * m.stride_dim] *= mult;
 }
 
-// the instantiations: widths 16 .. 128, 1 .. MLP_INPUT_GRAD_MAX_HIDDEN hidden layers, ReLU | run-time activation, NB as the two-pass kernels have it
-// (one column block at 128 wide reads every weight fragment twice as often per sample: 128 x 4 at 2^20 rows took 1.04 ms against the
-// two passes' 0.91).  256 wide is not instantiated: its 64 accumulators and 32 kept registers per layer leave room for one hidden layer.
-constexpr int nb_of(int W, int) { return W >= 128 ? 2 : 4; }
-
+// the instantiations: widths 16 .. 128, 1 .. MLP_INPUT_GRAD_MAX_HIDDEN hidden layers, ReLU | run-time activation, NB as the two-pass kernels have it (nb_of)
 template <int W, int NH>
 void launch_act(hipStream_t stream, const MlpDesc& d, const InputGradArgs& a, const MlpInputGradPlan& p) {
 	constexpr int NB = nb_of(W, NH);

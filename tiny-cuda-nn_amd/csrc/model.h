@@ -1810,6 +1810,28 @@ public:
 		backward(stream, ctx, n, io.x_half, io.out_half, d_doutput.data(), dL_dinput, params, nullptr, GradientMode::Ignore, dx_plane_features);
 	}
 
+	// ---- input_jacobian: input_gradient for n_dims output columns from one forward pass.  dL_dinput: n_dims buffers one behind the other,
+	// buffer k bit for bit what input_gradient(dim = dims[k]) writes.  The fused kernel (mlp_input_jacobian_plan), or one forward pass and
+	// n_dims backward passes on its context.
+	MlpInputGradPlan input_jacobian_plan(uint32_t n, uint32_t n_dims) const { return mlp_input_jacobian_plan(m_desc, m_layerwise, n, n_dims); }
+	void input_jacobian(hipStream_t stream, const MlpInputGradPlan& plan, uint32_t n, const MlpIo& io, const uint32_t* dims, uint32_t n_dims, float backprop_scale, const void* params,
+	                    void* dL_dinput, uint32_t dx_plane_features) const {
+		CHECK_THROW(dims != nullptr && n_dims > 0 && dL_dinput != nullptr);
+		for (uint32_t k = 0; k < n_dims; ++k) CHECK_THROW(dims[k] < m_padded_output_width);
+		if (plan.fused) {
+			ArenaBuf image = prepare(stream, params, true);
+			return mlp_input_jacobian(stream, m_desc, plan, image.data(), n, io, dims, n_dims, backprop_scale, dL_dinput, dx_plane_features);
+		}
+		CHECK_THROW(io.x_half != nullptr && io.out_half != nullptr && !io.x_plane_features && !io.x_f32.data && !io.x_oneblob_bins);
+		ArenaBuf d_doutput{stream, (size_t)n * m_padded_output_width * element_size()};
+		const NetworkContext ctx = forward(stream, n, io.x_half, io.out_half, params);
+		for (uint32_t k = 0; k < n_dims; ++k) {
+			input_gradient_one_hot(stream, precision(), n, m_padded_output_width, dims[k], backprop_scale, d_doutput.data());
+			backward(stream, ctx, n, io.x_half, io.out_half, d_doutput.data(), (char*)dL_dinput + (size_t)k * n * m_input_width * element_size(), params, nullptr, GradientMode::Ignore,
+			         dx_plane_features);
+		}
+	}
+
 	// ---- Second-order input gradients of a CutlassMLP: the gradients of S = <v, dL/dinput> for a given v = dL2/d(dL/dinput).
 	// With h_0 = input, z_k = W_k h_{k-1}, h_k = a_k(z_k), g_K = dL/dy, d_k = g_k a_k'(z_k), g_{k-1} = W_k^T d_k (dL/dinput = g_0):
 	//   tangent    u_0 = v, z'_k = W_k u_{k-1}, u_k = a_k'(z_k) z'_k                  dS/d(dL/dy) = u_K
@@ -2105,6 +2127,24 @@ public:
 		input_gradient_rescale(stream, n, input_width(), 1.0f / backprop_scale, d_dinput);
 	}
 	const char* last_input_gradient_route() const { return m_last_input_gradient_route.c_str(); } // "none" before the first call
+	// input_gradient for n_dims output columns from ONE forward pass: jacobian [n][n_dims][input_width] floats, row-major; rows [:, k, :] are
+	// bit for bit what input_gradient(dim = dims[k]) gives, and output is the output it gives.  dims (host): any order, repeats and padded
+	// columns allowed, 1 <= n_dims <= padded_output_width().  Everything is checked before anything is allocated or launched.
+	void input_jacobian(hipStream_t stream, uint32_t n, const uint32_t* dims, uint32_t n_dims, MatView input, float* jacobian, void* output, const void* params, float backprop_scale) {
+		if (!dims || n_dims == 0 || n_dims > padded_output_width()) {
+			throw std::runtime_error{"input_jacobian: n_dims = " + std::to_string(n_dims) + " must be between 1 and the padded output width " + std::to_string(padded_output_width()) +
+			                         ", with that many dims"};
+		}
+		for (uint32_t k = 0; k < n_dims; ++k) {
+			if (dims[k] >= padded_output_width()) throw std::runtime_error{"Invalid dimension to compute the input gradient for."}; // object.h:350
+		}
+		check_batch(n);
+		CHECK_THROW(n == 0 || (input.data != nullptr && jacobian != nullptr));
+		if (n == 0) return;
+		m_last_input_jacobian_route = input_jacobian_impl(stream, n, dims, n_dims, input, jacobian, output, params, backprop_scale);
+		input_gradient_rescale(stream, n, n_dims * input_width(), 1.0f / backprop_scale, MatViewMut{jacobian, n_dims * input_width(), 1u});
+	}
+	const char* last_input_jacobian_route() const { return m_last_input_jacobian_route.c_str(); } // "none" before the first call
 	virtual Json hyperparams() const = 0;
 	std::string name() const { return hyperparams().value("otype", "<Unknown>"); } // object.h:51-53
 protected:
@@ -2123,8 +2163,32 @@ protected:
 		const std::unique_ptr<ModelContext> ctx = forward(stream, n, input, out, params, true);
 		backward(stream, *ctx, n, input, out, d_doutput.data(), &d_dinput, params, nullptr, GradientMode::Ignore);
 	}
+	// writes the jacobian scaled by backprop_scale and returns the route's name.  The generic route, for every module: ONE
+	// forward(prepare_input_gradients), then a one-hot dL/dy and backward(GradientMode::Ignore) per dim on the same context, each into its
+	// strided slice of the result (the encodings' input-gradient kernels write through any view).
+	virtual std::string input_jacobian_impl(hipStream_t stream, uint32_t n, const uint32_t* dims, uint32_t n_dims, MatView input, float* jacobian, void* output, const void* params,
+	                                        float backprop_scale) {
+		input_jacobian_two_pass(stream, n, dims, n_dims, input, jacobian, output, params, backprop_scale);
+		return "two-pass";
+	}
+	void input_jacobian_two_pass(hipStream_t stream, uint32_t n, const uint32_t* dims, uint32_t n_dims, MatView input, float* jacobian, void* output, const void* params, float backprop_scale) {
+		const uint32_t pw = padded_output_width();
+		const size_t bytes = (size_t)n * pw * (precision() == Precision::Fp32 ? 4 : 2);
+		ArenaBuf out_tmp, d_doutput{stream, bytes};
+		if (!output) out_tmp = ArenaBuf{stream, bytes};
+		void* out = output ? output : out_tmp.data();
+		const std::unique_ptr<ModelContext> ctx = forward(stream, n, input, out, params, true);
+		for (uint32_t k = 0; k < n_dims; ++k) {
+			input_gradient_one_hot(stream, precision(), n, pw, dims[k], backprop_scale, d_doutput.data());
+			MatViewMut slice = jacobian_slice(jacobian, k, n_dims);
+			backward(stream, *ctx, n, input, out, d_doutput.data(), &slice, params, nullptr, GradientMode::Ignore);
+		}
+	}
+	// rows [:, k, :] of the [n][n_dims][input_width] result as a view of [n][input_width]
+	MatViewMut jacobian_slice(float* jacobian, uint32_t k, uint32_t n_dims) const { return MatViewMut{jacobian + (size_t)k * input_width(), n_dims * input_width(), 1u}; }
 private:
 	std::string m_last_input_gradient_route = "none";
+	std::string m_last_input_jacobian_route = "none";
 public:
 
 	static void check_batch(uint32_t n) { // object.h:130,150,197,246
@@ -2397,6 +2461,53 @@ public:
 		const GridBackwardRoute route = m_encoding->backward_route(switches(), stream, encoding_ctx, n, input, offer, true, GradientMode::Ignore);
 		m_network->input_gradient(stream, plan, n, io, dim, backprop_scale, params, dL_dnetwork_input.data(), route.plane_features);
 		m_encoding->backward(stream, encoding_ctx, n, input, dL_dnetwork_input.data(), &d_dinput, encoding_params(params), nullptr, GradientMode::Ignore, route);
+		return plan.name;
+	}
+
+	// input_gradient_impl for n_dims output columns: the encoding's forward pass with dy_dx runs ONCE (behind a grid it is most of an
+	// input_gradient call), the network writes one dL/d(network input) buffer per dim -- the fused Jacobian kernel from one forward chain, or
+	// one forward pass and a backward pass per dim -- and the encoding's backward pass runs per buffer into its strided slice of the result,
+	// on one route asked once.  The buffers are temporaries: groups of as many dims as fit INPUT_JACOBIAN_TMP_BYTES at a time (a fused
+	// network repeats its forward chain per group, a two-pass network its forward pass; the encoding pass is never repeated).
+	static constexpr size_t INPUT_JACOBIAN_TMP_BYTES = (size_t)256 << 20; // (the bound of mlp_wgrad_panels' workspace)
+	std::string input_jacobian_impl(hipStream_t stream, uint32_t n, const uint32_t* dims, uint32_t n_dims, MatView input, float* jacobian, void* output, const void* params,
+	                                float backprop_scale) override {
+		MlpInputGradPlan plan = m_network->input_jacobian_plan(n, n_dims);
+		if (m_encoding->as_oneblob()) plan = MlpInputGradPlan{};
+		const uint32_t enc_w = m_encoding->padded_output_width();
+		MlpIo io{};
+		io.out_half = output;
+		ArenaBuf network_input, out_tmp;
+		EncodingContext encoding_ctx;
+		float scale = 1, offset = 0;
+		if (plan.fused && m_encoding->as_identity(scale, offset)) {
+			io.x_f32 = input;
+			io.x_f32_dims = m_encoding->input_width();
+			io.x_scale = scale;
+			io.x_offset = offset;
+		} else {
+			network_input = ArenaBuf{stream, (size_t)n * enc_w * elem()};
+			encoding_ctx = m_encoding->forward(stream, n, input, encoding_params(params), network_input.data(), true, false);
+			io.x_half = network_input.data();
+		}
+		if (!plan.fused && !output) { // the two passes read the output back
+			out_tmp = ArenaBuf{stream, (size_t)n * m_network->padded_output_width() * elem()};
+			io.out_half = out_tmp.data();
+		}
+		const size_t buf_bytes = (size_t)n * enc_w * elem();
+		const uint32_t group = (uint32_t)std::min<size_t>(n_dims, std::max<size_t>(INPUT_JACOBIAN_TMP_BYTES / std::max<size_t>(buf_bytes, 1), 1));
+		ArenaBuf dL_dnetwork_input{stream, buf_bytes * group};
+		const GridDyForm offer = !m_network->layerwise() ? GridDyForm::Planes : GridDyForm::Rows; // (as backward() offers it)
+		const GridBackwardRoute route = m_encoding->backward_route(switches(), stream, encoding_ctx, n, input, offer, true, GradientMode::Ignore);
+		for (uint32_t k0 = 0; k0 < n_dims; k0 += group) {
+			const uint32_t n_group = std::min(group, n_dims - k0);
+			m_network->input_jacobian(stream, plan, n, io, dims + k0, n_group, backprop_scale, params, dL_dnetwork_input.data(), route.plane_features);
+			if (plan.fused) io.out_half = nullptr; // stored with the first group
+			for (uint32_t k = 0; k < n_group; ++k) {
+				MatViewMut slice = jacobian_slice(jacobian, k0 + k, n_dims);
+				m_encoding->backward(stream, encoding_ctx, n, input, (const char*)dL_dnetwork_input.data() + k * buf_bytes, &slice, encoding_params(params), nullptr, GradientMode::Ignore, route);
+			}
+		}
 		return plan.name;
 	}
 
@@ -3883,6 +3994,9 @@ public:
 	// object.h:342-366 on the inference parameters (trainer.h binds them to the model): no gradient buffer, no optimizer state is touched
 	void input_gradient(hipStream_t stream, uint32_t n, uint32_t dim, MatView input, MatViewMut d_dinput, float backprop_scale) {
 		m_model->input_gradient(stream, n, dim, input, d_dinput, nullptr, params_inference(), backprop_scale);
+	}
+	void input_jacobian(hipStream_t stream, uint32_t n, const uint32_t* dims, uint32_t n_dims, MatView input, float* jacobian, float backprop_scale) {
+		m_model->input_jacobian(stream, n, dims, n_dims, input, jacobian, nullptr, params_inference(), backprop_scale);
 	}
 
 	// object.h:133-145, inference_mixed_precision: the network's own output, half [n][padded_output_width] (what inference() casts); floats from an fp32 trainer

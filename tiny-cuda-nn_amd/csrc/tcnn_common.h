@@ -531,7 +531,7 @@ void mlp_backward(hipStream_t stream, const MlpDesc& d, const void* image, uint3
 constexpr uint32_t MLP_INPUT_GRAD_MAX_HIDDEN = 4; // depths 1 .. 4 are instantiated
 struct MlpInputGradPlan {
 	bool fused = false;          // false: forward + backward (name "two-pass")
-	char name[48] = "two-pass";  // the route's name (tcnn_module_last_input_gradient_route): "two-pass" | "k_mlp_input_grad<W,NB,NH>/relu|act"
+	char name[48] = "two-pass";  // the route's name (tcnn_module_last_input_gradient_route): "two-pass" | "k_mlp_input_grad<W,NB,NH>/relu|act" (mlp_input_jacobian_plan: k_mlp_input_jacobian<...>)
 	uint32_t nb = 0, grid = 0;   // fused: column blocks of 16 samples per wave and trip, workgroups of 4 waves
 	bool relu = false;           // fused: the compiled ReLU form, else the activation chosen at run time
 };
@@ -544,6 +544,25 @@ MlpInputGradPlan mlp_input_gradient_plan(const MlpDesc& d, bool layerwise, uint3
 // dL_dx half [n][in_width] or level planes (dx_plane_features), as mlp_backward writes it; dim < d.out_width; plan.fused must hold for (d, n)
 void mlp_input_gradient(hipStream_t stream, const MlpDesc& d, const MlpInputGradPlan& plan, const void* image, uint32_t n, const MlpIo& io, uint32_t dim, float backprop_scale,
                         void* dL_dx, uint32_t dx_plane_features);
+// ---- input_jacobian: input_gradient for K output columns d_0 .. d_{K-1} from ONE forward chain (k_mlp_input_jacobian.hip): buffer k is bit
+// for bit what mlp_input_gradient(dim = d_k) writes.  The dims travel in the kernel's arguments, MLP_INPUT_JACOBIAN_MAX_DIMS per launch; more
+// dims run as further launches, each with a forward chain of its own.
+constexpr uint32_t MLP_INPUT_JACOBIAN_MAX_DIMS = 16;
+// Pure host code, as mlp_input_gradient_plan: "two-pass" (one forward pass, n_dims backward passes) or "k_mlp_input_jacobian<W,NB,NH>/relu|act".
+// The rule: fused where the half-precision fused kernels exist -- not layerwise, fragment images present, 16 / 32 / 64 / 128 wide, 1 .. 4
+// hidden layers, n a multiple of 16 NB (NB = 2 at 128 wide, else 4) -- except in the classes where it measured no faster than the Jacobian's
+// own two passes by more than 3 % (DESIGN.md "input_jacobian"):
+//   - a run-time activation (anything but ReLU) with more than 256 workgroups (n / (64 NB)) and n_dims above the class's limit --
+//     16 wide: none for 1 .. 3 hidden layers, 0 for 4 (never fused); 32 wide: none for 1 | 2, 1 for 3, 0 for 4; 64 wide: 3 for 1, else 2;
+//     128 wide: 2 for 1, else 1;
+//   - ReLU, 128 wide, 2 hidden layers, n >= 2^20, n_dims > 8.
+// mlp_input_gradient_plan's exception (128 wide, ReLU, 3 | 4 hidden layers, full machine) is not carried over: it rests on a kernel whose
+// forward chain was not shared, and this one measured 1.14 to 1.21 there at 3 dims.
+MlpInputGradPlan mlp_input_jacobian_plan(const MlpDesc& d, bool layerwise, uint32_t n, uint32_t n_dims);
+// io as for mlp_input_gradient; dims: n_dims host values < d.out_width; dL_dx: n_dims buffers one behind the other, each half [n][in_width] or
+// level planes (dx_plane_features); the output (io.out_half, optional) is stored once
+void mlp_input_jacobian(hipStream_t stream, const MlpDesc& d, const MlpInputGradPlan& plan, const void* image, uint32_t n, const MlpIo& io, const uint32_t* dims, uint32_t n_dims,
+                        float backprop_scale, void* dL_dx, uint32_t dx_plane_features);
 // the two ends of every input_gradient route (object.h:352-365): d_doutput [n][width] T = (T)backprop_scale in column dim, +0 elsewhere;
 // d_dinput[i][j] *= mult for j < dims (mult = 1.0f / backprop_scale, formed once by the caller)
 void input_gradient_one_hot(hipStream_t stream, Precision precision, uint32_t n, uint32_t width, uint32_t dim, float backprop_scale, void* d_doutput);

@@ -160,6 +160,23 @@ class NativeModule:
         """ "none" before the first input_gradient call, then "two-pass" or the fused MLP kernel's name (tcnn_amd.h: tcnn_module_last_input_gradient_route)"""
         return _C.lib.tcnn_module_last_input_gradient_route(self._h).decode()
 
+    def input_jacobian(self, input, params, dims, backprop_scale, want_output=False):
+        """d output[dims[k]] / d input for every k from one forward pass, float32 [n, len(dims), n_input_dims] (and the forward pass's padded
+        output if asked for): tcnn_amd.h tcnn_module_input_jacobian.  dims count padded columns; n must be a multiple of the batch granularity."""
+        self._check_inputs(input, params)
+        dims = [int(d) for d in dims]
+        with torch.cuda.device(input.device):
+            n = input.shape[0]
+            jacobian = torch.empty((n, len(dims), self.n_input_dims()), dtype=torch.float32, device=input.device)
+            output = torch.empty((n, self.n_output_dims()), dtype=_torch_precision(self.output_precision()), device=input.device) if want_output else None
+            _C.check(_C.lib.tcnn_module_input_jacobian(self._h, _stream(), n, (_C.C.c_uint32 * len(dims))(*dims), len(dims), _ptr(input), _ptr(jacobian), _ptr(output), _ptr(params),
+                                                       float(backprop_scale)))
+        return jacobian, output
+
+    def last_input_jacobian_route(self):
+        """ "none" before the first input_jacobian call, then "two-pass" or the fused MLP kernel's name (tcnn_amd.h: tcnn_module_last_input_jacobian_route)"""
+        return _C.lib.tcnn_module_last_input_jacobian_route(self._h).decode()
+
     def bwd_bwd_input(self, ctx, input, params, dL_ddLdinput, dL_doutput):  # bindings.cpp:172-245
         """from dL_ddLdinput to (dL_ddLdoutput, dL_dparams, dL_dinput); each is None unless its tensor requires grad."""
         if ctx is None or not ctx._h:
@@ -412,6 +429,27 @@ class Module(torch.nn.Module):
                 gradient, output = native.input_gradient(rows, working, dim, scale, return_output)
             gradient = gradient[:n]
             return (gradient, output[:n, : self.n_output_dims]) if return_output else gradient
+
+    def input_jacobian(self, x, dims=None, backprop_scale=None, return_output=False):
+        """input_gradient for several output columns from ONE forward pass: float32 [n, len(dims), n_input_dims] for any n, where
+        [:, k, :] is bit for bit input_gradient(x, dims[k], backprop_scale).  dims (default: range(n_output_dims)) count the native
+        (padded) output columns, in any order, repeats allowed.  Outside autograd and under the max_level setting in force, as
+        input_gradient.  return_output=True: (jacobian, output[:n, :n_output_dims]) of the same pass."""
+        with torch.no_grad():
+            x = x.detach()
+            if not x.is_cuda:
+                warnings.warn("input must be a CUDA tensor, but isn't. This indicates suboptimal performance.")
+                x = x.cuda()
+            n = x.shape[0]
+            rows = _pad_rows(x.to(torch.float), _C.batch_size_granularity()).contiguous()
+            working = self.params.detach().to(self.dtype).contiguous()
+            scale = self.loss_scale if backprop_scale is None else backprop_scale
+            native = self.native_tcnn_module
+            call = _Call(native, scale, False, False, self._max_level_of_call(n, rows))
+            with call.setting():
+                jacobian, output = native.input_jacobian(rows, working, range(self.n_output_dims) if dims is None else dims, scale, return_output)
+            jacobian = jacobian[:n]
+            return (jacobian, output[:n, : self.n_output_dims]) if return_output else jacobian
 
     # --- max_level of the grid encoding(s) (the reference's GridEncoding::set_max_level / set_max_level_gpu, grid_interface.h:101-123).
     # Every forward call records the setting in force; its backward and double-backward passes run under that setting.

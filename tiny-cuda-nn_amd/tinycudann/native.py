@@ -204,6 +204,20 @@ class Trainer:
         _C.check(_C.lib.tcnn_trainer_input_gradient(self._h, _stream(stream), n, int(dim), _ptr(input), _ptr(d_dinput), float(scale)))
         return d_dinput
 
+    def input_jacobian(self, input, dims, backprop_scale=None, jacobian=None, stream=None):
+        """d output[dims[k]] / d input for every k from one forward pass, float32 [n, len(dims), n_input_dims]; [:, k, :] is bit for bit
+        input_gradient(input, dims[k], backprop_scale).  dims count padded columns."""
+        n = input.shape[0]
+        dims = [int(d) for d in dims]
+        shape = (n, len(dims), input.shape[1])
+        if jacobian is None:
+            jacobian = torch.empty(shape, dtype=torch.float32, device=input.device)
+        assert input.dtype == torch.float32 and input.is_contiguous() and jacobian.dtype == torch.float32 and jacobian.is_contiguous() and tuple(jacobian.shape) == shape
+        self._check_max_level_rows(n)
+        scale = self.default_loss_scale if backprop_scale is None else backprop_scale
+        _C.check(_C.lib.tcnn_trainer_input_jacobian(self._h, _stream(stream), n, (C.c_uint32 * len(dims))(*dims), len(dims), _ptr(input), _ptr(jacobian), float(scale)))
+        return jacobian
+
     # -- object.h:133-145: network->inference_mixed_precision(stream, input, output): half [n][padded_output_width]
     def inference_half(self, input, output=None, input_layout=LAYOUT_AOS, stream=None):
         if self.dtype != torch.half:
