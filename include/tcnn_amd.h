@@ -344,6 +344,38 @@ int         tcnn_optimizer_weights_restored(tcnn_optimizer_t o, tcnn_stream_t st
 int         tcnn_optimizer_serialize(tcnn_optimizer_t o, const void** out_bytes, size_t* out_size);
 int         tcnn_optimizer_deserialize(tcnn_optimizer_t o, const void* bytes, size_t size);
 
+
+/* ---- standalone losses (loss.h:41-60, src/loss.cu:57-65): the losses a trainer evaluates -- L2, RelativeL2, RelativeL2Luminance, L1,
+ * RelativeL1, Mape, Smape, CrossEntropy, Variance -- on predictions the caller owns (a renderer's output, a slice of a module's padded
+ * output).  Stateless: a loss is its type number, there is no handle.
+ * tcnn_loss_type: the type of a loss configuration ({"otype": ...}, matched case-insensitively; "Invalid loss type: X" otherwise).
+ * tcnn_loss_name: the canonical name of a type, or NULL + tcnn_last_error().
+ * tcnn_loss_evaluate: Loss<T>::evaluate on `stream`.  prediction: n rows of `dims` values in `precision` (TCNN_PRECISION_FP16 / _FP32), row
+ * stride prediction_stride >= dims, unit column stride.  target and data_pdf (or NULL): compact float [n][dims].  Every element is computed
+ * by the device code a trainer's loss runs, so values and gradients are bit for bit what a trainer computes from the same predictions.
+ * Each output is optional (NULL) and at least one must be given:
+ *   values     float [n][values_stride]: the per-element loss, already divided by n * dims;
+ *   gradients  [n][gradients_stride] in the prediction's precision: loss_scale * dL/dprediction -- the layout external_dL_dy takes;
+ *   loss_sum   one device float: the sum of all values (what tcnn_trainer_loss returns), reduced in a fixed order without storing them:
+ *              the same arguments -- the pointers' 16-byte alignment included: it decides between the 16-byte and the element-wise
+ *              form, which sum in different orders -- give the same bits, and no floating-point atomics are involved.
+ * Columns >= dims of every output row are written as zeros.  scale_dev (or NULL): one device float multiplied into loss_scale in fp32 before
+ * the gradient is rounded once to its precision -- an incoming gradient or a gradient scaler's factor, never read by the host.
+ * Extents: of the prediction only the n rows of dims values have to be readable, (n - 1) * prediction_stride + dims elements from the
+ * pointer -- a column or row slice of a larger matrix is fine; a load never leaves the 16-byte aligned block that holds a value.  target and
+ * data_pdf: n * dims floats.  Every requested output is written in full, padding included: n * its stride elements.
+ * n is any number of rows (no granularity); n == 0 succeeds, launches nothing and sets *loss_sum to 0.  n * stride must stay below 2^32 for
+ * every stride, RelativeL2Luminance needs dims >= 3 (it reads three channels of every row; six when dims >= 6).  All arguments are checked
+ * before anything is launched.  The call never synchronises; its workspace comes from the library's stream-ordered arena. */
+int         tcnn_loss_type(const char* loss_json, int* type_out);   /* src/loss.cu:57-65 */
+const char* tcnn_loss_name(int type);
+int         tcnn_loss_evaluate(int type, tcnn_stream_t stream, float loss_scale, const float* scale_dev /* or NULL */,
+                               uint32_t n, uint32_t dims, const void* prediction, uint32_t prediction_stride, int precision,
+                               const float* target, const float* data_pdf /* or NULL */,
+                               float* values, uint32_t values_stride,          /* or NULL */
+                               void* gradients, uint32_t gradients_stride,     /* or NULL */
+                               float* loss_sum /* device, or NULL */);         /* loss.h:41-49 */
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,7 @@
 //   tcnn::json                                     nlohmann::json as used by config.h:53 / the samples' config literals (the real one when <json/json.hpp> is on the include path)
 //   tcnn::GPUMemory<T>                             gpu_memory.h:60-392   (allocation, host <-> device copies, memset)
 //   tcnn::GPUMatrixDynamic<T>, GPUMatrix<T, L>     gpu_matrix.h:115-470  (m x n, column-major by default = [n][m] in memory)
-//   tcnn::Loss<T>, create_loss<T>                  loss.h:48-77, src/loss.cu:54-68          (L2, RelativeL2)
+//   tcnn::Loss<T>, create_loss<T>                  loss.h:41-77, src/loss.cu:54-68          (all nine losses; evaluate() on the caller's matrices)
 //   tcnn::Optimizer<T>, create_optimizer<T>        optimizer.h:44-95, src/optimizer.cu:50-82 (every optimizer of the library; allocate / step for callers with their own gradients)
 //   tcnn::NetworkWithInputEncoding<T>              network_with_input_encoding.h:40-180
 //   tcnn::Trainer<T, PARAMS_T, COMPUTE_T>          trainer.h:48-363  (training_step, loss, inference via the network, params)
@@ -154,6 +154,8 @@ public:
 };
 
 // ------------------------------------------------------------------------------------------ loss / optimizer / network
+// loss.h:38-61.  A Trainer takes the object for its configuration; evaluate() runs the loss on matrices that are the caller's
+// (tcnn_loss_evaluate): the device code a trainer's loss runs, so the same bits.  T is the type of predictions and gradients: half or float.
 template <typename T>
 class Loss {
 public:
@@ -165,11 +167,44 @@ public:
 		bool ok = false;
 		for (const char* k : known) ok = ok || lower == k;
 		if (!ok) throw std::runtime_error{"Invalid loss type: " + otype}; // src/loss.cu:85-93
+		detail::check(tcnn_loss_type(m_params.dump().c_str(), &m_type)); // resolved once: evaluate() is a call whose cost is the host's
 	}
 	json hyperparams() const { return m_params; }
+	void update_hyperparams(const json&) {} // no loss of the reference has any (losses/*.h)
+
+	// loss.h:41-49 with the checks of losses/*.h (l2.h:89-95): dims = target.m(), stride = prediction.m(); values and gradients have the
+	// prediction's stride, and their rows beyond dims are written as zeros.
+	void evaluate(stream_t stream, const float loss_scale, const GPUMatrix<T>& prediction, const GPUMatrix<float>& target, GPUMatrix<float>& values, GPUMatrix<T>& gradients,
+	              const GPUMatrix<float>* data_pdf = nullptr) const {
+		check_shapes(prediction, target, data_pdf);
+		if (values.m() != prediction.m()) throw std::runtime_error{"Loss::evaluate check failed: values.m() == stride"};
+		if (gradients.m() != prediction.m()) throw std::runtime_error{"Loss::evaluate check failed: gradients.m() == stride"};
+		detail::check(tcnn_loss_evaluate(type(), stream, loss_scale, nullptr, prediction.n(), target.m(), prediction.data(), prediction.m(), detail::precision_of<T>::value, target.data(),
+		                                 data_pdf ? data_pdf->data() : nullptr, values.data(), values.m(), gradients.data(), gradients.m(), nullptr));
+	}
+	void evaluate(const float loss_scale, const GPUMatrix<T>& prediction, const GPUMatrix<float>& target, GPUMatrix<float>& values, GPUMatrix<T>& gradients,
+	              const GPUMatrix<float>* data_pdf = nullptr) const { // loss.h:51-60
+		evaluate(nullptr, loss_scale, prediction, target, values, gradients, data_pdf);
+	}
+	// Not in the reference: the sum of the values -- what trainer->loss() reports -- into one device float instead of a values matrix,
+	// reduced in a fixed order inside the same pass (the same arguments give the same bits).
+	void evaluate(stream_t stream, const float loss_scale, const GPUMatrix<T>& prediction, const GPUMatrix<float>& target, float* loss_sum, GPUMatrix<T>& gradients,
+	              const GPUMatrix<float>* data_pdf = nullptr) const {
+		check_shapes(prediction, target, data_pdf);
+		if (gradients.m() != prediction.m()) throw std::runtime_error{"Loss::evaluate check failed: gradients.m() == stride"};
+		if (!loss_sum) throw std::runtime_error{"Loss::evaluate check failed: loss_sum != nullptr"};
+		detail::check(tcnn_loss_evaluate(type(), stream, loss_scale, nullptr, prediction.n(), target.m(), prediction.data(), prediction.m(), detail::precision_of<T>::value, target.data(),
+		                                 data_pdf ? data_pdf->data() : nullptr, nullptr, 0, gradients.data(), gradients.m(), loss_sum));
+	}
 
 private:
+	static void check_shapes(const GPUMatrix<T>& prediction, const GPUMatrix<float>& target, const GPUMatrix<float>* data_pdf) {
+		if (prediction.n() != target.n()) throw std::runtime_error{"Loss::evaluate check failed: prediction.n() == target.n()"};
+		if (data_pdf && data_pdf->m() != target.m()) throw std::runtime_error{"Loss::evaluate check failed: !data_pdf || data_pdf->m() == dims"};
+	}
+	int type() const { return m_type; }
 	json m_params;
+	int m_type = 0; // the library's number for the loss (tcnn_loss_type)
 };
 template <typename T> Loss<T>* create_loss(const json& params) { return new Loss<T>{params}; }
 

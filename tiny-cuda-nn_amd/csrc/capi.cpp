@@ -703,4 +703,29 @@ int tcnn_optimizer_deserialize(tcnn_optimizer_t o, const void* bytes, size_t siz
 	});
 }
 
+// ---------------------------------------------------------------------------------------------------------- standalone losses
+int tcnn_loss_type(const char* loss_json, int* type_out) {
+	return guarded([&] {
+		CHECK_THROW(type_out != nullptr);
+		*type_out = (int)create_loss(parse_or_empty(loss_json));
+	});
+}
+
+const char* tcnn_loss_name(int type) {
+	const char* name = nullptr;
+	guarded([&] {
+		if (type < 0 || type > (int)LossType::RelativeL2Luminance) throw std::runtime_error{"Invalid loss type: " + std::to_string(type)};
+		name = to_string((LossType)type);
+	});
+	return name;
+}
+
+int tcnn_loss_evaluate(int type, tcnn_stream_t stream, float loss_scale, const float* scale_dev, uint32_t n, uint32_t dims, const void* prediction, uint32_t prediction_stride,
+                       int precision, const float* target, const float* data_pdf, float* values, uint32_t values_stride, void* gradients, uint32_t gradients_stride, float* loss_sum) {
+	return guarded([&] {
+		loss_evaluate_on_predictions((hipStream_t)stream, type, precision, loss_scale, scale_dev, n, dims, prediction, prediction_stride, target, data_pdf, values, values_stride,
+		                             gradients, gradients_stride, loss_sum);
+	});
+}
+
 } // extern "C"

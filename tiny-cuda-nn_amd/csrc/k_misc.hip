@@ -12,8 +12,10 @@
 #include "tcnn_common.h"
 #include "adam_device.h"
 #include "grid_fixed.h"
+#include "loss_device.h"
 #include "mlp_side_jobs.h"
 #include "oneblob_device.h"
+#include "reduce_device.h"
 
 #include <hip/hip_fp16.h>
 
@@ -201,77 +203,7 @@ __global__ void __launch_bounds__(256) k_identity_bwd_bwd_input(const uint32_t n
 	dL_ddLdy[gid] = j >= n_dims ? (T)0.0f : (T)(dL_ddLdx.data[(size_t)i * dL_ddLdx.stride_sample + (size_t)j * dL_ddLdx.stride_dim] * scale);
 }
 
-// ---- loss: l2.h:40-74 / relative_l2.h:40-75 and the other element-wise losses.  One element: the reference's expressions, term for term.
-// (row: the sample's padded prediction row -- RelativeL2Luminance reads the pixel's other channels from it)
-// P: the predictions' and gradients' type, half_t, or float (Loss<float>: the cast of the gradient is then no rounding)
-template <typename P>
-__device__ inline void loss_element(const uint32_t type, const float prediction, const float target, const float pdf, const uint32_t n_total, const float loss_scale,
-                                    const P* __restrict__ row, const uint32_t dims, float& value_out, P& grad_out) {
-	const float difference = prediction - target;
-	float value, gradient;
-	switch ((LossType)type) {
-		case LossType::RelativeL2: { // relative_l2.h:60-73
-			const float prediction_sq_plus_epsilon = prediction * prediction + 0.01f;
-			value = difference * difference / prediction_sq_plus_epsilon / pdf / n_total;
-			gradient = 2 * difference / prediction_sq_plus_epsilon / pdf;
-			break;
-		}
-		case LossType::RelativeL2Luminance: { // relative_l2_luminance.h:40-85: the divisor is the squared luminance of the pixel
-			const P* px = row;
-			float r = (float)px[0], g = (float)px[1], b = (float)px[2];
-			if (dims >= 6) {
-				r += (float)px[3];
-				g += (float)px[4];
-				b += (float)px[5];
-			}
-			const float luminance = (0.299f * r + 0.587f * g + 0.114f * b);
-			const float prediction_sq_plus_epsilon = luminance * luminance + 0.01f;
-			value = difference * difference / prediction_sq_plus_epsilon / pdf / n_total;
-			gradient = 2 * difference / prediction_sq_plus_epsilon / pdf;
-			break;
-		}
-		case LossType::L1: // l1.h:40-70
-			value = fabsf(difference) / pdf / n_total;
-			gradient = copysignf(1.0f / pdf, difference);
-			break;
-		case LossType::RelativeL1: { // relative_l1.h:40-72
-			const float scale = 1.0f / (fabsf(prediction) + 1e-2f) / pdf;
-			value = fabsf(difference) * scale / n_total;
-			gradient = copysignf(scale, difference);
-			break;
-		}
-		case LossType::Mape: { // mape.h:40-73
-			const float scale = 1.0f / (fabsf(target) + 1e-2f) / pdf;
-			value = fabsf(difference) * scale / n_total;
-			gradient = copysignf(scale, difference);
-			break;
-		}
-		case LossType::Smape: { // smape.h:40-73
-			const float scale = 1.0f / (0.5f * (fabsf(target) + fabsf(prediction)) + 1e-2f) / pdf;
-			value = fabsf(difference) * scale / n_total;
-			gradient = copysignf(scale, difference);
-			break;
-		}
-		case LossType::CrossEntropy: { // cross_entropy.h:40-72: the gradient already carries 1 / n_total
-			const float factor = -target / pdf / n_total;
-			value_out = factor * logf(prediction);
-			grad_out = (P)(loss_scale * (factor / prediction));
-			return;
-		}
-		case LossType::Variance: { // variance_is.h:40-72
-			const float factor = target * target / pdf / n_total;
-			value_out = factor / prediction - factor / pdf;
-			grad_out = (P)(loss_scale * (-factor / (prediction * prediction)));
-			return;
-		}
-		default: // L2, l2.h:60-72
-			value = difference * difference / pdf / n_total;
-			gradient = 2 * difference / pdf;
-			break;
-	}
-	value_out = value;
-	grad_out = (P)(loss_scale * gradient / n_total);
-}
+// ---- loss: one element is loss_element (loss_device.h), the reference's expressions term for term
 
 // one thread per padded output element (any stride)
 template <typename P>
@@ -358,20 +290,6 @@ __global__ void __launch_bounds__(256) k_loss4_f32(
 }
 
 // ---- deterministic two-stage sum: stage 1 = one partial per block (fixed grid), stage 2 = one block sums the partials
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-	for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-	return v;
-}
-
-__device__ inline float block_sum_256(float v, float* smem4) {
-	v = wave_sum(v);
-	const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-	if (lane == 0) smem4[w] = v;
-	__syncthreads();
-	return smem4[0] + smem4[1] + smem4[2] + smem4[3];
-}
-
 __global__ void __launch_bounds__(256) k_reduce_stage1(const size_t n, const float* __restrict__ values, float* __restrict__ partials) {
 	__shared__ float sm[4];
 	float acc = 0.0f;
@@ -697,6 +615,10 @@ void reduce_sum(hipStream_t stream, size_t n, const float* values, float* partia
 	if (blocks == 0) blocks = 1;
 	hipLaunchKernelGGL(k_reduce_stage1, dim3(blocks), dim3(256), 0, stream, n, values, partials);
 	hipLaunchKernelGGL(k_reduce_stage2, dim3(1), dim3(256), 0, stream, blocks, partials, result_dev);
+}
+
+void reduce_partials(hipStream_t stream, uint32_t n_partials, const float* partials, float* result_dev) {
+	hipLaunchKernelGGL(k_reduce_stage2, dim3(1), dim3(256), 0, stream, n_partials, partials, result_dev);
 }
 
 AdamArgs make_adam_args(const AdamHyper& h, float loss_scale, uint32_t current_step) {

@@ -2865,6 +2865,56 @@ inline const char* to_string(LossType t) {
 	static const char* names[] = {"L2", "RelativeL2", "L1", "RelativeL1", "Mape", "Smape", "CrossEntropy", "Variance", "RelativeL2Luminance"};
 	return names[(uint32_t)t];
 }
+// Loss<T>::evaluate (loss.h:41-60) on predictions that are the caller's (tcnn_loss_evaluate): everything is checked here, before anything
+// touches the device; the partials of the sum come from the arena, so a call allocates nothing once warm and never synchronises.
+inline void loss_evaluate_on_predictions(hipStream_t stream, int type, int precision, float loss_scale, const float* scale_dev, uint32_t n, uint32_t dims,
+                                         const void* prediction, uint32_t prediction_stride, const float* target, const float* data_pdf,
+                                         float* values, uint32_t values_stride, void* gradients, uint32_t gradients_stride, float* loss_sum) {
+	const std::string who = "tcnn_loss_evaluate: ";
+	if (type < 0 || type > (int)LossType::RelativeL2Luminance) throw std::runtime_error{who + "Invalid loss type: " + std::to_string(type)};
+	if (precision != (int)Precision::Fp32 && precision != (int)Precision::Fp16) throw std::runtime_error{who + "Unknown precision " + std::to_string(precision)};
+	if (!values && !gradients && !loss_sum) throw std::runtime_error{who + "no output requested (values, gradients and loss_sum are all NULL)"};
+	if (dims < 1) throw std::runtime_error{who + "dims must be at least 1"};
+	if ((LossType)type == LossType::RelativeL2Luminance && dims < 3) throw std::runtime_error{who + "RelativeL2Luminance reads three channels per row and needs dims >= 3, got " + std::to_string(dims)};
+	uint32_t max_stride = prediction_stride;
+	const auto check_stride = [&](const char* name, uint32_t stride) {
+		if (stride < dims) throw std::runtime_error{who + "the " + name + " stride " + std::to_string(stride) + " is smaller than dims " + std::to_string(dims)};
+		max_stride = std::max(max_stride, stride);
+	};
+	check_stride("prediction", prediction_stride);
+	if (values) check_stride("values", values_stride);
+	if (gradients) check_stride("gradients", gradients_stride);
+	if ((uint64_t)n * max_stride >= (1ull << 32)) throw std::runtime_error{who + "n * stride must be below 2^32"};
+	if (n == 0) { // nothing to launch; the sum of no values
+		if (loss_sum) HIP_CHECK_THROW(hipMemsetAsync(loss_sum, 0, sizeof(float), stream));
+		return;
+	}
+	if (!prediction || !target) throw std::runtime_error{who + "prediction and target must not be NULL"};
+	LossEvalRequest r;
+	r.type = (LossType)type;
+	r.precision = (Precision)precision;
+	r.n = n;
+	r.dims = dims;
+	r.loss_scale = loss_scale;
+	r.scale_dev = scale_dev;
+	r.prediction = prediction;
+	r.prediction_stride = prediction_stride;
+	r.target = target;
+	r.data_pdf = data_pdf;
+	r.values = values;
+	r.values_stride = values_stride;
+	r.gradients = gradients;
+	r.gradients_stride = gradients_stride;
+	r.loss_sum = loss_sum;
+	ArenaBuf partials; // returned to the stream's free list when this call ends: the stream orders its reuse
+	if (loss_sum) {
+		partials = ArenaBuf{stream, LOSS_EVAL_MAX_BLOCKS * sizeof(float)};
+		r.partials = partials.as<float>();
+	}
+	loss_eval_launch(stream, r);
+	HIP_CHECK_THROW(hipGetLastError());
+}
+
 // the fused training kernel evaluates these two inside its loss stage; the others go forward -> k_loss -> backward
 inline bool loss_in_fused_kernel(LossType t) { return t == LossType::L2 || t == LossType::RelativeL2; }
 

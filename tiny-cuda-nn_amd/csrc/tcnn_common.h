@@ -683,6 +683,31 @@ void loss_evaluate(hipStream_t stream, LossType type, uint32_t n, uint32_t strid
                    const void* pred_half, const float* target, float* values, void* grads_half, const float* data_pdf, Precision precision = Precision::Fp16);
 // sum of n floats -> *result_dev (device float, overwritten). workspace-free: uses a two-stage reduction through `partials` (>= 1024 floats)
 void reduce_sum(hipStream_t stream, size_t n, const float* values, float* partials, float* result_dev);
+// reduce_sum's second stage alone: the sum of n_partials floats, in k_reduce_stage2's order, for kernels that write their own partials
+void reduce_partials(hipStream_t stream, uint32_t n_partials, const float* partials, float* result_dev);
+
+// Loss evaluation on caller-owned predictions (k_loss_eval.hip): every element is loss_element (loss_device.h), as in loss_evaluate.
+// Each output is optional (NULL) and has its own row stride; columns >= dims of an output row are written as zeros.
+constexpr uint32_t LOSS_EVAL_MAX_BLOCKS = 1024; // the fixed grid's bound = the number of floats `partials` must hold
+struct LossEvalRequest {
+	LossType type = LossType::L2;
+	Precision precision = Precision::Fp16; // of prediction and gradients
+	uint32_t n = 0, dims = 0;
+	float loss_scale = 1.0f;
+	const float* scale_dev = nullptr; // device, optional: one more fp32 factor of the gradient, multiplied in before its one rounding
+	const void* prediction = nullptr; // [n][prediction_stride], unit column stride
+	uint32_t prediction_stride = 0;
+	const float* target = nullptr;    // compact [n][dims]
+	const float* data_pdf = nullptr;  // compact [n][dims], optional
+	float* values = nullptr;          // [n][values_stride]
+	uint32_t values_stride = 0;
+	void* gradients = nullptr;        // [n][gradients_stride], in the prediction's type
+	uint32_t gradients_stride = 0;
+	float* loss_sum = nullptr;        // device: the sum of all values, reduced in a fixed order without storing them
+	float* partials = nullptr;        // with loss_sum: LOSS_EVAL_MAX_BLOCKS floats of workspace
+};
+// the arguments are the caller's to check (model.h: loss_evaluate_on_predictions); launches one kernel, and k_reduce_stage2 for loss_sum
+void loss_eval_launch(hipStream_t stream, const LossEvalRequest& r);
 
 struct AdamHyper {
 	float learning_rate = 1e-3f, beta1 = 0.9f, beta2 = 0.999f, epsilon = 1e-8f, l2_reg = 1e-8f;
