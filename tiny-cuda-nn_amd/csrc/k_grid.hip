@@ -333,8 +333,10 @@ void dispatch_bwd_F(hipStream_t s, const GridMeta& m, const GridMeta* dm, uint32
 void grid_forward(hipStream_t stream, const GridMeta& meta, const GridMeta* dev_meta, bool fp32, uint32_t n, MatView x, const void* grid, void* out, uint32_t out_stride, float* dy_dx,
                   uint64_t* chunk_mask) {
 	const uint32_t F = meta.n_features_per_level;
+	if (meta.n_pos_dims > 4) return grid_nd_forward(stream, meta, dev_meta, fp32, n, x, grid, out, out_stride, dy_dx, chunk_mask); // k_grid_nd.hip
 #define TCNN_GRID_FWD(T) \
 	switch (meta.n_pos_dims) { \
+		case 1: return dispatch_fwd_F<T, 1>(stream, F, dev_meta, n, x, grid, out, out_stride, dy_dx, chunk_mask); \
 		case 2: return dispatch_fwd_F<T, 2>(stream, F, dev_meta, n, x, grid, out, out_stride, dy_dx, chunk_mask); \
 		case 3: return dispatch_fwd_F<T, 3>(stream, F, dev_meta, n, x, grid, out, out_stride, dy_dx, chunk_mask); \
 		case 4: return dispatch_fwd_F<T, 4>(stream, F, dev_meta, n, x, grid, out, out_stride, dy_dx, chunk_mask); \
@@ -346,8 +348,10 @@ void grid_forward(hipStream_t stream, const GridMeta& meta, const GridMeta* dev_
 
 void grid_backward(hipStream_t stream, const GridMeta& meta, const GridMeta* dev_meta, bool fp32_grad, uint32_t n, MatView x, const void* dL_dy, bool dy_fp32, uint32_t dy_stride, void* grad,
                    bool stochastic) {
+	if (meta.n_pos_dims > 4) return grid_nd_backward(stream, meta, dev_meta, fp32_grad, n, x, dL_dy, dy_fp32, dy_stride, grad, stochastic); // k_grid_nd.hip
 #define TCNN_GRID_BWD(T, GT) \
 	switch (meta.n_pos_dims) { \
+		case 1: return dispatch_bwd_F<T, GT, 1>(stream, meta, dev_meta, n, x, dL_dy, dy_stride, grad, stochastic); \
 		case 2: return dispatch_bwd_F<T, GT, 2>(stream, meta, dev_meta, n, x, dL_dy, dy_stride, grad, stochastic); \
 		case 3: return dispatch_bwd_F<T, GT, 3>(stream, meta, dev_meta, n, x, dL_dy, dy_stride, grad, stochastic); \
 		case 4: return dispatch_bwd_F<T, GT, 4>(stream, meta, dev_meta, n, x, dL_dy, dy_stride, grad, stochastic); \
@@ -370,9 +374,13 @@ void grid_backward_input(hipStream_t stream, const GridMeta& meta, bool fp32, ui
 	if (blocks == 0) return;
 #define TCNN_GRID_BWDI(T) \
 	switch (meta.n_pos_dims) { \
+		case 1: hipLaunchKernelGGL((k_grid_bwd_input<T, 1>), dim3(blocks), dim3(128), 0, stream, n, nf, (const T*)dL_dy, dy_stride, dy_dx, dL_dx); return; \
 		case 2: hipLaunchKernelGGL((k_grid_bwd_input<T, 2>), dim3(blocks), dim3(128), 0, stream, n, nf, (const T*)dL_dy, dy_stride, dy_dx, dL_dx); return; \
 		case 3: hipLaunchKernelGGL((k_grid_bwd_input<T, 3>), dim3(blocks), dim3(128), 0, stream, n, nf, (const T*)dL_dy, dy_stride, dy_dx, dL_dx); return; \
 		case 4: hipLaunchKernelGGL((k_grid_bwd_input<T, 4>), dim3(blocks), dim3(128), 0, stream, n, nf, (const T*)dL_dy, dy_stride, dy_dx, dL_dx); return; \
+		case 5: hipLaunchKernelGGL((k_grid_bwd_input<T, 5>), dim3(blocks), dim3(128), 0, stream, n, nf, (const T*)dL_dy, dy_stride, dy_dx, dL_dx); return; \
+		case 6: hipLaunchKernelGGL((k_grid_bwd_input<T, 6>), dim3(blocks), dim3(128), 0, stream, n, nf, (const T*)dL_dy, dy_stride, dy_dx, dL_dx); return; \
+		case 7: hipLaunchKernelGGL((k_grid_bwd_input<T, 7>), dim3(blocks), dim3(128), 0, stream, n, nf, (const T*)dL_dy, dy_stride, dy_dx, dL_dx); return; \
 		default: throw std::runtime_error{"GridEncoding: number of input dims must be 2 or 3."}; \
 	}
 	if (fp32) { TCNN_GRID_BWDI(float) } else { TCNN_GRID_BWDI(half_t) }

@@ -66,6 +66,22 @@ __device__ inline void for_each_corner(const GridLevel& lv, const uint32_t (&pri
 		fn(level_index<D>(lv, primes, hash_type, local), 1.0f);
 		return;
 	}
+	if constexpr (D > 4) { // 5 - 7 dimensions: a rolled loop, the corner from bit tests on its counter (the form of k_grid_nd.hip)
+#pragma unroll 1
+		for (uint32_t idx = 0; idx < (1u << D); ++idx) {
+			float weight = 1;
+			uint32_t local[D];
+#pragma unroll
+			for (int d = 0; d < D; ++d) {
+				const bool up = (idx >> d) & 1u;
+				weight *= up ? pos[d] : 1 - pos[d];
+				local[d] = cell[d] + (up ? 1u : 0u);
+			}
+			asm volatile("" : "+v"(weight));
+			fn(level_index<D>(lv, primes, hash_type, local), weight);
+		}
+		return;
+	}
 #pragma unroll
 	for (int idx = 0; idx < (1 << D); ++idx) {
 		float weight = 1;
@@ -573,7 +589,7 @@ uint32_t grid_bin_acc_bytes() {
 
 bool grid_bin_supported(const GridMeta& meta) {
 	const uint32_t D = meta.n_pos_dims, F = meta.n_features_per_level;
-	return (F == 2 || F == 4 || F == 8) && D >= 2 && D <= 4;
+	return (F == 2 || F == 4 || F == 8) && D >= 1 && D <= GRID_MAX_DIMS;
 }
 
 size_t grid_bin_workspace_bytes(const GridMeta& meta, uint32_t n) { return bin_layout(meta, nullptr, n).bytes; }
@@ -597,9 +613,13 @@ void grid_backward_binned(hipStream_t stream, const GridMeta& meta, const GridMe
 	else launch_binned<D, 8, S>(stream, l, x, dL_dy, dy_stride_sample, dy_stride_level, grad, accumulate, ws, fallback_count);
 #define TCNN_BIN(D) if (stochastic) { TCNN_BIN_F(D, true) } else { TCNN_BIN_F(D, false) }
 	switch (meta.n_pos_dims) {
+		case 1: TCNN_BIN(1) break;
 		case 2: TCNN_BIN(2) break;
 		case 3: TCNN_BIN(3) break;
-		default: TCNN_BIN(4) break;
+		case 4: TCNN_BIN(4) break;
+		case 5: TCNN_BIN(5) break;
+		case 6: TCNN_BIN(6) break;
+		default: TCNN_BIN(7) break;
 	}
 #undef TCNN_BIN_F
 #undef TCNN_BIN

@@ -273,8 +273,23 @@ void launch_all(hipStream_t s, const GridMeta& meta, const GridMeta* dm, uint32_
 void grid_backward_backward_input(hipStream_t stream, const GridMeta& meta, const GridMeta* dev_meta, bool fp32, bool fp32_grad, uint32_t n, MatView x, MatView dL_ddLdx, const void* dL_dy,
                                   uint32_t dy_stride, const void* grid, const float* dy_dx, void* grad, void* dL_ddLdy, MatViewMut* dL_dx) {
 	if (n == 0) return;
+	if (meta.n_pos_dims > 4) { // k_grid_nd.hip: the grid and the input term in the rolled form; dL_ddLdy walks no corners and keeps its kernel
+		grid_nd_backward_backward_input(stream, meta, dev_meta, fp32, fp32_grad, n, x, dL_ddLdx, dL_dy, dy_stride, grid, grad, dL_dx);
+		if (!dL_ddLdy) return;
+		CHECK_THROW(dy_dx != nullptr);
+		const uint32_t nf = meta.n_levels * meta.n_features_per_level;
+		const dim3 blocks(div_round_up(n, 128));
+#define TCNN_BB_DDY(T, D) hipLaunchKernelGGL((k_grid_bwdbwd_dLdoutput<T, D>), blocks, dim3(128), 0, stream, n, nf, dL_ddLdx, dy_dx, (T*)dL_ddLdy, dy_stride)
+#define TCNN_BB_DDY_D(T) switch (meta.n_pos_dims) { case 5: TCNN_BB_DDY(T, 5); break; case 6: TCNN_BB_DDY(T, 6); break; default: TCNN_BB_DDY(T, 7); break; }
+		if (fp32) { TCNN_BB_DDY_D(float) } else { TCNN_BB_DDY_D(half_t) }
+#undef TCNN_BB_DDY_D
+#undef TCNN_BB_DDY
+		HIP_CHECK_THROW(hipGetLastError());
+		return;
+	}
 #define TCNN_BB(T, GT) \
 	switch (meta.n_pos_dims) { \
+		case 1: return launch_all<T, GT, 1>(stream, meta, dev_meta, n, x, dL_ddLdx, dL_dy, dy_stride, grid, dy_dx, grad, dL_ddLdy, dL_dx); \
 		case 2: return launch_all<T, GT, 2>(stream, meta, dev_meta, n, x, dL_ddLdx, dL_dy, dy_stride, grid, dy_dx, grad, dL_ddLdy, dL_dx); \
 		case 3: return launch_all<T, GT, 3>(stream, meta, dev_meta, n, x, dL_ddLdx, dL_dy, dy_stride, grid, dy_dx, grad, dL_ddLdy, dL_dx); \
 		case 4: return launch_all<T, GT, 4>(stream, meta, dev_meta, n, x, dL_ddLdx, dL_dy, dy_stride, grid, dy_dx, grad, dL_ddLdy, dL_dx); \

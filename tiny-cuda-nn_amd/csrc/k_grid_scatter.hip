@@ -162,6 +162,23 @@ __global__ void __launch_bounds__(SCATTER_THREADS) k_grid_scatter(
 			}
 			return;
 		}
+		if constexpr (D > 4) {
+			// 5 - 7 dimensions: 32 - 128 corners do not fit registers as (index, weight) pairs; the corners are walked in lockstep instead,
+			// a rolled loop whose corner comes from bit tests on the loop counter (the form of k_grid_nd.hip)
+#pragma unroll 1
+			for (uint32_t idx = 0; idx < (1u << D); ++idx) {
+				float weight = 1;
+				uint32_t local[D];
+#pragma unroll
+				for (int d = 0; d < D; ++d) {
+					const bool up = (idx >> d) & 1u;
+					weight *= up ? pos[d] : 1 - pos[d];
+					local[d] = cell[d] + (up ? 1u : 0u);
+				}
+				add(local, weight);
+			}
+			return;
+		}
 		// All 2^D corners are located first; then the wave adds "the next corner of mine that falls into the chunk" until no
 		// lane has one left.  A sample that reaches this point typically owns 2^(D-1) such corners (one row of the cell), so
 		// this takes half as many -- fully populated -- LDS atomic instructions as walking the corners in lockstep.
@@ -228,6 +245,28 @@ __global__ void __launch_bounds__(SCATTER_THREADS) k_grid_scatter(
 				}
 				return;
 			}
+		}
+		if constexpr (D > 4) { // the rolled form (see accumulate)
+#pragma unroll 1
+			for (uint32_t idx = 0; idx < (nearest ? 1u : (uint32_t)C); ++idx) {
+				float weight = 1;
+				uint32_t local[D];
+#pragma unroll
+				for (int d = 0; d < D; ++d) {
+					const bool up = (idx >> d) & 1u;
+					weight *= up ? pos[d] : (nearest ? 1.0f : 1 - pos[d]);
+					local[d] = cell[d] + (up ? 1u : 0u);
+				}
+				asm volatile("" : "+v"(weight));
+				const uint32_t index = level_index<D>(lv, primes, hash_type, local);
+				const half_t w = (half_t)weight;
+#pragma unroll
+				for (int f = 0; f < F; ++f) {
+					const half_t c = w * gv[f];
+					__hip_atomic_fetch_add(acc_lds + index * F + f, (unsigned long long)half_to_fixed_fast(c), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+				}
+			}
+			return;
 		}
 #pragma unroll
 		for (int idx = 0; idx < C; ++idx) {
@@ -819,9 +858,13 @@ bool grid_backward_lds(hipStream_t stream, const GridMeta& meta, const GridMeta*
 		~TimesGuard() { g_task_times = nullptr; }
 	} guard{task_times};
 	switch (meta.n_pos_dims) {
+		case 1: dispatch_scatter<1>(stream, meta.n_features_per_level, dev_meta, dev_tasks, n_tasks, n, x, dL_dy, dy_stride_sample, dy_stride_level, grad, bits, sc, accumulate, dy_records, stochastic); break;
 		case 2: dispatch_scatter<2>(stream, meta.n_features_per_level, dev_meta, dev_tasks, n_tasks, n, x, dL_dy, dy_stride_sample, dy_stride_level, grad, bits, sc, accumulate, dy_records, stochastic); break;
 		case 3: dispatch_scatter<3>(stream, meta.n_features_per_level, dev_meta, dev_tasks, n_tasks, n, x, dL_dy, dy_stride_sample, dy_stride_level, grad, bits, sc, accumulate, dy_records, stochastic); break;
 		case 4: dispatch_scatter<4>(stream, meta.n_features_per_level, dev_meta, dev_tasks, n_tasks, n, x, dL_dy, dy_stride_sample, dy_stride_level, grad, bits, sc, accumulate, dy_records, stochastic); break;
+		case 5: dispatch_scatter<5>(stream, meta.n_features_per_level, dev_meta, dev_tasks, n_tasks, n, x, dL_dy, dy_stride_sample, dy_stride_level, grad, bits, sc, accumulate, dy_records, stochastic); break;
+		case 6: dispatch_scatter<6>(stream, meta.n_features_per_level, dev_meta, dev_tasks, n_tasks, n, x, dL_dy, dy_stride_sample, dy_stride_level, grad, bits, sc, accumulate, dy_records, stochastic); break;
+		case 7: dispatch_scatter<7>(stream, meta.n_features_per_level, dev_meta, dev_tasks, n_tasks, n, x, dL_dy, dy_stride_sample, dy_stride_level, grad, bits, sc, accumulate, dy_records, stochastic); break;
 		default: throw std::runtime_error{"GridEncoding: number of input dims must be 2 or 3."};
 	}
 	return grid_scatter_finalize(stream, dev_ranges, n_ranges, scratch, grad, accumulate, reduce_job);

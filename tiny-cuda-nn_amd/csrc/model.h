@@ -347,7 +347,7 @@ public:
 		const float per_level_scale = enc.value("per_level_scale", grid_type == GridType::Dense ? std::exp(std::log(256.0f / (float)base_resolution) / (n_levels - 1)) : 2.0f);
 		const HashType hash_type = string_to_hash_type(enc.value("hash", "CoherentPrime"));
 		m_stochastic_interpolation = enc.value("stochastic_interpolation", false); // grid.h:284-298: read by the parameter-gradient pass alone (GridBackwardRoute::stochastic)
-		if (n_dims_to_encode < 2 || n_dims_to_encode > 4) throw std::runtime_error{"GridEncoding: number of input dims must be 2 or 3."};
+		if (n_dims_to_encode < 1 || n_dims_to_encode > GRID_MAX_DIMS) throw std::runtime_error{"GridEncoding: number of input dims must be 2 or 3."}; // (grid.h:1181: the reference's text)
 		if (n_levels > MAX_N_LEVELS) throw std::runtime_error{"GridEncoding: m_n_levels must be at most MAX_N_LEVELS=128"};
 		if (n_features % F != 0) throw std::runtime_error{"GridEncoding: n_features must be a multiple of N_FEATURES_PER_LEVEL"};
 
@@ -367,7 +367,7 @@ public:
 		static const uint32_t coherent[7] = {1u, 2654435761u, 805459861u, 3674653429u, 2097192037u, 1434869437u, 2165219737u};
 		static const uint32_t reversed[7] = {2165219737u, 1434869437u, 2097192037u, 3674653429u, 805459861u, 2654435761u, 1958374283u};
 		const uint32_t* primes = hash_type == HashType::Prime ? prime : (hash_type == HashType::ReversedPrime ? reversed : coherent);
-		for (uint32_t d = 0; d < 4; ++d) m_meta.primes[d] = primes[d]; // common_device.h:645-661
+		for (uint32_t d = 0; d < GRID_MAX_DIMS; ++d) m_meta.primes[d] = primes[d]; // common_device.h:645-661
 
 		const float log2_scale = std::log2(per_level_scale); // float overload (grid.h:694)
 		uint32_t offset = 0;
@@ -386,7 +386,7 @@ public:
 			lv.scale = scale;
 			// grid_index's stride loop (common_device.h:692-704), evaluated once here, uint32 wrap-around included
 			uint32_t stride = 1;
-			for (uint32_t d = 0; d < 4; ++d) lv.stride[d] = 0;
+			for (uint32_t d = 0; d < GRID_MAX_DIMS; ++d) lv.stride[d] = 0;
 			for (uint32_t d = 0; d < n_dims_to_encode && stride <= params_in_level; ++d) {
 				lv.stride[d] = stride;
 				stride *= resolution;

@@ -114,12 +114,13 @@ inline uint32_t next_multiple(uint32_t v, uint32_t d) { return div_round_up(v, d
 // Grid encoding: per-level table precomputed on the HOST (so host and device agree bit-for-bit on scale/resolution,
 // SURVEY 7 "hard parts"); the encoding keeps one device copy (6 KiB, too large for the kernarg segment).
 // ------------------------------------------------------------------------------------------------------------------
+constexpr uint32_t GRID_MAX_DIMS = 7; // dimensions a grid encodes: the hash has seven primes (common_device.h:633)
 struct GridLevel {
 	uint32_t offset;      // first entry of the level (in entries, grid.h:714)
 	uint32_t size;        // hashmap_size = entries in the level
 	float    scale;       // grid_scale(level) (common_device.h:709-714)
 	uint32_t hashed;      // 1: index = hash(cell) ; 0: index = sum cell_d * stride[d]   (common_device.h:690-707)
-	uint32_t stride[4];   // per-dim stride of the dense index INCLUDING the uint32 wrap-around / early-exit behaviour
+	uint32_t stride[GRID_MAX_DIMS]; // per-dim stride of the dense index INCLUDING the uint32 wrap-around / early-exit behaviour
 	uint32_t size_mask;   // size-1 if size is a power of two, else 0 (then a real modulo is used)
 	// LDS owner-computes scatter (k_grid_bwd_lds): the level's table is cut into scatter_n_chunks chunks of scatter_per_chunk entries
 	uint32_t scatter_per_chunk;
@@ -135,7 +136,7 @@ struct GridMeta {
 	uint32_t grid_type;
 	uint32_t hash_type;
 	uint32_t interpolation;
-	uint32_t primes[4];
+	uint32_t primes[GRID_MAX_DIMS];
 	GridLevel levels[MAX_N_LEVELS];
 };
 
@@ -155,6 +156,15 @@ struct MatViewMut {
 // chunk_mask (optional, uint64 [n_levels][n][GRID_FILTER_MAX_CHUNKS / 64]): bit c set <=> the sample touches scatter chunk c of that level (filter for k_grid_scatter)
 void grid_forward(hipStream_t stream, const GridMeta& meta, const GridMeta* dev_meta, bool fp32, uint32_t n, MatView x, const void* grid, void* out, uint32_t out_stride, float* dy_dx,
                   uint64_t* chunk_mask);
+// ---- 5, 6 and 7 dimensions (k_grid_nd.hip): the same three passes in the rolled kernel form; grid_forward, grid_backward and
+// grid_backward_backward_input hand such grids on to these
+void grid_nd_forward(hipStream_t stream, const GridMeta& meta, const GridMeta* dev_meta, bool fp32, uint32_t n, MatView x, const void* grid, void* out, uint32_t out_stride, float* dy_dx,
+                     uint64_t* chunk_mask);
+void grid_nd_backward(hipStream_t stream, const GridMeta& meta, const GridMeta* dev_meta, bool fp32_grad, uint32_t n, MatView x, const void* dL_dy, bool dy_fp32, uint32_t dy_stride, void* grad,
+                      bool stochastic);
+// (the grid and the input term; dL_ddLdy has no corner loop and keeps k_grid_bwdbwd_dLdoutput)
+void grid_nd_backward_backward_input(hipStream_t stream, const GridMeta& meta, const GridMeta* dev_meta, bool fp32, bool fp32_grad, uint32_t n, MatView x, MatView dL_ddLdx, const void* dL_dy,
+                                     uint32_t dy_stride, const void* grid, void* grad, MatViewMut* dL_dx);
 // ---- training-step forward (k_grid_planes.hip): half, F >= 2, D in {2, 3}; level-major and XCD-aware.
 // out_planes: half [n_levels][n][F]; chunk_bits (optional): uint64 [n_levels][GRID_FILTER_MAX_CHUNKS][n / 64], written for levels with 2 .. GRID_FILTER_MAX_CHUNKS scatter chunks.
 bool grid_planes_supported(const GridMeta& meta, uint32_t n);
