@@ -145,6 +145,25 @@ int  tcnn_module_input_jacobian(tcnn_module_t m, tcnn_stream_t stream, uint32_t 
 /* The route the module's last input_jacobian call took: "none" before the first call, "two-pass" (one forward pass, n_dims backward passes)
  * or the fused MLP kernel's name, "k_mlp_input_jacobian<W,NB,NH>/relu|act".  Owned by the module, as tcnn_module_last_input_gradient_route. */
 const char* tcnn_module_last_input_jacobian_route(tcnn_module_t m);
+/* Forward mode, the opposite question: how do ALL outputs change when the input moves along a direction v.  tangents [n_elements][n_tangents]
+ * [n_input_dims] floats, row-major, n_tangents >= 1; jvp [n_elements][n_tangents][tcnn_module_n_output_dims] in the module's OUTPUT
+ * precision (tcnn_module_output_precision), row-major: jvp[:, t, :] = J(x) tangents[:, t, :] -- d/dt of every feature of a 4-D field, grad f . d
+ * along a ray, a 3 x 3 (or n_out x 3) deformation Jacobian from three directions.  Runs at inference: no parameter gradient is read or written
+ * and no context is left; a grid encoding's max_level state applies as in any forward pass.  output (may be NULL), [n_elements]
+ * [tcnn_module_n_output_dims] in the output precision, is bit for bit what tcnn_module_inference returns.  Padded output columns hold what the
+ * second-order pass puts there.  On the route "two-pass" -- one forward pass with input gradients prepared, then per direction the
+ * encoding's tangent and the network's layer-by-layer tangent pass -- jvp[:, t, :] is bit for bit the dL_ddLdoutput that tcnn_module_forward
+ * (prepare_input_gradients = 1) + tcnn_module_backward_backward_input(dL_ddLdinput = tangents[:, t, :]) return, for every module that has that
+ * pass; FullyFusedMLP networks and OneBlob encodings, which have none, have tangents all the same.  There is NO backprop_scale: the map is linear
+ * in v, so a caller who fears overflow in half precision scales v and divides the result.  Checked before anything is allocated or
+ * launched: NULL tangents or jvp, n_tangents == 0 (a message that names n_tangents), n_elements off tcnn_batch_size_granularity(), and a module
+ * without a tangent -- PPNG1, PPNG2 or a Composite holding one: "input_jvp: not implemented for <module name>".  A refused call leaves the
+ * route strings alone. */
+int  tcnn_module_input_jvp(tcnn_module_t m, tcnn_stream_t stream, uint32_t n_elements, uint32_t n_tangents, const float* input, const float* tangents, void* jvp, void* output,
+                           const void* params);
+/* The route the module's last input_jvp call took: "none" before the first call, "two-pass", or the fused MLP kernel's name,
+ * "k_mlp_input_jvp<W,NB,NH,TT>/relu|act" (TT: tangent chains per launch).  Owned by the module, as tcnn_module_last_input_gradient_route. */
+const char* tcnn_module_last_input_jvp_route(tcnn_module_t m);
 void tcnn_context_destroy(tcnn_context_t ctx);
 
 uint32_t    tcnn_module_n_input_dims(tcnn_module_t m);     /* cpp_api.cu:129 */
@@ -205,6 +224,9 @@ int  tcnn_trainer_input_gradient(tcnn_trainer_t t, tcnn_stream_t stream, uint32_
 /* tcnn_module_input_jacobian on the trainer's inference parameters: jacobian [n_elements][n_dims][n_input_dims] floats; dims is a host array */
 int  tcnn_trainer_input_jacobian(tcnn_trainer_t t, tcnn_stream_t stream, uint32_t n_elements, const uint32_t* dims, uint32_t n_dims, const float* input, float* jacobian,
                                  float backprop_scale);
+/* tcnn_module_input_jvp on the trainer's inference parameters: tangents [n_elements][n_tangents][n_input_dims] floats, jvp [n_elements][n_tangents]
+ * [padded output width] in the trainer's precision */
+int  tcnn_trainer_input_jvp(tcnn_trainer_t t, tcnn_stream_t stream, uint32_t n_elements, uint32_t n_tangents, const float* input, const float* tangents, void* jvp);
 
 /* network->inference_mixed_precision(stream, input, output) (object.h:133-145): the network's own output, half
  * [n_elements][padded_output_width] -- what inference() casts to float; half the bytes for a caller that gathers row shards.

@@ -87,6 +87,12 @@ public:
 		detail::ok(tcnn_module_input_jacobian(m_handle, stream, n_elements, dims, n_dims, input, jacobian, output, params, backprop_scale));
 	}
 	std::string last_input_jacobian_route() const { return tcnn_module_last_input_jacobian_route(m_handle); } // "none" | "two-pass" | the fused kernel's name
+	// forward mode: jvp [n_elements][n_tangents][n_output_dims()] in output_precision(), jvp[:, t, :] = J(x) tangents[:, t, :] for tangents
+	// [n_elements][n_tangents][n_input_dims()] floats; output may be null.  No backprop_scale (linear in the tangent).  See tcnn_module_input_jvp.
+	void input_jvp(stream_t stream, uint32_t n_elements, uint32_t n_tangents, const float* input, const float* tangents, void* jvp, void* output, const void* params) {
+		detail::ok(tcnn_module_input_jvp(m_handle, stream, n_elements, n_tangents, input, tangents, jvp, output, params));
+	}
+	std::string last_input_jvp_route() const { return tcnn_module_last_input_jvp_route(m_handle); } // "none" | "two-pass" | the fused kernel's name
 
 	uint32_t n_input_dims() const { return tcnn_module_n_input_dims(m_handle); }
 	uint32_t n_output_dims() const { return tcnn_module_n_output_dims(m_handle); } // padded width, cpp_api.cu:130

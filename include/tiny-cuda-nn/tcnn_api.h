@@ -311,6 +311,17 @@ public:
 		if (input.m() != m_n_input_dims || jacobian.m() != dims.size() * m_n_input_dims || input.n() != jacobian.n()) throw std::runtime_error{"input_jacobian: matrix shapes do not match the network"};
 		detail::check(tcnn_trainer_input_jacobian(m_trainer, stream, input.n(), dims.data(), (uint32_t)dims.size(), input.data(), jacobian.data(), backprop_scale));
 	}
+	// Forward mode: every output's derivative along n_tangents input directions.  tangents is column-major (n_tangents * n_dims) x batch --
+	// sample i's block is [n_tangents][n_dims] -- and jvp column-major (n_tangents * padded_output_width()) x batch in the network's
+	// precision T: sample i's block is [n_tangents][padded_output_width()], row t = J(x_i) tangents_i[t].  No backprop_scale: the map is
+	// linear in the tangent (tcnn_amd.h: tcnn_module_input_jvp).
+	void input_jvp(stream_t stream, uint32_t n_tangents, const GPUMatrix<float>& input, const GPUMatrix<float>& tangents, GPUMatrix<T>& jvp) {
+		if (!m_trainer) throw std::runtime_error{"NetworkWithInputEncoding::input_jvp: the network has no parameters yet (construct a Trainer first)"};
+		if (input.m() != m_n_input_dims || tangents.m() != n_tangents * m_n_input_dims || jvp.m() != n_tangents * padded_output_width() || input.n() != tangents.n() || input.n() != jvp.n()) {
+			throw std::runtime_error{"input_jvp: matrix shapes do not match the network"};
+		}
+		detail::check(tcnn_trainer_input_jvp(m_trainer, stream, input.n(), n_tangents, input.data(), tangents.data(), jvp.data()));
+	}
 
 	uint32_t input_width() const { return m_n_input_dims; }
 	uint32_t output_width() const { return m_n_output_dims; }

@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libtcnn_amd.so")
-SOURCES = ["k_grid.hip", "k_grid_nd.hip", "k_grid_planes.hip", "k_grid_scatter.hip", "k_grid_scatter_lists.hip", "k_grid_bin.hip", "k_grid_bwdbwd.hip", "k_grid_max_level.hip", "k_encodings.hip", "k_ppng.hip", "k_mlp.hip", "k_mlp_input_grad.hip", "k_mlp_input_jacobian.hip", "k_mlp_layers.hip", "k_mlp_layers_f32.hip", "k_train.hip", "k_train_regs.hip", "k_train_r32.hip", "k_train_r32a.hip", "k_train_r32ob.hip", "k_train_r32w.hip", "k_misc.hip", "k_loss_eval.hip", "capi.cpp"]
+SOURCES = ["k_grid.hip", "k_grid_nd.hip", "k_grid_planes.hip", "k_grid_scatter.hip", "k_grid_scatter_lists.hip", "k_grid_bin.hip", "k_grid_bwdbwd.hip", "k_grid_max_level.hip", "k_encodings.hip", "k_ppng.hip", "k_mlp.hip", "k_mlp_input_grad.hip", "k_mlp_input_jacobian.hip", "k_mlp_input_jvp.hip", "k_mlp_layers.hip", "k_mlp_layers_f32.hip", "k_train.hip", "k_train_regs.hip", "k_train_r32.hip", "k_train_r32a.hip", "k_train_r32ob.hip", "k_train_r32w.hip", "k_misc.hip", "k_loss_eval.hip", "capi.cpp"]
 HEADERS = ["tcnn_common.h", "grid_device.h", "grid_fixed.h", "mlp_device.h", "mlp_input_grad_device.h", "r32_device.h", "r32_train.h", "mlp_train_kernels.h", "mlp_side_jobs.h", "adam_device.h", "oneblob_device.h", "loss_device.h", "reduce_device.h", "model.h", "json_lite.h", os.path.join("..", "..", "include", "tcnn_amd.h"),
            os.path.join("..", "..", "include", "tiny-cuda-nn", "json_lite.h")]
 # -ffp-contract=off: fused multiply-adds only where the source says fma (bit-exact grid arithmetic, see k_grid.hip)

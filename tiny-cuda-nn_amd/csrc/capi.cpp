@@ -292,6 +292,21 @@ const char* tcnn_module_last_input_jacobian_route(tcnn_module_t m) {
 	return m->model->last_input_jacobian_route();
 }
 
+int tcnn_module_input_jvp(tcnn_module_t m, tcnn_stream_t stream, uint32_t n, uint32_t n_tangents, const float* input, const float* tangents, void* jvp, void* output, const void* params) {
+	return guarded([&] {
+		CHECK_THROW(m && m->model);
+		m->model->input_jvp((hipStream_t)stream, n, n_tangents, MatView{input, m->model->input_width(), 1u}, tangents, jvp, output, params);
+	});
+}
+
+const char* tcnn_module_last_input_jvp_route(tcnn_module_t m) {
+	if (!m || !m->model) {
+		g_last_error = "tcnn_module_last_input_jvp_route: null module";
+		return nullptr;
+	}
+	return m->model->last_input_jvp_route();
+}
+
 void tcnn_context_destroy(tcnn_context_t ctx) { delete ctx; }
 
 uint32_t tcnn_module_n_input_dims(tcnn_module_t m) { return m->model->input_width(); }
@@ -471,6 +486,14 @@ int tcnn_trainer_input_jacobian(tcnn_trainer_t t, tcnn_stream_t stream, uint32_t
 		CHECK_THROW(t && t->trainer);
 		Trainer& tr = *t->trainer;
 		tr.input_jacobian((hipStream_t)stream, n, dims, n_dims, MatView{input, tr.model().input_width(), 1u}, jacobian, backprop_scale);
+	});
+}
+
+int tcnn_trainer_input_jvp(tcnn_trainer_t t, tcnn_stream_t stream, uint32_t n, uint32_t n_tangents, const float* input, const float* tangents, void* jvp) {
+	return guarded([&] {
+		CHECK_THROW(t && t->trainer);
+		Trainer& tr = *t->trainer;
+		tr.input_jvp((hipStream_t)stream, n, n_tangents, MatView{input, tr.model().input_width(), 1u}, tangents, jvp);
 	});
 }
 

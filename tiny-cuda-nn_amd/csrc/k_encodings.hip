@@ -5,12 +5,15 @@
 //   encodings/triangle_wave.h:44-107       triangle_wave_encoding / _backward    -> k_trianglewave_fwd, k_periodic_bwd_input
 //   encodings/spherical_harmonics.h:44-108 kernel_sh / kernel_sh_backward, common_device.h:339-700 sh_enc / sh_enc_grad
 //                                                                                -> k_sh_fwd, k_sh_bwd_input
+// Also here: k_oneblob_tangent, the OneBlob encoding's tangent for input_jvp (no counterpart in the reference; the encoding's other
+// kernels are in k_misc.hip).
 // All streaming, AoS output [n][out_stride] (padding = 1).  The reference hard-codes the 64 spherical-harmonic polynomials
 // of degree <= 8 and their 192 partial derivatives (generated from the recurrences of Sloan, "Stupid Spherical Harmonics
 // Tricks", appendix A1); here the same polynomials are evaluated through those recurrences (see the oracle's sh_eval): identical
 // functions of (x, y, z), summed in another floating-point order (~1e-7 relative).  Frequency: sinf / cosf instead of the
 // reference's __sinf / __cosf hardware approximations.
 #include "tcnn_common.h"
+#include "oneblob_device.h" // k_oneblob_tangent: the OneBlob kernel's derivative, as k_misc.hip's k_oneblob_bwd_input forms it
 
 #include <hip/hip_fp16.h>
 
@@ -448,6 +451,48 @@ void composite_reduce_backward(hipStream_t stream, bool fp32, bool product, size
 		if (product) hipLaunchKernelGGL((k_composite_reduce_bwd<_Float16, true>), grid, dim3(256), 0, stream, n_elems, n_nested, (const _Float16*)in, (const _Float16*)dL_dout, (_Float16*)dL_din);
 		else hipLaunchKernelGGL((k_composite_reduce_bwd<_Float16, false>), grid, dim3(256), 0, stream, n_elems, n_nested, (const _Float16*)in, (const _Float16*)dL_dout, (_Float16*)dL_din);
 	}
+}
+
+namespace {
+// The OneBlob encoding's tangent J v (input_jvp; the encoding has no second-order pass and needs none for this).  One thread per element of
+// the padded row: column d * n_bins + b holds (T)(v[d] * k'), where k' = (derivative of C at bin b's left edge) - (at its right edge) is
+// formed from the very expressions k_oneblob_bwd_input (k_misc.hip) walks through bin by bin -- its `left` of bin b is its `right` of
+// bin b - 1, evaluated at scalbnf(b, -log2_bins), and at bin 0 it reads -x where this reads 0 - x: the quartic squares its argument and
+// (+-0) +- 1 is +-1 either way, so every k' has that kernel's bits.  One rounding of the fp32 product; the padding columns are exactly zero.
+template <typename T>
+__global__ void __launch_bounds__(256) k_oneblob_tangent(const uint32_t n_elements, const uint32_t n_dims, const uint32_t log2_bins, const uint32_t t_stride, const MatView x, const MatView v,
+                                                         T* __restrict__ t) {
+	const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+	if (e >= n_elements) return;
+	const uint32_t i = e / t_stride, j = e - i * t_stride;
+	const uint32_t d = j >> log2_bins, b = j & ((1u << log2_bins) - 1);
+	if (d >= n_dims) {
+		t[e] = (T)0.0f;
+		return;
+	}
+	const float nb = (float)(1u << log2_bins);
+	const float xv = x.data[(size_t)i * x.stride_sample + (size_t)d * x.stride_dim];
+	const float lb = scalbnf((float)b, -(int)log2_bins), rb = scalbnf((float)(b + 1), -(int)log2_bins);
+	const float left = quartic_cdf_deriv(lb - xv, nb) + quartic_cdf_deriv(lb - xv - 1.0f, nb) + quartic_cdf_deriv(lb - xv + 1.0f, nb);
+	const float right = quartic_cdf_deriv(rb - xv, nb) + quartic_cdf_deriv(rb - xv - 1.0f, nb) + quartic_cdf_deriv(rb - xv + 1.0f, nb);
+	const float deriv = left - right;
+	// the fp32 product as a value of its own: contracted with the conversion into one fused multiply-add onto +0 (v_fma_mixlo_f16), a
+	// negative v times k' = 0 would come out as +0 instead of the product's -0
+	float product = v.data[(size_t)i * v.stride_sample + (size_t)d * v.stride_dim] * deriv;
+	asm volatile("" : "+v"(product));
+	t[e] = (T)product;
+}
+} // namespace
+
+void oneblob_tangent(hipStream_t stream, bool fp32, uint32_t n, uint32_t n_dims, uint32_t n_bins, MatView x, MatView v, void* t, uint32_t t_stride) {
+	const uint64_t total = (uint64_t)n * t_stride;
+	if (total == 0) return;
+	CHECK_THROW(total < (1ull << 32) && n_bins > 0 && (n_bins & (n_bins - 1)) == 0 && t_stride >= n_dims * n_bins && x.data && v.data && t);
+	uint32_t lb = 0;
+	while ((1u << lb) < n_bins) ++lb;
+	const dim3 blocks((uint32_t)((total + 255) / 256));
+	if (fp32) hipLaunchKernelGGL((k_oneblob_tangent<float>), blocks, dim3(256), 0, stream, (uint32_t)total, n_dims, lb, t_stride, x, v, (float*)t);
+	else hipLaunchKernelGGL((k_oneblob_tangent<half_t>), blocks, dim3(256), 0, stream, (uint32_t)total, n_dims, lb, t_stride, x, v, (half_t*)t);
 }
 
 } // namespace tcnn_amd

@@ -285,6 +285,13 @@ public:
 	// the error comes before anything of its own is allocated or launched (NetworkWithInputEncoding).
 	virtual bool has_second_order() const { return false; }
 	virtual bool second_order_reads_dL_dy() const { return true; } // false: backward_backward_input() needs no dL_dy (dL/dx is linear in x)
+	// input_jvp: the tangent alone, t [n][padded] T = J v for v [n][d_in] fp32 (exactly zero in the padding columns), on the context of a
+	// forward(prepare_input_gradients).  Every encoding with a second-order pass has it there -- backward_backward_input() asked for
+	// dL_ddLdy only, so that t is that pass's dL_ddLdy bit for bit; OneBlob has a kernel for it; PPNG1 / PPNG2 have none.
+	virtual bool has_tangent() const { return has_second_order(); }
+	virtual void tangent(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, MatView v, void* t, const void* params) {
+		backward_backward_input(stream, ctx, n, x, v, nullptr, t, nullptr, params, nullptr, GradientMode::Ignore);
+	}
 	// true: the encoding is half(x * scale + offset) padded with ones -- cheap enough to apply inside the consumer's load
 	virtual bool as_identity(float& scale, float& offset) const { return false; }
 	// n_bins if this is a half-precision OneBlob encoding the MLP kernels can evaluate inside their input load (MlpIo::x_oneblob_bins), else 0
@@ -910,6 +917,11 @@ public:
 		if (!dL_dx) return;
 		oneblob_backward_input(stream, m_fp32, n, m_n_dims, m_n_bins, x, dL_dy, padded_output_width(), *dL_dx);
 	}
+	// no second-order pass (as in the reference), but a tangent: (T)(v k') with backward()'s k' (k_oneblob_tangent)
+	bool has_tangent() const override { return true; }
+	void tangent(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, MatView v, void* t, const void* params) override {
+		if (t && padded_output_width() > 0 && n > 0) oneblob_tangent(stream, m_fp32, n, m_n_dims, m_n_bins, x, v, t, padded_output_width());
+	}
 	Json hyperparams() const override {
 		Json j = Json::object();
 		j["otype"] = "OneBlob";
@@ -1452,6 +1464,50 @@ public:
 		}
 		if (dL_dx) add_input_gradient(stream, n, m_n_dims, MatView{dx_view.data, dx_view.stride_sample, dx_view.stride_dim}, *dL_dx);
 	}
+	// The tangent alone: what backward_backward_input() runs for dL_ddLdy -- the nested tangents on their slices of x and v, copied into
+	// their column ranges (Concatenation), summed (Sum), or sum_i t_i P_i (Product) by the same kernels on the same values -- but through
+	// the nested tangent(), so that a nested OneBlob, which has no second-order pass, takes part.
+	bool has_tangent() const override {
+		for (const auto& e : m_nested) {
+			if (!e->has_tangent()) return false;
+		}
+		return true;
+	}
+	void tangent(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, MatView v, void* t, const void* params) override {
+		if (n == 0 || !t) return;
+		CHECK_THROW(has_tangent() && ctx.nested.size() == m_nested.size());
+		const size_t elem = m_fp32 ? 4 : 2;
+		const auto slice = [&](const MatView& m, size_t i) { return MatView{m.data + (size_t)m_begin[i] * m.stride_dim, m.stride_sample, m.stride_dim}; };
+		size_t p_off = 0;
+		if (m_reduction == Reduction::Concatenation) {
+			uint32_t col = 0;
+			for (size_t i = 0; i < m_nested.size(); ++i) {
+				Encoding& e = *m_nested[i];
+				const uint32_t w = e.padded_output_width();
+				if (w > 0) {
+					ArenaBuf t_block{stream, (size_t)n * w * elem};
+					e.tangent(stream, ctx.nested[i], n, slice(x, i), slice(v, i), t_block.data(), (const char*)params + p_off * elem);
+					copy_columns(stream, elem, n, t_block.data(), w, 0, t, padded_output_width(), col, w);
+				}
+				col += w;
+				p_off += e.n_params();
+			}
+			return;
+		}
+		const uint32_t n_nested = (uint32_t)m_nested.size();
+		const uint32_t w = reduction_width();
+		const size_t n_elems = (size_t)n * w, block_bytes = n_elems * elem;
+		if (w == 0) return;
+		ArenaBuf tangents{stream, block_bytes * n_nested};
+		for (size_t i = 0; i < n_nested; ++i) {
+			Encoding& e = *m_nested[i];
+			e.tangent(stream, ctx.nested[i], n, slice(x, i), slice(v, i), (char*)tangents.data() + i * block_bytes, (const char*)params + p_off * elem);
+			p_off += e.n_params();
+		}
+		if (m_reduction == Reduction::Sum) return composite_reduce_forward(stream, m_fp32, false, n_elems, n_nested, tangents.data(), t);
+		CHECK_THROW(ctx.to_reduce);
+		composite_reduce_backward_backward(stream, m_fp32, n_elems, n_nested, ctx.to_reduce.data(), tangents.data(), nullptr, t, nullptr);
+	}
 	Json hyperparams() const override {
 		Json j = Json::object();
 		j["otype"] = "Composite";
@@ -1832,6 +1888,37 @@ public:
 		}
 	}
 
+	// ---- input_jvp: the network's part of J v for n_tangents directions.  tangents: n_tangents buffers one behind the other, each
+	// [n][in_width] in the network's precision (a fused plan: or tangents_f32, see mlp_input_jvp); jvp [n][jvp_tangents][padded output
+	// width], of which this call writes tangents t0 .. t0 + n_tangents - 1.  The fused kernel (mlp_input_jvp_plan), or layer by layer from
+	// the row-major input exactly as second_order_begin / _finish run their forward and tangent passes -- mlp_layer_forward once,
+	// mlp_layer_tangent per tangent with g = r_out = nullptr -- for any otype: a FullyFusedMLP has tangents though no second-order pass.
+	// io.out_half (optional): the output, bit for bit inference()'s -- the fused kernel's forward chain, the layer-by-layer chain of a
+	// layerwise network, or for a fused-shape network on the two passes its own inference().
+	MlpInputJvpPlan input_jvp_plan(uint32_t n, uint32_t n_tangents) const { return mlp_input_jvp_plan(m_desc, m_layerwise, n, n_tangents); }
+	void input_jvp(hipStream_t stream, const MlpInputJvpPlan& plan, uint32_t n, const MlpIo& io, const void* tangents, MatView tangents_f32, uint32_t n_tangents, const void* params,
+	               void* jvp, uint32_t jvp_tangents, uint32_t t0) const {
+		CHECK_THROW(n_tangents > 0 && t0 + n_tangents <= jvp_tangents && jvp != nullptr);
+		const uint32_t pw = m_padded_output_width;
+		if (plan.fused) {
+			ArenaBuf image = prepare(stream, params, false);
+			return mlp_input_jvp(stream, m_desc, plan, image.data(), n, io, tangents, tangents_f32, n_tangents, at(jvp, (size_t)t0 * pw), jvp_tangents * pw);
+		}
+		CHECK_THROW(io.x_half != nullptr && tangents != nullptr && !io.x_plane_features && !io.x_f32.data && !io.x_oneblob_bins && !tangents_f32.data);
+		SecondOrderPass pass = second_order_forward(stream, n, io.x_half, params);
+		if (io.out_half) {
+			if (m_layerwise) HIP_CHECK_THROW(hipMemcpyAsync(io.out_half, at((const void*)pass.h.data(), pass.slot * (m_desc.n_layers - 1)), (size_t)n * pw * element_size(), hipMemcpyDeviceToDevice, stream));
+			else inference(stream, n, io.x_half, io.out_half, params);
+		}
+		ArenaBuf one;
+		if (jvp_tangents > 1) one = ArenaBuf{stream, (size_t)n * pw * element_size()};
+		for (uint32_t t = 0; t < n_tangents; ++t) {
+			void* u_K = jvp_tangents > 1 ? one.data() : jvp;
+			second_order_finish(stream, pass, n, at(tangents, (size_t)t * n * m_input_width), u_K, nullptr, params, nullptr, GradientMode::Ignore);
+			if (jvp_tangents > 1) copy_columns(stream, element_size(), n, u_K, pw, 0, jvp, jvp_tangents * pw, (t0 + t) * pw, pw);
+		}
+	}
+
 	// ---- Second-order input gradients of a CutlassMLP: the gradients of S = <v, dL/dinput> for a given v = dL2/d(dL/dinput).
 	// With h_0 = input, z_k = W_k h_{k-1}, h_k = a_k(z_k), g_K = dL/dy, d_k = g_k a_k'(z_k), g_{k-1} = W_k^T d_k (dL/dinput = g_0):
 	//   tangent    u_0 = v, z'_k = W_k u_{k-1}, u_k = a_k'(z_k) z'_k                  dS/d(dL/dy) = u_K
@@ -1858,24 +1945,11 @@ public:
 	// need_d: second_order_finish() will be asked for parameter gradients or for dS_dinput (else only the forward pass is run again)
 	SecondOrderPass second_order_begin(hipStream_t stream, uint32_t n, const void* input, const void* dL_doutput, const void* params, bool need_d) const {
 		CHECK_THROW(!m_fully_fused);
-		SecondOrderPass s;
-		const uint32_t K = m_desc.n_layers;
-		s.slot = (size_t)n * std::max(m_width, m_padded_output_width);
-		s.input = input;
+		SecondOrderPass s = second_order_forward(stream, n, input, params);
 		s.dL_doutput = dL_doutput;
+		const uint32_t K = m_desc.n_layers;
 		const bool curved = any_curvature();
 		const void* p = params;
-		s.h = ArenaBuf{stream, K * s.slot * element_size()};
-		if (curved) s.z = ArenaBuf{stream, K * s.slot * element_size()};
-		const void* in = input;
-		uint32_t ldi = m_input_width;
-		for (uint32_t l = 0; l < K; ++l) {
-			const MlpLayer& L = m_desc.layers[l];
-			void* out = at(s.h.data(), s.slot * l);
-			mlp_layer_forward(stream, precision(), n, in, ldi, at(p, L.w_off), L.rows, L.cols, layer_act(l), out, layer_ld(l), has_curvature(layer_act(l)) ? at(s.z.data(), s.slot * l) : nullptr);
-			in = out;
-			ldi = m_width;
-		}
 		if (!need_d) return s;
 		s.have_d = true;
 		s.d = ArenaBuf{stream, K * s.slot * element_size()};
@@ -1890,6 +1964,28 @@ public:
 			const uint32_t act = layer_act(l - 1);
 			mlp_layer_backward_keep(stream, precision(), n, d_of(s, l), layer_ld(l), at(s.wt.data(), L.w_off), L.rows, L.cols, act, aux_of(s, l - 1),
 			                    has_curvature(act) ? at(s.g.data(), s.slot * (l - 1)) : nullptr, at(s.d.data(), s.slot * (l - 1)), m_width);
+		}
+		return s;
+	}
+	// the forward half of second_order_begin(): h_k (and z_k where a' needs it), layer by layer from the row-major input.  For any otype:
+	// input_jvp() runs it for a FullyFusedMLP too, which has tangents though no second-order pass.
+	SecondOrderPass second_order_forward(hipStream_t stream, uint32_t n, const void* input, const void* params) const {
+		SecondOrderPass s;
+		const uint32_t K = m_desc.n_layers;
+		s.slot = (size_t)n * std::max(m_width, m_padded_output_width);
+		s.input = input;
+		const bool curved = any_curvature();
+		const void* p = params;
+		s.h = ArenaBuf{stream, K * s.slot * element_size()};
+		if (curved) s.z = ArenaBuf{stream, K * s.slot * element_size()};
+		const void* in = input;
+		uint32_t ldi = m_input_width;
+		for (uint32_t l = 0; l < K; ++l) {
+			const MlpLayer& L = m_desc.layers[l];
+			void* out = at(s.h.data(), s.slot * l);
+			mlp_layer_forward(stream, precision(), n, in, ldi, at(p, L.w_off), L.rows, L.cols, layer_act(l), out, layer_ld(l), has_curvature(layer_act(l)) ? at(s.z.data(), s.slot * l) : nullptr);
+			in = out;
+			ldi = m_width;
 		}
 		return s;
 	}
@@ -2145,6 +2241,24 @@ public:
 		input_gradient_rescale(stream, n, n_dims * input_width(), 1.0f / backprop_scale, MatViewMut{jacobian, n_dims * input_width(), 1u});
 	}
 	const char* last_input_jacobian_route() const { return m_last_input_jacobian_route.c_str(); } // "none" before the first call
+	// Forward mode: jvp [n][n_tangents][padded_output_width] in the module's precision, jvp[:, t, :] = J(x) tangents[:, t, :] for tangents
+	// [n][n_tangents][input_width] floats, row-major -- every output column's derivative along n_tangents input directions, at inference:
+	// no parameter gradient is touched and no context is left.  output (optional) is bit for bit inference()'s.  On the "two-pass" route
+	// jvp[:, t, :] is bit for bit the dL_ddLdoutput of forward(prepare_input_gradients) + backward_backward_input(dL_ddLdinput =
+	// tangents[:, t, :]) wherever that pass exists.  No backprop_scale: the map is linear in v, a caller who fears half overflow scales v.
+	// Everything is checked before anything is allocated or launched; a refused call leaves the route strings alone.
+	void input_jvp(hipStream_t stream, uint32_t n, uint32_t n_tangents, MatView input, const float* tangents, void* jvp, void* output, const void* params) {
+		if (!tangents) throw std::runtime_error{"input_jvp: tangents must not be NULL"};
+		if (!jvp) throw std::runtime_error{"input_jvp: jvp must not be NULL"};
+		if (n_tangents == 0) throw std::runtime_error{"input_jvp: n_tangents = 0 must be at least 1"};
+		check_batch(n);
+		if (!has_tangent()) throw std::runtime_error{"input_jvp: not implemented for " + name()};
+		CHECK_THROW(n == 0 || input.data != nullptr);
+		if (n == 0) return;
+		m_last_input_jvp_route = input_jvp_impl(stream, n, n_tangents, input, tangents, jvp, output, params);
+	}
+	const char* last_input_jvp_route() const { return m_last_input_jvp_route.c_str(); } // "none" before the first call
+	virtual bool has_tangent() const { return false; } // false: PPNG1 / PPNG2 (or a Composite holding one) is part of the module
 	virtual Json hyperparams() const = 0;
 	std::string name() const { return hyperparams().value("otype", "<Unknown>"); } // object.h:51-53
 protected:
@@ -2186,9 +2300,36 @@ protected:
 	}
 	// rows [:, k, :] of the [n][n_dims][input_width] result as a view of [n][input_width]
 	MatViewMut jacobian_slice(float* jacobian, uint32_t k, uint32_t n_dims) const { return MatViewMut{jacobian + (size_t)k * input_width(), n_dims * input_width(), 1u}; }
+	// writes jvp and returns the route's name.  The generic route, for every module with a tangent: ONE forward(prepare_input_gradients),
+	// then the module's tangent per direction on that context -- its second-order pass asked for dL_ddLdoutput alone -- into a row-major
+	// [n][padded_output_width] buffer that is copied into its columns of the result (one direction: written in place).
+	virtual std::string input_jvp_impl(hipStream_t stream, uint32_t n, uint32_t n_tangents, MatView input, const float* tangents, void* jvp, void* output, const void* params) {
+		input_jvp_two_pass(stream, n, n_tangents, input, tangents, jvp, output, params);
+		return "two-pass";
+	}
+	// t [n][padded_output_width] = J v on the context of a forward(prepare_input_gradients); v: a view of [n][input_width] floats
+	virtual void tangent(hipStream_t stream, const ModelContext& ctx, uint32_t n, MatView input, MatView v, void* t, const void* params) {
+		throw std::runtime_error{"input_jvp: not implemented for " + name()};
+	}
+	void input_jvp_two_pass(hipStream_t stream, uint32_t n, uint32_t n_tangents, MatView input, const float* tangents, void* jvp, void* output, const void* params) {
+		const uint32_t pw = padded_output_width();
+		const size_t elem = precision() == Precision::Fp32 ? 4 : 2, bytes = (size_t)n * pw * elem;
+		ArenaBuf out_tmp, one;
+		if (!output) out_tmp = ArenaBuf{stream, bytes};
+		if (n_tangents > 1) one = ArenaBuf{stream, bytes};
+		const std::unique_ptr<ModelContext> ctx = forward(stream, n, input, output ? output : out_tmp.data(), params, true);
+		for (uint32_t t = 0; t < n_tangents; ++t) {
+			void* dst = n_tangents > 1 ? one.data() : jvp;
+			tangent(stream, *ctx, n, input, tangent_slice(tangents, t, n_tangents), dst, params);
+			if (n_tangents > 1) copy_columns(stream, elem, n, dst, pw, 0, jvp, n_tangents * pw, t * pw, pw);
+		}
+	}
+	// rows [:, t, :] of the [n][n_tangents][input_width] tangents as a view of [n][input_width]
+	MatView tangent_slice(const float* tangents, uint32_t t, uint32_t n_tangents) const { return MatView{tangents + (size_t)t * input_width(), n_tangents * input_width(), 1u}; }
 private:
 	std::string m_last_input_gradient_route = "none";
 	std::string m_last_input_jacobian_route = "none";
+	std::string m_last_input_jvp_route = "none";
 public:
 
 	static void check_batch(uint32_t n) { // object.h:130,150,197,246
@@ -2507,6 +2648,50 @@ public:
 				MatViewMut slice = jacobian_slice(jacobian, k0 + k, n_dims);
 				m_encoding->backward(stream, encoding_ctx, n, input, (const char*)dL_dnetwork_input.data() + k * buf_bytes, &slice, encoding_params(params), nullptr, GradientMode::Ignore, route);
 			}
+		}
+		return plan.name;
+	}
+
+	// input_jvp for this model, mirroring input_jacobian_impl: the encoding's forward pass with dy_dx runs ONCE, the encoding's tangent
+	// (Encoding::tangent: its second-order pass asked for dL_ddLdy alone, or OneBlob's kernel) runs per direction into buffers one behind
+	// the other, and the network carries them to the output -- the fused kernel, or the layer-by-layer forward and tangent passes
+	// (Network::input_jvp).  A fused plan behind an Identity encoding reads input and tangents through the fused Identity load and needs no
+	// buffer.  The tangent buffers are temporaries: groups of as many directions as fit INPUT_JACOBIAN_TMP_BYTES at a time; a further group
+	// repeats the network's forward chain, never the encoding pass.  (A grid tangent kernel that reads dy_dx once for all directions
+	// is left for later: DESIGN.md "input_jvp".)
+	bool has_tangent() const override { return m_encoding->has_tangent(); }
+	std::string input_jvp_impl(hipStream_t stream, uint32_t n, uint32_t n_tangents, MatView input, const float* tangents, void* jvp, void* output, const void* params) override {
+		MlpInputJvpPlan plan = m_network->input_jvp_plan(n, n_tangents);
+		if (m_encoding->as_oneblob()) plan = MlpInputJvpPlan{};
+		const uint32_t enc_w = m_encoding->padded_output_width();
+		MlpIo io{};
+		io.out_half = output;
+		ArenaBuf network_input, encoded_tangents;
+		EncodingContext encoding_ctx;
+		float scale = 1, offset = 0;
+		const bool identity = plan.fused && m_encoding->as_identity(scale, offset);
+		if (identity) {
+			io.x_f32 = input;
+			io.x_f32_dims = m_encoding->input_width();
+			io.x_scale = scale;
+			io.x_offset = offset;
+		} else {
+			network_input = ArenaBuf{stream, (size_t)n * enc_w * elem()};
+			encoding_ctx = m_encoding->forward(stream, n, input, encoding_params(params), network_input.data(), true, false);
+			io.x_half = network_input.data();
+		}
+		const size_t buf_bytes = (size_t)n * enc_w * elem();
+		const uint32_t group = identity ? n_tangents : (uint32_t)std::min<size_t>(n_tangents, std::max<size_t>(INPUT_JACOBIAN_TMP_BYTES / std::max<size_t>(buf_bytes, 1), 1));
+		if (!identity) encoded_tangents = ArenaBuf{stream, buf_bytes * group};
+		for (uint32_t t0 = 0; t0 < n_tangents; t0 += group) {
+			const uint32_t n_group = std::min(group, n_tangents - t0);
+			MatView tangents_f32{};
+			if (identity) tangents_f32 = MatView{tangents + (size_t)t0 * input_width(), n_tangents * input_width(), 1u};
+			for (uint32_t t = 0; t < n_group && !identity; ++t) {
+				m_encoding->tangent(stream, encoding_ctx, n, input, tangent_slice(tangents, t0 + t, n_tangents), (char*)encoded_tangents.data() + t * buf_bytes, encoding_params(params));
+			}
+			m_network->input_jvp(stream, plan, n, io, encoded_tangents.data(), tangents_f32, n_group, params, jvp, n_tangents, t0);
+			io.out_half = nullptr; // stored with the first group
 		}
 		return plan.name;
 	}
@@ -2844,7 +3029,13 @@ public:
 		const Ctx& ctx = dynamic_cast<const Ctx&>(mctx);
 		m_encoding->backward_backward_input(stream, ctx.encoding_ctx, n, input, dL_ddLdinput, dL_doutput, dL_ddLdoutput, dL_dinput, params, gradients, mode);
 	}
+	bool has_tangent() const override { return m_encoding->has_tangent(); }
 	Json hyperparams() const override { return m_encoding->hyperparams(); }
+protected:
+	void tangent(hipStream_t stream, const ModelContext& mctx, uint32_t n, MatView input, MatView v, void* t, const void* params) override {
+		const Ctx& ctx = dynamic_cast<const Ctx&>(mctx);
+		m_encoding->tangent(stream, ctx.encoding_ctx, n, input, v, t, params);
+	}
 private:
 	Precision m_precision;
 	std::unique_ptr<Encoding> m_encoding;
@@ -4047,6 +4238,9 @@ public:
 	}
 	void input_jacobian(hipStream_t stream, uint32_t n, const uint32_t* dims, uint32_t n_dims, MatView input, float* jacobian, float backprop_scale) {
 		m_model->input_jacobian(stream, n, dims, n_dims, input, jacobian, nullptr, params_inference(), backprop_scale);
+	}
+	void input_jvp(hipStream_t stream, uint32_t n, uint32_t n_tangents, MatView input, const float* tangents, void* jvp) {
+		m_model->input_jvp(stream, n, n_tangents, input, tangents, jvp, nullptr, params_inference());
 	}
 
 	// object.h:133-145, inference_mixed_precision: the network's own output, half [n][padded_output_width] (what inference() casts); floats from an fp32 trainer

@@ -465,6 +465,9 @@ void grid_backward_backward_input(hipStream_t stream, const GridMeta& meta, cons
 // OneBlob / Identity (AoS output, T = half or float)
 void oneblob_forward(hipStream_t stream, bool fp32, uint32_t n, uint32_t n_dims, uint32_t n_bins, MatView x, void* out, uint32_t out_stride);
 void oneblob_backward_input(hipStream_t stream, bool fp32, uint32_t n, uint32_t n_dims, uint32_t n_bins, MatView x, const void* dL_dy, uint32_t dy_stride, MatViewMut dL_dx);
+// the tangent J v (k_encodings.hip k_oneblob_tangent): t[i][d * n_bins + b] = (T)(v[i][d] * k'), k' the fp32 derivative of bin b that
+// oneblob_backward_input multiplies dL_dy by -- one rounding; exactly zero in the padding columns
+void oneblob_tangent(hipStream_t stream, bool fp32, uint32_t n, uint32_t n_dims, uint32_t n_bins, MatView x, MatView v, void* t, uint32_t t_stride);
 void identity_forward(hipStream_t stream, bool fp32, uint32_t n, uint32_t n_dims, float scale, float offset, MatView x, void* out, uint32_t out_stride);
 void identity_backward_input(hipStream_t stream, bool fp32, uint32_t n, uint32_t n_dims, float scale, const void* dL_dy, uint32_t dy_stride, MatViewMut dL_dx);
 // second order: dL_ddLdy[i][j] = (T)(dL_ddLdx[i][j] * scale) for j < n_dims, 0 for the padding
@@ -573,6 +576,34 @@ MlpInputGradPlan mlp_input_jacobian_plan(const MlpDesc& d, bool layerwise, uint3
 // level planes (dx_plane_features); the output (io.out_half, optional) is stored once
 void mlp_input_jacobian(hipStream_t stream, const MlpDesc& d, const MlpInputGradPlan& plan, const void* image, uint32_t n, const MlpIo& io, const uint32_t* dims, uint32_t n_dims,
                         float backprop_scale, void* dL_dx, uint32_t dx_plane_features);
+// ---- input_jvp: J(x) v for every output column along T input directions, forward mode (k_mlp_input_jvp.hip).  The network's part: from its
+// input rows and T tangent buffers u_0 (one behind the other, each half [n][in_width]) to T buffers u_K (each half [n][out_width]), with
+// u_k = a_k' (.) half(W_k u_{k-1}): the accumulator starts at +0, the k-steps ascend, one rounding to half per layer, a' in fp32 from the half
+// pre-activation (the sign of the half output for ReLU / LeakyReLU).  One wave owns 16 NB samples; per layer every weight fragment is read
+// once and feeds the forward product and the products of TT tangent chains; nothing but the live operands is kept across layers.  More
+// tangents than TT are further launches, each with a forward chain of its own; the output is stored by the first.
+constexpr uint32_t MLP_INPUT_JVP_MAX_TT = 3; // tangent chains per launch: TT = 1 and TT = 3 are instantiated
+struct MlpInputJvpPlan {
+	bool fused = false;          // false: the layer-by-layer passes (name "two-pass")
+	char name[48] = "two-pass";  // tcnn_module_last_input_jvp_route: "two-pass" | "k_mlp_input_jvp<W,NB,NH,TT>/relu|act"
+	uint32_t nb = 0, grid = 0;   // fused: column blocks of 16 samples per wave and trip, workgroups of 4 waves
+	uint32_t tt = 0;             // fused: tangent chains per launch
+	bool relu = false;           // fused: the compiled ReLU form, else the activation chosen at run time
+};
+// Pure host code, as the two plans above.  Layer-by-layer networks (fp32, Sine, zero hidden layers, widths and depths without an
+// instantiation, TCNN_AMD_MLP_LAYERWISE=1) are always "two-pass", and so is n that is no multiple of 16 NB.  A fused class gets the kernel
+// only where tools/bench_input_jvp.py measured it faster than this call's own two-pass route by more than 3 %, the spread between boxes:
+// measured in every class -- ReLU | run-time form x 16 / 32 / 64 / 128 wide x 1 .. 4 hidden layers x TT = 1 | 3, at 2^18 and 2^14 rows --
+// the two passes take 1.31 to 9.85 times the kernel's time, so every instantiated class is fused (DESIGN.md "input_jvp / The plan rule";
+// profiles/input_jvp_bench.txt, section 2).  TT = 1 for one tangent, else 3; NB = nb_of's, halved for TT = 3 at 64 and 128 wide.
+MlpInputJvpPlan mlp_input_jvp_plan(const MlpDesc& d, bool layerwise, uint32_t n, uint32_t n_tangents);
+// io: the network's input as mlp_input_gradient takes it (rows, level planes or the fused Identity input) and, optionally, out_half.
+// tangents: n_tangents buffers of half [n][in_width] rows one behind the other, or -- tangents_f32.data != nullptr -- the caller's float
+// [n][n_tangents][x_f32_dims] with the Identity encoding's tangent applied in the load: (half)(v * io.x_scale), ZERO in the padding.
+// jvp: half, tangent t of sample s at jvp[s * jvp_stride + t * out_width] (jvp_stride = out_width times the tangents of the whole call, of
+// which this may be a group).  plan.fused must hold for (d, n).
+void mlp_input_jvp(hipStream_t stream, const MlpDesc& d, const MlpInputJvpPlan& plan, const void* image, uint32_t n, const MlpIo& io, const void* tangents, MatView tangents_f32,
+                   uint32_t n_tangents, void* jvp, uint32_t jvp_stride);
 // the two ends of every input_gradient route (object.h:352-365): d_doutput [n][width] T = (T)backprop_scale in column dim, +0 elsewhere;
 // d_dinput[i][j] *= mult for j < dims (mult = 1.0f / backprop_scale, formed once by the caller)
 void input_gradient_one_hot(hipStream_t stream, Precision precision, uint32_t n, uint32_t width, uint32_t dim, float backprop_scale, void* d_doutput);

@@ -81,6 +81,9 @@ _SIGNATURES = {
     "tcnn_module_input_jacobian": (_int, [_vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _f32]),
     "tcnn_module_last_input_jacobian_route": (_cp, [_vp]),
     "tcnn_trainer_input_jacobian": (_int, [_vp, _vp, _u32, _vp, _u32, _vp, _vp, _f32]),
+    "tcnn_module_input_jvp": (_int, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "tcnn_module_last_input_jvp_route": (_cp, [_vp]),
+    "tcnn_trainer_input_jvp": (_int, [_vp, _vp, _u32, _u32, _vp, _vp, _vp]),
     "tcnn_context_destroy": (None, [_vp]),
     "tcnn_module_n_input_dims": (_u32, [_vp]),
     "tcnn_module_n_output_dims": (_u32, [_vp]),

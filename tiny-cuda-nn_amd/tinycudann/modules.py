@@ -177,6 +177,23 @@ class NativeModule:
         """ "none" before the first input_jacobian call, then "two-pass" or the fused MLP kernel's name (tcnn_amd.h: tcnn_module_last_input_jacobian_route)"""
         return _C.lib.tcnn_module_last_input_jacobian_route(self._h).decode()
 
+    def input_jvp(self, input, params, tangents, want_output=False):
+        """J(x) tangents[:, t, :] for every t, [n, T, n_output_dims] in the output precision, from float32 tangents [n, T, n_input_dims] (and
+        the forward pass's padded output if asked for): tcnn_amd.h tcnn_module_input_jvp.  n must be a multiple of the batch granularity."""
+        self._check_inputs(input, params)
+        n, n_tangents = input.shape[0], tangents.shape[1]
+        assert tangents.dtype == torch.float32 and tangents.is_contiguous() and tangents.device == input.device and tuple(tangents.shape) == (n, n_tangents, self.n_input_dims())
+        with torch.cuda.device(input.device):
+            dtype = _torch_precision(self.output_precision())
+            jvp = torch.empty((n, n_tangents, self.n_output_dims()), dtype=dtype, device=input.device)
+            output = torch.empty((n, self.n_output_dims()), dtype=dtype, device=input.device) if want_output else None
+            _C.check(_C.lib.tcnn_module_input_jvp(self._h, _stream(), n, n_tangents, _ptr(input), _ptr(tangents), _ptr(jvp), _ptr(output), _ptr(params)))
+        return jvp, output
+
+    def last_input_jvp_route(self):
+        """ "none" before the first input_jvp call, then "two-pass" or the fused MLP kernel's name (tcnn_amd.h: tcnn_module_last_input_jvp_route)"""
+        return _C.lib.tcnn_module_last_input_jvp_route(self._h).decode()
+
     def bwd_bwd_input(self, ctx, input, params, dL_ddLdinput, dL_doutput):  # bindings.cpp:172-245
         """from dL_ddLdinput to (dL_ddLdoutput, dL_dparams, dL_dinput); each is None unless its tensor requires grad."""
         if ctx is None or not ctx._h:
@@ -450,6 +467,37 @@ class Module(torch.nn.Module):
                 jacobian, output = native.input_jacobian(rows, working, range(self.n_output_dims) if dims is None else dims, scale, return_output)
             jacobian = jacobian[:n]
             return (jacobian, output[:n, : self.n_output_dims]) if return_output else jacobian
+
+    def input_jvp(self, x, tangents, return_output=False):
+        """Forward mode: every output's derivative along given input directions, for any n.  tangents [n, T, n_input_dims] gives
+        [n, T, n_output_dims] in the module's output precision with [:, t, :] = J(x) tangents[:, t, :]; a 2-D tangents [n, n_input_dims]
+        means T = 1 and gives [n, n_output_dims].  Outside autograd (not differentiable) and under the max_level setting in force, as
+        input_gradient.  There is no backprop_scale: the map is linear in the tangent, so scale the tangent if half precision might
+        overflow.  return_output=True: (jvp, output[:n, :n_output_dims]) of the same pass."""
+        with torch.no_grad():
+            x = x.detach()
+            if not x.is_cuda:
+                warnings.warn("input must be a CUDA tensor, but isn't. This indicates suboptimal performance.")
+                x = x.cuda()
+            n = x.shape[0]
+            v = tangents.detach().to(device=x.device, dtype=torch.float)
+            flat = v.dim() == 2
+            if flat:
+                v = v[:, None, :]
+            if v.dim() != 3 or v.shape[0] != n or v.shape[1] < 1 or v.shape[2] != self.n_input_dims:
+                raise ValueError("input_jvp: tangents must be [n, T, n_input_dims] or [n, n_input_dims] with T >= 1, got %s" % (tuple(tangents.shape),))
+            granularity = _C.batch_size_granularity()
+            rows = _pad_rows(x.to(torch.float), granularity).contiguous()
+            v = _pad_rows(v.reshape(n, -1), granularity).reshape(rows.shape[0], -1, self.n_input_dims).contiguous()
+            working = self.params.detach().to(self.dtype).contiguous()
+            native = self.native_tcnn_module
+            call = _Call(native, self.loss_scale, False, False, self._max_level_of_call(n, rows))
+            with call.setting():
+                jvp, output = native.input_jvp(rows, working, v, return_output)
+            jvp = jvp[:n, :, : self.n_output_dims]
+            if flat:
+                jvp = jvp[:, 0]
+            return (jvp, output[:n, : self.n_output_dims]) if return_output else jvp
 
     # --- max_level of the grid encoding(s) (the reference's GridEncoding::set_max_level / set_max_level_gpu, grid_interface.h:101-123).
     # Every forward call records the setting in force; its backward and double-backward passes run under that setting.

@@ -218,6 +218,19 @@ class Trainer:
         _C.check(_C.lib.tcnn_trainer_input_jacobian(self._h, _stream(stream), n, (C.c_uint32 * len(dims))(*dims), len(dims), _ptr(input), _ptr(jacobian), float(scale)))
         return jacobian
 
+    def input_jvp(self, input, tangents, jvp=None, stream=None):
+        """J(x) tangents[:, t, :] for every t on the trainer's inference parameters: [n, T, padded output width] in the trainer's precision,
+        from float32 tangents [n, T, n_input_dims].  No backprop_scale: the map is linear in the tangent."""
+        n, n_tangents = input.shape[0], tangents.shape[1]
+        shape = (n, n_tangents, self.padded_output_width)
+        if jvp is None:
+            jvp = torch.empty(shape, dtype=self.dtype, device=input.device)
+        assert input.dtype == torch.float32 and input.is_contiguous() and tangents.dtype == torch.float32 and tangents.is_contiguous()
+        assert tuple(tangents.shape) == (n, n_tangents, input.shape[1]) and jvp.dtype == self.dtype and jvp.is_contiguous() and tuple(jvp.shape) == shape
+        self._check_max_level_rows(n)
+        _C.check(_C.lib.tcnn_trainer_input_jvp(self._h, _stream(stream), n, n_tangents, _ptr(input), _ptr(tangents), _ptr(jvp)))
+        return jvp
+
     # -- object.h:133-145: network->inference_mixed_precision(stream, input, output): half [n][padded_output_width]
     def inference_half(self, input, output=None, input_layout=LAYOUT_AOS, stream=None):
         if self.dtype != torch.half:
