@@ -68,9 +68,17 @@ public:
 	json hyperparams() const override { return json::parse(tcnn_module_hyperparams(m)); }
 	std::string name() const override { return tcnn_module_name(m); }
 
+	tcnn_module_t handle() const { return m; }
+
 private:
 	tcnn_module_t m;
 };
+
+tcnn_module_t module_of(Module& module, const char* who) {
+	auto* a = dynamic_cast<AmdModule*>(&module);
+	if (!a) throw std::runtime_error{std::string{who} + ": not a module of this library"};
+	return a->handle();
+}
 
 // set_log_callback: the C ABI takes a function pointer + user pointer; the std::function lives here
 std::function<void(LogSeverity, const std::string&)>& log_callback() {
@@ -81,6 +89,25 @@ void log_trampoline(int severity, const char* message, void*) {
 	if (log_callback()) log_callback()((LogSeverity)severity, std::string{message ? message : ""});
 }
 } // namespace
+
+// Training through input_jvp (tcnn_amd.h: tcnn_module_input_jvp_forward / _backward).  The reference's Module has no such members, so these
+// are functions beside it; a client declares them as they stand here.  input_jvp_fwd: jvp [n_elements][n_tangents][n_output_dims()] and
+// output (may be null) as input_jvp / inference give them, and the context for input_jvp_bwd, which writes what is not null of dL_dparams
+// (overwritten), dL_dinput [n_elements][n_input_dims()] and dL_dtangents [n_elements][n_tangents][n_input_dims()].
+Context input_jvp_fwd(Module& module, cudaStream_t stream, uint32_t n_elements, uint32_t n_tangents, const float* input, const float* tangents, void* jvp, void* output,
+                      const void* params) {
+	std::unique_ptr<AmdContext> c{new AmdContext};
+	ok(tcnn_module_input_jvp_forward(module_of(module, "input_jvp_fwd"), (tcnn_stream_t)stream, n_elements, n_tangents, input, tangents, jvp, output, params, &c->h));
+	Context result;
+	result.ctx = std::move(c);
+	return result;
+}
+
+void input_jvp_bwd(Module& module, cudaStream_t stream, const Context& ctx, uint32_t n_elements, uint32_t n_tangents, const float* input, const float* tangents, const void* dL_djvp,
+                   const void* dL_doutput, const void* params, void* dL_dparams, float* dL_dinput, float* dL_dtangents) {
+	ok(tcnn_module_input_jvp_backward(module_of(module, "input_jvp_bwd"), (tcnn_stream_t)stream, handle_of(ctx), n_elements, n_tangents, input, tangents, dL_djvp, dL_doutput, params,
+	                                  dL_dparams, dL_dinput, dL_dtangents, dL_dparams ? TCNN_GRADIENT_OVERWRITE : TCNN_GRADIENT_IGNORE));
+}
 
 uint32_t batch_size_granularity() { return tcnn_batch_size_granularity(); }
 

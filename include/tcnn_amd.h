@@ -164,6 +164,36 @@ int  tcnn_module_input_jvp(tcnn_module_t m, tcnn_stream_t stream, uint32_t n_ele
 /* The route the module's last input_jvp call took: "none" before the first call, "two-pass", or the fused MLP kernel's name,
  * "k_mlp_input_jvp<W,NB,NH,TT>/relu|act" (TT: tangent chains per launch).  Owned by the module, as tcnn_module_last_input_gradient_route. */
 const char* tcnn_module_last_input_jvp_route(tcnn_module_t m);
+/* Training through input_jvp: the pair below puts J v into a loss.  tcnn_module_input_jvp_forward is tcnn_module_input_jvp -- the same route,
+ * the same bits in jvp and output (output may be NULL), the same refusals -- and returns a context for tcnn_module_input_jvp_backward
+ * (destroy it with tcnn_context_destroy; it holds no device memory: the backward call runs the module's forward pass again from input).
+ * tcnn_module_input_jvp_backward gives the gradients of
+ *     L = sum_t <dL_djvp[:, t, :], J(input) tangents[:, t, :]> + <dL_doutput, f(input)>
+ * for dL_djvp [n_elements][n_tangents][padded output width] and dL_doutput [n_elements][padded output width] (may be NULL) in the module's
+ * output precision, taken as they are: there is no loss scale inside.  Results, each may be NULL and only what is asked for is computed:
+ * dL_dparams [n_params] in the parameters' precision under gradient_mode (TCNN_GRADIENT_*, as tcnn_module_backward_backward_input_mode),
+ * dL_dinput [n_elements][n_input_dims] and dL_dtangents [n_elements][n_tangents][n_input_dims] floats.  First order only.  input, tangents
+ * and params are those of the forward call.  On the route "two-pass" the call is composed of the module's existing passes -- one forward
+ * pass with input gradients prepared; the backward pass of dL_doutput, if there is one; then per tangent the second-order pass (dL_ddLdinput =
+ * tangents[:, t, :], dL_doutput = dL_djvp[:, t, :]) for dL_dparams and dL_dinput and a first-order backward pass for dL_dtangents[:, t, :] -- and
+ * every result is bit for bit what a caller gets who chains tcnn_module_forward / _backward / _backward_backward_input_mode by hand in that
+ * order, accumulating dL_dparams through TCNN_GRADIENT_ACCUMULATE and adding the dL_dinput terms in fp32 (a grid's second-order parameter
+ * gradients: up to the order of its atomic additions).  FullyFusedMLP networks and OneBlob
+ * encodings, whose tcnn_module_backward_backward_input stays refused, are served here.  A grid's max_level state in force applies to both
+ * calls.  Checked before anything is allocated or launched, a refused call leaving the route strings alone: what tcnn_module_input_jvp
+ * checks (NULL tangents or dL_djvp, n_tangents == 0, n_elements off the granularity, a module without a tangent: "input_jvp: not implemented
+ * for <module name>"); a context that is not one of tcnn_module_input_jvp_forward ("Module::bwd: called with invalid context. ..."), or of a call
+ * with another n_elements or n_tangents; dL_dinput behind an encoding whose tangent has no derivative by x here -- OneBlob, or a Composite
+ * holding one: "input_jvp_backward: dL_dinput not implemented for <module name>" (dL_dparams and dL_dtangents work there; dL_dparams is refused
+ * likewise only if such a Composite has parameters of its own). */
+int  tcnn_module_input_jvp_forward(tcnn_module_t m, tcnn_stream_t stream, uint32_t n_elements, uint32_t n_tangents, const float* input, const float* tangents, void* jvp,
+                                   void* output, const void* params, tcnn_context_t* ctx_out);
+int  tcnn_module_input_jvp_backward(tcnn_module_t m, tcnn_stream_t stream, tcnn_context_t ctx, uint32_t n_elements, uint32_t n_tangents, const float* input,
+                                    const float* tangents, const void* dL_djvp, const void* dL_doutput, const void* params, void* dL_dparams, float* dL_dinput,
+                                    float* dL_dtangents, int gradient_mode);
+/* The route the module's last input_jvp_backward call took: "none" before the first call, "two-pass" (the composed route; a fused kernel's
+ * name, "k_mlp_input_jvp_bwd<W,NB,NH,TT>/relu|act", is reserved for one that is measured faster).  Owned by the module. */
+const char* tcnn_module_last_input_jvp_backward_route(tcnn_module_t m);
 void tcnn_context_destroy(tcnn_context_t ctx);
 
 uint32_t    tcnn_module_n_input_dims(tcnn_module_t m);     /* cpp_api.cu:129 */
@@ -227,6 +257,12 @@ int  tcnn_trainer_input_jacobian(tcnn_trainer_t t, tcnn_stream_t stream, uint32_
 /* tcnn_module_input_jvp on the trainer's inference parameters: tangents [n_elements][n_tangents][n_input_dims] floats, jvp [n_elements][n_tangents]
  * [padded output width] in the trainer's precision */
 int  tcnn_trainer_input_jvp(tcnn_trainer_t t, tcnn_stream_t stream, uint32_t n_elements, uint32_t n_tangents, const float* input, const float* tangents, void* jvp);
+/* tcnn_module_input_jvp_forward / _backward on the trainer's TRAINING parameters; the parameter gradients go into the trainer's gradient buffer
+ * under gradient_mode, where tcnn_trainer_optimizer_step reads them (cotangents scaled by a loss scale give gradients scaled by it) */
+int  tcnn_trainer_input_jvp_forward(tcnn_trainer_t t, tcnn_stream_t stream, uint32_t n_elements, uint32_t n_tangents, const float* input, const float* tangents, void* jvp,
+                                    void* output, tcnn_context_t* ctx_out);
+int  tcnn_trainer_input_jvp_backward(tcnn_trainer_t t, tcnn_stream_t stream, tcnn_context_t ctx, uint32_t n_elements, uint32_t n_tangents, const float* input,
+                                     const float* tangents, const void* dL_djvp, const void* dL_doutput, float* dL_dinput, float* dL_dtangents, int gradient_mode);
 
 /* network->inference_mixed_precision(stream, input, output) (object.h:133-145): the network's own output, half
  * [n_elements][padded_output_width] -- what inference() casts to float; half the bytes for a caller that gathers row shards.

@@ -93,6 +93,22 @@ public:
 		detail::ok(tcnn_module_input_jvp(m_handle, stream, n_elements, n_tangents, input, tangents, jvp, output, params));
 	}
 	std::string last_input_jvp_route() const { return tcnn_module_last_input_jvp_route(m_handle); } // "none" | "two-pass" | the fused kernel's name
+	// Training through input_jvp: input_jvp_fwd is input_jvp (the same bits in jvp and output) and returns the context input_jvp_bwd takes.
+	// input_jvp_bwd: the gradients of sum_t <dL_djvp[:, t, :], J v_t> + <dL_doutput, f(x)> -- dL_dparams under gradient_mode (TCNN_GRADIENT_*), dL_dinput
+	// [n_elements][n_input_dims()], dL_dtangents [n_elements][n_tangents][n_input_dims()]; dL_doutput and every result may be null.  No loss
+	// scale inside.  See tcnn_module_input_jvp_forward / _backward.
+	Context input_jvp_fwd(stream_t stream, uint32_t n_elements, uint32_t n_tangents, const float* input, const float* tangents, void* jvp, void* output, const void* params) {
+		tcnn_context_t c = nullptr;
+		detail::ok(tcnn_module_input_jvp_forward(m_handle, stream, n_elements, n_tangents, input, tangents, jvp, output, params, &c));
+		return Context{std::shared_ptr<void>{(void*)c, [](void* p) { tcnn_context_destroy((tcnn_context_t)p); }}};
+	}
+	void input_jvp_bwd(stream_t stream, const Context& ctx, uint32_t n_elements, uint32_t n_tangents, const float* input, const float* tangents, const void* dL_djvp, const void* dL_doutput,
+	                   const void* params, void* dL_dparams, float* dL_dinput, float* dL_dtangents, int gradient_mode = TCNN_GRADIENT_OVERWRITE) {
+		if (!ctx.ctx) throw std::runtime_error{"Module::bwd: called with invalid context. fwd likely (mistakenly) ran in inference mode."};
+		detail::ok(tcnn_module_input_jvp_backward(m_handle, stream, (tcnn_context_t)ctx.ctx.get(), n_elements, n_tangents, input, tangents, dL_djvp, dL_doutput, params, dL_dparams, dL_dinput,
+		                                          dL_dtangents, dL_dparams ? gradient_mode : TCNN_GRADIENT_IGNORE));
+	}
+	std::string last_input_jvp_backward_route() const { return tcnn_module_last_input_jvp_backward_route(m_handle); } // "none" | "two-pass"
 
 	uint32_t n_input_dims() const { return tcnn_module_n_input_dims(m_handle); }
 	uint32_t n_output_dims() const { return tcnn_module_n_output_dims(m_handle); } // padded width, cpp_api.cu:130

@@ -322,6 +322,41 @@ public:
 		}
 		detail::check(tcnn_trainer_input_jvp(m_trainer, stream, input.n(), n_tangents, input.data(), tangents.data(), jvp.data()));
 	}
+	// Training through input_jvp, on the bound Trainer's TRAINING parameters (tcnn_amd.h: tcnn_module_input_jvp_forward / _backward).
+	// input_jvp_forward: input_jvp's jvp, the network's output (optional: padded_output_width() x batch) and the context of the backward call.
+	// input_jvp_backward: the gradients of sum_t <dL_djvp_t, J v_t> + <dL_doutput, f(x)> -- the parameter gradients into the Trainer's
+	// gradient buffer under param_gradients_mode (Trainer::optimizer_step reads it), and optionally dL_dinput (n_dims x batch) and
+	// dL_dtangents (shaped as tangents).  No loss scale inside: cotangents scaled by one give gradients scaled by it.  First order only.
+	struct InputJvpContext {
+		tcnn_context_t handle = nullptr;
+		InputJvpContext() = default;
+		InputJvpContext(const InputJvpContext&) = delete;
+		InputJvpContext& operator=(const InputJvpContext&) = delete;
+		~InputJvpContext() { if (handle) tcnn_context_destroy(handle); }
+	};
+	std::unique_ptr<InputJvpContext> input_jvp_forward(stream_t stream, uint32_t n_tangents, const GPUMatrix<float>& input, const GPUMatrix<float>& tangents, GPUMatrix<T>& jvp,
+	                                                   GPUMatrix<T>* output = nullptr) {
+		if (!m_trainer) throw std::runtime_error{"NetworkWithInputEncoding::input_jvp_forward: the network has no parameters yet (construct a Trainer first)"};
+		if (input.m() != m_n_input_dims || tangents.m() != n_tangents * m_n_input_dims || jvp.m() != n_tangents * padded_output_width() || input.n() != tangents.n() || input.n() != jvp.n() ||
+		    (output && (output->m() != padded_output_width() || output->n() != input.n()))) {
+			throw std::runtime_error{"input_jvp_forward: matrix shapes do not match the network"};
+		}
+		std::unique_ptr<InputJvpContext> ctx{new InputJvpContext};
+		detail::check(tcnn_trainer_input_jvp_forward(m_trainer, stream, input.n(), n_tangents, input.data(), tangents.data(), jvp.data(), output ? output->data() : nullptr, &ctx->handle));
+		return ctx;
+	}
+	void input_jvp_backward(stream_t stream, const InputJvpContext& ctx, uint32_t n_tangents, const GPUMatrix<float>& input, const GPUMatrix<float>& tangents, const GPUMatrix<T>& dL_djvp,
+	                        const GPUMatrix<T>* dL_doutput = nullptr, GPUMatrix<float>* dL_dinput = nullptr, GPUMatrix<float>* dL_dtangents = nullptr,
+	                        GradientMode param_gradients_mode = GradientMode::Overwrite) {
+		if (!m_trainer) throw std::runtime_error{"NetworkWithInputEncoding::input_jvp_backward: the network has no parameters yet (construct a Trainer first)"};
+		if (input.m() != m_n_input_dims || tangents.m() != n_tangents * m_n_input_dims || dL_djvp.m() != n_tangents * padded_output_width() || input.n() != tangents.n() ||
+		    input.n() != dL_djvp.n() || (dL_doutput && (dL_doutput->m() != padded_output_width() || dL_doutput->n() != input.n())) ||
+		    (dL_dinput && (dL_dinput->m() != m_n_input_dims || dL_dinput->n() != input.n())) || (dL_dtangents && (dL_dtangents->m() != tangents.m() || dL_dtangents->n() != input.n()))) {
+			throw std::runtime_error{"input_jvp_backward: matrix shapes do not match the network"};
+		}
+		detail::check(tcnn_trainer_input_jvp_backward(m_trainer, stream, ctx.handle, input.n(), n_tangents, input.data(), tangents.data(), dL_djvp.data(), dL_doutput ? dL_doutput->data() : nullptr,
+		                                              dL_dinput ? dL_dinput->data() : nullptr, dL_dtangents ? dL_dtangents->data() : nullptr, (int)param_gradients_mode));
+	}
 
 	uint32_t input_width() const { return m_n_input_dims; }
 	uint32_t output_width() const { return m_n_output_dims; }

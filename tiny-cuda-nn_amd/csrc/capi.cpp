@@ -232,7 +232,9 @@ int tcnn_module_backward(tcnn_module_t m, tcnn_stream_t stream, tcnn_context_t c
                          const float* input, const void* output, const void* params) {
 	return guarded([&] {
 		CHECK_THROW(m && m->model);
-		if (!ctx || !ctx->ctx) throw std::runtime_error{"Module::bwd: called with invalid context. fwd likely (mistakenly) ran in inference mode."};
+		if (!ctx || !ctx->ctx || dynamic_cast<const Model::InputJvpContext*>(ctx->ctx.get())) { // (an input_jvp_forward context holds no activations)
+			throw std::runtime_error{"Module::bwd: called with invalid context. fwd likely (mistakenly) ran in inference mode."};
+		}
 		MatViewMut dx{dL_dinput, m->model->input_width(), 1u};
 		m->model->backward((hipStream_t)stream, *ctx->ctx, n, MatView{input, m->model->input_width(), 1u}, output, dL_doutput, dL_dinput ? &dx : nullptr, params,
 		                   dL_dparams, dL_dparams ? GradientMode::Overwrite : GradientMode::Ignore); // cpp_api.cu:108
@@ -250,7 +252,9 @@ int tcnn_module_backward_backward_input_mode(tcnn_module_t m, tcnn_stream_t stre
 	return guarded([&] { // cpp_api.cu:111-127
 		CHECK_THROW(gradient_mode == TCNN_GRADIENT_IGNORE || ((gradient_mode == TCNN_GRADIENT_OVERWRITE || gradient_mode == TCNN_GRADIENT_ACCUMULATE) && dL_dparams != nullptr));
 		CHECK_THROW(m && m->model);
-		if (!ctx || !ctx->ctx) throw std::runtime_error{"Module::bwd_bwd_input: called with invalid context. fwd likely (mistakenly) ran in inference mode."};
+		if (!ctx || !ctx->ctx || dynamic_cast<const Model::InputJvpContext*>(ctx->ctx.get())) {
+			throw std::runtime_error{"Module::bwd_bwd_input: called with invalid context. fwd likely (mistakenly) ran in inference mode."};
+		}
 		CHECK_THROW(dL_ddLdinput != nullptr && input != nullptr);
 		const uint32_t w = m->model->input_width();
 		MatViewMut dx{dL_dinput, w, 1u};
@@ -305,6 +309,36 @@ const char* tcnn_module_last_input_jvp_route(tcnn_module_t m) {
 		return nullptr;
 	}
 	return m->model->last_input_jvp_route();
+}
+
+int tcnn_module_input_jvp_forward(tcnn_module_t m, tcnn_stream_t stream, uint32_t n, uint32_t n_tangents, const float* input, const float* tangents, void* jvp, void* output,
+                                  const void* params, tcnn_context_t* ctx_out) {
+	return guarded([&] {
+		CHECK_THROW(m && m->model && ctx_out);
+		auto c = std::make_unique<tcnn_context_s>();
+		c->ctx = m->model->input_jvp_forward((hipStream_t)stream, n, n_tangents, MatView{input, m->model->input_width(), 1u}, tangents, jvp, output, params);
+		*ctx_out = c.release();
+	});
+}
+
+int tcnn_module_input_jvp_backward(tcnn_module_t m, tcnn_stream_t stream, tcnn_context_t ctx, uint32_t n, uint32_t n_tangents, const float* input, const float* tangents,
+                                   const void* dL_djvp, const void* dL_doutput, const void* params, void* dL_dparams, float* dL_dinput, float* dL_dtangents, int gradient_mode) {
+	return guarded([&] {
+		CHECK_THROW(gradient_mode == TCNN_GRADIENT_IGNORE || ((gradient_mode == TCNN_GRADIENT_OVERWRITE || gradient_mode == TCNN_GRADIENT_ACCUMULATE) && dL_dparams != nullptr));
+		CHECK_THROW(m && m->model);
+		if (!ctx || !ctx->ctx) throw std::runtime_error{"Module::bwd: called with invalid context. fwd likely (mistakenly) ran in inference mode."};
+		MatViewMut dx{dL_dinput, m->model->input_width(), 1u};
+		m->model->input_jvp_backward((hipStream_t)stream, *ctx->ctx, n, n_tangents, MatView{input, m->model->input_width(), 1u}, tangents, dL_djvp, dL_doutput, params,
+		                             gradient_mode == TCNN_GRADIENT_IGNORE ? nullptr : dL_dparams, dL_dinput ? &dx : nullptr, dL_dtangents, (GradientMode)gradient_mode);
+	});
+}
+
+const char* tcnn_module_last_input_jvp_backward_route(tcnn_module_t m) {
+	if (!m || !m->model) {
+		g_last_error = "tcnn_module_last_input_jvp_backward_route: null module";
+		return nullptr;
+	}
+	return m->model->last_input_jvp_backward_route();
 }
 
 void tcnn_context_destroy(tcnn_context_t ctx) { delete ctx; }
@@ -494,6 +528,31 @@ int tcnn_trainer_input_jvp(tcnn_trainer_t t, tcnn_stream_t stream, uint32_t n, u
 		CHECK_THROW(t && t->trainer);
 		Trainer& tr = *t->trainer;
 		tr.input_jvp((hipStream_t)stream, n, n_tangents, MatView{input, tr.model().input_width(), 1u}, tangents, jvp);
+	});
+}
+
+int tcnn_trainer_input_jvp_forward(tcnn_trainer_t t, tcnn_stream_t stream, uint32_t n, uint32_t n_tangents, const float* input, const float* tangents, void* jvp, void* output,
+                                   tcnn_context_t* ctx_out) {
+	return guarded([&] {
+		CHECK_THROW(t && t->trainer && ctx_out);
+		Trainer& tr = *t->trainer;
+		auto c = std::make_unique<tcnn_context_s>();
+		c->ctx = tr.input_jvp_forward((hipStream_t)stream, n, n_tangents, MatView{input, tr.model().input_width(), 1u}, tangents, jvp, output);
+		*ctx_out = c.release();
+	});
+}
+
+int tcnn_trainer_input_jvp_backward(tcnn_trainer_t t, tcnn_stream_t stream, tcnn_context_t ctx, uint32_t n, uint32_t n_tangents, const float* input, const float* tangents,
+                                    const void* dL_djvp, const void* dL_doutput, float* dL_dinput, float* dL_dtangents, int gradient_mode) {
+	return guarded([&] {
+		CHECK_THROW(gradient_mode == TCNN_GRADIENT_IGNORE || gradient_mode == TCNN_GRADIENT_OVERWRITE || gradient_mode == TCNN_GRADIENT_ACCUMULATE);
+		CHECK_THROW(t && t->trainer);
+		if (!ctx || !ctx->ctx) throw std::runtime_error{"Module::bwd: called with invalid context. fwd likely (mistakenly) ran in inference mode."};
+		Trainer& tr = *t->trainer;
+		const uint32_t w = tr.model().input_width();
+		MatViewMut dx{dL_dinput, w, 1u};
+		tr.input_jvp_backward((hipStream_t)stream, *ctx->ctx, n, n_tangents, MatView{input, w, 1u}, tangents, dL_djvp, dL_doutput, dL_dinput ? &dx : nullptr, dL_dtangents,
+		                      (GradientMode)gradient_mode);
 	});
 }
 

@@ -1942,9 +1942,13 @@ public:
 		bool have_d = false, have_wt0 = false;
 	};
 
+	// the route of input_jvp_backward() for this network ("two-pass": the passes below, composed by the model)
+	MlpInputJvpBackwardPlan input_jvp_backward_plan(uint32_t n, uint32_t n_tangents) const { return mlp_input_jvp_backward_plan(m_desc, m_layerwise, n, n_tangents); }
+
 	// need_d: second_order_finish() will be asked for parameter gradients or for dS_dinput (else only the forward pass is run again)
+	// (For any otype, as second_order_forward(): input_jvp_backward() runs these passes for a FullyFusedMLP too.  The public
+	// backward_backward_input of a FullyFusedMLP is refused by the model in front, before it gets here.)
 	SecondOrderPass second_order_begin(hipStream_t stream, uint32_t n, const void* input, const void* dL_doutput, const void* params, bool need_d) const {
-		CHECK_THROW(!m_fully_fused);
 		SecondOrderPass s = second_order_forward(stream, n, input, params);
 		s.dL_doutput = dL_doutput;
 		const uint32_t K = m_desc.n_layers;
@@ -2258,6 +2262,49 @@ public:
 		m_last_input_jvp_route = input_jvp_impl(stream, n, n_tangents, input, tangents, jvp, output, params);
 	}
 	const char* last_input_jvp_route() const { return m_last_input_jvp_route.c_str(); } // "none" before the first call
+
+	// ---- Training through input_jvp (DESIGN.md "Training through input_jvp").  input_jvp_forward() is input_jvp() -- the same route, the
+	// same bits in jvp and output -- and returns a context that holds no device memory: input_jvp_backward() runs the module's
+	// forward(prepare_input_gradients) again from x, which is cheaper to repeat than to keep for every pending call.
+	struct InputJvpContext : public ModelContext {
+		uint32_t n = 0, n_tangents = 0;
+	};
+	std::unique_ptr<ModelContext> input_jvp_forward(hipStream_t stream, uint32_t n, uint32_t n_tangents, MatView input, const float* tangents, void* jvp, void* output, const void* params) {
+		input_jvp(stream, n, n_tangents, input, tangents, jvp, output, params);
+		auto ctx = std::make_unique<InputJvpContext>();
+		ctx->n = n;
+		ctx->n_tangents = n_tangents;
+		return ctx;
+	}
+	// The gradients of L = sum_t <dL_djvp[:, t, :], J(x) tangents[:, t, :]> + <dL_doutput, f(x)>, first order only.  dL_djvp
+	// [n][n_tangents][padded_output_width] and dL_doutput [n][padded_output_width] (optional) in the module's precision, taken as they are
+	// (no loss scale inside).  Optional results: gradients per `mode`, dL_dinput [n][input_width] and dL_dtangents
+	// [n][n_tangents][input_width] floats.  Only what is asked for is computed.  Everything is checked before anything is allocated or
+	// launched; a refused call leaves the route strings alone.
+	void input_jvp_backward(hipStream_t stream, const ModelContext& mctx, uint32_t n, uint32_t n_tangents, MatView input, const float* tangents, const void* dL_djvp,
+	                        const void* dL_doutput, const void* params, void* gradients, MatViewMut* dL_dinput, float* dL_dtangents, GradientMode mode) {
+		if (!tangents) throw std::runtime_error{"input_jvp_backward: tangents must not be NULL"};
+		if (!dL_djvp) throw std::runtime_error{"input_jvp_backward: dL_djvp must not be NULL"};
+		if (n_tangents == 0) throw std::runtime_error{"input_jvp_backward: n_tangents = 0 must be at least 1"};
+		check_batch(n);
+		if (!has_tangent()) throw std::runtime_error{"input_jvp: not implemented for " + name()};
+		const InputJvpContext* ctx = dynamic_cast<const InputJvpContext*>(&mctx);
+		if (!ctx) throw std::runtime_error{"Module::bwd: called with invalid context. fwd likely (mistakenly) ran in inference mode."};
+		if (ctx->n != n || ctx->n_tangents != n_tangents) {
+			throw std::runtime_error{"input_jvp_backward: the context is of a call with n = " + std::to_string(ctx->n) + ", n_tangents = " + std::to_string(ctx->n_tangents)};
+		}
+		const bool want_grads = mode != GradientMode::Ignore;
+		CHECK_THROW(!want_grads || gradients != nullptr);
+		// d/dx of an encoding's tangent is its second-order pass: OneBlob has a tangent but no k''
+		Encoding* e = input_encoding();
+		const bool encoding_second_order = !e || e->has_second_order();
+		if (dL_dinput && !encoding_second_order) throw std::runtime_error{"input_jvp_backward: dL_dinput not implemented for " + name()};
+		if (want_grads && !encoding_second_order && e->n_params() > 0) throw std::runtime_error{"input_jvp_backward: dL_dparams not implemented for " + name()};
+		CHECK_THROW(n == 0 || (input.data != nullptr && (params != nullptr || n_params() == 0)));
+		if (n == 0 || (!want_grads && !dL_dinput && !dL_dtangents)) return;
+		m_last_input_jvp_backward_route = input_jvp_backward_impl(stream, n, n_tangents, input, tangents, dL_djvp, dL_doutput, params, want_grads ? gradients : nullptr, dL_dinput, dL_dtangents, mode);
+	}
+	const char* last_input_jvp_backward_route() const { return m_last_input_jvp_backward_route.c_str(); } // "none" before the first call
 	virtual bool has_tangent() const { return false; } // false: PPNG1 / PPNG2 (or a Composite holding one) is part of the module
 	virtual Json hyperparams() const = 0;
 	std::string name() const { return hyperparams().value("otype", "<Unknown>"); } // object.h:51-53
@@ -2324,12 +2371,66 @@ protected:
 			if (n_tangents > 1) copy_columns(stream, elem, n, dst, pw, 0, jvp, n_tangents * pw, t * pw, pw);
 		}
 	}
+	// The composed route of input_jvp_backward(), for every module with a tangent, from existing passes alone.  <u, J(x, theta) v>
+	// differentiated by theta and x is what the second-order pass gives for dL_ddLdinput = v and dL_doutput = u, and by v it is the
+	// first-order J^T u.  So, on ONE forward(prepare_input_gradients):
+	//   first           backward(dL_doutput), if there is one: the parameter gradients under the caller's mode, dL_dinput written in place
+	//   per tangent t   tangent_reverse(v_t, u_t) -- the second-order pass -- for the parameter gradients (the caller's mode if nothing was
+	//                   written before, else Accumulate) and dL_dinput (likewise in place, else added in order);
+	//                   backward(dL_doutput = u_t, Ignore) into the tangent's strided slice of dL_dtangents
+	// with u_t = dL_djvp[:, t, :] copied out of the caller's matrix (one tangent: read in place).  Every result is bit for bit what a caller
+	// gets who chains forward / backward / backward_backward_input by hand in this order, accumulating the parameter gradients through the
+	// second-order pass's Accumulate mode and adding the input gradients in fp32, where the module has those passes.
+	virtual std::string input_jvp_backward_impl(hipStream_t stream, uint32_t n, uint32_t n_tangents, MatView input, const float* tangents, const void* dL_djvp, const void* dL_doutput,
+	                                            const void* params, void* gradients, MatViewMut* dL_dinput, float* dL_dtangents, GradientMode mode) {
+		const uint32_t pw = padded_output_width(), w = input_width();
+		const size_t elem = precision() == Precision::Fp32 ? 4 : 2, bytes = (size_t)n * pw * elem;
+		const bool want_grads = gradients != nullptr && mode != GradientMode::Ignore;
+		ArenaBuf out{stream, bytes}, one, dx_more;
+		if (n_tangents > 1) one = ArenaBuf{stream, bytes};
+		MatViewMut dx_view{nullptr, w, 1u};
+		if (dL_dinput && (n_tangents > 1 || dL_doutput)) {
+			dx_more = ArenaBuf{stream, (size_t)n * w * sizeof(float)};
+			dx_view.data = dx_more.as<float>();
+		}
+		const std::unique_ptr<ModelContext> ctx = forward(stream, n, input, out.data(), params, true);
+		bool first = true; // nothing written yet: the next pass writes the gradients under the caller's mode and dL_dinput in place
+		if (dL_doutput && (want_grads || dL_dinput)) {
+			backward(stream, *ctx, n, input, out.data(), dL_doutput, dL_dinput, params, gradients, want_grads ? mode : GradientMode::Ignore);
+			first = false;
+		}
+		for (uint32_t t = 0; t < n_tangents; ++t) {
+			const void* u = dL_djvp;
+			if (n_tangents > 1) {
+				copy_columns(stream, elem, n, dL_djvp, n_tangents * pw, t * pw, one.data(), pw, 0, pw);
+				u = one.data();
+			}
+			if (want_grads || dL_dinput) {
+				MatViewMut* dx = !dL_dinput ? nullptr : first ? dL_dinput : &dx_view;
+				tangent_reverse(stream, *ctx, n, input, tangent_slice(tangents, t, n_tangents), u, dx, params, gradients, !want_grads ? GradientMode::Ignore : first ? mode : GradientMode::Accumulate);
+				if (dL_dinput && !first) add_input_gradient(stream, n, w, MatView{dx_view.data, dx_view.stride_sample, dx_view.stride_dim}, *dL_dinput);
+				first = false;
+			}
+			if (dL_dtangents) {
+				MatViewMut slice{dL_dtangents + (size_t)t * w, n_tangents * w, 1u};
+				backward(stream, *ctx, n, input, out.data(), u, &slice, params, nullptr, GradientMode::Ignore);
+			}
+		}
+		return "two-pass";
+	}
+	// the second-order pass as input_jvp_backward() needs it: backward_backward_input() asked for dL_dinput and the parameter gradients.
+	// A model whose public pass refuses modules that this one serves (FullyFusedMLP, OneBlob) overrides it.
+	virtual void tangent_reverse(hipStream_t stream, const ModelContext& ctx, uint32_t n, MatView input, MatView v, const void* u, MatViewMut* dL_dinput, const void* params,
+	                             void* gradients, GradientMode mode) {
+		backward_backward_input(stream, ctx, n, input, v, u, nullptr, dL_dinput, params, gradients, mode);
+	}
 	// rows [:, t, :] of the [n][n_tangents][input_width] tangents as a view of [n][input_width]
 	MatView tangent_slice(const float* tangents, uint32_t t, uint32_t n_tangents) const { return MatView{tangents + (size_t)t * input_width(), n_tangents * input_width(), 1u}; }
 private:
 	std::string m_last_input_gradient_route = "none";
 	std::string m_last_input_jacobian_route = "none";
 	std::string m_last_input_jvp_route = "none";
+	std::string m_last_input_jvp_backward_route = "none";
 public:
 
 	static void check_batch(uint32_t n) { // object.h:130,150,197,246
@@ -2710,6 +2811,30 @@ public:
 		if (m_network->fully_fused() || !m_encoding->has_second_order()) {
 			return Model::backward_backward_input(stream, mctx, n, input, dL_ddLdinput, dL_doutput, dL_ddLdoutput, dL_dinput, params, gradients, mode);
 		}
+		second_order(stream, mctx, n, input, dL_ddLdinput, dL_doutput, dL_ddLdoutput, dL_dinput, params, gradients, mode);
+	}
+protected:
+	// the route is the network's plan's (mlp_input_jvp_backward_plan).  Every class is "two-pass" today, the generic composition; a fused entry
+	// has no kernel to run yet and is refused here instead of being served by another route under its name.
+	std::string input_jvp_backward_impl(hipStream_t stream, uint32_t n, uint32_t n_tangents, MatView input, const float* tangents, const void* dL_djvp, const void* dL_doutput,
+	                                    const void* params, void* gradients, MatViewMut* dL_dinput, float* dL_dtangents, GradientMode mode) override {
+		const MlpInputJvpBackwardPlan plan = m_network->input_jvp_backward_plan(n, n_tangents);
+		if (plan.fused) throw std::runtime_error{std::string{"input_jvp_backward: no kernel for the plan's route "} + plan.name};
+		Model::input_jvp_backward_impl(stream, n, n_tangents, input, tangents, dL_djvp, dL_doutput, params, gradients, dL_dinput, dL_dtangents, mode);
+		return plan.name;
+	}
+	// input_jvp_backward()'s second-order pass: the passes above for any network otype -- Network::second_order_* run for a FullyFusedMLP as
+	// they do for input_jvp -- and behind an encoding that has a tangent but no second-order pass (OneBlob), where step 2 is the tangent
+	// alone: such an encoding has no parameters here and dL_dinput is not asked for (Model::input_jvp_backward refuses both).
+	void tangent_reverse(hipStream_t stream, const ModelContext& ctx, uint32_t n, MatView input, MatView v, const void* u, MatViewMut* dL_dinput, const void* params, void* gradients,
+	                     GradientMode mode) override {
+		second_order(stream, ctx, n, input, v, u, nullptr, dL_dinput, params, gradients, mode);
+	}
+private:
+	void second_order(hipStream_t stream, const ModelContext& mctx, uint32_t n, MatView input, MatView dL_ddLdinput, const void* dL_doutput,
+	                  void* dL_ddLdoutput, MatViewMut* dL_dinput, const void* params, void* gradients, GradientMode mode) {
+		const bool tangent_only = !m_encoding->has_second_order();
+		CHECK_THROW(!tangent_only || (!dL_dinput && m_encoding->n_params() == 0));
 		check_batch(n);
 		const Ctx& ctx = dynamic_cast<const Ctx&>(mctx);
 		if (ctx.fused || !ctx.input_gradients) throw std::runtime_error{"NetworkWithInputEncoding::backward: input gradients were not prepared by forward()"};
@@ -2724,7 +2849,7 @@ public:
 		const bool want_q = m_network->any_curvature() && (enc_grads || dL_dinput);
 
 		ArenaBuf g_e, t{stream, enc_bytes}, q;
-		if (m_encoding->second_order_reads_dL_dy() && (enc_grads || dL_dinput)) {
+		if (!tangent_only && m_encoding->second_order_reads_dL_dy() && (enc_grads || dL_dinput)) {
 			g_e = ArenaBuf{stream, enc_bytes};
 			ArenaBuf output; // backward() reads it for the output activation's derivative only
 			if (m_network->has_output_activation()) {
@@ -2734,7 +2859,8 @@ public:
 			m_network->backward(stream, ctx.network_ctx, n, ctx.network_input.data(), output.data(), dL_doutput, g_e.data(), p, nullptr, GradientMode::Ignore);
 		}
 		Network::SecondOrderPass pass = m_network->second_order_begin(stream, n, ctx.network_input.data(), dL_doutput, p, want_grads || want_q);
-		m_encoding->backward_backward_input(stream, ctx.encoding_ctx, n, input, dL_ddLdinput, g_e.data(), t.data(), dL_dinput, encoding_params(p), encoding_params(g), mode);
+		if (tangent_only) m_encoding->tangent(stream, ctx.encoding_ctx, n, input, dL_ddLdinput, t.data(), encoding_params(p));
+		else m_encoding->backward_backward_input(stream, ctx.encoding_ctx, n, input, dL_ddLdinput, g_e.data(), t.data(), dL_dinput, encoding_params(p), encoding_params(g), mode);
 		if (want_q) q = ArenaBuf{stream, enc_bytes};
 		m_network->second_order_finish(stream, pass, n, t.data(), dL_ddLdoutput, q.data(), p, g, mode);
 		if (!want_q) return;
@@ -2748,6 +2874,7 @@ public:
 		                          enc_grads ? GradientMode::Accumulate : GradientMode::Ignore);
 		if (dL_dinput) add_input_gradient(stream, n, m_encoding->input_width(), MatView{dx_view.data, dx_view.stride_sample, dx_view.stride_dim}, *dL_dinput);
 	}
+public:
 
 	// TCNN_AMD_FUSED_STEP=0 selects the reference-shaped kernel sequence (forward / loss / backward / wgrad) for A/B runs
 	static bool use_fused_step() { return switches().fused_step; }
@@ -3035,6 +3162,11 @@ protected:
 	void tangent(hipStream_t stream, const ModelContext& mctx, uint32_t n, MatView input, MatView v, void* t, const void* params) override {
 		const Ctx& ctx = dynamic_cast<const Ctx&>(mctx);
 		m_encoding->tangent(stream, ctx.encoding_ctx, n, input, v, t, params);
+	}
+	// (an encoding with a tangent but no second-order pass -- OneBlob -- has no parameters and is not asked for dL_dinput: nothing to do)
+	void tangent_reverse(hipStream_t stream, const ModelContext& ctx, uint32_t n, MatView input, MatView v, const void* u, MatViewMut* dL_dinput, const void* params, void* gradients,
+	                     GradientMode mode) override {
+		if (m_encoding->has_second_order()) Model::tangent_reverse(stream, ctx, n, input, v, u, dL_dinput, params, gradients, mode);
 	}
 private:
 	Precision m_precision;
@@ -4324,6 +4456,16 @@ public:
 		l["otype"] = to_string(m_loss);
 		j["loss"] = l;
 		return j;
+	}
+
+	// Training through input_jvp on the trainer's training parameters: Model::input_jvp_forward / _backward, the parameter gradients into
+	// the trainer's gradient buffer (optimizer_step() reads it).  No loss scale inside: the caller's cotangents carry it.
+	std::unique_ptr<ModelContext> input_jvp_forward(hipStream_t stream, uint32_t n, uint32_t n_tangents, MatView input, const float* tangents, void* jvp, void* output) {
+		return m_model->input_jvp_forward(stream, n, n_tangents, input, tangents, jvp, output, working_params());
+	}
+	void input_jvp_backward(hipStream_t stream, const ModelContext& ctx, uint32_t n, uint32_t n_tangents, MatView input, const float* tangents, const void* dL_djvp, const void* dL_doutput,
+	                        MatViewMut* dL_dinput, float* dL_dtangents, GradientMode mode) {
+		m_model->input_jvp_backward(stream, ctx, n, n_tangents, input, tangents, dL_djvp, dL_doutput, working_params(), m_grads.data(), dL_dinput, dL_dtangents, mode);
 	}
 
 	NetworkWithInputEncoding& model() { return *m_model; }

@@ -604,6 +604,22 @@ MlpInputJvpPlan mlp_input_jvp_plan(const MlpDesc& d, bool layerwise, uint32_t n,
 // which this may be a group).  plan.fused must hold for (d, n).
 void mlp_input_jvp(hipStream_t stream, const MlpDesc& d, const MlpInputJvpPlan& plan, const void* image, uint32_t n, const MlpIo& io, const void* tangents, MatView tangents_f32,
                    uint32_t n_tangents, void* jvp, uint32_t jvp_stride);
+// ---- input_jvp_backward: the reverse of input_jvp (parameter, input and tangent gradients of L = sum_t <dL_djvp_t, J v_t> + <dL_doutput, f>).
+// The plan has MlpInputJvpPlan's shape, so that a fused kernel "k_mlp_input_jvp_bwd<W,NB,NH,TT>/relu|act" can enter a class here once
+// tools/bench_input_jvp_backward.py has measured it faster than the composed route by more than 3 %.  No such kernel is built yet: every
+// class is "two-pass" -- the composed route of the existing second-order and first-order passes (DESIGN.md "Training through input_jvp").
+struct MlpInputJvpBackwardPlan {
+	bool fused = false;          // false: the composed route (name "two-pass")
+	char name[48] = "two-pass";  // tcnn_module_last_input_jvp_backward_route
+	uint32_t nb = 0, grid = 0;   // fused: column blocks of 16 samples per wave and trip, workgroups of 4 waves
+	uint32_t tt = 0;             // fused: tangent chains per launch
+	bool relu = false;           // fused: the compiled ReLU form, else the activation chosen at run time
+};
+// Pure host code, a pure function of its arguments.  NetworkWithInputEncoding::input_jvp_backward_impl asks it per call and reports its name.
+inline MlpInputJvpBackwardPlan mlp_input_jvp_backward_plan(const MlpDesc& d, bool layerwise, uint32_t n, uint32_t n_tangents) {
+	(void)d; (void)layerwise; (void)n; (void)n_tangents;
+	return MlpInputJvpBackwardPlan{};
+}
 // the two ends of every input_gradient route (object.h:352-365): d_doutput [n][width] T = (T)backprop_scale in column dim, +0 elsewhere;
 // d_dinput[i][j] *= mult for j < dims (mult = 1.0f / backprop_scale, formed once by the caller)
 void input_gradient_one_hot(hipStream_t stream, Precision precision, uint32_t n, uint32_t width, uint32_t dim, float backprop_scale, void* d_doutput);

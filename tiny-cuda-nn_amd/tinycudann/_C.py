@@ -84,6 +84,11 @@ _SIGNATURES = {
     "tcnn_module_input_jvp": (_int, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     "tcnn_module_last_input_jvp_route": (_cp, [_vp]),
     "tcnn_trainer_input_jvp": (_int, [_vp, _vp, _u32, _u32, _vp, _vp, _vp]),
+    "tcnn_module_input_jvp_forward": (_int, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tcnn_module_input_jvp_backward": (_int, [_vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int]),
+    "tcnn_module_last_input_jvp_backward_route": (_cp, [_vp]),
+    "tcnn_trainer_input_jvp_forward": (_int, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "tcnn_trainer_input_jvp_backward": (_int, [_vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _int]),
     "tcnn_context_destroy": (None, [_vp]),
     "tcnn_module_n_input_dims": (_u32, [_vp]),
     "tcnn_module_n_output_dims": (_u32, [_vp]),

@@ -194,6 +194,50 @@ class NativeModule:
         """ "none" before the first input_jvp call, then "two-pass" or the fused MLP kernel's name (tcnn_amd.h: tcnn_module_last_input_jvp_route)"""
         return _C.lib.tcnn_module_last_input_jvp_route(self._h).decode()
 
+    def input_jvp_fwd(self, input, params, tangents, want_output=False):
+        """input_jvp with a context for input_jvp_bwd: (context, jvp, output) -- the same bits (tcnn_amd.h: tcnn_module_input_jvp_forward)"""
+        self._check_inputs(input, params)
+        n, n_tangents = input.shape[0], tangents.shape[1]
+        assert tangents.dtype == torch.float32 and tangents.is_contiguous() and tangents.device == input.device and tuple(tangents.shape) == (n, n_tangents, self.n_input_dims())
+        with torch.cuda.device(input.device):
+            dtype = _torch_precision(self.output_precision())
+            jvp = torch.empty((n, n_tangents, self.n_output_dims()), dtype=dtype, device=input.device)
+            output = torch.empty((n, self.n_output_dims()), dtype=dtype, device=input.device) if want_output else None
+            h = _C.C.c_void_p()
+            _C.check(_C.lib.tcnn_module_input_jvp_forward(self._h, _stream(), n, n_tangents, _ptr(input), _ptr(tangents), _ptr(jvp), _ptr(output), _ptr(params), _C.C.byref(h)))
+        return NativeContext(h), jvp, output
+
+    def input_jvp_bwd(self, ctx, input, params, tangents, dL_djvp, dL_doutput=None, want_params=True, want_input=True, want_tangents=True, dL_dparams=None):
+        """The gradients of sum_t <dL_djvp[:, t], J v_t> + <dL_doutput, f(x)>: (dL_dparams, dL_dinput, dL_dtangents), None where not wanted
+        (tcnn_amd.h: tcnn_module_input_jvp_backward).  No loss scale inside.  dL_dparams given: accumulated onto it, else a new tensor."""
+        if ctx is None or not ctx._h:
+            raise RuntimeError("Module::bwd: called with invalid context. fwd likely (mistakenly) ran in inference mode.")
+        self._check_inputs(input, params)
+        n, n_tangents = input.shape[0], tangents.shape[1]
+        dtype = _torch_precision(self.output_precision())
+        assert tangents.dtype == torch.float32 and tangents.is_contiguous() and tuple(tangents.shape) == (n, n_tangents, self.n_input_dims())
+        assert dL_djvp.dtype == dtype and dL_djvp.is_contiguous() and tuple(dL_djvp.shape) == (n, n_tangents, self.n_output_dims())
+        assert dL_doutput is None or (dL_doutput.dtype == dtype and dL_doutput.is_contiguous() and tuple(dL_doutput.shape) == (n, self.n_output_dims()))
+        with torch.cuda.device(input.device):
+            mode = 0  # TCNN_GRADIENT_IGNORE
+            if dL_dparams is not None:
+                assert dL_dparams.dtype == params.dtype and dL_dparams.is_contiguous() and dL_dparams.shape == params.shape
+                mode = 2  # TCNN_GRADIENT_ACCUMULATE
+            elif want_params:
+                dL_dparams = torch.empty(self.n_params(), dtype=params.dtype, device=input.device)
+                mode = 1  # TCNN_GRADIENT_OVERWRITE
+            if self.n_params() == 0:
+                mode = 0  # (nothing to write, and no buffer to name)
+            dL_dinput = torch.empty((n, self.n_input_dims()), dtype=torch.float32, device=input.device) if want_input else None
+            dL_dtangents = torch.empty((n, n_tangents, self.n_input_dims()), dtype=torch.float32, device=input.device) if want_tangents else None
+            _C.check(_C.lib.tcnn_module_input_jvp_backward(self._h, _stream(), ctx._h, n, n_tangents, _ptr(input), _ptr(tangents), _ptr(dL_djvp), _ptr(dL_doutput), _ptr(params),
+                                                           _ptr(dL_dparams), _ptr(dL_dinput), _ptr(dL_dtangents), mode))
+        return dL_dparams, dL_dinput, dL_dtangents
+
+    def last_input_jvp_backward_route(self):
+        """ "none" before the first input_jvp_bwd call, then "two-pass" (tcnn_amd.h: tcnn_module_last_input_jvp_backward_route)"""
+        return _C.lib.tcnn_module_last_input_jvp_backward_route(self._h).decode()
+
     def bwd_bwd_input(self, ctx, input, params, dL_ddLdinput, dL_doutput):  # bindings.cpp:172-245
         """from dL_ddLdinput to (dL_ddLdoutput, dL_dparams, dL_dinput); each is None unless its tensor requires grad."""
         if ctx is None or not ctx._h:
@@ -351,6 +395,55 @@ class _Differentiate(torch.autograd.Function):
         return g_doutput, g_input, g_params, None, None
 
 
+class _InputJvp(torch.autograd.Function):
+    """input_jvp attached to autograd with respect to (input, params, tangents): first order only."""
+
+    @staticmethod
+    def forward(ctx, input, params, tangents, native, loss_scale, want_output, max_level):
+        call = _Call(native, loss_scale, ctx.needs_input_grad[0], ctx.needs_input_grad[1], max_level)
+        ctx.wants_tangents = ctx.needs_input_grad[2]
+        with call.setting():
+            call.native_ctx, jvp, output = native.input_jvp_fwd(input.detach(), params.detach(), tangents.detach(), want_output)
+        ctx.call = call
+        ctx.save_for_backward(input, params, tangents)
+        ctx.set_materialize_grads(False)
+        if not want_output:
+            output = jvp.new_empty(0)
+            ctx.mark_non_differentiable(output)
+        return jvp, output
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_jvp, d_output):
+        if d_jvp is None and d_output is None:
+            return (None,) * 7
+        input, params, tangents = ctx.saved_tensors
+        call = ctx.call
+        native = call.native
+        dtype = _torch_precision(native.output_precision())
+        n, n_tangents = tangents.shape[0], tangents.shape[1]
+        if d_jvp is None:
+            # only the output entered the loss: the plain forward and first-order backward pass, no pass per tangent
+            g_input = g_params = None
+            if call.wants_input or call.wants_params:
+                inp, par = call.flagged(input, params)
+                with call.setting():
+                    plain_ctx, output = native.fwd(inp, par)
+                    g_input, g_params = native.bwd(plain_ctx, inp, par, output, (d_output * call.loss_scale).to(dtype).contiguous())
+            inv = 1.0 / call.loss_scale
+            return (None if g_input is None else g_input * inv, None if g_params is None else g_params * inv,
+                    torch.zeros_like(tangents) if ctx.wants_tangents else None, None, None, None, None)
+        # (cotangents at loss_scale in the output precision, the gradients divided by it again: as _Call.first_order)
+        d_jvp = (d_jvp * call.loss_scale).to(dtype).contiguous()
+        if d_output is not None:
+            d_output = (d_output * call.loss_scale).to(dtype).contiguous()
+        with call.setting():
+            g_params, g_input, g_tangents = native.input_jvp_bwd(call.native_ctx, input.detach(), params.detach(), tangents.detach(), d_jvp, d_output,
+                                                                call.wants_params, call.wants_input, ctx.wants_tangents)
+        inv = 1.0 / call.loss_scale
+        return (None if g_input is None else g_input * inv, None if g_params is None else g_params * inv, None if g_tangents is None else g_tangents * inv, None, None, None, None)
+
+
 def _pad_rows(x, multiple):
     """x with its row count rounded up to a multiple (zero rows appended); the batch granularity of the kernels (common.h:235)"""
     n = x.shape[0]
@@ -468,12 +561,17 @@ class Module(torch.nn.Module):
             jacobian = jacobian[:n]
             return (jacobian, output[:n, : self.n_output_dims]) if return_output else jacobian
 
-    def input_jvp(self, x, tangents, return_output=False):
+    def input_jvp(self, x, tangents, return_output=False, differentiable=False):
         """Forward mode: every output's derivative along given input directions, for any n.  tangents [n, T, n_input_dims] gives
         [n, T, n_output_dims] in the module's output precision with [:, t, :] = J(x) tangents[:, t, :]; a 2-D tangents [n, n_input_dims]
         means T = 1 and gives [n, n_output_dims].  Outside autograd (not differentiable) and under the max_level setting in force, as
         input_gradient.  There is no backprop_scale: the map is linear in the tangent, so scale the tangent if half precision might
-        overflow.  return_output=True: (jvp, output[:n, :n_output_dims]) of the same pass."""
+        overflow.  return_output=True: (jvp, output[:n, :n_output_dims]) of the same pass.
+        differentiable=True: the same values, attached to autograd with respect to `params`, x and tangents, whichever require grad --
+        J v in a loss (first order only: a second backward through the graph raises).  Cotangents are multiplied by the module's
+        loss_scale and the gradients divided by it again, as forward() does."""
+        if differentiable:
+            return self._input_jvp_differentiable(x, tangents, return_output)
         with torch.no_grad():
             x = x.detach()
             if not x.is_cuda:
@@ -498,6 +596,30 @@ class Module(torch.nn.Module):
             if flat:
                 jvp = jvp[:, 0]
             return (jvp, output[:n, : self.n_output_dims]) if return_output else jvp
+
+    def _input_jvp_differentiable(self, x, tangents, return_output):
+        if not x.is_cuda:
+            warnings.warn("input must be a CUDA tensor, but isn't. This indicates suboptimal performance.")
+            x = x.cuda()
+        n = x.shape[0]
+        v = tangents.to(device=x.device, dtype=torch.float)
+        flat = v.dim() == 2
+        if flat:
+            v = v[:, None, :]
+        if v.dim() != 3 or v.shape[0] != n or v.shape[1] < 1 or v.shape[2] != self.n_input_dims:
+            raise ValueError("input_jvp: tangents must be [n, T, n_input_dims] or [n, n_input_dims] with T >= 1, got %s" % (tuple(tangents.shape),))
+        granularity = _C.batch_size_granularity()
+        rows = _pad_rows(x.to(torch.float), granularity).contiguous()
+        v = _pad_rows(v.reshape(n, -1), granularity).reshape(rows.shape[0], -1, self.n_input_dims).contiguous()
+        if self.params.dtype == self.dtype:
+            working = self.params.contiguous()
+        else:
+            working = _WorkingCopy.apply(self.params, self)
+        jvp, output = _InputJvp.apply(rows, working, v, self.native_tcnn_module, self.loss_scale, return_output, self._max_level_of_call(n, rows))
+        jvp = jvp[:n, :, : self.n_output_dims]  # (padded rows and output columns receive zero cotangent through the slices)
+        if flat:
+            jvp = jvp[:, 0]
+        return (jvp, output[:n, : self.n_output_dims]) if return_output else jvp
 
     # --- max_level of the grid encoding(s) (the reference's GridEncoding::set_max_level / set_max_level_gpu, grid_interface.h:101-123).
     # Every forward call records the setting in force; its backward and double-backward passes run under that setting.

@@ -231,6 +231,35 @@ class Trainer:
         _C.check(_C.lib.tcnn_trainer_input_jvp(self._h, _stream(stream), n, n_tangents, _ptr(input), _ptr(tangents), _ptr(jvp)))
         return jvp
 
+    def input_jvp_forward(self, input, tangents, want_output=False, stream=None):
+        """input_jvp on the trainer's TRAINING parameters with a context for input_jvp_backward: (context, jvp, padded output or None)
+        (tcnn_amd.h: tcnn_trainer_input_jvp_forward)"""
+        from .modules import NativeContext
+
+        n, n_tangents = input.shape[0], tangents.shape[1]
+        assert input.dtype == torch.float32 and input.is_contiguous() and tangents.dtype == torch.float32 and tangents.is_contiguous()
+        assert tuple(tangents.shape) == (n, n_tangents, input.shape[1])
+        self._check_max_level_rows(n)
+        jvp = torch.empty((n, n_tangents, self.padded_output_width), dtype=self.dtype, device=input.device)
+        output = torch.empty((n, self.padded_output_width), dtype=self.dtype, device=input.device) if want_output else None
+        h = C.c_void_p()
+        _C.check(_C.lib.tcnn_trainer_input_jvp_forward(self._h, _stream(stream), n, n_tangents, _ptr(input), _ptr(tangents), _ptr(jvp), _ptr(output), C.byref(h)))
+        return NativeContext(h), jvp, output
+
+    def input_jvp_backward(self, ctx, input, tangents, dL_djvp, dL_doutput=None, want_input=True, want_tangents=True, gradient_mode=GRADIENT_OVERWRITE, stream=None):
+        """The gradients of sum_t <dL_djvp[:, t], J v_t> + <dL_doutput, f(x)>: the parameters' into the trainer's gradient buffer under
+        gradient_mode (optimizer_step reads it; no loss scale inside), and (dL_dinput, dL_dtangents), None where not wanted
+        (tcnn_amd.h: tcnn_trainer_input_jvp_backward)"""
+        n, n_tangents = input.shape[0], tangents.shape[1]
+        assert dL_djvp.dtype == self.dtype and dL_djvp.is_contiguous() and tuple(dL_djvp.shape) == (n, n_tangents, self.padded_output_width)
+        assert dL_doutput is None or (dL_doutput.dtype == self.dtype and dL_doutput.is_contiguous() and tuple(dL_doutput.shape) == (n, self.padded_output_width))
+        self._check_max_level_rows(n)
+        dL_dinput = torch.empty((n, input.shape[1]), dtype=torch.float32, device=input.device) if want_input else None
+        dL_dtangents = torch.empty((n, n_tangents, input.shape[1]), dtype=torch.float32, device=input.device) if want_tangents else None
+        _C.check(_C.lib.tcnn_trainer_input_jvp_backward(self._h, _stream(stream), ctx._h, n, n_tangents, _ptr(input), _ptr(tangents), _ptr(dL_djvp), _ptr(dL_doutput),
+                                                        _ptr(dL_dinput), _ptr(dL_dtangents), gradient_mode))
+        return dL_dinput, dL_dtangents
+
     # -- object.h:133-145: network->inference_mixed_precision(stream, input, output): half [n][padded_output_width]
     def inference_half(self, input, output=None, input_layout=LAYOUT_AOS, stream=None):
         if self.dtype != torch.half:
