@@ -18,183 +18,12 @@ import math
 import numpy as np
 import pytest
 
+# the recipes, restated: shared with the first-order per-element tests
+from analytic_encoding_reference import _half_ulp, _restate, _triangle_inputs, _width
+
 gpu = pytest.mark.gpu
 LOSS_SCALE = 128.0
 NOT_IMPLEMENTED = "backward_backward_input_impl: not implemented error"
-
-
-# ---------------------------------------------------------------------------------------------------- the recipes, restated
-def _mode(mode):
-    """(compute dtype, rounding applied where the kernels store a value of the encoding's precision)"""
-    import torch
-
-    if mode == "r64":
-        return torch.float64, (lambda t: t)
-    if mode == "f32":
-        return torch.float32, (lambda t: t)
-    assert mode == "half"
-    return torch.float32, (lambda t: t.half().float())
-
-
-def _pi(mode):
-    return math.pi if mode == "r64" else float(np.float32(math.pi))  # the kernels' constant is a float
-
-
-def _padded(live, pad, value, first=False):
-    import torch
-
-    fill = torch.full((live.shape[0], pad), value, dtype=live.dtype)
-    return torch.cat([fill, live] if first else [live, fill], dim=1)
-
-
-def _frequency(x, v, d, n_frequencies, pad, mode):
-    """k_frequency_fwd and k_frequency_bwd_bwd_input.  Output j of dim a: (frequency k, phase) at a * 2F + 2k + phase.
-    Returns y, t [n][D * 2F + pad] and dx [n][D]."""
-    import torch
-
-    dt, store = _mode(mode)
-    PI = _pi(mode)
-    x, v = x.to(dt), v.to(dt)
-    n, D = x.shape
-    F2 = 2 * n_frequencies
-    dl = d[:, :D * F2].to(dt).reshape(n, D, F2)
-    ys, ts = [None] * F2, [None] * F2
-    total = torch.zeros(n, D, dtype=dt)
-    for k in range(n_frequencies):
-        scaled = x * float(2 ** k)
-        scale = float(2 ** k) * PI
-        for phase in range(2):
-            arg = scaled * PI + phase * (PI / 2)
-            ys[2 * k + phase] = store(torch.sin(arg))
-            ts[2 * k + phase] = store(scale * torch.cos(arg) * v)
-            total = total + dl[:, :, 2 * k + phase] * (-(scale * scale) * torch.sin(arg))
-    y = torch.stack(ys, dim=2).reshape(n, D * F2)
-    t = torch.stack(ts, dim=2).reshape(n, D * F2)
-    return _padded(y, pad, 1.0), _padded(t, pad, 0.0), v * total
-
-
-def _triangle_val(x, k, dt):
-    return x.to(dt) * float(2.0 ** (k - 1)) + k * 0.25
-
-
-def _trianglewave(x, v, d, n_frequencies, pad, mode):
-    """k_trianglewave_fwd and k_trianglewave_bwd_bwd_input: the slope's sign by the kernel's rule (floor(2 val) even: falling)"""
-    import torch
-
-    dt, store = _mode(mode)
-    x, v = x.to(dt), v.to(dt)
-    n, D = x.shape
-    ys, ts = [], []
-    for k in range(n_frequencies):
-        val = _triangle_val(x, k, dt)
-        ys.append(store((val - torch.floor(val) - 0.5).abs() * 4 - 1))
-        sign = torch.where(torch.floor(val * 2.0).to(torch.int64) % 2 == 0, -torch.ones_like(val), torch.ones_like(val))
-        ts.append(store(sign * float(2.0 ** (k + 1)) * v))
-    y = torch.stack(ys, dim=2).reshape(n, D * n_frequencies)
-    t = torch.stack(ts, dim=2).reshape(n, D * n_frequencies)
-    return _padded(y, pad, 1.0), _padded(t, pad, 0.0), torch.zeros(n, D, dtype=dt)
-
-
-def _sh_norm(l, m, mode):
-    ratio = 1.0
-    for k in range(l - m + 1, l + m + 1):
-        ratio /= k
-    value = math.sqrt((2.0 * l + 1.0) / (4.0 * math.pi) * ratio) * (math.sqrt(2.0) if m else 1.0)
-    return value if mode == "r64" else float(np.float32(value))
-
-
-def _spherical_harmonics(p, v, d, degree, pad, mode):
-    """sh_eval / sh_eval_dotted line by line: every quantity with its directional derivative along 2 v.  The padding columns come
-    first.  Returns y, t [n][pad + degree^2] and dx [n][3]."""
-    import torch
-
-    dt, store = _mode(mode)
-    x, y, z = [p[:, i].to(dt) * 2.0 - 1.0 for i in range(3)]
-    dx, dy, dz = [v[:, i].to(dt) * 2.0 for i in range(3)]
-    dl = d[:, pad:].to(dt)
-    n = p.shape[0]
-    zero, one = torch.zeros(n, dtype=dt), torch.ones(n, dtype=dt)
-    values, tangent = [None] * (degree * degree), [None] * (degree * degree)
-    gx_, gy_, gz_ = zero, zero, zero
-    c, s, cp, sp = one, zero, zero, zero
-    c_, s_, cp_, sp_ = zero, zero, zero, zero
-    qmm = 1.0
-    for m in range(degree):
-        if m > 0:
-            cp, sp, cp_, sp_ = c, s, c_, s_
-            c = x * cp - y * sp
-            s = x * sp + y * cp
-            c_ = (dx * cp + x * cp_) - (dy * sp + y * sp_)
-            s_ = (dx * sp + x * sp_) + (dy * cp + y * cp_)
-            qmm = -qmm * (2 * m - 1)
-        q2 = q1 = d2 = d1 = zero
-        q2_ = q1_ = d2_ = d1_ = zero
-        for l in range(m, degree):
-            if l == m:
-                q, dq, q_, dq_ = qmm * one, zero, zero, zero
-            elif l == m + 1:
-                q = (2 * m + 1) * z * q1
-                dq = (2 * m + 1) * q1
-                q_ = (2 * m + 1) * (dz * q1 + z * q1_)
-                dq_ = (2 * m + 1) * q1_
-            else:
-                q = ((2 * l - 1) * z * q1 - (l + m - 1) * q2) / (l - m)
-                dq = ((2 * l - 1) * (q1 + z * d1) - (l + m - 1) * d2) / (l - m)
-                q_ = ((2 * l - 1) * (dz * q1 + z * q1_) - (l + m - 1) * q2_) / (l - m)
-                dq_ = ((2 * l - 1) * (q1_ + (dz * d1 + z * d1_)) - (l + m - 1) * d2_) / (l - m)
-            q2, q1, d2, d1 = q1, q, d1, dq
-            q2_, q1_, d2_, d1_ = q1_, q_, d1_, dq_
-            norm = _sh_norm(l, m, mode)
-            nq, ndq, nq_, ndq_ = norm * q, norm * dq, norm * q_, norm * dq_
-            base = l * l + l
-            if m == 0:
-                values[base] = store(nq)
-                tangent[base] = store(nq_)
-                gz_ = gz_ + dl[:, base] * ndq_
-            else:
-                values[base + m], values[base - m] = store(nq * c), store(nq * s)
-                tangent[base + m], tangent[base - m] = store(nq_ * c + nq * c_), store(nq_ * s + nq * s_)
-                gp, gm = dl[:, base + m], dl[:, base - m]
-                ncp_, nsp_ = m * (nq_ * cp + nq * cp_), m * (nq_ * sp + nq * sp_)
-                gx_ = gx_ + (gp * ncp_ + gm * nsp_)
-                gy_ = gy_ + (gp * -nsp_ + gm * ncp_)
-                gz_ = gz_ + (gp * (ndq_ * c + ndq * c_) + gm * (ndq_ * s + ndq * s_))
-    return (_padded(torch.stack(values, dim=1), pad, 1.0, first=True), _padded(torch.stack(tangent, dim=1), pad, 0.0, first=True),
-            torch.stack([2.0 * gx_, 2.0 * gy_, 2.0 * gz_], dim=1))
-
-
-def _empty(x, v, d, pad, mode):
-    import torch
-
-    dt, _ = _mode(mode)
-    n = x.shape[0]
-    return torch.ones(n, pad, dtype=dt), torch.zeros(n, pad, dtype=dt), torch.zeros(n, x.shape[1], dtype=dt)
-
-
-def _restate(cfg, x, v, d, pad, mode):
-    otype = cfg["otype"]
-    if otype == "Frequency":
-        return _frequency(x, v, d, cfg["n_frequencies"], pad, mode)
-    if otype == "TriangleWave":
-        return _trianglewave(x, v, d, cfg["n_frequencies"], pad, mode)
-    if otype == "SphericalHarmonics":
-        return _spherical_harmonics(x, v, d, cfg["degree"], pad, mode)
-    assert otype == "Empty"
-    return _empty(x, v, d, pad, mode)
-
-
-def _width(cfg, n_in):
-    return {"Frequency": lambda: n_in * 2 * cfg["n_frequencies"], "TriangleWave": lambda: n_in * cfg["n_frequencies"],
-            "SphericalHarmonics": lambda: cfg["degree"] ** 2, "Empty": lambda: 0}[cfg["otype"]]()
-
-
-def _triangle_inputs(n, n_in, seed):
-    """x = (m + 0.37) / 2^16 with integer m: x 2^(k+1) is never an integer for k <= 11, so no sample sits on a kink of any frequency"""
-    import torch
-
-    g = torch.Generator().manual_seed(seed)
-    m = torch.randint(0, 2 ** 16, (n, n_in), generator=g)
-    return ((m.double() + 0.37) / 2.0 ** 16).float()
 
 
 def _inputs(cfg, n, n_in, pad, seed, half_d=True):
@@ -206,14 +35,6 @@ def _inputs(cfg, n, n_in, pad, seed, half_d=True):
     v = torch.rand(n, n_in, generator=g) * 2 - 1
     d = ((torch.rand(n, _width(cfg, n_in) + pad, generator=g) * 2 - 1) * (LOSS_SCALE / n)).half().float()
     return x, v, d
-
-
-def _half_ulp(value):
-    """half of the distance between neighbouring half-precision numbers at |value| (2^-24 apart below 2^-14)"""
-    import torch
-
-    exponent = torch.floor(torch.log2(value.abs().clamp_min(2.0 ** -14)))
-    return 0.5 * torch.pow(2.0, exponent - 10)
 
 
 # ---------------------------------------------------------------------------------------------------- CPU: R64 is the oracle's function
