@@ -401,6 +401,20 @@ void*       tcnn_optimizer_custom_weights(tcnn_optimizer_t o);                  
 int         tcnn_optimizer_weights_restored(tcnn_optimizer_t o, tcnn_stream_t stream, const void* params_half);
 int         tcnn_optimizer_serialize(tcnn_optimizer_t o, const void** out_bytes, size_t* out_size);
 int         tcnn_optimizer_deserialize(tcnn_optimizer_t o, const void* bytes, size_t size);
+/* Test hook: the Adam kernels take their square root and their division through exact fast forms between range tests, and through sqrtf
+ * and `/` outside them.  This runs those very functions against the plain expressions on the device, compares bit for bit, stores nothing
+ * per element and waits for the result.  *mismatches: how many inputs differ (expected: 0); *first_bad: the smallest of them, ~0 if none.
+ *   TCNN_ADAM_SWEEP_SQRT       every float bit pattern in [first, first + count); first_bad is the pattern
+ *   TCNN_ADAM_SWEEP_DIV_GRID   every denominator pattern in [first, first + count) against n_numerators positive numerators whose patterns
+ *                              step evenly from numerator_lo to numerator_hi, low 16 bits hashed with seed; first_bad is denominator << 32 | numerator.
+ *                              (A denominator outside the division's range test selects the plain expression for every numerator, which
+ *                              cannot differ from itself: it is visited with the first numerator only.)
+ *   TCNN_ADAM_SWEEP_DIV_PAIRS  `count` pairs drawn from seed around both range tests' edges, a quarter of each operand negative */
+#define TCNN_ADAM_SWEEP_SQRT 0
+#define TCNN_ADAM_SWEEP_DIV_GRID 1
+#define TCNN_ADAM_SWEEP_DIV_PAIRS 2
+int         tcnn_adam_math_sweep(tcnn_stream_t stream, int what, uint64_t first, uint64_t count, uint32_t n_numerators, float numerator_lo, float numerator_hi, uint64_t seed,
+                                 uint64_t* mismatches, uint64_t* first_bad);
 
 
 /* ---- standalone losses (loss.h:41-60, src/loss.cu:57-65): the losses a trainer evaluates -- L2, RelativeL2, RelativeL2Luminance, L1,

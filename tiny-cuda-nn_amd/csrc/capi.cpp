@@ -166,6 +166,10 @@ int tcnn_generate_random_uniform(tcnn_stream_t stream, uint64_t rng_state_inc[2]
 		HIP_CHECK_THROW(hipGetLastError());
 	});
 }
+int tcnn_adam_math_sweep(tcnn_stream_t stream, int what, uint64_t first, uint64_t count, uint32_t n_numerators, float numerator_lo, float numerator_hi, uint64_t seed,
+                         uint64_t* mismatches, uint64_t* first_bad) {
+	return guarded([&] { adam_math_sweep((hipStream_t)stream, what, first, count, n_numerators, numerator_lo, numerator_hi, seed, mismatches, first_bad); });
+}
 int tcnn_has_networks(void) { return 1; }
 float tcnn_default_loss_scale(int precision) { return precision == TCNN_PRECISION_FP32 ? 1.0f : LOSS_SCALE_FP16; }
 int tcnn_preferred_precision(void) { return TCNN_PRECISION_FP16; }

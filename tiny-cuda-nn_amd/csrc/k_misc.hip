@@ -19,6 +19,8 @@
 
 #include <hip/hip_fp16.h>
 
+#include <cstring>
+
 #include <cmath>
 #include <limits>
 
@@ -349,15 +351,33 @@ template <> struct GradQuad<half_t> { typedef h4 type; };
 template <> struct GradQuad<float> { typedef f4 type; };
 // W: the working weights' type.  half_t: w is the half copy of w_fp.  float: w_fp is the optimizer's one weight vector -- read once, stored
 // once, w is not touched (30 - 32 B/param instead of 32 - 36) -- and G is float.
-template <bool QUAD_UNIFORM, typename STEP_T, typename G, typename W>
+// debias_table at min(step + 1, common_step) for each of a quad's parameters: requested together, in front of the arithmetic
+__device__ inline void adam_load_debias(const float* __restrict__ debias_table, const uint32_t common_step, const uint4 st, float (&debias)[4]) {
+	debias[0] = debias_table[min(st.x + 1, common_step)];
+	debias[1] = debias_table[min(st.y + 1, common_step)];
+	debias[2] = debias_table[min(st.z + 1, common_step)];
+	debias[3] = debias_table[min(st.w + 1, common_step)];
+}
+// one parameter on its own (ragged tails, unaligned ranges, the MLP's weights behind their slab sums)
+template <typename STEP_T, typename G, typename W>
+__device__ inline void adam_single(const AdamArgs& a, const float* __restrict__ debias_table, const bool is_matrix, const size_t i, const G g, float* __restrict__ w_fp, W* __restrict__ w,
+                                   float* __restrict__ m1, float* __restrict__ m2, STEP_T* __restrict__ steps) {
+	bool up;
+	W wh;
+	uint32_t st1 = steps[i];
+	adam_one(a, debias_table[min(st1 + 1, a.common_step)], is_matrix, g, w_fp[i], wh, m1[i], m2[i], st1, up);
+	steps[i] = (STEP_T)st1;
+	if constexpr (sizeof(W) == 2) { if (up) w[i] = wh; }
+}
+
+// PLAIN: adam_device.h (a power-of-two loss scale and no weight clipping, found by the host)
+template <bool PLAIN, bool QUAD_UNIFORM, typename STEP_T, typename G, typename W>
 __global__ void __launch_bounds__(256) k_adam(
 	const AdamArgs a, const size_t n, const size_t n_matrix,
 	float* __restrict__ w_fp, W* __restrict__ w, const G* __restrict__ g, float* __restrict__ m1, float* __restrict__ m2, STEP_T* __restrict__ steps,
 	const float* __restrict__ debias_table
 ) {
 	const size_t base = (size_t)blockIdx.x * (256 * 4 * ADAM_Q) + threadIdx.x * 4;
-	const float debias = debias_table[a.common_step];
-	const auto from_table = [&](const uint32_t t) { return debias_table[t]; };
 	// phase 1: the gradients of all quads (8 B each, 16 B for fp32 gradients).  Grid (non-matrix) quads whose 4 gradients are all zero are skipped
 	// without touching the other 32 B/param (adam.h:76-79 returns before reading anything else).
 	typedef typename GradQuad<G>::type g4;
@@ -375,17 +395,19 @@ __global__ void __launch_bounds__(256) k_adam(
 		const bool zero = gv[q][0] == (G)0.0f && gv[q][1] == (G)0.0f && gv[q][2] == (G)0.0f && gv[q][3] == (G)0.0f;
 		if (live[q] && i4 >= n_matrix && zero) live[q] = false;
 	}
-	// phase 2: all remaining loads in flight together
+	// phase 2: all remaining loads in flight together; the counts first, the debias factors they select right behind them
 	float4 wf[ADAM_Q], a1[ADAM_Q], a2[ADAM_Q];
 	uint4 st[ADAM_Q];
+	float debias[ADAM_Q][4];
 #pragma unroll
 	for (int q = 0; q < ADAM_Q; ++q) {
 		const size_t i4 = base + (size_t)q * 1024;
 		if (live[q]) {
+			st[q] = adam_load_steps(steps + i4);
 			wf[q] = *(const float4*)(w_fp + i4);
 			a1[q] = *(const float4*)(m1 + i4);
 			a2[q] = *(const float4*)(m2 + i4);
-			st[q] = adam_load_steps(steps + i4);
+			adam_load_debias(debias_table, a.common_step, st[q], debias[q]);
 		}
 	}
 #pragma unroll
@@ -395,14 +417,16 @@ __global__ void __launch_bounds__(256) k_adam(
 			W wh[4];
 			bool up[4];
 			const bool quad_matrix = i4 < n_matrix;
-			adam_one(a, from_table, debias, QUAD_UNIFORM ? quad_matrix : i4 + 0 < n_matrix, gv[q][0], wf[q].x, wh[0], a1[q].x, a2[q].x, st[q].x, up[0]);
-			adam_one(a, from_table, debias, QUAD_UNIFORM ? quad_matrix : i4 + 1 < n_matrix, gv[q][1], wf[q].y, wh[1], a1[q].y, a2[q].y, st[q].y, up[1]);
-			adam_one(a, from_table, debias, QUAD_UNIFORM ? quad_matrix : i4 + 2 < n_matrix, gv[q][2], wf[q].z, wh[2], a1[q].z, a2[q].z, st[q].z, up[2]);
-			adam_one(a, from_table, debias, QUAD_UNIFORM ? quad_matrix : i4 + 3 < n_matrix, gv[q][3], wf[q].w, wh[3], a1[q].w, a2[q].w, st[q].w, up[3]);
-			*(float4*)(w_fp + i4) = wf[q];
-			*(float4*)(m1 + i4) = a1[q];
-			*(float4*)(m2 + i4) = a2[q];
-			adam_store_steps(steps + i4, st[q]);
+			const bool is_matrix[4] = {QUAD_UNIFORM ? quad_matrix : i4 + 0 < n_matrix, QUAD_UNIFORM ? quad_matrix : i4 + 1 < n_matrix, QUAD_UNIFORM ? quad_matrix : i4 + 2 < n_matrix,
+			                           QUAD_UNIFORM ? quad_matrix : i4 + 3 < n_matrix};
+			const G gq[4] = {gv[q][0], gv[q][1], gv[q][2], gv[q][3]};
+			float w4[4] = {wf[q].x, wf[q].y, wf[q].z, wf[q].w}, f4_[4] = {a1[q].x, a1[q].y, a1[q].z, a1[q].w}, s4[4] = {a2[q].x, a2[q].y, a2[q].z, a2[q].w};
+			uint32_t c4[4] = {st[q].x, st[q].y, st[q].z, st[q].w};
+			adam_four<PLAIN>(a, debias[q], is_matrix, gq, w4, wh, f4_, s4, c4, up);
+			*(float4*)(w_fp + i4) = float4{w4[0], w4[1], w4[2], w4[3]};
+			*(float4*)(m1 + i4) = float4{f4_[0], f4_[1], f4_[2], f4_[3]};
+			*(float4*)(m2 + i4) = float4{s4[0], s4[1], s4[2], s4[3]};
+			adam_store_steps(steps + i4, uint4{c4[0], c4[1], c4[2], c4[3]});
 			if constexpr (sizeof(W) == 2) {
 				if (up[0] && up[1] && up[2] && up[3]) {
 					*(h4*)(w + i4) = h4{wh[0], wh[1], wh[2], wh[3]};
@@ -412,14 +436,7 @@ __global__ void __launch_bounds__(256) k_adam(
 				}
 			}
 		} else if (i4 < n && i4 + 4 > n) { // ragged tail
-			for (size_t i = i4; i < n; ++i) {
-				bool up;
-				W wh;
-				uint32_t st1 = steps[i];
-				adam_one(a, from_table, debias, i < n_matrix, g[i], w_fp[i], wh, m1[i], m2[i], st1, up);
-				steps[i] = (STEP_T)st1;
-				if constexpr (sizeof(W) == 2) { if (up) w[i] = wh; }
-			}
+			for (size_t i = i4; i < n; ++i) adam_single(a, debias_table, i < n_matrix, i, g[i], w_fp, w, m1, m2, steps);
 		}
 	}
 }
@@ -434,14 +451,7 @@ __global__ void __launch_bounds__(256) k_adam_scalar(
 ) {
 	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
-	const float debias = debias_table[a.common_step];
-	const auto from_table = [&](const uint32_t t) { return debias_table[t]; };
-	bool up;
-	W wh;
-	uint32_t st1 = steps[i];
-	adam_one(a, from_table, debias,  i < n_matrix, g[i], w_fp[i], wh, m1[i], m2[i], st1, up);
-	steps[i] = (STEP_T)st1;
-	if constexpr (sizeof(W) == 2) { if (up) w[i] = wh; }
+	adam_single(a, debias_table, i < n_matrix, i, g[i], w_fp, w, m1, m2, steps);
 }
 
 // ---- pcg32 strided uniform fill, random.h:40-55 (N_TO_GENERATE = 4, thread i advances a copy of the rng by 4 i)
@@ -649,6 +659,8 @@ AdamArgs make_adam_args(const AdamHyper& h, float loss_scale, uint32_t current_s
 }
 
 namespace {
+// the PLAIN instantiations' condition (adam_device.h): both tests are of launch constants
+inline bool adam_args_plain(const AdamArgs& a) { return a.inv_loss_scale_exact != 0 && a.weight_clipping_magnitude == 0.0f; }
 __global__ void __launch_bounds__(256) k_adam_widen_steps(const size_t n, const uint16_t* __restrict__ in, uint32_t* __restrict__ out) {
 	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i < n) out[i] = in[i];
@@ -662,8 +674,12 @@ void adam_launch(hipStream_t stream, const AdamArgs& a, size_t n, size_t n_matri
 		return;
 	}
 	const dim3 grid(blocks_for((n + 3) / 4, 256 * ADAM_Q));
-	if (n_matrix % 4 == 0) hipLaunchKernelGGL((k_adam<true, STEP_T, G, W>), grid, dim3(256), 0, stream, a, n, n_matrix, w_fp, w, g, m1, m2, steps, debias_table);
-	else hipLaunchKernelGGL((k_adam<false, STEP_T, G, W>), grid, dim3(256), 0, stream, a, n, n_matrix, w_fp, w, g, m1, m2, steps, debias_table);
+	const bool uniform = n_matrix % 4 == 0;
+	if (adam_args_plain(a)) {
+		if (uniform) hipLaunchKernelGGL((k_adam<true, true, STEP_T, G, W>), grid, dim3(256), 0, stream, a, n, n_matrix, w_fp, w, g, m1, m2, steps, debias_table);
+		else hipLaunchKernelGGL((k_adam<true, false, STEP_T, G, W>), grid, dim3(256), 0, stream, a, n, n_matrix, w_fp, w, g, m1, m2, steps, debias_table);
+	} else if (uniform) hipLaunchKernelGGL((k_adam<false, true, STEP_T, G, W>), grid, dim3(256), 0, stream, a, n, n_matrix, w_fp, w, g, m1, m2, steps, debias_table);
+	else hipLaunchKernelGGL((k_adam<false, false, STEP_T, G, W>), grid, dim3(256), 0, stream, a, n, n_matrix, w_fp, w, g, m1, m2, steps, debias_table);
 }
 template <typename G, typename W>
 void adam_launch_steps(hipStream_t stream, const AdamArgs& a, size_t n, size_t n_matrix, float* w_fp, W* w, const G* g, float* m1, float* m2, void* steps, bool steps16, const float* debias_table) {
@@ -698,23 +714,26 @@ constexpr uint32_t PRO_MAX_BLOCKS_PER_RANGE = 64;
 // workgroups of a shared range: one per 1024 quads, at most 64 (k_grid_scatter_finalize's number)
 __host__ __device__ inline uint32_t pro_range_blocks(const uint32_t n_elems) { return min(PRO_MAX_BLOCKS_PER_RANGE, max(1u, (n_elems / 4 + PRO_THREADS - 1) / PRO_THREADS)); }
 
-template <typename STEP_T, typename DebiasOf>
-__device__ inline void adam_quad(const AdamArgs& a, DebiasOf&& from_table, const float debias, const bool quad_matrix, const size_t i4, const h4 gv,
+template <bool PLAIN, typename STEP_T>
+__device__ inline void adam_quad(const AdamArgs& a, const float* __restrict__ debias_table, const bool quad_matrix, const size_t i4, const h4 gv,
                                  float* __restrict__ w_fp, half_t* __restrict__ w, float* __restrict__ m1, float* __restrict__ m2, STEP_T* __restrict__ steps) {
 	// adam.h:76-79: a grid parameter with a zero gradient is left alone -- nothing else of it is read
 	if (!quad_matrix && gv[0] == (half_t)0.0f && gv[1] == (half_t)0.0f && gv[2] == (half_t)0.0f && gv[3] == (half_t)0.0f) return;
-	float4 wf = *(const float4*)(w_fp + i4), a1 = *(const float4*)(m1 + i4), a2 = *(const float4*)(m2 + i4);
-	uint4 st = adam_load_steps(steps + i4);
+	const uint4 st = adam_load_steps(steps + i4); // first: the debias factors wait for it alone
+	const float4 wf = *(const float4*)(w_fp + i4), a1 = *(const float4*)(m1 + i4), a2 = *(const float4*)(m2 + i4);
+	float debias[4];
+	adam_load_debias(debias_table, a.common_step, st, debias);
 	half_t wh[4];
 	bool up[4];
-	adam_one(a, from_table, debias, quad_matrix, gv[0], wf.x, wh[0], a1.x, a2.x, st.x, up[0]);
-	adam_one(a, from_table, debias, quad_matrix, gv[1], wf.y, wh[1], a1.y, a2.y, st.y, up[1]);
-	adam_one(a, from_table, debias, quad_matrix, gv[2], wf.z, wh[2], a1.z, a2.z, st.z, up[2]);
-	adam_one(a, from_table, debias, quad_matrix, gv[3], wf.w, wh[3], a1.w, a2.w, st.w, up[3]);
-	*(float4*)(w_fp + i4) = wf;
-	*(float4*)(m1 + i4) = a1;
-	*(float4*)(m2 + i4) = a2;
-	adam_store_steps(steps + i4, st);
+	const bool is_matrix[4] = {quad_matrix, quad_matrix, quad_matrix, quad_matrix};
+	const half_t gq[4] = {gv[0], gv[1], gv[2], gv[3]};
+	float w4[4] = {wf.x, wf.y, wf.z, wf.w}, f4_[4] = {a1.x, a1.y, a1.z, a1.w}, s4[4] = {a2.x, a2.y, a2.z, a2.w};
+	uint32_t c4[4] = {st.x, st.y, st.z, st.w};
+	adam_four<PLAIN>(a, debias, is_matrix, gq, w4, wh, f4_, s4, c4, up);
+	*(float4*)(w_fp + i4) = float4{w4[0], w4[1], w4[2], w4[3]};
+	*(float4*)(m1 + i4) = float4{f4_[0], f4_[1], f4_[2], f4_[3]};
+	*(float4*)(m2 + i4) = float4{s4[0], s4[1], s4[2], s4[3]};
+	adam_store_steps(steps + i4, uint4{c4[0], c4[1], c4[2], c4[3]});
 	if (up[0] && up[1] && up[2] && up[3]) {
 		*(h4*)(w + i4) = h4{wh[0], wh[1], wh[2], wh[3]};
 	} else { // skipped parameters keep their half value, whatever it is
@@ -744,12 +763,10 @@ struct PrologueArgs {
 #define TCNN_PRO_Q 1
 #endif
 constexpr int PRO_Q = TCNN_PRO_Q; // quads per thread of the k_adam part, one workgroup width apart
-template <typename STEP_T>
+template <bool PLAIN, typename STEP_T>
 __global__ void TCNN_PRO_BOUNDS k_adam_prologue(const AdamArgs a, const size_t n, const size_t n_matrix, float* __restrict__ w_fp, half_t* __restrict__ w, half_t* __restrict__ g,
                                                                float* __restrict__ m1, float* __restrict__ m2, STEP_T* __restrict__ steps, const float* __restrict__ debias_table, const PrologueArgs p) {
 	__shared__ float part[SLAB_REDUCE_GROUPS * SLAB_REDUCE_ELEMS];
-	const float debias = debias_table[a.common_step];
-	const auto from_table = [&](const uint32_t t) { return debias_table[t]; };
 	const uint32_t tid = threadIdx.x;
 	if (blockIdx.x < p.n_reduce_blocks) {
 		// mlp_reduce_block's sum of element i over the slabs, term for term
@@ -773,12 +790,7 @@ __global__ void TCNN_PRO_BOUNDS k_adam_prologue(const AdamArgs a, const size_t n
 			if (p.reduce_accumulate) s += (float)g[i];
 			const half_t gh = (half_t)s;
 			g[i] = gh;
-			bool up;
-			half_t wh;
-			uint32_t st1 = steps[i];
-			adam_one(a, from_table, debias, i < n_matrix, gh, w_fp[i], wh, m1[i], m2[i], st1, up);
-			steps[i] = (STEP_T)st1;
-			if (up) w[i] = wh;
+			adam_single(a, debias_table, i < n_matrix, i, gh, w_fp, w, m1, m2, steps);
 		}
 		return;
 	}
@@ -805,7 +817,7 @@ __global__ void TCNN_PRO_BOUNDS k_adam_prologue(const AdamArgs a, const size_t n
 			}
 			const h4 gv = h4{fixed_to_half(s[0]), fixed_to_half(s[1]), fixed_to_half(s[2]), fixed_to_half(s[3])};
 			*(h4*)(g + i4) = gv;
-			adam_quad(a, from_table, debias, i4 < n_matrix, i4, gv, w_fp, w, m1, m2, steps);
+			adam_quad<PLAIN>(a, debias_table, i4 < n_matrix, i4, gv, w_fp, w, m1, m2, steps);
 		}
 		return;
 	}
@@ -824,7 +836,7 @@ __global__ void TCNN_PRO_BOUNDS k_adam_prologue(const AdamArgs a, const size_t n
 #pragma unroll
 	for (int k = 0; k < PRO_Q; ++k) {
 		const size_t i4 = p.bulk_begin + (((size_t)(b - p.n_range_blocks) * PRO_Q + k) * PRO_THREADS + tid) * 4;
-		if (live[k]) adam_quad(a, from_table, debias, i4 < n_matrix, i4, gv[k], w_fp, w, m1, m2, steps);
+		if (live[k]) adam_quad<PLAIN>(a, debias_table, i4 < n_matrix, i4, gv[k], w_fp, w, m1, m2, steps);
 	}
 }
 } // namespace
@@ -870,8 +882,11 @@ bool adam_step_with_prologue(hipStream_t stream, const AdamHyper& h, size_t n, s
 	const AdamArgs a = make_adam_args(h, loss_scale, current_step);
 	const uint32_t bulk_blocks = div_round_up((uint32_t)((n - p.bulk_begin) / 4), PRO_THREADS * (uint32_t)PRO_Q);
 	const dim3 grid(p.n_reduce_blocks + p.n_range_blocks + bulk_blocks);
-	if (steps16) hipLaunchKernelGGL(k_adam_prologue<uint16_t>, grid, dim3(PRO_THREADS), 0, stream, a, n, n_matrix, w_fp, (half_t*)w_half, (half_t*)g_half, m1, m2, (uint16_t*)steps, debias_table, p);
-	else hipLaunchKernelGGL(k_adam_prologue<uint32_t>, grid, dim3(PRO_THREADS), 0, stream, a, n, n_matrix, w_fp, (half_t*)w_half, (half_t*)g_half, m1, m2, (uint32_t*)steps, debias_table, p);
+	if (adam_args_plain(a)) {
+		if (steps16) hipLaunchKernelGGL((k_adam_prologue<true, uint16_t>), grid, dim3(PRO_THREADS), 0, stream, a, n, n_matrix, w_fp, (half_t*)w_half, (half_t*)g_half, m1, m2, (uint16_t*)steps, debias_table, p);
+		else hipLaunchKernelGGL((k_adam_prologue<true, uint32_t>), grid, dim3(PRO_THREADS), 0, stream, a, n, n_matrix, w_fp, (half_t*)w_half, (half_t*)g_half, m1, m2, (uint32_t*)steps, debias_table, p);
+	} else if (steps16) hipLaunchKernelGGL((k_adam_prologue<false, uint16_t>), grid, dim3(PRO_THREADS), 0, stream, a, n, n_matrix, w_fp, (half_t*)w_half, (half_t*)g_half, m1, m2, (uint16_t*)steps, debias_table, p);
+	else hipLaunchKernelGGL((k_adam_prologue<false, uint32_t>), grid, dim3(PRO_THREADS), 0, stream, a, n, n_matrix, w_fp, (half_t*)w_half, (half_t*)g_half, m1, m2, (uint32_t*)steps, debias_table, p);
 	HIP_CHECK_THROW(hipGetLastError());
 	return true;
 }
@@ -879,6 +894,102 @@ bool adam_step_with_prologue(hipStream_t stream, const AdamHyper& h, size_t n, s
 void adam_fill_debias_table(hipStream_t stream, float beta1, float beta2, uint32_t from, uint32_t to, float* table) {
 	if (to <= from) return;
 	hipLaunchKernelGGL(k_adam_debias_table, dim3(blocks_for(to - from, 256)), dim3(256), 0, stream, beta1, beta2, from, to, table);
+}
+
+// ---- the math sweep (adam_math_sweep, tcnn_common.h): adam_device.h's guarded square root and division against the plain expressions
+namespace {
+__device__ inline uint32_t sweep_hash(const uint32_t v) { // pcg output function on a counter
+	const uint32_t s = v * 747796405u + 2891336453u;
+	const uint32_t w = ((s >> ((s >> 28u) + 4u)) ^ s) * 277803737u;
+	return (w >> 22u) ^ w;
+}
+__device__ inline void sweep_report(const unsigned long long bad, const unsigned long long first_bad, unsigned long long* __restrict__ out) {
+	if (bad) {
+		atomicAdd(out, bad);
+		atomicMin(out + 1, first_bad);
+	}
+}
+// every bit pattern in [first, first + count)
+__global__ void __launch_bounds__(256) k_adam_sweep_sqrt(const uint64_t first, const uint64_t count, unsigned long long* __restrict__ out) {
+	unsigned long long bad = 0, first_bad = ~0ull;
+	for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (uint64_t)gridDim.x * 256) {
+		const uint32_t b = (uint32_t)(first + i);
+		const float x = __uint_as_float(b);
+		if (__float_as_uint(adam_sqrt(x)) != __float_as_uint(sqrtf(x))) {
+			++bad;
+			first_bad = min(first_bad, (unsigned long long)b);
+		}
+	}
+	sweep_report(bad, first_bad, out);
+}
+// every denominator pattern in [first, first + count) against n_numerators numerators whose patterns step evenly from lo_bits to hi_bits
+// (the same for every denominator: evenly spread over the binades in between), their low 16 bits hashed
+__global__ void __launch_bounds__(256) k_adam_sweep_div_grid(const uint64_t first, const uint64_t count, const uint32_t n_numerators, const uint32_t lo_bits, const uint32_t hi_bits,
+                                                             const uint32_t seed, unsigned long long* __restrict__ out) {
+	unsigned long long bad = 0, first_bad = ~0ull;
+	for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (uint64_t)gridDim.x * 256) {
+		const uint32_t db = (uint32_t)(first + i);
+		const float d = __uint_as_float(db);
+		const uint32_t pitch = (hi_bits - lo_bits) / n_numerators;
+		// A denominator outside adam_div's range makes adam_div(n, d) the expression `n / d` itself for every n: comparing that with `n / d`
+		// a thousand times is 2 s of divisions that cannot differ.  Such a denominator is visited with the first numerator only.
+		const uint32_t n_here = adam_div_d_in_range(d) ? n_numerators : 1u;
+		uint32_t lowest = 0xffffffffu;
+		for (uint32_t k = 0; k < n_here; ++k) {
+			const uint32_t nb = (lo_bits + pitch * k) ^ (sweep_hash(k ^ seed) & 0xffffu);
+			const float n = __uint_as_float(nb);
+			const bool differs = __float_as_uint(adam_div(n, d)) != __float_as_uint(n / d);
+			bad += differs ? 1u : 0u;
+			lowest = min(lowest, differs ? nb : 0xffffffffu);
+		}
+		if (lowest != 0xffffffffu) first_bad = min(first_bad, (unsigned long long)db << 32 | lowest);
+	}
+	sweep_report(bad, first_bad, out);
+}
+// `count` seeded pairs around the guard's edges: numerators of 2^-70 .. 2^70, denominators of 2^-54 .. 2^24, a quarter of each negative
+__global__ void __launch_bounds__(256) k_adam_sweep_div_pairs(const uint64_t count, const uint32_t seed, unsigned long long* __restrict__ out) {
+	unsigned long long bad = 0, first_bad = ~0ull;
+	for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (uint64_t)gridDim.x * 256) {
+		const uint32_t h1 = sweep_hash((uint32_t)(2 * i) ^ seed), h2 = sweep_hash((uint32_t)(2 * i + 1) ^ seed), h3 = sweep_hash(h1 ^ h2);
+		const uint32_t nb = ((127u - 70u + (((h1 >> 23) & 0xffu) * 140u >> 8)) << 23) | (h1 & 0x7fffffu) | ((h3 & 3u) == 0 ? 0x80000000u : 0u);
+		const uint32_t db = ((127u - 54u + (((h2 >> 23) & 0xffu) * 78u >> 8)) << 23) | (h2 & 0x7fffffu) | ((h3 & 12u) == 0 ? 0x80000000u : 0u);
+		const float n = __uint_as_float(nb), d = __uint_as_float(db);
+		if (__float_as_uint(adam_div(n, d)) != __float_as_uint(n / d)) {
+			++bad;
+			first_bad = min(first_bad, (unsigned long long)db << 32 | nb);
+		}
+	}
+	sweep_report(bad, first_bad, out);
+}
+} // namespace
+
+void adam_math_sweep(hipStream_t stream, int what, uint64_t first, uint64_t count, uint32_t n_numerators, float numerator_lo, float numerator_hi, uint64_t seed, uint64_t* mismatches,
+                     uint64_t* first_bad) {
+	CHECK_THROW(what >= 0 && what <= 2 && mismatches != nullptr && first_bad != nullptr);
+	CHECK_THROW(what == 2 || first + count <= (1ull << 32));
+	uint32_t lo_bits = 0, hi_bits = 0;
+	if (what == 1) {
+		CHECK_THROW(n_numerators > 0 && numerator_lo > 0.0f && numerator_hi >= numerator_lo && std::isfinite(numerator_hi));
+		std::memcpy(&lo_bits, &numerator_lo, 4);
+		std::memcpy(&hi_bits, &numerator_hi, 4);
+	}
+	unsigned long long host[2] = {0ull, ~0ull};
+	unsigned long long* out = nullptr;
+	HIP_CHECK_THROW(hipMalloc((void**)&out, sizeof(host)));
+	hipError_t err = hipMemcpyAsync(out, host, sizeof(host), hipMemcpyHostToDevice, stream);
+	if (err == hipSuccess && count) {
+		const dim3 grid((uint32_t)std::min<uint64_t>((count + 255) / 256, 8192));
+		if (what == 0) hipLaunchKernelGGL(k_adam_sweep_sqrt, grid, dim3(256), 0, stream, first, count, out);
+		else if (what == 1) hipLaunchKernelGGL(k_adam_sweep_div_grid, grid, dim3(256), 0, stream, first, count, n_numerators, lo_bits, hi_bits, (uint32_t)seed, out);
+		else hipLaunchKernelGGL(k_adam_sweep_div_pairs, grid, dim3(256), 0, stream, count, (uint32_t)seed, out);
+		err = hipGetLastError();
+	}
+	if (err == hipSuccess) err = hipMemcpyAsync(host, out, sizeof(host), hipMemcpyDeviceToHost, stream);
+	if (err == hipSuccess) err = hipStreamSynchronize(stream);
+	(void)hipFree(out);
+	HIP_CHECK_THROW(err);
+	*mismatches = host[0];
+	*first_bad = host[1];
 }
 
 namespace {

@@ -707,7 +707,7 @@ __global__ void __launch_bounds__(WR_ELEMS * WR_GROUPS) k_wgrad_reduce_adam(cons
 	half_t w_h;
 	bool updated;
 	const float* __restrict__ table = adam.debias_table;
-	adam_one(adam.args, [&](const uint32_t t) { return table[t]; }, table[adam.args.common_step], /*is_matrix=*/true, g, w_fp, w_h, m1, m2, step, updated);
+	adam_one(adam.args, table[min(step + 1, adam.args.common_step)], /*is_matrix=*/true, g, w_fp, w_h, m1, m2, step, updated);
 	if (updated) {
 		adam.w_fp[i] = w_fp;
 		((half_t*)adam.w_half)[i] = w_h;

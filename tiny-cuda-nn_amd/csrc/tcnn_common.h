@@ -827,6 +827,11 @@ void adam_step(hipStream_t stream, const AdamHyper& h, size_t n, size_t n_matrix
 void adam_widen_steps(hipStream_t stream, size_t n, const void* steps16, void* steps32); // uint16 -> uint32
 // debias_table[t] = sqrtf(1 - powf(beta2, t)) / (1 - powf(beta1, t)) (adam.h:97-98), evaluated on the device, for t in [from, to)
 void adam_fill_debias_table(hipStream_t stream, float beta1, float beta2, uint32_t from, uint32_t to, float* table);
+// Test hook (tcnn_adam_math_sweep, tcnn_amd.h): adam_device.h's guarded square root and division against sqrtf and `/`, compared bit for
+// bit on the device; nothing is stored per element.  Synchronises.  mismatches: their number; first_bad: the smallest offending input
+// (the square root's operand; denominator << 32 | numerator), ~0 if none.
+void adam_math_sweep(hipStream_t stream, int what, uint64_t first, uint64_t count, uint32_t n_numerators, float numerator_lo, float numerator_hi, uint64_t seed, uint64_t* mismatches,
+                     uint64_t* first_bad);
 // dst[i][dst_col + j] = src[i][src_col + j] for j < width; elements of 2 or 4 bytes (Composite encoding)
 void copy_columns(hipStream_t stream, size_t elem_bytes, uint32_t n, const void* src, uint32_t src_stride, uint32_t src_col, void* dst, uint32_t dst_stride, uint32_t dst_col, uint32_t width);
 // optimizers/sgd.h:44-72 and optimizers/ema.h:44-78 (half parameters; gradients in `precision`, here and below)

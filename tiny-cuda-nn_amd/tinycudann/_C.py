@@ -162,6 +162,7 @@ _SIGNATURES = {
     "tcnn_optimizer_weights_restored": (_int, [_vp, _vp, _vp]),
     "tcnn_optimizer_serialize": (_int, [_vp, _pp, C.POINTER(_sz)]),
     "tcnn_optimizer_deserialize": (_int, [_vp, _vp, _sz]),
+    "tcnn_adam_math_sweep": (_int, [_vp, _int, C.c_uint64, C.c_uint64, _u32, _f32, _f32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "tcnn_loss_type": (_int, [_cp, C.POINTER(C.c_int)]),
     "tcnn_loss_name": (_cp, [_int]),
     "tcnn_loss_evaluate": (_int, [_int, _vp, _f32, _vp, _u32, _u32, _vp, _u32, _int, _vp, _vp, _vp, _u32, _vp, _u32, _vp]),
