@@ -371,9 +371,8 @@ public:
 		m_meta.hash_type = (uint32_t)hash_type;
 		m_meta.interpolation = (uint32_t)string_to_interpolation_type(enc.value("interpolation", "Linear"));
 		static const uint32_t prime[7] = {1958374283u, 2654435761u, 805459861u, 3674653429u, 2097192037u, 1434869437u, 2165219737u};
-		static const uint32_t coherent[7] = {1u, 2654435761u, 805459861u, 3674653429u, 2097192037u, 1434869437u, 2165219737u};
 		static const uint32_t reversed[7] = {2165219737u, 1434869437u, 2097192037u, 3674653429u, 805459861u, 2654435761u, 1958374283u};
-		const uint32_t* primes = hash_type == HashType::Prime ? prime : (hash_type == HashType::ReversedPrime ? reversed : coherent);
+		const uint32_t* primes = hash_type == HashType::Prime ? prime : (hash_type == HashType::ReversedPrime ? reversed : GRID_COHERENT_PRIMES);
 		for (uint32_t d = 0; d < GRID_MAX_DIMS; ++d) m_meta.primes[d] = primes[d]; // common_device.h:645-661
 
 		const float log2_scale = std::log2(per_level_scale); // float overload (grid.h:694)
@@ -1076,6 +1075,76 @@ private:
 	std::map<const void*, std::unique_ptr<DeviceBuf>> m_scratch;
 };
 
+// "PermutoGrid" / "Permutohedral" (k_permuto.hip): the hash grid's levels, tables and hash, interpolated on the simplices of a
+// permutohedral lattice -- D + 1 vertices per level where a grid cell has 2^D corners.  Not in the reference; the keys keep the grid's
+// names and defaults.  First order only: no second-order pass, no tangent, no max_level.
+class PermutoEncoding : public Encoding {
+public:
+	PermutoEncoding(uint32_t n_dims_to_encode, const Json& enc, bool fp32) : Encoding{fp32} {
+		m_shape.n_dims = n_dims_to_encode;
+		m_shape.n_levels = enc.value("n_levels", 16u);
+		m_shape.n_features_per_level = enc.value("n_features_per_level", 2u);
+		m_shape.log2_hashmap_size = enc.value("log2_hashmap_size", 19u);
+		memset(&m_shape.scales, 0, sizeof(m_shape.scales));
+		m_base_resolution = enc.value("base_resolution", 16u);
+		m_per_level_scale = enc.value("per_level_scale", 2.0f);
+		const uint32_t F = m_shape.n_features_per_level;
+		const std::string hash = enc.value("hash", "CoherentPrime");
+		if (n_dims_to_encode < 2 || n_dims_to_encode > GRID_MAX_DIMS) throw std::runtime_error{"PermutoGrid: n_dims_to_encode must be 2 to 7, not " + std::to_string(n_dims_to_encode)};
+		if (F != 1 && F != 2 && F != 4 && F != 8) throw std::runtime_error{"PermutoGrid: n_features_per_level must be 1, 2, 4 or 8, not " + std::to_string(F)};
+		if (!equals_case_insensitive(hash, "CoherentPrime")) throw std::runtime_error{"PermutoGrid: hash must be CoherentPrime, not " + hash};
+		if (m_shape.n_levels < 1 || m_shape.n_levels > MAX_N_LEVELS) throw std::runtime_error{"PermutoGrid: n_levels must be 1 to " + std::to_string(MAX_N_LEVELS) + ", not " + std::to_string(m_shape.n_levels)};
+		if (m_shape.log2_hashmap_size < 1 || m_shape.log2_hashmap_size > 28) throw std::runtime_error{"PermutoGrid: log2_hashmap_size must be 1 to 28, not " + std::to_string(m_shape.log2_hashmap_size)};
+		if (m_base_resolution < 1) throw std::runtime_error{"PermutoGrid: base_resolution must be at least 1"};
+		if (!(m_per_level_scale > 0.0f) || !std::isfinite(m_per_level_scale)) throw std::runtime_error{"PermutoGrid: per_level_scale must be positive and finite"};
+		m_n_params = ((size_t)m_shape.n_levels << m_shape.log2_hashmap_size) * F;
+		const float log2_scale = std::log2(m_per_level_scale);
+		for (uint32_t l = 0; l < m_shape.n_levels; ++l) m_shape.scales.v[l] = exp2f(l * log2_scale) * m_base_resolution; // the grid's scale without its - 1
+	}
+	uint32_t input_width() const override { return m_shape.n_dims; }
+	uint32_t output_width() const override { return m_shape.n_levels * m_shape.n_features_per_level; }
+	uint32_t required_output_alignment() const override { return m_shape.n_features_per_level; }
+	size_t n_params() const override { return m_n_params; }
+	void initialize_params(Pcg32& rng, float* params_full_precision, float scale) override { // as the grid's
+		generate_random_uniform(nullptr, rng.st, n_params(), params_full_precision, -1e-4f * scale, 1e-4f * scale);
+	}
+	EncodingContext forward(hipStream_t stream, uint32_t n, MatView x, const void* params, void* out, bool prepare_input_gradients, bool prepare_param_gradients, const ForwardPlan* plan) override {
+		if (out && padded_output_width() > 0 && n > 0) permuto_forward(stream, m_shape, m_fp32, n, x, params, out, padded_output_width());
+		return {}; // the backward pass recomputes the lattice coordinates from x
+	}
+	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, const GridBackwardRoute&, BackwardHandoff*) override {
+		if (dL_dx) permuto_backward_input(stream, m_shape, m_fp32, n, x, params, dL_dy, padded_output_width(), *dL_dx);
+		if (mode == GradientMode::Ignore) return;
+		CHECK_THROW(grads != nullptr);
+		permuto_backward(stream, m_shape, m_fp32, n, x, dL_dy, padded_output_width(), m_fp32 ? nullptr : scratch_for(stream), grads, mode == GradientMode::Accumulate);
+	}
+	Json hyperparams() const override {
+		Json j = Json::object();
+		j["otype"] = "PermutoGrid";
+		j["n_levels"] = m_shape.n_levels;
+		j["n_features_per_level"] = m_shape.n_features_per_level;
+		j["log2_hashmap_size"] = m_shape.log2_hashmap_size;
+		j["base_resolution"] = m_base_resolution;
+		j["per_level_scale"] = m_per_level_scale;
+		j["hash"] = "CoherentPrime";
+		return j;
+	}
+private:
+	uint64_t* scratch_for(hipStream_t stream) { // per stream: zero between passes (k_permuto_finalize)
+		std::unique_ptr<DeviceBuf>& scratch = m_scratch[(const void*)stream];
+		if (!scratch) {
+			scratch = std::make_unique<DeviceBuf>(m_n_params * sizeof(uint64_t));
+			scratch->memset(0);
+		}
+		return scratch->as<uint64_t>();
+	}
+	PermutoShape m_shape;
+	uint32_t m_base_resolution;
+	float m_per_level_scale;
+	size_t m_n_params;
+	std::map<const void*, std::unique_ptr<DeviceBuf>> m_scratch;
+};
+
 class IdentityEncoding : public Encoding {
 public:
 	IdentityEncoding(uint32_t n_dims_to_encode, float scale, float offset, bool fp32) : Encoding{fp32}, m_n_dims{n_dims_to_encode}, m_scale{scale}, m_offset{offset} {}
@@ -1576,6 +1645,8 @@ inline std::unique_ptr<Encoding> create_encoding(uint32_t n_dims_to_encode, cons
 		result.reset(new EmptyEncoding{n_dims_to_encode, fp32});
 	} else if (name == "ppng1" || name == "ppng2" || name == "ppng3") {
 		result.reset(new PpngEncoding{(uint32_t)(name.back() - '0'), n_dims_to_encode, enc, fp32});
+	} else if (name == "permutogrid" || name == "permutohedral") {
+		result.reset(new PermutoEncoding{n_dims_to_encode, enc, fp32});
 	} else if (name == "frequency") {
 		result.reset(new PeriodicEncoding{false, enc.value("n_frequencies", 12u), n_dims_to_encode, fp32});
 	} else if (name == "trianglewave") {
@@ -1604,7 +1675,7 @@ inline std::unique_ptr<Encoding> create_encoding(uint32_t n_dims_to_encode, cons
 		composite["nested"] = nested;
 		result.reset(new CompositeEncoding{n_dims_to_encode, composite, fp32});
 	} else {
-		throw std::runtime_error{"Encoding '" + enc.value("otype", "OneBlob") + "' not found (this build provides Grid/HashGrid/TiledGrid/DenseGrid, OneBlob, Identity, Empty, Frequency, TriangleWave, SphericalHarmonics, Composite, PPNG1, PPNG2)"};
+		throw std::runtime_error{"Encoding '" + enc.value("otype", "OneBlob") + "' not found (this build provides Grid/HashGrid/TiledGrid/DenseGrid, OneBlob, Identity, Empty, Frequency, TriangleWave, SphericalHarmonics, Composite, PPNG1, PPNG2, PermutoGrid)"};
 	}
 	if (alignment > 0) result->set_alignment(alignment);
 	return result;

@@ -115,6 +115,8 @@ inline uint32_t next_multiple(uint32_t v, uint32_t d) { return div_round_up(v, d
 // SURVEY 7 "hard parts"); the encoding keeps one device copy (6 KiB, too large for the kernarg segment).
 // ------------------------------------------------------------------------------------------------------------------
 constexpr uint32_t GRID_MAX_DIMS = 7; // dimensions a grid encodes: the hash has seven primes (common_device.h:633)
+// HashType::CoherentPrime (common_device.h:645-661): the one definition GridEncoding and k_permuto.hip read
+constexpr uint32_t GRID_COHERENT_PRIMES[GRID_MAX_DIMS] = {1u, 2654435761u, 805459861u, 3674653429u, 2097192037u, 1434869437u, 2165219737u};
 struct GridLevel {
 	uint32_t offset;      // first entry of the level (in entries, grid.h:714)
 	uint32_t size;        // hashmap_size = entries in the level
@@ -445,6 +447,19 @@ void ppng3_backward_input(hipStream_t stream, bool fp32_dy, uint32_t n, uint32_t
 // second order (ppng_3.h:609-676): grad (nullable; scratch as above), dL_ddLdy (nullable, [n][dy_stride]) and dL_dx (nullable, written)
 void ppng3_backward_backward_input(hipStream_t stream, bool fp32_dy, uint32_t n, uint32_t F, uint32_t Q, uint32_t C, int32_t log2_min_freq, int32_t log2_max_freq, MatView x, MatView dL_ddLdx,
                                    const void* features, const void* dL_dy, uint32_t dy_stride, uint64_t* scratch, void* grad, bool accumulate, void* dL_ddLdy, MatViewMut* dL_dx);
+
+// ---- PermutoGrid (k_permuto.hip): linear interpolation on the simplices of a permutohedral lattice, D + 1 hashed vertices per level.
+// params / grad T [n_levels][2^log2_hashmap_size][F] (T = float if fp32 else half, as out and dL_dy: AoS rows of out_stride / dy_stride);
+// scales: one float per level, passed to the kernels by value (no upload, nothing to break a stream capture).  out columns behind n_levels * F are written as ones.  dL_dx is written (not accumulated).
+// permuto_backward, half: scratch uint64[n_params], zero on entry and zero again on return (exact sums of the fp16 products, rounded once);
+// fp32: float atomics straight into grad (their order is not fixed), scratch unused.
+struct PermutoShape {
+	uint32_t n_dims, n_levels, n_features_per_level, log2_hashmap_size;
+	struct Scales { float v[MAX_N_LEVELS]; } scales;
+};
+void permuto_forward(hipStream_t stream, const PermutoShape& p, bool fp32, uint32_t n, MatView x, const void* params, void* out, uint32_t out_stride);
+void permuto_backward_input(hipStream_t stream, const PermutoShape& p, bool fp32, uint32_t n, MatView x, const void* params, const void* dL_dy, uint32_t dy_stride, MatViewMut dL_dx);
+void permuto_backward(hipStream_t stream, const PermutoShape& p, bool fp32, uint32_t n, MatView x, const void* dL_dy, uint32_t dy_stride, uint64_t* scratch, void* grad, bool accumulate);
 
 // ---- binned form for levels cut into more than 64 chunks (k_grid_bin.hip; GridLevel::scatter_binned): no filter, no gathers.
 // Same exact result as grid_backward_lds; writes every gradient element of the binned levels.  workspace: grid_bin_workspace_bytes().
