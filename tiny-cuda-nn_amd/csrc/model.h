@@ -1145,6 +1145,93 @@ private:
 	std::map<const void*, std::unique_ptr<DeviceBuf>> m_scratch;
 };
 
+// "KPlanes" (k_kplanes.hip): per level the D (D - 1) / 2 dense 2-D feature grids over the axis pairs of a 2- to 4-D input, multiplied
+// ("Product": K-Planes, HexPlane) or summed ("Sum": tri-planes) per feature.  Not in the reference; levels, scales and resolutions are the
+// dense grid's, and with one plane (D = 2) so are the parameter layout and, in fp32, the output's bits.  First order only: no
+// second-order pass, no tangent, no max_level.
+// Initialisation: Sum draws the grid's uniform +-1e-4 * scale; Product draws uniform [0.1, 0.5), the range of the K-Planes paper -- a
+// product of K values of 1e-4 is zero in half, and so is every gradient that passes through it: nothing would ever train.
+class KPlanesEncoding : public Encoding {
+public:
+	KPlanesEncoding(uint32_t n_dims_to_encode, const Json& enc, bool fp32) : Encoding{fp32} {
+		memset(&m_shape, 0, sizeof(m_shape));
+		m_shape.n_dims = n_dims_to_encode;
+		m_shape.n_levels = enc.value("n_levels", 4u);
+		m_shape.n_features_per_level = enc.value("n_features_per_level", 2u);
+		m_base_resolution = enc.value("base_resolution", 64u);
+		m_per_level_scale = enc.value("per_level_scale", 2.0f);
+		const std::string reduction = enc.value("reduction", "Product");
+		const uint32_t F = m_shape.n_features_per_level, K = n_dims_to_encode * (n_dims_to_encode - 1) / 2;
+		if (n_dims_to_encode < 2 || n_dims_to_encode > 4) throw std::runtime_error{"KPlanes: n_dims_to_encode must be 2 to 4, not " + std::to_string(n_dims_to_encode)};
+		if (F != 1 && F != 2 && F != 4 && F != 8) throw std::runtime_error{"KPlanes: n_features_per_level must be 1, 2, 4 or 8, not " + std::to_string(F)};
+		if (!equals_case_insensitive(reduction, "Product") && !equals_case_insensitive(reduction, "Sum")) throw std::runtime_error{"KPlanes: reduction must be Product or Sum, not " + reduction};
+		if (m_shape.n_levels < 1 || m_shape.n_levels > MAX_N_LEVELS) throw std::runtime_error{"KPlanes: n_levels must be 1 to " + std::to_string(MAX_N_LEVELS) + ", not " + std::to_string(m_shape.n_levels)};
+		if (m_base_resolution < 1) throw std::runtime_error{"KPlanes: base_resolution must be at least 1"};
+		if (!(m_per_level_scale > 0.0f) || !std::isfinite(m_per_level_scale)) throw std::runtime_error{"KPlanes: per_level_scale must be positive and finite"};
+		m_shape.product = equals_case_insensitive(reduction, "Product") ? 1u : 0u;
+		const float log2_scale = std::log2(m_per_level_scale);
+		uint64_t offset = 0;
+		for (uint32_t l = 0; l < m_shape.n_levels; ++l) { // scale and resolution: GridEncoding's
+			const float scale = exp2f(l * log2_scale) * m_base_resolution - 1.0f;
+			const float resolution = ceilf(scale) + 1.0f;
+			// the grid caps a level at half the uint32 range and hashes beyond it; a plane cannot, and all planes are addressed in uint32 entries
+			if (!(resolution >= 1.0f) || resolution * resolution > (float)(std::numeric_limits<uint32_t>::max() / 2)) {
+				throw std::runtime_error{"KPlanes: base_resolution and per_level_scale give level " + std::to_string(l) + " a resolution of " + std::to_string(resolution) + ": its planes do not fit 2^31 entries"};
+			}
+			const uint32_t R = (uint32_t)resolution, entries = next_multiple(R * R, 8u);
+			m_shape.levels.scale[l] = scale;
+			m_shape.levels.resolution[l] = R;
+			m_shape.levels.entries[l] = entries;
+			m_shape.levels.offset[l] = (uint32_t)offset;
+			offset += (uint64_t)K * entries;
+			if (offset * F > std::numeric_limits<uint32_t>::max()) throw std::runtime_error{"KPlanes: n_levels, base_resolution and per_level_scale give more than 2^32 parameters"};
+		}
+		m_n_params = (size_t)offset * F;
+	}
+	uint32_t input_width() const override { return m_shape.n_dims; }
+	uint32_t output_width() const override { return m_shape.n_levels * m_shape.n_features_per_level; }
+	uint32_t required_output_alignment() const override { return m_shape.n_features_per_level; }
+	size_t n_params() const override { return m_n_params; }
+	void initialize_params(Pcg32& rng, float* params_full_precision, float scale) override { // (see the class comment)
+		if (m_shape.product) generate_random_uniform(nullptr, rng.st, n_params(), params_full_precision, 0.1f, 0.5f);
+		else generate_random_uniform(nullptr, rng.st, n_params(), params_full_precision, -1e-4f * scale, 1e-4f * scale);
+	}
+	EncodingContext forward(hipStream_t stream, uint32_t n, MatView x, const void* params, void* out, bool prepare_input_gradients, bool prepare_param_gradients, const ForwardPlan* plan) override {
+		if (out && padded_output_width() > 0 && n > 0) kplanes_forward(stream, m_shape, m_fp32, n, x, params, out, padded_output_width());
+		return {}; // the backward pass recomputes cells and plane values from x
+	}
+	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, const GridBackwardRoute&, BackwardHandoff*) override {
+		if (dL_dx) kplanes_backward_input(stream, m_shape, m_fp32, n, x, params, dL_dy, padded_output_width(), *dL_dx);
+		if (mode == GradientMode::Ignore) return;
+		CHECK_THROW(grads != nullptr);
+		kplanes_backward(stream, m_shape, m_fp32, n, x, params, dL_dy, padded_output_width(), m_fp32 ? nullptr : scratch_for(stream), grads, mode == GradientMode::Accumulate);
+	}
+	Json hyperparams() const override {
+		Json j = Json::object();
+		j["otype"] = "KPlanes";
+		j["n_levels"] = m_shape.n_levels;
+		j["n_features_per_level"] = m_shape.n_features_per_level;
+		j["base_resolution"] = m_base_resolution;
+		j["per_level_scale"] = m_per_level_scale;
+		j["reduction"] = m_shape.product ? "Product" : "Sum";
+		return j;
+	}
+private:
+	uint64_t* scratch_for(hipStream_t stream) { // per stream: zero between passes (k_kplanes_finalize)
+		std::unique_ptr<DeviceBuf>& scratch = m_scratch[(const void*)stream];
+		if (!scratch) {
+			scratch = std::make_unique<DeviceBuf>(m_n_params * sizeof(uint64_t));
+			scratch->memset(0);
+		}
+		return scratch->as<uint64_t>();
+	}
+	KPlanesShape m_shape;
+	uint32_t m_base_resolution;
+	float m_per_level_scale;
+	size_t m_n_params;
+	std::map<const void*, std::unique_ptr<DeviceBuf>> m_scratch;
+};
+
 class IdentityEncoding : public Encoding {
 public:
 	IdentityEncoding(uint32_t n_dims_to_encode, float scale, float offset, bool fp32) : Encoding{fp32}, m_n_dims{n_dims_to_encode}, m_scale{scale}, m_offset{offset} {}
@@ -1647,6 +1734,8 @@ inline std::unique_ptr<Encoding> create_encoding(uint32_t n_dims_to_encode, cons
 		result.reset(new PpngEncoding{(uint32_t)(name.back() - '0'), n_dims_to_encode, enc, fp32});
 	} else if (name == "permutogrid" || name == "permutohedral") {
 		result.reset(new PermutoEncoding{n_dims_to_encode, enc, fp32});
+	} else if (name == "kplanes") {
+		result.reset(new KPlanesEncoding{n_dims_to_encode, enc, fp32});
 	} else if (name == "frequency") {
 		result.reset(new PeriodicEncoding{false, enc.value("n_frequencies", 12u), n_dims_to_encode, fp32});
 	} else if (name == "trianglewave") {
@@ -1675,7 +1764,7 @@ inline std::unique_ptr<Encoding> create_encoding(uint32_t n_dims_to_encode, cons
 		composite["nested"] = nested;
 		result.reset(new CompositeEncoding{n_dims_to_encode, composite, fp32});
 	} else {
-		throw std::runtime_error{"Encoding '" + enc.value("otype", "OneBlob") + "' not found (this build provides Grid/HashGrid/TiledGrid/DenseGrid, OneBlob, Identity, Empty, Frequency, TriangleWave, SphericalHarmonics, Composite, PPNG1, PPNG2, PermutoGrid)"};
+		throw std::runtime_error{"Encoding '" + enc.value("otype", "OneBlob") + "' not found (this build provides Grid/HashGrid/TiledGrid/DenseGrid, OneBlob, Identity, Empty, Frequency, TriangleWave, SphericalHarmonics, Composite, PPNG1, PPNG2, PermutoGrid, KPlanes)"};
 	}
 	if (alignment > 0) result->set_alignment(alignment);
 	return result;

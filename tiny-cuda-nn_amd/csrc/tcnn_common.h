@@ -461,6 +461,20 @@ void permuto_forward(hipStream_t stream, const PermutoShape& p, bool fp32, uint3
 void permuto_backward_input(hipStream_t stream, const PermutoShape& p, bool fp32, uint32_t n, MatView x, const void* params, const void* dL_dy, uint32_t dy_stride, MatViewMut dL_dx);
 void permuto_backward(hipStream_t stream, const PermutoShape& p, bool fp32, uint32_t n, MatView x, const void* dL_dy, uint32_t dy_stride, uint64_t* scratch, void* grad, bool accumulate);
 
+// ---- KPlanes (k_kplanes.hip): per level the K = D (D - 1) / 2 dense 2-D feature grids over the axis pairs (a, b), a < b, in lexicographic
+// order; each is a 2-D DenseGrid level with Linear interpolation whose fp32 value P_k[f] is kept unrounded, and the K values are multiplied
+// (product != 0) or summed left to right in fp32 and rounded to T once.  params / grad T [n_levels][K][entries][F], entries =
+// next_multiple(resolution^2, 8); offset: a level's first entry (all K planes), in entries.  The level table travels by value (2 KiB of the
+// kernel arguments: no upload).  out / dL_dy / dL_dx / scratch as for PermutoGrid above; kplanes_backward reads params only when product != 0.
+struct KPlanesShape {
+	uint32_t n_dims, n_levels, n_features_per_level, product;
+	struct Levels { float scale[MAX_N_LEVELS]; uint32_t resolution[MAX_N_LEVELS], entries[MAX_N_LEVELS], offset[MAX_N_LEVELS]; } levels;
+};
+void kplanes_forward(hipStream_t stream, const KPlanesShape& p, bool fp32, uint32_t n, MatView x, const void* params, void* out, uint32_t out_stride);
+void kplanes_backward_input(hipStream_t stream, const KPlanesShape& p, bool fp32, uint32_t n, MatView x, const void* params, const void* dL_dy, uint32_t dy_stride, MatViewMut dL_dx);
+void kplanes_backward(hipStream_t stream, const KPlanesShape& p, bool fp32, uint32_t n, MatView x, const void* params, const void* dL_dy, uint32_t dy_stride, uint64_t* scratch, void* grad,
+                      bool accumulate);
+
 // ---- binned form for levels cut into more than 64 chunks (k_grid_bin.hip; GridLevel::scatter_binned): no filter, no gathers.
 // Same exact result as grid_backward_lds; writes every gradient element of the binned levels.  workspace: grid_bin_workspace_bytes().
 bool grid_bin_supported(const GridMeta& meta); // F in {2, 4}
