@@ -1147,8 +1147,8 @@ private:
 
 // "KPlanes" (k_kplanes.hip): per level the D (D - 1) / 2 dense 2-D feature grids over the axis pairs of a 2- to 4-D input, multiplied
 // ("Product": K-Planes, HexPlane) or summed ("Sum": tri-planes) per feature.  Not in the reference; levels, scales and resolutions are the
-// dense grid's, and with one plane (D = 2) so are the parameter layout and, in fp32, the output's bits.  First order only: no
-// second-order pass, no tangent, no max_level.
+// dense grid's, and with one plane (D = 2) so are the parameter layout and, in fp32, the output's bits.  First and second order
+// (a plane is bilinear: its mixed derivative, and in the product every other plane's value, enter the second-order pass) and the tangent; no max_level.
 // Initialisation: Sum draws the grid's uniform +-1e-4 * scale; Product draws uniform [0.1, 0.5), the range of the K-Planes paper -- a
 // product of K values of 1e-4 is zero in half, and so is every gradient that passes through it: nothing would ever train.
 class KPlanesEncoding : public Encoding {
@@ -1205,6 +1205,18 @@ public:
 		if (mode == GradientMode::Ignore) return;
 		CHECK_THROW(grads != nullptr);
 		kplanes_backward(stream, m_shape, m_fp32, n, x, params, dL_dy, padded_output_width(), m_fp32 ? nullptr : scratch_for(stream), grads, mode == GradientMode::Accumulate);
+	}
+	// one kernel per result asked for: the tangent (k_kplanes_tangent), dL_dx (k_kplanes_bwdbwd_input), the parameter gradient (k_kplanes_bwdbwd)
+	bool has_second_order() const override { return true; }
+	void backward_backward_input(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, MatView dL_ddLdx, const void* dL_dy, void* dL_ddLdy,
+	                             MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode) override {
+		if (padded_output_width() == 0) return;
+		if (dL_ddLdy) kplanes_tangent(stream, m_shape, m_fp32, n, x, dL_ddLdx, params, dL_ddLdy, padded_output_width());
+		const bool want_grads = mode != GradientMode::Ignore;
+		if (!dL_dx && !want_grads) return;
+		CHECK_THROW(dL_dy != nullptr && (grads != nullptr || !want_grads));
+		kplanes_backward_backward_input(stream, m_shape, m_fp32, n, x, dL_ddLdx, params, dL_dy, padded_output_width(), dL_dx, want_grads && !m_fp32 ? scratch_for(stream) : nullptr,
+		                                want_grads ? grads : nullptr, mode == GradientMode::Accumulate);
 	}
 	Json hyperparams() const override {
 		Json j = Json::object();

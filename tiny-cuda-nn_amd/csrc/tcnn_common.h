@@ -474,6 +474,11 @@ void kplanes_forward(hipStream_t stream, const KPlanesShape& p, bool fp32, uint3
 void kplanes_backward_input(hipStream_t stream, const KPlanesShape& p, bool fp32, uint32_t n, MatView x, const void* params, const void* dL_dy, uint32_t dy_stride, MatViewMut dL_dx);
 void kplanes_backward(hipStream_t stream, const KPlanesShape& p, bool fp32, uint32_t n, MatView x, const void* params, const void* dL_dy, uint32_t dy_stride, uint64_t* scratch, void* grad,
                       bool accumulate);
+// second order, with v [n][n_dims] fp32 and Q = <v, J^T dL_dy>: t [n][t_stride] T = J v (zeros behind n_levels * F); dL_dx (nullable, written) =
+// dQ/dx; grad (nullable; scratch as for kplanes_backward) = dQ/dparams.  Sum reads params for dL_dx alone; dL_dy is not read by kplanes_tangent.
+void kplanes_tangent(hipStream_t stream, const KPlanesShape& p, bool fp32, uint32_t n, MatView x, MatView v, const void* params, void* t, uint32_t t_stride);
+void kplanes_backward_backward_input(hipStream_t stream, const KPlanesShape& p, bool fp32, uint32_t n, MatView x, MatView v, const void* params, const void* dL_dy, uint32_t dy_stride,
+                                     MatViewMut* dL_dx, uint64_t* scratch, void* grad, bool accumulate);
 
 // ---- binned form for levels cut into more than 64 chunks (k_grid_bin.hip; GridLevel::scatter_binned): no filter, no gathers.
 // Same exact result as grid_backward_lds; writes every gradient element of the binned levels.  workspace: grid_bin_workspace_bytes().

@@ -5,7 +5,10 @@ range over the repetitions.  Beside the times: the gathers a forward pass issues
 not measured) and the rate per gather.  The three encodings are different functions with different widths (8 columns against 32): the table
 says what each costs per call, not which fits a field better.
 Writes profiles/kplanes_bench.txt / .json (or --out-dir) and prints the JSON.  A GPU is required: there is no fallback.
-usage (GPU box): python tools/bench_kplanes.py [--reps 7] [--iters 20] [--warmup 5] [--log2-batch 18]"""
+--second-order: the same protocol for the second-order pass, through the native module (half): the tangent alone (backward_backward_input
+asked for dL_ddLdy only), the full call (tangent, dL/dx and the parameter gradient) and input_jvp with 3 tangents behind a 64 x 2 CutlassMLP,
+for KPlanes and for HashGrid; writes profiles/kplanes_second_order_bench.txt / .json instead.
+usage (GPU box): python tools/bench_kplanes.py [--second-order] [--reps 7] [--iters 20] [--warmup 5] [--log2-batch 18]"""
 import argparse
 import json
 import os
@@ -39,8 +42,61 @@ def timed(fn, iters):
     return e0.elapsed_time(e1) / iters
 
 
+MLP = {"otype": "CutlassMLP", "activation": "Softplus", "output_activation": "None", "n_neurons": 64, "n_hidden_layers": 2}
+SECOND_ORDER_KINDS = ("KPlanes/Product", "KPlanes/Sum", "HashGrid")
+
+
+def second_order_runs(D, config, n, gen):
+    """the three timed calls of one (D, encoding): closures over device tensors made once"""
+    x, v = torch.rand(n, D, device="cuda", generator=gen), torch.rand(n, 3, D, device="cuda", generator=gen) * 2 - 1
+    enc, model = tcnn.Encoding(D, config), tcnn.NetworkWithInputEncoding(D, 16, config, MLP)
+    native, params = enc.native_tcnn_module, enc.params.detach().half()
+    dy = (torch.randn(n, native.n_output_dims(), device="cuda") * 1e-3).half()
+    ctx = native.fwd(x.requires_grad_(True), params)[0]
+    v0, frozen, model_params = v[:, 0].contiguous(), x.detach(), model.params.detach().half()
+
+    def full():
+        native.bwd_bwd_input(ctx, x, params.requires_grad_(True), v0, dy.requires_grad_(True))
+
+    return {"tangent": lambda: native.bwd_bwd_input(ctx, frozen, params.detach(), v0, dy.requires_grad_(True)), "second_order": full,
+            "input_jvp_3_mlp": lambda: model.native_tcnn_module.input_jvp(frozen, model_params, v)}
+
+
+def second_order(args):
+    n, gen = 1 << args.log2_batch, torch.Generator(device="cuda").manual_seed(42)
+    runs = {(D, kind): second_order_runs(D, KINDS[kind](D)[0], n, gen) for D in DIMS for kind in SECOND_ORDER_KINDS}
+    for passes in runs.values():
+        for fn in passes.values():
+            for _ in range(args.warmup):
+                fn()
+    torch.cuda.synchronize()
+    samples = {key: {k: [] for k in passes} for key, passes in runs.items()}
+    for _ in range(args.reps):
+        for key, passes in runs.items():
+            for k, fn in passes.items():
+                samples[key][k].append(timed(fn, args.iters))
+    result = {"metric": "native second-order pass of KPlanes (defaults) beside HashGrid (L16 F2 T2^19), half: tangent alone, full call, input_jvp (3 tangents) behind a 64x2 CutlassMLP", "unit": "ms",
+              "rows": n, "reps": args.reps, "iters": args.iters, "warmup": args.warmup, "device": torch.cuda.get_device_name(0),
+              "dims": {str(D): {kind: {k: {"median_ms": round(statistics.median(t), 4), "min_ms": round(min(t), 4), "max_ms": round(max(t), 4)} for k, t in samples[D, kind].items()}
+                                for kind in SECOND_ORDER_KINDS} for D in DIMS}}
+    print(json.dumps(result), flush=True)
+    os.makedirs(args.out_dir, exist_ok=True)
+    with open(os.path.join(args.out_dir, "kplanes_second_order_bench.json"), "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    lines = [f"# {result['metric']}; {n} rows, {args.reps} alternating repetitions of {args.iters} calls, device events ({result['device']})",
+             f"{'D':>2s} {'encoding':>16s} " + " ".join(f"{k + ' ms (median, min .. max)':>40s}" for k in ("tangent", "second_order", "input_jvp_3_mlp"))]
+    for D in DIMS:
+        for kind in SECOND_ORDER_KINDS:
+            r = result["dims"][str(D)][kind]
+            lines.append(f"{D:2d} {kind:>16s} " + " ".join(f"{t['median_ms']:18.4f} {t['min_ms']:9.4f} .. {t['max_ms']:8.4f}" for t in r.values()))
+    with open(os.path.join(args.out_dir, "kplanes_second_order_bench.txt"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--second-order", action="store_true")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
@@ -48,6 +104,8 @@ def main():
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_kplanes.py needs a GPU"
+    if args.second_order:
+        return second_order(args)
     n = 1 << args.log2_batch
     gen = torch.Generator(device="cuda").manual_seed(42)
     runs, shapes = {}, {}
