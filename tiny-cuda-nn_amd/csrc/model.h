@@ -534,7 +534,7 @@ public:
 		}
 		PlanesPlan& plan = planes_plan(n, want_lists);
 		grid_forward_planes(stream, m_meta, dev_meta(), plan.dev_work.as<uint32_t>(), plan.max_items, plan.blocks_per_xcd, n, x, params, out_planes, ctx.chunk_mask.as<uint64_t>(), prep_job,
-		                    want_lists ? &ctx.hit_lists : nullptr);
+		                    want_lists ? &ctx.hit_lists : nullptr, route.plain);
 		if (m_n_to_pad) HIP_CHECK_THROW(hipMemsetAsync((uint16_t*)out_planes + (size_t)n * m_n_features, 0, (size_t)n * m_n_to_pad * sizeof(uint16_t), stream)); // grid.h:749-759: the grid pads with zeros
 		if (max_level_forward_active()) { // grid.h:67-90 (hit lists and chunk masks stay those of every level: the gradient side decides for itself)
 			const uint32_t F = m_meta.n_features_per_level;

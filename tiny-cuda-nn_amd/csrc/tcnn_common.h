@@ -170,6 +170,17 @@ void grid_nd_backward_backward_input(hipStream_t stream, const GridMeta& meta, c
 // ---- training-step forward (k_grid_planes.hip): half, F >= 2, D in {2, 3}; level-major and XCD-aware.
 // out_planes: half [n_levels][n][F]; chunk_bits (optional): uint64 [n_levels][GRID_FILTER_MAX_CHUNKS][n / 64], written for levels with 2 .. GRID_FILTER_MAX_CHUNKS scatter chunks.
 bool grid_planes_supported(const GridMeta& meta, uint32_t n);
+// The kernel's PLAIN body (with hit lists only) takes this grid at this batch size: Linear interpolation, a hash that is a product with
+// primes (not Rng), and every byte offset the kernel forms -- into a level's table, a level's output plane, the coordinates -- within 32
+// bits.  2-D with two features per level: the shapes whose PLAIN body keeps the generic one's waves per SIMD (DESIGN.md "The forward
+// kernel's instruction stream").
+inline bool grid_planes_plain(const GridMeta& meta, uint32_t n) {
+	const uint64_t F = meta.n_features_per_level, D = meta.n_pos_dims;
+	if (D != 2 || F != 2 || meta.interpolation != (uint32_t)InterpolationType::Linear || meta.hash_type == (uint32_t)HashType::Rng) return false;
+	uint64_t entries = 0;
+	for (uint32_t l = 0; l < meta.n_levels; ++l) entries = entries > meta.levels[l].size ? entries : meta.levels[l].size;
+	return (entries + 1) * F * 2 <= (1ull << 32) && (uint64_t)n * (F * 2 > D * 4 ? F * 2 : D * 4) <= (1ull << 32);
+}
 bool grid_planes_to_rows_supported(const GridMeta& meta, uint32_t n, uint32_t width);
 // planes [width / F][n][F] -> the first `width` columns of rows [n][row_stride] and back (halves; the callers that want the encoded batch as a
 // matrix, k_grid_planes.hip; width: the levels' features, or the padded width with its planes of zeros)
@@ -249,7 +260,8 @@ uint32_t grid_hit_item_samples(const GridMeta& meta); // samples per work item o
 inline uint32_t grid_hit_max_samples(const GridMeta& meta) { return meta.n_pos_dims <= 2 ? (1u << 24) : (1u << 22); }
 // hit_lists (optional, instead of chunk_bits): see above
 void grid_forward_planes(hipStream_t stream, const GridMeta& meta, const GridMeta* dev_meta, const uint32_t* dev_work, uint32_t max_items, uint32_t blocks_per_xcd, uint32_t n,
-                         MatView x, const void* grid, void* out_planes, uint64_t* chunk_bits, const MlpPrepJob* prep_job = nullptr, const GridHitLists* hit_lists = nullptr);
+                         MatView x, const void* grid, void* out_planes, uint64_t* chunk_bits, const MlpPrepJob* prep_job = nullptr, const GridHitLists* hit_lists = nullptr,
+                         bool plain = false); // plain: GridForwardRoute::plain
 // reference-shaped gradient scatter with global float atomics (fp32 grids, F == 1, tables too large for the LDS scheme).
 // grad: T[n_params] accumulated in place (caller zeroes it).  For F == 1 && !fp32 the caller passes an fp32 scratch as `grad`.
 // stochastic (here and in the other gradient launchers): GridBackwardRoute::stochastic -- dL/dy itself onto the one corner drawn per (sample, level)
@@ -328,6 +340,7 @@ struct GridForwardRoute {
 	GridRecorded recorded = GridRecorded::Nothing;
 	bool lds = false;            // a later backward pass with parameter gradients runs the LDS owner-computes kernels, else the global-atomic one
 	uint32_t plane_features = 0; // Planes: the encoded batch is level planes [padded / F][n][F] of this F
+	bool plain = false;          // HitLists: k_grid_fwd_planes' PLAIN instantiation (grid_planes_plain), else its generic body
 };
 // half precision, F >= 2, every level's table cut into at most 64 chunks (the sample filter) or binned; TCNN_AMD_GRID_SCATTER=atomic: never
 inline bool grid_lds_gradients(const GridFacts& g, const Switches& sw, uint32_t n) {
@@ -361,6 +374,7 @@ inline GridForwardRoute grid_forward_route(const GridFacts& g, const Switches& s
 	// the drawn corner is one of the corners whose chunks were recorded)
 	const bool lists = r.kernel != GridForwardKernel::Rows && !grid_stochastic_gradients(g) && grid_hit_lists_wanted(g, sw, n);
 	if (param_gradients && r.lds) r.recorded = lists ? GridRecorded::HitLists : GridRecorded::BitPlanes;
+	r.plain = r.recorded == GridRecorded::HitLists && grid_planes_plain(meta, n);
 	return r;
 }
 
