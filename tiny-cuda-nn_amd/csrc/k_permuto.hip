@@ -17,6 +17,10 @@
 //                        workgroups per CU in gfx950's 160 KB), flushed to the global scratch afterwards, else straight into the global
 //                        scratch.  k_permuto_finalize rounds each sum once and leaves the scratch zero.  Integer adds: any order, same bits.
 //   k_permuto_bwd_f32    fp32 modules: float atomicAdd into the gradient itself (order not fixed, as on the fp32 grid route).
+// Second order ("second_order": true).  b is affine in x inside a simplex, so the Hessian term is zero: what is left of <v, J^T d> is
+// beta = db/dx . v (PermutoSimplex::weight_tangent: the elevation of v, sorted by the ranks the lookup already has).
+//   k_permuto_tangent    k_permuto_fwd's split; simplex, indices and gathers once, then a rolled loop over any number of directions.
+//   k_permuto_bwdbwd     k_permuto_bwd with beta in place of b (signed contributions, the same exact sums); k_permuto_bwdbwd_f32 likewise.
 //
 // Compiled with -ffp-contract=off: every fused multiply-add is explicit.
 #include "grid_fixed.h"
@@ -115,6 +119,33 @@ struct PermutoSimplex {
 			if (i >= 1) dx[i - 1] = (scale * PERMUTO_SF[i - 1]) * (pre - (float)i * dE);
 			pre += dE;
 		}
+	}
+
+	// beta[r] = d b[r] / dx along v inside this simplex: setup()'s elevation applied to the direction (no rounding, no rem0), sorted by
+	// the ranks after the fix-up, and the additions setup() makes for b without its 1 -.  The beta sum to zero.
+	__device__ inline void weight_tangent(const float (&v)[D], const float scale, float (&beta)[N]) const {
+		constexpr float inv = 1.0f / (float)N;
+		float Ep[N];
+		float sm = 0.0f;
+#pragma unroll
+		for (int i = D; i >= 1; --i) {
+			const float cf = (v[i - 1] * scale) * PERMUTO_SF[i - 1];
+			Ep[i] = sm - (float)i * cf;
+			sm += cf;
+		}
+		Ep[0] = sm;
+		float s[N];
+#pragma unroll
+		for (int k = 0; k < N; ++k) s[k] = 0.0f;
+#pragma unroll
+		for (int i = 0; i < N; ++i) {
+			const float d = Ep[i] * inv;
+#pragma unroll
+			for (int k = 0; k < N; ++k) s[k] += rank[i] == k ? d : 0.0f;
+		}
+		beta[0] = s[D] - s[0];
+#pragma unroll
+		for (int r = 1; r < N; ++r) beta[r] = s[D - r] - s[N - r];
 	}
 };
 
@@ -322,6 +353,154 @@ __global__ void __launch_bounds__(256) k_permuto_bwd_f32(const uint32_t n, const
 	}
 }
 
+// ---------------------------------------------------------------------------------------------------------------- tangent, n_t directions
+// k_permuto_fwd's split.  The simplex is set up, the D + 1 indices formed and the D + 1 gathers issued ONCE; the rolled loop over the
+// directions keeps the ranks and the gathered vectors in registers and adds, per direction, the elevation of v and O(D^2) selects.
+// Direction t is v.data + t * v_next through v's strides; its result goes to the buffer t * t_next bytes behind `out`.
+template <typename T, int D, int F>
+__global__ void __launch_bounds__(256) k_permuto_tangent(const uint32_t n, const uint32_t n_levels, const uint32_t log2_T, const PermutoShape::Scales scales, const MatView x,
+                                                         const MatView v, const uint32_t v_next, const uint32_t n_t, const T* __restrict__ params, T* __restrict__ out,
+                                                         const uint32_t out_stride, const size_t t_next, const uint32_t n_slots, const int vector_stores) {
+	typedef typename VecOf<T, F>::type vecF;
+	constexpr int N = D + 1;
+	const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
+	const uint32_t i = gid / n_slots;
+	if (i >= n) return;
+	const uint32_t level = gid - i * n_slots; // slots behind the levels write the padding: zeros
+	const bool live = level < n_levels;
+	const float scale = live ? scales.v[level] : 0.0f;
+	PermutoSimplex<D> sx;
+	vecF val[N];
+	if (live) {
+		float xin[D];
+		load_coords<D>(x, i, xin);
+		sx.setup(xin, scale);
+		const T* __restrict__ table = params + (((size_t)level << log2_T) * F);
+		const uint32_t mask = (1u << log2_T) - 1u;
+		uint32_t index[N];
+#pragma unroll
+		for (int r = 0; r < N; ++r) index[r] = sx.index(r, mask);
+#pragma unroll
+		for (int r = 0; r < N; ++r) val[r] = *(const vecF*)&table[(size_t)index[r] * F];
+	}
+	const size_t o_first = (size_t)i * out_stride + (size_t)level * F;
+#pragma unroll 1
+	for (uint32_t t = 0; t < n_t; ++t) {
+		float res[F];
+#pragma unroll
+		for (int f = 0; f < F; ++f) res[f] = 0.0f;
+		if (live) {
+			float vin[D], beta[N];
+			load_coords<D>(MatView{v.data + (size_t)t * v_next, v.stride_sample, v.stride_dim}, i, vin);
+			sx.weight_tangent(vin, scale, beta);
+#pragma unroll
+			for (int r = 0; r < N; ++r) {
+#pragma unroll
+				for (int f = 0; f < F; ++f) res[f] = fmaf(beta[r], permuto_elem<T, F>(val[r], f), res[f]);
+			}
+		}
+		T* o = (T*)((char*)out + (size_t)t * t_next) + o_first;
+		if (vector_stores) { // (out_stride % F == 0, so level * F + F <= out_stride, and every buffer starts on a multiple of F elements)
+			vecF w;
+			if constexpr (F == 1) w = (T)res[0];
+			else {
+#pragma unroll
+				for (int f = 0; f < F; ++f) w[f] = (T)res[f];
+			}
+			*(vecF*)o = w;
+		} else {
+#pragma unroll
+			for (int f = 0; f < F; ++f) if (level * F + f < out_stride) o[f] = (T)res[f];
+		}
+	}
+}
+
+// ---------------------------------------------------------------------------------------------------------------- d<v, J^T dL/dy>/dparams, half
+// k_permuto_bwd with beta = weight_tangent(v) in place of b: the same split, accumulators, exact signed sums and k_permuto_finalize.
+template <int D, int F>
+__global__ void __launch_bounds__(256) k_permuto_bwdbwd(const uint32_t n, const uint32_t log2_T, const PermutoShape::Scales scales, const MatView x, const MatView v,
+                                                        const half_t* __restrict__ dL_dy, const uint32_t dy_stride, unsigned long long* __restrict__ scratch, const int in_lds) {
+	extern __shared__ __attribute__((aligned(16))) char permuto_smem[];
+	typedef __attribute__((address_space(3))) unsigned long long lds_u64;
+	typedef typename VecOf<half_t, F>::type vecF;
+	constexpr int N = D + 1;
+	lds_u64* acc = (lds_u64*)permuto_smem;
+	const uint32_t level = blockIdx.y;
+	const uint32_t entries = (1u << log2_T) * F, mask = (1u << log2_T) - 1u;
+	if (in_lds) {
+		for (uint32_t e = threadIdx.x; e < entries; e += blockDim.x) ((unsigned long long*)permuto_smem)[e] = 0ull;
+		__syncthreads();
+	}
+	const float scale = scales.v[level];
+	unsigned long long* global_acc = scratch + (((size_t)level << log2_T) * F);
+	const uint32_t begin = blockIdx.x * PERMUTO_BWD_SAMPLES, end = min(n, begin + PERMUTO_BWD_SAMPLES);
+	for (uint32_t i = begin + threadIdx.x; i < end; i += blockDim.x) {
+		float xin[D], vin[D], beta[N];
+		load_coords<D>(x, i, xin);
+		load_coords<D>(v, i, vin);
+		PermutoSimplex<D> sx;
+		sx.setup(xin, scale);
+		sx.weight_tangent(vin, scale, beta);
+		const half_t* __restrict__ dy = dL_dy + (size_t)i * dy_stride + (size_t)level * F;
+		float g[F];
+		if (dy_stride % F == 0) {
+			const vecF gv = *(const vecF*)dy;
+#pragma unroll
+			for (int f = 0; f < F; ++f) g[f] = permuto_elem<half_t, F>(gv, f);
+		} else {
+#pragma unroll
+			for (int f = 0; f < F; ++f) g[f] = (float)dy[f];
+		}
+#pragma unroll
+		for (int r = 0; r < N; ++r) {
+			const uint32_t e = sx.index(r, mask) * F;
+#pragma unroll
+			for (int f = 0; f < F; ++f) {
+				const unsigned long long c = (unsigned long long)half_to_fixed_fast((half_t)(g[f] * beta[r]));
+				if (in_lds) __hip_atomic_fetch_add(acc + e + f, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+				else if (c != 0) atomicAdd(global_acc + e + f, c);
+			}
+		}
+	}
+	if (in_lds) {
+		__syncthreads();
+		for (uint32_t e = threadIdx.x; e < entries; e += blockDim.x) {
+			const unsigned long long s = ((unsigned long long*)permuto_smem)[e];
+			if (s != 0) atomicAdd(global_acc + e, s);
+		}
+	}
+}
+
+// fp32 modules: k_permuto_bwd_f32's split, float atomicAdd of dL/dy_f * beta_r
+template <int D, int F>
+__global__ void __launch_bounds__(256) k_permuto_bwdbwd_f32(const uint32_t n, const uint32_t n_levels, const uint32_t log2_T, const PermutoShape::Scales scales, const MatView x,
+                                                            const MatView v, const float* __restrict__ dL_dy, const uint32_t dy_stride, float* __restrict__ grad) {
+	constexpr int N = D + 1;
+	const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
+	const uint32_t i = gid / n_levels;
+	if (i >= n) return;
+	const uint32_t level = gid - i * n_levels;
+	const float scale = scales.v[level];
+	float xin[D], vin[D], beta[N];
+	load_coords<D>(x, i, xin);
+	load_coords<D>(v, i, vin);
+	PermutoSimplex<D> sx;
+	sx.setup(xin, scale);
+	sx.weight_tangent(vin, scale, beta);
+	float* __restrict__ table = grad + (((size_t)level << log2_T) * F);
+	const float* __restrict__ dy = dL_dy + (size_t)i * dy_stride + (size_t)level * F;
+	const uint32_t mask = (1u << log2_T) - 1u;
+	float g[F];
+#pragma unroll
+	for (int f = 0; f < F; ++f) g[f] = dy[f];
+#pragma unroll
+	for (int r = 0; r < N; ++r) {
+		const size_t e = (size_t)sx.index(r, mask) * F;
+#pragma unroll
+		for (int f = 0; f < F; ++f) atomicAdd(table + e + f, g[f] * beta[r]);
+	}
+}
+
 // ---------------------------------------------------------------------------------------------------------------- launches
 uint32_t blocks_for(uint64_t threads) {
 	CHECK_THROW(threads < (1ull << 32));
@@ -357,6 +536,32 @@ void launch_bwd(hipStream_t s, const PermutoShape& p, bool fp32, uint32_t n, Mat
 		const bool in_lds = lds_bytes <= PERMUTO_LDS_BYTES;
 		hipLaunchKernelGGL((k_permuto_bwd<D, F>), dim3(div_round_up(n, PERMUTO_BWD_SAMPLES), p.n_levels), dim3(256), in_lds ? (uint32_t)lds_bytes : 0u, s, n, p.log2_hashmap_size,
 		                   p.scales, x, (const half_t*)dL_dy, dy_stride, (unsigned long long*)scratch, in_lds ? 1 : 0);
+	}
+	hipLaunchKernelGGL(k_permuto_finalize, dim3((uint32_t)((n_params + 255) / 256)), dim3(256), 0, s, n_params, (unsigned long long*)scratch, (half_t*)grad, accumulate ? 1 : 0);
+}
+
+template <typename T, int D, int F>
+void launch_tangent(hipStream_t s, const PermutoShape& p, uint32_t n, MatView x, MatView v, uint32_t v_next, uint32_t n_t, const void* params, void* t, uint32_t t_stride, size_t t_next) {
+	const uint32_t n_slots = div_round_up(t_stride, (uint32_t)F);
+	const bool vector_stores = t_stride % F == 0 && t_next % (F * sizeof(T)) == 0;
+	hipLaunchKernelGGL((k_permuto_tangent<T, D, F>), dim3(blocks_for((uint64_t)n * n_slots)), dim3(256), 0, s, n, p.n_levels, p.log2_hashmap_size, p.scales, x, v, v_next, n_t,
+	                   (const T*)params, (T*)t, t_stride, t_next, n_slots, vector_stores ? 1 : 0);
+}
+
+template <int D, int F>
+void launch_bwdbwd(hipStream_t s, const PermutoShape& p, bool fp32, uint32_t n, MatView x, MatView v, const void* dL_dy, uint32_t dy_stride, uint64_t* scratch, void* grad, bool accumulate) {
+	const size_t n_params = ((size_t)p.n_levels << p.log2_hashmap_size) * F;
+	if (fp32) {
+		if (!accumulate) hipLaunchKernelGGL(k_permuto_zero, dim3((uint32_t)((n_params + 255) / 256)), dim3(256), 0, s, n_params, (float*)grad);
+		if (n > 0) hipLaunchKernelGGL((k_permuto_bwdbwd_f32<D, F>), dim3(blocks_for((uint64_t)n * p.n_levels)), dim3(256), 0, s, n, p.n_levels, p.log2_hashmap_size, p.scales, x, v,
+		                              (const float*)dL_dy, dy_stride, (float*)grad);
+		return;
+	}
+	if (n > 0) {
+		const size_t lds_bytes = ((size_t)F << p.log2_hashmap_size) * sizeof(uint64_t);
+		const bool in_lds = lds_bytes <= PERMUTO_LDS_BYTES;
+		hipLaunchKernelGGL((k_permuto_bwdbwd<D, F>), dim3(div_round_up(n, PERMUTO_BWD_SAMPLES), p.n_levels), dim3(256), in_lds ? (uint32_t)lds_bytes : 0u, s, n, p.log2_hashmap_size,
+		                   p.scales, x, v, (const half_t*)dL_dy, dy_stride, (unsigned long long*)scratch, in_lds ? 1 : 0);
 	}
 	hipLaunchKernelGGL(k_permuto_finalize, dim3((uint32_t)((n_params + 255) / 256)), dim3(256), 0, s, n_params, (unsigned long long*)scratch, (half_t*)grad, accumulate ? 1 : 0);
 }
@@ -400,6 +605,21 @@ void permuto_backward_input(hipStream_t stream, const PermutoShape& p, bool fp32
 
 void permuto_backward(hipStream_t stream, const PermutoShape& p, bool fp32, uint32_t n, MatView x, const void* dL_dy, uint32_t dy_stride, uint64_t* scratch, void* grad, bool accumulate) {
 	TCNN_PERMUTO_DISPATCH((launch_bwd<D, F>(stream, p, fp32, n, x, dL_dy, dy_stride, scratch, grad, accumulate)))
+	HIP_CHECK_THROW(hipGetLastError());
+}
+
+void permuto_tangent(hipStream_t stream, const PermutoShape& p, bool fp32, uint32_t n, MatView x, MatView v, uint32_t v_next, uint32_t n_tangents, const void* params, void* t,
+                     uint32_t t_stride, size_t t_next) {
+	if (n == 0 || t_stride == 0 || n_tangents == 0) return;
+	CHECK_THROW(t_stride >= p.n_levels * p.n_features_per_level && t_next % (fp32 ? 4 : 2) == 0);
+	if (fp32) { TCNN_PERMUTO_DISPATCH((launch_tangent<float, D, F>(stream, p, n, x, v, v_next, n_tangents, params, t, t_stride, t_next))) }
+	else { TCNN_PERMUTO_DISPATCH((launch_tangent<half_t, D, F>(stream, p, n, x, v, v_next, n_tangents, params, t, t_stride, t_next))) }
+	HIP_CHECK_THROW(hipGetLastError());
+}
+
+void permuto_backward_backward(hipStream_t stream, const PermutoShape& p, bool fp32, uint32_t n, MatView x, MatView v, const void* dL_dy, uint32_t dy_stride, uint64_t* scratch,
+                               void* grad, bool accumulate) {
+	TCNN_PERMUTO_DISPATCH((launch_bwdbwd<D, F>(stream, p, fp32, n, x, v, dL_dy, dy_stride, scratch, grad, accumulate)))
 	HIP_CHECK_THROW(hipGetLastError());
 }
 

@@ -292,6 +292,15 @@ public:
 	virtual void tangent(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, MatView v, void* t, const void* params) {
 		backward_backward_input(stream, ctx, n, x, v, nullptr, t, nullptr, params, nullptr, GradientMode::Ignore);
 	}
+	// Directions first .. first + n_group - 1 of a row-major [n][n_tangents][d_in] block of floats, tangent k into the buffer k * t_next
+	// bytes behind t.  Here: tangent() per direction.  An encoding whose set-up dwarfs the per-direction work serves the group in one
+	// launch (PermutoEncoding), with the bits its tangent() gives.
+	virtual void tangents(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const float* directions, uint32_t first, uint32_t n_group, uint32_t n_tangents,
+	                      void* t, size_t t_next, const void* params) {
+		for (uint32_t k = 0; k < n_group; ++k) {
+			tangent(stream, ctx, n, x, MatView{directions + (size_t)(first + k) * input_width(), n_tangents * input_width(), 1u}, (char*)t + k * t_next, params);
+		}
+	}
 	// true: the encoding is half(x * scale + offset) padded with ones -- cheap enough to apply inside the consumer's load
 	virtual bool as_identity(float& scale, float& offset) const { return false; }
 	// n_bins if this is a half-precision OneBlob encoding the MLP kernels can evaluate inside their input load (MlpIo::x_oneblob_bins), else 0
@@ -1077,7 +1086,8 @@ private:
 
 // "PermutoGrid" / "Permutohedral" (k_permuto.hip): the hash grid's levels, tables and hash, interpolated on the simplices of a
 // permutohedral lattice -- D + 1 vertices per level where a grid cell has 2^D corners.  Not in the reference; the keys keep the grid's
-// names and defaults.  First order only: no second-order pass, no tangent, no max_level.
+// names and defaults.  The second-order pass and the tangent are opt-in ("second_order": true; the weights are affine in x inside a simplex,
+// so there is no Hessian term: a tangent, a parameter gradient, and dL_dx = 0); no max_level.
 class PermutoEncoding : public Encoding {
 public:
 	PermutoEncoding(uint32_t n_dims_to_encode, const Json& enc, bool fp32) : Encoding{fp32} {
@@ -1097,6 +1107,8 @@ public:
 		if (m_shape.log2_hashmap_size < 1 || m_shape.log2_hashmap_size > 28) throw std::runtime_error{"PermutoGrid: log2_hashmap_size must be 1 to 28, not " + std::to_string(m_shape.log2_hashmap_size)};
 		if (m_base_resolution < 1) throw std::runtime_error{"PermutoGrid: base_resolution must be at least 1"};
 		if (!(m_per_level_scale > 0.0f) || !std::isfinite(m_per_level_scale)) throw std::runtime_error{"PermutoGrid: per_level_scale must be positive and finite"};
+		if (enc.contains("second_order") && !enc["second_order"].is_bool()) throw std::runtime_error{"PermutoGrid: second_order must be true or false"};
+		m_second_order = enc.value("second_order", false);
 		m_n_params = ((size_t)m_shape.n_levels << m_shape.log2_hashmap_size) * F;
 		const float log2_scale = std::log2(m_per_level_scale);
 		for (uint32_t l = 0; l < m_shape.n_levels; ++l) m_shape.scales.v[l] = exp2f(l * log2_scale) * m_base_resolution; // the grid's scale without its - 1
@@ -1118,6 +1130,25 @@ public:
 		CHECK_THROW(grads != nullptr);
 		permuto_backward(stream, m_shape, m_fp32, n, x, dL_dy, padded_output_width(), m_fp32 ? nullptr : scratch_for(stream), grads, mode == GradientMode::Accumulate);
 	}
+	// one kernel per result asked for: the tangent (k_permuto_tangent), zeros for dL_dx, the parameter gradient (k_permuto_bwdbwd).
+	// tangent() is the inherited call, so the tangent alone is the full call's dL_ddLdy bit for bit.
+	bool has_second_order() const override { return m_second_order; }
+	void backward_backward_input(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, MatView dL_ddLdx, const void* dL_dy, void* dL_ddLdy,
+	                             MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode) override {
+		if (!m_second_order) return Encoding::backward_backward_input(stream, ctx, n, x, dL_ddLdx, dL_dy, dL_ddLdy, dL_dx, params, grads, mode);
+		if (dL_ddLdy) permuto_tangent(stream, m_shape, m_fp32, n, x, dL_ddLdx, 0, 1, params, dL_ddLdy, padded_output_width(), 0);
+		if (dL_dx) zero_input_gradient(stream, n, m_shape.n_dims, *dL_dx);
+		if (mode == GradientMode::Ignore || padded_output_width() == 0) return;
+		CHECK_THROW(dL_dy != nullptr && grads != nullptr);
+		permuto_backward_backward(stream, m_shape, m_fp32, n, x, dL_ddLdx, dL_dy, padded_output_width(), m_fp32 ? nullptr : scratch_for(stream), grads, mode == GradientMode::Accumulate);
+	}
+	// a group of directions in ONE launch: simplex, indices and gathers once per (sample, level), then a loop over the directions
+	void tangents(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const float* directions, uint32_t first, uint32_t n_group, uint32_t n_tangents,
+	              void* t, size_t t_next, const void* params) override {
+		if (!m_second_order) return Encoding::tangents(stream, ctx, n, x, directions, first, n_group, n_tangents, t, t_next, params);
+		const uint32_t D = m_shape.n_dims;
+		if (t) permuto_tangent(stream, m_shape, m_fp32, n, x, MatView{directions + (size_t)first * D, n_tangents * D, 1u}, D, n_group, params, t, padded_output_width(), t_next);
+	}
 	Json hyperparams() const override {
 		Json j = Json::object();
 		j["otype"] = "PermutoGrid";
@@ -1127,6 +1158,7 @@ public:
 		j["base_resolution"] = m_base_resolution;
 		j["per_level_scale"] = m_per_level_scale;
 		j["hash"] = "CoherentPrime";
+		j["second_order"] = m_second_order;
 		return j;
 	}
 private:
@@ -1141,6 +1173,7 @@ private:
 	PermutoShape m_shape;
 	uint32_t m_base_resolution;
 	float m_per_level_scale;
+	bool m_second_order;
 	size_t m_n_params;
 	std::map<const void*, std::unique_ptr<DeviceBuf>> m_scratch;
 };
@@ -2926,7 +2959,8 @@ public:
 	}
 
 	// input_jvp for this model, mirroring input_jacobian_impl: the encoding's forward pass with dy_dx runs ONCE, the encoding's tangent
-	// (Encoding::tangent: its second-order pass asked for dL_ddLdy alone, or OneBlob's kernel) runs per direction into buffers one behind
+	// (Encoding::tangents: per direction Encoding::tangent -- the second-order pass asked for dL_ddLdy alone, or OneBlob's kernel -- or, for
+	// PermutoGrid, one launch per group that sets the lattice up once) fills buffers one behind
 	// the other, and the network carries them to the output -- the fused kernel, or the layer-by-layer forward and tangent passes
 	// (Network::input_jvp).  A fused plan behind an Identity encoding reads input and tangents through the fused Identity load and needs no
 	// buffer.  The tangent buffers are temporaries: groups of as many directions as fit INPUT_JACOBIAN_TMP_BYTES at a time; a further group
@@ -2960,9 +2994,7 @@ public:
 			const uint32_t n_group = std::min(group, n_tangents - t0);
 			MatView tangents_f32{};
 			if (identity) tangents_f32 = MatView{tangents + (size_t)t0 * input_width(), n_tangents * input_width(), 1u};
-			for (uint32_t t = 0; t < n_group && !identity; ++t) {
-				m_encoding->tangent(stream, encoding_ctx, n, input, tangent_slice(tangents, t0 + t, n_tangents), (char*)encoded_tangents.data() + t * buf_bytes, encoding_params(params));
-			}
+			if (!identity) m_encoding->tangents(stream, encoding_ctx, n, input, tangents, t0, n_group, n_tangents, encoded_tangents.data(), buf_bytes, encoding_params(params));
 			m_network->input_jvp(stream, plan, n, io, encoded_tangents.data(), tangents_f32, n_group, params, jvp, n_tangents, t0);
 			io.out_half = nullptr; // stored with the first group
 		}

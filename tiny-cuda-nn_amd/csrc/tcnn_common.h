@@ -474,6 +474,13 @@ struct PermutoShape {
 void permuto_forward(hipStream_t stream, const PermutoShape& p, bool fp32, uint32_t n, MatView x, const void* params, void* out, uint32_t out_stride);
 void permuto_backward_input(hipStream_t stream, const PermutoShape& p, bool fp32, uint32_t n, MatView x, const void* params, const void* dL_dy, uint32_t dy_stride, MatViewMut dL_dx);
 void permuto_backward(hipStream_t stream, const PermutoShape& p, bool fp32, uint32_t n, MatView x, const void* dL_dy, uint32_t dy_stride, uint64_t* scratch, void* grad, bool accumulate);
+// second order, Q = <v, J^T dL_dy> (dQ/dx is exactly zero: the weights are affine in x inside a simplex).  permuto_tangent: n_tangents
+// directions, direction k the view v moved on by k * v_next floats, t_k [n][t_stride] T = J v_k (zeros behind n_levels * F) at t + k * t_next
+// BYTES -- one launch, the lattice set up and gathered once for all of them.  permuto_backward_backward: grad = dQ/dparams, scratch as above.
+void permuto_tangent(hipStream_t stream, const PermutoShape& p, bool fp32, uint32_t n, MatView x, MatView v, uint32_t v_next, uint32_t n_tangents, const void* params, void* t,
+                     uint32_t t_stride, size_t t_next);
+void permuto_backward_backward(hipStream_t stream, const PermutoShape& p, bool fp32, uint32_t n, MatView x, MatView v, const void* dL_dy, uint32_t dy_stride, uint64_t* scratch,
+                               void* grad, bool accumulate);
 
 // ---- KPlanes (k_kplanes.hip): per level the K = D (D - 1) / 2 dense 2-D feature grids over the axis pairs (a, b), a < b, in lexicographic
 // order; each is a 2-D DenseGrid level with Linear interpolation whose fp32 value P_k[f] is kept unrounded, and the K values are multiplied

@@ -4,7 +4,13 @@ events around a warmed-up loop; median and range over the repetitions.  Beside t
 (D + 1) on the lattice, x 2^D on the grid, 4 bytes each -- counted from the shapes, not measured), the rate per gather, and the lattice's time
 as a fraction of the grid's next to the fraction of the gathers, (D + 1) / 2^D.
 Writes profiles/permuto_bench.txt / .json (or --out-dir) and prints the JSON.  A GPU is required: there is no fallback.
-usage (GPU box): python tools/bench_permuto.py [--reps 7] [--iters 20] [--warmup 5] [--log2-batch 18]"""
+--second-order: the same protocol for the second-order pass ("second_order": true), D = 3, 5, 7, through the native module (half): the
+encoding's forward call; the tangent alone (backward_backward_input asked for dL_ddLdy only: one k_permuto_tangent launch for one direction);
+that call three times over (three tangent() calls); the full call (tangent, zeros for dL/dx, the parameter gradient); and input_jvp with 1 and
+with 3 tangents behind a 64 x 2 CutlassMLP -- the one caller of Encoding::tangents(), which serves all directions of a group in ONE launch.
+No entry point runs tangents() alone: input_jvp_3 - input_jvp_1 is two more directions in that launch PLUS two more in the network.  HashGrid
+(a tangent() call per direction) runs beside it as context.  Writes profiles/permuto_second_order_bench.txt / .json instead.
+usage (GPU box): python tools/bench_permuto.py [--second-order] [--reps 7] [--iters 20] [--warmup 5] [--log2-batch 18]"""
 import argparse
 import json
 import os
@@ -34,8 +40,69 @@ def timed(fn, iters):
     return e0.elapsed_time(e1) / iters
 
 
+MLP = {"otype": "CutlassMLP", "activation": "Softplus", "output_activation": "None", "n_neurons": 64, "n_hidden_layers": 2}
+SECOND_ORDER_DIMS = (3, 5, 7)
+SECOND_ORDER_PASSES = ("forward", "tangent", "three_tangent_calls", "second_order", "input_jvp_1_mlp", "input_jvp_3_mlp")
+
+
+def second_order_runs(D, config, n, gen):
+    """the timed calls of one (D, encoding): closures over device tensors made once"""
+    x, v = torch.rand(n, D, device="cuda", generator=gen), torch.rand(n, 3, D, device="cuda", generator=gen) * 2 - 1
+    enc, model = tcnn.Encoding(D, config), tcnn.NetworkWithInputEncoding(D, 16, config, MLP)
+    native, params = enc.native_tcnn_module, enc.params.detach().half()
+    dy = (torch.randn(n, native.n_output_dims(), device="cuda") * 1e-3).half()
+    ctx = native.fwd(x.requires_grad_(True), params)[0]
+    v0, v1, frozen, model_params = v[:, 0].contiguous(), v[:, :1].contiguous(), x.detach(), model.params.detach().half()
+
+    def tangent():
+        native.bwd_bwd_input(ctx, frozen, params.detach(), v0, dy.requires_grad_(True))
+
+    def three_tangent_calls():
+        for _ in range(3):
+            tangent()
+
+    return {"forward": lambda: native.fwd(frozen, params), "tangent": tangent, "three_tangent_calls": three_tangent_calls,
+            "second_order": lambda: native.bwd_bwd_input(ctx, x, params.requires_grad_(True), v0, dy.requires_grad_(True)),
+            "input_jvp_1_mlp": lambda: model.native_tcnn_module.input_jvp(frozen, model_params, v1),
+            "input_jvp_3_mlp": lambda: model.native_tcnn_module.input_jvp(frozen, model_params, v)}
+
+
+def second_order(args):
+    n, gen = 1 << args.log2_batch, torch.Generator(device="cuda").manual_seed(42)
+    configs = {"PermutoGrid": dict(SHAPE, otype="PermutoGrid", second_order=True), "HashGrid": dict(SHAPE, otype="HashGrid")}
+    runs = {(D, kind): second_order_runs(D, config, n, gen) for D in SECOND_ORDER_DIMS for kind, config in configs.items()}
+    for passes in runs.values():
+        for fn in passes.values():
+            for _ in range(args.warmup):
+                fn()
+    torch.cuda.synchronize()
+    samples = {key: {k: [] for k in passes} for key, passes in runs.items()}
+    for _ in range(args.reps):
+        for key, passes in runs.items():
+            for k, fn in passes.items():
+                samples[key][k].append(timed(fn, args.iters))
+    result = {"metric": "native second-order pass of PermutoGrid (second_order) beside HashGrid, L16 F2 T2^19 half: forward, tangent alone, three tangent calls, full call, input_jvp (1 and 3 tangents) behind a 64x2 CutlassMLP",
+              "unit": "ms", "rows": n, "reps": args.reps, "iters": args.iters, "warmup": args.warmup, "device": torch.cuda.get_device_name(0),
+              "dims": {str(D): {kind: {k: {"median_ms": round(statistics.median(t), 4), "min_ms": round(min(t), 4), "max_ms": round(max(t), 4)} for k, t in samples[D, kind].items()}
+                                for kind in configs} for D in SECOND_ORDER_DIMS}}
+    print(json.dumps(result), flush=True)
+    os.makedirs(args.out_dir, exist_ok=True)
+    with open(os.path.join(args.out_dir, "permuto_second_order_bench.json"), "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    lines = [f"# {result['metric']}; {n} rows, {args.reps} alternating repetitions of {args.iters} calls, device events ({result['device']})",
+             f"{'D':>2s} {'encoding':>11s} {'pass':>20s} {'ms (median, min .. max)':>34s}"]
+    for D in SECOND_ORDER_DIMS:
+        for kind in configs:
+            for k, t in result["dims"][str(D)][kind].items():
+                lines.append(f"{D:2d} {kind:>11s} {k:>20s} {t['median_ms']:12.4f} {t['min_ms']:9.4f} .. {t['max_ms']:8.4f}")
+    with open(os.path.join(args.out_dir, "permuto_second_order_bench.txt"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--second-order", action="store_true")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
@@ -43,6 +110,8 @@ def main():
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_permuto.py needs a GPU"
+    if args.second_order:
+        return second_order(args)
     n = 1 << args.log2_batch
     gen = torch.Generator(device="cuda").manual_seed(42)
     runs = {}

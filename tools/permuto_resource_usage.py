@@ -22,8 +22,8 @@ def main():
     names = subprocess.run([usage.demangler()], input="\n".join(r["name"].replace("DF16_", "Dh") for r in found), capture_output=True, text=True, check=True).stdout.splitlines()
     rows = sorted((re.sub(r"^void |\(.*$", "", re.sub(r"tcnn_amd::\(anonymous namespace\)::", "", name)), r) for r, name in zip(found, names))
     lines = ["# every kernel of k_permuto.hip (<T, D, F> / <D, F>): hipcc --offload-arch=gfx950, the library's flags, -Rpass-analysis=kernel-resource-usage",
-             "# (tools/permuto_resource_usage.py).  scratch: bytes per lane; occupancy: waves per SIMD; lds: static bytes per workgroup (k_permuto_bwd asks",
-             "# for its accumulators dynamically: 8 bytes x 2^log2_hashmap_size x F when that is at most 64 KB, else none)",
+             "# (tools/permuto_resource_usage.py).  scratch: bytes per lane; occupancy: waves per SIMD; lds: static bytes per workgroup (k_permuto_bwd and",
+             "# k_permuto_bwdbwd ask for their accumulators dynamically: 8 bytes x 2^log2_hashmap_size x F when that is at most 64 KB, else none)",
              f"{'kernel':44s} {'VGPR':>5s} {'AGPR':>5s} {'scratch':>8s} {'occupancy':>10s} {'lds':>6s}"]
     lines += [f"{name:44s} {r['vgpr']:5d} {r['agpr']:5d} {r['scratch']:8d} {r['occupancy']:10d} {r['lds']:6d}" for name, r in rows]
     bad = [name for name, r in rows if r["scratch"] != 0 or r["lds"] != 0]
