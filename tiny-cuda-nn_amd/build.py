@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libtcnn_amd.so")
-SOURCES = ["k_grid.hip", "k_grid_nd.hip", "k_grid_planes.hip", "k_grid_planes_plain.hip", "k_grid_scatter.hip", "k_grid_scatter_lists.hip", "k_grid_bin.hip", "k_grid_bwdbwd.hip", "k_grid_max_level.hip", "k_encodings.hip", "k_ppng.hip", "k_permuto.hip", "k_kplanes.hip", "k_mlp.hip", "k_mlp_input_grad.hip", "k_mlp_input_jacobian.hip", "k_mlp_input_jvp.hip", "k_mlp_layers.hip", "k_mlp_layers_f32.hip", "k_train.hip", "k_train_regs.hip", "k_train_r32.hip", "k_train_r32a.hip", "k_train_r32ob.hip", "k_train_r32w.hip", "k_misc.hip", "k_loss_eval.hip", "capi.cpp"]
+SOURCES = ["k_grid.hip", "k_grid_nd.hip", "k_grid_planes.hip", "k_grid_planes_plain.hip", "k_grid_scatter.hip", "k_grid_scatter_lists.hip", "k_grid_bin.hip", "k_grid_bwdbwd.hip", "k_grid_max_level.hip", "k_encodings.hip", "k_ppng.hip", "k_permuto.hip", "k_kplanes.hip", "k_tensorf.hip", "k_mlp.hip", "k_mlp_input_grad.hip", "k_mlp_input_jacobian.hip", "k_mlp_input_jvp.hip", "k_mlp_layers.hip", "k_mlp_layers_f32.hip", "k_train.hip", "k_train_regs.hip", "k_train_r32.hip", "k_train_r32a.hip", "k_train_r32ob.hip", "k_train_r32w.hip", "k_misc.hip", "k_loss_eval.hip", "capi.cpp"]
 HEADERS = ["tcnn_common.h", "grid_device.h", "grid_planes_kernel.h", "grid_fixed.h", "mlp_device.h", "mlp_input_grad_device.h", "r32_device.h", "r32_train.h", "mlp_train_kernels.h", "mlp_side_jobs.h", "adam_device.h", "oneblob_device.h", "loss_device.h", "reduce_device.h", "model.h", "json_lite.h", os.path.join("..", "..", "include", "tcnn_amd.h"),
            os.path.join("..", "..", "include", "tiny-cuda-nn", "json_lite.h")]
 # -ffp-contract=off: fused multiply-adds only where the source says fma (bit-exact grid arithmetic, see k_grid.hip)
@@ -33,12 +33,14 @@ def _newest(paths):
 # exact gradient sums).  Left to itself hipcc pairs the lattice arithmetic into 4976 of them across the file's 146 kernels; without them
 # the file has 112 701 instructions instead of 113 188 and the same registers, so the caution costs nothing (DESIGN.md "PermutoGrid").
 # (The host pass of the same compile answers that its target has no such feature and ignores it.)
+# k_tensorf.hip: as k_kplanes.hip (plane values are KPlanes' chains; two runs the same bits; exact gradient sums).
 # k_kplanes.hip: the same contracts (the fp32 DenseGrid's bits at D = 2, two runs the same bits, exact gradient sums), the same flags.
 # k_grid_planes_plain.hip: the same flags for the PLAIN instantiations of k_grid_fwd_planes (bit-identical planes and hit lists); its two
 # kernels keep their registers (118 and 69).  The generic instantiations in k_grid_planes.hip stay as they were built before: without the
 # packed instructions <2, 2, 4, false> goes from 72 to 74 registers and from 7 to 6 waves per SIMD.
 EXTRA_FLAGS = {"k_permuto.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                "k_kplanes.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+               "k_tensorf.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                "k_grid_planes_plain.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                "k_train_regs.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"], "k_train_r32.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
                # k_train_r32ob.hip keeps its weight-gradient accumulators in AGPRs through inline assembly; the builtins' results must then stay in VGPRs

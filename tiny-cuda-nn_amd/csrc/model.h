@@ -1277,6 +1277,93 @@ private:
 	std::map<const void*, std::unique_ptr<DeviceBuf>> m_scratch;
 };
 
+// "TensoRF" (k_tensorf.hip): one resolution per level, many components.  "VM" (3-D): three modes, each a feature plane over an axis pair
+// (KPlanes' pair order) times a feature line over the remaining axis, concatenated: 3 L F columns.  "CP" (2- to 4-D): the product of one
+// feature line per axis: L F columns.  Not in the reference; levels, scales and resolutions are the dense grid's.  First order only: no
+// second-order pass, no tangent, no max_level; upsampling the factors during training is a host-side re-sample and not provided.
+// Rows are stored in 16-byte chunks, so the output is aligned to 8 columns in half and 4 in float -- the smallest that keeps every row
+// 16-byte storable (with F >= 8 the width is a multiple already; a caller that sets another width gets element stores).
+// Initialisation: every factor uniform in (-0.1, 0.1), TensoRF's 0.1-scaled draw: the grid's 1e-4 would multiply to zero in half.
+class TensoRFEncoding : public Encoding {
+public:
+	TensoRFEncoding(uint32_t n_dims_to_encode, const Json& enc, bool fp32) : Encoding{fp32} {
+		memset(&m_shape, 0, sizeof(m_shape));
+		m_shape.n_dims = n_dims_to_encode;
+		m_shape.n_levels = enc.value("n_levels", 1u);
+		m_shape.n_components = enc.value("n_components", 16u);
+		m_base_resolution = enc.value("base_resolution", 128u);
+		m_per_level_scale = enc.value("per_level_scale", 2.0f);
+		const std::string decomposition = enc.value("decomposition", "VM");
+		const uint32_t F = m_shape.n_components;
+		if (!equals_case_insensitive(decomposition, "VM") && !equals_case_insensitive(decomposition, "CP")) throw std::runtime_error{"TensoRF: decomposition must be VM or CP, not " + decomposition};
+		m_shape.cp = equals_case_insensitive(decomposition, "CP") ? 1u : 0u;
+		if (!m_shape.cp && n_dims_to_encode != 3) throw std::runtime_error{"TensoRF: n_dims_to_encode must be 3 for decomposition VM, not " + std::to_string(n_dims_to_encode)};
+		if (m_shape.cp && (n_dims_to_encode < 2 || n_dims_to_encode > 4)) throw std::runtime_error{"TensoRF: n_dims_to_encode must be 2 to 4 for decomposition CP, not " + std::to_string(n_dims_to_encode)};
+		if (F != 2 && F != 4 && F != 8 && F != 16 && F != 32) throw std::runtime_error{"TensoRF: n_components must be 2, 4, 8, 16 or 32, not " + std::to_string(F)};
+		if (m_shape.n_levels < 1 || m_shape.n_levels > MAX_N_LEVELS) throw std::runtime_error{"TensoRF: n_levels must be 1 to " + std::to_string(MAX_N_LEVELS) + ", not " + std::to_string(m_shape.n_levels)};
+		if (m_base_resolution < 1) throw std::runtime_error{"TensoRF: base_resolution must be at least 1"};
+		if (!(m_per_level_scale > 0.0f) || !std::isfinite(m_per_level_scale)) throw std::runtime_error{"TensoRF: per_level_scale must be positive and finite"};
+		const float log2_scale = std::log2(m_per_level_scale);
+		uint64_t offset = 0;
+		for (uint32_t l = 0; l < m_shape.n_levels; ++l) { // scale and resolution: GridEncoding's, as KPlanesEncoding
+			const float scale = exp2f(l * log2_scale) * m_base_resolution - 1.0f;
+			const float resolution = ceilf(scale) + 1.0f;
+			if (!(resolution >= 1.0f) || resolution * resolution > (float)(std::numeric_limits<uint32_t>::max() / 2)) {
+				throw std::runtime_error{"TensoRF: base_resolution and per_level_scale give level " + std::to_string(l) + " a resolution of " + std::to_string(resolution) + ": its plane does not fit 2^31 entries"};
+			}
+			const uint32_t R = (uint32_t)resolution, entries = next_multiple(R * R, 8u);
+			m_shape.levels.scale[l] = scale;
+			m_shape.levels.resolution[l] = R;
+			m_shape.levels.entries[l] = entries;
+			m_shape.levels.offset[l] = (uint32_t)offset;
+			offset += m_shape.cp ? (uint64_t)n_dims_to_encode * next_multiple(R, 8u) : 3ull * ((uint64_t)entries + next_multiple(R, 8u));
+			if (offset * F > std::numeric_limits<uint32_t>::max()) throw std::runtime_error{"TensoRF: n_levels, base_resolution and per_level_scale give more than 2^32 parameters"};
+		}
+		m_n_params = (size_t)offset * F;
+	}
+	uint32_t input_width() const override { return m_shape.n_dims; }
+	uint32_t output_width() const override { return m_shape.output_width(); }
+	uint32_t required_output_alignment() const override { return m_fp32 ? 4u : 8u; } // 16 bytes (see the class comment)
+	size_t n_params() const override { return m_n_params; }
+	void initialize_params(Pcg32& rng, float* params_full_precision, float scale) override {
+		generate_random_uniform(nullptr, rng.st, n_params(), params_full_precision, -0.1f, 0.1f);
+	}
+	EncodingContext forward(hipStream_t stream, uint32_t n, MatView x, const void* params, void* out, bool prepare_input_gradients, bool prepare_param_gradients, const ForwardPlan* plan) override {
+		if (out && padded_output_width() > 0 && n > 0) tensorf_forward(stream, m_shape, m_fp32, n, x, params, out, padded_output_width());
+		return {}; // the backward pass repeats the lookup from x
+	}
+	void backward(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const void* dL_dy, MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode, const GridBackwardRoute&, BackwardHandoff*) override {
+		if (dL_dx) tensorf_backward_input(stream, m_shape, m_fp32, n, x, params, dL_dy, padded_output_width(), *dL_dx);
+		if (mode == GradientMode::Ignore) return;
+		CHECK_THROW(grads != nullptr);
+		tensorf_backward(stream, m_shape, m_fp32, n, x, params, dL_dy, padded_output_width(), m_fp32 ? nullptr : scratch_for(stream), grads, mode == GradientMode::Accumulate);
+	}
+	Json hyperparams() const override {
+		Json j = Json::object();
+		j["otype"] = "TensoRF";
+		j["decomposition"] = m_shape.cp ? "CP" : "VM";
+		j["n_components"] = m_shape.n_components;
+		j["n_levels"] = m_shape.n_levels;
+		j["base_resolution"] = m_base_resolution;
+		j["per_level_scale"] = m_per_level_scale;
+		return j;
+	}
+private:
+	uint64_t* scratch_for(hipStream_t stream) { // per stream: zero between passes (k_tensorf_finalize)
+		std::unique_ptr<DeviceBuf>& scratch = m_scratch[(const void*)stream];
+		if (!scratch) {
+			scratch = std::make_unique<DeviceBuf>(m_n_params * sizeof(uint64_t));
+			scratch->memset(0);
+		}
+		return scratch->as<uint64_t>();
+	}
+	TensoRFShape m_shape;
+	uint32_t m_base_resolution;
+	float m_per_level_scale;
+	size_t m_n_params;
+	std::map<const void*, std::unique_ptr<DeviceBuf>> m_scratch;
+};
+
 class IdentityEncoding : public Encoding {
 public:
 	IdentityEncoding(uint32_t n_dims_to_encode, float scale, float offset, bool fp32) : Encoding{fp32}, m_n_dims{n_dims_to_encode}, m_scale{scale}, m_offset{offset} {}
@@ -1781,6 +1868,8 @@ inline std::unique_ptr<Encoding> create_encoding(uint32_t n_dims_to_encode, cons
 		result.reset(new PermutoEncoding{n_dims_to_encode, enc, fp32});
 	} else if (name == "kplanes") {
 		result.reset(new KPlanesEncoding{n_dims_to_encode, enc, fp32});
+	} else if (name == "tensorf") {
+		result.reset(new TensoRFEncoding{n_dims_to_encode, enc, fp32});
 	} else if (name == "frequency") {
 		result.reset(new PeriodicEncoding{false, enc.value("n_frequencies", 12u), n_dims_to_encode, fp32});
 	} else if (name == "trianglewave") {
@@ -1809,7 +1898,7 @@ inline std::unique_ptr<Encoding> create_encoding(uint32_t n_dims_to_encode, cons
 		composite["nested"] = nested;
 		result.reset(new CompositeEncoding{n_dims_to_encode, composite, fp32});
 	} else {
-		throw std::runtime_error{"Encoding '" + enc.value("otype", "OneBlob") + "' not found (this build provides Grid/HashGrid/TiledGrid/DenseGrid, OneBlob, Identity, Empty, Frequency, TriangleWave, SphericalHarmonics, Composite, PPNG1, PPNG2, PermutoGrid, KPlanes)"};
+		throw std::runtime_error{"Encoding '" + enc.value("otype", "OneBlob") + "' not found (this build provides Grid/HashGrid/TiledGrid/DenseGrid, OneBlob, Identity, Empty, Frequency, TriangleWave, SphericalHarmonics, Composite, PPNG1, PPNG2, PermutoGrid, KPlanes, TensoRF)"};
 	}
 	if (alignment > 0) result->set_alignment(alignment);
 	return result;

@@ -501,6 +501,23 @@ void kplanes_tangent(hipStream_t stream, const KPlanesShape& p, bool fp32, uint3
 void kplanes_backward_backward_input(hipStream_t stream, const KPlanesShape& p, bool fp32, uint32_t n, MatView x, MatView v, const void* params, const void* dL_dy, uint32_t dy_stride,
                                      MatViewMut* dL_dx, uint64_t* scratch, void* grad, bool accumulate);
 
+// ---- TensoRF (k_tensorf.hip): one resolution per level, many components.  VM (cp == 0, 3-D): mode k = 0, 1, 2 is the plane over KPlanes'
+// axis pair k times the line over the remaining axis (2, 1, 0), y[l 3F + k F + f] = (T)(P_k[f] * V_k[f]); CP (cp != 0, 2- to 4-D): one line
+// per axis, y[l F + f] = (T)(V_0[f] * ... * V_{D-1}[f]).  params / grad T, per level [K planes][entries][F] then [K lines][line_entries][F]
+// (K = 3; CP: the D lines alone), entries = next_multiple(resolution^2, 8), line_entries = next_multiple(resolution, 8); offset: a level's
+// first entry, in entries of F components.  The level table travels by value.  out: [n][out_stride] T, columns behind the width are ones;
+// dL_dy, dL_dx, scratch (n_params 64-bit words, zero between passes; half only) as for KPlanes above.
+struct TensoRFShape {
+	uint32_t n_dims, n_levels, n_components, cp;
+	struct Levels { float scale[MAX_N_LEVELS]; uint32_t resolution[MAX_N_LEVELS], entries[MAX_N_LEVELS], offset[MAX_N_LEVELS]; } levels;
+	uint32_t n_modes() const { return cp ? 1u : 3u; }
+	uint32_t output_width() const { return n_levels * n_modes() * n_components; }
+};
+void tensorf_forward(hipStream_t stream, const TensoRFShape& p, bool fp32, uint32_t n, MatView x, const void* params, void* out, uint32_t out_stride);
+void tensorf_backward_input(hipStream_t stream, const TensoRFShape& p, bool fp32, uint32_t n, MatView x, const void* params, const void* dL_dy, uint32_t dy_stride, MatViewMut dL_dx);
+void tensorf_backward(hipStream_t stream, const TensoRFShape& p, bool fp32, uint32_t n, MatView x, const void* params, const void* dL_dy, uint32_t dy_stride, uint64_t* scratch, void* grad,
+                      bool accumulate);
+
 // ---- binned form for levels cut into more than 64 chunks (k_grid_bin.hip; GridLevel::scatter_binned): no filter, no gathers.
 // Same exact result as grid_backward_lds; writes every gradient element of the binned levels.  workspace: grid_bin_workspace_bytes().
 bool grid_bin_supported(const GridMeta& meta); // F in {2, 4}
