@@ -1279,8 +1279,10 @@ private:
 
 // "TensoRF" (k_tensorf.hip): one resolution per level, many components.  "VM" (3-D): three modes, each a feature plane over an axis pair
 // (KPlanes' pair order) times a feature line over the remaining axis, concatenated: 3 L F columns.  "CP" (2- to 4-D): the product of one
-// feature line per axis: L F columns.  Not in the reference; levels, scales and resolutions are the dense grid's.  First order only: no
-// second-order pass, no tangent, no max_level; upsampling the factors during training is a host-side re-sample and not provided.
+// feature line per axis: L F columns.  Not in the reference; levels, scales and resolutions are the dense grid's.  The second-order pass
+// and the tangent are opt-in ("second_order": true; a plane is bilinear and a line linear, so the mixed derivative of a plane and the
+// products of slopes enter: a tangent, dQ/dx and a parameter gradient); no max_level; upsampling the factors during training is a host-side
+// re-sample and not provided.
 // Rows are stored in 16-byte chunks, so the output is aligned to 8 columns in half and 4 in float -- the smallest that keeps every row
 // 16-byte storable (with F >= 8 the width is a multiple already; a caller that sets another width gets element stores).
 // Initialisation: every factor uniform in (-0.1, 0.1), TensoRF's 0.1-scaled draw: the grid's 1e-4 would multiply to zero in half.
@@ -1303,6 +1305,8 @@ public:
 		if (m_shape.n_levels < 1 || m_shape.n_levels > MAX_N_LEVELS) throw std::runtime_error{"TensoRF: n_levels must be 1 to " + std::to_string(MAX_N_LEVELS) + ", not " + std::to_string(m_shape.n_levels)};
 		if (m_base_resolution < 1) throw std::runtime_error{"TensoRF: base_resolution must be at least 1"};
 		if (!(m_per_level_scale > 0.0f) || !std::isfinite(m_per_level_scale)) throw std::runtime_error{"TensoRF: per_level_scale must be positive and finite"};
+		if (enc.contains("second_order") && !enc["second_order"].is_bool()) throw std::runtime_error{"TensoRF: second_order must be true or false"};
+		m_second_order = enc.value("second_order", false);
 		const float log2_scale = std::log2(m_per_level_scale);
 		uint64_t offset = 0;
 		for (uint32_t l = 0; l < m_shape.n_levels; ++l) { // scale and resolution: GridEncoding's, as KPlanesEncoding
@@ -1338,6 +1342,27 @@ public:
 		CHECK_THROW(grads != nullptr);
 		tensorf_backward(stream, m_shape, m_fp32, n, x, params, dL_dy, padded_output_width(), m_fp32 ? nullptr : scratch_for(stream), grads, mode == GradientMode::Accumulate);
 	}
+	// one kernel per result asked for: the tangent (k_tensorf_tangent), dL_dx (k_tensorf_bwdbwd_input), the parameter gradient (k_tensorf_bwdbwd).
+	// tangent() is the inherited call, so the tangent alone is the full call's dL_ddLdy bit for bit.
+	bool has_second_order() const override { return m_second_order; }
+	void backward_backward_input(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, MatView dL_ddLdx, const void* dL_dy, void* dL_ddLdy,
+	                             MatViewMut* dL_dx, const void* params, void* grads, GradientMode mode) override {
+		if (!m_second_order) return Encoding::backward_backward_input(stream, ctx, n, x, dL_ddLdx, dL_dy, dL_ddLdy, dL_dx, params, grads, mode);
+		if (padded_output_width() == 0) return;
+		if (dL_ddLdy) tensorf_tangent(stream, m_shape, m_fp32, n, x, dL_ddLdx, 0, 1, params, dL_ddLdy, padded_output_width(), 0);
+		const bool want_grads = mode != GradientMode::Ignore;
+		if (!dL_dx && !want_grads) return;
+		CHECK_THROW(dL_dy != nullptr && (grads != nullptr || !want_grads));
+		tensorf_backward_backward_input(stream, m_shape, m_fp32, n, x, dL_ddLdx, params, dL_dy, padded_output_width(), dL_dx, want_grads && !m_fp32 ? scratch_for(stream) : nullptr,
+		                                want_grads ? grads : nullptr, mode == GradientMode::Accumulate);
+	}
+	// a group of directions in ONE launch: cells, gathers and every term without v once per lane, then a loop over the directions
+	void tangents(hipStream_t stream, const EncodingContext& ctx, uint32_t n, MatView x, const float* directions, uint32_t first, uint32_t n_group, uint32_t n_tangents,
+	              void* t, size_t t_next, const void* params) override {
+		if (!m_second_order) return Encoding::tangents(stream, ctx, n, x, directions, first, n_group, n_tangents, t, t_next, params);
+		const uint32_t D = m_shape.n_dims;
+		if (t) tensorf_tangent(stream, m_shape, m_fp32, n, x, MatView{directions + (size_t)first * D, n_tangents * D, 1u}, D, n_group, params, t, padded_output_width(), t_next);
+	}
 	Json hyperparams() const override {
 		Json j = Json::object();
 		j["otype"] = "TensoRF";
@@ -1346,6 +1371,7 @@ public:
 		j["n_levels"] = m_shape.n_levels;
 		j["base_resolution"] = m_base_resolution;
 		j["per_level_scale"] = m_per_level_scale;
+		if (m_second_order) j["second_order"] = true; // (absent when off: the key set of a module built without it stays as it was)
 		return j;
 	}
 private:
@@ -1360,6 +1386,7 @@ private:
 	TensoRFShape m_shape;
 	uint32_t m_base_resolution;
 	float m_per_level_scale;
+	bool m_second_order;
 	size_t m_n_params;
 	std::map<const void*, std::unique_ptr<DeviceBuf>> m_scratch;
 };

@@ -517,6 +517,13 @@ void tensorf_forward(hipStream_t stream, const TensoRFShape& p, bool fp32, uint3
 void tensorf_backward_input(hipStream_t stream, const TensoRFShape& p, bool fp32, uint32_t n, MatView x, const void* params, const void* dL_dy, uint32_t dy_stride, MatViewMut dL_dx);
 void tensorf_backward(hipStream_t stream, const TensoRFShape& p, bool fp32, uint32_t n, MatView x, const void* params, const void* dL_dy, uint32_t dy_stride, uint64_t* scratch, void* grad,
                       bool accumulate);
+// second order, with v [n][n_dims] fp32 and Q = <v, J^T dL_dy>.  tensorf_tangent: n_tangents directions in one launch, direction k the view v
+// moved on by k * v_next floats, t_k [n][t_stride] T = J v_k (zeros behind the width) at t + k * t_next BYTES; dL_dy is not read.
+// tensorf_backward_backward_input: dL_dx (nullable, written) = dQ/dx; grad (nullable; scratch as for tensorf_backward) = dQ/dparams.
+void tensorf_tangent(hipStream_t stream, const TensoRFShape& p, bool fp32, uint32_t n, MatView x, MatView v, uint32_t v_next, uint32_t n_tangents, const void* params, void* t,
+                     uint32_t t_stride, size_t t_next);
+void tensorf_backward_backward_input(hipStream_t stream, const TensoRFShape& p, bool fp32, uint32_t n, MatView x, MatView v, const void* params, const void* dL_dy, uint32_t dy_stride,
+                                     MatViewMut* dL_dx, uint64_t* scratch, void* grad, bool accumulate);
 
 // ---- binned form for levels cut into more than 64 chunks (k_grid_bin.hip; GridLevel::scatter_binned): no filter, no gathers.
 // Same exact result as grid_backward_lds; writes every gradient element of the binned levels.  workspace: grid_bin_workspace_bytes().
