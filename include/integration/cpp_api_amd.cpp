@@ -109,6 +109,10 @@ void input_jvp_bwd(Module& module, cudaStream_t stream, const Context& ctx, uint
 	                                  dL_dparams, dL_dinput, dL_dtangents, dL_dparams ? TCNN_GRADIENT_OVERWRITE : TCNN_GRADIENT_IGNORE));
 }
 
+// "otype": "BatchedMLP": which rows go to which network (tcnn_module_set_network_offsets), and how many networks a module holds (0: no BatchedMLP)
+void set_network_offsets(Module& module, const uint32_t* device_offsets) { ok(tcnn_module_set_network_offsets(module_of(module, "set_network_offsets"), device_offsets)); }
+uint32_t n_networks(Module& module) { return tcnn_module_n_networks(module_of(module, "n_networks")); }
+
 uint32_t batch_size_granularity() { return tcnn_batch_size_granularity(); }
 
 int cuda_device() {

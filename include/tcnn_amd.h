@@ -106,6 +106,18 @@ int  tcnn_module_forward(tcnn_module_t m, tcnn_stream_t stream, uint32_t n_eleme
                          int prepare_input_gradients, tcnn_context_t* ctx_out);
 int  tcnn_module_backward(tcnn_module_t m, tcnn_stream_t stream, tcnn_context_t ctx, uint32_t n_elements, float* dL_dinput,
                           const void* dL_doutput, void* dL_dparams, const float* input, const void* output, const void* params);
+/* the same with an explicit TCNN_GRADIENT_* mode for dL_dparams (ACCUMULATE adds onto what the buffer holds; IGNORE: dL_dparams unused) */
+int  tcnn_module_backward_mode(tcnn_module_t m, tcnn_stream_t stream, tcnn_context_t ctx, uint32_t n_elements, float* dL_dinput,
+                               const void* dL_doutput, void* dL_dparams, const float* input, const void* output, const void* params, int gradient_mode);
+/* ---- "otype": "BatchedMLP" (tcnn_create_network*): n_networks networks of one shape, network k on rows [offsets[k], offsets[k + 1]) of
+ * every call.  params: [n_networks][one network's layout], one network's layout being CutlassMLP's.  device_offsets: n_networks + 1
+ * ascending uint32 row indices in DEVICE memory (the caller's; read by the calls that follow, on their stream, never by the host), or NULL
+ * for the equal split, which needs n_elements % n_networks == 0.  Segments may be empty and of any length.  Rows before offsets[0] and
+ * from offsets[n_networks] on belong to no network: their output and dL_dinput are +0 and they reach no gradient.  An empty network's
+ * gradients are +0 under OVERWRITE and untouched under ACCUMULATE.  Other modules report an error.
+ * tcnn_module_n_networks: 0 for every module that is not a BatchedMLP. */
+int      tcnn_module_set_network_offsets(tcnn_module_t m, const uint32_t* device_offsets);
+uint32_t tcnn_module_n_networks(tcnn_module_t m);
 /* second-order input gradients (cpp_api.h:94, cpp_api.cu:111-127; grid.h:902-1026): dL_ddLdinput [n][n_input_dims] float is the
  * gradient arriving at dL_dinput; optional results dL_dparams (Overwrite), dL_ddLdoutput [n][n_output_dims], dL_dinput [n][n_input_dims]
  * (overwritten; the reference adds into a zeroed buffer).  The context must come from tcnn_module_forward(prepare_input_gradients = 1).

@@ -110,6 +110,11 @@ public:
 	}
 	std::string last_input_jvp_backward_route() const { return tcnn_module_last_input_jvp_backward_route(m_handle); } // "none" | "two-pass"
 
+	// "otype": "BatchedMLP": n_networks() + 1 ascending row indices in device memory say which rows go to which network (nullptr: the equal
+	// split); read by the calls that follow, on their stream.  n_networks() is 0 for every other module.  See tcnn_module_set_network_offsets.
+	void set_network_offsets(const uint32_t* device_offsets) { detail::ok(tcnn_module_set_network_offsets(m_handle, device_offsets)); }
+	uint32_t n_networks() const { return tcnn_module_n_networks(m_handle); }
+
 	uint32_t n_input_dims() const { return tcnn_module_n_input_dims(m_handle); }
 	uint32_t n_output_dims() const { return tcnn_module_n_output_dims(m_handle); } // padded width, cpp_api.cu:130
 	size_t n_params() const { return tcnn_module_n_params(m_handle); }

@@ -185,8 +185,8 @@ int tcnn_create_network_with_input_encoding_precision(uint32_t n_input_dims, uin
 		CHECK_THROW(out != nullptr);
 		if (precision != TCNN_PRECISION_FP32 && precision != TCNN_PRECISION_FP16) throw std::runtime_error{"Unknown precision " + std::to_string(precision)};
 		auto m = std::make_unique<tcnn_module_s>();
-		m->model.reset(new NetworkWithInputEncoding{n_input_dims, n_output_dims, parse_or_empty(encoding_json), parse_or_empty(network_json),
-		                                            precision == TCNN_PRECISION_FP32 ? Precision::Fp32 : Precision::Fp16});
+		m->model = create_network_module(n_input_dims, n_output_dims, parse_or_empty(encoding_json), parse_or_empty(network_json),
+		                                 precision == TCNN_PRECISION_FP32 ? Precision::Fp32 : Precision::Fp16);
 		*out = m.release();
 	});
 }
@@ -234,15 +234,35 @@ int tcnn_module_forward(tcnn_module_t m, tcnn_stream_t stream, uint32_t n, const
 
 int tcnn_module_backward(tcnn_module_t m, tcnn_stream_t stream, tcnn_context_t ctx, uint32_t n, float* dL_dinput, const void* dL_doutput, void* dL_dparams,
                          const float* input, const void* output, const void* params) {
+	return tcnn_module_backward_mode(m, stream, ctx, n, dL_dinput, dL_doutput, dL_dparams, input, output, params, dL_dparams ? TCNN_GRADIENT_OVERWRITE : TCNN_GRADIENT_IGNORE); // cpp_api.cu:108
+}
+
+int tcnn_module_backward_mode(tcnn_module_t m, tcnn_stream_t stream, tcnn_context_t ctx, uint32_t n, float* dL_dinput, const void* dL_doutput, void* dL_dparams,
+                              const float* input, const void* output, const void* params, int gradient_mode) {
 	return guarded([&] {
+		CHECK_THROW(gradient_mode == TCNN_GRADIENT_IGNORE || ((gradient_mode == TCNN_GRADIENT_OVERWRITE || gradient_mode == TCNN_GRADIENT_ACCUMULATE) && dL_dparams != nullptr));
 		CHECK_THROW(m && m->model);
 		if (!ctx || !ctx->ctx || dynamic_cast<const Model::InputJvpContext*>(ctx->ctx.get())) { // (an input_jvp_forward context holds no activations)
 			throw std::runtime_error{"Module::bwd: called with invalid context. fwd likely (mistakenly) ran in inference mode."};
 		}
 		MatViewMut dx{dL_dinput, m->model->input_width(), 1u};
 		m->model->backward((hipStream_t)stream, *ctx->ctx, n, MatView{input, m->model->input_width(), 1u}, output, dL_doutput, dL_dinput ? &dx : nullptr, params,
-		                   dL_dparams, dL_dparams ? GradientMode::Overwrite : GradientMode::Ignore); // cpp_api.cu:108
+		                   gradient_mode == TCNN_GRADIENT_IGNORE ? nullptr : dL_dparams, (GradientMode)gradient_mode);
 	});
+}
+
+int tcnn_module_set_network_offsets(tcnn_module_t m, const uint32_t* device_offsets) {
+	return guarded([&] {
+		CHECK_THROW(m && m->model);
+		BatchedMlpModel* batched = dynamic_cast<BatchedMlpModel*>(m->model.get());
+		if (!batched) throw std::runtime_error{"network offsets: " + m->model->name() + " is no BatchedMLP"};
+		batched->set_network_offsets(device_offsets);
+	});
+}
+
+uint32_t tcnn_module_n_networks(tcnn_module_t m) {
+	const BatchedMlpModel* batched = m ? dynamic_cast<const BatchedMlpModel*>(m->model.get()) : nullptr;
+	return batched ? batched->n_networks() : 0u;
 }
 
 int tcnn_module_backward_backward_input(tcnn_module_t m, tcnn_stream_t stream, tcnn_context_t ctx, uint32_t n, const float* dL_ddLdinput, const float* input, const void* dL_doutput,

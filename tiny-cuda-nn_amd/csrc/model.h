@@ -14,6 +14,7 @@
 #include "json_lite.h"
 #include "tcnn_common.h"
 #include "mlp_side_jobs.h"
+#include "mlp_batched.h"
 
 #include <algorithm>
 #include <cctype>
@@ -3493,6 +3494,127 @@ private:
 	std::unique_ptr<Encoding> m_encoding;
 };
 
+// "otype": "BatchedMLP" -- n_networks small networks of one shape in one launch, network k on rows [offsets[k], offsets[k + 1]) of the
+// batch (k_mlp_batched.hip, DESIGN.md "BatchedMLP").  Half precision; the module's float input is cast and padded with ones inside the
+// kernels, as the Identity encoding in front of a Network does.  Parameters: [n_networks][one Network's layout].
+inline bool is_batched_mlp(const Json& network) { return network.is_object() && equals_case_insensitive(network.value("otype", "MLP"), "BatchedMLP"); }
+
+class BatchedMlpModel : public Model {
+public:
+	// everything is checked here, before anything touches a device
+	BatchedMlpModel(uint32_t n_input_dims, uint32_t n_output_dims, const Json& network, Precision precision)
+	: m_input_dims{n_input_dims}, m_n_networks{network.value("n_networks", 0u)}, m_net{checked(n_input_dims, n_output_dims, network, precision)} {
+		m_desc = bmlp_desc(m_net.desc(), m_n_networks, n_input_dims);
+		const size_t lds = bmlp_backward_lds_bytes(m_desc);
+		if (lds > BMLP_LDS_LIMIT) {
+			throw std::runtime_error{"BatchedMLP: one network of this shape needs " + std::to_string(lds) + " bytes of LDS in the backward kernel (weights in half, their gradients in fp32, " +
+			                         std::to_string(BMLP_STAGE_BYTES) + " bytes of staging); the limit is " + std::to_string(BMLP_LDS_LIMIT) + " bytes."};
+		}
+		if ((uint64_t)m_n_networks * m_net.n_params() >= (1ull << 32)) throw std::runtime_error{"BatchedMLP: n_networks times one network's parameters must be below 2^32"};
+	}
+
+	uint32_t n_networks() const { return m_n_networks; }
+	// K + 1 ascending row indices in device memory (the caller's, read by the calls that follow on their stream), or nullptr: the equal split
+	void set_network_offsets(const uint32_t* offsets) { m_offsets = offsets; }
+
+	uint32_t input_width() const override { return m_input_dims; }
+	uint32_t output_width() const override { return m_net.output_width(); }
+	uint32_t padded_output_width() const override { return m_net.padded_output_width(); }
+	size_t n_params() const override { return (size_t)m_n_networks * m_net.n_params(); }
+	Precision precision() const override { return Precision::Fp16; }
+	std::vector<std::pair<uint32_t, uint32_t>> layer_sizes() const override {
+		const auto one = m_net.layer_sizes();
+		std::vector<std::pair<uint32_t, uint32_t>> r;
+		for (uint32_t k = 0; k < m_n_networks; ++k) r.insert(r.end(), one.begin(), one.end());
+		return r;
+	}
+	void initialize_params(Pcg32& rng, float* params_full_precision, float scale) override { // network 0, then 1, ..: one stream
+		for (uint32_t k = 0; k < m_n_networks; ++k) m_net.initialize_params(rng, params_full_precision + (size_t)k * m_net.n_params(), scale);
+	}
+
+	struct Ctx : public ModelContext {
+		ArenaBuf hidden; // [n_hidden][n][width] half
+	};
+	void inference(hipStream_t stream, uint32_t n, MatView input, void* output, const void* params) override {
+		check_rows(n);
+		bmlp_forward(stream, m_desc, n, m_offsets, input, params, output, nullptr);
+	}
+	std::unique_ptr<ModelContext> forward(hipStream_t stream, uint32_t n, MatView input, void* output, const void* params, bool prepare_input_gradients) override {
+		check_rows(n);
+		auto ctx = std::make_unique<Ctx>();
+		if (n == 0) return ctx;
+		ctx->hidden = ArenaBuf{stream, (size_t)m_net.n_hidden() * n * m_net.width() * sizeof(_Float16)};
+		bmlp_forward(stream, m_desc, n, m_offsets, input, params, output, ctx->hidden.data());
+		return ctx;
+	}
+	void backward(hipStream_t stream, const ModelContext& mctx, uint32_t n, MatView input, const void* output, const void* dL_doutput, MatViewMut* dL_dinput, const void* params,
+	              void* gradients, GradientMode mode) override {
+		check_rows(n);
+		const Ctx& ctx = dynamic_cast<const Ctx&>(mctx);
+		CHECK_THROW(mode == GradientMode::Ignore || gradients != nullptr);
+		if (n == 0) return;
+		ArenaBuf partials; // returned to the stream's free list when this call ends: the stream orders its reuse
+		const size_t floats = mode == GradientMode::Ignore ? 0 : bmlp_partial_floats(m_desc, n, m_offsets != nullptr);
+		if (floats) partials = ArenaBuf{stream, floats * sizeof(float)};
+		bmlp_backward(stream, m_desc, n, m_offsets, input, ctx.hidden.data(), output, dL_doutput, params, dL_dinput, gradients, mode, partials.as<float>());
+	}
+	Json hyperparams() const override {
+		Json j = Json::object();
+		j["otype"] = "BatchedMLP";
+		j["n_networks"] = m_n_networks;
+		j["n_neurons"] = m_net.width();
+		j["n_hidden_layers"] = m_net.n_hidden();
+		j["activation"] = to_string((Activation)m_desc.activation);
+		j["output_activation"] = to_string((Activation)m_desc.output_activation);
+		return j;
+	}
+private:
+	// the configuration of ONE network as a CutlassMLP description (layout, layer sizes, initialisation), after BatchedMLP's own rules
+	static Json checked(uint32_t n_input_dims, uint32_t n_output_dims, const Json& network, Precision precision) {
+		if (precision == Precision::Fp32) throw std::runtime_error{"BatchedMLP can only be used if the network precision is set to __half."};
+		if (network.value("n_networks", 0u) < 1) throw std::runtime_error{"BatchedMLP: n_networks must be at least 1."};
+		const uint32_t width = network.value("n_neurons", 64u), n_hidden = network.value("n_hidden_layers", 2u);
+		if (width != 16 && width != 32 && width != 64) throw std::runtime_error{"BatchedMLP only supports 16, 32, and 64 neurons, but got " + std::to_string(width) + "."};
+		if (n_hidden < 1) throw std::runtime_error{"BatchedMLP requires at least 1 hidden layer (3 layers in total)."};
+		if (string_to_activation(network.value("activation", "ReLU")) == Activation::Sine || string_to_activation(network.value("output_activation", "None")) == Activation::Sine) {
+			throw std::runtime_error{"BatchedMLP: Sine activation is not supported in the fused kernels"};
+		}
+		const uint32_t in_width = next_multiple(n_input_dims, Network::REQUIRED_ALIGNMENT), out_width = next_multiple(n_output_dims, Network::REQUIRED_ALIGNMENT);
+		if (n_input_dims < 1 || in_width > BMLP_MAX_WIDTH) throw std::runtime_error{"BatchedMLP: the input width must be between 1 and " + std::to_string(BMLP_MAX_WIDTH) + ", but got " + std::to_string(n_input_dims) + "."};
+		if (n_output_dims < 1 || out_width > BMLP_MAX_WIDTH) throw std::runtime_error{"BatchedMLP: the output width must be between 1 and " + std::to_string(BMLP_MAX_WIDTH) + ", but got " + std::to_string(n_output_dims) + "."};
+		Json one = Json::object();
+		one["otype"] = "CutlassMLP";
+		one["n_input_dims"] = in_width;
+		one["n_output_dims"] = n_output_dims;
+		one["n_neurons"] = width;
+		one["n_hidden_layers"] = n_hidden;
+		one["activation"] = network.value("activation", "ReLU");
+		one["output_activation"] = network.value("output_activation", "None");
+		return one;
+	}
+	void check_rows(uint32_t n) const {
+		check_batch(n);
+		if (!m_offsets && n % m_n_networks != 0) {
+			throw std::runtime_error{"BatchedMLP: without network offsets the rows are split equally, and " + std::to_string(n) + " rows are no multiple of n_networks = " + std::to_string(m_n_networks)};
+		}
+	}
+	uint32_t m_input_dims, m_n_networks;
+	Network m_net;
+	BmlpDesc m_desc;
+	const uint32_t* m_offsets = nullptr;
+};
+
+// tcnn_create_network*: NetworkWithInputEncoding, or BatchedMlpModel when the network's otype asks for it
+inline std::unique_ptr<Model> create_network_module(uint32_t n_input_dims, uint32_t n_output_dims, const Json& encoding, const Json& network, Precision precision) {
+	if (!is_batched_mlp(network)) return std::unique_ptr<Model>{new NetworkWithInputEncoding{n_input_dims, n_output_dims, encoding, network, precision}};
+	const std::string enc = encoding.is_object() ? encoding.value("otype", "Identity") : std::string{"Identity"};
+	if (!equals_case_insensitive(enc, "Identity") || encoding.value("scale", 1.0f) != 1.0f || encoding.value("offset", 0.0f) != 0.0f) {
+		throw std::runtime_error{"BatchedMLP reads the module's input itself (an Identity encoding of scale 1 and offset 0) and takes no other input encoding, but got " + enc +
+		                         ". Compose tcnn.Encoding -> tcnn.Network(BatchedMLP) instead: its dL/dinput makes the pair differentiable end to end."};
+	}
+	return std::unique_ptr<Model>{new BatchedMlpModel{n_input_dims, n_output_dims, network, precision}};
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // Loss (src/loss.cu:85-93) and Adam (optimizers/adam.h:122-327, src/optimizer.cu:50-82)
 // ------------------------------------------------------------------------------------------------------------------
@@ -4491,6 +4613,10 @@ public:
 		const Json loss = config.value("loss", Json::object());
 		const Json optimizer = config.value("optimizer", Json::object());
 		const Json network = config.value("network", Json::object());
+		if (is_batched_mlp(network)) {
+			throw std::runtime_error{"BatchedMLP cannot be trained through a Trainer / create_from_config: a trainer has no way to say which rows go to which network. "
+			                         "Create the module with tcnn_create_network (tcnn.Network) and set its network offsets."};
+		}
 		m_loss = create_loss(loss);
 		m_optimizer = create_optimizer(optimizer);
 		if (m_fp32) { // what the configuration alone decides is reported before anything is allocated on the device (network.cu:102-103)

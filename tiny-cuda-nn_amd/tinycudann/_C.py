@@ -73,6 +73,9 @@ _SIGNATURES = {
     "tcnn_module_inference": (_int, [_vp, _vp, _u32, _vp, _vp, _vp]),
     "tcnn_module_forward": (_int, [_vp, _vp, _u32, _vp, _vp, _vp, _int, _pp]),
     "tcnn_module_backward": (_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tcnn_module_backward_mode": (_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _int]),
+    "tcnn_module_set_network_offsets": (_int, [_vp, _vp]),
+    "tcnn_module_n_networks": (_u32, [_vp]),
     "tcnn_module_backward_backward_input": (_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tcnn_module_backward_backward_input_mode": (_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int]),
     "tcnn_module_input_gradient": (_int, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _f32]),

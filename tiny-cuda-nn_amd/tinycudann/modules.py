@@ -48,6 +48,7 @@ class NativeModule:
     def __init__(self, handle):
         self._h = handle
         self._max_level_gpu = None  # the per-sample array handed to the native module (kept alive here)
+        self._network_offsets = None  # BatchedMLP: the offsets tensor handed to the native module (kept alive here)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -71,6 +72,19 @@ class NativeModule:
 
     def max_level_gpu(self):
         return self._max_level_gpu
+
+    # --- "otype": "BatchedMLP" (tcnn_amd.h: tcnn_module_set_network_offsets, tcnn_module_n_networks)
+    def n_networks(self):
+        """how many networks the module holds; 0: no BatchedMLP"""
+        return int(_C.lib.tcnn_module_n_networks(self._h))
+
+    def set_network_offsets(self, offsets):
+        """offsets: n_networks + 1 ascending row indices as an int32 / uint32 device tensor (kept alive here), or None: the equal split"""
+        _C.check(_C.lib.tcnn_module_set_network_offsets(self._h, _ptr(offsets)))
+        self._network_offsets = offsets
+
+    def network_offsets(self):
+        return self._network_offsets
 
     # --- bindings.cpp:242-260
     def n_input_dims(self):
@@ -292,20 +306,35 @@ def _create(fn, *args):
 class _Call:
     """What one forward call leaves behind for its backward passes."""
 
-    __slots__ = ("native", "native_ctx", "loss_scale", "wants_input", "wants_params", "max_level")
+    __slots__ = ("native", "native_ctx", "loss_scale", "wants_input", "wants_params", "max_level", "offsets")
 
-    def __init__(self, native, loss_scale, wants_input, wants_params, max_level=None):
+    def __init__(self, native, loss_scale, wants_input, wants_params, max_level=None, offsets=None):
         self.native = native
         self.native_ctx = None
         self.loss_scale = loss_scale
         self.wants_input = wants_input
         self.wants_params = wants_params
         self.max_level = max_level  # None, or the max_level setting of the forward pass: (value, per-sample array padded to the batch or None)
+        self.offsets = offsets  # None, or the network offsets of the forward pass (BatchedMLP: which rows go to which network)
 
     @contextlib.contextmanager
     def setting(self):
-        """The call's max_level in force on the native module (its backward passes belong to the forward pass's setting); the one
-        in force before comes back afterwards."""
+        """The call's max_level and network offsets in force on the native module (its backward passes belong to the forward pass's
+        setting); the ones in force before come back afterwards."""
+        if self.offsets is not None:
+            previous_offsets = self.native.network_offsets()
+            self.native.set_network_offsets(self.offsets)
+            try:
+                with self._max_level_setting():
+                    yield
+            finally:
+                self.native.set_network_offsets(previous_offsets)
+            return
+        with self._max_level_setting():
+            yield
+
+    @contextlib.contextmanager
+    def _max_level_setting(self):
         if self.max_level is None:
             yield
             return
@@ -347,8 +376,8 @@ class _Call:
 class _Evaluate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, input, params, native, loss_scale, *max_level):
-        # (max_level: optional, the setting recorded by Module._max_level_of_call)
-        call = _Call(native, loss_scale, ctx.needs_input_grad[0], ctx.needs_input_grad[1], max_level[0] if max_level else None)
+        # (max_level: optional, the setting recorded by Module._max_level_of_call, then the one recorded by Module._offsets_of_call)
+        call = _Call(native, loss_scale, ctx.needs_input_grad[0], ctx.needs_input_grad[1], max_level[0] if max_level else None, max_level[1] if len(max_level) > 1 else None)
         ctx.n_inputs = 4 + len(max_level)
         inp, par = call.flagged(input, params)
         with call.setting():
@@ -516,7 +545,7 @@ class Module(torch.nn.Module):
             working = self.params.contiguous()
         else:
             working = _WorkingCopy.apply(self.params, self)
-        output = _Evaluate.apply(rows, working, self.native_tcnn_module, self.loss_scale, self._max_level_of_call(n, rows))
+        output = _Evaluate.apply(rows, working, self.native_tcnn_module, self.loss_scale, self._max_level_of_call(n, rows), self._offsets_of_call(n, rows))
         return output[:n, : self.n_output_dims]
 
     def input_gradient(self, x, dim=0, backprop_scale=None, return_output=False):
@@ -534,7 +563,7 @@ class Module(torch.nn.Module):
             working = self.params.detach().to(self.dtype).contiguous()
             scale = self.loss_scale if backprop_scale is None else backprop_scale
             native = self.native_tcnn_module
-            call = _Call(native, scale, False, False, self._max_level_of_call(n, rows))
+            call = _Call(native, scale, False, False, self._max_level_of_call(n, rows), self._offsets_of_call(n, rows))
             with call.setting():
                 gradient, output = native.input_gradient(rows, working, dim, scale, return_output)
             gradient = gradient[:n]
@@ -555,7 +584,7 @@ class Module(torch.nn.Module):
             working = self.params.detach().to(self.dtype).contiguous()
             scale = self.loss_scale if backprop_scale is None else backprop_scale
             native = self.native_tcnn_module
-            call = _Call(native, scale, False, False, self._max_level_of_call(n, rows))
+            call = _Call(native, scale, False, False, self._max_level_of_call(n, rows), self._offsets_of_call(n, rows))
             with call.setting():
                 jacobian, output = native.input_jacobian(rows, working, range(self.n_output_dims) if dims is None else dims, scale, return_output)
             jacobian = jacobian[:n]
@@ -662,9 +691,44 @@ class Module(torch.nn.Module):
             per_sample = per_sample[:n] if rows.shape[0] == n else _pad_rows(per_sample[:n], rows.shape[0])  # the kernels read one value per padded row
         return (value, per_sample)
 
+    # --- "otype": "BatchedMLP": which rows go to which network.  Every forward call records the offsets in force; its backward pass runs
+    # under them, as with max_level.
+    def set_network_offsets(self, offsets):
+        """n_networks + 1 ascending row indices: network k owns rows [offsets[k], offsets[k + 1]) of every later call, rows from
+        offsets[-1] on belong to no network (their output and input gradient are 0).  A contiguous one-dimensional int32 / uint32
+        tensor on the module's device (the module keeps a reference; it is never read back to the host), or None: the rows of
+        each call are split equally, which needs a row count that is a multiple of n_networks."""
+        if self.native_tcnn_module.n_networks() == 0:
+            raise RuntimeError("tcnn: set_network_offsets needs a network of otype BatchedMLP")
+        if offsets is not None:
+            if not isinstance(offsets, torch.Tensor) or offsets.dtype not in (torch.int32, torch.uint32) or not offsets.is_contiguous() or offsets.dim() != 1:
+                raise RuntimeError("tcnn: the network offsets must be a contiguous one-dimensional int32 or uint32 tensor")
+            if offsets.numel() != self.native_tcnn_module.n_networks() + 1:
+                raise RuntimeError(f"tcnn: {self.native_tcnn_module.n_networks()} networks need {self.native_tcnn_module.n_networks() + 1} offsets, got {offsets.numel()}")
+            if offsets.device != self.params.device:
+                raise RuntimeError(f"tcnn: the network offsets live on {offsets.device}, the module on {self.params.device}")
+        self._network_offsets = offsets
+
+    def _offsets_of_call(self, n, rows):
+        """None for a module that is no BatchedMLP, else the offsets of this call: the ones set, or the equal split of the n unpadded rows"""
+        k = self.native_tcnn_module.n_networks()
+        if k == 0:
+            return None
+        offsets = getattr(self, "_network_offsets", None)
+        if offsets is not None:
+            return offsets
+        if n % k != 0:
+            raise RuntimeError(f"tcnn: without network offsets the rows are split equally, and {n} rows are no multiple of n_networks = {k}")
+        cache = self.__dict__.setdefault("_equal_split", {})
+        key = (n, rows.device)
+        if key not in cache:
+            cache.clear()
+            cache[key] = torch.arange(k + 1, dtype=torch.int32, device=rows.device) * (n // k)
+        return cache[key]
+
     # native handles do not pickle: drop them, and rebuild them from the configuration on the other side
     def __getstate__(self):
-        return {k: v for k, v in self.__dict__.items() if k not in ("native_tcnn_module", "_working_copy", "_working_key", "_max_level_value", "_max_level_tensor")}
+        return {k: v for k, v in self.__dict__.items() if k not in ("native_tcnn_module", "_working_copy", "_working_key", "_max_level_value", "_max_level_tensor", "_network_offsets", "_equal_split")}
 
     def __setstate__(self, state):
         self.__dict__.update(state)
