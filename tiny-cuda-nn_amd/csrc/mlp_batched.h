@@ -60,4 +60,25 @@ void bmlp_forward(hipStream_t stream, const BmlpDesc& d, uint32_t n, const uint3
 void bmlp_backward(hipStream_t stream, const BmlpDesc& d, uint32_t n, const uint32_t* offsets, MatView x, const void* hidden, const void* out, const void* dL_dout,
                    const void* params, const MatViewMut* dL_dinput, void* gradients, GradientMode mode, float* partials);
 
+// ---- second order (DESIGN.md "BatchedMLP: second-order pass and tangent"): the gradients of S = <v, dL/dinput>, per network on its rows
+constexpr uint32_t BMLP_TANGENT_GROUP = 3; // tangent chains that run beside the forward chain in one launch of k_bmlp_tangent
+
+__host__ __device__ inline bool bmlp_curved(uint32_t act) { // a'' != 0 somewhere
+	return act != (uint32_t)Activation::None && act != (uint32_t)Activation::ReLU && act != (uint32_t)Activation::LeakyReLU;
+}
+inline bool bmlp_any_curvature(const BmlpDesc& d) { return bmlp_curved(d.activation) || bmlp_curved(d.output_activation); }
+// what the up pass leaves for the down pass, per kind: [n_layers - 1][n][width] like `hidden`, then [n][out_width] for the last layer
+inline size_t bmlp_second_order_halves(const BmlpDesc& d, uint32_t n) { return (size_t)n * ((d.n_layers - 1) * d.width + d.out_width); }
+
+// The up pass.  v: the first of n_tangents (1 .. BMLP_TANGENT_GROUP) directions [n][in_dims] floats, the next one v_next floats behind it.
+// jvp (optional): tangent t's u_K at jvp[row * jvp_ld + t * out_width ..]; out (optional): the forward output, inference()'s bits.
+// u, z, c (all or none, n_tangents == 1, bmlp_second_order_halves() halves each): u_1 .. u_{K-1} in the hidden slots; z_k of every layer
+// with an activation; c_k = a_k''(z_k) z'_k of every layer with curvature.
+void bmlp_tangent(hipStream_t stream, const BmlpDesc& d, uint32_t n, const uint32_t* offsets, MatView x, MatView v, uint32_t v_next, uint32_t n_tangents, const void* params,
+                  void* jvp, uint32_t jvp_ld, void* out, void* u, void* z, void* c);
+// The down pass, on what bmlp_tangent left.  dL_dinput (optional) is written only where the network has curvature (else it is zero: the
+// caller's to clear); gradients / mode / partials as bmlp_backward.
+void bmlp_backward_second(hipStream_t stream, const BmlpDesc& d, uint32_t n, const uint32_t* offsets, MatView x, MatView v, const void* hidden, const void* dL_dout, const void* params,
+                          const void* u, const void* z, const void* c, const MatViewMut* dL_dinput, void* gradients, GradientMode mode, float* partials);
+
 } // namespace tcnn_amd

@@ -3558,6 +3558,35 @@ public:
 		if (floats) partials = ArenaBuf{stream, floats * sizeof(float)};
 		bmlp_backward(stream, m_desc, n, m_offsets, input, ctx.hidden.data(), output, dL_doutput, params, dL_dinput, gradients, mode, partials.as<float>());
 	}
+	// The recipe of Network::second_order_*, per network on its rows, in two launches (k_bmlp_tangent up, k_bmlp_bwd2 down; DESIGN.md
+	// "BatchedMLP: second-order pass and tangent").  The up pass runs the forward chain again beside the tangent -- z_k is what a' and a''
+	// are taken from, and the context holds only h_k -- and leaves u_k, z_k and c_k for the down pass, which reads h_k from the context.
+	// Only what is asked for runs: without parameter gradients and without dL_dinput, the up pass alone.
+	void backward_backward_input(hipStream_t stream, const ModelContext& mctx, uint32_t n, MatView input, MatView dL_ddLdinput, const void* dL_doutput, void* dL_ddLdoutput,
+	                             MatViewMut* dL_dinput, const void* params, void* gradients, GradientMode mode) override {
+		check_rows(n);
+		const Ctx& ctx = dynamic_cast<const Ctx&>(mctx);
+		const bool want_grads = mode != GradientMode::Ignore, curved = bmlp_any_curvature(m_desc);
+		const bool down = want_grads || (curved && dL_dinput);
+		CHECK_THROW(!want_grads || gradients != nullptr);
+		CHECK_THROW(!down || dL_doutput != nullptr);
+		if (n == 0) return;
+		if (dL_dinput && !curved) zero_input_gradient(stream, n, m_input_dims, *dL_dinput); // no a'' anywhere: +0, and no curvature chain
+		if (!down && !dL_ddLdoutput) return;
+		ArenaBuf u, z, c, partials;
+		if (down) {
+			const size_t bytes = bmlp_second_order_halves(m_desc, n) * sizeof(_Float16);
+			u = ArenaBuf{stream, bytes};
+			z = ArenaBuf{stream, bytes};
+			c = ArenaBuf{stream, bytes};
+		}
+		bmlp_tangent(stream, m_desc, n, m_offsets, input, dL_ddLdinput, 0, 1, params, dL_ddLdoutput, m_desc.out_width, nullptr, u.data(), z.data(), c.data());
+		if (!down) return;
+		const size_t floats = want_grads ? bmlp_partial_floats(m_desc, n, m_offsets != nullptr) : 0;
+		if (floats) partials = ArenaBuf{stream, floats * sizeof(float)};
+		bmlp_backward_second(stream, m_desc, n, m_offsets, input, dL_ddLdinput, ctx.hidden.data(), dL_doutput, params, u.data(), z.data(), c.data(), dL_dinput, gradients, mode, partials.as<float>());
+	}
+	bool has_tangent() const override { return true; }
 	Json hyperparams() const override {
 		Json j = Json::object();
 		j["otype"] = "BatchedMLP";
@@ -3567,6 +3596,21 @@ public:
 		j["activation"] = to_string((Activation)m_desc.activation);
 		j["output_activation"] = to_string((Activation)m_desc.output_activation);
 		return j;
+	}
+protected:
+	// one direction: the up pass alone (the forward chain runs beside it, so the context is not read)
+	void tangent(hipStream_t stream, const ModelContext& ctx, uint32_t n, MatView input, MatView v, void* t, const void* params) override {
+		backward_backward_input(stream, ctx, n, input, v, nullptr, t, nullptr, params, nullptr, GradientMode::Ignore);
+	}
+	// the up pass for BMLP_TANGENT_GROUP directions per launch, straight into their columns of jvp; the first launch writes the output
+	std::string input_jvp_impl(hipStream_t stream, uint32_t n, uint32_t n_tangents, MatView input, const float* tangents, void* jvp, void* output, const void* params) override {
+		check_rows(n);
+		const uint32_t pw = m_desc.out_width;
+		for (uint32_t t0 = 0; t0 < n_tangents; t0 += BMLP_TANGENT_GROUP) {
+			bmlp_tangent(stream, m_desc, n, m_offsets, input, tangent_slice(tangents, t0, n_tangents), m_input_dims, std::min(BMLP_TANGENT_GROUP, n_tangents - t0), params,
+			             (_Float16*)jvp + (size_t)t0 * pw, n_tangents * pw, t0 == 0 ? output : nullptr, nullptr, nullptr, nullptr);
+		}
+		return "k_bmlp_tangent";
 	}
 private:
 	// the configuration of ONE network as a CutlassMLP description (layout, layer sizes, initialisation), after BatchedMLP's own rules

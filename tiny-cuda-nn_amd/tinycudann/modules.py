@@ -299,9 +299,9 @@ def _create(fn, *args):
 # INPUT gradients: eikonal / SDF losses); nothing is propagated through dL_dparams.  The construction is this package's own:
 # one record per call, two Functions that only shuttle tensors in and out of it.  The native second-order pass exists for the
 # grid, PPNG3, Identity, Frequency, TriangleWave, SphericalHarmonics and Empty encodings, for a Composite of those (Concatenation,
-# Sum or Product) and for CutlassMLP networks, alone or behind one of those encodings; FullyFusedMLP, OneBlob, PPNG1 / PPNG2 and a
-# Composite that holds one of them (OneBlobFrequency / NRC) raise the reference's "not implemented error" (for a network: ask for
-# "otype": "CutlassMLP").
+# Sum or Product), for CutlassMLP networks, alone or behind one of those encodings, and for BatchedMLP (its own two fused kernels, under
+# the network offsets of the forward call); FullyFusedMLP, OneBlob, PPNG1 / PPNG2 and a Composite that holds one of them
+# (OneBlobFrequency / NRC) raise the reference's "not implemented error" (for a network: ask for "otype": "CutlassMLP").
 # ----------------------------------------------------------------------------------------------------------------------
 class _Call:
     """What one forward call leaves behind for its backward passes."""
@@ -428,8 +428,8 @@ class _InputJvp(torch.autograd.Function):
     """input_jvp attached to autograd with respect to (input, params, tangents): first order only."""
 
     @staticmethod
-    def forward(ctx, input, params, tangents, native, loss_scale, want_output, max_level):
-        call = _Call(native, loss_scale, ctx.needs_input_grad[0], ctx.needs_input_grad[1], max_level)
+    def forward(ctx, input, params, tangents, native, loss_scale, want_output, max_level, offsets=None):
+        call = _Call(native, loss_scale, ctx.needs_input_grad[0], ctx.needs_input_grad[1], max_level, offsets)
         ctx.wants_tangents = ctx.needs_input_grad[2]
         with call.setting():
             call.native_ctx, jvp, output = native.input_jvp_fwd(input.detach(), params.detach(), tangents.detach(), want_output)
@@ -445,7 +445,7 @@ class _InputJvp(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, d_jvp, d_output):
         if d_jvp is None and d_output is None:
-            return (None,) * 7
+            return (None,) * 8
         input, params, tangents = ctx.saved_tensors
         call = ctx.call
         native = call.native
@@ -461,7 +461,7 @@ class _InputJvp(torch.autograd.Function):
                     g_input, g_params = native.bwd(plain_ctx, inp, par, output, (d_output * call.loss_scale).to(dtype).contiguous())
             inv = 1.0 / call.loss_scale
             return (None if g_input is None else g_input * inv, None if g_params is None else g_params * inv,
-                    torch.zeros_like(tangents) if ctx.wants_tangents else None, None, None, None, None)
+                    torch.zeros_like(tangents) if ctx.wants_tangents else None, None, None, None, None, None)
         # (cotangents at loss_scale in the output precision, the gradients divided by it again: as _Call.first_order)
         d_jvp = (d_jvp * call.loss_scale).to(dtype).contiguous()
         if d_output is not None:
@@ -470,7 +470,7 @@ class _InputJvp(torch.autograd.Function):
             g_params, g_input, g_tangents = native.input_jvp_bwd(call.native_ctx, input.detach(), params.detach(), tangents.detach(), d_jvp, d_output,
                                                                 call.wants_params, call.wants_input, ctx.wants_tangents)
         inv = 1.0 / call.loss_scale
-        return (None if g_input is None else g_input * inv, None if g_params is None else g_params * inv, None if g_tangents is None else g_tangents * inv, None, None, None, None)
+        return (None if g_input is None else g_input * inv, None if g_params is None else g_params * inv, None if g_tangents is None else g_tangents * inv, None, None, None, None, None)
 
 
 def _pad_rows(x, multiple):
@@ -618,7 +618,7 @@ class Module(torch.nn.Module):
             v = _pad_rows(v.reshape(n, -1), granularity).reshape(rows.shape[0], -1, self.n_input_dims).contiguous()
             working = self.params.detach().to(self.dtype).contiguous()
             native = self.native_tcnn_module
-            call = _Call(native, self.loss_scale, False, False, self._max_level_of_call(n, rows))
+            call = _Call(native, self.loss_scale, False, False, self._max_level_of_call(n, rows), self._offsets_of_call(n, rows))
             with call.setting():
                 jvp, output = native.input_jvp(rows, working, v, return_output)
             jvp = jvp[:n, :, : self.n_output_dims]
@@ -644,7 +644,7 @@ class Module(torch.nn.Module):
             working = self.params.contiguous()
         else:
             working = _WorkingCopy.apply(self.params, self)
-        jvp, output = _InputJvp.apply(rows, working, v, self.native_tcnn_module, self.loss_scale, return_output, self._max_level_of_call(n, rows))
+        jvp, output = _InputJvp.apply(rows, working, v, self.native_tcnn_module, self.loss_scale, return_output, self._max_level_of_call(n, rows), self._offsets_of_call(n, rows))
         jvp = jvp[:n, :, : self.n_output_dims]  # (padded rows and output columns receive zero cotangent through the slices)
         if flat:
             jvp = jvp[:, 0]
